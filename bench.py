@@ -17,6 +17,11 @@ robot, mono_kitti.cc:80-101) -- no data-path collective; RCCL only gathers the m
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` the ranks are the launcher's.
 
 Prints ONE JSON line on rank 0 (see the contract in the task statement).
+
+A plain run sets up, warms up, times `--steps` steps and prints the record (`value`, `ms_per_step`, ...).  `--full` adds
+every other measurement and check: CPU baseline, oracle parity of the last step, the natural-image, Tracking-shaped,
+host-buffer, live-stream and drop-in side blocks, the per-kernel profile, serialized replay and roofline.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import glob
@@ -66,7 +71,18 @@ def parse_args(argv=None):
                     "tracking_path, host_path); a block that would start beyond it is skipped and the record says so -- the headline never waits for them longer than this")
     ap.add_argument("--no-profile", action="store_true", help="do not record HIP events inside the timed region")
     ap.add_argument("--no-replay", action="store_true", help="skip the untimed serialized replay (roofline.isolated); used under rocprofv3 so that its per-kernel averages are those of the timed launches")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: CPU baseline, oracle parity of the last step, "
+                    "natural-image, Tracking-shaped, host-buffer, live-stream and drop-in side blocks, per-kernel profile, serialized replay and roofline, "
+                    "shader-clock probe; the --no-* options above then switch single parts off.  Without it a run sets up, warms up, times the steps "
+                    "and prints the record")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed (keypoints, descriptors and "
+                    "match tables of its frames, rank 0's stream) as DIR/<name>.npy in float32 / float64")
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run does what its headline figure needs and nothing else
+        args.no_cpu_baseline = args.no_host_path = args.no_parity_check = args.no_natural = args.no_tracking_path = True
+        args.no_live_streams = args.no_dropin_classes = args.no_profile = args.no_replay = True
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -812,6 +828,39 @@ def parity_check(ex, cfg, host_frames, frames_idx):
             "what": "keypoints, descriptors and match table of these frames of the last timed step, byte for byte against the CPU oracle on the same input"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ex, B, out_dir):
+    """What a caller of the timed step receives for the frames of the LAST timed step, as out_dir/<name>.npy, so that two
+    builds run with the same arguments (hence the same input frames) can be compared output for output:
+      frames.npy       [F]        which frames of the step are written (all B, or a fixed seeded sample when all would
+                                  exceed 64 MB)
+      n_keypoints.npy  [F]        keypoints per frame;  n_matches.npy [F]  accepted matches per frame
+      keypoints.npy    [N, 7]     float64 x, y, size, angle, response, octave, class_id of every keypoint, frame after frame
+      descriptors.npy  [N, 32]    float32 bytes of the descriptors, same rows
+      matches.npy      [N]        float64 match table: index of the matched keypoint of the previous frame, -1 = none"""
+    import numpy as np
+    per_frame = ex.max_keypoints * (7 * 8 + 32 * 4 + 8) + 16   # bytes a frame can take at most
+    frames = np.arange(B)
+    if per_frame * B > DUMP_LIMIT_BYTES:
+        frames = np.sort(np.random.default_rng(0).choice(B, max(1, DUMP_LIMIT_BYTES // per_frame), replace=False))
+    kps, desc, match, nk, nm = [], [], [], [], []
+    for f in frames:
+        k, d = ex.download(int(f))
+        m, n = ex.download_matches(int(f))
+        kps.append(np.stack([k[name].astype(np.float64) for name in k.dtype.names], axis=1).reshape(len(k), len(k.dtype.names)))
+        desc.append(np.asarray(d, np.float32).reshape(len(k), 32))
+        match.append(np.asarray(m[:len(k)], np.float64))
+        nk.append(len(k))
+        nm.append(n)
+    out = {"frames": frames.astype(np.float64), "n_keypoints": np.array(nk, np.float64), "n_matches": np.array(nm, np.float64),
+           "keypoints": np.concatenate(kps), "descriptors": np.concatenate(desc), "matches": np.concatenate(match)}
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT_BYTES
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def natural_sequences(W, H, B):
     """The 64-frame step on frames with natural statistics (the reference's inputs are photographs,
     mono_tum.cc:60-78 -- absent here).  From tests/golden/natural.npz (scikit-image photographs, 1241x376 only):
@@ -957,6 +1006,8 @@ def run_rank(args):
             first_batch = fr
         dargs.append(ex.upload_frames(fr, stride=STRIDE))
     del fr
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)   # (fails before the GPU work, not after it)
 
     if distributed:
         # torch only for torch.distributed (backend "nccl" = RCCL over xGMI); a 1-GPU run needs no torch at all
@@ -1026,13 +1077,16 @@ def run_rank(args):
     diag = {"device": dev_index, "pci": None, "clock_mhz": None}
     if not os.environ.get("ORBX_BENCH_EXTRACTOR"):
         from orbslamm_amd import _lib as _l
-        diag["clock_mhz"] = _l.shader_clock_mhz(dev_index)
+        if args.full:
+            diag["clock_mhz"] = _l.shader_clock_mhz(dev_index)
         diag["pci"] = _l.device_pci_bus_id(dev_index)
     prof = ex.profile_read(reset=True) if not args.no_profile else {}
     ex.profile_enable(False)
     ex.profile_select(None)
     steps_bracketed = (args.steps + SAMPLE - 1) // SAMPLE
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ex, B, args.dump_outputs)
 
     # match statistics of the last frame; RCCL all_gather over xGMI (not on the data path)
     _, nmatch_last = ex.download_matches(B - 1)
@@ -1131,22 +1185,25 @@ def run_rank(args):
             "keypoints_last_frame": [int(g[1]) for g in gathered],
             "matches_last_frame": [int(g[2]) for g in gathered],
         }
-        traffic_src = _latest_profile("pmc_traffic.json")
-        sq_src = _latest_profile("pmc_sq.json")
-        traffic_tab = json.load(open(traffic_src)) if traffic_src else {}
-        sq_tab = json.load(open(sq_src)) if sq_src else {}
-        # the replayed PMC tables carry the hash of the kernel sources they were measured on
-        sys.path.insert(0, os.path.join(_ROOT, "tools"))
-        from kernels_sha import kernels_sha
-        sha_now = kernels_sha()
-        replay = {"kernels_sha16_now": sha_now,
-                  "traffic": {"source": os.path.basename(traffic_src) if traffic_src else None, "kernels_sha16": traffic_tab.pop("_kernels_sha16", None)},
-                  "issue": {"source": os.path.basename(sq_src) if sq_src else None, "kernels_sha16": sq_tab.get("kernels_sha16")}}
-        for k in ("traffic", "issue"):
-            replay[k]["stale"] = replay[k]["kernels_sha16"] != sha_now   # (tables older than round 4 carry no hash: stale by definition)
-        if replay["traffic"]["stale"] or replay["issue"]["stale"]:
-            sys.stderr.write("bench.py: the replayed PMC tables (%s, %s) were not taken on the current kernel sources: roofline.traffic / roofline.issue are from an older build\n"
-                             % (replay["traffic"]["source"], replay["issue"]["source"]))
+        traffic_src = sq_src = replay = None
+        traffic_tab, sq_tab = {}, {}
+        if args.full:   # the roofline's replayed PMC tables
+            traffic_src = _latest_profile("pmc_traffic.json")
+            sq_src = _latest_profile("pmc_sq.json")
+            traffic_tab = json.load(open(traffic_src)) if traffic_src else {}
+            sq_tab = json.load(open(sq_src)) if sq_src else {}
+            # the replayed PMC tables carry the hash of the kernel sources they were measured on
+            sys.path.insert(0, os.path.join(_ROOT, "tools"))
+            from kernels_sha import kernels_sha
+            sha_now = kernels_sha()
+            replay = {"kernels_sha16_now": sha_now,
+                      "traffic": {"source": os.path.basename(traffic_src) if traffic_src else None, "kernels_sha16": traffic_tab.pop("_kernels_sha16", None)},
+                      "issue": {"source": os.path.basename(sq_src) if sq_src else None, "kernels_sha16": sq_tab.get("kernels_sha16")}}
+            for k in ("traffic", "issue"):
+                replay[k]["stale"] = replay[k]["kernels_sha16"] != sha_now   # (tables older than round 4 carry no hash: stale by definition)
+            if replay["traffic"]["stale"] or replay["issue"]["stale"]:
+                sys.stderr.write("bench.py: the replayed PMC tables (%s, %s) were not taken on the current kernel sources: roofline.traffic / roofline.issue are from an older build\n"
+                                 % (replay["traffic"]["source"], replay["issue"]["source"]))
 
         def roofline_of(prof, dom=None, nsteps=args.steps):
             kern = {k: v for k, v in prof.items() if v[1] > 0 and k.startswith("k_")}
@@ -1241,12 +1298,14 @@ def run_rank(args):
             out["natural"] = nat
         if trk is not None:
             out["tracking_path"] = trk
-        out["replayed_pmc"] = replay
+        if args.full:
+            out["replayed_pmc"] = replay
         if ls is not None:
             out["live_streams"] = ls
         if dic is not None:
             out["dropin_classes"] = dic
-        out["side_blocks"] = budget.record()
+        if args.full:
+            out["side_blocks"] = budget.record()
         if not args.no_cpu_baseline:
             # the CPU figure beside EVERY number.  N = 1: ~12 s on one thread + the one-thread-per-stream leg;
             # N > 1 (rank 0, the other ranks wait in finalize's barrier): a 6 s one-thread sample, so that a scaling sweep

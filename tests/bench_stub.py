@@ -7,6 +7,8 @@ import time
 
 import numpy as np
 
+from orbslamm_amd._lib import KP_DTYPE
+
 
 class StubExtractor:
     def __init__(self, nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST, max_width=0, max_height=0, max_batch=1, device=0):
@@ -51,8 +53,13 @@ class StubExtractor:
     def set_serial(self, on=True):
         pass
 
+    max_keypoints = 2048
+
     def download(self, frame):
-        return np.zeros(1500 + self.rank, dtype=np.uint8), None
+        # records and descriptor rows of the real layout, made up from the frame index (for --dump-outputs)
+        kps = np.zeros(1500 + self.rank, dtype=KP_DTYPE)
+        kps["x"], kps["octave"] = frame, frame % 8
+        return kps, np.full((len(kps), 32), frame, dtype=np.uint8)
 
     def download_matches(self, frame):
         dump = os.environ.get("ORBX_BENCH_STUB_DUMP")
@@ -60,7 +67,9 @@ class StubExtractor:
             with open(os.path.join(dump, "rank%d.json" % self.rank), "w") as f:
                 json.dump({"rank": self.rank, "device": self.device, "steps": self.steps, "uploads": self.uploads,
                            "world": int(os.environ.get("WORLD_SIZE", "1"))}, f)
-        return None, 700 + self.rank
+        m = np.full(self.max_keypoints, -1, dtype=np.int32)
+        m[:700 + self.rank] = np.arange(700 + self.rank)
+        return m, 700 + self.rank
 
     def level_sizes(self):
         out, w, h = [], self.w, self.h

@@ -62,14 +62,19 @@ def test_check_vs_opencv_compiles(tmp_path):
     """tools/check_vs_opencv/check_vs_opencv.cpp -- the program that pins the oracle against a real OpenCV + the
     reference's unmodified ORBextractor.cc wherever OpenCV exists -- at least parses and type-checks here: against
     declaration-only cv:: headers (tests/cpp/mock_opencv) and, when the reference checkout is present, its own
-    include/ORBextractor.h.  Nothing is built or run (there is no OpenCV in this image); the exporter of the frames it
-    reads is run for real."""
-    import pytest
+    include/ORBextractor.h -- without it, include/ORBextractor_hip.hpp in its -DORBSLAMM_WITH_OPENCV form, the drop-in
+    with the same class, namespace and signatures.  Nothing is built or run (there is no OpenCV in this image); the
+    exporter of the frames it reads is run for real."""
     ref_inc = "/root/reference/SingleRobotScenario/include"
+    extra = []
     if not os.path.exists(os.path.join(ref_inc, "ORBextractor.h")):
-        pytest.skip("no reference checkout: the program includes the reference's own header")
+        ref_inc = str(tmp_path / "dropin_include")
+        os.makedirs(ref_inc)
+        with open(os.path.join(ref_inc, "ORBextractor.h"), "w") as f:
+            f.write('#include "ORBextractor_hip.hpp"\n')
+        extra = ["-DORBSLAMM_WITH_OPENCV", "-I", os.path.join(ROOT, "include")]
     subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-I", os.path.join(ROOT, "tests", "cpp", "mock_opencv"), "-I", ref_inc,
-                           "-I", os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tools", "check_vs_opencv", "check_vs_opencv.cpp")])
+                           "-I", os.path.join(ROOT, "oracle")] + extra + [os.path.join(ROOT, "tools", "check_vs_opencv", "check_vs_opencv.cpp")])
     subprocess.check_call(["python3", os.path.join(ROOT, "tools", "check_vs_opencv", "export_pgm.py"), str(tmp_path / "frames")])
     names = os.listdir(tmp_path / "frames")
     assert len(names) == 19 and all(n.endswith(".pgm") for n in names)

@@ -73,7 +73,7 @@ def test_a_failing_rank_fails_the_launch(tmp_path):
 def test_two_rank_record_carries_the_cpu_baseline_and_the_interval_stamp(tmp_path):
     """the CPU figure beside EVERY number -- the N > 1 record too (rank 0 times a bounded one-thread
     sample of the oracle after the gather; round 4 emitted it at N = 1 only)."""
-    args = [a for a in ARGS if a != "--no-cpu-baseline"]
+    args = [a for a in ARGS if a != "--no-cpu-baseline"] + ["--full"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + args, capture_output=True, text=True,
                          env=_env(tmp_path, ORBX_BENCH_CPU_SECONDS="1.0"), cwd=ROOT, timeout=280)
     rec = _check_record(out, tmp_path)
@@ -91,7 +91,7 @@ def test_eight_ranks_eight_disjoint_streams_one_record(tmp_path):
     gloo on a free port, the stub standing in for the GPUs.  Eight different camera streams on eight different devices,
     ONE record, with `roofline` and `cpu_baseline` in it (MultipleRobotsScenario/Examples/Monocular/mono_kitti.cc:80-101:
     eight robots, nothing shared but the counters)."""
-    args = [a for a in ARGS if a != "--no-cpu-baseline"]
+    args = [a for a in ARGS if a != "--no-cpu-baseline"] + ["--full"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"] + args, capture_output=True, text=True,
                          env=_env(tmp_path, ORBX_BENCH_STUB_DEVICES="8", ORBX_BENCH_CPU_SECONDS="1.0", ORBX_BENCH_STUB_PROFILE="1"), cwd=ROOT, timeout=550)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -135,6 +135,40 @@ def test_single_rank_with_the_stub_prints_one_line(tmp_path):
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads(out.stdout)
     assert rec["n_gpus"] == 1 and "torch" not in out.stderr.lower()
+
+
+FULL_ONLY = ("cpu_baseline", "roofline", "parity_check", "natural", "tracking_path", "host_path", "live_streams", "dropin_classes",
+             "replayed_pmc", "side_blocks")
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_times_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """a plain run (no --full): the headline fields, exactly --steps timed steps, none of --full's blocks; --dump-outputs
+    writes the last step's keypoints, descriptors and match tables in float32 / float64, the same from run to run"""
+    import numpy as np
+    args = [a for a in ARGS if a != "--no-cpu-baseline"]
+    got = []
+    for run in range(2):
+        d = tmp_path / ("outputs%d" % run)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(d)], capture_output=True, text=True,
+                             env=_env(tmp_path, ORBX_BENCH_STUB_PROFILE="1"), cwd=ROOT, timeout=280)
+        assert out.returncode == 0, out.stderr[-2000:]
+        rec = json.loads(out.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in rec, k
+        assert rec["steps"] == 6 and rec["unit"] == "frames/s" and rec["higher_is_better"] is True and rec["dtype"] == "u8"
+        assert abs(rec["value"] - 4 * 6 / (rec["ms_per_step"] * 6 / 1e3)) < 1e-6 * rec["value"]
+        assert not set(FULL_ONLY) & set(rec), set(FULL_ONLY) & set(rec)
+        assert json.load(open(tmp_path / "rank0.json"))["steps"] == 3 + 2 + 6   # pool validation + warmup + EXACTLY the timed steps
+        a = {n: np.load(str(d / (n + ".npy"))) for n in ("frames", "n_keypoints", "n_matches", "keypoints", "descriptors", "matches")}
+        assert sorted(os.listdir(str(d))) == sorted(n + ".npy" for n in a)
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+        assert a["frames"].tolist() == [0, 1, 2, 3] and a["n_keypoints"].tolist() == [1500] * 4 and a["n_matches"].tolist() == [700] * 4
+        assert a["keypoints"].shape == (6000, 7) and a["descriptors"].shape == (6000, 32) and a["matches"].shape == (6000,)
+        assert a["keypoints"][1500:3000, 0].tolist() == [1.0] * 1500 and a["descriptors"][4500:, 0].tolist() == [3.0] * 1500
+        assert (a["matches"][:700] == np.arange(700)).all() and (a["matches"][700:1500] == -1).all()
+        got.append(a)
+    assert all(np.array_equal(got[0][n], got[1][n]) for n in got[0])
 
 
 def test_device_of_rank():

@@ -25,7 +25,8 @@ def run_bench(extra_env, extra_args=()):
     env.update(extra_env)
     # (the live-stream / drop-in / tracking side blocks are a dozen sub-processes: one dedicated test below keeps them, the
     # contract tests do not pay for them four times over -- round 4's suite took 695 s at the driver that way)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--no-cpu-baseline", "--no-replay",
+    # (--full: the roofline and natural blocks these tests read are no part of a plain run)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "2", "--no-cpu-baseline", "--no-replay",
            "--no-host-path", "--no-live-streams", "--no-tracking-path", "--pool", "2"]
     return subprocess.run(cmd + list(extra_args), capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
 
@@ -108,10 +109,10 @@ def test_c2_config_has_a_bench_line(gpu):
 
 @pytest.mark.timeout(600)
 def test_default_record_carries_the_side_blocks_under_one_budget(gpu):
-    """the record the DRIVER gets (no --no-* flags but the CPU baseline's): the side blocks run under one wall-clock budget
+    """the --full record (no --no-* flags but the CPU baseline's): the side blocks run under one wall-clock budget
     and say what they took; SURVEY.md 8(d)'s PCIe-inclusive figures and the timed-region stamp ride in `config` as scalars;
     the drop-in classes' Tracking-shaped loop is in the record and made no device state per matcher object."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--pool", "4", "--side-budget", "120"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--pool", "4", "--side-budget", "120"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=_plain_env(), cwd=ROOT, timeout=550)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads(out.stdout)
@@ -138,10 +139,46 @@ def test_default_record_carries_the_side_blocks_under_one_budget(gpu):
 
 @pytest.mark.timeout(300)
 def test_side_budget_of_zero_skips_every_side_block_and_keeps_the_headline(gpu):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-replay", "--pool", "2", "--side-budget", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-replay", "--pool", "2", "--side-budget", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=_plain_env(), cwd=ROOT, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads(out.stdout)
     assert rec["value"] > 50000 and rec["parity_check"]["ok"] is True
     assert set(rec["side_blocks"]["skipped"]) >= {"live_streams", "dropin_classes", "tracking_path", "host_path"}
     assert "live_streams" not in rec and "host_path" not in rec and rec["config"]["host_inclusive_fps_pinned"] is None
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_dumps_the_last_step_as_the_oracle_computes_it(gpu, oracle, tmp_path):
+    """a plain run (no --full) with --dump-outputs: the headline record without --full's blocks, and the dumped keypoints,
+    descriptors and match tables of the last timed step -- its last two frames byte for byte the CPU oracle's on the same input"""
+    import numpy as np
+    from orbslamm_amd import synth
+    steps, warmup, pool, B, W, H = 7, 2, 2, 64, 1241, 376
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--pool", str(pool),
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, env=_plain_env(), cwd=ROOT, timeout=550)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads(out.stdout)
+    assert rec["steps"] == steps and rec["unit"] == "frames/s" and rec["higher_is_better"] is True and rec["dtype"] == "u8"
+    assert rec["value"] > 0 and abs(rec["value"] - B * steps / (rec["ms_per_step"] * steps / 1e3)) < 1e-6 * rec["value"]
+    assert not {"roofline", "parity_check", "natural", "cpu_baseline", "side_blocks", "live_streams", "host_path", "tracking_path"} & set(rec)
+    a = {n: np.load(str(tmp_path / "out" / (n + ".npy"))) for n in ("frames", "n_keypoints", "n_matches", "keypoints", "descriptors", "matches")}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["frames"].tolist() == list(range(B))
+    nk = a["n_keypoints"].astype(np.int64)
+    assert nk[-1] == rec["keypoints_last_frame"][0] and a["n_matches"][-1] == rec["matches_last_frame"][0]
+    start = np.concatenate([[0], np.cumsum(nk)])
+    assert a["keypoints"].shape == (start[-1], 7) and a["descriptors"].shape == (start[-1], 32) and a["matches"].shape == (start[-1],)
+    canvas = synth.make_scene(W, H, 0)
+    p_last = (warmup + steps - 1) % pool   # the resident batch the last timed step extracted (rank 0 = camera stream 0)
+    oex = oracle.Extractor(2000, 1.2, 8, 20, 7)
+    ref = {f: oex(synth.frame_from_scene(canvas, W, H, p_last * B + f, 0)) for f in (B - 3, B - 2, B - 1)}
+    for f in (B - 2, B - 1):
+        r, rp = ref[f], ref[f - 1]
+        assert nk[f] == len(r["kps"]) > 1000
+        k = a["keypoints"][start[f]:start[f + 1]]
+        assert all(np.array_equal(k[:, i], r["kps"][name].astype(np.float64)) for i, name in enumerate(r["kps"].dtype.names))
+        assert np.array_equal(a["descriptors"][start[f]:start[f + 1]], r["desc"].astype(np.float32))
+        wm, wn = oracle.match_bruteforce(r["desc"], r["kps"]["angle"], rp["desc"], rp["kps"]["angle"], 0.7, 50, True)
+        assert a["n_matches"][f] == wn > 100 and np.array_equal(a["matches"][start[f]:start[f] + len(wm)], np.asarray(wm, np.float64))

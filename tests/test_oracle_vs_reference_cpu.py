@@ -1,9 +1,10 @@
 """The oracle's BowVector / FeatureVector assembly against the REFERENCE's own object code.
 
-oracle/_ref/libdbow2_ref.so is DBoW2's BowVector.cpp + FeatureVector.cpp compiled from /root/reference where they lie
-(oracle/Makefile target _ref; these two files need the C++ standard library only -- everything else on the path
-includes OpenCV and is unbuildable here) plus oracle/ref_dbow2_shim.cpp, a caller of the two classes.  It is built in
-the authoring container and travels to the GPU box as a prebuilt library; /root/reference is not read at test time.
+oracle/_ref/libdbow2_ref.so is DBoW2's BowVector.cpp + FeatureVector.cpp compiled from the reference checkout where they
+lie (oracle/Makefile target _ref; these two files need the C++ standard library only -- everything else on the path
+includes OpenCV and is unbuildable here) plus oracle/ref_dbow2_shim.cpp, a caller of the two classes.  Its outputs for
+every call below are recorded in tests/golden/dbow2_ref.npz (tests/golden/make_dbow2_ref.py): where the library is
+built, each call runs on it and must equal the recording; elsewhere the recording stands in for it.
 
 What this pins, bit for bit (float64 compared with ==):
   BowVector::addWeight / addIfNotExist   accumulation of repeated words, in feature order
@@ -20,17 +21,65 @@ every occurrence of a word carries the SAME weight, so the order in which a word
 (reversing it: 0 of 12 configurations differ) -- test_transform_assembly... does detect the wrong norm (10 of 10),
 first-instead-of-sum (10 of 10) and the norm summed over the words in another order (8 of 10).  The accumulation order
 itself is pinned by test_summation_order... with unequal weights per word, where reversing the stream changes the bits."""
+import hashlib
+import os
+
 import numpy as np
 import pytest
 
 from vocab_cases import make_vocab
 
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dbow2_ref.npz")
+
+
+def _key(kind, *args):
+    """the recording's name for one call: a digest of exactly what the call feeds the reference"""
+    h = hashlib.sha1(kind.encode())
+    for a in args:
+        a = np.ascontiguousarray(a)
+        h.update(("%s%s" % (a.dtype.str, a.shape)).encode())
+        h.update(a.tobytes())
+    return "%s_%s" % (kind, h.hexdigest()[:20])
+
+
+class RecordedRef:
+    """The reference's outputs for the calls these tests make, recorded from oracle/_ref/libdbow2_ref.so into
+    tests/golden/dbow2_ref.npz (tests/golden/make_dbow2_ref.py), so that the tests hold the oracle to the reference's
+    object code wherever they run, built or not.  With `live` (the library is built here) every call goes to the
+    reference itself and must also equal the recording; with `record` the calls are written down instead."""
+
+    def __init__(self, oracle, live=False, record=False):
+        self.oracle, self.live, self.record = oracle, live or record, record
+        self.Vocabulary = oracle.Vocabulary
+        self.calls = {} if record else dict(np.load(GOLDEN))
+
+    def _call(self, kind, names, fn, inputs):
+        k = _key(kind, *inputs)
+        if self.record:
+            out = fn(*inputs)
+            self.calls.update({k + "_" + n: v for n, v in zip(names, out)})
+            return out
+        assert k + "_" + names[0] in self.calls, "call not in %s: regenerate it with tests/golden/make_dbow2_ref.py" % os.path.basename(GOLDEN)
+        rec = tuple(self.calls[k + "_" + n] for n in names)
+        if self.live:
+            out = fn(*inputs)
+            assert all(a.dtype == b.dtype and a.tobytes() == b.tobytes() for a, b in zip(out, rec)), "the recording differs from the reference's object code"
+        return rec
+
+    def ref_bow_build(self, ids, w, add_if_not_exist, norm):
+        ids, w = np.ascontiguousarray(ids, dtype=np.uint32), np.ascontiguousarray(w, dtype=np.float64)
+        mode = np.array([int(bool(add_if_not_exist)), int(norm)], np.int32)
+        return self._call("bow", ("ids", "w"), lambda i, x, m: self.oracle.ref_bow_build(i, x, bool(m[0]), int(m[1])), (ids, w, mode))
+
+    def ref_fv_build(self, node, feat):
+        node, feat = np.ascontiguousarray(node, dtype=np.uint32), np.ascontiguousarray(feat, dtype=np.uint32)
+        return self._call("fv", ("node", "start", "idx"), self.oracle.ref_fv_build, (node, feat))
+
+
 @pytest.fixture(scope="module")
 def ref(oracle):
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref/libdbow2_ref.so absent and no /root/reference to build it from")
-    return oracle
+    return RecordedRef(oracle, live=oracle.ref_lib() is not None)
 
 
 def reference_assembly(ref, word, w, nid, scoring, weighting):

@@ -6,7 +6,7 @@ N=$1; shift
 for i in $(seq $N); do
   for cfg in "$@"; do
     if [ "$cfg" = "-" ]; then E=""; else E="$cfg"; fi
-    env $E python $R/bench.py --no-cpu-baseline --no-host-path --no-tracking-path --no-live-streams --no-dropin-classes 2>/dev/null | tail -1 | python -c "
+    env $E python $R/bench.py --full --no-cpu-baseline --no-host-path --no-tracking-path --no-live-streams --no-dropin-classes 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['isolated']['kernel_ms_per_step']
 print('[$cfg]', round(d['value']), round(d['ms_per_step'],4), 'parity', d.get('parity_check',{}).get('ok'), {n: round(k[n],4) for n in ('k_fast','k_distribute') if n in k})"

@@ -6,7 +6,7 @@ VAR=$1; N=$2; shift 2
 for i in $(seq $N); do
   for v in "$@"; do
     if [ "$v" = "-" ]; then unset $VAR; else export $VAR=$v; fi
-    python $R/bench.py --no-cpu-baseline --no-host-path --no-tracking-path --no-live-streams --no-dropin-classes 2>/dev/null | tail -1 | python -c "
+    python $R/bench.py --full --no-cpu-baseline --no-host-path --no-tracking-path --no-live-streams --no-dropin-classes 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['isolated']['kernel_ms_per_step']
 print('$VAR=$v', round(d['value']), round(d['ms_per_step'],4), d.get('parity_check',{}).get('ok'), {n: round(k[n],4) for n in ('k_pyramid','k_fast','k_blur','k_orient_desc','k_distribute','k_match_mfma') if n in k})"

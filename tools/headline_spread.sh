@@ -2,7 +2,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 N=${1:-6}
 for i in $(seq $N); do
-  python $R/bench.py --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  python $R/bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; print(round(d['value']), round(d['ms_per_step'],4), round(r['avg_launch_ms'],4), round(r['isolated']['kernel_ms_per_step']['k_fast'],4))"
 done | tee $R/gpurun_out/headline_spread.txt

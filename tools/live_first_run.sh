@@ -9,7 +9,7 @@ for i in 1 2 3; do
 done
 for i in 1 2; do
   SECONDS=0
-  timeout 600 python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-path --no-tracking-path --no-parity-check --no-profile > /tmp/b$i.json 2>/tmp/b$i.err; tail -1 /tmp/b$i.err
+  timeout 600 python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-host-path --no-tracking-path --no-parity-check --no-profile > /tmp/b$i.json 2>/tmp/b$i.err; tail -1 /tmp/b$i.err
   python3 - <<PY
 import json
 d=json.loads(open("/tmp/b$i.json").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # HBM traffic of the stream matcher per 64-pair step (FETCH_SIZE / WRITE_SIZE passes, kernels alone): bash tools/match_traffic.sh
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
-pmc() { ORBX_SERIAL=1 timeout 240 rocprofv3 --pmc $2 -d /tmp/pmc_$1 -o p -- python $R/bench.py --no-cpu-baseline --no-profile --no-host-path --no-tracking-path --no-parity-check --no-live-streams --pool 2 --steps 5 --warmup 2 > /dev/null 2>&1; }
+pmc() { ORBX_SERIAL=1 timeout 240 rocprofv3 --pmc $2 -d /tmp/pmc_$1 -o p -- python $R/bench.py --full --no-cpu-baseline --no-profile --no-host-path --no-tracking-path --no-parity-check --no-live-streams --pool 2 --steps 5 --warmup 2 > /dev/null 2>&1; }
 pmc f FETCH_SIZE; pmc w WRITE_SIZE
 python $R/tools/pmc_traffic.py /tmp/pmc_f/p_results.db /tmp/pmc_w/p_results.db /tmp/traffic.json > /dev/null
 python - <<PY

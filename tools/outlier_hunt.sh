@@ -1,4 +1,4 @@
-for i in $(seq 1 40); do python bench.py --no-cpu-baseline --no-replay --steps 10 2>/dev/null | tail -1 > /tmp/o_$i.json; python - <<PY
+for i in $(seq 1 40); do python bench.py --full --no-cpu-baseline --no-replay --steps 10 2>/dev/null | tail -1 > /tmp/o_$i.json; python - <<PY
 import json
 d=json.load(open("/tmp/o_$i.json"))
 v=d["value"]

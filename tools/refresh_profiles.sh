@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 # the counter passes FIRST: bench.py replays their tables (profiles/${TAG}_pmc_*.json) and flags them stale when the kernel sources changed since
 export ORBX_SERIAL=1
 pmc() { # tag, counters
-  timeout 240 rocprofv3 --pmc $2 -d /tmp/pmc_$1 -o p -- python $R/bench.py --no-cpu-baseline --no-profile --no-host-path --no-tracking-path --no-natural --no-parity-check --pool 2 --steps 5 --warmup 2 > /dev/null 2>&1
+  timeout 240 rocprofv3 --pmc $2 -d /tmp/pmc_$1 -o p -- python $R/bench.py --full --no-cpu-baseline --no-profile --no-host-path --no-tracking-path --no-natural --no-parity-check --pool 2 --steps 5 --warmup 2 > /dev/null 2>&1
 }
 pmc fetch "FETCH_SIZE"; python $R/tools/rocprof_summary.py pmc /tmp/pmc_fetch/p_results.db > $O/${TAG}_pmc_fetch.txt
 pmc write "WRITE_SIZE"; python $R/tools/rocprof_summary.py pmc /tmp/pmc_write/p_results.db > $O/${TAG}_pmc_write.txt
@@ -21,14 +21,14 @@ pmc sqc "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU_MFMA_I8 GRBM_GUI_A
 python $R/tools/pmc_sq_json.py $O/${TAG}_pmc_sq.json /tmp/pmc_sqa/p_results.db /tmp/pmc_sqb/p_results.db /tmp/pmc_sqc/p_results.db > /dev/null
 unset ORBX_SERIAL
 cp $O/${TAG}_pmc_traffic.json $O/${TAG}_pmc_sq.json $R/profiles/
-python $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-path --no-tracking-path > $O/${TAG}_bench_20steps.json 2>> $O/${TAG}_bench.err
-python $R/bench.py --config c2 --no-cpu-baseline --no-host-path --no-tracking-path > $O/${TAG}_bench_c2.json 2>> $O/${TAG}_bench.err
-ORBX_SERIAL=1 python $R/bench.py --no-cpu-baseline --no-host-path --no-tracking-path > $O/${TAG}_bench_serial.json 2>> $O/${TAG}_bench.err
-timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_o -o t -- python $R/bench.py --no-cpu-baseline --no-replay --no-host-path --no-tracking-path --no-parity-check > $O/${TAG}_bench_under_rocprof.json 2>/dev/null
+python $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-path --no-tracking-path > $O/${TAG}_bench_20steps.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --config c2 --no-cpu-baseline --no-host-path --no-tracking-path > $O/${TAG}_bench_c2.json 2>> $O/${TAG}_bench.err
+ORBX_SERIAL=1 python $R/bench.py --full --no-cpu-baseline --no-host-path --no-tracking-path > $O/${TAG}_bench_serial.json 2>> $O/${TAG}_bench.err
+timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_o -o t -- python $R/bench.py --full --no-cpu-baseline --no-replay --no-host-path --no-tracking-path --no-parity-check > $O/${TAG}_bench_under_rocprof.json 2>/dev/null
 python $R/tools/rocprof_summary.py stats /tmp/prof_o/t_results.db > $O/${TAG}_kernel_stats.txt
 python $R/tools/timeline.py /tmp/prof_o/t_results.db 70 300 > $O/${TAG}_timeline.txt
-ORBX_SERIAL=1 timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_s -o t -- python $R/bench.py --no-cpu-baseline --no-replay --no-host-path --no-tracking-path --no-parity-check > /dev/null 2>&1
+ORBX_SERIAL=1 timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_s -o t -- python $R/bench.py --full --no-cpu-baseline --no-replay --no-host-path --no-tracking-path --no-parity-check > /dev/null 2>&1
 python $R/tools/rocprof_summary.py stats /tmp/prof_s/t_results.db > $O/${TAG}_kernel_stats_serial.txt
 if [ -x $R/build_ub/fetch_calib ]; then
   rocprofv3 --pmc FETCH_SIZE -d /tmp/c1 -o p -- $R/build_ub/fetch_calib > /dev/null 2>&1; rocprofv3 --pmc WRITE_SIZE -d /tmp/c2 -o p -- $R/build_ub/fetch_calib > /dev/null 2>&1
