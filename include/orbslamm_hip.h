@@ -456,7 +456,10 @@ int orbm_last_search_stats(orbm_t* h, int* rounds, int* candidates);
  *     orbm_search_by_projection_frame on the same data.  pp->mode must be 4.  Asynchronous.
  *   orbm_track_results: waits for the last (back = 0) or an earlier (back = 1 .. 3) orbm_track_frames; assign[p*cap + t] =
  *     LastFrame feature index held by CurrentFrame feature t (or -1), nmatches[p]; both point into pinned host memory the
- *     kernel wrote (four result sets in rotation: valid until three more calls have been issued).
+ *     kernel wrote (four result sets in rotation: valid until three more calls have been issued).  A search whose
+ *     candidates overflowed the set's arena is run again with a larger one -- a frame-to-frame search and a query search
+ *     (orbm_track_local_points, orbm_track_frame_projected) alike; ORBX_E_CAPACITY when a slot it read has been rebuilt
+ *     since, or a larger query search issued behind it reallocated its staging.
  * bounds = mnMinX, mnMaxX, mnMinY, mnMaxY (Frame::ComputeImageBounds); scale_factors = mvScaleFactors. */
 typedef struct orbm_frameset orbm_frameset_t;
 int orbm_frameset_create(orbm_t* h, int slots, int cap, const float K[4], const float D[5], const OrbmGrid* grid,

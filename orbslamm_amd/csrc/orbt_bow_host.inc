@@ -10,10 +10,8 @@ struct orbm_frameset_bow {
     uint32_t* d_fvNode = nullptr; int32_t *d_fvStart = nullptr, *d_fvIdx = nullptr, *d_counts = nullptr;
     uint8_t* d_zero = nullptr; size_t zeroBytes = 0;     // matched[S][C] | hist[S][32]: cleared before every search
     uint8_t* d_matched = nullptr; int32_t* d_hist = nullptr; int32_t* d_match = nullptr; uint8_t* d_binOf = nullptr;
-    uint8_t* h_block = nullptr; int32_t* h_match = nullptr; int32_t* h_n = nullptr;   // pinned, kResSets result sets
-    static constexpr int kResSets = 4;
-    int resSet = 0; int lastPairs[kResSets] = {0, 0, 0, 0};
-    hipEvent_t evRes[kResSets] = {nullptr, nullptr, nullptr, nullptr};
+    uint8_t* h_block = nullptr; int32_t* h_match = nullptr; int32_t* h_n = nullptr;   // pinned, one share per result set
+    ResultRing res;   // (searches that write no flags and are never run again)
     int maxNodes = 0, P = 2;
     bool computed = false;
     void* d_gkeys = nullptr;   // sort scratch of the memory form (frames of more than 8192 features)
@@ -26,7 +24,7 @@ static void frameset_bow_free(orbm_frameset* fs)
     if (b->d_block) (void)hipFree(b->d_block);
     if (b->d_gkeys) (void)hipFree(b->d_gkeys);
     if (b->h_block) (void)hipHostFree(b->h_block);
-    for (auto e : b->evRes) if (e) (void)hipEventDestroy(e);
+    b->res.destroy();
     delete b;
     fs->bow = nullptr;
 }
@@ -41,7 +39,7 @@ static int frameset_bow_alloc(orbm_frameset* fs)
     const size_t oFn = pk.take(S * C * 4), oFs = pk.take(S * (C + 1) * 4), oFi = pk.take(S * C * 4), oCt = pk.take(S * 8);
     const size_t oMa = pk.take(S * C), oHi = pk.take(S * 32 * 4), oMt = pk.take(S * C * 4), oBn = pk.take(S * C);
     Packer hp;
-    const size_t hM = hp.take(orbm_frameset_bow::kResSets * S * C * 4), hN = hp.take(orbm_frameset_bow::kResSets * S * 4);
+    const size_t hM = hp.take(ResultRing::kSets * S * C * 4), hN = hp.take(ResultRing::kSets * S * 4);
     if (hipMalloc(&b->d_block, pk.off) != hipSuccess || hipHostMalloc(&b->h_block, hp.off, hipHostMallocDefault) != hipSuccess) {
         if (b->d_block) (void)hipFree(b->d_block);
         delete b;
@@ -138,9 +136,8 @@ extern "C" int orbm_bow_frames(orbm_frameset_t* fs, const int32_t* kf_slots, con
         if (kf_slots[p] < 0 || kf_slots[p] >= fs->slots || frame_slots[p] < 0 || frame_slots[p] >= fs->slots) return fail(ORBX_E_INVALID, "slot outside the frame set");
     orbm_frameset_bow* b = fs->bow;
     orbm_handle* h = fs->owner;
-    const int set = b->resSet = (b->resSet + 1) % orbm_frameset_bow::kResSets;
-    b->lastPairs[set] = npairs;
-    if (!b->evRes[set]) HIPCHK(hipEventCreateWithFlags(&b->evRes[set], hipEventDisableTiming));
+    const int set = b->res.next();
+    if ((rc = b->res.begin(set))) return rc;
     if (npairs) {
         const size_t S = (size_t)fs->slots, C = (size_t)fs->cap;
         HIPCHK(hipMemsetAsync(b->d_zero, 0, b->zeroBytes, h->stream));
@@ -158,7 +155,8 @@ extern "C" int orbm_bow_frames(orbm_frameset_t* fs, const int32_t* kf_slots, con
         }
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(b->evRes[set], h->stream));
+    HIPCHK(hipEventRecord(b->res.rec[set].ev, h->stream));
+    b->res.commit(set, ResultRecord::kNone, npairs, 0);
     return ORBX_OK;
 }
 
@@ -166,15 +164,16 @@ extern "C" int orbm_bow_results(orbm_frameset_t* fs, int back, const int32_t** m
 {
     int rc = frameset_check(fs);
     if (rc) return rc;
-    if (!fs->bow || back < 0 || back >= orbm_frameset_bow::kResSets) return fail(ORBX_E_INVALID, "bad argument");
+    if (!fs->bow || back < 0 || back >= ResultRing::kSets) return fail(ORBX_E_INVALID, "bad argument");
     orbm_frameset_bow* b = fs->bow;
-    const int set = (b->resSet + orbm_frameset_bow::kResSets - back) % orbm_frameset_bow::kResSets;
-    if (!b->evRes[set]) return fail(ORBX_E_INVALID, "no such search has been issued");
-    HIPCHK(hipEventSynchronize(b->evRes[set]));
+    const int set = b->res.back(back);
+    const ResultRecord& r = b->res.rec[set];
+    if (!r.ev) return fail(ORBX_E_INVALID, "no such search has been issued");
+    HIPCHK(hipEventSynchronize(r.ev));
     const size_t S = (size_t)fs->slots, C = (size_t)fs->cap;
     if (match) *match = b->h_match + set * S * C;
     if (nmatches) *nmatches = b->h_n + set * S;
-    if (npairs) *npairs = b->lastPairs[set];
+    if (npairs) *npairs = r.pairs;
     if (cap) *cap = fs->cap;
     return ORBX_OK;
 }

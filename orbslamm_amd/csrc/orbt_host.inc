@@ -378,6 +378,43 @@ static int proj_core(orbm_handle* h, const OrbmProjParams* pp, const float* q_uv
 struct orbm_frameset_bow;
 static void frameset_bow_free(struct orbm_frameset* fs);
 
+// One result set of a frame set's searches: its completion event, pair count, the value its flags carry once raised (0: none
+// are -- wait on the event), and the search that filled it, which orbm_track_results runs again when its candidates overflowed.
+// A search takes next(), begin()s the set (it holds none) before it enqueues anything, writes its arguments and enqueues its
+// launches and the event from them, and only then commit()s: a failed call leaves the previous search the newest.
+struct ResultRecord {
+    enum Kind { kNone, kFramePairs, kQueries };
+    Kind kind = kNone;
+    hipEvent_t ev = nullptr;
+    int pairs = 0; int32_t flagValue = 0;
+    OrbmProjParams pp{};
+    uint32_t builds = 0;   // the frame set's build count when the search was issued: a slot stamped later has been rebuilt since
+    // frame pairs: th and the slot pairs
+    float th = 0;
+    std::vector<int32_t> cur, last;
+    // queries: train slot, query slot (-1: queries from the host); the set's staging block (its share of h_q, ProjPair first,
+    // `total` bytes) as allocated at epoch qEpoch; the launch plan
+    int slot = -1, qslot = -1, nq = 0;
+    uint32_t qEpoch = 0;
+    size_t total = 0;
+    ProjPlan plan{};
+};
+struct ResultRing {   // kSets result sets in rotation: a caller may read up to kSets - 1 calls behind the newest
+    static constexpr int kSets = 4;
+    ResultRecord rec[kSets];
+    int newest = 0;
+    int next() const { return (newest + 1) % kSets; }
+    int back(int b) const { return (newest + kSets - b) % kSets; }
+    int begin(int set)
+    {
+        rec[set].kind = ResultRecord::kNone; rec[set].pairs = 0; rec[set].flagValue = 0;
+        if (!rec[set].ev) HIPCHK(hipEventCreateWithFlags(&rec[set].ev, hipEventDisableTiming));
+        return ORBX_OK;
+    }
+    void commit(int set, ResultRecord::Kind kind, int pairs, int32_t flagValue) { newest = set; rec[set].kind = kind; rec[set].pairs = pairs; rec[set].flagValue = flagValue; }
+    void destroy() { for (auto& r : rec) if (r.ev) (void)hipEventDestroy(r.ev); }
+};
+
 struct orbm_frameset {
     orbm_frameset_bow* bow = nullptr;   // orbt_bow_host.inc: allocated by the first orbm_frameset_compute_bow
     orbm_handle* owner = nullptr;
@@ -393,32 +430,42 @@ struct orbm_frameset {
     int32_t* d_candOff = nullptr; int32_t* d_candCnt = nullptr; int32_t* d_qres = nullptr; uint8_t* d_occ = nullptr; int32_t* d_total = nullptr; int32_t* d_qscr = nullptr;
     int32_t* d_tscr = nullptr;   // [slots][3 tCap]: the resolve's per-train tables of a set whose frames are too large for the LDS form (ProjCommon::big)
     uint2* d_cand = nullptr; int candCapPair = 0;
-    uint8_t* h_block = nullptr;   // pinned, kResSets result sets: assign[R][slots][cap] | nmatch[R][slots] | stats[R][slots][2]
+    uint8_t* h_block = nullptr;   // pinned, one share per result set (set_tables): assign[R][slots][cap] | nmatch[R][slots] | stats[R][slots][2] | flag[R][slots]
     int32_t* h_assign = nullptr; int32_t* h_nmatch = nullptr; int32_t* h_stats = nullptr;
-    static constexpr int kResSets = 4;     // result sets in rotation: a caller may read up to three calls behind the newest
-    int resSet = 0;
-    int lastPairs[kResSets] = {0, 0, 0, 0};
-    hipEvent_t evRes[kResSets] = {nullptr, nullptr, nullptr, nullptr};
+    int32_t* h_flag = nullptr;                 // raised by the resolve behind a pair's results (at most kTrackFlagPairs pairs)
+    ResultRing res;
+    int32_t seq = 0;                           // value the flags of the newest search carry
+    uint32_t builds = 0;                       // frame builds so far
+    std::vector<uint32_t> slotBuilt;           // per slot: the build count that last wrote it
     hipEvent_t evExt[2] = {nullptr, nullptr};  // this set's build has read the extractor's result set s
     std::vector<orbx_handle*> readOf;          // extractors whose evExtReader lists may hold them
     // orbm_frameset_attach: the set's kernels ride on this extractor's own stream, right behind the kernels whose
     // output they read (the live stream: no cross-stream hand-over, no host hop between Frame::Frame and the search)
     orbx_handle* liveEx = nullptr;
-    int32_t* h_flag = nullptr;                 // [kResSets][slots] pinned: raised by the resolve behind a pair's results
-    int32_t seq = 0;                           // value the flags of the newest search carry
-    int32_t flagSeq[kResSets] = {0, 0, 0, 0};
-    // the arguments of the search each result set holds: a search whose candidates overflow the arena (a frame far denser than
-    // 64 candidates per feature) is re-issued by orbm_track_results with a larger one -- the reference's loop takes any number
-    // (a slot may have been rebuilt by a later frame since -- callers that run tickets deep --: every build stamps its slots with a
-    // generation, the call remembers those it searched, and a retry over slots that moved on is refused instead of run)
-    struct Call { bool valid = false; OrbmProjParams pp{}; float th = 0; std::vector<int32_t> cur, last; std::vector<uint32_t> genCur, genLast; } call[kResSets];
-    std::vector<uint32_t> slotGen;             // per slot: how many times it has been built
-    // orbm_track_local_points: one pinned block + its device twin per result set (pair record | queries | occupancy)
+    // the query searches: one pinned block + its device twin per result set (pair record | queries | occupancy); qEpoch counts
+    // their allocations (a larger local map than any before reallocates all four)
     uint8_t* h_q = nullptr; uint8_t* d_q = nullptr; size_t qBytes = 0;   // per set
+    uint32_t qEpoch = 0;
 };
 
 // the stream a frame set's kernels are enqueued on
 static inline hipStream_t fs_stream(const orbm_frameset* fs) { return fs->liveEx ? fs->liveEx->streamP[0] : fs->owner->stream; }
+
+// result set `set`'s share of the pinned tables: assign[slots][cap], nmatch[slots], stats[slots][2], flag[slots]
+struct SetTables { int32_t *assign, *nmatch, *stats, *flag; };
+static inline SetTables set_tables(const orbm_frameset* fs, int set)
+{
+    const size_t S = (size_t)fs->slots, C = (size_t)fs->cap;
+    return {fs->h_assign + set * S * C, fs->h_nmatch + set * S, fs->h_stats + set * S * 2, fs->h_flag + set * S};
+}
+
+// every pair of the set's search has raised its flag (a search without flags never has)
+static inline bool flags_raised(const ResultRecord& r, const int32_t* flag)
+{
+    bool up = r.flagValue != 0;
+    for (int p = 0; p < r.pairs && up; p++) up = ((const volatile int32_t*)flag)[p] == r.flagValue;
+    return up;
+}
 
 extern "C" int orbm_frameset_destroy(orbm_frameset_t* fs)
 {
@@ -434,7 +481,7 @@ extern "C" int orbm_frameset_destroy(orbm_frameset_t* fs)
         if (fs->h_block) (void)hipHostFree(fs->h_block);
         if (fs->h_q) (void)hipHostFree(fs->h_q);
         if (fs->d_q) (void)hipFree(fs->d_q);
-        for (auto e : fs->evRes) if (e) (void)hipEventDestroy(e);
+        fs->res.destroy();
         for (auto e : fs->evExt) {
             if (!e) continue;
             for (orbx_handle* x : fs->readOf)
@@ -461,8 +508,8 @@ extern "C" int orbm_frameset_create(orbm_t* h, int slots, int cap, const float K
     const bool bigSet = plan0.c.big != 0;   // frames beyond the LDS form: general-size build, tables in memory (slower; the reference has no bound)
     *out = nullptr;
     orbm_frameset* f = new orbm_frameset;
-    f->slotGen.assign((size_t)slots, 0u);
-    for (auto& c : f->call) { c.cur.reserve((size_t)slots); c.last.reserve((size_t)slots); c.genCur.reserve((size_t)slots); c.genLast.reserve((size_t)slots); }   // no allocation in the per-frame path
+    f->slotBuilt.assign((size_t)slots, 0u);
+    for (auto& r : f->res.rec) { r.cur.reserve((size_t)slots); r.last.reserve((size_t)slots); }   // no allocation in the per-frame path
     f->owner = h; f->device = h->device; f->slots = slots; f->cap = cap; f->ncell = grid->cols * grid->rows; f->nlevels = nlevels;
     f->gd = {grid->minX, grid->minY, grid->invW, grid->invH, grid->cols, grid->rows};
     f->und = {K[0], K[1], K[2], K[3], D[0], D[1], D[2], D[3], D[4]};
@@ -476,7 +523,7 @@ extern "C" int orbm_frameset_create(orbm_t* h, int slots, int cap, const float K
     const size_t oTs = bigSet ? pk.take(S * (size_t)plan0.c.tCap * 12) : 0;
     f->candCapPair = (int)std::max<size_t>(C * 64, 1 << 16);
     Packer hp;
-    const size_t R = orbm_frameset::kResSets;
+    const size_t R = ResultRing::kSets;
     const size_t hA = hp.take(R * S * C * 4), hN = hp.take(R * S * 4), hS = hp.take(R * S * 8), hF = hp.take(R * S * 4);
 #define FSC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { int r_ = fail(ORBX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); orbm_frameset_destroy(f); return r_; } } while (0)
     FSC(hipMalloc(&f->d_block, pk.off));
@@ -510,16 +557,18 @@ static int frameset_check(orbm_frameset* fs)
     return orbm_check(fs->owner);
 }
 
-static int frameset_build(orbm_frameset* fs, int slot0, int n, const OrbxKeyPoint* d_keys, const uint8_t* d_desc,
-                          const int32_t* d_counts, int src_cap)
+// the arguments of a build of n frames into slots (slot0 + i) % slots, which it stamps with the new build count
+static orbt::FrameBuildArgs frameset_build_args(orbm_frameset* fs, int slot0, int n, const OrbxKeyPoint* d_keys, const uint8_t* d_desc,
+                                                const int32_t* d_counts, int src_cap)
 {
     orbt::FrameBuildArgs fa{};
     fa.fs = fs->fs;
     fa.srcKeys = (const orbm::KeyDev*)d_keys; fa.srcDesc = d_desc; fa.srcCount = d_counts; fa.srcCap = src_cap; fa.srcN = 0;
     fa.slot0 = slot0; fa.slotMod = fs->slots;
     fa.grid = fs->gd; fa.und = fs->und; fa.undistort = fs->undistort;
-    for (int i = 0; i < n; i++) fs->slotGen[(size_t)((slot0 + i) % fs->slots)]++;
-    return frame_build_launch(fs->owner, fa, n, fs_stream(fs));
+    fs->builds++;
+    for (int i = 0; i < n; i++) fs->slotBuilt[(size_t)((slot0 + i) % fs->slots)] = fs->builds;
+    return fa;
 }
 
 extern "C" int orbm_frameset_build(orbm_frameset_t* fs, int slot0, int n, const OrbxKeyPoint* d_keys, const uint8_t* d_desc,
@@ -531,7 +580,7 @@ extern "C" int orbm_frameset_build(orbm_frameset_t* fs, int slot0, int n, const 
         return fail(ORBX_E_INVALID, "bad argument");
     if ((uintptr_t)d_desc & 15) return fail(ORBX_E_INVALID, "descriptors must be 16-byte aligned");
     if (n == 0) return ORBX_OK;
-    return frameset_build(fs, slot0, n, d_keys, d_desc, d_counts, src_cap);
+    return frame_build_launch(fs->owner, frameset_build_args(fs, slot0, n, d_keys, d_desc, d_counts, src_cap), n, fs_stream(fs));
 }
 
 // the frames of the extractor's last batch, ordered behind its kernels on the device; the extractor will not overwrite
@@ -551,25 +600,18 @@ extern "C" int orbm_frameset_build_from_extractor(orbm_frameset_t* fs, int slot0
     // (an event between two kernels of a chain costs ~5 us of gap, tools/live_timeline.sh)
     const bool sameStream = fs->liveEx == ex && ex->lastLat;
     if (!sameStream && ((rc = flush_pack(ex)) || (rc = join_parts(ex, ms)))) return rc;
+    const orbt::FrameBuildArgs fa = frameset_build_args(fs, slot0, B, (const OrbxKeyPoint*)(r_kps(ex, set) + ex->maxKp), r_desc(ex, set) + (size_t)ex->maxKp * 32,
+                                                        r_count(ex, set) + 1, ex->maxKp);
     if (sameStream && ex->packPending && ex->packB == B && frame_build_fits_lds(fs->fs.cap, fs->fs.ncell)) {
         // the ticket's results go to the host from the build's own launch (k_frame_build_pack)
-        orbt::FrameBuildArgs fa{};
-        fa.fs = fs->fs;
-        fa.srcKeys = (const orbm::KeyDev*)(r_kps(ex, set) + ex->maxKp); fa.srcDesc = r_desc(ex, set) + (size_t)ex->maxKp * 32;
-        fa.srcCount = r_count(ex, set) + 1; fa.srcCap = ex->maxKp; fa.srcN = 0;
-        fa.slot0 = slot0; fa.slotMod = fs->slots;
-        fa.grid = fs->gd; fa.und = fs->und; fa.undistort = fs->undistort;
         const size_t lds = (size_t)fa.fs.ncell * 8 + (size_t)align_up(fa.fs.cap, 2) * 14;
         if ((rc = lds_attr((const void*)orbt::k_frame_build_pack, lds, fs->owner->ldsAttr[7]))) return rc;
         ex->packPending = false;
-        for (int i = 0; i < B; i++) fs->slotGen[(size_t)((slot0 + i) % fs->slots)]++;
         hipLaunchKernelGGL(orbt::k_frame_build_pack, dim3(B * (1 + orbt::kPackParts)), dim3(orbt::kThreads), lds, ms, fa, ex->packPa, B);
         HIPCHK(hipGetLastError());
         return ORBX_OK;
     }
-    if ((rc = flush_pack(ex))) return rc;
-    if ((rc = frameset_build(fs, slot0, B, (const OrbxKeyPoint*)(r_kps(ex, set) + ex->maxKp), r_desc(ex, set) + (size_t)ex->maxKp * 32,
-                             r_count(ex, set) + 1, ex->maxKp))) return rc;
+    if ((rc = flush_pack(ex)) || (rc = frame_build_launch(fs->owner, fa, B, ms))) return rc;
     if (sameStream) return ORBX_OK;
     if (!fs->evExt[set]) HIPCHK(hipEventCreateWithFlags(&fs->evExt[set], hipEventDisableTiming));
     HIPCHK(hipEventRecord(fs->evExt[set], ms));
@@ -625,47 +667,44 @@ extern "C" int orbm_frameset_download(orbm_frameset_t* fs, int slot, OrbxKeyPoin
 // LastFrame feature is a query (as if it held a MapPoint with observations), projected with the identity pose.
 // Asynchronous, uploads nothing (the pair records are made on the device from the slot numbers); results alternate
 // between four pinned result sets so that a caller can read call n-1 .. n-3 while call n runs.
-// the launches of one frame-to-frame search into result set `set` (+ its event); allowFlags: the few-pairs flag protocol
-static int track_frames_issue(orbm_frameset_t* fs, const OrbmProjParams* pp, float th, const int32_t* cur_slots,
-                              const int32_t* last_slots, int npairs, int set, bool allowFlags)
+// the launches of the frame-to-frame search that result set `set`'s record holds (+ the set's event); flags: the few-pairs
+// flag protocol, its flags carry fs->seq + 1
+static int track_frames_issue(orbm_frameset_t* fs, int set, bool flags)
 {
     int rc;
     orbm_handle* h = fs->owner;
     hipStream_t st = fs_stream(fs);
-    if (!fs->evRes[set]) HIPCHK(hipEventCreateWithFlags(&fs->evRes[set], hipEventDisableTiming));
-    // few pairs (a live stream): every resolve workgroup raises a flag behind its results, orbm_track_results polls it
-    const bool flags = allowFlags && npairs > 0 && npairs <= kTrackFlagPairs;
+    const ResultRecord& r = fs->res.rec[set];
+    const int npairs = (int)r.cur.size();
     if (npairs) {
         ProjPlan pl{};
-        if ((rc = proj_lds_plan(fs->cap, fs->cap, fs->ncell, pl, th > 20.f ? 72 : 32))) return rc;  // th = 15: ~12 per query listed, th = 30: ~45
+        if ((rc = proj_lds_plan(fs->cap, fs->cap, fs->ncell, pl, r.th > 20.f ? 72 : 32))) return rc;  // th = 15: ~12 per query listed, th = 30: ~45
         orbt::ProjCommon& c = pl.c;
-        c.mode = 4; c.nnratio = pp->nnratio; c.checkOri = pp->check_ori; c.thDist = pp->th_dist;
+        c.mode = 4; c.nnratio = r.pp.nnratio; c.checkOri = r.pp.check_ori; c.thDist = r.pp.th_dist;
         c.scale = fs->d_scale; c.nlevels = fs->nlevels;
         c.interleave = npairs <= 4;
         if (!c.big) c.lanes = cand_lanes(npairs);
         if ((rc = lds_attr((const void*)orbt::k_track_candidates, pl.ldsCand, h->ldsAttr[3])) ||
             (rc = lds_attr((const void*)orbt::k_track_resolve, pl.ldsResolve, h->ldsAttr[4]))) return rc;
-        const size_t C = (size_t)fs->cap, S = (size_t)fs->slots;
+        const SetTables t = set_tables(fs, set);
         orbt::TrackArgs a{};
         a.fs = fs->fs; a.grid = fs->gd;
-        a.th = th; a.minX = fs->bounds[0]; a.maxX = fs->bounds[1]; a.minY = fs->bounds[2]; a.maxY = fs->bounds[3];
-        a.occ = fs->d_occ; a.assign = fs->h_assign + set * S * C; a.nmatch = fs->h_nmatch + set * S; a.stats = fs->h_stats + set * S * 2;
+        a.th = r.th; a.minX = fs->bounds[0]; a.maxX = fs->bounds[1]; a.minY = fs->bounds[2]; a.maxY = fs->bounds[3];
+        a.occ = fs->d_occ; a.assign = t.assign; a.nmatch = t.nmatch; a.stats = t.stats;
         a.total = fs->d_total; a.candOff = fs->d_candOff; a.candCnt = fs->d_candCnt; a.cand = fs->d_cand; a.candCap = fs->candCapPair; a.qres = fs->d_qres; a.qscr = fs->d_qscr; a.tscr = c.big ? fs->d_tscr : nullptr;
-        a.flag = flags ? fs->h_flag + set * S : nullptr; a.flagValue = fs->seq + 1;
+        a.flag = flags ? t.flag : nullptr; a.flagValue = fs->seq + 1;
         const int perSlice = orbt::kCandThreads / c.lanes;
         const int slices = (fs->cap + perSlice - 1) / perSlice;
         for (int p0 = 0; p0 < npairs; p0 += orbt::kTrackMaxPairs) {
             const int nb = std::min(orbt::kTrackMaxPairs, npairs - p0);
             a.pair0 = p0;
-            for (int i = 0; i < nb; i++) { a.cur[i] = (int16_t)cur_slots[p0 + i]; a.last[i] = (int16_t)last_slots[p0 + i]; }
+            for (int i = 0; i < nb; i++) { a.cur[i] = (int16_t)r.cur[(size_t)(p0 + i)]; a.last[i] = (int16_t)r.last[(size_t)(p0 + i)]; }
             hipLaunchKernelGGL(orbt::k_track_candidates, dim3(slices, nb), dim3(orbt::kCandThreads), pl.ldsCand, st, a, c);
             hipLaunchKernelGGL(orbt::k_track_resolve, dim3(nb), dim3(orbt::kThreads), pl.ldsResolve, st, a, c);
         }
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(fs->evRes[set], st));
-    fs->lastPairs[set] = npairs;
-    fs->flagSeq[set] = flags ? ++fs->seq : 0;
+    HIPCHK(hipEventRecord(r.ev, st));
     return ORBX_OK;
 }
 
@@ -679,17 +718,32 @@ extern "C" int orbm_track_frames(orbm_frameset_t* fs, const OrbmProjParams* pp, 
     for (int p = 0; p < npairs; p++)
         if (cur_slots[p] < 0 || cur_slots[p] >= fs->slots || last_slots[p] < 0 || last_slots[p] >= fs->slots)
             return fail(ORBX_E_INVALID, "slot outside the frame set");
-    const int set = (fs->resSet + 1) % orbm_frameset::kResSets;
-    fs->call[set].valid = false;
-    if ((rc = track_frames_issue(fs, pp, th, cur_slots, last_slots, npairs, set, true))) return rc;
-    // the result set rotates only now that its launches and its event are in the queue (a failed call leaves the
-    // previous search's tables the newest)
-    fs->resSet = set;
-    orbm_frameset::Call& c = fs->call[set];
-    c.pp = *pp; c.th = th; c.cur.assign(cur_slots, cur_slots + npairs); c.last.assign(last_slots, last_slots + npairs);
-    c.genCur.resize((size_t)npairs); c.genLast.resize((size_t)npairs);
-    for (int p = 0; p < npairs; p++) { c.genCur[(size_t)p] = fs->slotGen[(size_t)cur_slots[p]]; c.genLast[(size_t)p] = fs->slotGen[(size_t)last_slots[p]]; }
-    c.valid = true;
+    const int set = fs->res.next();
+    if ((rc = fs->res.begin(set))) return rc;
+    ResultRecord& r = fs->res.rec[set];
+    r.pp = *pp; r.builds = fs->builds; r.th = th; r.cur.assign(cur_slots, cur_slots + npairs); r.last.assign(last_slots, last_slots + npairs);
+    // few pairs (a live stream): every resolve workgroup raises a flag behind its results, orbm_track_results polls it
+    const bool flags = npairs > 0 && npairs <= kTrackFlagPairs;
+    if ((rc = track_frames_issue(fs, set, flags))) return rc;
+    fs->res.commit(set, ResultRecord::kFramePairs, npairs, flags ? ++fs->seq : 0);
+    return ORBX_OK;
+}
+
+// a query search lists into the whole arena
+static inline void query_arena(const orbm_frameset* fs, orbt::ProjPair& P) { P.cand = fs->d_cand; P.candCap = (int)std::min<size_t>((size_t)fs->slots * fs->candCapPair, 0x7FFFFFFF); }
+
+// the launches of the query search that result set `set`'s record holds (+ the set's event): its staging block goes up through
+// the copy kernel of the live chain (orbx::k_upload: the DMA engine's completion reaches the compute queue ~20 us after the
+// copy's end, a kernel's successor follows it at once), the search follows
+static int track_queries_issue(orbm_frameset_t* fs, int set)
+{
+    int rc;
+    const ResultRecord& r = fs->res.rec[set];
+    hipStream_t st = fs_stream(fs);
+    uint8_t* ds = fs->d_q + (size_t)set * fs->qBytes;
+    hipLaunchKernelGGL(k_upload, dim3((unsigned)((r.total / 16 + 255) / 256)), dim3(256), 0, st, (const uint4*)(fs->h_q + (size_t)set * fs->qBytes), (uint4*)ds, (int)(r.total / 16));
+    if ((rc = proj_launch(fs->owner, (const orbt::ProjPair*)ds, 1, r.nq, r.plan, st))) return rc;
+    HIPCHK(hipEventRecord(r.ev, st));
     return ORBX_OK;
 }
 
@@ -710,31 +764,30 @@ static int track_queries(orbm_frameset_t* fs, int slot, int qslot, const OrbmPro
     const size_t C = (size_t)fs->cap, S = (size_t)fs->slots;
     if ((size_t)nq > S * C || nq > orbt::kMaxQueryIters * orbt::kThreads)
         return fail(ORBX_E_UNSUPPORTED, "%d queries: the set's scratch holds slots x cap = %zu", nq, S * C);
-    orbm_handle* h = fs->owner;
-    hipStream_t st = fs_stream(fs);
-    const int set = (fs->resSet + 1) % orbm_frameset::kResSets;
-    if (!fs->evRes[set]) HIPCHK(hipEventCreateWithFlags(&fs->evRes[set], hipEventDisableTiming));
+    const int set = fs->res.next();
+    ResultRecord& r = fs->res.rec[set];
     Packer pk;
     const size_t oPair = pk.take(sizeof(orbt::ProjPair));
     const size_t oUvr = pk.take((size_t)nq * 12), oLvl = pk.take((size_t)nq * 2), oQd = qslot < 0 ? pk.take((size_t)nq * 32) : 0;
     const size_t oQv = qvalid ? pk.take((size_t)nq) : 0, oQo = q_obs_pos ? pk.take((size_t)nq) : 0, oOcc = t_occ ? pk.take(C) : 0;
     const size_t total = pk.off;
     if (total > fs->qBytes) {   // (first call, or a larger local map than any before: the only allocation, behind a drain)
-        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipStreamSynchronize(fs_stream(fs)));
         if (fs->h_q) HIPCHK(hipHostFree(fs->h_q));
         if (fs->d_q) HIPCHK(hipFree(fs->d_q));
         fs->h_q = nullptr; fs->d_q = nullptr; fs->qBytes = 0;
+        fs->qEpoch++;
         const size_t want = (total * 3 / 2 + 4095) & ~(size_t)4095;
-        HIPCHK(hipHostMalloc(&fs->h_q, want * orbm_frameset::kResSets, hipHostMallocCoherent));   // (read by the copy kernel where it lies)
-        HIPCHK(hipMalloc(&fs->d_q, want * orbm_frameset::kResSets));
+        HIPCHK(hipHostMalloc(&fs->h_q, want * ResultRing::kSets, hipHostMallocCoherent));   // (read by the copy kernel where it lies)
+        HIPCHK(hipMalloc(&fs->d_q, want * ResultRing::kSets));
         fs->qBytes = want;
-    } else {
-        // the search that last read this set's block (four calls ago) must be through: its flag says so without a
-        // runtime call (an event query costs tens of microseconds)
-        const bool flagged = fs->flagSeq[set] && fs->lastPairs[set] == 1 && ((volatile int32_t*)fs->h_flag)[set * S] == fs->flagSeq[set];
-        if (!flagged) HIPCHK(hipEventSynchronize(fs->evRes[set]));
+    } else if (r.ev && !flags_raised(r, set_tables(fs, set).flag)) {
+        // the search that last read this set's block (four calls ago) must be through: its flags say so without a runtime
+        // call (an event query costs tens of microseconds)
+        HIPCHK(hipEventSynchronize(r.ev));
     }
-    ProjPlan pl{};
+    if ((rc = fs->res.begin(set))) return rc;
+    ProjPlan& pl = r.plan;
     if ((rc = proj_lds_plan(fs->cap, nq, fs->ncell, pl))) return rc;
     orbt::ProjCommon& c = pl.c;
     c.mode = pp->mode; c.nnratio = pp->nnratio; c.thDist = pp->th_dist;
@@ -749,6 +802,7 @@ static int track_queries(orbm_frameset_t* fs, int slot, int qslot, const OrbmPro
     if (qvalid) memcpy(hs + oQv, qvalid, (size_t)nq);
     if (q_obs_pos) memcpy(hs + oQo, q_obs_pos, (size_t)nq);
     if (t_occ) memcpy(hs + oOcc, t_occ, C);
+    const SetTables t = set_tables(fs, set);
     orbt::ProjPair P{};
     const int64_t cs = slot;
     P.grid = fs->gd;
@@ -761,22 +815,13 @@ static int track_queries(orbm_frameset_t* fs, int slot, int qslot, const OrbmPro
     P.qur = nullptr; P.turight = nullptr; P.qkeys = nullptr;
     P.nqPtr = qslot < 0 ? nullptr : fs->fs.n + qslot; P.nq = nq;   // (never more queries than the slot holds features)
     P.toccIn = t_occ ? ds + oOcc : nullptr; P.toccOut = fs->d_occ;
-    P.assign = fs->h_assign + set * S * C; P.initAssign = 1;
-    P.nmatch = fs->h_nmatch + set * S;
-    P.total = fs->d_total;
-    P.candOff = fs->d_candOff; P.candCnt = fs->d_candCnt; P.cand = fs->d_cand; P.candCap = (int)std::min<size_t>(S * (size_t)fs->candCapPair, 0x7FFFFFFF);
-    P.qres = fs->d_qres; P.qscr = fs->d_qscr; P.stats = fs->h_stats + set * S * 2;
-    P.tscr = c.big ? fs->d_tscr : nullptr;
-    P.flag = fs->h_flag + set * S; P.flagValue = fs->seq + 1;
+    P.assign = t.assign; P.initAssign = 1; P.nmatch = t.nmatch; P.stats = t.stats; P.flag = t.flag; P.flagValue = fs->seq + 1;
+    P.total = fs->d_total; P.candOff = fs->d_candOff; P.candCnt = fs->d_candCnt; query_arena(fs, P);
+    P.qres = fs->d_qres; P.qscr = fs->d_qscr; P.tscr = c.big ? fs->d_tscr : nullptr;
     memcpy(hs + oPair, &P, sizeof P);
-    // the block goes up through the copy kernel of the live chain (orbx::k_upload): the DMA engine's completion reaches the
-    // compute queue ~20 us after the copy's end, a kernel's successor follows it at once
-    hipLaunchKernelGGL(k_upload, dim3((unsigned)((total / 16 + 255) / 256)), dim3(256), 0, st, (const uint4*)hs, (uint4*)ds, (int)(total / 16));
-    if ((rc = proj_launch(h, (const orbt::ProjPair*)(ds + oPair), 1, nq, pl, st))) return rc;
-    HIPCHK(hipEventRecord(fs->evRes[set], st));
-    fs->resSet = set;
-    fs->lastPairs[set] = 1;
-    fs->flagSeq[set] = ++fs->seq;
+    r.pp = *pp; r.builds = fs->builds; r.slot = slot; r.qslot = qslot; r.nq = nq; r.total = total; r.qEpoch = fs->qEpoch;
+    if ((rc = track_queries_issue(fs, set))) return rc;
+    fs->res.commit(set, ResultRecord::kQueries, 1, ++fs->seq);
     return ORBX_OK;
 }
 
@@ -798,42 +843,43 @@ extern "C" int orbm_track_frame_projected(orbm_frameset_t* fs, int cur_slot, int
     return track_queries(fs, cur_slot, last_slot, pp, q_uvr, q_lvl, nullptr, qvalid, q_obs_pos, nq, t_occ);
 }
 
-// waits for the last (back = 0) or an earlier (back = 1 .. 3) orbm_track_frames; views into the frame set's pinned
-// result block (valid until three more calls have been issued): assign[p * cap + t] = LastFrame feature matched to CurrentFrame
-// feature t or -1
+// waits for the last (back = 0) or an earlier (back = 1 .. 3) search; views into the frame set's pinned result block (valid
+// until three more calls have been issued): assign[p * cap + t] = LastFrame feature matched to CurrentFrame feature t or -1
 extern "C" int orbm_track_results(orbm_frameset_t* fs, int back, const int32_t** assign, const int32_t** nmatches, int* npairs, int* cap)
 {
     int rc = frameset_check(fs);
     if (rc) return rc;
-    if (back < 0 || back >= orbm_frameset::kResSets) return fail(ORBX_E_INVALID, "back must be 0 .. %d", orbm_frameset::kResSets - 1);
-    const int set = (fs->resSet + orbm_frameset::kResSets - back) % orbm_frameset::kResSets;
-    if (!fs->evRes[set]) return fail(ORBX_E_INVALID, "no such search has been issued");
-    const size_t C = (size_t)fs->cap, S = (size_t)fs->slots;
+    if (back < 0 || back >= ResultRing::kSets) return fail(ORBX_E_INVALID, "back must be 0 .. %d", ResultRing::kSets - 1);
+    const int set = fs->res.back(back);
+    ResultRecord& r = fs->res.rec[set];
+    if (!r.ev) return fail(ORBX_E_INVALID, "no such search has been issued");
+    const SetTables t = set_tables(fs, set);
+    const size_t S = (size_t)fs->slots;
     bool landed = false;
-    if (fs->flagSeq[set]) {
-        volatile int32_t* fl = (volatile int32_t*)(fs->h_flag + set * S);
-        const int want = fs->flagSeq[set], np = fs->lastPairs[set];
-        for (int spin = 0; spin < 400000 && !landed; spin++) {
-            landed = true;
-            for (int p = 0; p < np; p++) landed &= fl[p] == want;
-            if (!landed) cpu_relax();
-        }
+    if (r.flagValue) {
+        for (int spin = 0; spin < 400000 && !(landed = flags_raised(r, t.flag)); spin++) cpu_relax();
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
     }
-    if (!landed) HIPCHK(hipEventSynchronize(fs->evRes[set]));
-    const int32_t* nm = fs->h_nmatch + set * S;
+    if (!landed) HIPCHK(hipEventSynchronize(r.ev));
     int need = 0;
-    for (int p = 0; p < fs->lastPairs[set]; p++)
-        if (nm[p] < 0) need = std::max(need, -nm[p] - 1);
-    if (need > 0 && fs->call[set].valid) {
+    for (int p = 0; p < r.pairs; p++)
+        if (t.nmatch[p] < 0) need = std::max(need, -t.nmatch[p] - 1);
+    if (need > 0 && r.kind != ResultRecord::kNone) {
         // a pair's candidates did not fit the arena (64 per feature; the kernels count what they could not list and write
-        // nothing past it): grow it and run this search again into the same result set -- slow path, allocates
-        const orbm_frameset::Call c = fs->call[set];
-        for (size_t p = 0; p < c.cur.size(); p++)
-            if (fs->slotGen[(size_t)c.cur[p]] != c.genCur[p] || fs->slotGen[(size_t)c.last[p]] != c.genLast[p])
-                return fail(ORBX_E_CAPACITY, "pair %zu: its candidates exceed the arena of %d and slot %d or %d has been rebuilt since the search was issued: "
-                                             "it cannot be run again -- read a search's results before its frames' slots are reused, or search fewer pairs per call",
-                            p, fs->candCapPair, c.cur[p], c.last[p]);
+        // nothing past it): grow it and run the search this set's record holds again, into the same set -- slow path, allocates.
+        // Refused when a slot it read has been rebuilt by a later frame since (callers that run tickets deep: every build
+        // stamps its slots with a generation), or a query search's staging block has been reallocated by a larger one.
+        auto rebuilt = [&](int slot) { return slot >= 0 && fs->slotBuilt[(size_t)slot] > r.builds; };
+        bool moved = false;
+        if (r.kind == ResultRecord::kFramePairs) {
+            for (size_t p = 0; p < r.cur.size(); p++) moved |= rebuilt(r.cur[p]) || rebuilt(r.last[p]);
+        } else {
+            moved = rebuilt(r.slot) || rebuilt(r.qslot) || r.qEpoch != fs->qEpoch;
+            need = (int)((need + S - 1) / S);   // (the query search lists into the whole arena: size each pair's share)
+        }
+        if (moved)
+            return fail(ORBX_E_CAPACITY, "the search's candidates exceed the arena and a slot it read has been rebuilt (or its staging block reallocated) since it was "
+                                         "issued: it cannot be run again -- read a search's results before its slots are reused, or search fewer pairs per call");
         HIPCHK(hipStreamSynchronize(fs_stream(fs)));
         const size_t newCap = (size_t)need + (size_t)need / 4 + 1024;
         if (newCap * S * 8 > ((size_t)1 << 32)) return fail(ORBX_E_CAPACITY, "%d candidates per pair are more than the frame set can list", need);
@@ -841,14 +887,20 @@ extern "C" int orbm_track_results(orbm_frameset_t* fs, int back, const int32_t**
         HIPCHK(hipMalloc(&bigger, S * newCap * 8));
         HIPCHK(hipFree(fs->d_cand));
         fs->d_cand = bigger; fs->candCapPair = (int)newCap;
-        if ((rc = track_frames_issue(fs, &c.pp, c.th, c.cur.data(), c.last.data(), (int)c.cur.size(), set, false))) return rc;
-        HIPCHK(hipEventSynchronize(fs->evRes[set]));
+        if (r.kind == ResultRecord::kFramePairs) {
+            if ((rc = track_frames_issue(fs, set, false))) return rc;
+            r.flagValue = 0;
+        } else {   // (only the search that takes a set writes its staging block: only the arena in its pair record changes)
+            query_arena(fs, *(orbt::ProjPair*)(fs->h_q + (size_t)set * fs->qBytes));
+            if ((rc = track_queries_issue(fs, set))) return rc;
+        }
+        HIPCHK(hipEventSynchronize(r.ev));
     }
-    for (int p = 0; p < fs->lastPairs[set]; p++)
-        if (nm[p] < 0) return fail(ORBX_E_CAPACITY, "pair %d: %d candidates exceed the arena of %d", p, -nm[p] - 1, fs->candCapPair);
-    if (assign) *assign = fs->h_assign + set * S * C;
-    if (nmatches) *nmatches = nm;
-    if (npairs) *npairs = fs->lastPairs[set];
+    for (int p = 0; p < r.pairs; p++)
+        if (t.nmatch[p] < 0) return fail(ORBX_E_CAPACITY, "pair %d: %d candidates exceed the arena of %d", p, -t.nmatch[p] - 1, fs->candCapPair);
+    if (assign) *assign = t.assign;
+    if (nmatches) *nmatches = t.nmatch;
+    if (npairs) *npairs = r.pairs;
     if (cap) *cap = fs->cap;
     return ORBX_OK;
 }
@@ -858,9 +910,10 @@ extern "C" int orbm_track_stats(orbm_frameset_t* fs, int pair, int* rounds, int*
 {
     int rc = frameset_check(fs);
     if (rc) return rc;
-    if (pair < 0 || pair >= fs->lastPairs[fs->resSet] || !fs->evRes[fs->resSet]) return fail(ORBX_E_INVALID, "bad argument");
-    HIPCHK(hipEventSynchronize(fs->evRes[fs->resSet]));
-    const int32_t* st = fs->h_stats + (size_t)fs->resSet * fs->slots * 2;
+    const ResultRecord& r = fs->res.rec[fs->res.newest];
+    if (pair < 0 || pair >= r.pairs || !r.ev) return fail(ORBX_E_INVALID, "bad argument");
+    HIPCHK(hipEventSynchronize(r.ev));
+    const int32_t* st = set_tables(fs, fs->res.newest).stats;
     if (rounds) *rounds = st[2 * pair];
     if (candidates) *candidates = st[2 * pair + 1];
     return ORBX_OK;

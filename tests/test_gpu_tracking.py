@@ -399,14 +399,11 @@ def test_track_with_projections_from_the_host(gpu, oracle):
     fs.close(); m.close(); gex.close()
 
 
-def test_frame_to_frame_search_regrows_its_candidate_arena(gpu, oracle):
-    """A small, dense frame (2 400 features on 401 x 263) searched against itself with a wide window (th = 60) lists far
-    more than the arena's 64 candidates per feature: orbm_track_results grows the arena and runs the search again (it used to
-    return ORBX_E_CAPACITY -- found by tests/soak/fuzz_frontend.py); the table equals the sequential oracle's."""
-    from orbslamm_amd import ORBextractor, ORBmatcher, make_grid, synth
+def _dense_periodic_scene(oracle):
+    """A small, dense pair of frames (2 400 features on 401 x 263) of a periodic texture: every corner looks like every other,
+    so all the spatial neighbours of a query survive the Hamming threshold and are listed"""
+    from orbslamm_amd import ORBextractor, make_grid
     w, h, nf, B = 401, 263, 2400, 2
-    # a periodic texture: every corner looks like every other, so all the spatial neighbours of a query survive the Hamming
-    # threshold and are listed
     yy, xx = np.mgrid[0:h + 2, 0:w + 3]
     base = np.where(((yy // 7) + (xx // 7)) % 2 == 0, 40, 210) + np.random.default_rng(12).integers(-2, 3, yy.shape)
     base = np.clip(base, 0, 255).astype(np.uint8)
@@ -422,6 +419,16 @@ def test_frame_to_frame_search_regrows_its_candidate_arena(gpu, oracle):
     bounds = [0.0, float(w), 0.0, float(h)]
     g = make_grid(bounds[0], bounds[2], bounds[1], bounds[3])
     gp = oracle.make_grid_params(bounds[0], bounds[2], bounds[1], bounds[3])
+    return gex, host, sf, K, D, bounds, g, gp
+
+
+def test_frame_to_frame_search_regrows_its_candidate_arena(gpu, oracle):
+    """A small, dense frame (2 400 features on 401 x 263) searched against itself with a wide window (th = 60) lists far
+    more than the arena's 64 candidates per feature: orbm_track_results grows the arena and runs the search again (it used to
+    return ORBX_E_CAPACITY -- found by tests/soak/fuzz_frontend.py); the table equals the sequential oracle's."""
+    from orbslamm_amd import ORBmatcher
+    gex, host, sf, K, D, bounds, g, gp = _dense_periodic_scene(oracle)
+    B = 2
     m = ORBmatcher(0.9, True, device=0)
     fs = m.frame_set(B, gex.max_keypoints, K, D, g, bounds, sf)
     fs.build_from_extractor(0, gex)
@@ -439,6 +446,72 @@ def test_frame_to_frame_search_regrows_its_candidate_arena(gpu, oracle):
         r, cands = fs.stats(0)
         assert cands > 64 * gex.max_keypoints   # the scenario does overflow the initial arena
     fs.close()
+
+
+def test_query_search_overflow_runs_that_search_again(gpu, oracle):
+    """A query search (orbm_track_local_points, orbm_track_frame_projected) whose candidates overflow the arena is run again by
+    orbm_track_results with a larger one -- that search, not the frame-to-frame search its result set held four calls earlier
+    (four result sets: the fifth search after a frame set is created lands in the first one's set).  A query search over a slot
+    rebuilt since, or whose staging block a larger local map has reallocated, is refused instead."""
+    from orbslamm_amd import ORBmatcher, OrbError
+    from orbslamm_amd._lib import ORBX_E_CAPACITY
+    gex, host, sf, K, D, bounds, g, gp = _dense_periodic_scene(oracle)
+    cap = gex.max_keypoints
+    m = ORBmatcher(0.9, True, device=0)
+    (kc, dc), (kl, dl) = host
+    start, idx = oracle.grid_build(gp, kc)
+    free = np.zeros(len(kc), np.uint8)
+    # the frame-to-frame search left in the result set: pair 0 is frame 0 against itself
+    uvr0, lvl0, qv0 = _identity_queries(kc, sf, 60.0, bounds)
+    stale, _, _ = oracle.search_by_projection(4, 0.9, True, 100, uvr0, lvl0, dc, kc["angle"], qv0, None, gp, kc, start, idx, dc,
+                                              free, np.full(len(kc), -1, np.int32))
+
+    def queries(keys):   # every feature a query over most of the frame, half of them dropped
+        uvr = np.stack([keys["x"], keys["y"], np.full(len(keys), 150.0, np.float32)], axis=1).astype(np.float32)
+        lvl = np.stack([keys["octave"] - 1, keys["octave"] + 1], axis=1).astype(np.int8)
+        return uvr, lvl, (np.arange(len(keys)) % 2 == 0).astype(np.uint8)
+
+    def local_points(fs, keys, desc):
+        uvr, lvl, qv = queries(keys)
+        fs.track_local_points(0, uvr, lvl, desc, qv, th_dist=100, nnratio=0.8, mode=3)
+        return oracle.search_by_projection(3, 0.8, False, 100, uvr, lvl, desc, None, qv, None, gp, kc, start, idx, dc, free,
+                                           np.full(len(kc), -1, np.int32))
+
+    def projected(fs):
+        uvr, lvl, qv = queries(kl)
+        fs.track_projected(0, 1, uvr, lvl, qv, th_dist=100, nnratio=0.9, check_ori=True, mode=4)
+        return oracle.search_by_projection(4, 0.9, True, 100, uvr, lvl, dl, kl["angle"], qv, None, gp, kc, start, idx, dc, free,
+                                           np.full(len(kc), -1, np.int32))
+
+    for search in (lambda fs: local_points(fs, kc, dc), projected):   # a fresh set each: the first retry grows the arena
+        fs = m.frame_set(2, cap, K, D, g, bounds, sf)
+        fs.build_from_extractor(0, gex)
+        fs.track([0, 1], [0, 0], th=60.0)      # issued, never read
+        for _ in range(3):
+            fs.track([1], [0], th=5.0)
+        wa, _, wn = search(fs)
+        assert not np.array_equal(wa, stale[:len(kc)])
+        assign, nm = fs.results()
+        assert len(nm) == 1 and nm[0] == wn and np.array_equal(assign[0, :len(kc)], wa), (nm, wn)
+        r, cands = fs.stats(0)
+        assert cands > 2 * 64 * cap   # the query search does overflow the initial arena (slots x 64 per feature)
+        fs.close()
+    # its train slot rebuilt before the results are read: refused
+    fs = m.frame_set(2, cap, K, D, g, bounds, sf)
+    fs.build_from_extractor(0, gex)
+    local_points(fs, kc, dc)
+    fs.build_from_extractor(0, gex)
+    with pytest.raises(OrbError) as e:
+        fs.results()
+    assert e.value.code == ORBX_E_CAPACITY
+    # its staging block reallocated by a larger local map issued behind it: refused
+    fs.build_from_extractor(0, gex)
+    local_points(fs, kc, dc)
+    local_points(fs, np.concatenate([kc, kl]), np.concatenate([dc, dl]))
+    with pytest.raises(OrbError) as e:
+        fs.results(back=1)
+    assert e.value.code == ORBX_E_CAPACITY
+    fs.close(); m.close(); gex.close()
 
 
 def test_search_by_bow_on_the_set_searches_the_root_node_of_a_ragged_tree(gpu, oracle):
