@@ -598,6 +598,81 @@ int orbm_search_for_triangulation_frames(orbm_t* h, orbm_frame_t* f1, const uint
 int orbm_search_for_initialization_frames(orbm_t* h, const float* q_xy, float window_size, orbm_frame_t* f1, orbm_frame_t* f2,
                                           float nnratio, int check_ori, int32_t* matches12, int* nmatches);
 
+/* ---------------------------------------------------------------- keyframe database
+ * replaces KeyFrameDatabase (src/KeyFrameDatabase.cc, identical in both scenarios) and ORBVocabulary::score
+ * (DBoW2 L1Scoring::score, Thirdparty/DBoW2/DBoW2/ScoringObject.cpp).  Results equal the reference bit for bit: the same
+ * keyframes in the same order, the same float scores, the reference's stateful quirks included.
+ * Only L1_NORM scoring (ORBvoc.txt's) is implemented: any other vocabulary is refused with ORBX_E_UNSUPPORTED.
+ *
+ * orbv_score: double ORBVocabulary::score(const BowVector& v1, const BowVector& v2); word ids ascending. */
+int orbv_score(orbv_t* voc, const uint32_t* a_ids, const double* a_vals, int na, const uint32_t* b_ids, const double* b_vals, int nb, double* out);
+
+/* A pool holds keyframes by slot (one per KeyFrame): its mBowVec in HBM and the six query fields of KeyFrame.h:162-167
+ * (mnLoopQuery, mnLoopWords, mLoopScore, mnRelocQuery, mnRelocWords, mRelocScore), which belong to the keyframe and so
+ * persist across queries and across the databases over the pool.  They start at 0 (the reference leaves the two scores
+ * uninitialised: 0.0f is this library's defined choice).  Slots grow on demand: orbk_pool_set_bow on slot s makes slots
+ * [0, s] exist (a slot never given a BowVector has an empty one).  A slot's BowVector cannot change while a database
+ * holds it.  Every pool and database call holds the pool's lock for its duration; calls from any thread are serialised.
+ * orbk_pool_set_bow_from_frameset copies a frame set slot's mBowVec (orbm_frameset_compute_bow) device to device, in
+ *   order with the frame set's stream.  The slot must have been transformed with the pool's vocabulary (else
+ *   ORBX_E_INVALID).  The frame set is a handle of its matcher: as for every call on it, the caller serialises this one
+ *   (and orbk_detect_relocalization_candidates_frameset) with the other calls on the frame set and its matcher.
+ * BowVectors live in an arena that grows: a new BowVector for a slot reuses the slot's range when it fits, else it is
+ *   appended (the old range stays unused); a frame set slot reserves the set's per-frame capacity.
+ * orbk_pool_score: out[i] = (float)score(slot's mBowVec, others[i]'s) -- the minScore loop of LoopClosing::DetectLoop
+ *   (src/LoopClosing.cc:127-147) and MultiMapper::DetectLoop (MultipleRobotsScenario/src/MultiMapper.cc:140-152).
+ * orbk_pool_set_covisibility: the slot's GetBestCovisibilityKeyFrames(10) for orbk_detect_loop_batch and for queries
+ *   given no neighbour callback.
+ * orbk_pool_read_state: the six fields of slots [0, n) (any pointer may be NULL); ORBX_E_CAPACITY when cap < n. */
+typedef struct orbk_pool orbk_pool_t;
+typedef struct orbk_db orbk_db_t;
+int orbk_pool_create(orbv_t* voc, int slots_hint, orbk_pool_t** out);
+void orbk_pool_destroy(orbk_pool_t* pool);
+int orbk_pool_size(orbk_pool_t* pool, int* n_slots);
+int orbk_pool_set_bow(orbk_pool_t* pool, int slot, const uint32_t* word_id, const double* word_value, int n);
+int orbk_pool_set_bow_from_frameset(orbk_pool_t* pool, int slot, orbm_frameset_t* fs, int fs_slot);
+int orbk_pool_score(orbk_pool_t* pool, int slot, const int32_t* others, int n, float* out);
+int orbk_pool_set_covisibility(orbk_pool_t* pool, int slot, const int32_t* best, int n /* <= 10 */);
+int orbk_pool_read_state(orbk_pool_t* pool, uint64_t* reloc_query, int32_t* reloc_words, float* reloc_score,
+                         uint64_t* loop_query, int32_t* loop_words, float* loop_score, int cap);
+
+/* KeyFrameDatabase over a pool: add / erase / clear / size / empty as the reference (add twice = every shared word counts
+ * twice, erase removes the earliest copy, size counts adds minus erases floored at 0, clear keeps that count). */
+int orbk_db_create(orbk_pool_t* pool, orbk_db_t** out);
+void orbk_db_destroy(orbk_db_t* db);
+int orbk_db_add(orbk_db_t* db, int slot);
+int orbk_db_erase(orbk_db_t* db, int slot);
+int orbk_db_clear(orbk_db_t* db);
+int orbk_db_size(orbk_db_t* db, int* n);
+int orbk_db_empty(orbk_db_t* db, int* empty);
+/* lScoreAndMatch of the database's last single query: the scored slots in list order and their float scores */
+int orbk_db_last_scored(orbk_db_t* db, int32_t* slots, float* scores, int cap, int* n);
+
+/* The neighbours of a scored keyframe at the point the reference reads them (pKFi->GetBestCovisibilityKeyFrames(10)):
+ * writes at most 10 pool slots to out and returns how many, or a negative value to abort the query.  It runs while the
+ * pool is locked and must not call into the pool or its databases.  NULL: the pool's covisibility table. */
+typedef int (*orbk_neighbours_fn)(void* user, int32_t slot, int32_t* out);
+
+/* vector<KeyFrame*> DetectRelocalizationCandidates(Frame* F) (src/KeyFrameDatabase.cc:211-303): F->mnId = query_id,
+ * F->mBowVec from host arrays or from a frame set slot.  out: candidate slots in the reference's order; ORBX_E_CAPACITY
+ * with the true count in *n_out when cap is short. */
+int orbk_detect_relocalization_candidates(orbk_db_t* db, uint64_t query_id, const uint32_t* word_id, const double* word_value, int n,
+                                          orbk_neighbours_fn neighbours, void* user, int32_t* out, int cap, int* n_out);
+int orbk_detect_relocalization_candidates_frameset(orbk_db_t* db, uint64_t query_id, orbm_frameset_t* fs, int fs_slot,
+                                                   orbk_neighbours_fn neighbours, void* user, int32_t* out, int cap, int* n_out);
+/* vector<KeyFrame*> DetectLoopCandidates(KeyFrame* pKF, float minScore) (:97-209): pKF = slot, pKF->mnId = query_id,
+ * connected = pKF->GetConnectedKeyFrames() */
+int orbk_detect_loop_candidates(orbk_db_t* db, int slot, uint64_t query_id, const int32_t* connected, int n_connected, float min_score,
+                                orbk_neighbours_fn neighbours, void* user, int32_t* out, int cap, int* n_out);
+/* MultiMapper::DetectLoop's inner scan (MultiMapper.cc:117-157) for n keyframes: minScore from each keyframe's covisible
+ * list (GetVectorCovisibleKeyFrames() without the bad ones, CSR cov_start / cov_idx), then DetectLoopCandidates with the
+ * connected set (CSR conn_start / conn_idx) -- identical to the n queries issued one after another, enqueued with no
+ * host synchronisation in between; neighbours from the pool's covisibility table.  Candidates of query q:
+ * out[out_start[q] .. out_start[q + 1]); ORBX_E_CAPACITY (out_start complete) when out_start[n] > cap. */
+int orbk_detect_loop_batch(orbk_db_t* db, int n, const int32_t* slots, const uint64_t* query_ids,
+                           const int32_t* conn_start, const int32_t* conn_idx, const int32_t* cov_start, const int32_t* cov_idx,
+                           int32_t* out_start, int32_t* out, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,10 +72,18 @@ EXPORTS = [
     "orbm_search_by_bow", "orbm_search_by_projection", "orbm_search_by_projection_stereo", "orbm_projection_prepare", "orbm_features_in_area", "orbm_window_best",
     "orbm_search_for_initialization", "orbm_search_for_triangulation", "orbm_distinctive_descriptors", "orbm_descriptors_to_text", "orbm_descriptors_from_text", "orbm_undistort_keypoints", "orbm_compute_stereo_from_rgbd", "orbm_frame_create", "orbm_frame_destroy", "orbm_frame_size", "orbm_frame_settle",
     "orbm_frame_download_keys_un", "orbm_search_by_projection_frame", "orbm_frame_compute_bow", "orbm_search_by_bow_frames", "orbm_search_for_initialization_frames", "orbm_window_best_frame", "orbm_search_for_triangulation_frames",
-    "orbv_create", "orbv_load_text", "orbv_destroy", "orbv_transform",
+    "orbv_create", "orbv_load_text", "orbv_destroy", "orbv_transform", "orbv_score",
     "orbm_last_search_stats", "orbm_frameset_create", "orbm_frameset_destroy", "orbm_frameset_build", "orbm_frameset_build_from_extractor",
     "orbm_frameset_sync", "orbm_frameset_attach", "orbm_frameset_download", "orbm_track_frames", "orbm_track_local_points", "orbm_track_frame_projected", "orbm_track_results", "orbm_track_stats",
     "orbm_frameset_compute_bow", "orbm_frameset_bow_vector", "orbm_bow_frames", "orbm_bow_results",
+]
+
+# the keyframe database's block of the header (orbk_*)
+EXPORTS_KFDB = [
+    "orbk_pool_create", "orbk_pool_destroy", "orbk_pool_size", "orbk_pool_set_bow", "orbk_pool_set_bow_from_frameset", "orbk_pool_score",
+    "orbk_pool_set_covisibility", "orbk_pool_read_state", "orbk_db_create", "orbk_db_destroy", "orbk_db_add", "orbk_db_erase", "orbk_db_clear",
+    "orbk_db_size", "orbk_db_empty", "orbk_db_last_scored", "orbk_detect_relocalization_candidates",
+    "orbk_detect_relocalization_candidates_frameset", "orbk_detect_loop_candidates", "orbk_detect_loop_batch",
 ]
 
 
@@ -128,7 +136,7 @@ def lib():
         L = C.CDLL(os.environ.get("ORBSLAMM_HIP_LIB") or SO_PATH)
         L.orbx_last_error.restype = C.c_char_p
         L.orbx_scale_factor.restype = C.c_float
-        for name in EXPORTS:
+        for name in EXPORTS + EXPORTS_KFDB:
             getattr(L, name)
         L.orbx_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _lib = L

@@ -19,6 +19,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <deque>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -36,6 +37,7 @@
 #include "orbm_kernels.hip"
 #include "orbt_kernels.hip"
 #include "orbv_kernels.hip"
+#include "orbk_kernels.hip"
 
 using namespace orbx;
 
@@ -175,3 +177,4 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbv_host.inc"   // vocabulary
 
 #include "orbt_bow_host.inc"
+#include "orbk_host.inc"   // keyframe database

@@ -14,6 +14,7 @@ struct orbm_frameset_bow {
     ResultRing res;   // (searches that write no flags and are never run again)
     int maxNodes = 0, P = 2;
     bool computed = false;
+    std::vector<uint64_t> slotVoc;   // per slot: serial of the vocabulary that last transformed it (0: none)
     void* d_gkeys = nullptr;   // sort scratch of the memory form (frames of more than 8192 features)
 };
 
@@ -53,6 +54,7 @@ static int frameset_bow_alloc(orbm_frameset* fs)
     b->d_matched = d + oMa; b->d_hist = (int32_t*)(d + oHi); b->d_match = (int32_t*)(d + oMt); b->d_binOf = d + oBn;
     b->h_match = (int32_t*)(b->h_block + hM); b->h_n = (int32_t*)(b->h_block + hN);
     while (b->P < fs->cap) b->P <<= 1;
+    b->slotVoc.assign(S, 0);
     fs->bow = b;   // (owned by the set from here: a failure below leaves it to orbm_frameset_destroy)
     HIPCHK(hipMemsetAsync(b->d_counts, 0, S * 8, fs->owner->stream));
     return ORBX_OK;
@@ -68,6 +70,7 @@ extern "C" int orbm_frameset_compute_bow(orbm_frameset_t* fs, orbv_t* voc, int s
     if (slot0 < 0 || slot0 >= fs->slots || n < 0 || n > fs->slots) return fail(ORBX_E_INVALID, "bad argument");
     if ((rc = frameset_bow_alloc(fs))) return rc;
     orbm_frameset_bow* b = fs->bow;
+    for (int i = 0; i < n; i++) b->slotVoc[(size_t)((slot0 + i) % fs->slots)] = voc->serial;
     if (n == 0) return ORBX_OK;
     if (voc->nWords == 0) { b->computed = true; return ORBX_OK; }   // an empty vocabulary: empty BowVectors, searches match nothing
     orbm_handle* h = fs->owner;

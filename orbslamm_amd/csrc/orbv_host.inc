@@ -6,6 +6,7 @@ struct orbv_handle {
     int device = 0;
     hipStream_t stream = nullptr;
     int k = 0, L = 0, scoring = 0, weighting = 0, nNodes = 0, nWords = 0;
+    uint64_t serial = 0;             // unique per vocabulary made in this process (a frame set slot records the one that transformed it)
     std::vector<int> nodesAtLevel;   // [0 .. deepest]: how many nodes the tree has at each depth (root = 0)
     int32_t* d_childStart = nullptr; int32_t* d_childIdx = nullptr; uint8_t* d_desc = nullptr;
     int32_t* d_wordId = nullptr; double* d_weight = nullptr;
@@ -99,7 +100,9 @@ extern "C" int orbv_create(int device, int k, int L, int scoring, int weighting,
             memcpy(&dN[(size_t)i * 32], &d[(size_t)old * 32], 32);
         }
     }
+    static std::atomic<uint64_t> serials(0);
     orbv_handle* h = new orbv_handle();
+    h->serial = ++serials;
     h->device = device; h->k = k; h->L = L; h->scoring = scoring; h->weighting = weighting; h->nNodes = nNodes; h->nWords = nWords;
     {
         std::vector<int> depth(nNodes, 0);

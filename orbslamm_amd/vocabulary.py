@@ -60,3 +60,12 @@ class ORBVocabulary:
         check(self._L.orbv_transform(self._h, ptr(d), n, int(levelsup), ptr(wid), ptr(wv), C.byref(nw), ptr(fn), ptr(fs), ptr(fi),
                                      C.byref(nf)))
         return (wid[:nw.value].copy(), wv[:nw.value].copy()), (fn[:nf.value].copy(), fs[:nf.value + 1].copy(), fi[:fs[nf.value]].copy())
+
+    def score(self, v1, v2):
+        """double score(const BowVector& v1, const BowVector& v2) -- TemplatedVocabulary.h:1199 (L1Scoring::score; other
+        scorings are refused).  v1, v2: (word ids ascending, values)"""
+        a_ids, a_vals = (np.ascontiguousarray(v1[0], dtype=np.uint32), np.ascontiguousarray(v1[1], dtype=np.float64))
+        b_ids, b_vals = (np.ascontiguousarray(v2[0], dtype=np.uint32), np.ascontiguousarray(v2[1], dtype=np.float64))
+        out = C.c_double()
+        check(self._L.orbv_score(self._h, ptr(a_ids), ptr(a_vals), a_ids.shape[0], ptr(b_ids), ptr(b_vals), b_ids.shape[0], C.byref(out)))
+        return out.value
