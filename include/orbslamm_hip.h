@@ -673,6 +673,60 @@ int orbk_detect_loop_batch(orbk_db_t* db, int n, const int32_t* slots, const uin
                            const int32_t* conn_start, const int32_t* conn_idx, const int32_t* cov_start, const int32_t* cov_idx,
                            int32_t* out_start, int32_t* out, int cap);
 
+/* ---------------------------------------------------------------- Initializer
+ * replaces Initializer (src/Initializer.cc): the H / F RANSAC and the two-view reconstruction of monocular map
+ * initialisation.  ORBI_MODEL_HF is SingleRobotScenario's (FindHomography and FindFundamental, ReconstructH when
+ * RH = SH/(SH+SF) > 0.45, else ReconstructF); ORBI_MODEL_F is MultipleRobotsScenario's (FindFundamental, ReconstructF).
+ * Results equal the reference's bit for bit given the same sets (its OpenCV arithmetic is restated, unpinned: §2).
+ *
+ * orbi_create: Initializer(ReferenceFrame, sigma, iterations) with ReferenceFrame.mvKeysUn = keys1_un (host) and
+ *   mK = [fx 0 cx; 0 fy cy; 0 0 1], K = (fx, fy, cx, cy); frame 1's Normalize is computed once here.  The handle runs on
+ *   the matcher handle's device and stream and holds a reference to it.  orbi_create_frame takes mvKeysUn from a
+ *   device-resident frame (copied device to device).
+ * orbi_initialize: bool Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated) with CurrentFrame.mvKeysUn =
+ *   keys2_un; matches12 (host, n1 long): vMatches12 (-1: none); sets (host, iterations x 8): the RANSAC sets as indices
+ *   into the compacted match list (the entries i with matches12[i] >= 0, in order), which the reference draws with
+ *   DUtils::Random (Initializer.cc:80-97) -- the caller draws them the same way.  res: the return value, R21 / t21 and
+ *   diagnostics.  p3d (n1 x 3) and triangulated (n1) are written only where the reference writes vP3D / vbTriangulated:
+ *   on success (res->ok).  orbi_initialize_frame reads mvKeysUn from a device-resident frame.
+ * Refusals (nothing computed): ORBX_E_UNSUPPORTED for fewer than 8 matches (the reference would draw from an empty
+ *   vector; Tracking never calls it below 100), iterations above ORBI_MAX_ITERATIONS, or more than ORBI_MAX_FEATURES
+ *   keys in a frame; ORBX_E_INVALID for a null argument, iterations < 1, an unknown model, a match index outside
+ *   frame 2, or a set index outside [0, matches).
+ * Defined outcome: when the model to reconstruct has best score 0 (no hypothesis beat score = 0.0) the result is false
+ *   with every output untouched (the reference would run OpenCV on an empty cv::Mat). */
+#define ORBI_MODEL_HF 0
+#define ORBI_MODEL_F 1
+#define ORBI_MAX_ITERATIONS 4096
+#define ORBI_MAX_FEATURES 65535
+typedef struct {
+    int32_t ok;                /* Initialize's return value */
+    int32_t reconstructed_h;   /* 1: ReconstructH ran; 0: ReconstructF ran (or neither: n_candidates == 0, rt_state == 0) */
+    int32_t rt_state;          /* R21 / t21: 0 untouched, 1 emptied (ReconstructF's failure), 2 written */
+    float R21[9], t21[3];      /* row-major 3x3, 3x1 (rt_state == 2) */
+    float SH, SF, RH;          /* scores (SH = 0 and RH = 0 under ORBI_MODEL_F) */
+    float H21[9], F21[9];      /* the winning hypotheses (zeros where no iteration beat 0) */
+    int32_t it_H, it_F;        /* their iterations (-1: none) */
+    int32_t inliers_H, inliers_F;
+    int32_t n_matches;         /* N: the entries of matches12 >= 0 */
+    int32_t n_inliers;         /* inliers of the model reconstructed */
+    int32_t n_candidates;      /* 4 (F), 8 (H) or 0 (ReconstructH's singular-value test failed, or no model) */
+    int32_t best;              /* the candidate whose points are returned (-1: none) */
+    int32_t n_good[8];         /* CheckRT's nGood of every candidate */
+    float parallax[8];         /* and its parallax (degrees) */
+} OrbiResult;
+typedef struct orbi_init orbi_t;
+int orbi_create(orbm_t* h, const OrbxKeyPoint* keys1_un, int n1, const float K[4], float sigma, int iterations, int model, orbi_t** out);
+int orbi_create_frame(orbm_t* h, orbm_frame_t* f1, const float K[4], float sigma, int iterations, int model, orbi_t** out);
+int orbi_initialize(orbi_t* ini, const OrbxKeyPoint* keys2_un, int n2, const int32_t* matches12, const int32_t* sets,
+                    OrbiResult* res, float* p3d, uint8_t* triangulated);
+int orbi_initialize_frame(orbi_t* ini, orbm_frame_t* f2, const int32_t* matches12, const int32_t* sets,
+                          OrbiResult* res, float* p3d, uint8_t* triangulated);
+/* frame 1's size and its Normalize: (meanX, meanY, sX, sY) */
+int orbi_size(orbi_t* ini, int* n1);
+int orbi_normalization(orbi_t* ini, float out[4]);
+void orbi_destroy(orbi_t* ini);
+
 #ifdef __cplusplus
 }
 #endif

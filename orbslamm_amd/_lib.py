@@ -86,6 +86,11 @@ EXPORTS_KFDB = [
     "orbk_detect_relocalization_candidates_frameset", "orbk_detect_loop_candidates", "orbk_detect_loop_batch",
 ]
 
+# the Initializer's block (orbi_*)
+EXPORTS_INIT = [
+    "orbi_create", "orbi_create_frame", "orbi_initialize", "orbi_initialize_frame", "orbi_size", "orbi_normalization", "orbi_destroy",
+]
+
 
 def build(force=False):
     """hipcc the extension in-tree for gfx950 (cross-compiles without a GPU)."""
@@ -136,7 +141,7 @@ def lib():
         L = C.CDLL(os.environ.get("ORBSLAMM_HIP_LIB") or SO_PATH)
         L.orbx_last_error.restype = C.c_char_p
         L.orbx_scale_factor.restype = C.c_float
-        for name in EXPORTS + EXPORTS_KFDB:
+        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT:
             getattr(L, name)
         L.orbx_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _lib = L

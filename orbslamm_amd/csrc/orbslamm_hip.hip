@@ -38,6 +38,7 @@
 #include "orbt_kernels.hip"
 #include "orbv_kernels.hip"
 #include "orbk_kernels.hip"
+#include "orbi_kernels.hip"
 
 using namespace orbx;
 
@@ -178,3 +179,4 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 #include "orbt_bow_host.inc"
 #include "orbk_host.inc"   // keyframe database
+#include "orbi_host.inc"   // Initializer

@@ -1,0 +1,199 @@
+"""The Initializer's contract on the CPU: the restatement's SVD (JacobiSVDImpl_<float> as cv::SVD::compute runs it)
+against numpy.linalg.svd, the restatement recovering a known pose (F on a general scene, H on a planar one), make_sets
+against a literal restatement of DUtils::Random::RandomInt over libc's rand(), and the orbi_* block of the header
+declared and exported by the built library."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import init_cases as ic
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _check_svd(a, full):
+    w, u, vt = ic.ref_svd(a, full)
+    m, n = a.shape
+    k = min(m, n)
+    ws = np.linalg.svd(a.astype(np.float64), compute_uv=False)
+    scale = max(float(ws[0]), 1e-30)
+    assert w.shape == (k,)
+    assert np.all(np.diff(w.astype(np.float64)) <= 0)                               # sorted, descending
+    assert np.allclose(w, ws, rtol=0, atol=2e-5 * scale), (w, ws)
+    rec = (u[:, :k].astype(np.float64) * w.astype(np.float64)) @ vt[:k].astype(np.float64)
+    assert np.allclose(rec, a, rtol=0, atol=5e-5 * scale)
+    assert vt.shape == ((n, n) if (full or m >= n) else (k, n)) or vt.shape == (n, n)
+    # the full factors are orthonormal, the completed rows (random vector, Gram-Schmidt'ed) included
+    if full:
+        assert np.allclose(vt.astype(np.float64) @ vt.T.astype(np.float64), np.eye(vt.shape[0]), atol=2e-5)
+        assert np.allclose(u.T.astype(np.float64) @ u.astype(np.float64), np.eye(u.shape[1]), atol=2e-5)
+
+
+@pytest.mark.parametrize("shape", [(8, 9), (16, 9), (3, 3), (4, 4)])
+def test_restated_svd_against_numpy(shape):
+    rng = np.random.default_rng(sum(shape))
+    for trial in range(20):
+        a = rng.normal(0, 1, shape).astype(np.float32)
+        if trial % 4 == 1:   # rank deficient: one row a combination of two others
+            a[-1] = a[0] * np.float32(0.5) - a[1] * np.float32(2.0)
+        if trial % 4 == 2:   # a zero row
+            a[1] = 0
+        if trial % 4 == 3:   # a repeated row (degenerate 8-point set)
+            a[2] = a[0]
+        _check_svd(a, True)
+    _check_svd(np.zeros(shape, np.float32), True)
+    _check_svd(rng.normal(0, 1, shape).astype(np.float32), False)
+
+
+def test_restated_svd_completion_of_the_null_row():
+    """an 8x9 A takes the transposed path: vt's row 8 is the RNG(0x12345678) vector Gram-Schmidt'ed against the others,
+    so it spans A's null space (A vt[8] = 0) even though no rotation ever produced it"""
+    rng = np.random.default_rng(5)
+    a = rng.normal(0, 1, (8, 9)).astype(np.float32)
+    _, _, vt = ic.ref_svd(a, True)
+    assert vt.shape == (9, 9)
+    assert np.abs(a.astype(np.float64) @ vt[8].astype(np.float64)).max() < 1e-5
+    assert abs(np.linalg.norm(vt[8].astype(np.float64)) - 1) < 1e-6
+
+
+def test_normalize_is_the_ordered_float_chain():
+    rng = np.random.default_rng(1)
+    keys = ic.keys_from_xy(rng.uniform(0, 640, (777, 2)).astype(np.float32), rng)
+    T, pn = ic.ref_normalize(keys)
+    f = np.float32
+    mx = my = f(0)
+    for k in keys:
+        mx = f(mx + k["x"]); my = f(my + k["y"])
+    mx, my = f(mx / f(len(keys))), f(my / f(len(keys)))
+    dx = dy = f(0)
+    for k in keys:
+        dx = f(dx + abs(f(k["x"] - mx))); dy = f(dy + abs(f(k["y"] - my)))
+    sx, sy = f(1.0 / float(f(dx / f(len(keys))))), f(1.0 / float(f(dy / f(len(keys)))))
+    assert T[0, 0] == sx and T[1, 1] == sy and T[0, 2] == f(-mx * sx) and T[1, 2] == f(-my * sy)
+    assert np.array_equal(pn[:, 0], ((keys["x"] - mx) * sx).astype(np.float32))
+
+
+def _angle(Ra, Rb):
+    c = (np.trace(Ra.T @ Rb) - 1) / 2
+    return np.degrees(np.arccos(np.clip(c, -1, 1)))
+
+
+def test_restatement_recovers_pose_with_f_on_a_general_scene():
+    rng = np.random.default_rng(11)
+    keys1, keys2, m12, R, t = ic.make_scene(rng, n_match=400, n1=700, n2=650, noise=0.0, outliers=0.0)
+    from orbslamm_amd.initializer import make_sets
+    sets = make_sets(int((m12 >= 0).sum()), 200)
+    out = ic.ref_initialize(keys1, keys2, m12, sets, model="HF")
+    r = out["res"]
+    assert r["reconstructed_h"] == 0 and r["RH"] <= np.float32(0.45), r["RH"]
+    assert out["ok"] and r["rt_state"] == 2
+    assert _angle(out["R21"].astype(np.float64), R) < 0.05
+    assert np.dot(out["t21"].astype(np.float64), t / np.linalg.norm(t)) > 0.9999
+    good = out["triangulated"]
+    assert good.sum() > 0.9 * 400
+    # triangulated points are (up to the scale of t) the true ones
+    i = np.flatnonzero(good)[0]
+    assert out["p3d"][i, 2] > 0
+    f_only = ic.ref_initialize(keys1, keys2, m12, sets, model="F")
+    assert f_only["res"]["SH"] == 0 and f_only["res"]["it_H"] == -1
+    assert f_only["ok"] and ic.same(f_only["R21"], out["R21"]) and ic.same(f_only["p3d"], out["p3d"])
+
+
+def test_restatement_picks_h_on_a_planar_scene():
+    rng = np.random.default_rng(12)
+    keys1, keys2, m12, R, t = ic.make_scene(rng, n_match=400, n1=600, n2=600, planar=True, noise=0.0, outliers=0.0)
+    from orbslamm_amd.initializer import make_sets
+    sets = make_sets(int((m12 >= 0).sum()), 200)
+    out = ic.ref_initialize(keys1, keys2, m12, sets, model="HF")
+    r = out["res"]
+    assert r["reconstructed_h"] == 1 and r["RH"] > np.float32(0.45), r["RH"]
+    assert r["n_candidates"] == 8
+    assert out["ok"] and r["rt_state"] == 2, r
+    assert _angle(out["R21"].astype(np.float64), R) < 0.2          # (a minimal 8-point set in float: H is less exact)
+    assert np.dot(out["t21"].astype(np.float64), t / np.linalg.norm(t)) > 0.999
+
+
+def test_restatement_returns_false_with_outputs_untouched_when_nothing_scores():
+    """frame 2 collapsed to one point: Normalize divides by a zero deviation, every score is NaN, none beats 0 -> false
+    (the defined outcome), R21 / t21, vP3D and vbTriangulated untouched"""
+    rng = np.random.default_rng(3)
+    keys1, keys2, m12, _, _ = ic.make_scene(rng, n_match=60, n1=80, n2=70)
+    keys2["x"], keys2["y"] = 100.0, 200.0
+    from orbslamm_amd.initializer import make_sets
+    sets = make_sets(60, 50)
+    for model in ("HF", "F"):
+        out = ic.ref_initialize(keys1, keys2, m12, sets, model=model)
+        r = out["res"]
+        assert not out["ok"] and r["rt_state"] == 0 and r["it_F"] == -1 and r["it_H"] == -1 and r["n_candidates"] == 0
+        assert r["reconstructed_h"] == 0 and r["SF"] == 0 and r["SH"] == 0
+        assert not out["p3d"].any() and not out["triangulated"].any()
+
+
+def test_make_sets_is_randomint_over_libc_rand():
+    from orbslamm_amd.initializer import RAND_MAX, make_sets
+    libc = C.CDLL(None)
+    libc.rand.restype = C.c_int
+    for n, iters in ((8, 3), (9, 40), (500, 200), (2000, 17)):
+        got = make_sets(n, iters, seed=0)
+        libc.srand(0)
+        want = np.zeros((iters, 8), np.int32)
+        for it in range(iters):
+            avail = list(range(n))
+            for j in range(8):
+                d = (len(avail) - 1) - 0 + 1                                   # RandomInt(0, size - 1)
+                randi = int((float(libc.rand()) / (float(RAND_MAX) + 1.0)) * d) + 0
+                want[it, j] = avail[randi]
+                avail[randi] = avail[-1]
+                avail.pop()
+        assert np.array_equal(got, want)
+        assert all(len(set(s)) == 8 for s in got.tolist())
+        libc.srand(0)
+        L = ic.ref_lib()                    # the restatement's DUtils (SeedRandOnce(0) seeds at most once per process)
+        drawn = np.zeros(iters * 8, np.int32)
+        L.initref_draw_sets(n, iters, drawn.ctypes.data_as(C.c_void_p))
+        assert np.array_equal(drawn.reshape(iters, 8), got)
+    assert RAND_MAX == 2147483647
+    # seed None continues the stream
+    libc.srand(0)
+    a = make_sets(30, 2, seed=None)
+    assert np.array_equal(a, make_sets(30, 2, seed=0))
+    with pytest.raises(ValueError):
+        make_sets(7, 1)
+
+
+def test_header_declares_and_library_exports_the_orbi_block():
+    src = open(os.path.join(ROOT, "include", "orbslamm_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    declared = sorted(set(re.findall(r"\b(orbi_[a-z0-9_]+)\s*\(", src)))
+    from orbslamm_amd import _lib
+    assert declared == sorted(_lib.EXPORTS_INIT)
+    L = _lib.lib()
+    for name in declared:
+        assert hasattr(L, name), name
+    for macro in ("ORBI_MODEL_HF", "ORBI_MODEL_F", "ORBI_MAX_ITERATIONS", "ORBI_MAX_FEATURES", "OrbiResult"):
+        assert macro in src, macro
+    # OrbiResult's layout: the restatement's Result and the ctypes mirror agree with the header's field order
+    from orbslamm_amd.initializer import OrbiResult
+    fields = src[:src.index("} OrbiResult;")].rsplit("typedef struct {", 1)[1]
+    names = re.findall(r"\b(?:int32_t|float)\s+([^;]+);", fields)
+    flat = [n.strip().split("[")[0] for group in names for n in group.split(",")]
+    assert flat == [f for f, _ in OrbiResult._fields_]
+
+
+def test_entries_refuse_without_a_device_or_bad_arguments():
+    """no handle, no computation: every orbi_* entry refuses a null handle (there is no CPU fallback)"""
+    from orbslamm_amd import _lib
+    from orbslamm_amd.initializer import OrbiResult, _setup
+    L = _lib.lib()
+    _setup(L)
+    h = C.c_void_p()
+    K = np.array(ic.K_TUM, np.float32)
+    keys = np.zeros(10, _lib.KP_DTYPE)
+    assert L.orbi_create(None, keys.ctypes.data, 10, K.ctypes.data, 1.0, 200, 0, C.byref(h)) == _lib.ORBX_E_INVALID
+    r = OrbiResult()
+    assert L.orbi_initialize(None, None, 0, None, None, C.byref(r), None, None) == _lib.ORBX_E_INVALID
+    assert L.orbi_initialize_frame(None, None, None, None, C.byref(r), None, None) == _lib.ORBX_E_INVALID
+    L.orbi_destroy(None)

@@ -1,0 +1,780 @@
+// init_ref.hpp -- a literal C++ restatement of Initializer (src/Initializer.cc of both scenarios) and of the OpenCV 3.0
+// pieces it calls: SVD (JacobiSVDImpl_<float> behind cv::SVD::compute / cv::SVDecomp), gemm's small-matrix and
+// transposed branches, 3x3 invert / determinant, MatExpr scaling, addWeighted, norm and dot on CV_32F.  It is the checker
+// of the device Initializer (orbslamm_amd/csrc/orbi_kernels.hip): it shares no header with the library and is built with
+// g++ -ffp-contract=off (every operation one IEEE op).  The OpenCV pieces are restated from the published 3.0 source and
+// are UNPINNED: no OpenCV exists to compare against.
+//
+// Defined choices, the same on the device:
+//   - hypot inside the Jacobi rotation: lapack.cpp's written-out binary64 formula, not libm's
+//   - a model whose best score stayed 0 (no hypothesis beat score = 0.0) gives false with every output untouched (the
+//     reference would run OpenCV on an empty cv::Mat)
+//   - acos of the 51st-smallest cosParallax is the float overload (acosf), as `using namespace std` makes it in the
+//     reference; the sqrt of a float in ReconstructH likewise (sqrtf)
+#pragma once
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+namespace init_ref {
+
+struct KeyPt { float x, y, size, angle, response; int32_t octave, class_id; };   // cv::KeyPoint's layout
+
+// a dense row-major CV_32F matrix
+struct Mat {
+    int rows = 0, cols = 0;
+    std::vector<float> d;
+    Mat() {}
+    Mat(int r, int c) : rows(r), cols(c), d((size_t)r * c, 0.f) {}
+    float& at(int r, int c) { return d[(size_t)r * cols + c]; }
+    float at(int r, int c) const { return d[(size_t)r * cols + c]; }
+    bool empty() const { return d.empty(); }
+};
+
+inline Mat eye3() { Mat m(3, 3); m.at(0, 0) = m.at(1, 1) = m.at(2, 2) = 1.f; return m; }
+inline Mat transpose(const Mat& a) { Mat o(a.cols, a.rows); for (int r = 0; r < a.rows; r++) for (int c = 0; c < a.cols; c++) o.at(c, r) = a.at(r, c); return o; }
+
+// ------------------------------------------------------------------------------------------------ OpenCV arithmetic
+// gemm(A, B, alpha, noArray(), 0) with flags == 0 and len == 3 (matmul.cpp's small-matrix branch): the three products
+// summed in float, left to right, then d = (float)(t*alpha + c*beta) with c = 0, beta = 0 (so -0 becomes +0)
+inline Mat mul(const Mat& A, const Mat& B, double alpha = 1.0)
+{
+    Mat o(A.rows, B.cols);
+    for (int i = 0; i < A.rows; i++)
+        for (int j = 0; j < B.cols; j++) {
+            const float t = A.at(i, 0) * B.at(0, j) + A.at(i, 1) * B.at(1, j) + A.at(i, 2) * B.at(2, j);
+            o.at(i, j) = (float)((double)t * alpha + (double)0.f * 0.0);
+        }
+    return o;
+}
+// A*B + C (MatExpr folds it into one gemm(A, B, 1, C, 1)): the same branch with beta = 1
+inline Mat mulAdd(const Mat& A, const Mat& B, const Mat& Cm)
+{
+    Mat o(A.rows, B.cols);
+    for (int i = 0; i < A.rows; i++)
+        for (int j = 0; j < B.cols; j++) {
+            const float t = A.at(i, 0) * B.at(0, j) + A.at(i, 1) * B.at(1, j) + A.at(i, 2) * B.at(2, j);
+            o.at(i, j) = (float)((double)t * 1.0 + (double)Cm.at(i, j) * 1.0);
+        }
+    return o;
+}
+// GEMM_1_T / GEMM_2_T take the generic kernel, GEMMSingleMul<float, double>: double sums in k order, d = (float)(s*alpha)
+inline Mat mulT1(const Mat& A, const Mat& B, double alpha = 1.0)   // A.t()*B
+{
+    Mat o(A.cols, B.cols);
+    for (int i = 0; i < A.cols; i++)
+        for (int j = 0; j < B.cols; j++) {
+            double s = 0;
+            for (int k = 0; k < A.rows; k++) s += (double)A.at(k, i) * (double)B.at(k, j);
+            o.at(i, j) = (float)(s * alpha);
+        }
+    return o;
+}
+inline Mat mulT2(const Mat& A, const Mat& B)   // A*B.t()
+{
+    Mat o(A.rows, B.rows);
+    for (int i = 0; i < A.rows; i++)
+        for (int j = 0; j < B.rows; j++) {
+            double s = 0;
+            for (int k = 0; k < A.cols; k++) s += (double)A.at(i, k) * (double)B.at(j, k);
+            o.at(i, j) = (float)(s * 1.0);
+        }
+    return o;
+}
+// a MatExpr `alpha*A` (or A/s, -A) assigned to a Mat (MatOp_AddEx::assign): alpha 1 -> add(A, 0), alpha -1 ->
+// subtract(0, A), else convertTo with a double scale
+inline float exprScale(float x, double alpha)
+{
+    if (alpha == 1.0) return x + 0.f;
+    if (alpha == -1.0) return 0.f - x;
+    return (float)((double)x * alpha);
+}
+inline Mat exprScale(const Mat& a, double alpha) { Mat o = a; for (float& v : o.d) v = exprScale(v, alpha); return o; }
+// Mat::operator*=(double): convertTo in place, a copy when alpha is 1
+inline void scaleInPlace(Mat& a, double alpha) { if (alpha != 1.0) for (float& v : a.d) v = (float)((double)v * alpha); }
+inline Mat sub(const Mat& a, const Mat& b) { Mat o = a; for (size_t i = 0; i < o.d.size(); i++) o.d[i] = a.d[i] - b.d[i]; return o; }
+// cv::norm (normL2_<float, double>) and Mat::dot: double accumulation
+inline double norm(const Mat& a) { double s = 0; for (float v : a.d) s += (double)v * (double)v; return std::sqrt(s); }
+inline double dot(const Mat& a, const Mat& b) { double s = 0; for (size_t i = 0; i < a.d.size(); i++) s += (double)a.d[i] * (double)b.d[i]; return s; }
+// determinant / invert of a 3x3 CV_32F (lapack.cpp: det3 in double; invert's n == 3 branch, zeros when singular)
+inline double det3(const Mat& m)
+{
+    return m.at(0, 0) * ((double)m.at(1, 1) * m.at(2, 2) - (double)m.at(1, 2) * m.at(2, 1)) -
+           m.at(0, 1) * ((double)m.at(1, 0) * m.at(2, 2) - (double)m.at(1, 2) * m.at(2, 0)) +
+           m.at(0, 2) * ((double)m.at(1, 0) * m.at(2, 1) - (double)m.at(1, 1) * m.at(2, 0));
+}
+inline Mat inv3(const Mat& S)
+{
+    Mat D(3, 3);
+    double d = det3(S);
+    if (d == 0.) return D;
+    d = 1. / d;
+    const double t[9] = {
+        ((double)S.at(1, 1) * S.at(2, 2) - (double)S.at(1, 2) * S.at(2, 1)) * d,
+        ((double)S.at(0, 2) * S.at(2, 1) - (double)S.at(0, 1) * S.at(2, 2)) * d,
+        ((double)S.at(0, 1) * S.at(1, 2) - (double)S.at(0, 2) * S.at(1, 1)) * d,
+        ((double)S.at(1, 2) * S.at(2, 0) - (double)S.at(1, 0) * S.at(2, 2)) * d,
+        ((double)S.at(0, 0) * S.at(2, 2) - (double)S.at(0, 2) * S.at(2, 0)) * d,
+        ((double)S.at(0, 2) * S.at(1, 0) - (double)S.at(0, 0) * S.at(1, 2)) * d,
+        ((double)S.at(1, 0) * S.at(2, 1) - (double)S.at(1, 1) * S.at(2, 0)) * d,
+        ((double)S.at(0, 1) * S.at(2, 0) - (double)S.at(0, 0) * S.at(2, 1)) * d,
+        ((double)S.at(0, 0) * S.at(1, 1) - (double)S.at(0, 1) * S.at(1, 0)) * d};
+    for (int i = 0; i < 9; i++) D.d[i] = (float)t[i];
+    return D;
+}
+
+// cv::RNG
+struct Rng {
+    uint64_t state;
+    explicit Rng(uint64_t s) : state(s ? s : 0xffffffffu) {}
+    unsigned next() { state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32); return (unsigned)state; }
+};
+
+// lapack.cpp's hypot
+inline double hypotCv(double a, double b)
+{
+    a = std::abs(a);
+    b = std::abs(b);
+    if (a > b) { b /= a; return a * std::sqrt(1 + b * b); }
+    if (b > 0) { a /= b; return b * std::sqrt(1 + a * a); }
+    return 0;
+}
+
+// JacobiSVDImpl_<float>(At, astep, W, Vt, vstep, m, n, n1, FLT_MIN, FLT_EPSILON*2), steps in elements
+inline void jacobiSVD(float* At, int astep, float* Wout, float* Vt, int vstep, int m, int n, int n1)
+{
+    const double minval = FLT_MIN;
+    const float eps = FLT_EPSILON * 2;
+    std::vector<double> W((size_t)n);
+    const int max_iter = std::max(m, 30);
+    double sd;
+    for (int i = 0; i < n; i++) {
+        sd = 0;
+        for (int k = 0; k < m; k++) { const float t = At[i * astep + k]; sd += (double)t * t; }
+        W[i] = sd;
+        if (Vt) { for (int k = 0; k < n; k++) Vt[i * vstep + k] = 0; Vt[i * vstep + i] = 1; }
+    }
+    for (int iter = 0; iter < max_iter; iter++) {
+        bool changed = false;
+        for (int i = 0; i < n - 1; i++)
+            for (int j = i + 1; j < n; j++) {
+                float *Ai = At + i * astep, *Aj = At + j * astep;
+                double a = W[i], p = 0, b = W[j];
+                for (int k = 0; k < m; k++) p += (double)Ai[k] * Aj[k];
+                if (std::abs(p) <= eps * std::sqrt((double)a * b)) continue;
+                p *= 2;
+                const double beta = a - b, gamma = hypotCv(p, beta);
+                float c, s;
+                if (beta < 0) {
+                    const double delta = (gamma - beta) * 0.5;
+                    s = (float)std::sqrt(delta / gamma);
+                    c = (float)(p / (gamma * s * 2));
+                } else {
+                    c = (float)std::sqrt((gamma + beta) / (gamma * 2));
+                    s = (float)(p / (gamma * c * 2));
+                }
+                a = b = 0;
+                for (int k = 0; k < m; k++) {
+                    const float t0 = c * Ai[k] + s * Aj[k];
+                    const float t1 = -s * Ai[k] + c * Aj[k];
+                    Ai[k] = t0; Aj[k] = t1;
+                    a += (double)t0 * t0; b += (double)t1 * t1;
+                }
+                W[i] = a; W[j] = b;
+                changed = true;
+                if (Vt) {
+                    float *Vi = Vt + i * vstep, *Vj = Vt + j * vstep;
+                    for (int k = 0; k < n; k++) {
+                        const float t0 = c * Vi[k] + s * Vj[k];
+                        const float t1 = -s * Vi[k] + c * Vj[k];
+                        Vi[k] = t0; Vj[k] = t1;
+                    }
+                }
+            }
+        if (!changed) break;
+    }
+    for (int i = 0; i < n; i++) {
+        sd = 0;
+        for (int k = 0; k < m; k++) { const float t = At[i * astep + k]; sd += (double)t * t; }
+        W[i] = std::sqrt(sd);
+    }
+    for (int i = 0; i < n - 1; i++) {
+        int j = i;
+        for (int k = i + 1; k < n; k++) if (W[j] < W[k]) j = k;
+        if (i != j) {
+            std::swap(W[i], W[j]);
+            if (Vt) {
+                for (int k = 0; k < m; k++) std::swap(At[i * astep + k], At[j * astep + k]);
+                for (int k = 0; k < n; k++) std::swap(Vt[i * vstep + k], Vt[j * vstep + k]);
+            }
+        }
+    }
+    for (int i = 0; i < n; i++) Wout[i] = (float)W[i];
+    if (!Vt) return;
+    Rng rng(0x12345678);
+    for (int i = 0; i < n1; i++) {
+        sd = i < n ? W[i] : 0;
+        for (int ii = 0; ii < 100 && sd <= minval; ii++) {
+            // a zero singular value: a random vector, projected off the previous rows, normalised
+            const float val0 = (float)(1. / m);
+            for (int k = 0; k < m; k++) At[i * astep + k] = (rng.next() & 256) != 0 ? val0 : -val0;
+            for (int it = 0; it < 2; it++)
+                for (int j = 0; j < i; j++) {
+                    sd = 0;
+                    for (int k = 0; k < m; k++) sd += At[i * astep + k] * At[j * astep + k];
+                    float asum = 0;
+                    for (int k = 0; k < m; k++) {
+                        const float t = (float)(At[i * astep + k] - sd * At[j * astep + k]);
+                        At[i * astep + k] = t;
+                        asum += std::abs(t);
+                    }
+                    asum = asum > eps * 100 ? 1 / asum : 0;
+                    for (int k = 0; k < m; k++) At[i * astep + k] *= asum;
+                }
+            sd = 0;
+            for (int k = 0; k < m; k++) { const float t = At[i * astep + k]; sd += (double)t * t; }
+            sd = std::sqrt(sd);
+        }
+        const float s = (float)(sd > minval ? 1 / sd : 0.);
+        for (int k = 0; k < m; k++) At[i * astep + k] *= s;
+    }
+}
+
+// cv::SVD::compute(src, w, u, vt, flags) / cv::SVDecomp on CV_32F (_SVDcompute; MODIFY_A only permits reusing src)
+inline void svd(const Mat& src, bool fullUV, Mat& w, Mat& u, Mat& vt)
+{
+    int m = src.rows, n = src.cols;
+    bool at = false;
+    if (m < n) { std::swap(m, n); at = true; }
+    const int urows = fullUV ? m : n;
+    // temp_a (n x m) is the first n rows of temp_u (urows x m), zeroed when urows > n
+    std::vector<float> bufU((size_t)urows * m, 0.f), bufV((size_t)n * n, 0.f), bufW((size_t)n);
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < m; k++) bufU[(size_t)i * m + k] = at ? src.at(i, k) : src.at(k, i);
+    jacobiSVD(bufU.data(), m, bufW.data(), bufV.data(), n, m, n, urows);
+    w = Mat(n, 1);
+    for (int i = 0; i < n; i++) w.d[i] = bufW[i];
+    Mat tu(urows, m), tv(n, n);
+    tu.d = bufU; tv.d = bufV;
+    if (!at) { u = transpose(tu); vt = tv; }
+    else { u = transpose(tv); vt = tu; }
+}
+
+// ------------------------------------------------------------------------------------------------ DUtils::Random
+// Thirdparty/DBoW2/DUtils/Random.cpp over the process's rand()
+inline bool& alreadySeeded() { static bool s = false; return s; }
+inline void seedRandOnce(int seed) { if (!alreadySeeded()) { srand(seed); alreadySeeded() = true; } }
+inline int randomInt(int min, int max) { const int d = max - min + 1; return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min; }
+// Initialize's set drawing (:67-97) for N matches: `iterations` sets of 8, flattened
+inline std::vector<int32_t> drawSets(int N, int iterations)
+{
+    std::vector<size_t> all, avail;
+    for (int i = 0; i < N; i++) all.push_back((size_t)i);
+    std::vector<int32_t> sets((size_t)iterations * 8, 0);
+    seedRandOnce(0);
+    for (int it = 0; it < iterations; it++) {
+        avail = all;
+        for (size_t j = 0; j < 8; j++) {
+            const int randi = randomInt(0, (int)(avail.size() - 1));
+            const int idx = (int)avail[randi];
+            sets[(size_t)it * 8 + j] = idx;
+            avail[randi] = avail.back();
+            avail.pop_back();
+        }
+    }
+    return sets;
+}
+
+// ------------------------------------------------------------------------------------------------ Initializer
+// Initialize's outputs and diagnostics; the layout equals OrbiResult of include/orbslamm_hip.h field for field
+struct Result {
+    int32_t ok = 0;
+    int32_t reconH = 0;      // 1: ReconstructH ran, 0: ReconstructF (or neither: nCand 0, rtState 0)
+    int32_t rtState = 0;     // 0: R21 / t21 untouched, 1: emptied (ReconstructF's failure), 2: written
+    float R21[9] = {0}, t21[3] = {0};
+    float SH = 0, SF = 0, RH = 0;
+    float H21[9] = {0}, F21[9] = {0};
+    int32_t itH = -1, itF = -1, nInliersH = 0, nInliersF = 0;
+    int32_t nMatches = 0, nInliers = 0, nCand = 0, best = -1;
+    int32_t nGood[8] = {0};
+    float parallax[8] = {0};
+};
+
+typedef std::pair<int, int> Match;
+
+class Initializer {
+public:
+    // Initializer(ReferenceFrame, sigma, iterations): K = (fx, fy, cx, cy); hf: SingleRobotScenario (H and F), else F only
+    Initializer(const std::vector<KeyPt>& keys1Un, const float K[4], float sigma, int iterations, bool hf)
+        : mvKeys1(keys1Un), mK(eye3()), mSigma(sigma), mSigma2(sigma * sigma), mMaxIterations(iterations), mHF(hf)
+    {
+        mK.at(0, 0) = K[0]; mK.at(1, 1) = K[1]; mK.at(0, 2) = K[2]; mK.at(1, 2) = K[3];
+    }
+
+    // Initialize with the sets given (iterations x 8 indices into the compacted matches).  vP3D (n1 x 3) and
+    // vbTriangulated (n1) are written only where the reference writes them.
+    bool Initialize(const std::vector<KeyPt>& keys2Un, const std::vector<int>& vMatches12, const std::vector<int32_t>& sets,
+                    Result& res, std::vector<float>& vP3D, std::vector<uint8_t>& vbTriangulated)
+    {
+        res = Result();
+        mvKeys2 = keys2Un;
+        mvMatches12.clear();
+        for (size_t i = 0; i < vMatches12.size(); i++)
+            if (vMatches12[i] >= 0) mvMatches12.push_back(Match((int)i, vMatches12[i]));
+        res.nMatches = (int)mvMatches12.size();
+        mvSets.assign((size_t)mMaxIterations, std::vector<size_t>(8, 0));
+        for (int it = 0; it < mMaxIterations; it++)
+            for (int j = 0; j < 8; j++) mvSets[it][j] = (size_t)sets[(size_t)it * 8 + j];
+
+        std::vector<bool> inH, inF;
+        float SH = 0, SF = 0;
+        Mat H, F;
+        if (mHF) FindHomography(inH, SH, H, res.itH);
+        FindFundamental(inF, SF, F, res.itF);
+        res.SH = SH; res.SF = SF;
+        for (size_t i = 0; i < inH.size(); i++) res.nInliersH += inH[i];
+        for (size_t i = 0; i < inF.size(); i++) res.nInliersF += inF[i];
+        if (!H.empty()) std::memcpy(res.H21, H.d.data(), sizeof res.H21);
+        if (!F.empty()) std::memcpy(res.F21, F.d.data(), sizeof res.F21);
+        Mat R21, t21;
+        bool ok = false;
+        bool useH = false;
+        if (mHF) {
+            const float RH = SH / (SH + SF);
+            res.RH = RH;
+            useH = RH > 0.45;
+        }
+        if (useH) {
+            res.reconH = 1;
+            ok = ReconstructH(inH, H, mK, R21, t21, vP3D, vbTriangulated, 1.0, 50, res);
+        } else if (!F.empty())
+            ok = ReconstructF(inF, F, mK, R21, t21, vP3D, vbTriangulated, 1.0, 50, res);
+        res.ok = ok;
+        if (!R21.empty()) { std::memcpy(res.R21, R21.d.data(), sizeof res.R21); std::memcpy(res.t21, t21.d.data(), sizeof res.t21); }
+        return ok;
+    }
+
+    static void Normalize(const std::vector<KeyPt>& vKeys, std::vector<float>& pn /* x, y pairs */, Mat& T)
+    {
+        float meanX = 0, meanY = 0;
+        const int N = (int)vKeys.size();
+        pn.resize((size_t)N * 2);
+        for (int i = 0; i < N; i++) { meanX += vKeys[i].x; meanY += vKeys[i].y; }
+        meanX = meanX / N;
+        meanY = meanY / N;
+        float meanDevX = 0, meanDevY = 0;
+        for (int i = 0; i < N; i++) {
+            pn[2 * i] = vKeys[i].x - meanX;
+            pn[2 * i + 1] = vKeys[i].y - meanY;
+            meanDevX += std::fabs(pn[2 * i]);
+            meanDevY += std::fabs(pn[2 * i + 1]);
+        }
+        meanDevX = meanDevX / N;
+        meanDevY = meanDevY / N;
+        const float sX = 1.0 / meanDevX, sY = 1.0 / meanDevY;
+        for (int i = 0; i < N; i++) { pn[2 * i] = pn[2 * i] * sX; pn[2 * i + 1] = pn[2 * i + 1] * sY; }
+        T = eye3();
+        T.at(0, 0) = sX;
+        T.at(1, 1) = sY;
+        T.at(0, 2) = -meanX * sX;
+        T.at(1, 2) = -meanY * sY;
+    }
+
+private:
+    void FindHomography(std::vector<bool>& vbMatchesInliers, float& score, Mat& H21, int32_t& itBest)
+    {
+        const int N = (int)mvMatches12.size();
+        std::vector<float> vPn1, vPn2;
+        Mat T1, T2;
+        Normalize(mvKeys1, vPn1, T1);
+        Normalize(mvKeys2, vPn2, T2);
+        const Mat T2inv = inv3(T2);
+        score = 0.0;
+        vbMatchesInliers.assign((size_t)N, false);
+        std::vector<float> p1(16), p2(16);
+        std::vector<bool> cur((size_t)N, false);
+        for (int it = 0; it < mMaxIterations; it++) {
+            for (int j = 0; j < 8; j++) {
+                const int idx = (int)mvSets[it][j];
+                p1[2 * j] = vPn1[2 * mvMatches12[idx].first]; p1[2 * j + 1] = vPn1[2 * mvMatches12[idx].first + 1];
+                p2[2 * j] = vPn2[2 * mvMatches12[idx].second]; p2[2 * j + 1] = vPn2[2 * mvMatches12[idx].second + 1];
+            }
+            const Mat Hn = ComputeH21(p1, p2);
+            const Mat H21i = mul(mul(T2inv, Hn), T1);
+            const Mat H12i = inv3(H21i);
+            const float currentScore = CheckHomography(H21i, H12i, cur, mSigma);
+            if (currentScore > score) { H21 = H21i; vbMatchesInliers = cur; score = currentScore; itBest = it; }
+        }
+    }
+
+    void FindFundamental(std::vector<bool>& vbMatchesInliers, float& score, Mat& F21, int32_t& itBest)
+    {
+        // (:193 takes N from the caller's empty vector: the inlier vector stays empty unless a hypothesis wins)
+        const int N = (int)vbMatchesInliers.size();
+        std::vector<float> vPn1, vPn2;
+        Mat T1, T2;
+        Normalize(mvKeys1, vPn1, T1);
+        Normalize(mvKeys2, vPn2, T2);
+        const Mat T2t = transpose(T2);
+        score = 0.0;
+        vbMatchesInliers.assign((size_t)N, false);
+        std::vector<float> p1(16), p2(16);
+        std::vector<bool> cur((size_t)N, false);
+        for (int it = 0; it < mMaxIterations; it++) {
+            for (int j = 0; j < 8; j++) {
+                const int idx = (int)mvSets[it][j];
+                p1[2 * j] = vPn1[2 * mvMatches12[idx].first]; p1[2 * j + 1] = vPn1[2 * mvMatches12[idx].first + 1];
+                p2[2 * j] = vPn2[2 * mvMatches12[idx].second]; p2[2 * j + 1] = vPn2[2 * mvMatches12[idx].second + 1];
+            }
+            const Mat Fn = ComputeF21(p1, p2);
+            const Mat F21i = mul(mul(T2t, Fn), T1);
+            const float currentScore = CheckFundamental(F21i, cur, mSigma);
+            if (currentScore > score) { F21 = F21i; vbMatchesInliers = cur; score = currentScore; itBest = it; }
+        }
+    }
+
+    static Mat ComputeH21(const std::vector<float>& p1, const std::vector<float>& p2)
+    {
+        Mat A(16, 9);
+        for (int i = 0; i < 8; i++) {
+            const float u1 = p1[2 * i], v1 = p1[2 * i + 1], u2 = p2[2 * i], v2 = p2[2 * i + 1];
+            A.at(2 * i, 0) = 0.0; A.at(2 * i, 1) = 0.0; A.at(2 * i, 2) = 0.0;
+            A.at(2 * i, 3) = -u1; A.at(2 * i, 4) = -v1; A.at(2 * i, 5) = -1;
+            A.at(2 * i, 6) = v2 * u1; A.at(2 * i, 7) = v2 * v1; A.at(2 * i, 8) = v2;
+            A.at(2 * i + 1, 0) = u1; A.at(2 * i + 1, 1) = v1; A.at(2 * i + 1, 2) = 1;
+            A.at(2 * i + 1, 3) = 0.0; A.at(2 * i + 1, 4) = 0.0; A.at(2 * i + 1, 5) = 0.0;
+            A.at(2 * i + 1, 6) = -u2 * u1; A.at(2 * i + 1, 7) = -u2 * v1; A.at(2 * i + 1, 8) = -u2;
+        }
+        Mat u, w, vt;
+        svd(A, true, w, u, vt);
+        Mat h(3, 3);
+        for (int k = 0; k < 9; k++) h.d[k] = vt.at(8, k);
+        return h;
+    }
+
+    static Mat ComputeF21(const std::vector<float>& p1, const std::vector<float>& p2)
+    {
+        Mat A(8, 9);
+        for (int i = 0; i < 8; i++) {
+            const float u1 = p1[2 * i], v1 = p1[2 * i + 1], u2 = p2[2 * i], v2 = p2[2 * i + 1];
+            A.at(i, 0) = u2 * u1; A.at(i, 1) = u2 * v1; A.at(i, 2) = u2;
+            A.at(i, 3) = v2 * u1; A.at(i, 4) = v2 * v1; A.at(i, 5) = v2;
+            A.at(i, 6) = u1; A.at(i, 7) = v1; A.at(i, 8) = 1;
+        }
+        Mat u, w, vt;
+        svd(A, true, w, u, vt);
+        Mat Fpre(3, 3);
+        for (int k = 0; k < 9; k++) Fpre.d[k] = vt.at(8, k);
+        svd(Fpre, true, w, u, vt);
+        w.d[2] = 0;
+        Mat D(3, 3);
+        for (int k = 0; k < 3; k++) D.at(k, k) = w.d[k];
+        return mul(mul(u, D), vt);
+    }
+
+    float CheckHomography(const Mat& H21, const Mat& H12, std::vector<bool>& in, float sigma) const
+    {
+        const int N = (int)mvMatches12.size();
+        const float h11 = H21.at(0, 0), h12 = H21.at(0, 1), h13 = H21.at(0, 2), h21 = H21.at(1, 0), h22 = H21.at(1, 1),
+                    h23 = H21.at(1, 2), h31 = H21.at(2, 0), h32 = H21.at(2, 1), h33 = H21.at(2, 2);
+        const float h11inv = H12.at(0, 0), h12inv = H12.at(0, 1), h13inv = H12.at(0, 2), h21inv = H12.at(1, 0),
+                    h22inv = H12.at(1, 1), h23inv = H12.at(1, 2), h31inv = H12.at(2, 0), h32inv = H12.at(2, 1),
+                    h33inv = H12.at(2, 2);
+        in.resize((size_t)N);
+        float score = 0;
+        const float th = 5.991;
+        const float invSigmaSquare = 1.0 / (sigma * sigma);
+        for (int i = 0; i < N; i++) {
+            bool bIn = true;
+            const KeyPt& kp1 = mvKeys1[mvMatches12[i].first];
+            const KeyPt& kp2 = mvKeys2[mvMatches12[i].second];
+            const float u1 = kp1.x, v1 = kp1.y, u2 = kp2.x, v2 = kp2.y;
+            const float w2in1inv = 1.0 / (h31inv * u2 + h32inv * v2 + h33inv);
+            const float u2in1 = (h11inv * u2 + h12inv * v2 + h13inv) * w2in1inv;
+            const float v2in1 = (h21inv * u2 + h22inv * v2 + h23inv) * w2in1inv;
+            const float squareDist1 = (u1 - u2in1) * (u1 - u2in1) + (v1 - v2in1) * (v1 - v2in1);
+            const float chiSquare1 = squareDist1 * invSigmaSquare;
+            if (chiSquare1 > th) bIn = false;
+            else score += th - chiSquare1;
+            const float w1in2inv = 1.0 / (h31 * u1 + h32 * v1 + h33);
+            const float u1in2 = (h11 * u1 + h12 * v1 + h13) * w1in2inv;
+            const float v1in2 = (h21 * u1 + h22 * v1 + h23) * w1in2inv;
+            const float squareDist2 = (u2 - u1in2) * (u2 - u1in2) + (v2 - v1in2) * (v2 - v1in2);
+            const float chiSquare2 = squareDist2 * invSigmaSquare;
+            if (chiSquare2 > th) bIn = false;
+            else score += th - chiSquare2;
+            in[i] = bIn;
+        }
+        return score;
+    }
+
+    float CheckFundamental(const Mat& F21, std::vector<bool>& in, float sigma) const
+    {
+        const int N = (int)mvMatches12.size();
+        const float f11 = F21.at(0, 0), f12 = F21.at(0, 1), f13 = F21.at(0, 2), f21 = F21.at(1, 0), f22 = F21.at(1, 1),
+                    f23 = F21.at(1, 2), f31 = F21.at(2, 0), f32 = F21.at(2, 1), f33 = F21.at(2, 2);
+        in.resize((size_t)N);
+        float score = 0;
+        const float th = 3.841;
+        const float thScore = 5.991;
+        const float invSigmaSquare = 1.0 / (sigma * sigma);
+        for (int i = 0; i < N; i++) {
+            bool bIn = true;
+            const KeyPt& kp1 = mvKeys1[mvMatches12[i].first];
+            const KeyPt& kp2 = mvKeys2[mvMatches12[i].second];
+            const float u1 = kp1.x, v1 = kp1.y, u2 = kp2.x, v2 = kp2.y;
+            const float a2 = f11 * u1 + f12 * v1 + f13;
+            const float b2 = f21 * u1 + f22 * v1 + f23;
+            const float c2 = f31 * u1 + f32 * v1 + f33;
+            const float num2 = a2 * u2 + b2 * v2 + c2;
+            const float squareDist1 = num2 * num2 / (a2 * a2 + b2 * b2);
+            const float chiSquare1 = squareDist1 * invSigmaSquare;
+            if (chiSquare1 > th) bIn = false;
+            else score += thScore - chiSquare1;
+            const float a1 = f11 * u2 + f21 * v2 + f31;
+            const float b1 = f12 * u2 + f22 * v2 + f32;
+            const float c1 = f13 * u2 + f23 * v2 + f33;
+            const float num1 = a1 * u1 + b1 * v1 + c1;
+            const float squareDist2 = num1 * num1 / (a1 * a1 + b1 * b1);
+            const float chiSquare2 = squareDist2 * invSigmaSquare;
+            if (chiSquare2 > th) bIn = false;
+            else score += thScore - chiSquare2;
+            in[i] = bIn;
+        }
+        return score;
+    }
+
+    bool ReconstructF(std::vector<bool>& in, Mat& F21, Mat& K, Mat& R21, Mat& t21, std::vector<float>& vP3D,
+                      std::vector<uint8_t>& vbTriangulated, float minParallax, int minTriangulated, Result& res)
+    {
+        int N = 0;
+        for (size_t i = 0; i < in.size(); i++) if (in[i]) N++;
+        res.nInliers = N;
+        const Mat E21 = mul(mulT1(K, F21), K);
+        Mat R1, R2, t;
+        DecomposeE(E21, R1, R2, t);
+        const Mat t1 = t;
+        const Mat t2 = exprScale(t, -1.0);
+        const Mat* Rs[4] = {&R1, &R2, &R1, &R2};
+        const Mat* ts[4] = {&t1, &t1, &t2, &t2};
+        std::vector<float> P[4];
+        std::vector<uint8_t> G[4];
+        float par[4];
+        int nGood[4];
+        for (int c = 0; c < 4; c++) {
+            nGood[c] = CheckRT(*Rs[c], *ts[c], in, K, P[c], 4.0 * mSigma2, G[c], par[c]);
+            res.nGood[c] = nGood[c];
+            res.parallax[c] = par[c];
+        }
+        res.nCand = 4;
+        const int maxGood = std::max(nGood[0], std::max(nGood[1], std::max(nGood[2], nGood[3])));
+        R21 = Mat();
+        t21 = Mat();
+        res.rtState = 1;
+        const int nMinGood = std::max(static_cast<int>(0.9 * N), minTriangulated);
+        int nsimilar = 0;
+        for (int c = 0; c < 4; c++) if (nGood[c] > 0.7 * maxGood) nsimilar++;
+        int win = -1;   // the else-if chain: the first candidate with maxGood
+        for (int c = 0; c < 4 && win < 0; c++) if (maxGood == nGood[c]) win = c;
+        res.best = win;
+        if (maxGood < nMinGood || nsimilar > 1) return false;
+        if (par[win] > minParallax) {
+            vP3D = P[win];
+            vbTriangulated = G[win];
+            R21 = *Rs[win];
+            t21 = *ts[win];
+            res.rtState = 2;
+            return true;
+        }
+        return false;
+    }
+
+    bool ReconstructH(std::vector<bool>& in, Mat& H21, Mat& K, Mat& R21, Mat& t21, std::vector<float>& vP3D,
+                      std::vector<uint8_t>& vbTriangulated, float minParallax, int minTriangulated, Result& res)
+    {
+        int N = 0;
+        for (size_t i = 0; i < in.size(); i++) if (in[i]) N++;
+        res.nInliers = N;
+        const Mat invK = inv3(K);
+        const Mat A = mul(mul(invK, H21), K);
+        Mat U, w, Vt;
+        svd(A, true, w, U, Vt);
+        const float s = det3(U) * det3(Vt);
+        const float d1 = w.d[0], d2 = w.d[1], d3 = w.d[2];
+        if (d1 / d2 < 1.00001 || d2 / d3 < 1.00001) return false;
+        std::vector<Mat> vR, vt;
+        const float aux1 = std::sqrt((d1 * d1 - d2 * d2) / (d1 * d1 - d3 * d3));
+        const float aux3 = std::sqrt((d2 * d2 - d3 * d3) / (d1 * d1 - d3 * d3));
+        const float x1[] = {aux1, aux1, -aux1, -aux1};
+        const float x3[] = {aux3, -aux3, aux3, -aux3};
+        const float aux_stheta = std::sqrt((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)) / ((d1 + d3) * d2);
+        const float ctheta = (d2 * d2 + d1 * d3) / ((d1 + d3) * d2);
+        const float stheta[] = {aux_stheta, -aux_stheta, -aux_stheta, aux_stheta};
+        for (int i = 0; i < 4; i++) {
+            Mat Rp = eye3();
+            Rp.at(0, 0) = ctheta; Rp.at(0, 2) = -stheta[i]; Rp.at(2, 0) = stheta[i]; Rp.at(2, 2) = ctheta;
+            vR.push_back(mul(mul(U, Rp, (double)s), Vt));
+            Mat tp(3, 1);
+            tp.d[0] = x1[i]; tp.d[1] = 0; tp.d[2] = -x3[i];
+            scaleInPlace(tp, d1 - d3);
+            const Mat t = mul(U, tp);
+            vt.push_back(exprScale(t, 1. / norm(t)));
+        }
+        const float aux_sphi = std::sqrt((d1 * d1 - d2 * d2) * (d2 * d2 - d3 * d3)) / ((d1 - d3) * d2);
+        const float cphi = (d1 * d3 - d2 * d2) / ((d1 - d3) * d2);
+        const float sphi[] = {aux_sphi, -aux_sphi, -aux_sphi, aux_sphi};
+        for (int i = 0; i < 4; i++) {
+            Mat Rp = eye3();
+            Rp.at(0, 0) = cphi; Rp.at(0, 2) = sphi[i]; Rp.at(1, 1) = -1; Rp.at(2, 0) = sphi[i]; Rp.at(2, 2) = -cphi;
+            vR.push_back(mul(mul(U, Rp, (double)s), Vt));
+            Mat tp(3, 1);
+            tp.d[0] = x1[i]; tp.d[1] = 0; tp.d[2] = x3[i];
+            scaleInPlace(tp, d1 + d3);
+            const Mat t = mul(U, tp);
+            vt.push_back(exprScale(t, 1. / norm(t)));
+        }
+        // (the plane normals vn of :654-662 and :692-700 feed nothing: not restated)
+        int bestGood = 0, secondBestGood = 0, bestSolutionIdx = -1;
+        float bestParallax = -1;
+        std::vector<float> bestP3D;
+        std::vector<uint8_t> bestTriangulated;
+        res.nCand = 8;
+        for (int i = 0; i < 8; i++) {
+            float parallaxi;
+            std::vector<float> vP3Di;
+            std::vector<uint8_t> vbTriangulatedi;
+            const int nGood = CheckRT(vR[i], vt[i], in, K, vP3Di, 4.0 * mSigma2, vbTriangulatedi, parallaxi);
+            res.nGood[i] = nGood;
+            res.parallax[i] = parallaxi;
+            if (nGood > bestGood) {
+                secondBestGood = bestGood;
+                bestGood = nGood;
+                bestSolutionIdx = i;
+                bestParallax = parallaxi;
+                bestP3D = vP3Di;
+                bestTriangulated = vbTriangulatedi;
+            } else if (nGood > secondBestGood)
+                secondBestGood = nGood;
+        }
+        res.best = bestSolutionIdx;
+        if (secondBestGood < 0.75 * bestGood && bestParallax >= minParallax && bestGood > minTriangulated && bestGood > 0.9 * N) {
+            R21 = vR[bestSolutionIdx];
+            t21 = vt[bestSolutionIdx];
+            vP3D = bestP3D;
+            vbTriangulated = bestTriangulated;
+            res.rtState = 2;
+            return true;
+        }
+        return false;
+    }
+
+    static void Triangulate(const KeyPt& kp1, const KeyPt& kp2, const Mat& P1, const Mat& P2, Mat& x3D)
+    {
+        // A.row(r) = x*P.row(2) - P.row(0|1): MatOp_AddEx(alpha = x, beta = -1) -> addWeighted_<float, double>
+        // (alpha 1: subtract)
+        Mat A(4, 4);
+        const float xs[4] = {kp1.x, kp1.y, kp2.x, kp2.y};
+        for (int r = 0; r < 4; r++) {
+            const Mat& P = r < 2 ? P1 : P2;
+            const int pr = r & 1;
+            const float x = xs[r];
+            for (int c = 0; c < 4; c++) {
+                if (x == 1.f) A.at(r, c) = P.at(2, c) - P.at(pr, c);
+                else A.at(r, c) = (float)((double)P.at(2, c) * (double)x + (double)P.at(pr, c) * -1.0 + 0.0);
+            }
+        }
+        Mat u, w, vt;
+        svd(A, true, w, u, vt);
+        x3D = Mat(3, 1);
+        const double alpha = 1. / (double)vt.at(3, 3);
+        for (int k = 0; k < 3; k++) x3D.d[k] = exprScale(vt.at(3, k), alpha);
+    }
+
+    int CheckRT(const Mat& R, const Mat& t, const std::vector<bool>& in, const Mat& K, std::vector<float>& vP3D, float th2,
+                std::vector<uint8_t>& vbGood, float& parallax) const
+    {
+        const float fx = K.at(0, 0), fy = K.at(1, 1), cx = K.at(0, 2), cy = K.at(1, 2);
+        vbGood.assign(mvKeys1.size(), 0);
+        vP3D.assign(mvKeys1.size() * 3, 0.f);
+        std::vector<float> vCosParallax;
+        Mat P1(3, 4);
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) P1.at(r, c) = K.at(r, c);
+        const Mat O1(3, 1);
+        Mat Rt(3, 4);
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Rt.at(r, c) = R.at(r, c); Rt.at(r, 3) = t.d[r]; }
+        const Mat P2 = mul(K, Rt);
+        const Mat O2 = mulT1(R, t, -1.0);
+        int nGood = 0;
+        for (size_t i = 0; i < mvMatches12.size(); i++) {
+            if (!in[i]) continue;
+            const KeyPt& kp1 = mvKeys1[mvMatches12[i].first];
+            const KeyPt& kp2 = mvKeys2[mvMatches12[i].second];
+            Mat p3dC1;
+            Triangulate(kp1, kp2, P1, P2, p3dC1);
+            if (!std::isfinite(p3dC1.d[0]) || !std::isfinite(p3dC1.d[1]) || !std::isfinite(p3dC1.d[2])) {
+                vbGood[mvMatches12[i].first] = 0;
+                continue;
+            }
+            const Mat normal1 = sub(p3dC1, O1);
+            const float dist1 = norm(normal1);
+            const Mat normal2 = sub(p3dC1, O2);
+            const float dist2 = norm(normal2);
+            const float cosParallax = dot(normal1, normal2) / (dist1 * dist2);
+            if (p3dC1.d[2] <= 0 && cosParallax < 0.99998) continue;
+            const Mat p3dC2 = mulAdd(R, p3dC1, t);
+            if (p3dC2.d[2] <= 0 && cosParallax < 0.99998) continue;
+            const float invZ1 = 1.0 / p3dC1.d[2];
+            const float im1x = fx * p3dC1.d[0] * invZ1 + cx;
+            const float im1y = fy * p3dC1.d[1] * invZ1 + cy;
+            const float squareError1 = (im1x - kp1.x) * (im1x - kp1.x) + (im1y - kp1.y) * (im1y - kp1.y);
+            if (squareError1 > th2) continue;
+            const float invZ2 = 1.0 / p3dC2.d[2];
+            const float im2x = fx * p3dC2.d[0] * invZ2 + cx;
+            const float im2y = fy * p3dC2.d[1] * invZ2 + cy;
+            const float squareError2 = (im2x - kp2.x) * (im2x - kp2.x) + (im2y - kp2.y) * (im2y - kp2.y);
+            if (squareError2 > th2) continue;
+            vCosParallax.push_back(cosParallax);
+            for (int k = 0; k < 3; k++) vP3D[(size_t)mvMatches12[i].first * 3 + k] = p3dC1.d[k];
+            nGood++;
+            if (cosParallax < 0.99998) vbGood[mvMatches12[i].first] = 1;
+        }
+        if (nGood > 0) {
+            std::sort(vCosParallax.begin(), vCosParallax.end());
+            const size_t idx = std::min(50, int(vCosParallax.size() - 1));
+            parallax = std::acos(vCosParallax[idx]) * 180 / 3.1415926535897932384626433832795;
+        } else
+            parallax = 0;
+        return nGood;
+    }
+
+    static void DecomposeE(const Mat& E, Mat& R1, Mat& R2, Mat& t)
+    {
+        Mat u, w, vt;
+        svd(E, false, w, u, vt);
+        t = Mat(3, 1);
+        for (int r = 0; r < 3; r++) t.d[r] = u.at(r, 2);
+        t = exprScale(t, 1. / norm(t));
+        Mat W(3, 3);
+        W.at(0, 1) = -1; W.at(1, 0) = 1; W.at(2, 2) = 1;
+        R1 = mul(mul(u, W), vt);
+        if (det3(R1) < 0) R1 = exprScale(R1, -1.0);
+        R2 = mul(mulT2(u, W), vt);
+        if (det3(R2) < 0) R2 = exprScale(R2, -1.0);
+    }
+
+    std::vector<KeyPt> mvKeys1, mvKeys2;
+    std::vector<Match> mvMatches12;
+    Mat mK;
+    float mSigma, mSigma2;
+    int mMaxIterations;
+    bool mHF;
+    std::vector<std::vector<size_t>> mvSets;
+};
+
+}  // namespace init_ref
