@@ -207,3 +207,56 @@ def test_initializer_dropin_on_mock_frames(gpu, tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "init dropin ok" in r.stdout
+
+
+# ------------------------------------------------------------------------------------------------ scene families, sizes
+def _device_case(matcher, case, model, iterations=200, sigma=1.0, seed=0):
+    rng = np.random.default_rng(seed)
+    sets = ic.random_sets(rng, int((case["m12"] >= 0).sum()), iterations)
+    got, want = run_both(matcher, case["keys1"], case["keys2"], case["m12"], model=model, iterations=iterations, sigma=sigma,
+                         sets=sets, K=case["K"])
+    ic.assert_equal_results(got, want)
+    ic.check_result(case, got, sigma=sigma, model=model)
+    return got
+
+
+@pytest.mark.parametrize("model", ["HF", "F"])
+@pytest.mark.parametrize("family", ic.FAMILIES)
+def test_scene_families_on_the_device(matcher, family, model):
+    """every family of init_cases (motions, planes, rotation only, coincident rays, shared keys, keys outside the image,
+    collapsed frames), noiseless, noisy and with outliers: bits equal to the restatement, and the float64 check"""
+    import zlib
+    for variant in ic.VARIANTS:
+        rng = np.random.default_rng(zlib.crc32(("%s/%s/%d" % (family, variant, 0)).encode()))
+        case = ic.make_case(family, rng, variant)
+        _device_case(matcher, case, model, seed=1)
+
+
+K_ODD = np.array([700.0, 540.0, 330.5, 238.25], np.float32)           # fx != fy
+
+
+# (matches, iterations, sigma, family, K): the score blocks (256 threads), CheckRT blocks (128), fit blocks (32
+# hypotheses), iterations up to ORBI_MAX_ITERATIONS; frame 1 holds a third more keys than matches, frame 2 a quarter
+SWEEP = [(8, 1, 1.0, "lateral", ic.K_TUM), (9, 8, 0.5, "plane_slanted", K_ODD), (127, 31, 2.0, "lateral", K_ODD),
+         (128, 32, 1.0, "forward", ic.K_TUM), (129, 33, 0.5, "plane_fronto", K_ODD), (255, 257, 1.0, "wide_inward", ic.K_TUM),
+         (256, 4096, 2.0, "lateral", K_ODD), (257, 200, 1.0, "plane_slanted", ic.K_TUM), (511, 31, 0.5, "coincident_rays", K_ODD),
+         (513, 4096, 1.0, "plane_fronto", ic.K_TUM), (4097, 33, 2.0, "large_rotation", K_ODD), (20000, 257, 1.0, "lateral", ic.K_TUM)]
+
+
+@pytest.mark.parametrize("n,iterations,sigma,family,K", SWEEP, ids=["%d-%d-%g-%s" % s[:4] for s in SWEEP])
+def test_sizes_iterations_sigmas_and_intrinsics(matcher, n, iterations, sigma, family, K):
+    rng = np.random.default_rng(n + iterations)
+    case = ic.make_case(family, rng, "outliers" if n >= 50 else "noisy", n_match=n, K=K)
+    for model in ("HF", "F"):
+        _device_case(matcher, case, model, iterations=iterations, sigma=sigma, seed=n)
+
+
+def test_device_reaches_the_branches_the_mutations_would_break(matcher):
+    """the device takes ReconstructH's d1/d2 exit (pure rotation), stores unflagged points (cosParallax >= 0.99998) and
+    selects a negative cosParallax (rays more than 90 degrees apart), each bit-equal to the restatement"""
+    import zlib
+    for family, want in (("rotation", "d1/d2 early exit"), ("coincident_rays", "stored but not flagged"),
+                         ("wide_inward", "negative cosParallax selected")):
+        rng = np.random.default_rng(zlib.crc32(("%s/%s/%d" % (family, "clean", 0)).encode()))
+        got = _device_case(matcher, ic.make_case(family, rng, "clean"), "HF", seed=1)
+        assert want in ic.outcomes(got), (family, ic.outcomes(got))
