@@ -727,6 +727,70 @@ int orbi_size(orbi_t* ini, int* n1);
 int orbi_normalization(orbi_t* ini, float out[4]);
 void orbi_destroy(orbi_t* ini);
 
+/* ---------------------------------------------------------------- Sim3Solver
+ * replaces Sim3Solver (src/Sim3Solver.cc, the same in both scenarios): Horn's closed-form similarity from three
+ * correspondences under RANSAC, as MultiMapper::Run and LoopClosing::ComputeSim3 use it on every loop / merge candidate.
+ * Every hypothesis of every solver of a batch is evaluated in one chain (orbs_run); iterate / find are then replayed on
+ * the host over the per-hypothesis table, with the reference's state.  Results equal the reference's bit for bit given
+ * the same sets (its OpenCV arithmetic is restated, unpinned: §2); the binary64 atan2 / cos / sin of each hypothesis are
+ * taken on the host through libm, as the reference takes them.
+ *
+ * orbs_create: the constructor after its pointer chasing.  The caller walks vpMatched12 (skipping null / bad points and
+ *   negative GetIndexInKeyFrame) and passes the n survivors: idx1 = mvnIndices1 (positions in vpMatched12, n1 long),
+ *   X1w / X2w (n x 3) = GetWorldPos of pMP1 / pMP2, Rcw / tcw = the keyframes' GetRotation / GetTranslation (row-major),
+ *   K = (fx, fy, cx, cy) of mK, sigma2_1 / sigma2_2 = mvLevelSigma2[kp.octave].  Rcw*Xw + tcw, FromCameraToImage and the
+ *   thresholds ((size_t)(9.210*sigma2): truncated, as mvnMaxError1/2 are vector<size_t>) are computed on the device.  It
+ *   ends, as the constructor does, in SetRansacParameters(0.99, 6, 300).  The handle runs on the matcher handle's device
+ *   and stream and holds a reference to it.
+ * orbs_set_ransac: SetRansacParameters (libm on the host); orbs_max_iterations reads mRansacMaxIts back.  It resets
+ *   mnIterations (not mnBestInliers, as in the reference) and drops the table.
+ * orbs_run: every hypothesis 0 .. mRansacMaxIts-1 of every solver, in one chain of launches with one host step in the
+ *   middle.  sets[c] (host, mRansacMaxIts x 3): the RANSAC sets of solvers[c] as indices into its n correspondences,
+ *   which the reference draws with DUtils::Random inside iterate (Sim3Solver.cc:163-177; its draw can repeat a point) --
+ *   the caller draws them the same way.  A solver with n < min_inliers never draws: its sets[c] may be null.  All solvers
+ *   must belong to one matcher handle.  orbs_hypotheses copies a solver's table out.
+ * orbs_iterate: cv::Mat iterate(nIterations, bNoMore, vbInliers, nInliers) over the table; find is
+ *   orbs_iterate(mRansacMaxIts).  inliers (n1 bytes) is cleared, then set at idx1[i] for the inliers of the returning
+ *   hypothesis (recomputed on the device for that hypothesis).  Needs orbs_run first unless n < min_inliers.
+ * orbs_points: the constructor's products, n x 3 planes of 4 floats: (X1c, maxError1), (X2c, maxError2), (p1im1, p2im2).
+ * Refusals (nothing computed): ORBX_E_UNSUPPORTED for more than ORBS_MAX_POINTS correspondences, more than
+ *   ORBS_MAX_ITERATIONS iterations, or n < 3 with n >= min_inliers (the reference would draw from an emptied vector);
+ *   ORBX_E_INVALID for a null argument, idx1 outside [0, n1), a set index outside [0, n), solvers of different handles
+ *   or repeated in a batch, orbs_iterate / orbs_hypotheses without a table. */
+#define ORBS_MAX_POINTS 65535
+#define ORBS_MAX_ITERATIONS 4096
+typedef struct {
+    int32_t n_inliers;         /* mnInliersi */
+    float s12;                 /* ms12i */
+    float T12[16], R12[9], t12[3];   /* mT12i (row-major 4x4), mR12i, mt12i */
+} OrbsHypothesis;
+typedef struct {
+    int32_t returned;          /* 1: iterate returned T12 (else the empty cv::Mat) */
+    int32_t no_more;           /* bNoMore */
+    int32_t n_inliers;         /* nInliers */
+    int32_t hypothesis;        /* the iteration that returned (0-based), -1: none */
+    int32_t iterations;        /* mnIterations after the call */
+    int32_t best_inliers;      /* mnBestInliers after the call */
+    int32_t has_best;          /* 1: some hypothesis has passed `>= mnBestInliers` (the best fields are written) */
+    float T12[16];             /* the returned matrix (returned == 1) */
+    float best_R[9], best_t[3], best_s;   /* GetEstimatedRotation / Translation / Scale */
+} OrbsResult;
+typedef struct orbs_solver orbs_t;
+int orbs_create(orbm_t* h, int n1, const int32_t* idx1, int n, const float* X1w, const float* X2w, const float Rcw1[9],
+                const float tcw1[3], const float Rcw2[9], const float tcw2[3], const float K1[4], const float K2[4],
+                const float* sigma2_1, const float* sigma2_2, int fix_scale, orbs_t** out);
+int orbs_set_ransac(orbs_t* s, double probability, int min_inliers, int max_iterations);
+int orbs_max_iterations(orbs_t* s, int* iterations);
+int orbs_size(orbs_t* s, int* n, int* n1);
+int orbs_points(orbs_t* s, float* out);
+int orbs_run(orbs_t* const* solvers, int count, const int32_t* const* sets);
+int orbs_hypotheses(orbs_t* s, OrbsHypothesis* out, int cap, int* n_out);
+int orbs_iterate(orbs_t* s, int n_iterations, OrbsResult* res, uint8_t* inliers);
+/* host-clock milliseconds of the legs of the last orbs_run this solver took part in: upload + fit + quaternions down,
+ * the host's libm step, rotations up + pose + score + table down (tools/sim3_bench.py) */
+int orbs_last_run_ms(orbs_t* s, double ms[3]);
+void orbs_destroy(orbs_t* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,12 @@ EXPORTS_INIT = [
     "orbi_create", "orbi_create_frame", "orbi_initialize", "orbi_initialize_frame", "orbi_size", "orbi_normalization", "orbi_destroy",
 ]
 
+# the Sim3Solver's block (orbs_*)
+EXPORTS_SIM3 = [
+    "orbs_create", "orbs_set_ransac", "orbs_max_iterations", "orbs_size", "orbs_points", "orbs_run", "orbs_hypotheses", "orbs_iterate",
+    "orbs_last_run_ms", "orbs_destroy",
+]
+
 
 def build(force=False):
     """hipcc the extension in-tree for gfx950 (cross-compiles without a GPU)."""
@@ -141,7 +147,7 @@ def lib():
         L = C.CDLL(os.environ.get("ORBSLAMM_HIP_LIB") or SO_PATH)
         L.orbx_last_error.restype = C.c_char_p
         L.orbx_scale_factor.restype = C.c_float
-        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT:
+        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3:
             getattr(L, name)
         L.orbx_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _lib = L

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -39,6 +41,7 @@
 #include "orbv_kernels.hip"
 #include "orbk_kernels.hip"
 #include "orbi_kernels.hip"
+#include "orbs_kernels.hip"
 
 using namespace orbx;
 
@@ -180,3 +183,4 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbt_bow_host.inc"
 #include "orbk_host.inc"   // keyframe database
 #include "orbi_host.inc"   // Initializer
+#include "orbs_host.inc"   // Sim3Solver
