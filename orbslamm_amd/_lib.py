@@ -169,6 +169,38 @@ def ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def K4(K):
+    """a camera matrix as the C ABI takes it: float32 (fx, fy, cx, cy), from that or from the 3x3 K"""
+    K = np.asarray(K, dtype=np.float32)
+    if K.shape == (3, 3):
+        K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], dtype=np.float32)
+    return np.ascontiguousarray(K.reshape(4))
+
+
+RAND_MAX = 2147483647   # glibc's
+_libc = None
+
+
+def libc():
+    """the process's libc, for the rand() stream the reference's RANSAC draws consume"""
+    global _libc
+    if _libc is None:
+        _libc = C.CDLL(None)
+        _libc.rand.restype = C.c_int
+    return _libc
+
+
+def seed_rand(seed):
+    """DUtils::Random::SeedRandOnce(seed) is srand(seed); None continues the process's stream"""
+    if seed is not None:
+        libc().srand(C.c_uint(int(seed)))
+
+
+def random_int(k):
+    """DUtils::Random::RandomInt(0, k - 1): int(rand() / (RAND_MAX + 1.0) * k), one call of libc's rand()"""
+    return int((float(libc().rand()) / (RAND_MAX + 1.0)) * k)
+
+
 def device_pci_bus_id(device):
     """"0000:c1:00.0" or None"""
     buf = C.create_string_buffer(32)

@@ -3,30 +3,20 @@
 // compacted here), one packed upload, the launches, one copy down, and the last comparisons of ReconstructF /
 // ReconstructH, which need acosf of one value per candidate.
 
-struct orbi_init {
-    orbm_handle* h = nullptr;            // device and stream; a reference is held
+struct orbi_init : orbm_solver_base {    // (h_stage: the upload, then the results)
     int model = ORBI_MODEL_HF, iters = 0, n1 = 0;
     float K[4] = {0.f, 0.f, 0.f, 0.f};
     float sigma = 1.f;
     orbi::Key* d_keys1 = nullptr;        // mvKeys1 (n1) ...
     orbi::Norm* d_norm = nullptr;        // ... behind it: Normalize of frame 1 (cached) and frame 2 (per call)
     orbi::Norm norm1{};
-    void* d_work = nullptr; size_t workCap = 0;
-    uint8_t* h_stage = nullptr; size_t stageCap = 0;   // pinned: the upload, then the results
     std::vector<orbi::Pair> pairs;
 };
 
 static void orbi_free(orbi_init* ini)
 {
     if (!ini) return;
-    if (ini->h) {
-        (void)hipSetDevice(ini->h->device);
-        (void)hipStreamSynchronize(ini->h->stream);
-        if (ini->d_keys1) (void)hipFree(ini->d_keys1);
-        if (ini->d_work) (void)hipFree(ini->d_work);
-        if (ini->h_stage) (void)hipHostFree(ini->h_stage);
-        orbm_release(ini->h);
-    }
+    ini->release({ini->d_keys1});
     delete ini;
 }
 
@@ -45,23 +35,20 @@ static int orbi_make(orbm_handle* h, const OrbxKeyPoint* hkeys, orbm_frame* f1, 
     if (iterations > ORBI_MAX_ITERATIONS) return fail(ORBX_E_UNSUPPORTED, "iterations %d above %d", iterations, ORBI_MAX_ITERATIONS);
     if (n1 > ORBI_MAX_FEATURES) return fail(ORBX_E_UNSUPPORTED, "%d keys in frame 1: above %d", n1, ORBI_MAX_FEATURES);
     orbi_init* ini = new orbi_init();
-    ini->h = h;
-    h->refs++;
+    ini->attach(h);
     ini->model = model; ini->iters = iterations; ini->n1 = n1; ini->sigma = sigma;
     for (int k = 0; k < 4; k++) ini->K[k] = K[k];
     const size_t keyBytes = ((size_t)std::max(n1, 1) * sizeof(orbi::Key) + 255) & ~(size_t)255;
-#define ICR(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { int r_ = fail(ORBX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); orbi_free(ini); return r_; } } while (0)
-    ICR(hipMalloc((void**)&ini->d_keys1, keyBytes + 2 * sizeof(orbi::Norm)));
+    HIPCHK_OR(hipMalloc((void**)&ini->d_keys1, keyBytes + 2 * sizeof(orbi::Norm)), orbi_free(ini));
     ini->d_norm = (orbi::Norm*)((uint8_t*)ini->d_keys1 + keyBytes);
     if (n1) {
-        if (f1) ICR(hipMemcpyAsync(ini->d_keys1, f1->d_keysUn, (size_t)n1 * sizeof(orbi::Key), hipMemcpyDeviceToDevice, h->stream));
-        else ICR(hipMemcpyAsync(ini->d_keys1, hkeys, (size_t)n1 * sizeof(orbi::Key), hipMemcpyHostToDevice, h->stream));
+        if (f1) HIPCHK_OR(hipMemcpyAsync(ini->d_keys1, f1->d_keysUn, (size_t)n1 * sizeof(orbi::Key), hipMemcpyDeviceToDevice, h->stream), orbi_free(ini));
+        else HIPCHK_OR(hipMemcpyAsync(ini->d_keys1, hkeys, (size_t)n1 * sizeof(orbi::Key), hipMemcpyHostToDevice, h->stream), orbi_free(ini));
         hipLaunchKernelGGL(orbi::k_init_normalize, dim3(1), dim3(orbi::kNormThreads), 0, h->stream, ini->d_keys1, n1, ini->d_keys1, n1, ini->d_norm);
-        ICR(hipGetLastError());
-        ICR(hipMemcpyAsync(&ini->norm1, ini->d_norm, sizeof(orbi::Norm), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK_OR(hipGetLastError(), orbi_free(ini));
+        HIPCHK_OR(hipMemcpyAsync(&ini->norm1, ini->d_norm, sizeof(orbi::Norm), hipMemcpyDeviceToHost, h->stream), orbi_free(ini));
     }
-    ICR(hipStreamSynchronize(h->stream));
-#undef ICR
+    HIPCHK_OR(hipStreamSynchronize(h->stream), orbi_free(ini));
     *out = ini;
     return ORBX_OK;
 }
@@ -124,22 +111,7 @@ static int orbi_run(orbi_init* ini, const OrbxKeyPoint* hkeys2, const orbi::Key*
                  oScH = pk.take(hf ? (size_t)iters * 4 : 0), oRec = pk.take((size_t)8 * N * sizeof(float4)), oFlag = pk.take((size_t)8 * N);
     const size_t oHdr = pk.take(sizeof(orbi::Hdr)), oP3D = pk.take((size_t)n1 * 12), oTri = pk.take((size_t)n1), total = pk.off;
     const size_t downBytes = total - oHdr;
-    if (total > ini->workCap) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (ini->d_work) HIPCHK(hipFree(ini->d_work));
-        ini->d_work = nullptr; ini->workCap = 0;
-        const size_t want = std::max<size_t>(total * 3 / 2, 1 << 16);
-        HIPCHK(hipMalloc(&ini->d_work, want));
-        ini->workCap = want;
-    }
-    const size_t stage = std::max(upBytes, downBytes);
-    if (stage > ini->stageCap) {
-        if (ini->h_stage) HIPCHK(hipHostFree(ini->h_stage));
-        ini->h_stage = nullptr; ini->stageCap = 0;
-        const size_t want = std::max<size_t>(stage * 3 / 2, 1 << 16);
-        HIPCHK(hipHostMalloc((void**)&ini->h_stage, want, hipHostMallocDefault));
-        ini->stageCap = want;
-    }
+    if ((rc = ini->reserve(total, std::max(upBytes, downBytes)))) return rc;
     uint8_t* hs = ini->h_stage;
     uint8_t* d = (uint8_t*)ini->d_work;
     if (hkeys2 && n2) memcpy(hs + oKeys2, hkeys2, (size_t)n2 * sizeof(orbi::Key));

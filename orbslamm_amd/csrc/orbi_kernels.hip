@@ -48,97 +48,9 @@ struct Hdr {
     int32_t pad[3];
 };
 
-// ------------------------------------------------------------------ OpenCV 3.0 arithmetic (3x3 row-major, CV_32F)
-// gemm's small-matrix branch (flags 0, len 3): float products summed left to right, d = (float)(t*alpha + 0*0)
-__device__ __forceinline__ float gemm_out(float t, double alpha) { return (float)((double)t * alpha + (double)0.f * 0.0); }
-__device__ inline void mm3(const float* A, const float* B, float* D, double alpha = 1.0)
-{
-    float o[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) o[3 * i + j] = gemm_out(A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j], alpha);
-#pragma unroll
-    for (int k = 0; k < 9; k++) D[k] = o[k];
-}
-__device__ inline void mv3(const float* A, const float* b, float* d)
-{
-    float o[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) o[i] = gemm_out(A[3 * i] * b[0] + A[3 * i + 1] * b[1] + A[3 * i + 2] * b[2], 1.0);
-#pragma unroll
-    for (int i = 0; i < 3; i++) d[i] = o[i];
-}
-// GEMM_1_T / GEMM_2_T: GEMMSingleMul<float, double>, double sums in k order
-__device__ inline void mm3_t1(const float* A, const float* B, float* D)   // A.t()*B
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double s = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) s += (double)A[3 * k + i] * (double)B[3 * k + j];
-            D[3 * i + j] = (float)(s * 1.0);
-        }
-}
-__device__ inline void mm3_t2(const float* A, const float* B, float* D)   // A*B.t()
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double s = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) s += (double)A[3 * i + k] * (double)B[3 * j + k];
-            D[3 * i + j] = (float)(s * 1.0);
-        }
-}
-// MatOp_AddEx::assign of alpha*A: 1 -> A + 0, -1 -> 0 - A, else convertTo with a double scale
-__device__ __forceinline__ float expr_scale(float x, double alpha)
-{
-    if (alpha == 1.0) return x + 0.f;
-    if (alpha == -1.0) return 0.f - x;
-    return (float)((double)x * alpha);
-}
-__device__ __forceinline__ double norm3(const float* v)
-{
-    double s = 0;
-#pragma unroll
-    for (int i = 0; i < 3; i++) s += (double)v[i] * (double)v[i];
-    return sqrt(s);
-}
-__device__ __forceinline__ double det3(const float* m)
-{
-    return m[0] * ((double)m[4] * m[8] - (double)m[5] * m[7]) - m[1] * ((double)m[3] * m[8] - (double)m[5] * m[6]) +
-           m[2] * ((double)m[3] * m[7] - (double)m[4] * m[6]);
-}
-__device__ inline void inv3(const float* S, float* D)
-{
-    double d = det3(S);
-    if (d == 0.) {
-#pragma unroll
-        for (int k = 0; k < 9; k++) D[k] = 0.f;
-        return;
-    }
-    d = 1. / d;
-    const double t0 = ((double)S[4] * S[8] - (double)S[5] * S[7]) * d, t1 = ((double)S[2] * S[7] - (double)S[1] * S[8]) * d,
-                 t2 = ((double)S[1] * S[5] - (double)S[2] * S[4]) * d, t3 = ((double)S[5] * S[6] - (double)S[3] * S[8]) * d,
-                 t4 = ((double)S[0] * S[8] - (double)S[2] * S[6]) * d, t5 = ((double)S[2] * S[3] - (double)S[0] * S[5]) * d,
-                 t6 = ((double)S[3] * S[7] - (double)S[4] * S[6]) * d, t7 = ((double)S[1] * S[6] - (double)S[0] * S[7]) * d,
-                 t8 = ((double)S[0] * S[4] - (double)S[1] * S[3]) * d;
-    D[0] = (float)t0; D[1] = (float)t1; D[2] = (float)t2; D[3] = (float)t3; D[4] = (float)t4;
-    D[5] = (float)t5; D[6] = (float)t6; D[7] = (float)t7; D[8] = (float)t8;
-}
-// lapack.cpp's hypot, written out in binary64 (a defined choice: not libm's)
-__device__ __forceinline__ double hypot_cv(double a, double b)
-{
-    a = fabs(a);
-    b = fabs(b);
-    if (a > b) { b /= a; return a * sqrt(1 + b * b); }
-    if (b > 0) { a /= b; return b * sqrt(1 + a * a); }
-    return 0;
-}
+// OpenCV 3.0 arithmetic (3x3 row-major, CV_32F): orbx_cvmath.hpp
+using cvm::det3; using cvm::expr_scale; using cvm::gemm3_elem; using cvm::hypot_cv; using cvm::inv3; using cvm::mm3; using cvm::mm3_t1;
+using cvm::mm3_t2; using cvm::mv3; using cvm::norm3;
 
 // JacobiSVDImpl_<float>(At, .., W, Vt, .., m, n, n1, FLT_MIN, FLT_EPSILON*2) on arrays in LDS.  S threads interleave
 // their arrays: element (i, k) of At at At[(i*m + k)*S], of Vt at Vt[(i*n + k)*S], W[i] at W[i*S] (double; on return the
@@ -581,7 +493,7 @@ __global__ __launch_bounds__(kRtThreads) void k_init_checkrt(const Key* __restri
     float P1[12] = {fx, 0.f, cx, 0.f, 0.f, fy, cy, 0.f, 0.f, 0.f, 1.f, 0.f}, P2[12], Rt[12], O2[3];
     for (int r = 0; r < 3; r++) { for (int k = 0; k < 3; k++) Rt[4 * r + k] = R[3 * r + k]; Rt[4 * r + 3] = t[r]; }
     for (int r = 0; r < 3; r++)
-        for (int j = 0; j < 4; j++) P2[4 * r + j] = gemm_out(K[3 * r] * Rt[j] + K[3 * r + 1] * Rt[4 + j] + K[3 * r + 2] * Rt[8 + j], 1.0);
+        for (int j = 0; j < 4; j++) P2[4 * r + j] = gemm3_elem(K[3 * r], K[3 * r + 1], K[3 * r + 2], Rt[j], Rt[4 + j], Rt[8 + j], 1.0, 0.f, 0.0);
     for (int r = 0; r < 3; r++) {
         double s = 0;
         for (int k = 0; k < 3; k++) s += (double)R[3 * k + r] * (double)t[k];
@@ -617,7 +529,7 @@ __global__ __launch_bounds__(kRtThreads) void k_init_checkrt(const Key* __restri
     const float cosParallax = dt / (dist1 * dist2);
     if (X[2] <= 0 && cosParallax < 0.99998) return;
     float X2[3];
-    for (int r = 0; r < 3; r++) X2[r] = (float)((double)(R[3 * r] * X[0] + R[3 * r + 1] * X[1] + R[3 * r + 2] * X[2]) * 1.0 + (double)t[r] * 1.0);
+    for (int r = 0; r < 3; r++) X2[r] = gemm3_elem(R[3 * r], R[3 * r + 1], R[3 * r + 2], X[0], X[1], X[2], 1.0, t[r], 1.0);   // R*X + t: gemm with C
     if (X2[2] <= 0 && cosParallax < 0.99998) return;
     const float th2 = 4.0 * (double)(sigma * sigma);
     const float invZ1 = 1.0 / X[2];

@@ -78,28 +78,11 @@ struct orbk_db {
     std::vector<int32_t> lastSlots; std::vector<float> lastScores;   // lScoreAndMatch of the last single query
 };
 
-static int kbuf_reserve(orbk_pool* p, KBuf& b, size_t bytes)
-{
-    if (bytes <= b.cap) return ORBX_OK;
-    if (b.p) { HIPCHK(hipStreamSynchronize(p->stream)); HIPCHK(hipFree(b.p)); }
-    b.p = nullptr; b.cap = 0;
-    const size_t want = std::max<size_t>(bytes * 3 / 2, 4096);
-    HIPCHK(hipMalloc(&b.p, want));
-    b.cap = want;
-    return ORBX_OK;
-}
+// (the stream is drained only where there is an old block that queued kernels may read)
+static int kbuf_reserve(orbk_pool* p, KBuf& b, size_t bytes) { return grow_device(b.p, b.cap, bytes, 4096, b.p ? &p->stream : nullptr); }
 
-static int kf_stage(orbk_pool* p, size_t bytes)
-{
-    if (bytes <= p->h_stageCap) return ORBX_OK;
-    HIPCHK(hipStreamSynchronize(p->stream));   // (copies from / into the old block may be in flight)
-    if (p->h_stage) HIPCHK(hipHostFree(p->h_stage));
-    p->h_stage = nullptr; p->h_stageCap = 0;
-    const size_t want = std::max<size_t>(bytes * 3 / 2, 1 << 16);
-    HIPCHK(hipHostMalloc(&p->h_stage, want, hipHostMallocDefault));
-    p->h_stageCap = want;
-    return ORBX_OK;
-}
+// (copies from / into the old block may be in flight)
+static int kf_stage(orbk_pool* p, size_t bytes) { return grow_pinned(p->h_stage, p->h_stageCap, bytes, false, &p->stream); }
 
 template <class T>
 static int kf_grow_array(orbk_pool* p, T*& a, size_t oldN, size_t newN, int fill)
@@ -191,16 +174,14 @@ extern "C" int orbk_pool_create(orbv_t* voc, int slots, orbk_pool_t** out)
     if (voc->scoring != 0) return fail(ORBX_E_UNSUPPORTED, "scoring type %d: the keyframe database scores with L1_NORM only", voc->scoring);
     orbk_pool* p = new orbk_pool();
     p->voc = voc; p->device = voc->device; p->nWords = voc->nWords; p->vocSerial = voc->serial;
-#define KCRT(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { int r_ = fail(ORBX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); orbk_pool_destroy(p); return r_; } } while (0)
-    KCRT(hipSetDevice(p->device));
-    KCRT(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    KCRT(hipEventCreateWithFlags(&p->evIn, hipEventDisableTiming));
-    KCRT(hipEventCreateWithFlags(&p->evOut, hipEventDisableTiming));
-    KCRT(hipMalloc(&p->d_wEpoch, (size_t)std::max(p->nWords, 1) * 4));
-    KCRT(hipMalloc(&p->d_wIdx, (size_t)std::max(p->nWords, 1) * 4));
-    KCRT(hipMemset(p->d_wEpoch, 0, (size_t)std::max(p->nWords, 1) * 4));
-    KCRT(hipMemset(p->d_wIdx, 0, (size_t)std::max(p->nWords, 1) * 4));
-#undef KCRT
+    HIPCHK_OR(hipSetDevice(p->device), orbk_pool_destroy(p));
+    HIPCHK_OR(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking), orbk_pool_destroy(p));
+    HIPCHK_OR(hipEventCreateWithFlags(&p->evIn, hipEventDisableTiming), orbk_pool_destroy(p));
+    HIPCHK_OR(hipEventCreateWithFlags(&p->evOut, hipEventDisableTiming), orbk_pool_destroy(p));
+    HIPCHK_OR(hipMalloc(&p->d_wEpoch, (size_t)std::max(p->nWords, 1) * 4), orbk_pool_destroy(p));
+    HIPCHK_OR(hipMalloc(&p->d_wIdx, (size_t)std::max(p->nWords, 1) * 4), orbk_pool_destroy(p));
+    HIPCHK_OR(hipMemset(p->d_wEpoch, 0, (size_t)std::max(p->nWords, 1) * 4), orbk_pool_destroy(p));
+    HIPCHK_OR(hipMemset(p->d_wIdx, 0, (size_t)std::max(p->nWords, 1) * 4), orbk_pool_destroy(p));
     live_add(p);
     int rc = kf_grow_slots(p, std::max(slots, 1));
     if (!rc) rc = kf_grow_arena(p, 1);

@@ -98,17 +98,7 @@ struct orbm_handle {
 };
 static std::atomic<int64_t> g_orbmHandlesMade{0};
 
-static int orbm_reserve(orbm_handle* h, int slot, size_t bytes)
-{
-    if (bytes <= h->d_cap[slot]) return ORBX_OK;
-    if (h->d_buf[slot]) HIPCHK(hipFree(h->d_buf[slot]));
-    h->d_buf[slot] = nullptr; h->d_cap[slot] = 0;
-    const size_t want = std::max<size_t>(bytes * 3 / 2, 4096);
-    HIPCHK(hipMalloc(&h->d_buf[slot], want));
-    h->nDevAlloc++;
-    h->d_cap[slot] = want;
-    return ORBX_OK;
-}
+static int orbm_reserve(orbm_handle* h, int slot, size_t bytes) { return grow_device(h->d_buf[slot], h->d_cap[slot], bytes, 4096, nullptr, &h->nDevAlloc); }
 
 // own_stream: a queue of the handle's own (orbm_create); otherwise one of the device's four chain streams, shared with the
 // latency extractors (DESIGN.md section 4: every queue a process owns takes part in the GPU's rotation, busy or not -- a
@@ -177,6 +167,33 @@ extern "C" void orbm_destroy(orbm_t* h)
     live_remove(h);   // no new calls; frames that still point here keep the memory alive (orbm_release)
     orbm_release(h);
 }
+
+// What a solver made on a matcher handle holds of it (the Initializer, the Sim3Solver): a reference to the handle, whose
+// device and stream it works on, a grow-only device work block and the pinned block of its uploads and downloads.
+namespace {   // (its inline members are no exports of the library)
+struct orbm_solver_base {
+    orbm_handle* h = nullptr;            // device and stream; a reference is held
+    void* d_work = nullptr; size_t workCap = 0;
+    uint8_t* h_stage = nullptr; size_t stageCap = 0;
+    void attach(orbm_handle* handle) { h = handle; h->refs++; }
+    int reserve(size_t work, size_t stage)
+    {
+        const int rc = grow_device(d_work, workCap, work, 1 << 16, &h->stream);
+        return rc ? rc : grow_pinned(h_stage, stageCap, stage, false);
+    }
+    // drains the stream, frees the solver's own device blocks and the two above, lets go of the handle
+    void release(std::initializer_list<void*> own)
+    {
+        if (!h) return;
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        for (void* p : own) if (p) (void)hipFree(p);
+        if (d_work) (void)hipFree(d_work);
+        if (h_stage) (void)hipHostFree(h_stage);
+        orbm_release(h);
+    }
+};
+}  // namespace
 
 // The calling thread's matcher handle for `device` (ORBmatcher.h:37-102: the state an ORBmatcher temporary needs but
 // cannot own).  Made at the first call of a thread, returned as is afterwards; released when the thread ends.
@@ -604,7 +621,6 @@ extern "C" int orbm_frame_create(orbm_t* h, const OrbxKeyPoint* d_keys, const ui
     f->d_fill = (int32_t*)(b + oFill); f->d_idx = (int32_t*)(b + oIdx); f->d_ang = (float*)(b + oAng); f->d_rec = (uint4*)(b + oRec);
     f->d_n = (int32_t*)(b + oN); f->d_fvStart = (int32_t*)(b + oFvS); f->d_fvIdx = (int32_t*)(b + oFvI);
     hipStream_t s = h->stream;
-#define FCR(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { int r_ = fail(ORBX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); orbm_frame_destroy(f); return r_; } } while (0)
     if (ncell <= kProjMaxCells && n <= 16384 && !((uintptr_t)d_desc & 15)) {
         // one launch: mvKeysUn, angles, descriptors, grid, grid-ordered records
         orbt::FrameBuildArgs fa{};
@@ -618,22 +634,21 @@ extern "C" int orbm_frame_create(orbm_t* h, const OrbxKeyPoint* d_keys, const ui
         if ((rc = frame_build_launch(h, fa, 1))) { orbm_frame_destroy(f); return rc; }
     } else {
         if (n) {
-            FCR(hipMemcpyAsync(f->d_desc, d_desc, (size_t)n * 32, hipMemcpyDeviceToDevice, s));
+            HIPCHK_OR(hipMemcpyAsync(f->d_desc, d_desc, (size_t)n * 32, hipMemcpyDeviceToDevice, s), orbm_frame_destroy(f));
             if (D[0] == 0.0f) {  // mvKeysUn = mvKeys (Frame.cc:406-410)
-                FCR(hipMemcpyAsync(f->d_keysUn, d_keys, (size_t)n * sizeof(OrbxKeyPoint), hipMemcpyDeviceToDevice, s));
+                HIPCHK_OR(hipMemcpyAsync(f->d_keysUn, d_keys, (size_t)n * sizeof(OrbxKeyPoint), hipMemcpyDeviceToDevice, s), orbm_frame_destroy(f));
             } else {
                 orbm::UndistArgs a = {K[0], K[1], K[2], K[3], D[0], D[1], D[2], D[3], D[4]};
                 hipLaunchKernelGGL(orbm::k_undistort, dim3((n + 255) / 256), dim3(256), 0, s, (const orbm::KeyDev*)d_keys, n, a, f->d_keysUn);
             }
-            FCR(hipMemcpy2DAsync(f->d_ang, 4, (const uint8_t*)d_keys + 12, sizeof(OrbxKeyPoint), 4, (size_t)n, hipMemcpyDeviceToDevice, s));
+            HIPCHK_OR(hipMemcpy2DAsync(f->d_ang, 4, (const uint8_t*)d_keys + 12, sizeof(OrbxKeyPoint), 4, (size_t)n, hipMemcpyDeviceToDevice, s), orbm_frame_destroy(f));
         }
         if ((rc = grid_build_device(grid, f->d_keysUn, n, f->d_cnt, f->d_start, f->d_fill, f->d_idx, s, f->gd))) { orbm_frame_destroy(f); return rc; }
         // the grid-ordered records the projection searches walk (a frame this large is searched from memory: ProjCommon::big)
         if (n) hipLaunchKernelGGL(orbm::k_grid_records, dim3((n + 255) / 256), dim3(256), 0, s, (const orbm::KeyDev*)f->d_keysUn, (const int32_t*)f->d_start, ncell,
                                   (const int32_t*)f->d_idx, f->d_rec);
-        FCR(hipGetLastError());
+        HIPCHK_OR(hipGetLastError(), orbm_frame_destroy(f));
     }
-#undef FCR
     *out = f;
     return ORBX_OK;
 }

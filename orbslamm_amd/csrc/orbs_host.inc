@@ -4,8 +4,7 @@
 // calls; the device's are other implementations), the pose and score kernels finish.  orbs_iterate replays the
 // reference's iterate over the per-hypothesis table with the solver's state, on integers.
 
-struct orbs_solver {
-    orbm_handle* h = nullptr;            // device and stream; a reference is held
+struct orbs_solver : orbm_solver_base {  // (a batch's transit buffers, d_work and h_stage, live in its first solver)
     int n1 = 0, n = 0, fixScale = 0;
     float cam[32] = {0};                 // Rcw1, tcw1, Rcw2, tcw2, K1, K2
     std::vector<int32_t> idx1;           // mvnIndices1
@@ -22,9 +21,6 @@ struct orbs_solver {
     // the table of the last orbs_run
     bool tableValid = false;
     std::vector<OrbsHypothesis> table;
-    // a batch's transit buffers live in its first solver
-    void* d_work = nullptr; size_t workCap = 0;
-    uint8_t* h_stage = nullptr; size_t stageCap = 0;
     double runMs[3] = {0, 0, 0};         // the last batch's legs: up + fit + down, host libm, up + pose + score + down
 };
 
@@ -33,17 +29,7 @@ static_assert(sizeof(OrbsHypothesis) == orbs::kHypWords * 4, "OrbsHypothesis lay
 static void orbs_free(orbs_solver* s)
 {
     if (!s) return;
-    if (s->h) {
-        (void)hipSetDevice(s->h->device);
-        (void)hipStreamSynchronize(s->h->stream);
-        if (s->d_pts) (void)hipFree(s->d_pts);
-        if (s->d_cam) (void)hipFree(s->d_cam);
-        if (s->d_pose) (void)hipFree(s->d_pose);
-        if (s->d_mask) (void)hipFree(s->d_mask);
-        if (s->d_work) (void)hipFree(s->d_work);
-        if (s->h_stage) (void)hipHostFree(s->h_stage);
-        orbm_release(s->h);
-    }
+    s->release({s->d_pts, s->d_cam, s->d_pose, s->d_mask});
     delete s;
 }
 
@@ -93,18 +79,16 @@ extern "C" int orbs_create(orbm_t* h, int n1, const int32_t* idx1, int n, const 
     for (int i = 0; i < n; i++)
         if (idx1[i] < 0 || idx1[i] >= n1) return fail(ORBX_E_INVALID, "idx1[%d] = %d outside [0, %d)", i, idx1[i], n1);
     orbs_solver* s = new orbs_solver();
-    s->h = h;
-    h->refs++;
+    s->attach(h);
     s->n1 = n1; s->n = n; s->fixScale = fix_scale ? 1 : 0;
     s->idx1.assign(idx1, idx1 + n);
     memcpy(s->cam, Rcw1, 36); memcpy(s->cam + 9, tcw1, 12); memcpy(s->cam + 12, Rcw2, 36); memcpy(s->cam + 21, tcw2, 12);
     memcpy(s->cam + 24, K1, 16); memcpy(s->cam + 28, K2, 16);
-#define SCR(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { int r_ = fail(ORBX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); orbs_free(s); return r_; } } while (0)
     const int np = std::max(n, 1);
-    SCR(hipMalloc((void**)&s->d_pts, (size_t)np * 5 * sizeof(float4)));   // three planes, then the two input planes
-    SCR(hipMalloc((void**)&s->d_cam, sizeof s->cam));
-    SCR(hipMalloc((void**)&s->d_mask, (size_t)np));
-    SCR(hipMemcpyAsync(s->d_cam, s->cam, sizeof s->cam, hipMemcpyHostToDevice, h->stream));
+    HIPCHK_OR(hipMalloc((void**)&s->d_pts, (size_t)np * 5 * sizeof(float4)), orbs_free(s));   // three planes, then the two input planes
+    HIPCHK_OR(hipMalloc((void**)&s->d_cam, sizeof s->cam), orbs_free(s));
+    HIPCHK_OR(hipMalloc((void**)&s->d_mask, (size_t)np), orbs_free(s));
+    HIPCHK_OR(hipMemcpyAsync(s->d_cam, s->cam, sizeof s->cam, hipMemcpyHostToDevice, h->stream), orbs_free(s));
     if (n) {
         std::vector<float4> in((size_t)2 * n);
         for (int i = 0; i < n; i++) {
@@ -112,14 +96,13 @@ extern "C" int orbs_create(orbm_t* h, int n1, const int32_t* idx1, int n, const 
             in[(size_t)n + i] = make_float4(X2w[i * 3], X2w[i * 3 + 1], X2w[i * 3 + 2], sigma2_2[i]);
         }
         float4* d_in = s->d_pts + (size_t)3 * n;
-        SCR(hipMemcpyAsync(d_in, in.data(), in.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+        HIPCHK_OR(hipMemcpyAsync(d_in, in.data(), in.size() * sizeof(float4), hipMemcpyHostToDevice, h->stream), orbs_free(s));
         hipLaunchKernelGGL(orbs::k_sim3_points, dim3((n + orbs::kPointThreads - 1) / orbs::kPointThreads), dim3(orbs::kPointThreads), 0, h->stream,
                            (const float4*)d_in, n, (const float*)s->d_cam, s->d_pts);
-        SCR(hipGetLastError());
-        SCR(hipStreamSynchronize(h->stream));   // (`in` is pageable and local)
+        HIPCHK_OR(hipGetLastError(), orbs_free(s));
+        HIPCHK_OR(hipStreamSynchronize(h->stream), orbs_free(s));   // (`in` is pageable and local)
     } else
-        SCR(hipStreamSynchronize(h->stream));
-#undef SCR
+        HIPCHK_OR(hipStreamSynchronize(h->stream), orbs_free(s));
     // the constructor ends in SetRansacParameters()
     s->maxIts = orbs_ransac_iterations(n, s->prob, s->minInliers, 300);
     *out = s;
@@ -162,11 +145,7 @@ static void orbs_rotation(const float q[4], float R[9])
     const double ang = std::atan2(nrm, (double)q[0]);
     // vec = 2*ang*vec/norm(vec): one MatExpr, alpha = (2*ang) * (1./norm); 0 * inf = NaN when the imaginary part is zero
     const double alpha = (2 * ang) * (1. / nrm);
-    for (int k = 0; k < 3; k++) {
-        if (alpha == 1.0) vec[k] = vec[k] + 0.f;
-        else if (alpha == -1.0) vec[k] = 0.f - vec[k];
-        else vec[k] = (float)((double)vec[k] * alpha);
-    }
+    for (int k = 0; k < 3; k++) vec[k] = cvm::expr_scale(vec[k], alpha);
     double rx = vec[0], ry = vec[1], rz = vec[2];
     const double theta = std::sqrt(rx * rx + ry * ry + rz * rz);
     if (theta < DBL_EPSILON) {
@@ -180,26 +159,6 @@ static void orbs_rotation(const float q[4], float R[9])
     const double rrt[9] = {rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz};
     const double r_x[9] = {0, -rz, ry, rz, 0, -rx, -ry, rx, 0};
     for (int k = 0; k < 9; k++) R[k] = (float)(c * I[k] + c1 * rrt[k] + sn * r_x[k]);
-}
-
-static int orbs_reserve(orbs_solver* s, size_t work, size_t stage)
-{
-    if (work > s->workCap) {
-        HIPCHK(hipStreamSynchronize(s->h->stream));
-        if (s->d_work) HIPCHK(hipFree(s->d_work));
-        s->d_work = nullptr; s->workCap = 0;
-        const size_t want = std::max<size_t>(work * 3 / 2, 1 << 16);
-        HIPCHK(hipMalloc(&s->d_work, want));
-        s->workCap = want;
-    }
-    if (stage > s->stageCap) {
-        if (s->h_stage) HIPCHK(hipHostFree(s->h_stage));
-        s->h_stage = nullptr; s->stageCap = 0;
-        const size_t want = std::max<size_t>(stage * 3 / 2, 1 << 16);
-        HIPCHK(hipHostMalloc((void**)&s->h_stage, want, hipHostMallocDefault));
-        s->stageCap = want;
-    }
-    return ORBX_OK;
 }
 
 extern "C" int orbs_run(orbs_t* const* solvers, int count, const int32_t* const* sets)
@@ -244,8 +203,7 @@ extern "C" int orbs_run(orbs_t* const* solvers, int count, const int32_t* const*
         const size_t oQuat = pk.take((size_t)total * 16), oRot = pk.take((size_t)total * 36), oHyp = pk.take((size_t)total * sizeof(OrbsHypothesis)),
                      work = pk.off;
         orbs_solver* own = solvers[act[0]];
-        rc = orbs_reserve(own, work, work);
-        if (rc) return rc;
+        if ((rc = own->reserve(work, work))) return rc;
         uint8_t* hs = own->h_stage;
         uint8_t* d = (uint8_t*)own->d_work;
         orbs::Desc* hd = (orbs::Desc*)(hs + oDesc);

@@ -49,13 +49,9 @@ __device__ __forceinline__ int find_solver(const Desc* __restrict__ desc, int co
     return lo;
 }
 
-// gemm's small-matrix branch for one output: t = a0*b0 + a1*b1 + a2*b2 in float, d = (float)(t*alpha + c*beta)
-__device__ __forceinline__ float gemm3_elem(float a0, float a1, float a2, float b0, float b1, float b2, double alpha, float c, double beta)
-{
-    const float t = a0 * b0 + a1 * b1 + a2 * b2;
-    return (float)((double)t * alpha + (double)c * beta);
-}
-// The same with a NaN product defined as x86 defines it.  In mt12i = gemm(R, O2, -s, O1, 1) a NaN t (from a NaN R) meets
+// OpenCV 3.0 arithmetic: orbx_cvmath.hpp
+using cvm::expr_scale; using cvm::gemm3_elem; using cvm::hypot_cv;
+// gemm3_elem with a NaN product defined as x86 defines it.  In mt12i = gemm(R, O2, -s, O1, 1) a NaN t (from a NaN R) meets
 // alpha = -s, a NaN of the OPPOSITE sign: IEEE leaves the sign of the product open, the host's multiply returns its
 // first operand (t, as the restatement compiles), and the device compiler may move the negation.  Written out, so that
 // the stored NaN's bits are the host's.
@@ -67,22 +63,6 @@ __device__ __forceinline__ float gemm3_elem_nan_first(float a0, float a1, float 
     if (td != td) p = td;
     else if (alpha != alpha) p = alpha;
     return (float)(p + (double)c * beta);
-}
-// a MatExpr alpha*A assigned (MatOp_AddEx::assign)
-__device__ __forceinline__ float expr_scale(float x, double alpha)
-{
-    if (alpha == 1.0) return x + 0.f;
-    if (alpha == -1.0) return 0.f - x;
-    return (float)((double)x * alpha);
-}
-// lapack.cpp's hypot<float>
-__device__ __forceinline__ float hypot_cv(float a, float b)
-{
-    a = fabsf(a);
-    b = fabsf(b);
-    if (a > b) { b /= a; return a * sqrtf(1 + b * b); }
-    if (b > 0) { a /= b; return b * sqrtf(1 + a * a); }
-    return 0;
 }
 
 // ComputeCentroid of both point sets of a hypothesis: P (3x3, one point per column), Pr = P - C, O = C
@@ -153,7 +133,9 @@ __global__ __launch_bounds__(kFitThreads) void k_sim3_fit(const Desc* __restrict
     float Pr1[9], Pr2[9], O1[3], O2[3];
     centered(d.pts, sets + (size_t)g * 3, Pr1, O1);
     centered(d.pts + d.n, sets + (size_t)g * 3, Pr2, O2);
-    // M = Pr2*Pr1.t() (GEMM_2_T: the generic kernel, double sums)
+    // M = Pr2*Pr1.t() (GEMM_2_T: the generic kernel, double sums).  cvm::mm3_t2 written out: through the call the compiler
+    // swaps the operands of these multiplies and adds, and the operand order decides which NaN's payload survives (the
+    // tests compare NaN results as bits)
     float M[9];
 #pragma unroll
     for (int i = 0; i < 3; i++)
@@ -273,7 +255,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_sim3_pose(const Desc* __restri
     centered(d.pts + d.n, sets + (size_t)g * 3, Pr2, O2);
 #pragma unroll
     for (int k = 0; k < 9; k++) R[k] = rot[(size_t)g * 9 + k];
-    // P3 = mR12i*Pr2
+    // P3 = mR12i*Pr2 (cvm::mm3 written out, for the operand order of its multiplies: see k_sim3_fit's M)
     float P3[9];
 #pragma unroll
     for (int i = 0; i < 3; i++)

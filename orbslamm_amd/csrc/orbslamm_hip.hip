@@ -23,6 +23,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -34,6 +35,7 @@
 
 #include "../../include/orbslamm_hip.h"
 #include "orbx_common.hpp"
+#include "orbx_cvmath.hpp"   // OpenCV 3.0 float arithmetic shared by the solver families (orbi, orbs)
 
 #include "orbx_kernels.hip"
 #include "orbm_kernels.hip"
@@ -68,6 +70,8 @@ static int fail(int code, const char* fmt, ...)
     } while (0)
 
 extern "C" const char* orbx_last_error(void) { return g_err.c_str(); }
+
+#include "orbx_hostutil.inc"   // HIPCHK_OR, the grow-only device and pinned blocks, Packer
 
 // live handles: objects that point at another handle (a frame set at its matcher and at the extractor it last read
 // from) check here before touching it in their destructor -- handles may be destroyed in any order
@@ -175,7 +179,7 @@ static inline int cv_round(double v) { return (int)lrint(v); }  // cvRound: half
 static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 // The library is ONE translation unit (every kernel is a template or inline function of a header-like .hip file); its host
-// side is split by family:
+// side is split by family (orbx_hostutil.inc above: what they share):
 #include "orbx_host.inc"   // extractor: handle, tables, pipeline, host-buffer entries, stream matching
 #include "orbm_host.inc"   // matchers (includes orbt_host.inc: the Tracking-shaped searches and frame sets)
 #include "orbv_host.inc"   // vocabulary

@@ -8,19 +8,7 @@
 // ------------------------------------------------------------------ staging
 enum { T_STAGE = 24, T_OFF, T_CAND, T_QRES, T_STATS, T_FS, T_TSCR, T_PREP };
 
-static int orbm_pinned(orbm_handle* h, size_t bytes)
-{
-    if (bytes <= h->h_stageCap) return ORBX_OK;
-    if (h->h_stage) HIPCHK(hipHostFree(h->h_stage));
-    h->h_stage = nullptr; h->h_stageCap = 0;
-    const size_t want = (std::max<size_t>(bytes * 3 / 2, 1 << 16) + 63) & ~(size_t)63;
-    // read and written by copy KERNELS where it lies, its last 64 bytes polled by the host: explicitly coherent
-    HIPCHK(hipHostMalloc(&h->h_stage, want + 64, hipHostMallocCoherent));
-    h->nHostAlloc++;
-    h->h_stageCap = want;
-    *(volatile int32_t*)((uint8_t*)h->h_stage + want) = 0;
-    return ORBX_OK;
-}
+static int orbm_pinned(orbm_handle* h, size_t bytes) { return grow_pinned(h->h_stage, h->h_stageCap, bytes, true, nullptr, &h->nHostAlloc); }
 
 // The two ends of a drop-in call (host arrays in, host arrays out) ride on the call's own compute queue: the staging
 // block goes up and the results come down through orbx::k_upload, a one-lane kernel raises a flag behind them and the
@@ -49,11 +37,6 @@ static int stage_down_wait(orbm_handle* h, hipStream_t s, void* host, const void
     if (!wait_flag(flag, want)) HIPCHK(hipStreamSynchronize(s));
     return ORBX_OK;
 }
-
-struct Packer {  // lays host arrays out back to back (16-byte aligned) in the staging block
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; }
-};
 
 constexpr int kProjMaxTrain = 8192;      // the LDS form: resolve 12 bytes per train feature (+ queries, candidates); candidates 16 bytes
 constexpr int kProjMaxCells = 16383;     // the LDS form: cell starts as uint16
@@ -247,15 +230,9 @@ extern "C" int orbm_projection_prepare(orbm_t* h, const OrbmGrid* grid, const Or
     const int ncell = grid->cols * grid->rows;
     const ScratchFrame lay = scratch_frame_layout(nt, ncell);
     const size_t kb = ((size_t)nt * sizeof(OrbxKeyPoint) + 15) & ~(size_t)15, db = (size_t)nt * 32, up = kb + db;
-    if (up > h->h_prepCap) {
-        if (h->h_prep) HIPCHK(hipHostFree(h->h_prep));
-        h->h_prep = nullptr; h->h_prepCap = 0;
-        const size_t want = std::max<size_t>(up * 3 / 2, 1 << 16);
-        HIPCHK(hipHostMalloc(&h->h_prep, want, hipHostMallocDefault));
-        h->nHostAlloc++;
-        h->h_prepCap = want;
-    }
-    if ((rc = orbm_reserve(h, T_FS, lay.bytes)) || (rc = orbm_reserve(h, T_PREP, up))) return rc;
+    if ((rc = grow_pinned(h->h_prep, h->h_prepCap, up, false, nullptr, &h->nHostAlloc)) || (rc = orbm_reserve(h, T_FS, lay.bytes)) ||
+        (rc = orbm_reserve(h, T_PREP, up)))
+        return rc;
     uint8_t* hp = (uint8_t*)h->h_prep;
     uint8_t* dp = (uint8_t*)h->d_buf[T_PREP];
     memcpy(hp, t_keys_un, (size_t)nt * sizeof(OrbxKeyPoint));
@@ -525,18 +502,16 @@ extern "C" int orbm_frameset_create(orbm_t* h, int slots, int cap, const float K
     Packer hp;
     const size_t R = ResultRing::kSets;
     const size_t hA = hp.take(R * S * C * 4), hN = hp.take(R * S * 4), hS = hp.take(R * S * 8), hF = hp.take(R * S * 4);
-#define FSC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { int r_ = fail(ORBX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); orbm_frameset_destroy(f); return r_; } } while (0)
-    FSC(hipMalloc(&f->d_block, pk.off));
-    FSC(hipMalloc(&f->d_cand, S * (size_t)f->candCapPair * 8));
+    HIPCHK_OR(hipMalloc(&f->d_block, pk.off), orbm_frameset_destroy(f));
+    HIPCHK_OR(hipMalloc(&f->d_cand, S * (size_t)f->candCapPair * 8), orbm_frameset_destroy(f));
     // read by the host behind an event -- or, for the few pairs of a live stream, behind a flag while the kernel's queue
     // is still busy: explicitly coherent (fine-grained), whatever HIP_HOST_COHERENT says
-    FSC(hipHostMalloc(&f->h_block, hp.off, hipHostMallocCoherent));
+    HIPCHK_OR(hipHostMalloc(&f->h_block, hp.off, hipHostMallocCoherent), orbm_frameset_destroy(f));
     memset(f->h_block + hF, 0, R * S * 4);
-    FSC(hipMemsetAsync(f->d_block + oN, 0, S * 4, h->stream));
-    FSC(hipMemsetAsync(f->d_block + oTot, 0, S * 4, h->stream));
-    FSC(hipMemcpyAsync(f->d_block + oSc, scale_factors, (size_t)nlevels * 4, hipMemcpyHostToDevice, h->stream));
-    FSC(hipStreamSynchronize(h->stream));
-#undef FSC
+    HIPCHK_OR(hipMemsetAsync(f->d_block + oN, 0, S * 4, h->stream), orbm_frameset_destroy(f));
+    HIPCHK_OR(hipMemsetAsync(f->d_block + oTot, 0, S * 4, h->stream), orbm_frameset_destroy(f));
+    HIPCHK_OR(hipMemcpyAsync(f->d_block + oSc, scale_factors, (size_t)nlevels * 4, hipMemcpyHostToDevice, h->stream), orbm_frameset_destroy(f));
+    HIPCHK_OR(hipStreamSynchronize(h->stream), orbm_frameset_destroy(f));
     uint8_t* b = f->d_block;
     f->fs = {(orbm::KeyDev*)(b + oK), b + oD, (float*)(b + oA), (int32_t*)(b + oCs), (int32_t*)(b + oCi), (uint4*)(b + oRec), (int32_t*)(b + oN), cap, f->ncell};
     f->d_scale = (float*)(b + oSc);

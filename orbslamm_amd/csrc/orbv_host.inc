@@ -19,16 +19,7 @@ struct orbv_handle {
     size_t aggLds[2] = {0, 0};           // dynamic LDS already granted to k_voc_aggregate<false / true>
 };
 
-static int orbv_reserve(orbv_handle* h, int slot, size_t bytes)
-{
-    if (bytes <= h->d_cap[slot]) return ORBX_OK;
-    if (h->d_buf[slot]) HIPCHK(hipFree(h->d_buf[slot]));
-    h->d_buf[slot] = nullptr; h->d_cap[slot] = 0;
-    const size_t want = std::max<size_t>(bytes * 3 / 2, 4096);
-    HIPCHK(hipMalloc(&h->d_buf[slot], want));
-    h->d_cap[slot] = want;
-    return ORBX_OK;
-}
+static int orbv_reserve(orbv_handle* h, int slot, size_t bytes) { return grow_device(h->d_buf[slot], h->d_cap[slot], bytes, 4096); }
 
 extern "C" void orbv_destroy(orbv_t* h)
 {
@@ -113,20 +104,18 @@ extern "C" int orbv_create(int device, int k, int L, int scoring, int weighting,
             h->nodesAtLevel[dpt]++;
         }
     }
-#define VCRT(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { int r_ = fail(ORBX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); orbv_destroy(h); return r_; } } while (0)
-    VCRT(hipSetDevice(device));
-    VCRT(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    VCRT(hipMalloc(&h->d_childStart, (size_t)(nNodes + 1) * 4));
-    VCRT(hipMalloc(&h->d_childIdx, (size_t)nNodes * 4));
-    VCRT(hipMalloc(&h->d_desc, (size_t)nNodes * 32));
-    VCRT(hipMalloc(&h->d_wordId, (size_t)nNodes * 4));
-    VCRT(hipMalloc(&h->d_weight, (size_t)nNodes * 8));
-    VCRT(hipMemcpy(h->d_childStart, first.data(), (size_t)(nNodes + 1) * 4, hipMemcpyHostToDevice));
-    VCRT(hipMemcpy(h->d_childIdx, origId.data(), (size_t)nNodes * 4, hipMemcpyHostToDevice));   // (the slot of the old child list: now origId)
-    VCRT(hipMemcpy(h->d_desc, dN.data(), (size_t)nNodes * 32, hipMemcpyHostToDevice));
-    VCRT(hipMemcpy(h->d_wordId, wordIdN.data(), (size_t)nNodes * 4, hipMemcpyHostToDevice));
-    VCRT(hipMemcpy(h->d_weight, wN.data(), (size_t)nNodes * 8, hipMemcpyHostToDevice));
-#undef VCRT
+    HIPCHK_OR(hipSetDevice(device), orbv_destroy(h));
+    HIPCHK_OR(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking), orbv_destroy(h));
+    HIPCHK_OR(hipMalloc(&h->d_childStart, (size_t)(nNodes + 1) * 4), orbv_destroy(h));
+    HIPCHK_OR(hipMalloc(&h->d_childIdx, (size_t)nNodes * 4), orbv_destroy(h));
+    HIPCHK_OR(hipMalloc(&h->d_desc, (size_t)nNodes * 32), orbv_destroy(h));
+    HIPCHK_OR(hipMalloc(&h->d_wordId, (size_t)nNodes * 4), orbv_destroy(h));
+    HIPCHK_OR(hipMalloc(&h->d_weight, (size_t)nNodes * 8), orbv_destroy(h));
+    HIPCHK_OR(hipMemcpy(h->d_childStart, first.data(), (size_t)(nNodes + 1) * 4, hipMemcpyHostToDevice), orbv_destroy(h));
+    HIPCHK_OR(hipMemcpy(h->d_childIdx, origId.data(), (size_t)nNodes * 4, hipMemcpyHostToDevice), orbv_destroy(h));   // (the slot of the old child list: now origId)
+    HIPCHK_OR(hipMemcpy(h->d_desc, dN.data(), (size_t)nNodes * 32, hipMemcpyHostToDevice), orbv_destroy(h));
+    HIPCHK_OR(hipMemcpy(h->d_wordId, wordIdN.data(), (size_t)nNodes * 4, hipMemcpyHostToDevice), orbv_destroy(h));
+    HIPCHK_OR(hipMemcpy(h->d_weight, wN.data(), (size_t)nNodes * 8, hipMemcpyHostToDevice), orbv_destroy(h));
     *out = h;
     return ORBX_OK;
 }
@@ -247,15 +236,7 @@ extern "C" int orbv_transform(orbv_t* h, const uint8_t* desc, int n, int levelsu
     const size_t inBytes = ((size_t)n * 32 + 15) & ~(size_t)15;
     const VocOut lay = voc_out_layout(n, nullptr);
     const size_t need = inBytes + lay.bytes;
-    if (need > h->h_stageCap) {
-        if (h->h_stage) HIPCHK(hipHostFree(h->h_stage));
-        h->h_stage = nullptr; h->h_stageCap = 0;
-        const size_t want = (std::max<size_t>(need * 3 / 2, 1 << 16) + 63) & ~(size_t)63;
-        HIPCHK(hipHostMalloc(&h->h_stage, want + 64, hipHostMallocCoherent));
-        h->h_stageCap = want;
-        *(volatile int32_t*)((uint8_t*)h->h_stage + want) = 0;
-    }
-    if ((rc = orbv_reserve(h, SV_DESC, inBytes))) return rc;
+    if ((rc = grow_pinned(h->h_stage, h->h_stageCap, need, true)) || (rc = orbv_reserve(h, SV_DESC, inBytes))) return rc;
     uint8_t* hs = (uint8_t*)h->h_stage;
     hipStream_t s = h->stream;
     memcpy(hs, desc, (size_t)n * 32);

@@ -771,8 +771,8 @@ static int create_handle(const OrbxParams* params, int max_w, int max_h, int max
     HostGeom hg;
     rc = build_geometry(h, max_w, max_h, hg);
     if (rc) { delete h; return rc; }
-#define CRT(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { int r_ = fail(ORBX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); if (h->countedLat) g_latHandles[device & 63].fetch_sub(1); free_device(h); delete h; return r_; } } while (0)
-    CRT(hipSetDevice(device));
+    auto undo = [&]() { if (h->countedLat) g_latHandles[device & 63].fetch_sub(1); free_device(h); delete h; };   // the half-built handle
+    HIPCHK_OR(hipSetDevice(device), undo());
     // The first four streams of a process get a hardware queue each, later ones share the last (observed with
     // rocprofv3 --kernel-trace), and two busy streams on one queue serialise.  The steady-state pipeline therefore
     // uses exactly four: the host-facing stream (uploads, downloads -- idle while a device-resident stream runs --
@@ -781,13 +781,13 @@ static int create_handle(const OrbxParams* params, int max_w, int max_h, int max
     // level-0 FAST stream and the matcher have slack.  Queue priority (which queue's workgroups the dispatcher places
     // first) for the chain: 142.6 k -> 144.0 k frames/s; raising the matcher instead: 138.2 k, the blur stream: 140.6 k.
     int prLo = 0, prHi = 0;
-    CRT(hipDeviceGetStreamPriorityRange(&prLo, &prHi));
+    HIPCHK_OR(hipDeviceGetStreamPriorityRange(&prLo, &prHi), undo());
     const bool shared = max_batch > latCeil;   // the throughput handles of a device share ONE set of four streams (a set per handle: -7 % with two robots)
     if (shared) {
         rc = tput_streams_acquire(h, device, prHi);
         if (rc) { free_device(h); delete h; return rc; }
     } else
-    CRT(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    HIPCHK_OR(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking), undo());
     // ORBX_LAT_PRIO=0 puts a latency handle's chain at normal priority, the level of the matcher's stream.  High is the
     // default because the high-priority streams of a process get hardware queues of their own pool: K robots' chains then
     // sit on K different queues (17.4 k frames/s with four robots; 5.3 k when they share the normal pool with the
@@ -803,17 +803,17 @@ static int create_handle(const OrbxParams* params, int max_w, int max_h, int max
         if (rc) { free_device(h); delete h; return rc; }
         h->chainIdx = idx;
     } else if (!shared) {
-        CRT(hipStreamCreateWithPriority(&h->streamP[0], hipStreamNonBlocking, prHi));
+        HIPCHK_OR(hipStreamCreateWithPriority(&h->streamP[0], hipStreamNonBlocking, prHi), undo());
     }
     // (a latency handle never uses a second sub-batch stream or the matching stream: not created, no queue taken)
     if (max_batch > latCeil && !shared) {
-        CRT(hipStreamCreateWithPriority(&h->streamP[1], hipStreamNonBlocking, prHi));
-        CRT(hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking));
+        HIPCHK_OR(hipStreamCreateWithPriority(&h->streamP[1], hipStreamNonBlocking, prHi), undo());
+        HIPCHK_OR(hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking), undo());
     }
     // hardware queues are bound at a stream's first use: use the four once, now, in this order
     {
         void* scratch = nullptr;
-        CRT(hipMalloc(&scratch, 256));
+        HIPCHK_OR(hipMalloc(&scratch, 256), undo());
         hipStream_t four[4] = {h->stream, h->streamP[0], h->streamP[1], h->stream3};
         // A latency handle (one or two frames per call: one robot's live stream) only ever keeps its chain's stream(s)
         // busy: bind just those, so that the handles of K robots in one process land on K different hardware queues
@@ -825,20 +825,20 @@ static int create_handle(const OrbxParams* params, int max_w, int max_h, int max
         const int nbind = !latHandle ? (shared ? 0 : 4) : (h->latStreams == 2 ? 1 : 0);   // (the shared set was bound when it was made)
         (void)nLat;
         if (latHandle) four[0] = h->stream;
-        for (int i = 0; i < nbind; i++) { CRT(hipMemsetAsync(scratch, 0, 256, four[i])); CRT(hipStreamSynchronize(four[i])); }
-        CRT(hipFree(scratch));
+        for (int i = 0; i < nbind; i++) { HIPCHK_OR(hipMemsetAsync(scratch, 0, 256, four[i]), undo()); HIPCHK_OR(hipStreamSynchronize(four[i]), undo()); }
+        HIPCHK_OR(hipFree(scratch), undo());
     }
     for (int i = 0; i < orbx_handle::kMaxSplit; i++) {
-        if (i > 1 && max_batch > latCeil && !shared) CRT(hipStreamCreateWithPriority(&h->streamP[i], hipStreamNonBlocking, prHi));
-        CRT(hipEventCreateWithFlags(&h->evPyr[i], hipEventDisableTiming));
-        CRT(hipEventCreateWithFlags(&h->evBlur[i], hipEventDisableTiming));
-        CRT(hipEventCreateWithFlags(&h->evPart[i], hipEventDisableTiming));
-        CRT(hipEventCreateWithFlags(&h->evFast0[i], hipEventDisableTiming));
+        if (i > 1 && max_batch > latCeil && !shared) HIPCHK_OR(hipStreamCreateWithPriority(&h->streamP[i], hipStreamNonBlocking, prHi), undo());
+        HIPCHK_OR(hipEventCreateWithFlags(&h->evPyr[i], hipEventDisableTiming), undo());
+        HIPCHK_OR(hipEventCreateWithFlags(&h->evBlur[i], hipEventDisableTiming), undo());
+        HIPCHK_OR(hipEventCreateWithFlags(&h->evPart[i], hipEventDisableTiming), undo());
+        HIPCHK_OR(hipEventCreateWithFlags(&h->evFast0[i], hipEventDisableTiming), undo());
     }
-    CRT(hipEventCreateWithFlags(&h->evStart, hipEventDisableTiming));
-    CRT(hipEventCreateWithFlags(&h->evDesc, hipEventDisableTiming));
-    for (int i = 0; i < 2; i++) CRT(hipEventCreateWithFlags(&h->evMatch[i], hipEventDisableTiming));
-    for (int i = 0; i < 2; i++) CRT(hipEventCreateWithFlags(&h->evMatched[i], hipEventDisableTiming));
+    HIPCHK_OR(hipEventCreateWithFlags(&h->evStart, hipEventDisableTiming), undo());
+    HIPCHK_OR(hipEventCreateWithFlags(&h->evDesc, hipEventDisableTiming), undo());
+    for (int i = 0; i < 2; i++) HIPCHK_OR(hipEventCreateWithFlags(&h->evMatch[i], hipEventDisableTiming), undo());
+    for (int i = 0; i < 2; i++) HIPCHK_OR(hipEventCreateWithFlags(&h->evMatched[i], hipEventDisableTiming), undo());
     const size_t B = (size_t)max_batch;
     // capacities with head-room so that smaller shapes (different cell layouts) also fit
     h->cellsCap = hg.cells.size() * 2 + 64;
@@ -850,44 +850,43 @@ static int create_handle(const OrbxParams* params, int max_w, int max_h, int max
     h->candCapFrame = (size_t)hg.g.candFrameRecs + 1024;
     h->keptCapFrame = (size_t)hg.g.keptFrameRecs + 64;
     h->maxKp = hg.g.maxKp + 64;
-    CRT(hipMalloc(&h->d_geom, sizeof(Geom)));
-    CRT(hipMalloc(&h->d_cells, h->cellsCap * sizeof(Cell)));
-    CRT(hipMalloc(&h->d_tabs, h->tabsCap * sizeof(short4)));
+    HIPCHK_OR(hipMalloc(&h->d_geom, sizeof(Geom)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_cells, h->cellsCap * sizeof(Cell)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_tabs, h->tabsCap * sizeof(short4)), undo());
     h->pyrRangesCap = 64 * ORBX_MAXL;
-    CRT(hipMalloc(&h->d_pyrRanges, h->pyrRangesCap * sizeof(PyrRange)));
-    CRT(hipMalloc(&h->d_pyr, h->pyrCapFrame * B));
-    CRT(hipMalloc(&h->d_blur, h->blurCapFrame * B));
-    CRT(hipMalloc(&h->d_candRaw, h->candCapFrame * B * sizeof(uint64_t)));
-    CRT(hipMalloc(&h->d_candA, h->candCapFrame * B * sizeof(uint64_t)));
-    CRT(hipMalloc(&h->d_candB, h->candCapFrame * B * sizeof(uint64_t)));
-    CRT(hipMalloc(&h->d_candCount, B * ORBX_MAXL * sizeof(int32_t)));
-    CRT(hipMalloc(&h->d_cellCount, B * h->cellsCap * sizeof(int32_t)));
-    CRT(hipMalloc(&h->d_kept, h->keptCapFrame * B * sizeof(uint64_t)));
-    CRT(hipMalloc(&h->d_keptCount, B * ORBX_MAXL * sizeof(int32_t)));
-    CRT(hipMalloc(&h->d_err, 8 * sizeof(int32_t)));
-    CRT(hipMalloc(&h->d_kps, 2 * (B + 1) * h->maxKp * sizeof(OrbxKeyPointDev)));
-    CRT(hipMalloc(&h->d_desc, 2 * (B + 1) * (size_t)h->maxKp * 32));
-    CRT(hipMalloc(&h->d_count, 2 * (B + 1) * sizeof(int32_t)));
-    CRT(hipMalloc(&h->d_match, 2 * B * h->maxKp * sizeof(int32_t)));
-    CRT(hipMalloc(&h->d_binOf, B * (size_t)h->maxKp));
-    CRT(hipMalloc(&h->d_hist, B * 32 * sizeof(int32_t)));
-    CRT(hipMalloc(&h->d_nmatch, 2 * B * sizeof(int32_t)));
+    HIPCHK_OR(hipMalloc(&h->d_pyrRanges, h->pyrRangesCap * sizeof(PyrRange)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_pyr, h->pyrCapFrame * B), undo());
+    HIPCHK_OR(hipMalloc(&h->d_blur, h->blurCapFrame * B), undo());
+    HIPCHK_OR(hipMalloc(&h->d_candRaw, h->candCapFrame * B * sizeof(uint64_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_candA, h->candCapFrame * B * sizeof(uint64_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_candB, h->candCapFrame * B * sizeof(uint64_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_candCount, B * ORBX_MAXL * sizeof(int32_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_cellCount, B * h->cellsCap * sizeof(int32_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_kept, h->keptCapFrame * B * sizeof(uint64_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_keptCount, B * ORBX_MAXL * sizeof(int32_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_err, 8 * sizeof(int32_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_kps, 2 * (B + 1) * h->maxKp * sizeof(OrbxKeyPointDev)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_desc, 2 * (B + 1) * (size_t)h->maxKp * 32), undo());
+    HIPCHK_OR(hipMalloc(&h->d_count, 2 * (B + 1) * sizeof(int32_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_match, 2 * B * h->maxKp * sizeof(int32_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_binOf, B * (size_t)h->maxKp), undo());
+    HIPCHK_OR(hipMalloc(&h->d_hist, B * 32 * sizeof(int32_t)), undo());
+    HIPCHK_OR(hipMalloc(&h->d_nmatch, 2 * B * sizeof(int32_t)), undo());
     h->partialSlots = std::max<size_t>(B * kMatchChunks, 16);  // few frames: up to 8 train chunks per frame (k_match_mfma)
-    CRT(hipMalloc(&h->d_partial, h->partialSlots * h->maxKp * sizeof(uint2)));
+    HIPCHK_OR(hipMalloc(&h->d_partial, h->partialSlots * h->maxKp * sizeof(uint2)), undo());
     // a slot of the +-1 buffer: the descriptors in MFMA tile order, then the keypoints' ANGLES as a plain float array (round 5:
     // the acceptance rule's rotation test read them out of the 28-byte keypoint records -- 7 MB of the stream matcher's 22 MB
     // of fetches per step for 1 MB of angles)
     h->xAngOff = (int64_t)align_up(h->maxKp, orbm::kMfmaRowsPerBlock) * orbm::kMfmaDescBytes;
     h->xPitch = h->xAngOff + (int64_t)align_up(h->maxKp * 4, 4096);
-    CRT(hipFuncSetAttribute((const void*)orbm::k_match_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, orbm::kMfmaLdsBytes));  // its ring of train tiles
-    CRT(hipMalloc(&h->d_xdesc, 2 * (B + 1) * (size_t)h->xPitch));
-    CRT(hipMemset(h->d_xdesc, 0, 2 * (B + 1) * (size_t)h->xPitch));
-    CRT(hipMemset(h->d_err, 0, 8 * sizeof(int32_t)));
+    HIPCHK_OR(hipFuncSetAttribute((const void*)orbm::k_match_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, orbm::kMfmaLdsBytes), undo());  // its ring of train tiles
+    HIPCHK_OR(hipMalloc(&h->d_xdesc, 2 * (B + 1) * (size_t)h->xPitch), undo());
+    HIPCHK_OR(hipMemset(h->d_xdesc, 0, 2 * (B + 1) * (size_t)h->xPitch), undo());
+    HIPCHK_OR(hipMemset(h->d_err, 0, 8 * sizeof(int32_t)), undo());
     h->d_errCur = h->d_err;
-    CRT(hipMemset(h->d_count, 0, 2 * (B + 1) * sizeof(int32_t)));
-    CRT(hipMemset(h->d_hist, 0, B * 32 * sizeof(int32_t)));
-    CRT(hipMemset(h->d_nmatch, 0, 2 * B * sizeof(int32_t)));
-#undef CRT
+    HIPCHK_OR(hipMemset(h->d_count, 0, 2 * (B + 1) * sizeof(int32_t)), undo());
+    HIPCHK_OR(hipMemset(h->d_hist, 0, B * 32 * sizeof(int32_t)), undo());
+    HIPCHK_OR(hipMemset(h->d_nmatch, 0, 2 * B * sizeof(int32_t)), undo());
     live_add(h);
     *out = h;
     return ORBX_OK;
@@ -2208,11 +2207,10 @@ extern "C" int orbx_debug_link_rate(orbx_t* h, size_t up_bytes, size_t down_byte
     void *hu = nullptr, *hd = nullptr, *du = nullptr, *dd = nullptr;
     hipStream_t s1 = nullptr, s2 = nullptr;
     auto cleanup = [&]() { if (hu) (void)hipHostFree(hu); if (hd) (void)hipHostFree(hd); if (du) (void)hipFree(du); if (dd) (void)hipFree(dd); if (s1) (void)hipStreamDestroy(s1); if (s2) (void)hipStreamDestroy(s2); };
-#define LR(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(ORBX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
-    LR(hipHostMalloc(&hu, up_bytes)); LR(hipHostMalloc(&hd, down_bytes)); LR(hipMalloc(&du, up_bytes)); LR(hipMalloc(&dd, down_bytes));
-    LR(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking)); LR(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+    HIPCHK_OR(hipHostMalloc(&hu, up_bytes), cleanup()); HIPCHK_OR(hipHostMalloc(&hd, down_bytes), cleanup()); HIPCHK_OR(hipMalloc(&du, up_bytes), cleanup()); HIPCHK_OR(hipMalloc(&dd, down_bytes), cleanup());
+    HIPCHK_OR(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking), cleanup()); HIPCHK_OR(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking), cleanup());
     memset(hu, 1, up_bytes);
-    LR(hipMemsetAsync(dd, 2, down_bytes, s2)); LR(hipStreamSynchronize(s2));
+    HIPCHK_OR(hipMemsetAsync(dd, 2, down_bytes, s2), cleanup()); HIPCHK_OR(hipStreamSynchronize(s2), cleanup());
     using clk = std::chrono::steady_clock;
     auto run = [&](bool up, bool down, double& sec) -> hipError_t {
         for (int w = 0; w < 2; w++) {   // first round warms the queues
@@ -2229,12 +2227,11 @@ extern "C" int orbx_debug_link_rate(orbx_t* h, size_t up_bytes, size_t down_byte
         return hipSuccess;
     };
     double t = 0;
-    LR(run(true, false, t)); if (h2d_gbs) *h2d_gbs = (float)(up_bytes * (double)reps / t / 1e9);
-    LR(run(false, true, t)); if (d2h_gbs) *d2h_gbs = (float)(down_bytes * (double)reps / t / 1e9);
-    LR(run(true, true, t));
+    HIPCHK_OR(run(true, false, t), cleanup()); if (h2d_gbs) *h2d_gbs = (float)(up_bytes * (double)reps / t / 1e9);
+    HIPCHK_OR(run(false, true, t), cleanup()); if (d2h_gbs) *d2h_gbs = (float)(down_bytes * (double)reps / t / 1e9);
+    HIPCHK_OR(run(true, true, t), cleanup());
     if (both_up_gbs) *both_up_gbs = (float)(up_bytes * (double)reps / t / 1e9);
     if (both_down_gbs) *both_down_gbs = (float)(down_bytes * (double)reps / t / 1e9);
-#undef LR
     cleanup();
     return ORBX_OK;
 }

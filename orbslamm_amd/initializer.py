@@ -9,12 +9,11 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import KP_DTYPE, check, lib, ptr
+from ._lib import K4, KP_DTYPE, RAND_MAX, check, lib, ptr, random_int, seed_rand  # noqa: F401 (RAND_MAX: part of this module's names)
 
 ORBI_MODEL_HF, ORBI_MODEL_F = 0, 1
 MAX_ITERATIONS = 4096
 MAX_FEATURES = 65535
-RAND_MAX = 2147483647   # glibc's
 
 
 class OrbiResult(C.Structure):
@@ -35,37 +34,22 @@ def result_fields(r):
     return out
 
 
-_libc = None
-
-
 def make_sets(n, iterations, seed=0):
     """Initialize's set drawing (Initializer.cc:67-97) through libc's rand(), as DUtils::Random makes it: SeedRandOnce(seed)
     is srand(seed) (seed None: continue the process's stream), RandomInt(0, k - 1) = int(rand() / (RAND_MAX + 1.0) * k).
     Returns iterations x 8 indices into the compacted match list."""
-    global _libc
     if n < 8:
         raise ValueError("%d matches: the 8-point sets need at least 8" % n)
-    if _libc is None:
-        _libc = C.CDLL(None)
-        _libc.rand.restype = C.c_int
-    if seed is not None:
-        _libc.srand(C.c_uint(int(seed)))
+    seed_rand(seed)
     sets = np.zeros((iterations, 8), dtype=np.int32)
     for it in range(iterations):
         avail = list(range(n))
         for j in range(8):
-            randi = int((float(_libc.rand()) / (RAND_MAX + 1.0)) * len(avail))
+            randi = random_int(len(avail))
             sets[it, j] = avail[randi]
             avail[randi] = avail[-1]
             avail.pop()
     return sets
-
-
-def _K4(K):
-    K = np.asarray(K, dtype=np.float32)
-    if K.shape == (3, 3):
-        K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], dtype=np.float32)
-    return np.ascontiguousarray(K.reshape(4))
 
 
 def _setup(L):
@@ -94,12 +78,12 @@ class Initializer:
         self.iterations = int(iterations)
         self.model = {"HF": ORBI_MODEL_HF, "F": ORBI_MODEL_F}[model]
         self._h = C.c_void_p()
-        K4 = _K4(K)
+        k4 = K4(K)
         if isinstance(ref, np.ndarray):
             keys = np.ascontiguousarray(ref, dtype=KP_DTYPE)
-            check(self._L.orbi_create(matcher._h, ptr(keys), keys.shape[0], ptr(K4), float(sigma), self.iterations, self.model, C.byref(self._h)))
+            check(self._L.orbi_create(matcher._h, ptr(keys), keys.shape[0], ptr(k4), float(sigma), self.iterations, self.model, C.byref(self._h)))
         else:
-            check(self._L.orbi_create_frame(matcher._h, ref, ptr(K4), float(sigma), self.iterations, self.model, C.byref(self._h)))
+            check(self._L.orbi_create_frame(matcher._h, ref, ptr(k4), float(sigma), self.iterations, self.model, C.byref(self._h)))
         n = C.c_int(0)
         check(self._L.orbi_size(self._h, C.byref(n)))
         self.n1 = n.value

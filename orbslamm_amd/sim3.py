@@ -11,11 +11,10 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, lib, ptr
+from ._lib import K4, check, lib, ptr, random_int, seed_rand
 
 MAX_POINTS = 65535
 MAX_ITERATIONS = 4096
-RAND_MAX = 2147483647   # glibc's
 
 
 class OrbsHypothesis(C.Structure):
@@ -40,40 +39,25 @@ def result_fields(r, inliers):
                 best_t=np.array(r.best_t[:], dtype=np.float32), best_s=np.float32(r.best_s), inliers=inliers.astype(bool))
 
 
-_libc = None
-
-
 def make_sim3_sets(n, iterations, seed=0):
     """iterate's set drawing (Sim3Solver.cc:163-177) through libc's rand(), as DUtils::Random::RandomInt makes it
     (int(rand() / (RAND_MAX + 1.0) * k)); seed None continues the process's stream.  The reference overwrites
     vAvailableIndices[idx] with idx the drawn VALUE, not the drawn position, so a set can hold a point twice: kept.
     Returns iterations x 3 indices into the solver's correspondences."""
-    global _libc
     if n < 3:
         raise ValueError("%d correspondences: a set needs 3" % n)
-    if _libc is None:
-        _libc = C.CDLL(None)
-        _libc.rand.restype = C.c_int
-    if seed is not None:
-        _libc.srand(C.c_uint(int(seed)))
+    seed_rand(seed)
     sets = np.zeros((iterations, 3), dtype=np.int32)
     for it in range(iterations):
         avail = list(range(n))
         live = n
         for j in range(3):
-            randi = int((float(_libc.rand()) / (RAND_MAX + 1.0)) * live)
+            randi = random_int(live)
             idx = avail[randi]
             sets[it, j] = idx
             avail[idx] = avail[live - 1]
             live -= 1
     return sets
-
-
-def _K4(K):
-    K = np.asarray(K, dtype=np.float32)
-    if K.shape == (3, 3):
-        K = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], dtype=np.float32)
-    return np.ascontiguousarray(K.reshape(4))
 
 
 def _f32(a, shape):
@@ -110,7 +94,7 @@ class Sim3Solver:
         n = idx1.shape[0]
         self.n, self.n1 = n, int(n1)
         self._h = C.c_void_p()
-        args = [_f32(X1w, (n, 3)), _f32(X2w, (n, 3)), _f32(Rcw1, 9), _f32(tcw1, 3), _f32(Rcw2, 9), _f32(tcw2, 3), _K4(K1), _K4(K2),
+        args = [_f32(X1w, (n, 3)), _f32(X2w, (n, 3)), _f32(Rcw1, 9), _f32(tcw1, 3), _f32(Rcw2, 9), _f32(tcw2, 3), K4(K1), K4(K2),
                 _f32(sigma2_1, n), _f32(sigma2_2, n)]
         check(self._L.orbs_create(matcher._h, self.n1, ptr(idx1), n, *[ptr(a) for a in args], int(bool(fix_scale)), C.byref(self._h)))
         self.sets = None

@@ -3,11 +3,10 @@ behind a small C shim (tests/cpp/init_ref_capi.cpp), and a two-view scene genera
 and outliers)."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from ref_shim import build_ref_shim, p as _p
 from orbslamm_amd._lib import KP_DTYPE
 from orbslamm_amd.initializer import OrbiResult, result_fields
 
@@ -20,10 +19,7 @@ def ref_lib():
     """the restatement as a shared object (built once per process)"""
     global _ref
     if _ref is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="init_ref_"), "libinit_ref.so")
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror",
-                               os.path.join(ROOT, "tests", "cpp", "init_ref_capi.cpp"), "-o", out])
-        L = C.CDLL(out)
+        L = build_ref_shim("init_ref")
         vp = C.c_void_p
         L.initref_initialize.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, vp, vp, C.POINTER(OrbiResult), vp, vp]
         L.initref_svd.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
@@ -32,10 +28,6 @@ def ref_lib():
         L.initref_random_int.argtypes = [C.c_int, C.c_int]
         _ref = L
     return _ref
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def ref_initialize(keys1, keys2, m12, sets, K=K_TUM, sigma=1.0, model="HF"):

@@ -3,11 +3,10 @@ behind a small C shim (tests/cpp/sim3_ref_capi.cpp), named scene families with t
 check of a returned result that shares no code with the restatement."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+from ref_shim import build_ref_shim, p as _p
 from orbslamm_amd.sim3 import HYP_DTYPE, OrbsResult, make_sim3_sets, result_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,10 +38,7 @@ def ref_lib():
     """the restatement as a shared object (built once per process)"""
     global _ref
     if _ref is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="sim3_ref_"), "libsim3_ref.so")
-        subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror",
-                               os.path.join(ROOT, "tests", "cpp", "sim3_ref_capi.cpp"), "-o", out])
-        L = C.CDLL(out)
+        L = build_ref_shim("sim3_ref")
         vp = C.c_void_p
         L.sim3ref_eigen.argtypes = [vp, vp, vp]
         L.sim3ref_rodrigues.argtypes = [vp, vp]
@@ -58,10 +54,6 @@ def ref_lib():
         L.sim3ref_compute.argtypes = [vp, vp, C.c_int, vp]
         _ref = L
     return _ref
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def same(a, b):
