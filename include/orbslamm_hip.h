@@ -791,6 +791,84 @@ int orbs_iterate(orbs_t* s, int n_iterations, OrbsResult* res, uint8_t* inliers)
 int orbs_last_run_ms(orbs_t* s, double ms[3]);
 void orbs_destroy(orbs_t* s);
 
+/* ---------------------------------------------------------------- PnPsolver
+ * replaces PnPsolver (src/PnPsolver.cc, the same in both scenarios): EPnP from four correspondences under RANSAC with an
+ * n-point Refine, as Tracking::Relocalization runs it on every relocalisation candidate of every lost frame.  Every
+ * hypothesis of every solver of a frame is evaluated in one chain (orbp_run: fit, score, records, Refine of every record);
+ * iterate / find are then replayed on the host over the per-hypothesis table, with the reference's state.  Results equal
+ * the reference's bit for bit given the same sets (its OpenCV arithmetic is restated, unpinned: §2).
+ *
+ * orbp_create: the constructor after its pointer chasing.  The caller walks vpMapPointMatches (skipping null and bad
+ *   points) and passes the n survivors: idx = mvKeyPointIndices (positions in vpMapPointMatches, n_all long), P2D (n x 2)
+ *   = mvKeysUn[idx].pt, sigma2 (n) = mvLevelSigma2[kp.octave], P3Dw (n x 3) = GetWorldPos, K = (fx, fy, cx, cy).  It ends,
+ *   as the constructor does, in SetRansacParameters(0.99, 8, 300, 4, 0.4, 5.991).  The handle runs on the matcher
+ *   handle's device and stream and holds a reference to it.
+ * orbp_create_frame: the same from a device-resident frame (orbm_frame_create): n_all is
+ *   the frame's size, P2D and sigma2 are gathered on the device from its undistorted keys (pt, and level_sigma2[octave], a
+ *   host table of n_levels entries): nothing of the frame crosses the link, the caller sends idx and P3Dw.
+ * orbp_set_ransac: SetRansacParameters (libm on the host): min_inliers raised to (int)(N*epsilon) and to min_set, epsilon
+ *   raised to min_inliers/N, pow(epsilon, 3) in the iteration count, mvMaxError = sigma2*th2 as a float product.  As in
+ *   the reference it rewinds neither mnIterations nor the best; it drops the table.  orbp_max_iterations /
+ *   orbp_min_inliers read mRansacMaxIts / mRansacMinInliers back.
+ * orbp_run: hypotheses 0 .. n_sets[c]-1 of every solver, in one chain of launches.  sets[c] (host, n_sets[c] x 4): the
+ *   RANSAC sets of solvers[c] as indices into its n correspondences, which the reference draws with DUtils::Random inside
+ *   iterate (PnPsolver.cc:191-201; its draw can repeat a point) -- the caller draws them the same way.  iterate's loop is
+ *   an OR (`mnIterations < mRansacMaxIts || nCurrentIterations < nIterations`), so a solver can need up to
+ *   mRansacMaxIts + nIterations - 1 hypotheses: n_sets[c] may exceed mRansacMaxIts (iterate(5) reaches
+ *   mRansacMaxIts + 4).  A solver with n < min_inliers never draws: its sets[c] may be null.  All solvers must belong to
+ *   one matcher handle.  A solver that has not iterated gets a new table; one that has iterated CONTINUES its table: the
+ *   sets given are those of the hypotheses behind the last one it holds, the records go on from the table's largest, the
+ *   state stays (what a caller does when the reference's loop runs past the sets drawn so far).
+ *   orbp_hypotheses copies a solver's table out.
+ * orbp_iterate: cv::Mat iterate(nIterations, bNoMore, vbInliers, nInliers) over the table; find is
+ *   orbp_iterate(mRansacMaxIts).  inliers (n_all bytes) is cleared, then set at idx[i] for the inliers of the returned
+ *   pose (Refine's, or the best's at exhaustion), recomputed on the device for that pose.  Needs orbp_run first unless
+ *   n < min_inliers.  A call whose loop would step past the table returns ORBX_E_CAPACITY with the solver's state as
+ *   before the call.
+ * Refusals (nothing computed): ORBX_E_UNSUPPORTED for n == 0, min_set != 4, more than ORBP_MAX_POINTS correspondences,
+ *   more than ORBP_MAX_ITERATIONS iterations, a table beyond 2 * ORBP_MAX_ITERATIONS hypotheses, orbp_run on a solver that
+ *   has iterated and whose table orbp_set_ransac dropped; ORBX_E_INVALID for a null argument,
+ *   idx outside [0, n_all), a set index outside [0, n), n_sets outside [1, 2 * ORBP_MAX_ITERATIONS], solvers of
+ *   different handles or repeated in a batch, orbp_iterate / orbp_hypotheses without a table. */
+#define ORBP_MAX_POINTS 65535
+#define ORBP_MAX_ITERATIONS 4096
+typedef struct {
+    int32_t n_inliers;         /* mnInliersi */
+    int32_t is_record;         /* 1: count >= mRansacMinInliers and > mnBestInliers: it became the running best */
+    int32_t refine_inliers;    /* is_record: mnRefinedInliers of Refine() on its mask */
+    int32_t refine_ok;         /* is_record: Refine()'s return (refine_inliers > mRansacMinInliers) */
+    double R[9], t[3];         /* mRi (row-major), mti */
+    double refine_R[9], refine_t[3];   /* is_record: mRi, mti after Refine() */
+} OrbpHypothesis;
+typedef struct {
+    int32_t returned;          /* 1: iterate returned Tcw (else the empty cv::Mat) */
+    int32_t no_more;           /* bNoMore */
+    int32_t n_inliers;         /* nInliers */
+    int32_t hypothesis;        /* the iteration whose Refine returned, or the best's at exhaustion (0-based); -1: none */
+    int32_t refined;           /* 1: Tcw is mRefinedTcw (a Refine returned), 0: mBestTcw (exhaustion) */
+    int32_t iterations;        /* mnIterations after the call */
+    int32_t best_inliers;      /* mnBestInliers after the call */
+    int32_t best_hypothesis;   /* the iteration that holds the best, -1: none yet */
+    float Tcw[16];             /* the returned matrix (returned == 1), row-major 4x4 CV_32F */
+    float best_Tcw[16];        /* mBestTcw */
+} OrbpResult;
+typedef struct orbp_solver orbp_t;
+int orbp_create(orbm_t* h, int n_all, const int32_t* idx, int n, const float* P2D, const float* sigma2, const float* P3Dw,
+                const float K[4], orbp_t** out);
+int orbp_create_frame(orbm_t* h, orbm_frame_t* f, const int32_t* idx, int n, const float* P3Dw, const float* level_sigma2, int n_levels,
+                      const float K[4], orbp_t** out);
+int orbp_set_ransac(orbp_t* s, double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2);
+int orbp_max_iterations(orbp_t* s, int* iterations);
+int orbp_min_inliers(orbp_t* s, int* min_inliers);
+int orbp_size(orbp_t* s, int* n, int* n_all);
+int orbp_run(orbp_t* const* solvers, int count, const int32_t* const* sets, const int32_t* n_sets);
+int orbp_hypotheses(orbp_t* s, OrbpHypothesis* out, int cap, int* n_out);
+int orbp_iterate(orbp_t* s, int n_iterations, OrbpResult* res, uint8_t* inliers);
+/* the last orbp_run this solver took part in: ms[0] the whole chain on the host's clock (upload to table down), then
+ * its legs on the device's (events on the stream): ms[1] fit, ms[2] score + records, ms[3] Refine (tools/pnp_bench.py) */
+int orbp_last_run_ms(orbp_t* s, double ms[4]);
+void orbp_destroy(orbp_t* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,4 +6,5 @@ from .extractor import ORBextractor, unpack_candidates  # noqa: F401
 from .matcher import ORBmatcher, make_grid  # noqa: F401
 from .vocabulary import ORBVocabulary  # noqa: F401
 from .keyframe_db import KeyFrameDatabase, KeyFramePool  # noqa: F401
+from .pnp import PnPsolver, make_pnp_sets  # noqa: F401
 from ._lib import KP_DTYPE, OrbError  # noqa: F401

@@ -97,6 +97,12 @@ EXPORTS_SIM3 = [
     "orbs_last_run_ms", "orbs_destroy",
 ]
 
+# the PnPsolver's block (orbp_*)
+EXPORTS_PNP = [
+    "orbp_create", "orbp_create_frame", "orbp_set_ransac", "orbp_max_iterations", "orbp_min_inliers", "orbp_size", "orbp_run", "orbp_hypotheses", "orbp_iterate",
+    "orbp_last_run_ms", "orbp_destroy",
+]
+
 
 def build(force=False):
     """hipcc the extension in-tree for gfx950 (cross-compiles without a GPU)."""
@@ -147,7 +153,7 @@ def lib():
         L = C.CDLL(os.environ.get("ORBSLAMM_HIP_LIB") or SO_PATH)
         L.orbx_last_error.restype = C.c_char_p
         L.orbx_scale_factor.restype = C.c_float
-        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3:
+        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP:
             getattr(L, name)
         L.orbx_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _lib = L

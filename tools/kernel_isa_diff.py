@@ -5,8 +5,11 @@
     python tools/kernel_isa_diff.py a.s b.s
 
 Splits both files by kernel symbol (the amdhsa metadata lists them), drops comment and blank lines, compares each
-kernel's instruction stream line for line and its metadata row (registers, LDS, scratch, spills; tools/kernel_resources.py
-prints the same figures).  Prints every kernel that differs with both rows; exit status 1 when any does."""
+kernel's instruction stream line for line (block labels without the function's ordinal) and its metadata row (registers, LDS, scratch, spills; tools/kernel_resources.py
+prints the same figures).  Block labels are compared without the function's ordinal in the file (.LBB68_2 -> .LBB_2): a kernel
+added in front of a function renumbers them.  That hides nothing as long as labels are the only place the ordinal appears, which
+holds for hipcc's output (symbols, metadata and instructions carry none); branch targets still have to match by their local number.
+Prints every kernel that differs with both rows; exit status 1 when any does."""
 import re
 import sys
 
@@ -36,6 +39,8 @@ def bodies(txt, names):
             if l.startswith(".Lfunc_end"):
                 break
             l = l.split(";")[0].rstrip()
+            # block labels carry the function's ordinal in the file (.LBB68_2): a kernel added in front renumbers them
+            l = re.sub(r"\.LBB\d+_", ".LBB_", l)
             if l.strip():
                 body.append(l)
         out[name] = body
