@@ -869,6 +869,91 @@ int orbp_iterate(orbp_t* s, int n_iterations, OrbpResult* res, uint8_t* inliers)
 int orbp_last_run_ms(orbp_t* s, double ms[4]);
 void orbp_destroy(orbp_t* s);
 
+/* ---------------------------------------------------------------- CreateNewMapPoints
+ * replaces LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:207-452, the same in both scenarios), the only caller of
+ * SearchForTriangulation: one call searches the current keyframe against ALL its covisible neighbours, triangulates
+ * every pair (the reference's 4x4 cv::SVD), applies its five gates and returns the new points in the reference's order
+ * (neighbours ascending, idx1 ascending inside a neighbour).  Results equal the reference's loop bit for bit (its
+ * OpenCV arithmetic is restated, unpinned: §2).
+ *
+ * MONOCULAR ONLY: mbMonocular == true, bStereo1 == bStereo2 == false, bOnlyStereo == false.  The stereo branches
+ * (:311-316, :340-347, :377-387, :403-413) call binary64 atan2 / cos and are not built; the entries take no uright.
+ *
+ * The serial dependency.  In the reference a success with neighbour i calls mpCurrentKeyFrame->AddMapPoint(pMP, idx1),
+ * and SearchForTriangulation with neighbour i + 1 skips idx1.  The batch computes every (neighbour, feature) in parallel
+ * and then keeps, per feature, the first neighbour in order that was not skipped by the baseline gate and passed every
+ * gate; the same feature reads "feature skipped" in every later neighbour.  That equals the serial loop because without
+ * the orientation histogram (the reference builds ORBmatcher(0.6, false)) and with vbMatched2 never set, a query
+ * feature's result against a neighbour depends on no other query -- and because every neighbour is a DIFFERENT
+ * keyframe, so its AddMapPoint touches no later search.  Hence:
+ *   - check_ori != 0 is refused (ORBX_E_UNSUPPORTED): the histogram prunes a bin by counting ALL matches of a neighbour,
+ *     which would couple the queries and, through skip1, the neighbours;
+ *   - a frame handle given twice, or a neighbour that is the current keyframe, is refused (ORBX_E_INVALID).
+ *
+ * OrblKeyFrame: the pose and the camera centre as the reference's getters return them (GetRotation, GetTranslation,
+ *   GetCameraCenter: Ow is taken from the caller, not recomputed), K = (fx, fy, cx, cy); invfx = 1.0f/fx and invfy =
+ *   1.0f/fy are formed in the library as Frame.cc does.  median_depth: KeyFrame::ComputeSceneMedianDepth(2) of a
+ *   neighbour (it reads MapPoint positions from the object graph: the caller's); unused for the current keyframe.
+ * OrblNewPoint: pos is the x3D passed to `new MapPoint`; normal, min_distance, max_distance restate what
+ *   MapPoint::UpdateNormalAndDepth (MapPoint.cc:330-371) computes for a point with exactly these two observations and
+ *   mpRefKF the current keyframe: normal = (n1 * (float)(1/|n1|) + n2 * (float)(1/|n2|)) * 0.5, each `normal +
+ *   normali/norm` taken as cv::scaleAdd on CV_32F (float scale, float product, float sum; OpenCV's arithmetic is restated
+ *   and unpinned, §2: equal to the restatement bit for bit, not verified against an OpenCV build), so that the sum of two
+ *   floats does not depend on the std::map's pointer order; max_distance = dist1 *
+ *   mvScaleFactors[octave1], min_distance = max_distance / mvScaleFactors[nlevels - 1].  ComputeDistinctiveDescriptors
+ *   of a two-observation point picks by pointer order in the reference and is not produced here.
+ * status (optional, n_neighbours x n1 bytes): one ORBL_ST_* code per (neighbour, feature): which gate ended the pair.
+ * f12_used (optional, n_neighbours x 11 floats): F12 (9) and the epipole (2) the search of each processed neighbour used
+ *   (zeros for a neighbour under the baseline gate): what orbl_compute_f12 returns.
+ *
+ * orbl_compute_f12: ComputeF12 (:536-553) and SearchForTriangulation's epipole (ORBmatcher.cc:666-672) in cv::Mat
+ *   arithmetic, on the host; needs no GPU.  The batched entries call it themselves.
+ * orbl_create_new_map_points: host arrays.  keys: mvKeysUn; fv: mFeatVec as CSR (node ids ascending, every feature in
+ *   at most one node); skip: 1 where GetMapPoint(idx) is non-null (may be null: none), skip2 itself may be null;
+ *   scale_factors / level_sigma2: mvScaleFactors / mvLevelSigma2 (nlevels entries, octaves are taken modulo 16);
+ *   scale_factor: mfScaleFactor (ratioFactor = 1.5f * scale_factor).
+ * orbl_create_new_map_points_frames: the same on device-resident frames that ran orbm_frame_compute_bow: only the skip
+ *   flags and the keyframe records go up.
+ * Limits and refusals: ORBX_E_UNSUPPORTED for check_ori != 0 and more than ORBL_MAX_NEIGHBOURS neighbours (the
+ *   reference asks for 20); ORBX_E_INVALID for more than 65535 features in a keyframe (both entries), a malformed feature vector,
+ *   repeated frames, frames without BoW; ORBX_E_CAPACITY when capacity is too small, with *n_new the needed count and
+ *   nothing written (n1 always suffices: a feature yields at most one point).  Zero neighbours, zero features or no
+ *   shared vocabulary node: ORBX_OK with *n_new = 0.  Without a HIP device no matcher handle exists: no CPU fallback. */
+#define ORBL_MAX_NEIGHBOURS 32
+#define ORBL_ST_NEIGHBOUR_SKIPPED 0   /* baseline / median_depth < 0.01 (the float quotient compared in double, :256-260) */
+#define ORBL_ST_FEATURE_SKIPPED 1     /* skip1, or taken by an earlier neighbour */
+#define ORBL_ST_NO_MATCH 2            /* SearchForTriangulation found no partner */
+#define ORBL_ST_PARALLAX 3            /* !(cosParallaxRays > 0 && cosParallaxRays < 0.9998) */
+#define ORBL_ST_X3D_ZERO 4            /* x3D(3) == 0 */
+#define ORBL_ST_Z1 5                  /* z1 <= 0 */
+#define ORBL_ST_Z2 6                  /* z2 <= 0 */
+#define ORBL_ST_REPROJ1 7             /* reprojection error in the current keyframe above 5.991 sigma2 */
+#define ORBL_ST_REPROJ2 8             /* reprojection error in the neighbour */
+#define ORBL_ST_DIST_ZERO 9           /* dist1 == 0 || dist2 == 0 */
+#define ORBL_ST_SCALE 10              /* the scale-ratio gate */
+#define ORBL_ST_ACCEPTED 11           /* a new point */
+typedef struct {
+    float Rcw[9], tcw[3], Ow[3], K[4];
+    float median_depth;
+} OrblKeyFrame;
+typedef struct {
+    int32_t neighbour, idx1, idx2;
+    float pos[3];
+    float normal[3];
+    float min_distance, max_distance;
+} OrblNewPoint;
+int orbl_compute_f12(const OrblKeyFrame* kf1, const OrblKeyFrame* kf2, float F12[9], float epipole[2]);
+int orbl_create_new_map_points(orbm_t* h, const OrbxKeyPoint* keys1, const uint8_t* desc1, int n1, const OrbmFeatVec* fv1,
+                               const uint8_t* skip1, const OrblKeyFrame* kf1, const OrbxKeyPoint* const* keys2,
+                               const uint8_t* const* desc2, const int32_t* n2, const OrbmFeatVec* fv2, const uint8_t* const* skip2,
+                               const OrblKeyFrame* kf2, int n_neighbours, const float* scale_factors, const float* level_sigma2,
+                               int nlevels, float scale_factor, int check_ori, OrblNewPoint* out, int capacity, int* n_new,
+                               uint8_t* status, float* f12_used);
+int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t* skip1, const OrblKeyFrame* kf1,
+                                      orbm_frame_t* const* f2, const uint8_t* const* skip2, const OrblKeyFrame* kf2, int n_neighbours,
+                                      const float* scale_factors, const float* level_sigma2, int nlevels, float scale_factor,
+                                      int check_ori, OrblNewPoint* out, int capacity, int* n_new, uint8_t* status, float* f12_used);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,11 @@ EXPORTS_PNP = [
     "orbp_last_run_ms", "orbp_destroy",
 ]
 
+# CreateNewMapPoints' block (orbl_*)
+EXPORTS_LOCALMAP = [
+    "orbl_compute_f12", "orbl_create_new_map_points", "orbl_create_new_map_points_frames",
+]
+
 
 def build(force=False):
     """hipcc the extension in-tree for gfx950 (cross-compiles without a GPU)."""
@@ -153,7 +158,7 @@ def lib():
         L = C.CDLL(os.environ.get("ORBSLAMM_HIP_LIB") or SO_PATH)
         L.orbx_last_error.restype = C.c_char_p
         L.orbx_scale_factor.restype = C.c_float
-        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP:
+        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP + EXPORTS_LOCALMAP:
             getattr(L, name)
         L.orbx_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _lib = L

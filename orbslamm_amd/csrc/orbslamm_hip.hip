@@ -35,7 +35,7 @@
 
 #include "../../include/orbslamm_hip.h"
 #include "orbx_common.hpp"
-#include "orbx_cvmath.hpp"   // OpenCV 3.0 float arithmetic shared by the solver families (orbi, orbs, orbp)
+#include "orbx_cvmath.hpp"   // OpenCV 3.0 float arithmetic shared by the solver families (orbi, orbs, orbp, orbl)
 
 #include "orbx_kernels.hip"
 #include "orbm_kernels.hip"
@@ -45,6 +45,7 @@
 #include "orbi_kernels.hip"
 #include "orbs_kernels.hip"
 #include "orbp_kernels.hip"
+#include "orbl_kernels.hip"
 
 using namespace orbx;
 
@@ -190,3 +191,4 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbi_host.inc"   // Initializer
 #include "orbs_host.inc"   // Sim3Solver
 #include "orbp_host.inc"   // PnPsolver
+#include "orbl_host.inc"   // CreateNewMapPoints
