@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "orbslamm_dropin.hpp"
 #include "orbslamm_hip.h"
 
 namespace iORB_SLAM {
@@ -59,12 +60,8 @@ public:
                               m12_.data(), sets_.data(), &res_, p3d_.data(), tri_.data()));
         if (res_.rt_state == 1) { R21 = Mat(); t21 = Mat(); }
         if (res_.rt_state == 2) {
-            R21 = Mat(3, 3, kCV_32F);
-            t21 = Mat(3, 1, kCV_32F);
-            for (int r = 0; r < 3; r++) {
-                for (int c = 0; c < 3; c++) R21.template at<float>(r, c) = res_.R21[3 * r + c];
-                t21.template at<float>(r, 0) = res_.t21[r];
-            }
+            R21 = detail::mat32f<Mat>(res_.R21, 3, 3);
+            t21 = detail::mat32f<Mat>(res_.t21, 3, 1);
         }
         if (res_.ok) {
             vP3D.clear();
@@ -85,7 +82,6 @@ public:
     int mMaxIterations;
 
 private:
-    static const int kCV_32F = 5;
     void drawSets(int N)
     {
         std::vector<size_t> vAllIndices, vAvailableIndices;
@@ -104,7 +100,7 @@ private:
             }
         }
     }
-    static void check(int rc) { if (rc != ORBX_OK) throw std::runtime_error(std::string("Initializer(HIP): ") + orbx_last_error()); }
+    static void check(int rc) { detail::check(rc, "Initializer(HIP): "); }
 
     int n1_;
     orbi_t* ini_ = nullptr;

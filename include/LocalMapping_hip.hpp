@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "orbslamm_dropin.hpp"
 #include "orbslamm_hip.h"
 
 namespace iORB_SLAM {
@@ -73,8 +74,7 @@ public:
             KeyFrame* pKF2 = vpNeighKFs[i];
             for (; r < nOut && out[r].neighbour == i; r++) {
                 const OrblNewPoint& p = out[r];
-                Mat x3D(3, 1, 5 /* CV_32F */);
-                for (int c = 0; c < 3; c++) x3D.template at<float>(c, 0) = p.pos[c];
+                Mat x3D = detail::mat32f<Mat>(p.pos, 3, 1);
                 MapPoint* pMP = new MapPoint(x3D, pKF1, pMap);
                 pMP->AddObservation(pKF1, p.idx1);
                 pMP->AddObservation(pKF2, p.idx2);
@@ -131,10 +131,7 @@ private:
         s.kf.median_depth = 0.f;
     }
 
-    static void check(int rc)
-    {
-        if (rc != ORBX_OK) throw std::runtime_error(std::string("orbslamm_hip: ") + orbx_last_error());
-    }
+    static void check(int rc) { detail::check(rc, "orbslamm_hip: "); }
 };
 
 }  // namespace iORB_SLAM

@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "orbslamm_dropin.hpp"
 #include "orbslamm_hip.h"
 
 namespace iORB_SLAM {
@@ -98,11 +99,8 @@ public:
         nInliers = res_.n_inliers;
         vbInliers.clear();   // (the reference fills it only when it returns a pose)
         if (!res_.returned) return Mat();
-        vbInliers = std::vector<bool>((size_t)mNAll, false);
-        for (int i = 0; i < mNAll; i++) if (mask_[i]) vbInliers[i] = true;
-        Mat T(4, 4, kCV_32F);
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T.template at<float>(r, c) = res_.Tcw[4 * r + c];
-        return T;
+        vbInliers = detail::mask_bools(mask_, mNAll);
+        return detail::mat32f<Mat>(res_.Tcw, 4, 4);
     }
 
     // every hypothesis of every solver in one device call; the sets are drawn solver by solver, in list order
@@ -135,14 +133,12 @@ public:
     int minInliers() const { return mRansacMinInliers; }
 
 private:
-    static const int kCV_32F = 5;
     void readBack()
     {
         check(orbp_max_iterations(s_, &mRansacMaxIts));
         check(orbp_min_inliers(s_, &mRansacMinInliers));
     }
-    // iterate's draw (PnPsolver.cc:191-201) for mRansacMaxIts + kExtraSets iterations; vAvailableIndices[idx] is indexed by
-    // the drawn VALUE as in the reference (its write can land past the live part: here the vector keeps its N slots)
+    // iterate's draw (PnPsolver.cc:191-201) for mRansacMaxIts + kExtraSets iterations
     void drawSets() { sets_.clear(); drawMore(mRansacMaxIts + kExtraSets); }
     // `count` more hypotheses behind the table: their sets drawn now, evaluated by a run that continues the table
     void extend(int count)
@@ -155,24 +151,8 @@ private:
         const int32_t n = (int32_t)((sets_.size() - from) / 4);
         check(orbp_run(&h, 1, &p, &n));
     }
-    void drawMore(int count)
-    {
-        std::vector<size_t> vAvailableIndices((size_t)N);
-        const int first = (int)(sets_.size() / 4);
-        sets_.resize(sets_.size() + (size_t)count * 4, 0);
-        for (int it = first; it < first + count; it++) {
-            for (int i = 0; i < N; i++) vAvailableIndices[i] = (size_t)i;
-            int live = N;
-            for (short i = 0; i < 4; ++i) {
-                const int randi = Random::RandomInt(0, live - 1);
-                const int idx = (int)vAvailableIndices[randi];
-                sets_[(size_t)it * 4 + i] = idx;
-                vAvailableIndices[idx] = vAvailableIndices[live - 1];
-                live--;
-            }
-        }
-    }
-    static void check(int rc) { if (rc != ORBX_OK) throw std::runtime_error(std::string("PnPsolver(HIP): ") + orbx_last_error()); }
+    void drawMore(int count) { detail::draw_sets<Random>(N, 4, count, sets_); }
+    static void check(int rc) { detail::check(rc, "PnPsolver(HIP): "); }
 
     int N = 0, mNAll = 0, mRansacMinInliers = 8, mRansacMaxIts = 300;
     bool ran_ = false;

@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "orbslamm_dropin.hpp"
 #include "orbslamm_hip.h"
 
 namespace iORB_SLAM {
@@ -90,28 +91,12 @@ public:
         check(orbs_iterate(s_, nIterations, &res_, mask_.data()));
         bNoMore = res_.no_more != 0;
         nInliers = res_.n_inliers;
-        vbInliers = std::vector<bool>((size_t)mN1, false);
-        for (int i = 0; i < mN1; i++) if (mask_[i]) vbInliers[i] = true;
-        if (!res_.returned) return Mat();
-        Mat T(4, 4, kCV_32F);
-        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T.template at<float>(r, c) = res_.T12[4 * r + c];
-        return T;
+        vbInliers = detail::mask_bools(mask_, mN1);
+        return res_.returned ? detail::mat32f<Mat>(res_.T12, 4, 4) : Mat();
     }
 
-    Mat GetEstimatedRotation()
-    {
-        if (!res_.has_best) return Mat();
-        Mat R(3, 3, kCV_32F);
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) R.template at<float>(r, c) = res_.best_R[3 * r + c];
-        return R;
-    }
-    Mat GetEstimatedTranslation()
-    {
-        if (!res_.has_best) return Mat();
-        Mat t(3, 1, kCV_32F);
-        for (int r = 0; r < 3; r++) t.template at<float>(r, 0) = res_.best_t[r];
-        return t;
-    }
+    Mat GetEstimatedRotation() { return res_.has_best ? detail::mat32f<Mat>(res_.best_R, 3, 3) : Mat(); }
+    Mat GetEstimatedTranslation() { return res_.has_best ? detail::mat32f<Mat>(res_.best_t, 3, 1) : Mat(); }
     float GetEstimatedScale() { return res_.best_s; }
 
     // every hypothesis of every solver in one device call; the sets are drawn solver by solver, in list order
@@ -137,7 +122,6 @@ public:
     int maxIterations() const { return mRansacMaxIts; }
 
 private:
-    static const int kCV_32F = 5;
     template <class M> static void push3(std::vector<float>& v, const M& m) { for (int r = 0; r < 3; r++) v.push_back(m.template at<float>(r, 0)); }
     static void pose(KeyFrame* pKF, float R[9], float t[3])
     {
@@ -148,25 +132,9 @@ private:
             t[r] = tm.template at<float>(r, 0);
         }
     }
-    // iterate's draw (Sim3Solver.cc:163-177) for all mRansacMaxIts iterations; vAvailableIndices[idx] is indexed by the
-    // drawn VALUE as in the reference (its write can land one past the live part: here the vector keeps its N slots)
-    void drawSets()
-    {
-        std::vector<size_t> vAvailableIndices((size_t)N);
-        sets_.assign((size_t)mRansacMaxIts * 3, 0);
-        for (int it = 0; it < mRansacMaxIts; it++) {
-            for (int i = 0; i < N; i++) vAvailableIndices[i] = (size_t)i;
-            int live = N;
-            for (short i = 0; i < 3; ++i) {
-                const int randi = Random::RandomInt(0, live - 1);
-                const int idx = (int)vAvailableIndices[randi];
-                sets_[(size_t)it * 3 + i] = idx;
-                vAvailableIndices[idx] = vAvailableIndices[live - 1];
-                live--;
-            }
-        }
-    }
-    static void check(int rc) { if (rc != ORBX_OK) throw std::runtime_error(std::string("Sim3Solver(HIP): ") + orbx_last_error()); }
+    // iterate's draw (Sim3Solver.cc:163-177) for all mRansacMaxIts iterations
+    void drawSets() { sets_.clear(); detail::draw_sets<Random>(N, 3, mRansacMaxIts, sets_); }
+    static void check(int rc) { detail::check(rc, "Sim3Solver(HIP): "); }
 
     int N = 0, mN1 = 0, mRansacMinInliers = 6, mRansacMaxIts = 300;
     bool ran_ = false;

@@ -49,118 +49,14 @@ struct Hdr {
 };
 
 // OpenCV 3.0 arithmetic (3x3 row-major, CV_32F): orbx_cvmath.hpp
-using cvm::det3; using cvm::expr_scale; using cvm::gemm3_elem; using cvm::hypot_cv; using cvm::inv3; using cvm::mm3; using cvm::mm3_t1;
+using cvm::det3; using cvm::expr_scale; using cvm::gemm3_elem; using cvm::inv3; using cvm::jacobi_svd; using cvm::mm3; using cvm::mm3_t1;
 using cvm::mm3_t2; using cvm::mv3; using cvm::norm3;
-
-// JacobiSVDImpl_<float>(At, .., W, Vt, .., m, n, n1, FLT_MIN, FLT_EPSILON*2) on arrays in LDS.  S threads interleave
-// their arrays: element (i, k) of At at At[(i*m + k)*S], of Vt at Vt[(i*n + k)*S], W[i] at W[i*S] (double; on return the
-// sorted singular values, still double).  Vt always exists for the control flow (the sort swaps rows of At, the random
-// completion runs); trackV: its rotations are kept (callers that read only At skip them).  complete: run the random
-// completion of rows [0, n1) of At (callers that read only Vt skip it).
-template <int S>
-__device__ void jacobi_svd(float* At, double* W, float* Vt, int m, int n, int n1, bool trackV, bool complete)
-{
-#define A_(i, k) At[((i) * m + (k)) * S]
-#define V_(i, k) Vt[((i) * n + (k)) * S]
-    const double minval = FLT_MIN;
-    const float eps = FLT_EPSILON * 2;
-    const int max_iter = m > 30 ? m : 30;
-    for (int i = 0; i < n; i++) {
-        double sd = 0;
-        for (int k = 0; k < m; k++) { const float t = A_(i, k); sd += (double)t * t; }
-        W[i * S] = sd;
-        if (trackV) { for (int k = 0; k < n; k++) V_(i, k) = 0.f; V_(i, i) = 1.f; }
-    }
-    for (int iter = 0; iter < max_iter; iter++) {
-        bool changed = false;
-        for (int i = 0; i < n - 1; i++)
-            for (int j = i + 1; j < n; j++) {
-                double a = W[i * S], p = 0, b = W[j * S];
-                for (int k = 0; k < m; k++) p += (double)A_(i, k) * A_(j, k);
-                if (fabs(p) <= eps * sqrt((double)a * b)) continue;
-                p *= 2;
-                const double beta = a - b, gamma = hypot_cv(p, beta);
-                float c, s;
-                if (beta < 0) {
-                    const double delta = (gamma - beta) * 0.5;
-                    s = (float)sqrt(delta / gamma);
-                    c = (float)(p / (gamma * s * 2));
-                } else {
-                    c = (float)sqrt((gamma + beta) / (gamma * 2));
-                    s = (float)(p / (gamma * c * 2));
-                }
-                a = b = 0;
-                for (int k = 0; k < m; k++) {
-                    const float ai = A_(i, k), aj = A_(j, k);
-                    const float t0 = c * ai + s * aj;
-                    const float t1 = -s * ai + c * aj;
-                    A_(i, k) = t0; A_(j, k) = t1;
-                    a += (double)t0 * t0; b += (double)t1 * t1;
-                }
-                W[i * S] = a; W[j * S] = b;
-                changed = true;
-                if (trackV)
-                    for (int k = 0; k < n; k++) {
-                        const float vi = V_(i, k), vj = V_(j, k);
-                        V_(i, k) = c * vi + s * vj;
-                        V_(j, k) = -s * vi + c * vj;
-                    }
-            }
-        if (!changed) break;
-    }
-    for (int i = 0; i < n; i++) {
-        double sd = 0;
-        for (int k = 0; k < m; k++) { const float t = A_(i, k); sd += (double)t * t; }
-        W[i * S] = sqrt(sd);
-    }
-    for (int i = 0; i < n - 1; i++) {
-        int j = i;
-        for (int k = i + 1; k < n; k++) if (W[j * S] < W[k * S]) j = k;
-        if (i != j) {
-            const double tw = W[i * S]; W[i * S] = W[j * S]; W[j * S] = tw;
-            for (int k = 0; k < m; k++) { const float t = A_(i, k); A_(i, k) = A_(j, k); A_(j, k) = t; }
-            if (trackV) for (int k = 0; k < n; k++) { const float t = V_(i, k); V_(i, k) = V_(j, k); V_(j, k) = t; }
-        }
-    }
-    if (!complete) return;
-    uint64_t state = 0x12345678;   // cv::RNG(0x12345678)
-    for (int i = 0; i < n1; i++) {
-        double sd = i < n ? W[i * S] : 0;
-        for (int ii = 0; ii < 100 && sd <= minval; ii++) {
-            const float val0 = (float)(1. / m);
-            for (int k = 0; k < m; k++) {
-                state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32);
-                A_(i, k) = ((unsigned)state & 256) != 0 ? val0 : -val0;
-            }
-            for (int it = 0; it < 2; it++)
-                for (int j = 0; j < i; j++) {
-                    sd = 0;
-                    for (int k = 0; k < m; k++) sd += A_(i, k) * A_(j, k);   // float products, double sum
-                    float asum = 0;
-                    for (int k = 0; k < m; k++) {
-                        const float t = (float)(A_(i, k) - sd * A_(j, k));
-                        A_(i, k) = t;
-                        asum += fabsf(t);
-                    }
-                    asum = asum > eps * 100 ? 1 / asum : 0;
-                    for (int k = 0; k < m; k++) A_(i, k) *= asum;
-                }
-            sd = 0;
-            for (int k = 0; k < m; k++) { const float t = A_(i, k); sd += (double)t * t; }
-            sd = sqrt(sd);
-        }
-        const float s = (float)(sd > minval ? 1 / sd : 0.);
-        for (int k = 0; k < m; k++) A_(i, k) *= s;
-    }
-#undef A_
-#undef V_
-}
 
 // cv::SVD::compute(src 3x3, w, u, vt) for one lane: arrays in LDS (stride 1)
 __device__ inline void svd3_lane(const float* src, float* At, float* Vt, double* W, float* U, float* w, float* vt)
 {
     for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) At[i * 3 + k] = src[3 * k + i];   // !at: temp_a = src.t()
-    jacobi_svd<1>(At, W, Vt, 3, 3, 3, true, true);
+    jacobi_svd<float, 1>(At, W, Vt, 3, 3, 3, true, true);
     for (int i = 0; i < 3; i++) w[i] = (float)W[i];
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { U[3 * r + c] = At[c * 3 + r]; vt[3 * r + c] = Vt[3 * r + c]; }
 }
@@ -255,7 +151,7 @@ __global__ __launch_bounds__(kFitThreads) void k_init_fit(const Key* __restrict_
     norm_T(n1, T1);
     norm_T(n2, T2);
     if (H) {
-        jacobi_svd<kFitThreads>(A, W, sV + t, M, N, 16, true, false);
+        jacobi_svd<float, kFitThreads>(A, W, sV + t, M, N, 16, true, false);
         float Hn[9], T2inv[9], X[9], H21[9], H12[9];
         for (int k = 0; k < 9; k++) Hn[k] = sV[t + (8 * N + k) * kFitThreads];
         inv3(T2, T2inv);
@@ -265,7 +161,7 @@ __global__ __launch_bounds__(kFitThreads) void k_init_fit(const Key* __restrict_
         float* o = out + (size_t)h * 18;
         for (int k = 0; k < 9; k++) { o[k] = H21[k]; o[9 + k] = H12[k]; }
     } else {
-        jacobi_svd<kFitThreads>(A, W, nullptr, M, N, 9, false, true);
+        jacobi_svd<float, kFitThreads>(A, W, nullptr, M, N, 9, false, true);
         float Fpre[9];
         for (int k = 0; k < 9; k++) Fpre[k] = A[(8 * M + k) * kFitThreads];
         // SVDecomp(Fpre, w, u, vt, FULL_UV): 3x3, not transposed
@@ -273,7 +169,7 @@ __global__ __launch_bounds__(kFitThreads) void k_init_fit(const Key* __restrict_
         float* V3 = sV + t;
         double* W3 = W;   // (the 8x9 decomposition's W is no longer read)
         for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) A3[(i * 3 + k) * kFitThreads] = Fpre[3 * k + i];
-        jacobi_svd<kFitThreads>(A3, W3, V3, 3, 3, 3, true, true);
+        jacobi_svd<float, kFitThreads>(A3, W3, V3, 3, 3, 3, true, true);
         float u[9], vt[9], D[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         for (int r = 0; r < 3; r++)
             for (int c = 0; c < 3; c++) { u[3 * r + c] = A3[(c * 3 + r) * kFitThreads]; vt[3 * r + c] = V3[(r * 3 + c) * kFitThreads]; }
@@ -515,7 +411,7 @@ __global__ __launch_bounds__(kRtThreads) void k_init_checkrt(const Key* __restri
             At[(k * 4 + r) * kRtThreads] = v;   // !at: temp_a = A.t()
         }
     }
-    jacobi_svd<kRtThreads>(At, W, Vt, 4, 4, 4, true, false);
+    jacobi_svd<float, kRtThreads>(At, W, Vt, 4, 4, 4, true, false);
     const double alpha = 1. / (double)Vt[15 * kRtThreads];
     float X[3];
     for (int k = 0; k < 3; k++) X[k] = expr_scale(Vt[(12 + k) * kRtThreads], alpha);

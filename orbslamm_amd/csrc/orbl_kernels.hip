@@ -13,7 +13,7 @@
 //                         orientation histogram (the reference builds ORBmatcher(0.6, false)), so every (neighbour,
 //                         query) is independent of every other.
 //   k_newpoints_triangulate   one lane per (neighbour, query): the rays and their parallax, the 4x4 A and its
-//                         JacobiSVDImpl_<float> on arrays in LDS (orbi::jacobi_svd), x3D, the five gates, and what
+//                         JacobiSVDImpl_<float> on arrays in LDS (cvm::jacobi_svd), x3D, the five gates, and what
 //                         MapPoint::UpdateNormalAndDepth leaves for a point with these two observations; a status byte and
 //                         a record slot
 //   k_newpoints_resolve   one lane per query: the serial loop's AddMapPoint(pMP, idx1) -- the first neighbour that
@@ -114,7 +114,7 @@ __device__ __forceinline__ float row_dot(const float* R, int r, const float* X, 
     return (float)(s + (double)t);
 }
 
-// (flatten: orbi::jacobi_svd is inlined here as it is in the Initializer's kernels -- no call left in the device code)
+// (flatten: cvm::jacobi_svd is inlined here as it is in the Initializer's kernels -- no call left in the device code)
 __global__ __launch_bounds__(kTriThreads) __attribute__((flatten)) void k_newpoints_triangulate(Args a)
 {
     __shared__ float sA[16 * kTriThreads], sV[16 * kTriThreads];
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(kTriThreads) __attribute__((flatten)) void k_newpoi
             At[(c * 4 + r) * kTriThreads] = v;   // !at: temp_a = A.t()
         }
     }
-    orbi::jacobi_svd<kTriThreads>(At, W, Vt, 4, 4, 4, true, false);
+    cvm::jacobi_svd<float, kTriThreads>(At, W, Vt, 4, 4, 4, true, false);
     const float v3 = Vt[15 * kTriThreads];
     if (v3 == 0) { a.status[i] = ST_X3D_ZERO; return; }
     const double alpha = 1. / (double)v3;

@@ -168,8 +168,16 @@ extern "C" void orbm_destroy(orbm_t* h)
     orbm_release(h);
 }
 
-// What a solver made on a matcher handle holds of it (the Initializer, the Sim3Solver): a reference to the handle, whose
-// device and stream it works on, a grow-only device work block and the pinned block of its uploads and downloads.
+static int orbm_check(orbm_handle* h)
+{
+    if (!h) return fail(ORBX_E_INVALID, "null handle");
+    h->callSeq++;   // every entry on the handle counts: a prepared train side is good for the VERY NEXT call only (orbm_projection_prepare)
+    HIPCHK(hipSetDevice(h->device));
+    return ORBX_OK;
+}
+
+// What a solver made on a matcher handle holds of it (the Initializer, the Sim3Solver, the PnPsolver): a reference to the
+// handle, whose device and stream it works on, a grow-only device work block and the pinned block of its uploads and downloads.
 namespace {   // (its inline members are no exports of the library)
 struct orbm_solver_base {
     orbm_handle* h = nullptr;            // device and stream; a reference is held
@@ -193,6 +201,70 @@ struct orbm_solver_base {
         orbm_release(h);
     }
 };
+
+// What the two RANSAC solvers (the Sim3Solver, the PnPsolver) hold and do alike: SetRansacParameters' values, iterate's
+// counters, the per-hypothesis table of the family's last run (Hyp: its row) and the flags of the hypothesis it returns.
+// iterate itself and the run chains are the families' own: the two references differ there in substance.
+template <class Hyp>
+struct orbm_ransac_base : orbm_solver_base {
+    int n = 0;                           // N correspondences
+    uint8_t* d_mask = nullptr;           // n flags of the returned hypothesis
+    double prob = 0.99;
+    int minInliers = 0, maxIts = 300;    // (minInliers: the family's default, set by its struct)
+    int nIterations = 0, bestInliers = 0;
+    bool tableValid = false;
+    std::vector<Hyp> table;
+    double runMs[4] = {0, 0, 0, 0};      // the last batch's legs (the Sim3Solver has three)
+
+    // the table, behind orbs_hypotheses / orbp_hypotheses (family: "orbs", "orbp")
+    int hypotheses(const char* family, Hyp* out, int cap, int* n_out) const
+    {
+        if (!n_out || (cap > 0 && !out) || cap < 0) return fail(ORBX_E_INVALID, "bad argument");
+        if (!tableValid) return fail(ORBX_E_INVALID, "no table: %s_run comes first", family);
+        *n_out = (int)table.size();
+        if (cap < *n_out) return fail(ORBX_E_CAPACITY, "%d hypotheses, room for %d", *n_out, cap);
+        if (*n_out) memcpy(out, table.data(), table.size() * sizeof(Hyp));
+        return ORBX_OK;
+    }
+    // behind the family's mask kernel on the handle's stream: the n flags of d_mask down, inliers[idx[i]] = 1 where set
+    int scatter_mask(const std::vector<int32_t>& idx, uint8_t* inliers)
+    {
+        std::vector<uint8_t> m((size_t)n);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(m.data(), d_mask, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (int i = 0; i < n; i++) if (m[i]) inliers[idx[i]] = 1;
+        return ORBX_OK;
+    }
+};
+
+// SetRansacParameters' iteration count (Sim3Solver.cc:122-147, PnPsolver.cc:138-157), libm on the host as the references
+// call it: ceil(log(1 - p) / log(1 - epsilon^3)), 1 when every correspondence must be an inlier, inside [1, maxIterations].
+// The double -> int conversion is x86's (NaN and out-of-range values give INT_MIN), which the references leave to their compiler.
+static int ransac_iterations(int n, double probability, int minInliers, int maxIterations, float epsilon)
+{
+    int nIterations;
+    if (minInliers == n)
+        nIterations = 1;
+    else {
+        const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
+        nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : INT_MIN;
+    }
+    return std::max(1, std::min(nIterations, maxIterations));
+}
+
+// a run's batch: every entry a solver, all on one matcher handle, none twice; *h: that handle, made current
+template <class S>
+static int ransac_batch(S* const* solvers, int count, orbm_handle** h)
+{
+    for (int c = 0; c < count; c++) {
+        if (!solvers[c]) return fail(ORBX_E_INVALID, "solvers[%d] is null", c);
+        if (solvers[c]->h != solvers[0]->h) return fail(ORBX_E_INVALID, "solvers[%d] belongs to another matcher handle", c);
+        for (int e = 0; e < c; e++) if (solvers[e] == solvers[c]) return fail(ORBX_E_INVALID, "solvers[%d] repeats solvers[%d]", c, e);
+    }
+    *h = solvers[0]->h;
+    return orbm_check(*h);
+}
 }  // namespace
 
 // The calling thread's matcher handle for `device` (ORBmatcher.h:37-102: the state an ORBmatcher temporary needs but
@@ -222,14 +294,6 @@ extern "C" int orbm_alloc_stats(orbm_t* h, int64_t* device_allocs, int64_t* host
     if (device_allocs) *device_allocs = h ? h->nDevAlloc.load() : 0;
     if (host_allocs) *host_allocs = h ? h->nHostAlloc.load() : 0;
     if (handles_made) *handles_made = g_orbmHandlesMade.load();
-    return ORBX_OK;
-}
-
-static int orbm_check(orbm_handle* h)
-{
-    if (!h) return fail(ORBX_E_INVALID, "null handle");
-    h->callSeq++;   // every entry on the handle counts: a prepared train side is good for the VERY NEXT call only (orbm_projection_prepare)
-    HIPCHK(hipSetDevice(h->device));
     return ORBX_OK;
 }
 

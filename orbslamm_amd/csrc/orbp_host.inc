@@ -3,24 +3,18 @@
 // orbp_iterate replays the reference's iterate over the per-hypothesis table with the solver's state, on integers; the
 // mask it hands back is recomputed on the device for the returned pose.
 
-struct orbp_solver : orbm_solver_base {  // (a batch's transit buffers, d_work and h_stage, live in its first solver)
-    int nAll = 0, n = 0;
+struct orbp_solver : orbm_ransac_base<OrbpHypothesis> {  // (a batch's transit buffers, d_work and h_stage, live in its first solver)
+    orbp_solver() { minInliers = 8; }
+    int nAll = 0;
     float K[4] = {0};
     std::vector<int32_t> idx;            // mvKeyPointIndices
     float4* d_pts = nullptr;             // (P3Dw, sigma2)
     float2* d_uv = nullptr;              // P2D
-    uint8_t* d_mask = nullptr;           // n flags of the returned pose
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // SetRansacParameters / iterate's state
-    double prob = 0.99;
-    int minInliers = 8, maxIts = 300;
+    // SetRansacParameters / iterate's state beyond the base's
     float eps = 0.4f, th2 = 5.991f;
-    int nIterations = 0, bestInliers = 0, bestHyp = -1;
+    int bestHyp = -1;
     float bestTcw[16] = {0};
-    // the table of the last orbp_run
-    bool tableValid = false;
-    std::vector<OrbpHypothesis> table;
-    double runMs[4] = {0, 0, 0, 0};
 };
 
 static_assert(sizeof(OrbpHypothesis) == sizeof(orbp::Hyp) && sizeof(OrbpHypothesis) == 208, "OrbpHypothesis layout");
@@ -38,8 +32,7 @@ static void orbp_free(orbp_solver* s)
 
 extern "C" void orbp_destroy(orbp_t* s) { orbp_free(s); }
 
-// SetRansacParameters (PnPsolver.cc:121-157) on a copy of the parameters, libm on the host as the reference calls it.  The
-// double -> int conversion of the iteration count is x86's (NaN and out-of-range values give INT_MIN).
+// SetRansacParameters (PnPsolver.cc:121-157) on a copy of the parameters: epsilon is given, and raised to the inlier share
 static void orbp_ransac_parameters(int N, double probability, int& minInliers, int& maxIts, int minSet, float& epsilon)
 {
     int nMinInliers = (int)(N * epsilon);
@@ -47,14 +40,7 @@ static void orbp_ransac_parameters(int N, double probability, int& minInliers, i
     if (nMinInliers < minSet) nMinInliers = minSet;
     minInliers = nMinInliers;
     if (epsilon < (float)minInliers / N) epsilon = (float)minInliers / N;
-    int nIterations;
-    if (minInliers == N)
-        nIterations = 1;
-    else {
-        const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-        nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : INT_MIN;
-    }
-    maxIts = std::max(1, std::min(nIterations, maxIts));
+    maxIts = ransac_iterations(N, probability, minInliers, maxIts, epsilon);
 }
 
 extern "C" int orbp_set_ransac(orbp_t* s, double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2)
@@ -160,13 +146,8 @@ extern "C" int orbp_min_inliers(orbp_t* s, int* min_inliers)
 extern "C" int orbp_run(orbp_t* const* solvers, int count, const int32_t* const* sets, const int32_t* n_sets)
 {
     if (!solvers || !sets || !n_sets || count < 1) return fail(ORBX_E_INVALID, "bad argument");
-    for (int c = 0; c < count; c++) {
-        if (!solvers[c]) return fail(ORBX_E_INVALID, "solvers[%d] is null", c);
-        if (solvers[c]->h != solvers[0]->h) return fail(ORBX_E_INVALID, "solvers[%d] belongs to another matcher handle", c);
-        for (int e = 0; e < c; e++) if (solvers[e] == solvers[c]) return fail(ORBX_E_INVALID, "solvers[%d] repeats solvers[%d]", c, e);
-    }
-    orbm_handle* h = solvers[0]->h;
-    int rc = orbm_check(h);
+    orbm_handle* h = nullptr;
+    int rc = ransac_batch(solvers, count, &h);
     if (rc) return rc;
     // a solver with N < mRansacMinInliers never draws (iterate returns bNoMore at once): nothing to compute for it
     std::vector<int> act;
@@ -262,12 +243,7 @@ extern "C" int orbp_run(orbp_t* const* solvers, int count, const int32_t* const*
 
 extern "C" int orbp_hypotheses(orbp_t* s, OrbpHypothesis* out, int cap, int* n_out)
 {
-    if (!s || !n_out || (cap > 0 && !out) || cap < 0) return fail(ORBX_E_INVALID, "bad argument");
-    if (!s->tableValid) return fail(ORBX_E_INVALID, "no table: orbp_run comes first");
-    *n_out = (int)s->table.size();
-    if (cap < *n_out) return fail(ORBX_E_CAPACITY, "%d hypotheses, room for %d", *n_out, cap);
-    if (*n_out) memcpy(out, s->table.data(), s->table.size() * sizeof(OrbpHypothesis));
-    return ORBX_OK;
+    return s ? s->hypotheses("orbp", out, cap, n_out) : fail(ORBX_E_INVALID, "bad argument");
 }
 
 extern "C" int orbp_last_run_ms(orbp_t* s, double ms[4])
@@ -295,15 +271,10 @@ static int orbp_mask(orbp_solver* s, const double R[9], const double t[3], uint8
     if (rc) return rc;
     orbp::Pose pose;
     memcpy(pose.v, R, 72); memcpy(pose.v + 9, t, 24);
-    std::vector<uint8_t> m((size_t)s->n);
     hipLaunchKernelGGL(orbp::k_pnp_mask, dim3((s->n + orbp::kPointThreads - 1) / orbp::kPointThreads), dim3(orbp::kPointThreads), 0, h->stream,
                        (const float4*)s->d_pts, (const float2*)s->d_uv, s->n, pose, (double)s->K[0], (double)s->K[1], (double)s->K[2], (double)s->K[3],
                        s->th2, s->d_mask);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(m.data(), s->d_mask, (size_t)s->n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < s->n; i++) if (m[i]) inliers[s->idx[i]] = 1;
-    return ORBX_OK;
+    return s->scatter_mask(s->idx, inliers);
 }
 
 // iterate (PnPsolver.cc:165-258) over the table.  The state is advanced on copies and committed when the call is known to

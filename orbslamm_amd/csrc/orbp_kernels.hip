@@ -64,8 +64,6 @@ __device__ __forceinline__ int find_solver(const Desc* __restrict__ desc, int co
     return lo;
 }
 
-using cvm::hypot_cv;
-
 // A NaN of a returned pose leaves as ONE pattern, x86's default NaN.  Which of two NaN operands an operation hands on (and
 // with it the sign: a NaN born on the device is 0x7FF8..., on x86 0xFFF8..., and fabs / negation flip it on the way) is
 // the compiler's choice of operand order on both sides, not something the source fixes; the tests compare NaN results as
@@ -92,104 +90,12 @@ __device__ __forceinline__ bool is_inlier(const float4 P, const float2 q, const 
     return error2 < P.w * th2;
 }
 
-// JacobiSVDImpl_<double>(At, .., W, Vt, .., m, n, n1 = n, DBL_MIN, DBL_EPSILON*10) on one lane's arrays in LDS, S lanes
-// interleaved: element (i, k) of At at At[(i*m + k)*S], of Vt at Vt[(i*n + k)*S], W[i] at W[i*S].  Vt == nullptr: its
-// rotations are skipped (nothing else depends on them).  The random completion of zero singular values always runs.
+// JacobiSVDImpl_<double> (cvm::jacobi_svd) as cvSVD reaches it here: n1 = n, the random completion of zero singular values
+// always runs; Vt == nullptr: its rotations are skipped (nothing else depends on them)
 template <int S>
-__device__ void jacobi_svd_d(double* At, double* W, double* Vt, const int m, const int n)
+__device__ __forceinline__ void jacobi_svd_d(double* At, double* W, double* Vt, const int m, const int n)
 {
-#define A_(i, k) At[((i) * m + (k)) * S]
-#define V_(i, k) Vt[((i) * n + (k)) * S]
-    const double minval = DBL_MIN, eps = DBL_EPSILON * 10;
-    const int max_iter = m > 30 ? m : 30;
-    for (int i = 0; i < n; i++) {
-        double sd = 0;
-        for (int k = 0; k < m; k++) { const double t = A_(i, k); sd += t * t; }
-        W[i * S] = sd;
-        if (Vt) { for (int k = 0; k < n; k++) V_(i, k) = 0.; V_(i, i) = 1.; }
-    }
-    for (int iter = 0; iter < max_iter; iter++) {
-        bool changed = false;
-        for (int i = 0; i < n - 1; i++)
-            for (int j = i + 1; j < n; j++) {
-                double a = W[i * S], p = 0, b = W[j * S];
-                for (int k = 0; k < m; k++) p += A_(i, k) * A_(j, k);
-                if (fabs(p) <= eps * sqrt(a * b)) continue;
-                p *= 2;
-                const double beta = a - b, gamma = hypot_cv(p, beta);
-                double c, s;
-                if (beta < 0) {
-                    const double delta = (gamma - beta) * 0.5;
-                    s = sqrt(delta / gamma);
-                    c = p / (gamma * s * 2);
-                } else {
-                    c = sqrt((gamma + beta) / (gamma * 2));
-                    s = p / (gamma * c * 2);
-                }
-                a = b = 0;
-                for (int k = 0; k < m; k++) {
-                    const double ai = A_(i, k), aj = A_(j, k);
-                    const double t0 = c * ai + s * aj;
-                    const double t1 = -s * ai + c * aj;
-                    A_(i, k) = t0; A_(j, k) = t1;
-                    a += t0 * t0; b += t1 * t1;
-                }
-                W[i * S] = a; W[j * S] = b;
-                changed = true;
-                if (Vt)
-                    for (int k = 0; k < n; k++) {
-                        const double vi = V_(i, k), vj = V_(j, k);
-                        V_(i, k) = c * vi + s * vj;
-                        V_(j, k) = -s * vi + c * vj;
-                    }
-            }
-        if (!changed) break;
-    }
-    for (int i = 0; i < n; i++) {
-        double sd = 0;
-        for (int k = 0; k < m; k++) { const double t = A_(i, k); sd += t * t; }
-        W[i * S] = sqrt(sd);
-    }
-    for (int i = 0; i < n - 1; i++) {
-        int j = i;
-        for (int k = i + 1; k < n; k++) if (W[j * S] < W[k * S]) j = k;
-        if (i != j) {
-            const double tw = W[i * S]; W[i * S] = W[j * S]; W[j * S] = tw;
-            for (int k = 0; k < m; k++) { const double t = A_(i, k); A_(i, k) = A_(j, k); A_(j, k) = t; }
-            if (Vt) for (int k = 0; k < n; k++) { const double t = V_(i, k); V_(i, k) = V_(j, k); V_(j, k) = t; }
-        }
-    }
-    uint64_t state = 0x12345678;   // cv::RNG(0x12345678)
-    for (int i = 0; i < n; i++) {
-        double sd = W[i * S];
-        for (int ii = 0; ii < 100 && sd <= minval; ii++) {
-            const double val0 = 1. / m;
-            for (int k = 0; k < m; k++) {
-                state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32);
-                A_(i, k) = ((unsigned)state & 256) != 0 ? val0 : -val0;
-            }
-            for (int it = 0; it < 2; it++)
-                for (int j = 0; j < i; j++) {
-                    sd = 0;
-                    for (int k = 0; k < m; k++) sd += A_(i, k) * A_(j, k);
-                    double asum = 0;
-                    for (int k = 0; k < m; k++) {
-                        const double t = A_(i, k) - sd * A_(j, k);
-                        A_(i, k) = t;
-                        asum += fabs(t);
-                    }
-                    asum = asum > eps * 100 ? 1 / asum : 0;
-                    for (int k = 0; k < m; k++) A_(i, k) *= asum;
-                }
-            sd = 0;
-            for (int k = 0; k < m; k++) { const double t = A_(i, k); sd += t * t; }
-            sd = sqrt(sd);
-        }
-        const double s = sd > minval ? 1 / sd : 0.;
-        for (int k = 0; k < m; k++) A_(i, k) *= s;
-    }
-#undef A_
-#undef V_
+    cvm::jacobi_svd<double, S>(At, W, Vt, m, n, n, Vt != nullptr, true);
 }
 
 // the correspondences of a hypothesis: its set of four (a repeated point goes through as it is)

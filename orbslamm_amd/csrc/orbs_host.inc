@@ -4,24 +4,17 @@
 // calls; the device's are other implementations), the pose and score kernels finish.  orbs_iterate replays the
 // reference's iterate over the per-hypothesis table with the solver's state, on integers.
 
-struct orbs_solver : orbm_solver_base {  // (a batch's transit buffers, d_work and h_stage, live in its first solver)
-    int n1 = 0, n = 0, fixScale = 0;
+struct orbs_solver : orbm_ransac_base<OrbsHypothesis> {  // (a batch's transit buffers, d_work and h_stage, live in its first solver)
+    orbs_solver() { minInliers = 6; }
+    int n1 = 0, fixScale = 0;
     float cam[32] = {0};                 // Rcw1, tcw1, Rcw2, tcw2, K1, K2
     std::vector<int32_t> idx1;           // mvnIndices1
     float4* d_pts = nullptr;             // three planes of n (orbs::Desc::pts)
     float* d_cam = nullptr;
     float* d_pose = nullptr; int poseCap = 0;   // iterations x kPoseWords
-    uint8_t* d_mask = nullptr;           // n flags of the returning hypothesis
-    // SetRansacParameters / iterate's state
-    double prob = 0.99;
-    int minInliers = 6, maxIts = 300;
-    int nIterations = 0, bestInliers = 0;
+    // iterate's state beyond the base's (runMs: up + fit + down, host libm, up + pose + score + down)
     bool hasBest = false;
     float bestT12[16] = {0}, bestR[9] = {0}, bestT[3] = {0}, bestS = 0.f;
-    // the table of the last orbs_run
-    bool tableValid = false;
-    std::vector<OrbsHypothesis> table;
-    double runMs[3] = {0, 0, 0};         // the last batch's legs: up + fit + down, host libm, up + pose + score + down
 };
 
 static_assert(sizeof(OrbsHypothesis) == orbs::kHypWords * 4, "OrbsHypothesis layout");
@@ -35,19 +28,10 @@ static void orbs_free(orbs_solver* s)
 
 extern "C" void orbs_destroy(orbs_t* s) { orbs_free(s); }
 
-// SetRansacParameters' mRansacMaxIts (Sim3Solver.cc:122-147), libm on the host as the reference calls it.  The double ->
-// int conversion is x86's (NaN and out-of-range values give INT_MIN), which the reference leaves to its compiler.
+// SetRansacParameters' mRansacMaxIts (Sim3Solver.cc:122-147): epsilon is derived from the counts
 static int orbs_ransac_iterations(int n, double probability, int minInliers, int maxIterations)
 {
-    const float epsilon = (float)minInliers / n;
-    int nIterations;
-    if (minInliers == n)
-        nIterations = 1;
-    else {
-        const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-        nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : INT_MIN;
-    }
-    return std::max(1, std::min(nIterations, maxIterations));
+    return ransac_iterations(n, probability, minInliers, maxIterations, (float)minInliers / n);
 }
 
 extern "C" int orbs_set_ransac(orbs_t* s, double probability, int min_inliers, int max_iterations)
@@ -164,13 +148,8 @@ static void orbs_rotation(const float q[4], float R[9])
 extern "C" int orbs_run(orbs_t* const* solvers, int count, const int32_t* const* sets)
 {
     if (!solvers || !sets || count < 1) return fail(ORBX_E_INVALID, "bad argument");
-    for (int c = 0; c < count; c++) {
-        if (!solvers[c]) return fail(ORBX_E_INVALID, "solvers[%d] is null", c);
-        if (solvers[c]->h != solvers[0]->h) return fail(ORBX_E_INVALID, "solvers[%d] belongs to another matcher handle", c);
-        for (int e = 0; e < c; e++) if (solvers[e] == solvers[c]) return fail(ORBX_E_INVALID, "solvers[%d] repeats solvers[%d]", c, e);
-    }
-    orbm_handle* h = solvers[0]->h;
-    int rc = orbm_check(h);
+    orbm_handle* h = nullptr;
+    int rc = ransac_batch(solvers, count, &h);
     if (rc) return rc;
     // a solver with N < mRansacMinInliers never draws (iterate returns bNoMore at once): nothing to compute for it
     std::vector<int> act;
@@ -262,12 +241,7 @@ extern "C" int orbs_run(orbs_t* const* solvers, int count, const int32_t* const*
 
 extern "C" int orbs_hypotheses(orbs_t* s, OrbsHypothesis* out, int cap, int* n_out)
 {
-    if (!s || !n_out || (cap > 0 && !out) || cap < 0) return fail(ORBX_E_INVALID, "bad argument");
-    if (!s->tableValid) return fail(ORBX_E_INVALID, "no table: orbs_run comes first");
-    *n_out = (int)s->table.size();
-    if (cap < *n_out) return fail(ORBX_E_CAPACITY, "%d hypotheses, room for %d", *n_out, cap);
-    if (*n_out) memcpy(out, s->table.data(), s->table.size() * sizeof(OrbsHypothesis));
-    return ORBX_OK;
+    return s ? s->hypotheses("orbs", out, cap, n_out) : fail(ORBX_E_INVALID, "bad argument");
 }
 
 extern "C" int orbs_last_run_ms(orbs_t* s, double ms[3])
@@ -318,14 +292,10 @@ extern "C" int orbs_iterate(orbs_t* s, int n_iterations, OrbsResult* res, uint8_
                 orbm_handle* h = s->h;
                 int rc = orbm_check(h);
                 if (rc) { s->nIterations--; return rc; }
-                std::vector<uint8_t> m((size_t)s->n);
                 hipLaunchKernelGGL(orbs::k_sim3_mask, dim3((s->n + orbs::kPointThreads - 1) / orbs::kPointThreads), dim3(orbs::kPointThreads), 0, h->stream,
                                    (const float4*)s->d_pts, s->n, (const float*)(s->d_pose + (size_t)(s->nIterations - 1) * orbs::kPoseWords),
                                    (const float*)s->d_cam, s->d_mask);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(m.data(), s->d_mask, (size_t)s->n, hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipStreamSynchronize(h->stream));
-                for (int i = 0; i < s->n; i++) if (m[i]) inliers[s->idx1[i]] = 1;
+                if ((rc = s->scatter_mask(s->idx1, inliers))) return rc;
                 res->n_inliers = hy.n_inliers;
                 res->returned = 1;
                 res->hypothesis = s->nIterations - 1;

@@ -1,12 +1,15 @@
-// orbx_cvmath.hpp -- the pieces of OpenCV 3.0's float arithmetic that more than one solver family restates (the
-// Initializer, orbi_kernels.hip; the Sim3Solver, orbs_kernels.hip and orbs_host.inc).  Part of the library's one
-// translation unit.  3x3 matrices are row-major CV_32F.  One IEEE operation per source operation (the library is built
+// orbx_cvmath.hpp -- the pieces of OpenCV 3.0's arithmetic that more than one solver family restates: the 3x3 float
+// algebra (the Initializer, orbi_kernels.hip; the Sim3Solver, orbs_kernels.hip and orbs_host.inc; CreateNewMapPoints,
+// orbl_kernels.hip) and the one Jacobi SVD (the Initializer and CreateNewMapPoints in float, the PnPsolver,
+// orbp_kernels.hip, in double).  Part of the library's one translation unit.  3x3 matrices are row-major CV_32F.  One IEEE operation per source operation (the library is built
 // with -ffp-contract=off, host and device alike); each function names the OpenCV source branch it follows, and its
 // rounding is what keeps the device bit-equal with the reference.  (The checkers under tools/ restate the same branches
 // on their own and share nothing with this file.)
 #pragma once
 
+#include <cfloat>
 #include <cmath>
+#include <cstdint>
 
 namespace cvm {
 
@@ -109,6 +112,112 @@ __host__ __device__ __forceinline__ T hypot_cv(T a, T b)
     if (a > b) { b /= a; return a * sqrt(1 + b * b); }
     if (b > 0) { a /= b; return b * sqrt(1 + a * a); }
     return 0;
+}
+
+// JacobiSVDImpl_<T>(At, .., W, Vt, .., m, n, n1, minval, eps) of lapack.cpp, T = float (FLT_MIN, FLT_EPSILON*2) or double
+// (DBL_MIN, DBL_EPSILON*10), on arrays in LDS.  Device code only.  S threads interleave their arrays: element (i, k) of At
+// at At[(i*m + k)*S], of Vt at Vt[(i*n + k)*S], W[i] at W[i*S] (double; on return the sorted singular values, still
+// double).  As in the template, T is the precision of c, s, the rotated elements, val0, asum and the completion's products;
+// every sum of squares and the dot products are double.  trackV: Vt's rotations are kept (callers that read only At skip
+// them and may pass no Vt).  complete: run the random completion of rows [0, n1) of At (callers that read only Vt skip it).
+template <class T, int S>
+__device__ void jacobi_svd(T* At, double* W, T* Vt, int m, int n, int n1, bool trackV, bool complete)
+{
+#define A_(i, k) At[((i) * m + (k)) * S]
+#define V_(i, k) Vt[((i) * n + (k)) * S]
+    constexpr bool kFloat = sizeof(T) == sizeof(float);
+    const double minval = kFloat ? (double)FLT_MIN : DBL_MIN;
+    const T eps = kFloat ? (T)(FLT_EPSILON * 2) : (T)(DBL_EPSILON * 10);
+    const int max_iter = m > 30 ? m : 30;
+    for (int i = 0; i < n; i++) {
+        double sd = 0;
+        for (int k = 0; k < m; k++) { const T t = A_(i, k); sd += (double)t * t; }
+        W[i * S] = sd;
+        if (trackV) { for (int k = 0; k < n; k++) V_(i, k) = 0; V_(i, i) = 1; }
+    }
+    for (int iter = 0; iter < max_iter; iter++) {
+        bool changed = false;
+        for (int i = 0; i < n - 1; i++)
+            for (int j = i + 1; j < n; j++) {
+                double a = W[i * S], p = 0, b = W[j * S];
+                for (int k = 0; k < m; k++) p += (double)A_(i, k) * A_(j, k);
+                if (fabs(p) <= eps * sqrt((double)a * b)) continue;
+                p *= 2;
+                const double beta = a - b, gamma = hypot_cv(p, beta);
+                T c, s;
+                if (beta < 0) {
+                    const double delta = (gamma - beta) * 0.5;
+                    s = (T)sqrt(delta / gamma);
+                    c = (T)(p / (gamma * s * 2));
+                } else {
+                    c = (T)sqrt((gamma + beta) / (gamma * 2));
+                    s = (T)(p / (gamma * c * 2));
+                }
+                a = b = 0;
+                for (int k = 0; k < m; k++) {
+                    const T ai = A_(i, k), aj = A_(j, k);
+                    const T t0 = c * ai + s * aj;
+                    const T t1 = -s * ai + c * aj;
+                    A_(i, k) = t0; A_(j, k) = t1;
+                    a += (double)t0 * t0; b += (double)t1 * t1;
+                }
+                W[i * S] = a; W[j * S] = b;
+                changed = true;
+                if (trackV)
+                    for (int k = 0; k < n; k++) {
+                        const T vi = V_(i, k), vj = V_(j, k);
+                        V_(i, k) = c * vi + s * vj;
+                        V_(j, k) = -s * vi + c * vj;
+                    }
+            }
+        if (!changed) break;
+    }
+    for (int i = 0; i < n; i++) {
+        double sd = 0;
+        for (int k = 0; k < m; k++) { const T t = A_(i, k); sd += (double)t * t; }
+        W[i * S] = sqrt(sd);
+    }
+    for (int i = 0; i < n - 1; i++) {
+        int j = i;
+        for (int k = i + 1; k < n; k++) if (W[j * S] < W[k * S]) j = k;
+        if (i != j) {
+            const double tw = W[i * S]; W[i * S] = W[j * S]; W[j * S] = tw;
+            for (int k = 0; k < m; k++) { const T t = A_(i, k); A_(i, k) = A_(j, k); A_(j, k) = t; }
+            if (trackV) for (int k = 0; k < n; k++) { const T t = V_(i, k); V_(i, k) = V_(j, k); V_(j, k) = t; }
+        }
+    }
+    if (!complete) return;
+    uint64_t state = 0x12345678;   // cv::RNG(0x12345678)
+    for (int i = 0; i < n1; i++) {
+        double sd = i < n ? W[i * S] : 0;
+        for (int ii = 0; ii < 100 && sd <= minval; ii++) {
+            const T val0 = (T)(1. / m);
+            for (int k = 0; k < m; k++) {
+                state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32);
+                A_(i, k) = ((unsigned)state & 256) != 0 ? val0 : -val0;
+            }
+            for (int it = 0; it < 2; it++)
+                for (int j = 0; j < i; j++) {
+                    sd = 0;
+                    for (int k = 0; k < m; k++) sd += A_(i, k) * A_(j, k);   // T products, double sum
+                    T asum = 0;
+                    for (int k = 0; k < m; k++) {
+                        const T t = (T)(A_(i, k) - sd * A_(j, k));
+                        A_(i, k) = t;
+                        asum += fabs(t);
+                    }
+                    asum = asum > eps * 100 ? 1 / asum : 0;
+                    for (int k = 0; k < m; k++) A_(i, k) *= asum;
+                }
+            sd = 0;
+            for (int k = 0; k < m; k++) { const T t = A_(i, k); sd += (double)t * t; }
+            sd = sqrt(sd);
+        }
+        const T s = (T)(sd > minval ? 1 / sd : 0.);
+        for (int k = 0; k < m; k++) A_(i, k) *= s;
+    }
+#undef A_
+#undef V_
 }
 
 }  // namespace cvm

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import K4, KP_DTYPE, RAND_MAX, check, lib, ptr, random_int, seed_rand  # noqa: F401 (RAND_MAX: part of this module's names)
+from ._solver import Handle
 
 ORBI_MODEL_HF, ORBI_MODEL_F = 0, 1
 MAX_ITERATIONS = 4096
@@ -67,9 +68,10 @@ def _setup(L):
     L._orbi_ready = True
 
 
-class Initializer:
+class Initializer(Handle):
     """Initializer(ReferenceFrame, sigma, iterations) on a matcher's device and stream; the reference frame is mvKeysUn
     (KP_DTYPE records) or a device-resident frame (ORBmatcher.frame_from_device)."""
+    _destroy = "orbi_destroy"
 
     def __init__(self, matcher, ref, K, sigma=1.0, iterations=200, model="HF"):
         self._L = lib()
@@ -87,17 +89,6 @@ class Initializer:
         n = C.c_int(0)
         check(self._L.orbi_size(self._h, C.byref(n)))
         self.n1 = n.value
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.orbi_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def normalization(self):
         """frame 1's Normalize: (meanX, meanY, sX, sY)"""

@@ -11,7 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import K4, check, lib, ptr, random_int, seed_rand
+from ._lib import K4, check, lib, ptr
+from ._solver import RansacHandle, draw_sets, f32 as _f32, given_sets, run_batch
 
 MAX_POINTS = 65535
 MAX_ITERATIONS = 4096
@@ -44,28 +45,9 @@ def result_fields(r, inliers):
 
 
 def make_pnp_sets(n, iterations, seed=0):
-    """iterate's set drawing (PnPsolver.cc:191-201) through libc's rand(), as DUtils::Random::RandomInt makes it
-    (int(rand() / (RAND_MAX + 1.0) * k)); seed None continues the process's stream.  The reference overwrites
-    vAvailableIndices[idx] with idx the drawn VALUE, not the drawn position, so a set can hold a point twice: kept.
-    Returns iterations x 4 indices into the solver's correspondences."""
-    if n < 4:
-        raise ValueError("%d correspondences: a set needs 4" % n)
-    seed_rand(seed)
-    sets = np.zeros((iterations, 4), dtype=np.int32)
-    for it in range(iterations):
-        avail = list(range(n))
-        live = n
-        for j in range(4):
-            randi = random_int(live)
-            idx = avail[randi]
-            sets[it, j] = idx
-            avail[idx] = avail[live - 1]
-            live -= 1
-    return sets
-
-
-def _f32(a, shape):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
+    """iterate's set drawing (PnPsolver.cc:191-201; _solver.draw_sets): iterations x 4 indices into the solver's
+    correspondences; seed None continues the process's rand() stream"""
+    return draw_sets(n, 4, iterations, seed)
 
 
 def _setup(L):
@@ -87,9 +69,10 @@ def _setup(L):
     L._orbp_ready = True
 
 
-class PnPsolver:
+class PnPsolver(RansacHandle):
     """PnPsolver(F, vpMapPointMatches) after its pointer chasing, on a matcher's device and stream: the n usable
     correspondences with idx their positions in vpMapPointMatches (n_all long)."""
+    _destroy, _max_iterations = "orbp_destroy", "orbp_max_iterations"
 
     def __init__(self, matcher, n_all, idx, P2D, sigma2, P3Dw, K, frame=None, level_sigma2=None):
         """frame (an opaque device-resident frame of this matcher's device) with level_sigma2: P2D and sigma2 are gathered
@@ -112,24 +95,6 @@ class PnPsolver:
             check(self._L.orbp_size(self._h, C.byref(a), C.byref(b)))
             self.n, self.n_all = a.value, b.value
         self.sets = None
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.orbp_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def max_iterations(self):
-        """mRansacMaxIts"""
-        v = C.c_int(0)
-        check(self._L.orbp_max_iterations(self._h, C.byref(v)))
-        return v.value
 
     @property
     def min_inliers(self):
@@ -183,24 +148,14 @@ def run_all(solvers, sets=None, extend=False):
     those of the hypotheses BEHIND their tables (orbp_run continues a table, the state kept); solver.sets grows."""
     if not solvers:
         return
-    L = solvers[0]._L
     keep = []
-    counts = np.zeros(len(solvers), dtype=np.int32)
     for i, s in enumerate(solvers):
-        if sets is not None and sets[i] is not None:
-            a = np.ascontiguousarray(sets[i], dtype=np.int32).reshape(-1)
+        a = given_sets(sets, i)
+        if a is not None:
             if a.shape[0] % 4:
                 raise ValueError("sets[%d]: %d entries, not a multiple of 4" % (i, a.shape[0]))
         elif s.n >= s.min_inliers:
             a = make_pnp_sets(s.n, s.max_iterations + EXTRA_SETS, seed=None).reshape(-1)
-        else:
-            a = None
-        if a is not None and extend and s.sets is not None:
-            s.sets = np.concatenate([s.sets, a.reshape(-1, 4)])
-        else:
-            s.sets = None if a is None else a.reshape(-1, 4)
-        counts[i] = 0 if a is None else a.shape[0] // 4
         keep.append(a)
-    hs = (C.c_void_p * len(solvers))(*[s._h for s in solvers])
-    ps = (C.c_void_p * len(solvers))(*[ptr(a) for a in keep])
-    check(L.orbp_run(hs, len(solvers), ps, ptr(counts)))
+    counts = np.array([0 if a is None else a.shape[0] // 4 for a in keep], dtype=np.int32)
+    run_batch(solvers[0]._L.orbp_run, solvers, keep, 4, extend, ptr(counts))

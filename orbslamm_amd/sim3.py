@@ -11,7 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import K4, check, lib, ptr, random_int, seed_rand
+from ._lib import K4, check, lib, ptr
+from ._solver import RansacHandle, draw_sets, f32 as _f32, given_sets, run_batch
 
 MAX_POINTS = 65535
 MAX_ITERATIONS = 4096
@@ -40,28 +41,9 @@ def result_fields(r, inliers):
 
 
 def make_sim3_sets(n, iterations, seed=0):
-    """iterate's set drawing (Sim3Solver.cc:163-177) through libc's rand(), as DUtils::Random::RandomInt makes it
-    (int(rand() / (RAND_MAX + 1.0) * k)); seed None continues the process's stream.  The reference overwrites
-    vAvailableIndices[idx] with idx the drawn VALUE, not the drawn position, so a set can hold a point twice: kept.
-    Returns iterations x 3 indices into the solver's correspondences."""
-    if n < 3:
-        raise ValueError("%d correspondences: a set needs 3" % n)
-    seed_rand(seed)
-    sets = np.zeros((iterations, 3), dtype=np.int32)
-    for it in range(iterations):
-        avail = list(range(n))
-        live = n
-        for j in range(3):
-            randi = random_int(live)
-            idx = avail[randi]
-            sets[it, j] = idx
-            avail[idx] = avail[live - 1]
-            live -= 1
-    return sets
-
-
-def _f32(a, shape):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
+    """iterate's set drawing (Sim3Solver.cc:163-177; _solver.draw_sets): iterations x 3 indices into the solver's
+    correspondences; seed None continues the process's rand() stream"""
+    return draw_sets(n, 3, iterations, seed)
 
 
 def _setup(L):
@@ -82,9 +64,10 @@ def _setup(L):
     L._orbs_ready = True
 
 
-class Sim3Solver:
+class Sim3Solver(RansacHandle):
     """Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale) after its pointer chasing, on a matcher's device and stream: the n
     usable correspondences with idx1 their positions in vpMatched12 (n1 long)."""
+    _destroy, _max_iterations = "orbs_destroy", "orbs_max_iterations"
 
     def __init__(self, matcher, n1, idx1, X1w, X2w, Rcw1, tcw1, Rcw2, tcw2, K1, K2, sigma2_1, sigma2_2, fix_scale=True):
         self._L = lib()
@@ -98,24 +81,6 @@ class Sim3Solver:
                 _f32(sigma2_1, n), _f32(sigma2_2, n)]
         check(self._L.orbs_create(matcher._h, self.n1, ptr(idx1), n, *[ptr(a) for a in args], int(bool(fix_scale)), C.byref(self._h)))
         self.sets = None
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.orbs_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def max_iterations(self):
-        """mRansacMaxIts"""
-        v = C.c_int(0)
-        check(self._L.orbs_max_iterations(self._h, C.byref(v)))
-        return v.value
 
     def set_ransac(self, probability=0.99, min_inliers=6, max_iterations=300):
         """SetRansacParameters"""
@@ -166,20 +131,14 @@ def run_all(solvers, sets=None):
     solver in list order); kept as solver.sets."""
     if not solvers:
         return
-    L = solvers[0]._L
     keep = []
     for i, s in enumerate(solvers):
         its = s.max_iterations
-        if sets is not None and sets[i] is not None:
-            a = np.ascontiguousarray(sets[i], dtype=np.int32).reshape(-1)
+        a = given_sets(sets, i)
+        if a is not None:
             if a.shape[0] != its * 3:
                 raise ValueError("sets[%d]: %d entries, want %d" % (i, a.shape[0], its * 3))
         elif s.n >= 3:
             a = make_sim3_sets(s.n, its, seed=None).reshape(-1)
-        else:
-            a = None
-        s.sets = None if a is None else a.reshape(-1, 3)
         keep.append(a)
-    hs = (C.c_void_p * len(solvers))(*[s._h for s in solvers])
-    ps = (C.c_void_p * len(solvers))(*[ptr(a) for a in keep])
-    check(L.orbs_run(hs, len(solvers), ps))
+    run_batch(solvers[0]._L.orbs_run, solvers, keep, 3)
