@@ -18,8 +18,35 @@
 //   tests/cpp/newpoints_dropin_gpu.cpp) without OpenCV: Mat needs a (rows, cols, type) constructor and at<float>(r, c);
 //   the keyframe's mDescriptors needs ptr<unsigned char>(row).
 //   Every call runs on the calling thread's matcher handle (orbm_thread_handle), as the other drop-ins do.
+//
+//   SearchInNeighborsT<KeyFrame, MapPoint, Mat>::Run(pKF)
+//       the drop-in for the body of LocalMapping::SearchInNeighbors (:454-534, monocular; orbl_fuse_batch):
+//           typedef iORB_SLAM::SearchInNeighborsT<KeyFrame, MapPoint, cv::Mat> Neighbors;
+//           void LocalMapping::SearchInNeighbors() { Neighbors::Run(mpCurrentKeyFrame); }
+//       It builds vpTargetKFs exactly as :456-479 do (marks included), makes ONE device call for the first phase (the
+//       distinct targets x GetMapPointMatches(), nulls left out), replays it target by target in vpTargetKFs' order, repeats
+//       included, with :851 and :953-973 on the host; gathers the candidates (:493-512) AFTER that replay, because they
+//       depend on its isBad state; makes one call for the second phase and replays it; then runs the "update points" loop
+//       and UpdateConnections() through the reference's own members.
+//       The serial dependency.  The search of a (target, point) pair reads the point's position, normal, distance bounds and
+//       descriptor.  Nothing in the two Fuse loops touches the first three (UpdateNormalAndDepth runs in the update loop).
+//       The descriptor changes in exactly one place: Replace ends in ComputeDistinctiveDescriptors() on the SURVIVING point
+//       (MapPoint.cc:212).  A point of the current keyframe that survived a Replace at target k is therefore searched with a
+//       new descriptor at targets k+1...  The drop-in keeps the set of survivors of every Replace it issues (both branches,
+//       by pointer).  For a pair whose point is in that set the device's best is stale but its (u, v, level) is not: such a
+//       pair is re-scored on the host through the reference's own pKF->GetFeaturesInArea(u, v, radius) and :905-951 with the
+//       point's current GetDescriptor().  Every other pair's device result is what the serial loop computes, since it
+//       depends on nothing the loop writes.  The second phase reads every descriptor after the first phase's replay, and
+//       within it no candidate that is processed later can change before it is processed: the survivor of a Replace there
+//       is either the candidate just processed (candidates are distinct: mnFuseCandidateForKF) or a point of the current
+//       keyframe, which :851's IsInKeyFrame skips.  (The set is consulted there all the same.)
+//       MapPoint::mfMinDistance / mfMaxDistance are read raw (the library forms the invariance bounds and PredictScale's
+//       ratio itself); they are protected in the reference: INTEGRATION.md.  predict: the tree's own PredictScale as
+//       (ratio, logScaleFactor) -> level where its log resolves to the double overload; null: the float form.
 #pragma once
 
+#include <map>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -129,6 +156,210 @@ private:
         }
         s.kf.K[0] = pKF->fx; s.kf.K[1] = pKF->fy; s.kf.K[2] = pKF->cx; s.kf.K[3] = pKF->cy;
         s.kf.median_depth = 0.f;
+    }
+
+    static void check(int rc) { detail::check(rc, "orbslamm_hip: "); }
+};
+
+template <class KeyFrame, class MapPoint, class Mat>
+class SearchInNeighborsT {
+public:
+    static const int TH_LOW = 50;
+    struct Stats { int targets = 0, distinctTargets = 0, pairs1 = 0, pairs2 = 0, fused1 = 0, fused2 = 0, dirtyRescored = 0, replaced = 0, added = 0; };
+
+    static void Run(KeyFrame* pKF, int device = 0, Stats* stats = nullptr, orbl_predict_fn predict = nullptr, float th = 3.0f)
+    {
+        Stats st;
+        // Retrieve neighbor keyframes (:456-479)
+        const int nn = 20;
+        const std::vector<KeyFrame*> vpNeighKFs = pKF->GetBestCovisibilityKeyFrames(nn);
+        std::vector<KeyFrame*> vpTargetKFs;
+        for (size_t a = 0; a < vpNeighKFs.size(); a++) {
+            KeyFrame* pKFi = vpNeighKFs[a];
+            if (pKFi->isBad() || pKFi->mnFuseTargetForKF == pKF->mnId) continue;
+            vpTargetKFs.push_back(pKFi);
+            pKFi->mnFuseTargetForKF = pKF->mnId;
+            const std::vector<KeyFrame*> vpSecondNeighKFs = pKFi->GetBestCovisibilityKeyFrames(5);
+            for (size_t b = 0; b < vpSecondNeighKFs.size(); b++) {
+                KeyFrame* pKFi2 = vpSecondNeighKFs[b];
+                if (pKFi2->isBad() || pKFi2->mnFuseTargetForKF == pKF->mnId || pKFi2->mnId == pKF->mnId) continue;
+                vpTargetKFs.push_back(pKFi2);
+            }
+        }
+        st.targets = (int)vpTargetKFs.size();
+        orbm_t* h = nullptr;
+        check(orbm_thread_handle(device, &h));
+        const int nlevels = (int)pKF->mvScaleFactors.size();
+        std::vector<float> breaks((size_t)nlevels + 1);
+        check(orbl_level_breaks(pKF->mfLogScaleFactor, nlevels, predict, breaks.data()));
+        std::set<MapPoint*> dirty;
+
+        // Search matches by projection from current KF in target KFs (:482-490): one call over the distinct targets
+        std::vector<MapPoint*> vpMapPointMatches = pKF->GetMapPointMatches();
+        {
+            std::map<KeyFrame*, int> slotOf;
+            std::vector<KeyFrame*> distinct;
+            for (size_t t = 0; t < vpTargetKFs.size(); t++)
+                if (!slotOf.count(vpTargetKFs[t])) { slotOf[vpTargetKFs[t]] = (int)distinct.size(); distinct.push_back(vpTargetKFs[t]); }
+            st.distinctTargets = (int)distinct.size();
+            std::vector<OrblFusePoint> pool;
+            std::vector<int> poolOf(vpMapPointMatches.size(), -1);
+            for (size_t i = 0; i < vpMapPointMatches.size(); i++)
+                if (vpMapPointMatches[i]) { poolOf[i] = (int)pool.size(); pool.push_back(point(vpMapPointMatches[i])); }
+            std::vector<OrblFuseResult> res;
+            search(h, pKF, distinct, pool, th, breaks, res);
+            st.pairs1 = (int)res.size();
+            for (size_t t = 0; t < vpTargetKFs.size(); t++)
+                st.fused1 += replay(vpTargetKFs[t], vpMapPointMatches, poolOf, res.data() + (size_t)slotOf[vpTargetKFs[t]] * pool.size(), th, dirty, st);
+        }
+
+        // Search matches by projection from target KFs in current KF (:492-514): the candidates as the replay left them
+        {
+            std::vector<MapPoint*> vpFuseCandidates;
+            vpFuseCandidates.reserve(vpTargetKFs.size() * vpMapPointMatches.size());
+            for (size_t t = 0; t < vpTargetKFs.size(); t++) {
+                const std::vector<MapPoint*> vpMapPointsKFi = vpTargetKFs[t]->GetMapPointMatches();
+                for (size_t j = 0; j < vpMapPointsKFi.size(); j++) {
+                    MapPoint* pMP = vpMapPointsKFi[j];
+                    if (!pMP) continue;
+                    if (pMP->isBad() || pMP->mnFuseCandidateForKF == pKF->mnId) continue;
+                    pMP->mnFuseCandidateForKF = pKF->mnId;
+                    vpFuseCandidates.push_back(pMP);
+                }
+            }
+            std::vector<OrblFusePoint> pool(vpFuseCandidates.size());
+            std::vector<int> poolOf(vpFuseCandidates.size());
+            for (size_t i = 0; i < vpFuseCandidates.size(); i++) { pool[i] = point(vpFuseCandidates[i]); poolOf[i] = (int)i; }
+            std::vector<OrblFuseResult> res;
+            search(h, pKF, std::vector<KeyFrame*>(1, pKF), pool, th, breaks, res);
+            st.pairs2 = (int)res.size();
+            dirty.clear();   // (every descriptor was read after the first phase's replay)
+            st.fused2 = replay(pKF, vpFuseCandidates, poolOf, res.data(), th, dirty, st);
+        }
+
+        // Update points (:517-530)
+        vpMapPointMatches = pKF->GetMapPointMatches();
+        for (size_t i = 0; i < vpMapPointMatches.size(); i++) {
+            MapPoint* pMP = vpMapPointMatches[i];
+            if (pMP && !pMP->isBad()) { pMP->ComputeDistinctiveDescriptors(); pMP->UpdateNormalAndDepth(); }
+        }
+        // Update connections in covisibility graph
+        pKF->UpdateConnections();
+        if (stats) *stats = st;
+    }
+
+private:
+    static OrblFusePoint point(MapPoint* pMP)
+    {
+        OrblFusePoint p;
+        const Mat X = pMP->GetWorldPos(), n = pMP->GetNormal(), d = pMP->GetDescriptor();
+        for (int r = 0; r < 3; r++) { p.pos[r] = X.template at<float>(r, 0); p.normal[r] = n.template at<float>(r, 0); }
+        p.min_distance = pMP->mfMinDistance; p.max_distance = pMP->mfMaxDistance;
+        const unsigned char* b = d.template ptr<unsigned char>(0);
+        for (int i = 0; i < 32; i++) p.desc[i] = b[i];
+        return p;
+    }
+
+    struct Flat { std::vector<OrbxKeyPoint> keys; std::vector<uint8_t> desc; };
+
+    // every pool point against every target, one call: res[t * pool.size() + i]
+    static void search(orbm_t* h, KeyFrame* pCur, const std::vector<KeyFrame*>& targets, const std::vector<OrblFusePoint>& pool, float th,
+                       const std::vector<float>& breaks, std::vector<OrblFuseResult>& res)
+    {
+        const int T = (int)targets.size(), P = (int)pool.size();
+        res.assign((size_t)T * P, OrblFuseResult());
+        if (!T || !P) return;
+        if (T > ORBL_FUSE_MAX_TARGETS) throw std::runtime_error("SearchInNeighbors: more targets than ORBL_FUSE_MAX_TARGETS");
+        std::vector<OrblFuseTarget> rec((size_t)T);
+        std::vector<Flat> flat((size_t)T);
+        std::vector<const OrbxKeyPoint*> keys((size_t)T);
+        std::vector<const uint8_t*> desc((size_t)T);
+        std::vector<int32_t> n((size_t)T), jobStart((size_t)T + 1), jobPoint((size_t)T * P);
+        for (int t = 0; t < T; t++) {
+            KeyFrame* k = targets[t];
+            OrblFuseTarget& r = rec[t];
+            const Mat R = k->GetRotation(), tc = k->GetTranslation(), O = k->GetCameraCenter();
+            for (int a = 0; a < 3; a++) {
+                for (int c = 0; c < 3; c++) r.Rcw[3 * a + c] = R.template at<float>(a, c);
+                r.tcw[a] = tc.template at<float>(a, 0);
+                r.Ow[a] = O.template at<float>(a, 0);
+            }
+            r.K[0] = k->fx; r.K[1] = k->fy; r.K[2] = k->cx; r.K[3] = k->cy;
+            r.min_x = (float)k->mnMinX; r.max_x = (float)k->mnMaxX; r.min_y = (float)k->mnMinY; r.max_y = (float)k->mnMaxY;
+            r.grid.minX = (float)k->mnMinX; r.grid.minY = (float)k->mnMinY;
+            r.grid.invW = k->mfGridElementWidthInv; r.grid.invH = k->mfGridElementHeightInv;
+            r.grid.cols = k->mnGridCols; r.grid.rows = k->mnGridRows;
+            Flat& f = flat[t];
+            f.keys.resize((size_t)k->N); f.desc.resize((size_t)k->N * 32);
+            for (int i = 0; i < k->N; i++) {
+                const auto& kp = k->mvKeysUn[i];
+                OrbxKeyPoint& o = f.keys[i];
+                o.x = kp.pt.x; o.y = kp.pt.y; o.size = kp.size; o.angle = kp.angle; o.response = kp.response; o.octave = kp.octave; o.class_id = kp.class_id;
+                const unsigned char* d = k->mDescriptors.template ptr<unsigned char>(i);
+                for (int b = 0; b < 32; b++) f.desc[(size_t)i * 32 + b] = d[b];
+            }
+            keys[t] = f.keys.data(); desc[t] = f.desc.data(); n[t] = k->N;
+            jobStart[t] = t * P;
+            for (int i = 0; i < P; i++) jobPoint[(size_t)t * P + i] = i;
+        }
+        jobStart[T] = T * P;
+        check(orbl_fuse_batch(h, rec.data(), keys.data(), desc.data(), n.data(), T, pool.data(), P, jobStart.data(), jobPoint.data(), th,
+                              pCur->mvScaleFactors.data(), pCur->mvInvLevelSigma2.data(), (int)pCur->mvScaleFactors.size(), breaks.data(), res.data()));
+    }
+
+    // Fuse's loop (:844-974) over results the device holds for this target; a dirty point is re-scored on the host
+    static int replay(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const std::vector<int>& poolOf, const OrblFuseResult* res, float th,
+                      std::set<MapPoint*>& dirty, Stats& st)
+    {
+        int nFused = 0;
+        for (size_t i = 0; i < vpMapPoints.size(); i++) {
+            MapPoint* pMP = vpMapPoints[i];
+            if (!pMP) continue;
+            if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+            const OrblFuseResult& r = res[poolOf[i]];
+            if (r.status < ORBL_FUSE_ST_NO_CANDIDATE) continue;   // a projection gate, or the level outside mvScaleFactors
+            int bestDist = r.best_dist, bestIdx = r.best_idx;
+            if (dirty.count(pMP)) {
+                // :894-951 with the descriptor the point holds NOW; u, v and the level do not depend on it
+                st.dirtyRescored++;
+                const float u = r.u, v = r.v;
+                const int nPredictedLevel = r.level;
+                const float radius = th * pKF->mvScaleFactors[nPredictedLevel];
+                const std::vector<size_t> vIndices = pKF->GetFeaturesInArea(u, v, radius);
+                const Mat dMP = pMP->GetDescriptor();
+                const unsigned char* a = dMP.template ptr<unsigned char>(0);
+                bestDist = 256; bestIdx = -1;
+                for (size_t k = 0; k < vIndices.size(); k++) {
+                    const size_t idx = vIndices[k];
+                    const auto& kp = pKF->mvKeysUn[idx];
+                    const int kpLevel = kp.octave;
+                    if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) continue;
+                    const float ex = u - kp.pt.x, ey = v - kp.pt.y;
+                    const float e2 = ex * ex + ey * ey;
+                    if (e2 * pKF->mvInvLevelSigma2[kpLevel] > 5.99) continue;
+                    const unsigned char* b = pKF->mDescriptors.template ptr<unsigned char>((int)idx);
+                    int dist = 0;
+                    for (int w = 0; w < 32; w++) dist += __builtin_popcount((unsigned)(a[w] ^ b[w]));
+                    if (dist < bestDist) { bestDist = dist; bestIdx = (int)idx; }
+                }
+            }
+            if (bestDist <= TH_LOW && bestIdx >= 0) {   // :954-973
+                MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);
+                if (pMPinKF) {
+                    if (!pMPinKF->isBad()) {
+                        if (pMPinKF->Observations() > pMP->Observations()) { pMP->Replace(pMPinKF); dirty.insert(pMPinKF); }
+                        else { pMPinKF->Replace(pMP); dirty.insert(pMP); }
+                        st.replaced++;
+                    }
+                } else {
+                    pMP->AddObservation(pKF, bestIdx);
+                    pKF->AddMapPoint(pMP, bestIdx);
+                    st.added++;
+                }
+                nFused++;
+            }
+        }
+        return nFused;
     }
 
     static void check(int rc) { detail::check(rc, "orbslamm_hip: "); }

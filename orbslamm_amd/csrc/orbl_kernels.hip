@@ -22,6 +22,7 @@
 //                         written behind the earlier rows' in idx1 order (the reference's order).  Integers, no atomics.
 // Arithmetic: one IEEE operation per source operation (the library is built with -ffp-contract=off); OpenCV's pieces are
 // orbx_cvmath.hpp's.
+// Below them: k_fuse_batch, the searches of LocalMapping::SearchInNeighbors' Fuse calls for all targets in one launch (§8l).
 #pragma once
 
 namespace orbl {
@@ -274,6 +275,147 @@ __global__ __launch_bounds__(kRowThreads) void k_newpoints_compact(Args a)
         pos += chunk;
     }
     if (k == a.nNeigh - 1 && threadIdx.x == 0) *a.total = pos;
+}
+
+// ------------------------------------------------------------------ SearchInNeighbors: the batched Fuse
+// k_fuse_batch: the searches of ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:854-951, monocular) for every
+// (target, point) of a job list, one launch however many targets.  A workgroup takes one tile of kFuseTile consecutive job
+// entries of ONE target (the host cuts the CSR into tiles: FuseWork), so the machine is filled from the job list and not
+// from a target.  Two steps:
+//   1. one lane per entry: :855-892 in orbx_cvmath.hpp's forms, the level from the break table (no device log), the
+//      result of a pair that a gate ended written at once, the survivors compacted by ballot into LDS;
+//   2. kFuseLpp lanes per survivor walk its window together in GetFeaturesInArea's order (for_each_in_area): each lane
+//      holds 32 / kFuseLpp bytes of the point's descriptor and reads that share of a candidate's (one 32-byte line per
+//      candidate and group instead of a 32-byte gather per lane), the partial popcounts are summed across the lanes, and
+//      every lane keeps the same (bestDist, bestIdx) under the strict `<` of k_window_best.
+// No atomics: a job entry is written by exactly one lane.  kFuseLpp is a build-time choice (-DORBL_FUSE_LPP=1|2|4|8) so that
+// tools/fuse_bench.py can A/B it; 8 measured best, and staging the target's cell-start table in LDS lost at every kFuseLpp
+// (docs/experiments.md, "k_fuse_batch: lanes per point").
+#ifndef ORBL_FUSE_LPP
+#define ORBL_FUSE_LPP 8
+#endif
+constexpr int kFuseLpp = ORBL_FUSE_LPP;
+constexpr int kFuseThreads = 256;
+constexpr int kFuseTile = kFuseThreads / kFuseLpp;
+static_assert(kFuseLpp == 1 || kFuseLpp == 2 || kFuseLpp == 4 || kFuseLpp == 8, "lanes per point");
+
+enum : uint8_t { FST_DEPTH = 0, FST_OUTSIDE_IMAGE, FST_DISTANCE, FST_VIEW_ANGLE, FST_LEVEL_RANGE, FST_NO_CANDIDATE, FST_FOUND };
+
+struct FuseTgt {
+    const orbm::KeyDev* keys; const uint8_t* desc; const int32_t* cellStart; const int32_t* cellIdx;
+    orbm::GridDev grid;
+    float Rcw[9], tcw[3], Ow[3], fx, fy, cx, cy, minX, maxX, minY, maxY;
+    int32_t n;
+};
+struct FusePt { float pos[3], normal[3], minDistance, maxDistance; uint32_t desc[8]; };       // OrblFusePoint
+struct FuseRes { int32_t bestIdx, bestDist; float u, v; int8_t level; uint8_t status, pad[2]; };  // OrblFuseResult
+struct FuseWork { int32_t target, begin, count, pad; };
+struct FuseArgs {
+    const FuseTgt* tgt; const FusePt* pts; const int32_t* jobPoint; const FuseWork* work;
+    FuseRes* out;
+    float th; int32_t nlevels;
+    float sf[16], invSigma2[16], breaks[17];
+};
+
+__global__ __launch_bounds__(kFuseThreads) void k_fuse_batch(FuseArgs a)
+{
+    __shared__ float sU[kFuseTile], sV[kFuseTile];
+    __shared__ int32_t sEntry[kFuseTile], sPoint[kFuseTile], sLevel[kFuseTile];
+    __shared__ int sWave[kFuseThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const FuseWork w = a.work[blockIdx.x];
+    const FuseTgt& T = a.tgt[w.target];
+    const orbm::GridDev grid = T.grid;
+    // 1. the projection gates (:855-892), one lane per entry
+    bool alive = false;
+    FuseRes r;
+    r.bestIdx = -1; r.bestDist = 256; r.u = 0.f; r.v = 0.f; r.level = -1; r.status = FST_DEPTH; r.pad[0] = r.pad[1] = 0;
+    int entry = 0, p = 0;
+    if (tid < w.count) {   // (w.count <= kFuseTile)
+        entry = w.begin + tid;
+        p = a.jobPoint[entry];
+        const FusePt& P = a.pts[p];
+        const float X[3] = {P.pos[0], P.pos[1], P.pos[2]};
+        float pc[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) pc[i] = cvm::gemm3_elem(T.Rcw[3 * i], T.Rcw[3 * i + 1], T.Rcw[3 * i + 2], X[0], X[1], X[2], 1.0, T.tcw[i], 1.0);
+        if (!(pc[2] < 0.0f)) {
+            const float invz = __fdiv_rn(1.f, pc[2]);
+            const float x = pc[0] * invz, y = pc[1] * invz;
+            const float u = T.fx * x + T.cx, v = T.fy * y + T.cy;
+            r.u = u; r.v = v;
+            r.status = FST_OUTSIDE_IMAGE;
+            if (u >= T.minX && u < T.maxX && v >= T.minY && v < T.maxY) {
+                const float maxDistance = 1.2f * P.maxDistance, minDistance = 0.8f * P.minDistance;
+                const float PO[3] = {X[0] - T.Ow[0], X[1] - T.Ow[1], X[2] - T.Ow[2]};
+                const float dist3D = (float)cvm::norm3(PO);
+                r.status = FST_DISTANCE;
+                if (!(dist3D < minDistance || dist3D > maxDistance)) {
+                    double dt = 0;
+#pragma unroll
+                    for (int i = 0; i < 3; i++) dt += (double)PO[i] * (double)P.normal[i];
+                    r.status = FST_VIEW_ANGLE;
+                    if (!(dt < 0.5 * (double)dist3D)) {
+                        // PredictScale: the breaks below ratio (a NaN ratio is above none)
+                        const float ratio = __fdiv_rn(P.maxDistance, dist3D);
+                        int c = 0;
+                        for (int j = 0; j <= a.nlevels; j++) c += ratio > a.breaks[j] ? 1 : 0;
+                        r.level = (int8_t)(c - 1);
+                        r.status = FST_LEVEL_RANGE;
+                        alive = c >= 1 && c <= a.nlevels;
+                    }
+                }
+            }
+        }
+        if (!alive) a.out[entry] = r;
+    }
+    // the survivors, in entry order
+    const unsigned long long m = __ballot(alive);
+    if (lane == 0) sWave[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, nSurv = 0;
+#pragma unroll
+    for (int k = 0; k < kFuseThreads / 64; k++) { const int c = sWave[k]; nSurv += c; if (k < wave) before += c; }
+    if (alive) {
+        const int s = before + __popcll(m & ((1ull << lane) - 1ull));
+        sU[s] = r.u; sV[s] = r.v; sEntry[s] = entry; sPoint[s] = p; sLevel[s] = r.level;
+    }
+    __syncthreads();
+    // 2. kFuseLpp lanes per survivor: :894-951
+    constexpr int W = 8 / kFuseLpp;
+    const int sub = tid % kFuseLpp;
+    for (int s = tid / kFuseLpp; s < nSurv; s += kFuseThreads / kFuseLpp) {
+        const float u = sU[s], v = sV[s];
+        const int pred = sLevel[s];
+        const float radius = a.th * a.sf[pred];
+        uint32_t qw[W];
+        const uint32_t* qp = a.pts[sPoint[s]].desc + sub * W;
+#pragma unroll
+        for (int i = 0; i < W; i++) qw[i] = qp[i];
+        int bestDist = 256, bestIdx = -1;
+        orbm::for_each_in_area(grid, T.keys, T.cellStart, T.cellIdx, u, v, radius, -1, -1, [&](int idx) {
+            const orbm::KeyDev& kp = T.keys[idx];
+            const int kpLevel = kp.octave;
+            if (kpLevel < pred - 1 || kpLevel > pred) return;
+            const float ex = __fsub_rn(u, kp.x), ey = __fsub_rn(v, kp.y);
+            const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+            if ((double)__fmul_rn(e2, a.invSigma2[kpLevel]) > 5.99) return;
+            const uint32_t* tp = (const uint32_t*)(T.desc + (int64_t)idx * 32) + sub * W;
+            int d = 0;
+#pragma unroll
+            for (int i = 0; i < W; i++) d += __popc(qw[i] ^ tp[i]);
+            // (the lanes of a point take the same path through the walk: their partners are active here)
+#pragma unroll
+            for (int k = kFuseLpp / 2; k >= 1; k >>= 1) d += __shfl_xor(d, k);
+            if (d < bestDist) { bestDist = d; bestIdx = idx; }
+        });
+        if (sub == 0) {
+            FuseRes o;
+            o.bestIdx = bestIdx; o.bestDist = bestDist; o.u = u; o.v = v; o.level = (int8_t)pred;
+            o.status = bestIdx >= 0 ? FST_FOUND : FST_NO_CANDIDATE; o.pad[0] = o.pad[1] = 0;
+            a.out[sEntry[s]] = o;
+        }
+    }
 }
 
 }  // namespace orbl

@@ -6,12 +6,19 @@ triangulates every pair, applies the reference's gates and returns the new point
     nbs = [dict(keys=..., desc=..., fv=..., skip=..., kf=keyframe(..., median_depth=d)), ...]
     pts, status, f12 = create_new_map_points(matcher, cur, nbs, scale_factors, level_sigma2, 1.2)
 
-With device-resident frames (ORBmatcher.frame_from_device + frame_compute_bow) a side is dict(frame=F, skip=..., kf=...)."""
+With device-resident frames (ORBmatcher.frame_from_device + frame_compute_bow) a side is dict(frame=F, skip=..., kf=...).
+
+LocalMapping::SearchInNeighbors (:454-534): fuse_batch runs the searches of ORBmatcher::Fuse for many target keyframes in
+one call (orbl_fuse_batch*, include/orbslamm_fuse.h); level_breaks is the host-side table that stands in for PredictScale's log.
+
+    tg = [fuse_target(Rcw, tcw, Ow, K, (0, 640, 0, 480), grid, keys=mvKeysUn, desc=descriptors), ...]   # or frame=F
+    res = fuse_batch(matcher, tg, fuse_points(pos, normal, min_d, max_d, desc), (job_start, job_point), scale_factors,
+                     inv_level_sigma2, level_breaks(np.log(np.float32(1.2)), 8))"""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import KP_DTYPE, K4, OrbmFeatVec, check, lib, ptr
+from ._lib import KP_DTYPE, K4, OrbmFeatVec, OrbmGrid, check, lib, ptr
 
 MAX_NEIGHBOURS = 32
 (ST_NEIGHBOUR_SKIPPED, ST_FEATURE_SKIPPED, ST_NO_MATCH, ST_PARALLAX, ST_X3D_ZERO, ST_Z1, ST_Z2, ST_REPROJ1, ST_REPROJ2, ST_DIST_ZERO,
@@ -46,6 +53,9 @@ def _setup(L):
                                              C.c_int, vp, C.c_int, C.POINTER(C.c_int), vp, vp]
     L.orbl_create_new_map_points_frames.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, C.c_int, vp, C.c_int,
                                                     C.POINTER(C.c_int), vp, vp]
+    L.orbl_level_breaks.argtypes = [C.c_float, C.c_int, vp, vp]
+    L.orbl_fuse_batch.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, vp, vp]
+    L.orbl_fuse_batch_frames.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, vp, vp]
     L._orbl_ready = True
 
 
@@ -128,3 +138,104 @@ def create_new_map_points(matcher, cur, neighbours, scale_factors, level_sigma2,
             e.needed = n_new.value
             raise
     return out[:n_new.value].copy(), status, f12
+
+
+# ------------------------------------------------------------------------------------------------ SearchInNeighbors
+FUSE_MAX_TARGETS = 128
+FUSE_MAX_JOBS = 1 << 22
+(FUSE_ST_DEPTH, FUSE_ST_OUTSIDE_IMAGE, FUSE_ST_DISTANCE, FUSE_ST_VIEW_ANGLE, FUSE_ST_LEVEL_RANGE, FUSE_ST_NO_CANDIDATE,
+ FUSE_ST_FOUND) = range(7)
+FUSE_STATUS_NAMES = ("depth", "outside_image", "distance", "view_angle", "level_range", "no_candidate", "found")
+
+GRID_DTYPE = np.dtype([("minX", "<f4"), ("minY", "<f4"), ("invW", "<f4"), ("invH", "<f4"), ("cols", "<i4"), ("rows", "<i4")])
+FUSE_TARGET_DTYPE = np.dtype([("Rcw", "<f4", (3, 3)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("K", "<f4", (4,)),
+                              ("bounds", "<f4", (4,)), ("grid", GRID_DTYPE)])
+FUSE_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4"),
+                             ("desc", "u1", (32,))])
+FUSE_RESULT_DTYPE = np.dtype([("best_idx", "<i4"), ("best_dist", "<i4"), ("u", "<f4"), ("v", "<f4"), ("level", "i1"), ("status", "u1"),
+                              ("pad", "u1", (2,))])
+assert FUSE_TARGET_DTYPE.itemsize == 116 and FUSE_POINT_DTYPE.itemsize == 64 and FUSE_RESULT_DTYPE.itemsize == 20
+PREDICT_FN = C.CFUNCTYPE(C.c_int, C.c_float, C.c_float)
+
+
+def level_breaks(log_scale_factor, nlevels, predict=None):
+    """orbl_level_breaks (host; needs no GPU): nlevels + 1 floats, entry L + 1 the largest ratio whose PredictScale level is
+    <= L.  predict: the tree's own PredictScale as a Python callable (ratio, log_scale_factor) -> int; None: the float form"""
+    L = lib()
+    _setup(L)
+    out = np.zeros(int(nlevels) + 1, np.float32)
+    fn = PREDICT_FN(predict) if predict is not None else None
+    check(L.orbl_level_breaks(C.c_float(log_scale_factor), int(nlevels), fn, ptr(out)))
+    return out
+
+
+def fuse_target(Rcw, tcw, Ow, K, bounds, grid, keys=None, desc=None, frame=None):
+    """one target keyframe: the OrblFuseTarget record (bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY), grid an OrbmGrid) with
+    either its host arrays (mvKeysUn, descriptors) or a device-resident frame"""
+    rec = np.zeros((), dtype=FUSE_TARGET_DTYPE)
+    rec["Rcw"] = np.asarray(Rcw, dtype=np.float32).reshape(3, 3)
+    rec["tcw"] = np.asarray(tcw, dtype=np.float32).reshape(3)
+    rec["Ow"] = np.asarray(Ow, dtype=np.float32).reshape(3)
+    rec["K"] = K4(K)
+    rec["bounds"] = np.asarray(bounds, dtype=np.float32).reshape(4)
+    if isinstance(grid, OrbmGrid):
+        grid = (grid.minX, grid.minY, grid.invW, grid.invH, grid.cols, grid.rows)
+    rec["grid"] = np.array(tuple(grid), dtype=GRID_DTYPE)
+    t = dict(rec=rec)
+    if frame is not None:
+        t["frame"] = frame
+    else:
+        t["keys"] = np.ascontiguousarray(keys, dtype=KP_DTYPE)
+        t["desc"] = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        if t["keys"].shape[0] != t["desc"].shape[0]:
+            raise ValueError("keys and descriptors differ in length")
+    return t
+
+
+def fuse_points(pos, normal, min_distance, max_distance, desc):
+    """the pool of map points: GetWorldPos, GetNormal, the RAW mfMinDistance / mfMaxDistance, GetDescriptor"""
+    pos = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
+    pts = np.zeros(pos.shape[0], dtype=FUSE_POINT_DTYPE)
+    pts["pos"], pts["normal"] = pos, np.asarray(normal, dtype=np.float32).reshape(-1, 3)
+    pts["min_distance"], pts["max_distance"] = min_distance, max_distance
+    pts["desc"] = np.asarray(desc, dtype=np.uint8).reshape(-1, 32)
+    return pts
+
+
+def fuse_batch(matcher, targets, points, jobs, scale_factors, inv_level_sigma2, breaks, th=3.0):
+    """The searches of Fuse(pKF, vpMapPoints, th) for every target in one call.  targets: fuse_target(...) dicts, all with host
+    arrays or all with frames; points: a FUSE_POINT_DTYPE pool; jobs: (job_start, job_point), CSR over the targets.  Returns
+    a FUSE_RESULT_DTYPE array, one record per job entry in job order.  The caller applies bestDist <= TH_LOW and edits the map."""
+    L = lib()
+    _setup(L)
+    T = len(targets)
+    recs = np.zeros(max(T, 1), dtype=FUSE_TARGET_DTYPE)
+    for k, t in enumerate(targets):
+        recs[k] = t["rec"]
+    pts = np.ascontiguousarray(points, dtype=FUSE_POINT_DTYPE)
+    js = np.ascontiguousarray(jobs[0], dtype=np.int32).reshape(-1)
+    jp = np.ascontiguousarray(jobs[1], dtype=np.int32).reshape(-1)
+    if js.shape[0] != T + 1:
+        raise ValueError("job_start has %d entries for %d targets" % (js.shape[0], T))
+    if T and jp.shape[0] < js[-1]:
+        raise ValueError("job_point is shorter than job_start says")
+    sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+    sg = np.ascontiguousarray(inv_level_sigma2, dtype=np.float32).reshape(-1)
+    br = np.ascontiguousarray(breaks, dtype=np.float32).reshape(-1)
+    if sf.shape[0] != sg.shape[0] or br.shape[0] != sf.shape[0] + 1:
+        raise ValueError("scale_factors, inv_level_sigma2 and the break table disagree in length")
+    J = int(js[-1]) if T else 0
+    out = np.zeros(max(J, 0), dtype=FUSE_RESULT_DTYPE)
+    frames = T > 0 and "frame" in targets[0]
+    if any(("frame" in t) != frames for t in targets):
+        raise ValueError("device-resident frames and host arrays cannot be mixed in one call")
+    if frames:
+        fr = (C.c_void_p * max(T, 1))(*[t["frame"].value if isinstance(t["frame"], C.c_void_p) else t["frame"] for t in targets])
+        rc = L.orbl_fuse_batch_frames(matcher._h, ptr(recs), fr, T, ptr(pts), pts.shape[0], ptr(js), ptr(jp), C.c_float(th), ptr(sf), ptr(sg),
+                                      sf.shape[0], ptr(br), ptr(out))
+    else:
+        n = np.array([t["keys"].shape[0] for t in targets] or [0], dtype=np.int32)
+        rc = L.orbl_fuse_batch(matcher._h, ptr(recs), _ptr_array([t["keys"] for t in targets]), _ptr_array([t["desc"] for t in targets]), ptr(n),
+                               T, ptr(pts), pts.shape[0], ptr(js), ptr(jp), C.c_float(th), ptr(sf), ptr(sg), sf.shape[0], ptr(br), ptr(out))
+    check(rc)
+    return out
