@@ -1,0 +1,259 @@
+// LoopClosing_hip.hpp -- the reference's LoopClosing::SearchAndFuse (src/LoopClosing.cc:601-627) and
+// MultiMapper::SearchAndFuse (src/MultiMapper.cc:668-694), monocular, over the C ABI of liborbslamm_hip.so (orbc_*,
+// include/orbslamm_loopfuse.h).  Header-only, C++11.
+//
+//   SearchAndFuseT<KeyFrame, MapPoint, Mat>::Run(corrected, vpLoopMapPoints, th)
+//       the drop-in for the body of both functions.  `corrected` holds (KeyFrame*, Scw) in the caller's iteration order
+//       (CorrectedSim3's; for the merge, mvpCurrentMapKFs' with each keyframe's corrected pose), Scw a 4x4 CV_32F Mat as
+//       Converter::toCvMat(g2oScw) gives it.  In the reference tree:
+//           typedef iORB_SLAM::SearchAndFuseT<KeyFrame, MapPoint, cv::Mat> LoopFuse;
+//           void LoopClosing::SearchAndFuse(const KeyFrameAndPose& CorrectedPosesMap)
+//           {
+//               std::vector<std::pair<KeyFrame*, cv::Mat> > corrected;
+//               for (auto mit = CorrectedPosesMap.begin(); mit != CorrectedPosesMap.end(); mit++)
+//                   corrected.push_back(std::make_pair(mit->first, Converter::toCvMat(mit->second)));
+//               LoopFuse::Run(corrected, mvpLoopMapPoints, 4, [this] { return std::unique_lock<std::mutex>(mpMap->mMutexMapUpdate); });
+//           }
+//       Run decomposes every Scw (ORBmatcher.cc:987-992, cvsem::decomposeSim3), makes ONE device call over all targets
+//       (orbc_search_and_fuse: every loop point against every corrected keyframe; a keyframe listed twice is flattened and
+//       uploaded once) and then replays the serial part on the host, target by target, in the reference's order:
+//         1. spAlreadyFound = pKF->GetMapPoints(), read at this target's turn: it depends on every earlier Replace.
+//         2. for iMP ascending: skip isBad() and already-found points; take the pair's hit from the device list with a cursor
+//            over hit_start; apply :1084-1097 (GetMapPoint(bestIdx), vpReplacePoint[iMP], or AddObservation + AddMapPoint at
+//            once); count nFused.
+//         3. under the caller's lock: vpReplacePoints[i]->Replace(vpLoopMapPoints[i]) for i ascending (:616-625).
+//       The map mutex.  The reference takes mpMap->mMutexMapUpdate per target, after Fuse and around the Replace loop only.
+//       Run takes the lock as a functor: lock() is called once per target, right before step 3, and what it returns lives
+//       until that target's Replace loop has ended.  The default functor returns nothing worth holding: a caller that
+//       holds the mutex around the whole call, or has no other thread, passes none.
+//
+//       Which dependencies cross pairs, and how each is resolved:
+//         - Replace ends in ComputeDistinctiveDescriptors() on the SURVIVING point (MapPoint.cc:212), and in step 3 the
+//           survivor is the loop point.  Its descriptor may change, so its device results at LATER targets are stale.  Run
+//           keeps the set of survivors (by pointer).  For a pair whose point is in the set the device's hit, or its absence,
+//           is ignored and that ONE pair is searched again on the host: the projection forms of
+//           ORBmatcherT::projectIntoKeyFrame (cvsem, with :1021's 1.0/z), the level from the same break table the device
+//           uses, pKF->GetFeaturesInArea and :1060-1081 with the point's current GetDescriptor().  Position, normal and
+//           distance bounds do not change inside SearchAndFuse, so every other pair's device result is what the serial loop
+//           computes.
+//         - A point that Replace turns bad: pMPinKF may itself be a loop point, placed there by an earlier AddMapPoint or
+//           Replace.  The isBad() read at replay (step 2) skips it from then on.
+//         - Two loop points choosing the same feature of one target: the second finds the first as pMPinKF and replaces it.
+//           That is GetMapPoint(bestIdx) read at replay, in order; the device is not involved.
+//       Run returns the total of nFused; Stats::rescored counts the pairs searched again on the host.
+//       MapPoint::mfMinDistance / mfMaxDistance are read raw, as SearchInNeighborsT does.  predict: the
+//       tree's own PredictScale as (ratio, logScaleFactor) -> level where its log resolves to the double overload; null: the
+//       float form.  Monocular only.  Every call runs on the calling thread's matcher handle (orbm_thread_handle).
+#pragma once
+
+#include <algorithm>
+#include <map>
+#include <set>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "ORBmatcher_hip.hpp"
+#include "orbslamm_dropin.hpp"
+#include "orbslamm_hip.h"
+
+namespace iORB_SLAM {
+
+struct SearchAndFuseNoLock { int operator()() const { return 0; } };
+
+template <class KeyFrame, class MapPoint, class Mat>
+class SearchAndFuseT {
+public:
+    static const int TH_LOW = 50;
+    struct Stats { int targets = 0, distinctTargets = 0, points = 0, hits = 0, fused = 0, replaced = 0, added = 0; long pairs = 0, rescored = 0; };
+    // rescoreStale = false leaves the host re-score of survivors out: WRONG, and there for the test that shows it
+    struct Options { int device = 0; orbl_predict_fn predict = nullptr; bool rescoreStale = true; };
+
+    static int Run(const std::vector<std::pair<KeyFrame*, Mat> >& corrected, const std::vector<MapPoint*>& vpLoopMapPoints, float th,
+                   Stats* stats = nullptr, const Options& opt = Options())
+    {
+        return Run(corrected, vpLoopMapPoints, th, SearchAndFuseNoLock(), stats, opt);
+    }
+
+    template <class Lock>
+    static int Run(const std::vector<std::pair<KeyFrame*, Mat> >& corrected, const std::vector<MapPoint*>& vpLoopMapPoints, float th, Lock lock,
+                   Stats* stats = nullptr, const Options& opt = Options())
+    {
+        Stats st;
+        const int T = (int)corrected.size(), P = (int)vpLoopMapPoints.size();
+        st.targets = T; st.points = P; st.pairs = (long)T * P;
+        if (!T || !P) { if (stats) *stats = st; return 0; }
+        KeyFrame* pFirst = corrected[0].first;
+        const int nlevels = (int)pFirst->mvScaleFactors.size();
+        std::vector<float> breaks((size_t)nlevels + 1);
+        check(orbl_level_breaks(pFirst->mfLogScaleFactor, nlevels, opt.predict, breaks.data()));
+
+        // the targets: the decomposed Scw, the keyframe's intrinsics, bounds and grid; every distinct keyframe flattened once
+        std::vector<OrblFuseTarget> rec((size_t)T);
+        std::map<KeyFrame*, int> flatOf;
+        std::vector<Flat> flat;
+        flat.reserve((size_t)T);
+        std::vector<const OrbxKeyPoint*> keys((size_t)T);
+        std::vector<const uint8_t*> desc((size_t)T);
+        std::vector<int32_t> n((size_t)T);
+        for (int t = 0; t < T; t++) {
+            KeyFrame* k = corrected[t].first;
+            OrblFuseTarget& r = rec[t];
+            cvsem::Mat33 Rcw; cvsem::Vec3 tcw, Ow;
+            cvsem::decomposeSim3(corrected[t].second, Rcw, tcw, Ow);
+            for (int a = 0; a < 3; a++) {
+                for (int c = 0; c < 3; c++) r.Rcw[3 * a + c] = Rcw(a, c);
+                r.tcw[a] = tcw[a]; r.Ow[a] = Ow[a];
+            }
+            r.K[0] = k->fx; r.K[1] = k->fy; r.K[2] = k->cx; r.K[3] = k->cy;
+            r.min_x = (float)k->mnMinX; r.max_x = (float)k->mnMaxX; r.min_y = (float)k->mnMinY; r.max_y = (float)k->mnMaxY;
+            r.grid.minX = (float)k->mnMinX; r.grid.minY = (float)k->mnMinY;
+            r.grid.invW = k->mfGridElementWidthInv; r.grid.invH = k->mfGridElementHeightInv;
+            r.grid.cols = k->mnGridCols; r.grid.rows = k->mnGridRows;
+            if (!flatOf.count(k)) {
+                flatOf[k] = (int)flat.size();
+                flat.push_back(Flat());
+                Flat& f = flat.back();
+                f.keys.resize((size_t)k->N); f.desc.resize((size_t)k->N * 32);
+                for (int i = 0; i < k->N; i++) {
+                    const auto& kp = k->mvKeysUn[i];
+                    OrbxKeyPoint& o = f.keys[i];
+                    o.x = kp.pt.x; o.y = kp.pt.y; o.size = kp.size; o.angle = kp.angle; o.response = kp.response; o.octave = kp.octave; o.class_id = kp.class_id;
+                    const unsigned char* d = k->mDescriptors.template ptr<unsigned char>(i);
+                    for (int b = 0; b < 32; b++) f.desc[(size_t)i * 32 + b] = d[b];
+                }
+            }
+            const Flat& f = flat[flatOf[k]];   // (flat was reserved: the addresses stay)
+            keys[t] = f.keys.data(); desc[t] = f.desc.data(); n[t] = k->N;
+        }
+        st.distinctTargets = (int)flat.size();
+        std::vector<OrblFusePoint> pool((size_t)P);
+        for (int i = 0; i < P; i++) pool[i] = point(vpLoopMapPoints[i]);
+
+        // ONE device call; the hit list is small against T x P, its size unknown: a first guess, then the count the library names
+        orbm_t* h = nullptr;
+        check(orbm_thread_handle(opt.device, &h));
+        std::vector<OrbcHit> hits((size_t)std::max(4 * P, 4096));
+        std::vector<int32_t> hitStart((size_t)T + 1);
+        int nHits = 0;
+        for (int attempt = 0;; attempt++) {
+            const int rc = orbc_search_and_fuse(h, rec.data(), keys.data(), desc.data(), n.data(), T, pool.data(), P, th, TH_LOW,
+                                                pFirst->mvScaleFactors.data(), nlevels, breaks.data(), hits.data(), (int)hits.size(), &nHits,
+                                                hitStart.data(), nullptr);
+            if (rc == ORBX_E_CAPACITY && attempt == 0) { hits.resize((size_t)nHits); continue; }
+            check(rc);
+            break;
+        }
+        st.hits = nHits;
+
+        // the serial part, in the reference's order
+        std::set<MapPoint*> survivors;
+        int total = 0;
+        for (int t = 0; t < T; t++) {
+            KeyFrame* pKF = corrected[t].first;
+            std::vector<MapPoint*> vpReplacePoints((size_t)P, static_cast<MapPoint*>(nullptr));
+            const std::set<MapPoint*> spAlreadyFound = pKF->GetMapPoints();   // :995
+            int cur = hitStart[t];
+            const int end = hitStart[t + 1];
+            int nFused = 0;
+            for (int iMP = 0; iMP < P; iMP++) {
+                MapPoint* pMP = vpLoopMapPoints[iMP];
+                while (cur < end && hits[cur].point < iMP) cur++;
+                if (pMP->isBad() || spAlreadyFound.count(pMP)) continue;   // :1007
+                int bestIdx = -1;
+                if (opt.rescoreStale && survivors.count(pMP)) {
+                    st.rescored++;
+                    bestIdx = searchOnHost(pKF, rec[t], pMP, th, breaks);
+                } else if (cur < end && hits[cur].point == iMP) bestIdx = hits[cur].best_idx;
+                if (bestIdx < 0) continue;
+                MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);   // :1084-1097
+                if (pMPinKF) {
+                    if (!pMPinKF->isBad()) vpReplacePoints[iMP] = pMPinKF;
+                } else {
+                    pMP->AddObservation(pKF, bestIdx);
+                    pKF->AddMapPoint(pMP, bestIdx);
+                    st.added++;
+                }
+                nFused++;
+            }
+            total += nFused;
+            {
+                auto guard = lock();   // Get Map Mutex (LoopClosing.cc:616)
+                (void)guard;
+                for (int i = 0; i < P; i++) {
+                    MapPoint* pRep = vpReplacePoints[i];
+                    if (pRep) {
+                        pRep->Replace(vpLoopMapPoints[i]);
+                        survivors.insert(vpLoopMapPoints[i]);
+                        st.replaced++;
+                    }
+                }
+            }
+        }
+        st.fused = total;
+        if (stats) *stats = st;
+        return total;
+    }
+
+private:
+    struct Flat { std::vector<OrbxKeyPoint> keys; std::vector<uint8_t> desc; };
+
+    static OrblFusePoint point(MapPoint* pMP)
+    {
+        OrblFusePoint p;
+        const Mat X = pMP->GetWorldPos(), nrm = pMP->GetNormal(), d = pMP->GetDescriptor();
+        for (int r = 0; r < 3; r++) { p.pos[r] = X.template at<float>(r, 0); p.normal[r] = nrm.template at<float>(r, 0); }
+        p.min_distance = pMP->mfMinDistance; p.max_distance = pMP->mfMaxDistance;
+        const unsigned char* b = d.template ptr<unsigned char>(0);
+        for (int i = 0; i < 32; i++) p.desc[i] = b[i];
+        return p;
+    }
+
+    // ORBmatcher.cc:1010-1081 for ONE pair with the descriptor the point holds now; the best feature when bestDist <= TH_LOW, else -1
+    static int searchOnHost(KeyFrame* pKF, const OrblFuseTarget& T, MapPoint* pMP, float th, const std::vector<float>& breaks)
+    {
+        using namespace cvsem;
+        Mat33 Rcw; Vec3 tcw, Ow;
+        for (int i = 0; i < 9; i++) Rcw.m[i] = T.Rcw[i];
+        for (int i = 0; i < 3; i++) { tcw.v[i] = T.tcw[i]; Ow.v[i] = T.Ow[i]; }
+        const Vec3 p3Dw = col3(pMP->GetWorldPos());
+        const Vec3 p3Dc = mulAdd(Rcw, p3Dw, tcw);
+        if (p3Dc[2] < 0.0f) return -1;
+        const float invz = (float)(1.0 / (double)p3Dc[2]);
+        const float x = p3Dc[0] * invz, y = p3Dc[1] * invz;
+        const float u = T.K[0] * x + T.K[2], v = T.K[1] * y + T.K[3];
+        if (!(u >= T.min_x && u < T.max_x && v >= T.min_y && v < T.max_y)) return -1;
+        const float maxDistance = 1.2f * pMP->mfMaxDistance, minDistance = 0.8f * pMP->mfMinDistance;
+        const Vec3 PO = sub(p3Dw, Ow);
+        const float dist3D = (float)norm(PO);
+        if (dist3D < minDistance || dist3D > maxDistance) return -1;
+        if (dot(PO, col3(pMP->GetNormal())) < 0.5 * dist3D) return -1;
+        const float ratio = pMP->mfMaxDistance / dist3D;
+        int c = 0;
+        for (size_t j = 0; j < breaks.size(); j++) c += ratio > breaks[j] ? 1 : 0;
+        const int nlevels = (int)breaks.size() - 1;
+        if (c < 1 || c > nlevels) return -1;
+        const int nPredictedLevel = c - 1;
+        const float radius = th * pKF->mvScaleFactors[nPredictedLevel];
+        const std::vector<size_t> vIndices = pKF->GetFeaturesInArea(u, v, radius);
+        if (vIndices.empty()) return -1;
+        const Mat dMP = pMP->GetDescriptor();
+        const unsigned char* a = dMP.template ptr<unsigned char>(0);
+        int bestDist = 256, bestIdx = -1;
+        for (size_t k = 0; k < vIndices.size(); k++) {
+            const size_t idx = vIndices[k];
+            const int kpLevel = pKF->mvKeysUn[idx].octave;
+            if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) continue;
+            const unsigned char* b = pKF->mDescriptors.template ptr<unsigned char>((int)idx);
+            int dist = 0;
+            for (int w = 0; w < 32; w++) dist += __builtin_popcount((unsigned)(a[w] ^ b[w]));
+            if (dist < bestDist) { bestDist = dist; bestIdx = (int)idx; }
+        }
+        return bestDist <= TH_LOW ? bestIdx : -1;
+    }
+
+    static void check(int rc) { detail::check(rc, "orbslamm_hip: "); }
+};
+
+}  // namespace iORB_SLAM

@@ -961,4 +961,8 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 /* LocalMapping::SearchInNeighbors: the batched Fuse (orbl_level_breaks, orbl_fuse_batch, orbl_fuse_batch_frames) is the same
  * library's and is declared in orbslamm_fuse.h, which rides along with this header. */
 #include "orbslamm_fuse.h"
+
+/* LoopClosing::SearchAndFuse and MultiMapper::SearchAndFuse: the dense Sim3 Fuse over all corrected keyframes is the same
+ * library's and is declared in orbslamm_loopfuse.h. */
+#include "orbslamm_loopfuse.h"
 #endif

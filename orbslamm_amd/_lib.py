@@ -113,11 +113,16 @@ EXPORTS_FUSE = [
     "orbl_level_breaks", "orbl_fuse_batch", "orbl_fuse_batch_frames",
 ]
 
+# SearchAndFuse's block (include/orbslamm_loopfuse.h, which include/orbslamm_hip.h includes)
+EXPORTS_LOOPFUSE = [
+    "orbc_search_and_fuse", "orbc_search_and_fuse_frames",
+]
+
 
 def build(force=False):
     """hipcc the extension in-tree for gfx950 (cross-compiles without a GPU)."""
     deps = [os.path.join(_PKG, "csrc", f) for f in os.listdir(os.path.join(_PKG, "csrc"))]
-    deps += [os.path.join(_ROOT, "include", f) for f in ("orbslamm_hip.h", "orbslamm_fuse.h")]
+    deps += [os.path.join(_ROOT, "include", f) for f in ("orbslamm_hip.h", "orbslamm_fuse.h", "orbslamm_loopfuse.h")]
     if not force and os.path.exists(SO_PATH) and all(os.path.getmtime(SO_PATH) >= os.path.getmtime(d) for d in deps):
         return SO_PATH
     cmd = ["hipcc"] + HIPCC_FLAGS + ["-o", SO_PATH, SRC]
@@ -163,7 +168,7 @@ def lib():
         L = C.CDLL(os.environ.get("ORBSLAMM_HIP_LIB") or SO_PATH)
         L.orbx_last_error.restype = C.c_char_p
         L.orbx_scale_factor.restype = C.c_float
-        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP + EXPORTS_LOCALMAP + EXPORTS_FUSE:
+        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP + EXPORTS_LOCALMAP + EXPORTS_FUSE + EXPORTS_LOOPFUSE:
             getattr(L, name)
         L.orbx_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _lib = L

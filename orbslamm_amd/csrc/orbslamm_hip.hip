@@ -24,6 +24,7 @@
 #include <deque>
 #include <functional>
 #include <initializer_list>
+#include <map>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -46,6 +47,7 @@
 #include "orbs_kernels.hip"
 #include "orbp_kernels.hip"
 #include "orbl_kernels.hip"
+#include "orbc_kernels.hip"
 
 using namespace orbx;
 
@@ -192,3 +194,4 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbs_host.inc"   // Sim3Solver
 #include "orbp_host.inc"   // PnPsolver
 #include "orbl_host.inc"   // CreateNewMapPoints
+#include "orbc_host.inc"   // SearchAndFuse
