@@ -118,10 +118,9 @@ public:
     }
 
 private:
-    struct Side {
+    struct Side : detail::FlatFeatures {   // (keys, desc)
         int n = 0;
-        std::vector<OrbxKeyPoint> keys;
-        std::vector<uint8_t> desc, skip;
+        std::vector<uint8_t> skip;
         std::vector<uint32_t> node;
         std::vector<int32_t> start, idx;
         OrblKeyFrame kf;
@@ -131,29 +130,16 @@ private:
     static void flatten(KeyFrame* pKF, Side& s)
     {
         s.n = pKF->N;
-        s.keys.resize((size_t)s.n); s.desc.resize((size_t)s.n * 32); s.skip.resize((size_t)s.n);
-        for (int i = 0; i < s.n; i++) {
-            const auto& kp = pKF->mvKeysUn[i];
-            OrbxKeyPoint& o = s.keys[i];
-            o.x = kp.pt.x; o.y = kp.pt.y; o.size = kp.size; o.angle = kp.angle; o.response = kp.response; o.octave = kp.octave; o.class_id = kp.class_id;
-            const unsigned char* d = pKF->mDescriptors.template ptr<unsigned char>(i);
-            for (int b = 0; b < 32; b++) s.desc[(size_t)i * 32 + b] = d[b];
-            s.skip[i] = pKF->GetMapPoint(i) ? 1 : 0;
-        }
+        detail::flatten_features(pKF, s);
+        s.skip.resize((size_t)s.n);
+        for (int i = 0; i < s.n; i++) s.skip[i] = pKF->GetMapPoint(i) ? 1 : 0;
         s.start.assign(1, 0);
         for (auto it = pKF->mFeatVec.begin(); it != pKF->mFeatVec.end(); ++it) {
             s.node.push_back(it->first);
             for (size_t j = 0; j < it->second.size(); j++) s.idx.push_back((int32_t)it->second[j]);
             s.start.push_back((int32_t)s.idx.size());
         }
-        const auto R = pKF->GetRotation();
-        const auto t = pKF->GetTranslation();
-        const auto O = pKF->GetCameraCenter();
-        for (int r = 0; r < 3; r++) {
-            for (int c = 0; c < 3; c++) s.kf.Rcw[3 * r + c] = R.template at<float>(r, c);
-            s.kf.tcw[r] = t.template at<float>(r, 0);
-            s.kf.Ow[r] = O.template at<float>(r, 0);
-        }
+        detail::keyframe_pose(pKF, s.kf.Rcw, s.kf.tcw, s.kf.Ow);
         s.kf.K[0] = pKF->fx; s.kf.K[1] = pKF->fy; s.kf.K[2] = pKF->cx; s.kf.K[3] = pKF->cy;
         s.kf.median_depth = 0.f;
     }
@@ -205,7 +191,7 @@ public:
             std::vector<OrblFusePoint> pool;
             std::vector<int> poolOf(vpMapPointMatches.size(), -1);
             for (size_t i = 0; i < vpMapPointMatches.size(); i++)
-                if (vpMapPointMatches[i]) { poolOf[i] = (int)pool.size(); pool.push_back(point(vpMapPointMatches[i])); }
+                if (vpMapPointMatches[i]) { poolOf[i] = (int)pool.size(); pool.push_back(detail::fuse_point<Mat>(vpMapPointMatches[i])); }
             std::vector<OrblFuseResult> res;
             search(h, pKF, distinct, pool, th, breaks, res);
             st.pairs1 = (int)res.size();
@@ -229,7 +215,7 @@ public:
             }
             std::vector<OrblFusePoint> pool(vpFuseCandidates.size());
             std::vector<int> poolOf(vpFuseCandidates.size());
-            for (size_t i = 0; i < vpFuseCandidates.size(); i++) { pool[i] = point(vpFuseCandidates[i]); poolOf[i] = (int)i; }
+            for (size_t i = 0; i < vpFuseCandidates.size(); i++) { pool[i] = detail::fuse_point<Mat>(vpFuseCandidates[i]); poolOf[i] = (int)i; }
             std::vector<OrblFuseResult> res;
             search(h, pKF, std::vector<KeyFrame*>(1, pKF), pool, th, breaks, res);
             st.pairs2 = (int)res.size();
@@ -249,19 +235,6 @@ public:
     }
 
 private:
-    static OrblFusePoint point(MapPoint* pMP)
-    {
-        OrblFusePoint p;
-        const Mat X = pMP->GetWorldPos(), n = pMP->GetNormal(), d = pMP->GetDescriptor();
-        for (int r = 0; r < 3; r++) { p.pos[r] = X.template at<float>(r, 0); p.normal[r] = n.template at<float>(r, 0); }
-        p.min_distance = pMP->mfMinDistance; p.max_distance = pMP->mfMaxDistance;
-        const unsigned char* b = d.template ptr<unsigned char>(0);
-        for (int i = 0; i < 32; i++) p.desc[i] = b[i];
-        return p;
-    }
-
-    struct Flat { std::vector<OrbxKeyPoint> keys; std::vector<uint8_t> desc; };
-
     // every pool point against every target, one call: res[t * pool.size() + i]
     static void search(orbm_t* h, KeyFrame* pCur, const std::vector<KeyFrame*>& targets, const std::vector<OrblFusePoint>& pool, float th,
                        const std::vector<float>& breaks, std::vector<OrblFuseResult>& res)
@@ -271,34 +244,17 @@ private:
         if (!T || !P) return;
         if (T > ORBL_FUSE_MAX_TARGETS) throw std::runtime_error("SearchInNeighbors: more targets than ORBL_FUSE_MAX_TARGETS");
         std::vector<OrblFuseTarget> rec((size_t)T);
-        std::vector<Flat> flat((size_t)T);
+        std::vector<detail::FlatFeatures> flat((size_t)T);
         std::vector<const OrbxKeyPoint*> keys((size_t)T);
         std::vector<const uint8_t*> desc((size_t)T);
         std::vector<int32_t> n((size_t)T), jobStart((size_t)T + 1), jobPoint((size_t)T * P);
         for (int t = 0; t < T; t++) {
             KeyFrame* k = targets[t];
-            OrblFuseTarget& r = rec[t];
-            const Mat R = k->GetRotation(), tc = k->GetTranslation(), O = k->GetCameraCenter();
-            for (int a = 0; a < 3; a++) {
-                for (int c = 0; c < 3; c++) r.Rcw[3 * a + c] = R.template at<float>(a, c);
-                r.tcw[a] = tc.template at<float>(a, 0);
-                r.Ow[a] = O.template at<float>(a, 0);
-            }
-            r.K[0] = k->fx; r.K[1] = k->fy; r.K[2] = k->cx; r.K[3] = k->cy;
-            r.min_x = (float)k->mnMinX; r.max_x = (float)k->mnMaxX; r.min_y = (float)k->mnMinY; r.max_y = (float)k->mnMaxY;
-            r.grid.minX = (float)k->mnMinX; r.grid.minY = (float)k->mnMinY;
-            r.grid.invW = k->mfGridElementWidthInv; r.grid.invH = k->mfGridElementHeightInv;
-            r.grid.cols = k->mnGridCols; r.grid.rows = k->mnGridRows;
-            Flat& f = flat[t];
-            f.keys.resize((size_t)k->N); f.desc.resize((size_t)k->N * 32);
-            for (int i = 0; i < k->N; i++) {
-                const auto& kp = k->mvKeysUn[i];
-                OrbxKeyPoint& o = f.keys[i];
-                o.x = kp.pt.x; o.y = kp.pt.y; o.size = kp.size; o.angle = kp.angle; o.response = kp.response; o.octave = kp.octave; o.class_id = kp.class_id;
-                const unsigned char* d = k->mDescriptors.template ptr<unsigned char>(i);
-                for (int b = 0; b < 32; b++) f.desc[(size_t)i * 32 + b] = d[b];
-            }
-            keys[t] = f.keys.data(); desc[t] = f.desc.data(); n[t] = k->N;
+            float Rcw[9], tcw[3], Ow[3];
+            detail::keyframe_pose(k, Rcw, tcw, Ow);
+            detail::fuse_target(k, Rcw, tcw, Ow, rec[t]);
+            detail::flatten_features(k, flat[t]);
+            keys[t] = flat[t].keys.data(); desc[t] = flat[t].desc.data(); n[t] = k->N;
             jobStart[t] = t * P;
             for (int i = 0; i < P; i++) jobPoint[(size_t)t * P + i] = i;
         }
@@ -322,26 +278,7 @@ private:
             if (dirty.count(pMP)) {
                 // :894-951 with the descriptor the point holds NOW; u, v and the level do not depend on it
                 st.dirtyRescored++;
-                const float u = r.u, v = r.v;
-                const int nPredictedLevel = r.level;
-                const float radius = th * pKF->mvScaleFactors[nPredictedLevel];
-                const std::vector<size_t> vIndices = pKF->GetFeaturesInArea(u, v, radius);
-                const Mat dMP = pMP->GetDescriptor();
-                const unsigned char* a = dMP.template ptr<unsigned char>(0);
-                bestDist = 256; bestIdx = -1;
-                for (size_t k = 0; k < vIndices.size(); k++) {
-                    const size_t idx = vIndices[k];
-                    const auto& kp = pKF->mvKeysUn[idx];
-                    const int kpLevel = kp.octave;
-                    if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) continue;
-                    const float ex = u - kp.pt.x, ey = v - kp.pt.y;
-                    const float e2 = ex * ex + ey * ey;
-                    if (e2 * pKF->mvInvLevelSigma2[kpLevel] > 5.99) continue;
-                    const unsigned char* b = pKF->mDescriptors.template ptr<unsigned char>((int)idx);
-                    int dist = 0;
-                    for (int w = 0; w < 32; w++) dist += __builtin_popcount((unsigned)(a[w] ^ b[w]));
-                    if (dist < bestDist) { bestDist = dist; bestIdx = (int)idx; }
-                }
+                detail::fuse_rescore<true, Mat>(pKF, pMP, r.u, r.v, r.level, th, bestDist, bestIdx);
             }
             if (bestDist <= TH_LOW && bestIdx >= 0) {   // :954-973
                 MapPoint* pMPinKF = pKF->GetMapPoint(bestIdx);

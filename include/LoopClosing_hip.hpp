@@ -92,44 +92,27 @@ public:
         // the targets: the decomposed Scw, the keyframe's intrinsics, bounds and grid; every distinct keyframe flattened once
         std::vector<OrblFuseTarget> rec((size_t)T);
         std::map<KeyFrame*, int> flatOf;
-        std::vector<Flat> flat;
+        std::vector<detail::FlatFeatures> flat;
         flat.reserve((size_t)T);
         std::vector<const OrbxKeyPoint*> keys((size_t)T);
         std::vector<const uint8_t*> desc((size_t)T);
         std::vector<int32_t> n((size_t)T);
         for (int t = 0; t < T; t++) {
             KeyFrame* k = corrected[t].first;
-            OrblFuseTarget& r = rec[t];
             cvsem::Mat33 Rcw; cvsem::Vec3 tcw, Ow;
             cvsem::decomposeSim3(corrected[t].second, Rcw, tcw, Ow);
-            for (int a = 0; a < 3; a++) {
-                for (int c = 0; c < 3; c++) r.Rcw[3 * a + c] = Rcw(a, c);
-                r.tcw[a] = tcw[a]; r.Ow[a] = Ow[a];
-            }
-            r.K[0] = k->fx; r.K[1] = k->fy; r.K[2] = k->cx; r.K[3] = k->cy;
-            r.min_x = (float)k->mnMinX; r.max_x = (float)k->mnMaxX; r.min_y = (float)k->mnMinY; r.max_y = (float)k->mnMaxY;
-            r.grid.minX = (float)k->mnMinX; r.grid.minY = (float)k->mnMinY;
-            r.grid.invW = k->mfGridElementWidthInv; r.grid.invH = k->mfGridElementHeightInv;
-            r.grid.cols = k->mnGridCols; r.grid.rows = k->mnGridRows;
+            detail::fuse_target(k, Rcw.m, tcw.v, Ow.v, rec[t]);   // (Mat33::m is row-major)
             if (!flatOf.count(k)) {
                 flatOf[k] = (int)flat.size();
-                flat.push_back(Flat());
-                Flat& f = flat.back();
-                f.keys.resize((size_t)k->N); f.desc.resize((size_t)k->N * 32);
-                for (int i = 0; i < k->N; i++) {
-                    const auto& kp = k->mvKeysUn[i];
-                    OrbxKeyPoint& o = f.keys[i];
-                    o.x = kp.pt.x; o.y = kp.pt.y; o.size = kp.size; o.angle = kp.angle; o.response = kp.response; o.octave = kp.octave; o.class_id = kp.class_id;
-                    const unsigned char* d = k->mDescriptors.template ptr<unsigned char>(i);
-                    for (int b = 0; b < 32; b++) f.desc[(size_t)i * 32 + b] = d[b];
-                }
+                flat.push_back(detail::FlatFeatures());
+                detail::flatten_features(k, flat.back());
             }
-            const Flat& f = flat[flatOf[k]];   // (flat was reserved: the addresses stay)
+            const detail::FlatFeatures& f = flat[flatOf[k]];   // (flat was reserved: the addresses stay)
             keys[t] = f.keys.data(); desc[t] = f.desc.data(); n[t] = k->N;
         }
         st.distinctTargets = (int)flat.size();
         std::vector<OrblFusePoint> pool((size_t)P);
-        for (int i = 0; i < P; i++) pool[i] = point(vpLoopMapPoints[i]);
+        for (int i = 0; i < P; i++) pool[i] = detail::fuse_point<Mat>(vpLoopMapPoints[i]);
 
         // ONE device call; the hit list is small against T x P, its size unknown: a first guess, then the count the library names
         orbm_t* h = nullptr;
@@ -197,19 +180,6 @@ public:
     }
 
 private:
-    struct Flat { std::vector<OrbxKeyPoint> keys; std::vector<uint8_t> desc; };
-
-    static OrblFusePoint point(MapPoint* pMP)
-    {
-        OrblFusePoint p;
-        const Mat X = pMP->GetWorldPos(), nrm = pMP->GetNormal(), d = pMP->GetDescriptor();
-        for (int r = 0; r < 3; r++) { p.pos[r] = X.template at<float>(r, 0); p.normal[r] = nrm.template at<float>(r, 0); }
-        p.min_distance = pMP->mfMinDistance; p.max_distance = pMP->mfMaxDistance;
-        const unsigned char* b = d.template ptr<unsigned char>(0);
-        for (int i = 0; i < 32; i++) p.desc[i] = b[i];
-        return p;
-    }
-
     // ORBmatcher.cc:1010-1081 for ONE pair with the descriptor the point holds now; the best feature when bestDist <= TH_LOW, else -1
     static int searchOnHost(KeyFrame* pKF, const OrblFuseTarget& T, MapPoint* pMP, float th, const std::vector<float>& breaks)
     {
@@ -234,22 +204,8 @@ private:
         for (size_t j = 0; j < breaks.size(); j++) c += ratio > breaks[j] ? 1 : 0;
         const int nlevels = (int)breaks.size() - 1;
         if (c < 1 || c > nlevels) return -1;
-        const int nPredictedLevel = c - 1;
-        const float radius = th * pKF->mvScaleFactors[nPredictedLevel];
-        const std::vector<size_t> vIndices = pKF->GetFeaturesInArea(u, v, radius);
-        if (vIndices.empty()) return -1;
-        const Mat dMP = pMP->GetDescriptor();
-        const unsigned char* a = dMP.template ptr<unsigned char>(0);
-        int bestDist = 256, bestIdx = -1;
-        for (size_t k = 0; k < vIndices.size(); k++) {
-            const size_t idx = vIndices[k];
-            const int kpLevel = pKF->mvKeysUn[idx].octave;
-            if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) continue;
-            const unsigned char* b = pKF->mDescriptors.template ptr<unsigned char>((int)idx);
-            int dist = 0;
-            for (int w = 0; w < 32; w++) dist += __builtin_popcount((unsigned)(a[w] ^ b[w]));
-            if (dist < bestDist) { bestDist = dist; bestIdx = (int)idx; }
-        }
+        int bestDist, bestIdx;
+        detail::fuse_rescore<false, Mat>(pKF, pMP, u, v, c - 1, th, bestDist, bestIdx);
         return bestDist <= TH_LOW ? bestIdx : -1;
     }
 

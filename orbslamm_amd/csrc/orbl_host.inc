@@ -1,7 +1,7 @@
 // orbl_host.inc -- host side of the device CreateNewMapPoints (part of orbslamm_hip.hip; kernels: orbl_kernels.hip,
 // DESIGN.md §8k).  One call = the baseline gate, ComputeF12, the epipole and the lock-step walk over node ids for every
 // neighbour on the host, one packed upload, five launches, one copy down, one synchronise.  Below it: the batched Fuse of
-// SearchInNeighbors (orbl_level_breaks, orbl_fuse_batch*, DESIGN.md §8l).
+// SearchInNeighbors (orbl_level_breaks, orbl_fuse_batch*, DESIGN.md §8l) on the shared staging of orbf_host.inc.
 
 static_assert(sizeof(OrblNewPoint) == sizeof(orbl::Rec) && sizeof(OrblNewPoint) == 44, "OrblNewPoint layout");
 static_assert(sizeof(OrblKeyFrame) == 80, "OrblKeyFrame layout");
@@ -255,11 +255,9 @@ extern "C" int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, co
 }
 
 // ------------------------------------------------------------------ SearchInNeighbors: the batched Fuse (DESIGN.md §8l)
-// One call = the checks, the job list cut into tiles, (host arrays: every target's grid built on the host in
-// AssignFeaturesToGrid's order), one packed upload, one launch, one copy down, one synchronise.
-static_assert(sizeof(OrblFuseTarget) == 116 && sizeof(OrblFusePoint) == 64 && sizeof(OrblFusePoint) == sizeof(orbl::FusePt), "fuse record layouts");
+// One call = the checks, the job list cut into tiles, the staging of orbf_host.inc (host arrays: every distinct target's
+// grid built on the host), one packed upload, one launch, one copy down, one synchronise.
 static_assert(sizeof(OrblFuseResult) == 20 && sizeof(OrblFuseResult) == sizeof(orbl::FuseRes), "OrblFuseResult layout");
-static_assert(orbl::FST_FOUND == ORBL_FUSE_ST_FOUND && orbl::FST_LEVEL_RANGE == ORBL_FUSE_ST_LEVEL_RANGE, "fuse status codes");
 
 static int orbl_predict_float(float ratio, float log_scale_factor) { return (int)std::ceil(std::log(ratio) / log_scale_factor); }
 
@@ -287,9 +285,6 @@ extern "C" int orbl_level_breaks(float log_scale_factor, int nlevels, orbl_predi
     return ORBX_OK;
 }
 
-// one target's arrays as the core takes them: resident in HBM (a frame's), or host arrays that ride in the staging block
-struct OrblFuseSide { bool dev; const void* keys; const uint8_t* desc; const int32_t* cellStart; const int32_t* cellIdx; orbm::GridDev gd; int n; };
-
 static int orbl_fuse_check(orbm_handle* h, const OrblFuseTarget* targets, int n_targets, const OrblFusePoint* points, int n_points,
                            const int32_t* job_start, const int32_t* job_point, const float* scale_factors, const float* inv_level_sigma2,
                            int nlevels, const float* level_breaks, OrblFuseResult* out, int64_t* n_jobs)
@@ -307,8 +302,7 @@ static int orbl_fuse_check(orbm_handle* h, const OrblFuseTarget* targets, int n_
         if (job_start[k + 1] < job_start[k]) return fail(ORBX_E_INVALID, "job_start descends at target %d", k);
     const int64_t J = job_start[n_targets];
     if (J > ORBL_FUSE_MAX_JOBS) return fail(ORBX_E_UNSUPPORTED, "%lld job entries: above %d", (long long)J, ORBL_FUSE_MAX_JOBS);
-    for (int j = 0; j < nlevels; j++)
-        if (!(level_breaks[j] < level_breaks[j + 1])) return fail(ORBX_E_INVALID, "the level-break table does not ascend at %d", j);
+    if ((rc = orbf_check_breaks(level_breaks, nlevels))) return rc;
     if (J == 0) return ORBX_OK;
     if (!job_point || !points || !out) return fail(ORBX_E_INVALID, "bad argument");
     for (int64_t i = 0; i < J; i++)
@@ -317,7 +311,7 @@ static int orbl_fuse_check(orbm_handle* h, const OrblFuseTarget* targets, int n_
     return ORBX_OK;
 }
 
-static int orbl_fuse_core(orbm_handle* h, const OrblFuseTarget* targets, const std::vector<OrblFuseSide>& sides, const OrblFusePoint* points,
+static int orbl_fuse_core(orbm_handle* h, const OrblFuseTarget* targets, const std::vector<OrbfSide>& sides, const OrblFusePoint* points,
                           int n_points, const int32_t* job_start, const int32_t* job_point, int64_t J, float th, const float* scale_factors,
                           const float* inv_level_sigma2, int nlevels, const float* level_breaks, OrblFuseResult* out)
 {
@@ -327,20 +321,11 @@ static int orbl_fuse_core(orbm_handle* h, const OrblFuseTarget* targets, const s
     for (int k = 0; k < T; k++)
         for (int b = job_start[k]; b < job_start[k + 1]; b += orbl::kFuseTile)
             work.push_back({k, b, std::min(orbl::kFuseTile, job_start[k + 1] - b), 0});
-    // the staging block: target records | points | job list | tiles | (host arrays of the targets: keys, descriptors, grid)
+    // the staging block: orbf's head (target records | points | host arrays of the targets) | job list | tiles
     Packer pk;
-    const size_t oTgt = pk.take((size_t)T * sizeof(orbl::FuseTgt)), oPts = pk.take((size_t)n_points * sizeof(orbl::FusePt));
+    OrbfStage st;
+    orbf_stage_take(pk, sides, n_points, st);
     const size_t oJob = pk.take((size_t)J * 4), oWork = pk.take(work.size() * sizeof(orbl::FuseWork));
-    std::vector<size_t> oKeys((size_t)T, 0), oDesc((size_t)T, 0), oCs((size_t)T, 0), oCi((size_t)T, 0);
-    for (int k = 0; k < T; k++) {
-        const OrblFuseSide& S = sides[k];
-        if (S.dev) continue;
-        const size_t ncell = (size_t)S.gd.cols * S.gd.rows;
-        oKeys[k] = pk.take((size_t)std::max(S.n, 1) * sizeof(OrbxKeyPoint));
-        oDesc[k] = pk.take((size_t)std::max(S.n, 1) * 32);
-        oCs[k] = pk.take((ncell + 1) * 4);
-        oCi[k] = pk.take((size_t)std::max(S.n, 1) * 4);
-    }
     const size_t upBytes = pk.off;
     const size_t oOut = pk.take((size_t)J * sizeof(orbl::FuseRes));
     const size_t downBytes = (size_t)J * sizeof(orbl::FuseRes);
@@ -348,46 +333,15 @@ static int orbl_fuse_core(orbm_handle* h, const OrblFuseTarget* targets, const s
     if ((rc = orbm_reserve(h, S_BLOCK, pk.off)) || (rc = orbm_pinned(h, std::max(upBytes, downBytes)))) return rc;
     uint8_t* hs = (uint8_t*)h->h_stage;
     uint8_t* d = (uint8_t*)h->d_buf[S_BLOCK];
-    orbl::FuseTgt* td = (orbl::FuseTgt*)(hs + oTgt);
-    for (int k = 0; k < T; k++) {
-        const OrblFuseSide& S = sides[k];
-        const OrblFuseTarget& R = targets[k];
-        orbl::FuseTgt& D = td[k];
-        memset(&D, 0, sizeof D);
-        memcpy(D.Rcw, R.Rcw, sizeof D.Rcw); memcpy(D.tcw, R.tcw, sizeof D.tcw); memcpy(D.Ow, R.Ow, sizeof D.Ow);
-        D.fx = R.K[0]; D.fy = R.K[1]; D.cx = R.K[2]; D.cy = R.K[3];
-        D.minX = R.min_x; D.maxX = R.max_x; D.minY = R.min_y; D.maxY = R.max_y;
-        D.grid = S.gd; D.n = S.n;
-        if (S.dev) { D.keys = (const orbm::KeyDev*)S.keys; D.desc = S.desc; D.cellStart = S.cellStart; D.cellIdx = S.cellIdx; continue; }
-        // Frame::AssignFeaturesToGrid (Frame.cc:230-245, PosInGrid :382-392): a counting sort that keeps the insertion order
-        const OrbxKeyPoint* kp = (const OrbxKeyPoint*)S.keys;
-        const int ncell = S.gd.cols * S.gd.rows;
-        int32_t* cs = (int32_t*)(hs + oCs[k]);
-        int32_t* ci = (int32_t*)(hs + oCi[k]);
-        std::vector<int32_t> cell((size_t)S.n, -1);
-        memset(cs, 0, ((size_t)ncell + 1) * 4);
-        for (int i = 0; i < S.n; i++) {
-            const float px = roundf((kp[i].x - S.gd.minX) * S.gd.invW), py = roundf((kp[i].y - S.gd.minY) * S.gd.invH);
-            if (!(px >= 0.f && px < (float)S.gd.cols && py >= 0.f && py < (float)S.gd.rows)) continue;
-            cell[i] = (int)px * S.gd.rows + (int)py;
-            cs[cell[i] + 1]++;
-        }
-        for (int c = 0; c < ncell; c++) cs[c + 1] += cs[c];
-        std::vector<int32_t> fill(cs, cs + ncell);
-        for (int i = 0; i < S.n; i++) if (cell[i] >= 0) ci[fill[cell[i]]++] = i;
-        if (S.n) { memcpy(hs + oKeys[k], S.keys, (size_t)S.n * sizeof(OrbxKeyPoint)); memcpy(hs + oDesc[k], S.desc, (size_t)S.n * 32); }
-        D.keys = (const orbm::KeyDev*)(d + oKeys[k]); D.desc = d + oDesc[k];
-        D.cellStart = (const int32_t*)(d + oCs[k]); D.cellIdx = (const int32_t*)(d + oCi[k]);
-    }
-    memcpy(hs + oPts, points, (size_t)n_points * sizeof(orbl::FusePt));
+    orbf_stage_fill(hs, d, st, targets, sides, points, n_points);
     memcpy(hs + oJob, job_point, (size_t)J * 4);
     memcpy(hs + oWork, work.data(), work.size() * sizeof(orbl::FuseWork));
     orbl::FuseArgs a{};
-    a.tgt = (const orbl::FuseTgt*)(d + oTgt); a.pts = (const orbl::FusePt*)(d + oPts); a.jobPoint = (const int32_t*)(d + oJob);
+    a.tgt = (const orbf::FuseTgt*)(d + st.tgt); a.pts = (const orbf::FusePt*)(d + st.pts); a.jobPoint = (const int32_t*)(d + oJob);
     a.work = (const orbl::FuseWork*)(d + oWork); a.out = (orbl::FuseRes*)(d + oOut);
     a.th = th; a.nlevels = nlevels;
-    for (int i = 0; i < 16; i++) { a.sf[i] = i < nlevels ? scale_factors[i] : 0.f; a.invSigma2[i] = i < nlevels ? inv_level_sigma2[i] : 0.f; }
-    for (int i = 0; i < 17; i++) a.breaks[i] = i <= nlevels ? level_breaks[i] : 0.f;
+    orbf_fill_tables(scale_factors, level_breaks, nlevels, a.sf, a.breaks);
+    for (int i = 0; i < 16; i++) a.invSigma2[i] = i < nlevels ? inv_level_sigma2[i] : 0.f;
     hipStream_t s = h->stream;
     HIPCHK(hipMemcpyAsync(d, hs, upBytes, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(orbl::k_fuse_batch, dim3((unsigned)work.size()), dim3(orbl::kFuseThreads), 0, s, a);
@@ -406,18 +360,8 @@ extern "C" int orbl_fuse_batch(orbm_t* h, const OrblFuseTarget* targets, const O
     int64_t J;
     int rc = orbl_fuse_check(h, targets, n_targets, points, n_points, job_start, job_point, scale_factors, inv_level_sigma2, nlevels, level_breaks, out, &J);
     if (rc || n_targets == 0) return rc;
-    if (!keys_un || !desc || !n) return fail(ORBX_E_INVALID, "bad argument");
-    std::vector<OrblFuseSide> sides((size_t)n_targets);
-    for (int k = 0; k < n_targets; k++) {
-        if (n[k] < 0 || (n[k] && (!keys_un[k] || !desc[k]))) return fail(ORBX_E_INVALID, "target %d: bad argument", k);
-        if (n[k] > 65535) return fail(ORBX_E_INVALID, "%d features in target %d: above 65535", n[k], k);
-        const OrbmGrid& g = targets[k].grid;
-        if (g.cols < 1 || g.rows < 1 || g.cols * g.rows > (1 << 20)) return fail(ORBX_E_INVALID, "target %d: bad grid", k);
-        orbm::GridDev gd;
-        gd.minX = g.minX; gd.minY = g.minY; gd.invW = g.invW; gd.invH = g.invH; gd.cols = g.cols; gd.rows = g.rows;
-        sides[k] = {false, keys_un[k], desc[k], nullptr, nullptr, gd, n[k]};
-    }
-    if (J == 0) return ORBX_OK;
+    std::vector<OrbfSide> sides;
+    if ((rc = orbf_sides_host(targets, keys_un, desc, n, n_targets, sides)) || J == 0) return rc;
     return orbl_fuse_core(h, targets, sides, points, n_points, job_start, job_point, J, th, scale_factors, inv_level_sigma2, nlevels, level_breaks, out);
 }
 
@@ -430,13 +374,7 @@ extern "C" int orbl_fuse_batch_frames(orbm_t* h, const OrblFuseTarget* targets, 
     int rc = orbl_fuse_check(h, targets, n_targets, points, n_points, job_start, job_point, scale_factors, inv_level_sigma2, nlevels, level_breaks, out, &J);
     if (rc || n_targets == 0) return rc;
     if (!frames) return fail(ORBX_E_INVALID, "null frame");
-    std::vector<OrblFuseSide> sides((size_t)n_targets);
-    for (int k = 0; k < n_targets; k++) {
-        orbm_frame* f = frames[k];
-        if ((rc = frame_usable(h, f))) return rc;
-        if (f->n > 65535) return fail(ORBX_E_INVALID, "%d features in target %d: above 65535", f->n, k);
-        sides[k] = {true, f->d_keysUn, f->d_desc, f->d_start, f->d_idx, f->gd, f->n};
-    }
-    if (J == 0) return ORBX_OK;
+    std::vector<OrbfSide> sides;
+    if ((rc = orbf_sides_frames(h, frames, n_targets, sides)) || J == 0) return rc;
     return orbl_fuse_core(h, targets, sides, points, n_points, job_start, job_point, J, th, scale_factors, inv_level_sigma2, nlevels, level_breaks, out);
 }

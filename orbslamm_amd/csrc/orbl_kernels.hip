@@ -22,7 +22,8 @@
 //                         written behind the earlier rows' in idx1 order (the reference's order).  Integers, no atomics.
 // Arithmetic: one IEEE operation per source operation (the library is built with -ffp-contract=off); OpenCV's pieces are
 // orbx_cvmath.hpp's.
-// Below them: k_fuse_batch, the searches of LocalMapping::SearchInNeighbors' Fuse calls for all targets in one launch (§8l).
+// Below them: k_fuse_batch, the searches of LocalMapping::SearchInNeighbors' Fuse calls for all targets in one launch (§8l),
+// on the shared Fuse pieces of orbf_kernels.hip (§8n).
 #pragma once
 
 namespace orbl {
@@ -228,22 +229,6 @@ __global__ __launch_bounds__(kRowThreads) void k_newpoints_resolve(Args a)
     }
 }
 
-// the accepted records of the row's columns [base, base + kRowThreads) in front of this thread's, and in all of them
-__device__ __forceinline__ int row_rank(bool flag, int* sWave, int& chunkTotal)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    const int inWave = __popcll(m & ((1ull << lane) - 1ull));
-    __syncthreads();   // (the previous chunk's reads of sWave are done)
-    if (lane == 0) sWave[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kRowThreads / 64; w++) { const int c = sWave[w]; all += c; if (w < wave) before += c; }
-    chunkTotal = all;
-    return before + inWave;
-}
-
 __global__ __launch_bounds__(kRowThreads) void k_newpoints_count(Args a)
 {
     __shared__ int sWave[kRowThreads / 64];
@@ -253,7 +238,8 @@ __global__ __launch_bounds__(kRowThreads) void k_newpoints_count(Args a)
     for (int base = 0; base < a.n1; base += kRowThreads) {
         const int q = base + threadIdx.x;
         int chunk;
-        (void)row_rank(q < a.n1 && st[q] == ST_ACCEPTED, sWave, chunk);
+        __syncthreads();   // (the previous chunk's reads of sWave are done)
+        (void)orbf::block_rank<kRowThreads>(q < a.n1 && st[q] == ST_ACCEPTED, sWave, chunk);
         total += chunk;
     }
     if (threadIdx.x == 0) a.cnt[k] = total;
@@ -270,7 +256,8 @@ __global__ __launch_bounds__(kRowThreads) void k_newpoints_compact(Args a)
         const int q = base + threadIdx.x;
         const bool f = q < a.n1 && st[q] == ST_ACCEPTED;
         int chunk;
-        const int r = row_rank(f, sWave, chunk);
+        __syncthreads();   // (the previous chunk's reads of sWave are done)
+        const int r = orbf::block_rank<kRowThreads>(f, sWave, chunk);
         if (f && pos + r < a.n1) a.out[pos + r] = a.rec[(int64_t)k * a.n1 + q];
         pos += chunk;
     }
@@ -282,12 +269,14 @@ __global__ __launch_bounds__(kRowThreads) void k_newpoints_compact(Args a)
 // (target, point) of a job list, one launch however many targets.  A workgroup takes one tile of kFuseTile consecutive job
 // entries of ONE target (the host cuts the CSR into tiles: FuseWork), so the machine is filled from the job list and not
 // from a target.  Two steps:
-//   1. one lane per entry: :855-892 in orbx_cvmath.hpp's forms, the level from the break table (no device log), the
-//      result of a pair that a gate ended written at once, the survivors compacted by ballot into LDS;
+//   1. one lane per entry: the projection gates (orbf::project_gates), the result of a pair that a gate ended written at
+//      once, the survivors compacted by ballot (orbf::block_rank) into LDS;
 //   2. kFuseLpp lanes per survivor walk its window together in GetFeaturesInArea's order (for_each_in_area): each lane
 //      holds 32 / kFuseLpp bytes of the point's descriptor and reads that share of a candidate's (one 32-byte line per
 //      candidate and group instead of a 32-byte gather per lane), the partial popcounts are summed across the lanes, and
-//      every lane keeps the same (bestDist, bestIdx) under the strict `<` of k_window_best.
+//      every lane keeps the same (bestDist, bestIdx) under the strict `<` of k_window_best.  This is orbf::window_best's
+//      walk plus the chi-square test of :905-917, written out here: as a call of a shared template the kernel took two
+//      more registers and its callers measured slower than the parent's (docs/experiments.md, "One Fuse core").
 // No atomics: a job entry is written by exactly one lane.  kFuseLpp is a build-time choice (-DORBL_FUSE_LPP=1|2|4|8) so that
 // tools/fuse_bench.py can A/B it; 8 measured best, and staging the target's cell-start table in LDS lost at every kFuseLpp
 // (docs/experiments.md, "k_fuse_batch: lanes per point").
@@ -299,19 +288,10 @@ constexpr int kFuseThreads = 256;
 constexpr int kFuseTile = kFuseThreads / kFuseLpp;
 static_assert(kFuseLpp == 1 || kFuseLpp == 2 || kFuseLpp == 4 || kFuseLpp == 8, "lanes per point");
 
-enum : uint8_t { FST_DEPTH = 0, FST_OUTSIDE_IMAGE, FST_DISTANCE, FST_VIEW_ANGLE, FST_LEVEL_RANGE, FST_NO_CANDIDATE, FST_FOUND };
-
-struct FuseTgt {
-    const orbm::KeyDev* keys; const uint8_t* desc; const int32_t* cellStart; const int32_t* cellIdx;
-    orbm::GridDev grid;
-    float Rcw[9], tcw[3], Ow[3], fx, fy, cx, cy, minX, maxX, minY, maxY;
-    int32_t n;
-};
-struct FusePt { float pos[3], normal[3], minDistance, maxDistance; uint32_t desc[8]; };       // OrblFusePoint
 struct FuseRes { int32_t bestIdx, bestDist; float u, v; int8_t level; uint8_t status, pad[2]; };  // OrblFuseResult
 struct FuseWork { int32_t target, begin, count, pad; };
 struct FuseArgs {
-    const FuseTgt* tgt; const FusePt* pts; const int32_t* jobPoint; const FuseWork* work;
+    const orbf::FuseTgt* tgt; const orbf::FusePt* pts; const int32_t* jobPoint; const FuseWork* work;
     FuseRes* out;
     float th; int32_t nlevels;
     float sf[16], invSigma2[16], breaks[17];
@@ -322,70 +302,35 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_batch(FuseArgs a)
     __shared__ float sU[kFuseTile], sV[kFuseTile];
     __shared__ int32_t sEntry[kFuseTile], sPoint[kFuseTile], sLevel[kFuseTile];
     __shared__ int sWave[kFuseThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const FuseWork w = a.work[blockIdx.x];
-    const FuseTgt& T = a.tgt[w.target];
+    const orbf::FuseTgt& T = a.tgt[w.target];
     const orbm::GridDev grid = T.grid;
     // 1. the projection gates (:855-892), one lane per entry
     bool alive = false;
-    FuseRes r;
-    r.bestIdx = -1; r.bestDist = 256; r.u = 0.f; r.v = 0.f; r.level = -1; r.status = FST_DEPTH; r.pad[0] = r.pad[1] = 0;
-    int entry = 0, p = 0;
+    float u = 0.f, v = 0.f;
+    int level = -1, entry = 0, p = 0;
     if (tid < w.count) {   // (w.count <= kFuseTile)
         entry = w.begin + tid;
         p = a.jobPoint[entry];
-        const FusePt& P = a.pts[p];
-        const float X[3] = {P.pos[0], P.pos[1], P.pos[2]};
-        float pc[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) pc[i] = cvm::gemm3_elem(T.Rcw[3 * i], T.Rcw[3 * i + 1], T.Rcw[3 * i + 2], X[0], X[1], X[2], 1.0, T.tcw[i], 1.0);
-        if (!(pc[2] < 0.0f)) {
-            const float invz = __fdiv_rn(1.f, pc[2]);
-            const float x = pc[0] * invz, y = pc[1] * invz;
-            const float u = T.fx * x + T.cx, v = T.fy * y + T.cy;
-            r.u = u; r.v = v;
-            r.status = FST_OUTSIDE_IMAGE;
-            if (u >= T.minX && u < T.maxX && v >= T.minY && v < T.maxY) {
-                const float maxDistance = 1.2f * P.maxDistance, minDistance = 0.8f * P.minDistance;
-                const float PO[3] = {X[0] - T.Ow[0], X[1] - T.Ow[1], X[2] - T.Ow[2]};
-                const float dist3D = (float)cvm::norm3(PO);
-                r.status = FST_DISTANCE;
-                if (!(dist3D < minDistance || dist3D > maxDistance)) {
-                    double dt = 0;
-#pragma unroll
-                    for (int i = 0; i < 3; i++) dt += (double)PO[i] * (double)P.normal[i];
-                    r.status = FST_VIEW_ANGLE;
-                    if (!(dt < 0.5 * (double)dist3D)) {
-                        // PredictScale: the breaks below ratio (a NaN ratio is above none)
-                        const float ratio = __fdiv_rn(P.maxDistance, dist3D);
-                        int c = 0;
-                        for (int j = 0; j <= a.nlevels; j++) c += ratio > a.breaks[j] ? 1 : 0;
-                        r.level = (int8_t)(c - 1);
-                        r.status = FST_LEVEL_RANGE;
-                        alive = c >= 1 && c <= a.nlevels;
-                    }
-                }
-            }
+        uint8_t st;
+        alive = orbf::project_gates(T, a.pts[p], a.nlevels, a.breaks, u, v, level, st);
+        if (!alive) {
+            FuseRes r;
+            r.bestIdx = -1; r.bestDist = 256; r.u = u; r.v = v; r.level = (int8_t)level; r.status = st; r.pad[0] = r.pad[1] = 0;
+            a.out[entry] = r;
         }
-        if (!alive) a.out[entry] = r;
     }
     // the survivors, in entry order
-    const unsigned long long m = __ballot(alive);
-    if (lane == 0) sWave[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, nSurv = 0;
-#pragma unroll
-    for (int k = 0; k < kFuseThreads / 64; k++) { const int c = sWave[k]; nSurv += c; if (k < wave) before += c; }
-    if (alive) {
-        const int s = before + __popcll(m & ((1ull << lane) - 1ull));
-        sU[s] = r.u; sV[s] = r.v; sEntry[s] = entry; sPoint[s] = p; sLevel[s] = r.level;
-    }
+    int nSurv;
+    const int s0 = orbf::block_rank<kFuseThreads>(alive, sWave, nSurv);
+    if (alive) { sU[s0] = u; sV[s0] = v; sEntry[s0] = entry; sPoint[s0] = p; sLevel[s0] = level; }
     __syncthreads();
     // 2. kFuseLpp lanes per survivor: :894-951
     constexpr int W = 8 / kFuseLpp;
     const int sub = tid % kFuseLpp;
     for (int s = tid / kFuseLpp; s < nSurv; s += kFuseThreads / kFuseLpp) {
-        const float u = sU[s], v = sV[s];
+        const float su = sU[s], sv = sV[s];
         const int pred = sLevel[s];
         const float radius = a.th * a.sf[pred];
         uint32_t qw[W];
@@ -393,11 +338,11 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_batch(FuseArgs a)
 #pragma unroll
         for (int i = 0; i < W; i++) qw[i] = qp[i];
         int bestDist = 256, bestIdx = -1;
-        orbm::for_each_in_area(grid, T.keys, T.cellStart, T.cellIdx, u, v, radius, -1, -1, [&](int idx) {
+        orbm::for_each_in_area(grid, T.keys, T.cellStart, T.cellIdx, su, sv, radius, -1, -1, [&](int idx) {
             const orbm::KeyDev& kp = T.keys[idx];
             const int kpLevel = kp.octave;
             if (kpLevel < pred - 1 || kpLevel > pred) return;
-            const float ex = __fsub_rn(u, kp.x), ey = __fsub_rn(v, kp.y);
+            const float ex = __fsub_rn(su, kp.x), ey = __fsub_rn(sv, kp.y);
             const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
             if ((double)__fmul_rn(e2, a.invSigma2[kpLevel]) > 5.99) return;
             const uint32_t* tp = (const uint32_t*)(T.desc + (int64_t)idx * 32) + sub * W;
@@ -411,8 +356,8 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_batch(FuseArgs a)
         });
         if (sub == 0) {
             FuseRes o;
-            o.bestIdx = bestIdx; o.bestDist = bestDist; o.u = u; o.v = v; o.level = (int8_t)pred;
-            o.status = bestIdx >= 0 ? FST_FOUND : FST_NO_CANDIDATE; o.pad[0] = o.pad[1] = 0;
+            o.bestIdx = bestIdx; o.bestDist = bestDist; o.u = su; o.v = sv; o.level = (int8_t)pred;
+            o.status = bestIdx >= 0 ? orbf::FST_FOUND : orbf::FST_NO_CANDIDATE; o.pad[0] = o.pad[1] = 0;
             a.out[sEntry[s]] = o;
         }
     }

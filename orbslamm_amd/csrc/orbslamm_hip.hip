@@ -36,7 +36,7 @@
 
 #include "../../include/orbslamm_hip.h"
 #include "orbx_common.hpp"
-#include "orbx_cvmath.hpp"   // OpenCV 3.0 float arithmetic shared by the solver families (orbi, orbs, orbp, orbl)
+#include "orbx_cvmath.hpp"   // OpenCV 3.0 float arithmetic shared by the solver families (orbi, orbs, orbp, orbl, orbf)
 
 #include "orbx_kernels.hip"
 #include "orbm_kernels.hip"
@@ -46,6 +46,7 @@
 #include "orbi_kernels.hip"
 #include "orbs_kernels.hip"
 #include "orbp_kernels.hip"
+#include "orbf_kernels.hip"   // the Fuse pieces shared by orbl's k_fuse_batch and orbc's k_loopfuse_search
 #include "orbl_kernels.hip"
 #include "orbc_kernels.hip"
 
@@ -193,5 +194,6 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbi_host.inc"   // Initializer
 #include "orbs_host.inc"   // Sim3Solver
 #include "orbp_host.inc"   // PnPsolver
-#include "orbl_host.inc"   // CreateNewMapPoints
+#include "orbf_host.inc"   // the Fuse staging shared by orbl_fuse_batch* and orbc_search_and_fuse*
+#include "orbl_host.inc"   // CreateNewMapPoints, SearchInNeighbors' batched Fuse
 #include "orbc_host.inc"   // SearchAndFuse

@@ -202,6 +202,44 @@ def fuse_points(pos, normal, min_distance, max_distance, desc):
     return pts
 
 
+def _fuse_levels(scale_factors, breaks, inv_level_sigma2=None):
+    """the level tables of both Fuse entries as float32 rows, (sf, breaks, sigma2 or None), their lengths checked"""
+    sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+    br = np.ascontiguousarray(breaks, dtype=np.float32).reshape(-1)
+    sg = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, dtype=np.float32).reshape(-1)
+    if (sg is not None and sf.shape[0] != sg.shape[0]) or br.shape[0] != sf.shape[0] + 1:
+        raise ValueError("%s and the break table disagree in length" % ("scale_factors" if sg is None else "scale_factors, inv_level_sigma2"))
+    return sf, br, sg
+
+
+class _Head(tuple):
+    """the leading ctypes arguments of a Fuse entry, from the handle to the target count.  `keep` holds the arrays those
+    pointers point into: they live exactly as long as the head does"""
+    keep = ()
+
+
+def _fuse_targets(matcher, targets):
+    """what both Fuse entries take of fuse_target(...) dicts: (frames, head).  frames: the targets are device-resident frames
+    (mixing them with host arrays raises); head: the leading arguments of the frames or the host-array entry (a _Head)"""
+    T = len(targets)
+    recs = np.zeros(max(T, 1), dtype=FUSE_TARGET_DTYPE)
+    for k, t in enumerate(targets):
+        recs[k] = t["rec"]
+    frames = T > 0 and "frame" in targets[0]
+    if any(("frame" in t) != frames for t in targets):
+        raise ValueError("device-resident frames and host arrays cannot be mixed in one call")
+    if frames:
+        fr = (C.c_void_p * max(T, 1))(*[t["frame"].value if isinstance(t["frame"], C.c_void_p) else t["frame"] for t in targets])
+        head = _Head((matcher._h, ptr(recs), fr, T))
+        head.keep = (recs, fr)
+    else:
+        n = np.array([t["keys"].shape[0] for t in targets] or [0], dtype=np.int32)
+        keys, desc = [t["keys"] for t in targets], [t["desc"] for t in targets]
+        head = _Head((matcher._h, ptr(recs), _ptr_array(keys), _ptr_array(desc), ptr(n), T))
+        head.keep = (recs, n, keys, desc)
+    return frames, head
+
+
 def fuse_batch(matcher, targets, points, jobs, scale_factors, inv_level_sigma2, breaks, th=3.0):
     """The searches of Fuse(pKF, vpMapPoints, th) for every target in one call.  targets: fuse_target(...) dicts, all with host
     arrays or all with frames; points: a FUSE_POINT_DTYPE pool; jobs: (job_start, job_point), CSR over the targets.  Returns
@@ -209,9 +247,6 @@ def fuse_batch(matcher, targets, points, jobs, scale_factors, inv_level_sigma2, 
     L = lib()
     _setup(L)
     T = len(targets)
-    recs = np.zeros(max(T, 1), dtype=FUSE_TARGET_DTYPE)
-    for k, t in enumerate(targets):
-        recs[k] = t["rec"]
     pts = np.ascontiguousarray(points, dtype=FUSE_POINT_DTYPE)
     js = np.ascontiguousarray(jobs[0], dtype=np.int32).reshape(-1)
     jp = np.ascontiguousarray(jobs[1], dtype=np.int32).reshape(-1)
@@ -219,23 +254,10 @@ def fuse_batch(matcher, targets, points, jobs, scale_factors, inv_level_sigma2, 
         raise ValueError("job_start has %d entries for %d targets" % (js.shape[0], T))
     if T and jp.shape[0] < js[-1]:
         raise ValueError("job_point is shorter than job_start says")
-    sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
-    sg = np.ascontiguousarray(inv_level_sigma2, dtype=np.float32).reshape(-1)
-    br = np.ascontiguousarray(breaks, dtype=np.float32).reshape(-1)
-    if sf.shape[0] != sg.shape[0] or br.shape[0] != sf.shape[0] + 1:
-        raise ValueError("scale_factors, inv_level_sigma2 and the break table disagree in length")
+    sf, br, sg = _fuse_levels(scale_factors, breaks, inv_level_sigma2)
     J = int(js[-1]) if T else 0
     out = np.zeros(max(J, 0), dtype=FUSE_RESULT_DTYPE)
-    frames = T > 0 and "frame" in targets[0]
-    if any(("frame" in t) != frames for t in targets):
-        raise ValueError("device-resident frames and host arrays cannot be mixed in one call")
-    if frames:
-        fr = (C.c_void_p * max(T, 1))(*[t["frame"].value if isinstance(t["frame"], C.c_void_p) else t["frame"] for t in targets])
-        rc = L.orbl_fuse_batch_frames(matcher._h, ptr(recs), fr, T, ptr(pts), pts.shape[0], ptr(js), ptr(jp), C.c_float(th), ptr(sf), ptr(sg),
-                                      sf.shape[0], ptr(br), ptr(out))
-    else:
-        n = np.array([t["keys"].shape[0] for t in targets] or [0], dtype=np.int32)
-        rc = L.orbl_fuse_batch(matcher._h, ptr(recs), _ptr_array([t["keys"] for t in targets]), _ptr_array([t["desc"] for t in targets]), ptr(n),
-                               T, ptr(pts), pts.shape[0], ptr(js), ptr(jp), C.c_float(th), ptr(sf), ptr(sg), sf.shape[0], ptr(br), ptr(out))
-    check(rc)
+    frames, head = _fuse_targets(matcher, targets)
+    fn = L.orbl_fuse_batch_frames if frames else L.orbl_fuse_batch
+    check(fn(*head, ptr(pts), pts.shape[0], ptr(js), ptr(jp), C.c_float(th), ptr(sf), ptr(sg), sf.shape[0], ptr(br), ptr(out)))
     return out

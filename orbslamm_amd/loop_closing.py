@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import ORBX_E_CAPACITY, OrbError, check, lib, ptr
-from .local_mapping import FUSE_POINT_DTYPE, FUSE_TARGET_DTYPE, _ptr_array
+from .local_mapping import FUSE_POINT_DTYPE, _fuse_levels, _fuse_targets
 
 MAX_TARGETS = 8192
 MAX_PAIRS = 1 << 26
@@ -56,28 +56,13 @@ def search_and_fuse(matcher, targets, points, scale_factors, breaks, th=4.0, max
     L = lib()
     _setup(L)
     T = len(targets)
-    recs = np.zeros(max(T, 1), dtype=FUSE_TARGET_DTYPE)
-    for k, t in enumerate(targets):
-        recs[k] = t["rec"]
     pts = np.ascontiguousarray(points, dtype=FUSE_POINT_DTYPE)
     P = pts.shape[0]
-    sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
-    br = np.ascontiguousarray(breaks, dtype=np.float32).reshape(-1)
-    if br.shape[0] != sf.shape[0] + 1:
-        raise ValueError("scale_factors and the break table disagree in length")
-    frames = T > 0 and "frame" in targets[0]
-    if any(("frame" in t) != frames for t in targets):
-        raise ValueError("device-resident frames and host arrays cannot be mixed in one call")
+    sf, br, _ = _fuse_levels(scale_factors, breaks)
+    frames, head = _fuse_targets(matcher, targets)
     hit_start = np.zeros(T + 1, dtype=np.int32)
     status = np.zeros((T, P), dtype=np.uint8) if want_status else None
     n_hits = C.c_int(0)
-    if frames:
-        fr = (C.c_void_p * max(T, 1))(*[t["frame"].value if isinstance(t["frame"], C.c_void_p) else t["frame"] for t in targets])
-        head = (matcher._h, ptr(recs), fr, T)
-    else:
-        n = np.array([t["keys"].shape[0] for t in targets] or [0], dtype=np.int32)
-        keep = ([t["keys"] for t in targets], [t["desc"] for t in targets])
-        head = (matcher._h, ptr(recs), _ptr_array(keep[0]), _ptr_array(keep[1]), ptr(n), T)
     fn = L.orbc_search_and_fuse_frames if frames else L.orbc_search_and_fuse
 
     def call(cap):

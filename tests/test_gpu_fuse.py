@@ -1,7 +1,8 @@
 """The device SearchInNeighbors (orbl_fuse_batch*, k_fuse_batch) against the per-target reference (the restatement's
 projection tools/fuse_ref.hpp, then the oracle's window_best with the chi-square gate: tests/fuse_cases.py) as bits: every
 field of every OrblFuseResult, over the scene families, both entries (host arrays, device-resident frames), 25 targets x
-2000 points, a target above 8192 features, the empty cases and the refusals; against the library's own window_best fed with
+2000 points, a target above 8192 features, the job counts around the tile sizes, repeated host arrays, the empty cases and
+the refusals; against the library's own window_best fed with
 the restatement's projections; and the C++ drop-in on mock keyframes."""
 import ctypes as C
 import os
@@ -119,6 +120,43 @@ def test_target_above_8192_features(matcher, gex, oracle, breaks):
     assert max(len(t["keys"]) for t in case["targets"]) > 8192
     got = both_entries(matcher, gex, oracle, case, breaks, "> 8192 features")
     assert (got["status"] == lm.FUSE_ST_FOUND).sum() >= 4000
+
+
+@pytest.fixture(scope="module")
+def pool():
+    """three targets against 300 points, every point listed for every target: the job lists around the tile sizes are cut from it"""
+    return fc.make_case(5300, targets=(3, 3), points=(300, 300), feats=500, all_points=True)
+
+
+@pytest.mark.parametrize("n", [1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257])
+def test_job_counts_around_the_tile_sizes(matcher, gex, oracle, breaks, pool, n):
+    """one below, at and one above every tile of job entries the kernel can be built with (32, 64, 128, 256: the tile in use is
+    among them); the targets hold n, 1 and n + 1 entries, so a tile's edge also falls between two targets.  The first target
+    takes the head of the pool, the last its tail."""
+    P = len(pool["points"])
+    idx = [np.arange(n), np.arange(1), np.arange(P - (n + 1), P)]
+    case = dict(pool, jobs=(np.cumsum([0] + [len(i) for i in idx]).astype(np.int32), np.concatenate(idx).astype(np.int32)))
+    got = both_entries(matcher, gex, oracle, case, breaks, "%d, 1 and %d job entries" % (n, n + 1))
+    assert len(got) == 2 * n + 2
+    if n >= 31:   # (the walk ran: by the reference on the CPU about 0.9 n of these entries end FOUND; the floor is half of that)
+        assert (got["status"] == lm.FUSE_ST_FOUND).sum() >= n // 2
+
+
+def test_repeated_host_arrays_ride_once(matcher, oracle, breaks, pool):
+    """two targets that name the SAME keys / desc arrays under different poses share one copy and one grid in the staging block;
+    a third that names them under another grid (80 x 60 cells) gets a grid of its own.  Every result equals the call made with
+    separate copies of the arrays, and the reference."""
+    t0, t1 = pool["targets"][0], pool["targets"][1]
+    fine = t0["rec"].copy()
+    fine["grid"] = np.array(fc.grid_tuple(80, 60), dtype=lm.GRID_DTYPE)
+    shared = [t0, dict(t0, rec=t1["rec"]), dict(t0, rec=fine)]
+    assert all(t["keys"] is t0["keys"] and t["desc"] is t0["desc"] for t in shared)
+    apart = [dict(t, keys=t["keys"].copy(), desc=t["desc"].copy()) for t in shared]
+    got = run_host(matcher, dict(pool, targets=shared), breaks)
+    assert_equal(got, run_host(matcher, dict(pool, targets=apart), breaks), "shared arrays against separate copies")
+    assert_equal(got, fc.reference(oracle, dict(pool, targets=shared)), "shared arrays")
+    P = len(pool["points"])
+    assert all((got[k * P:(k + 1) * P]["status"] == lm.FUSE_ST_FOUND).sum() >= 50 for k in (0, 2))
 
 
 def test_equals_window_best_fed_with_the_restatements_projections(matcher, breaks):

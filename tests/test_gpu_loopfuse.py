@@ -182,6 +182,22 @@ def test_200_targets_over_5_frames(matcher, gex, oracle, breaks):
     assert len(start) == 201 and len(hits) >= 2000 and (np.diff(start) > 0).sum() >= 150
 
 
+def test_same_arrays_under_another_grid_do_not_share_a_grid(matcher, oracle, breaks, wide):
+    """two targets that name the SAME keys / desc arrays under different poses ride in the staging block once; a third that
+    names them under another grid (80 x 60 cells) gets a grid of its own: every output equals the call made with separate
+    copies of the arrays, and the reference"""
+    t0, t1 = wide["targets"][0], wide["targets"][1]
+    fine = t0["rec"].copy()
+    fine["grid"] = np.array(fc.grid_tuple(80, 60), dtype=lm.GRID_DTYPE)
+    shared = [t0, lc.with_pose(t0, t1["rec"]["Rcw"], t1["rec"]["tcw"], t1["rec"]["Ow"]), dict(t0, rec=fine)]
+    assert all(t["keys"] is t0["keys"] and t["desc"] is t0["desc"] for t in shared)
+    apart = [dict(t, keys=t["keys"].copy(), desc=t["desc"].copy()) for t in shared]
+    got = run_host(matcher, dict(wide, targets=shared, name=None), breaks)
+    assert_equal(got, run_host(matcher, dict(wide, targets=apart, name=None), breaks), "shared arrays against separate copies")
+    assert_equal(got, lc.reference(oracle, dict(wide, targets=shared, name=None)), "shared arrays")
+    assert (got[2][0] == lm.FUSE_ST_FOUND).sum() >= 100 and (got[2][2] == lm.FUSE_ST_FOUND).sum() >= 100
+
+
 def test_one_target_of_9000_features(matcher, gex, oracle, breaks):
     case = lc.make_dense(8193, name="9000", targets=(1, 1), points=(12000, 12000), feats=9000, vis=1.0, spread=0.0)
     assert len(case["targets"]) == 1 and len(case["targets"][0]["keys"]) >= 9000
