@@ -47,24 +47,22 @@ static int orbc_core(orbm_handle* h, const OrblFuseTarget* targets, const std::v
     orbf_stage_take(pk, sides, P, st);
     const size_t upBytes = pk.off;
     const size_t startBytes = ((size_t)T + 1) * 4;
-    enum { S_BLOCK = 12, S_PAIR = 13, S_TILES = 14, S_HITS = 15, S_STATUS = 16 };
     Packer tl;
     const size_t oCnt = tl.take((size_t)nTiles * 4), oOff = tl.take(((size_t)nTiles + 1) * 4), oStart = tl.take(startBytes);
     const int cap = (int)std::min<int64_t>(capacity, pairs);   // (there are never more hits than pairs)
-    if ((rc = orbm_reserve(h, S_BLOCK, upBytes)) || (rc = orbm_reserve(h, S_PAIR, (size_t)pairs * 4)) || (rc = orbm_reserve(h, S_TILES, tl.off)) ||
-        (rc = orbm_reserve(h, S_HITS, (size_t)std::max(cap, 1) * sizeof(orbc::Hit))) || (status && (rc = orbm_reserve(h, S_STATUS, (size_t)pairs))) ||
-        (rc = orbm_pinned(h, std::max(upBytes, startBytes))))
+    if ((rc = orbm_reserve(h, {{S_BLOCK, upBytes}, {S_LF_PAIR, (size_t)pairs * 4}, {S_LF_TILES, tl.off}, {S_LF_HITS, (size_t)std::max(cap, 1) * sizeof(orbc::Hit)}})) ||
+        (status && (rc = orbm_reserve(h, S_LF_STATUS, (size_t)pairs))) || (rc = orbm_pinned(h, std::max(upBytes, startBytes))))
         return rc;
     uint8_t* hs = (uint8_t*)h->h_stage;
-    uint8_t* d = (uint8_t*)h->d_buf[S_BLOCK];
-    uint8_t* dt = (uint8_t*)h->d_buf[S_TILES];
+    uint8_t* d = slot_ptr<uint8_t>(h, S_BLOCK);
+    uint8_t* dt = slot_ptr<uint8_t>(h, S_LF_TILES);
     orbf_stage_fill(hs, d, st, targets, sides, points, P);
     orbc::Args a{};
     a.tgt = (const orbf::FuseTgt*)(d + st.tgt); a.pts = (const orbf::FusePt*)(d + st.pts);
-    a.pair = (uint32_t*)h->d_buf[S_PAIR];
+    a.pair = slot_ptr<uint32_t>(h, S_LF_PAIR);
     a.tileCnt = (int32_t*)(dt + oCnt); a.tileOff = (const int32_t*)(dt + oOff); a.hitStart = (int32_t*)(dt + oStart);
-    a.hits = (orbc::Hit*)h->d_buf[S_HITS];
-    a.status = status ? (uint8_t*)h->d_buf[S_STATUS] : nullptr;
+    a.hits = slot_ptr<orbc::Hit>(h, S_LF_HITS);
+    a.status = status ? slot_ptr<uint8_t>(h, S_LF_STATUS) : nullptr;
     a.nTargets = T; a.nPoints = P; a.tilesPerTarget = tilesPerTarget; a.nTiles = nTiles; a.capacity = cap; a.maxDist = max_dist; a.nlevels = nlevels;
     a.th = th;
     orbf_fill_tables(scale_factors, level_breaks, nlevels, a.sf, a.breaks);

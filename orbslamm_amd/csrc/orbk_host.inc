@@ -14,12 +14,12 @@ extern "C" int orbv_score(orbv_t* voc, const uint32_t* a_ids, const double* a_va
     std::lock_guard<std::mutex> lk(voc->mu);
     Packer pk;
     const size_t oA = pk.take((size_t)na * 4), oAv = pk.take((size_t)na * 8), oB = pk.take((size_t)nb * 4), oBv = pk.take((size_t)nb * 8), oR = pk.take(8);
-    int rc = orbv_reserve(voc, 6, pk.off);
+    int rc = orbv_reserve(voc, SV_SCORE, pk.off);
     if (rc) return rc;
     std::vector<uint8_t> h(pk.off, 0);
     if (na) { memcpy(&h[oA], a_ids, (size_t)na * 4); memcpy(&h[oAv], a_vals, (size_t)na * 8); }
     if (nb) { memcpy(&h[oB], b_ids, (size_t)nb * 4); memcpy(&h[oBv], b_vals, (size_t)nb * 8); }
-    uint8_t* d = (uint8_t*)voc->d_buf[6];
+    uint8_t* d = slot_ptr<uint8_t>(voc, SV_SCORE);
     HIPCHK(hipMemcpyAsync(d, h.data(), oR, hipMemcpyHostToDevice, voc->stream));
     hipLaunchKernelGGL(orbk::k_kf_score_one, dim3(1), dim3(64), 0, voc->stream, (const uint32_t*)(d + oA), (const double*)(d + oAv), na,
                        (const uint32_t*)(d + oB), (const double*)(d + oBv), nb, (double*)(d + oR));

@@ -126,10 +126,9 @@ static int orbl_core(orbm_handle* h, const OrblSide& A, const OrblKeyFrame* kf1,
     const size_t oM12 = pk.take(cells * 4), oRec = pk.take(cells * sizeof(orbl::Rec)), oCnt = pk.take((size_t)K * 4);
     const size_t oDown = pk.take(16), oOut = pk.take((size_t)n1 * sizeof(orbl::Rec)), oStatus = pk.take(cells);
     const size_t downBytes = (status ? oStatus + ((cells + 15) & ~(size_t)15) : oStatus) - oDown;
-    enum { S_BLOCK = 12 };
     if ((rc = orbm_reserve(h, S_BLOCK, pk.off)) || (rc = orbm_pinned(h, std::max(upBytes, downBytes)))) return rc;
     uint8_t* hs = (uint8_t*)h->h_stage;
-    uint8_t* d = (uint8_t*)h->d_buf[S_BLOCK];
+    uint8_t* d = slot_ptr<uint8_t>(h, S_BLOCK);
     for (int s = 0; s <= K; s++) {
         const OrblSide& S = side(s);
         orbl::KfDev& D = kd[s];
@@ -329,10 +328,9 @@ static int orbl_fuse_core(orbm_handle* h, const OrblFuseTarget* targets, const s
     const size_t upBytes = pk.off;
     const size_t oOut = pk.take((size_t)J * sizeof(orbl::FuseRes));
     const size_t downBytes = (size_t)J * sizeof(orbl::FuseRes);
-    enum { S_BLOCK = 12 };
     if ((rc = orbm_reserve(h, S_BLOCK, pk.off)) || (rc = orbm_pinned(h, std::max(upBytes, downBytes)))) return rc;
     uint8_t* hs = (uint8_t*)h->h_stage;
-    uint8_t* d = (uint8_t*)h->d_buf[S_BLOCK];
+    uint8_t* d = slot_ptr<uint8_t>(h, S_BLOCK);
     orbf_stage_fill(hs, d, st, targets, sides, points, n_points);
     memcpy(hs + oJob, job_point, (size_t)J * 4);
     memcpy(hs + oWork, work.data(), work.size() * sizeof(orbl::FuseWork));

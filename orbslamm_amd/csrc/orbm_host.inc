@@ -68,14 +68,38 @@ extern "C" int orbm_descriptors_from_text(const char* text, uint8_t* desc, int c
 // block) cannot belong to the matcher OBJECT: it belongs to the calling THREAD (orbm_thread_handle), made at the thread's
 // first search and kept until the thread ends.  Constructing and destroying a matcher then touches no HIP API at all.
 // orbm_create / orbm_destroy remain for callers that want a handle of their own (the ctypes mirror, the frame sets).
+//
+// THE list of a handle's device scratch blocks, for every family that runs on one (orbm_*, orbt, orbl_*, orbc_*): one name per role, one entry
+// family (the entries and the core they share) per name, no numbers -- a new block is a new name.  Reached through the helpers below only.
+enum OrbmSlot {
+    S_DM_Q, S_DM_T, S_DM_DIST,                              // orbm_distance_matrix, the one entry
+    S_BF_QD, S_BF_TD, S_BF_QA, S_BF_TA, S_BF_CNT, S_BF_MATCH, S_BF_BIN, S_BF_HIST, S_BF_BEST2, S_BF_XDESC,   // orbm_match_bruteforce (CNT: {nq, nt}; HIST: 32 bins + nmatch)
+    S_FA_OUT, S_FA_CNT,                                     // orbm_features_in_area, on top of the G_ blocks
+    // the grid of a host-array train side: reserved and built by orbm_build_grid, read by its callers (orbm_features_in_area, orbm_window_best,
+    // orbm_search_for_initialization).  G_CNT / G_FILL: frame_build_big's scratch too, which may use them from a frame set's stream (and drains it)
+    G_KEYS, G_CNT, G_START, G_FILL, G_IDX,
+    // a family's entries reserve and fill the blocks before the bar (device-resident frames bring their own), its core the others; the core reads all
+    S_WIN_TD, S_WIN_TUR, /* orbm_window_best | window_core */ S_WIN_UVR, S_WIN_UR, S_WIN_PRED, S_WIN_QD, S_WIN_QV, S_WIN_SIG, S_WIN_BI, S_WIN_BD,
+    S_INI_QD, S_INI_QA, S_INI_QV, S_INI_TD, /* orbm_search_for_initialization (its _frames form: S_INI_QV alone) | init_core */
+    S_INI_UVR, S_INI_LVL, S_INI_CNT, S_INI_OFF, S_INI_KEY, S_INI_CIDX, S_INI_M12, S_INI_M21, S_INI_NM, S_INI_PUSHT, S_INI_PUSHB,
+    S_TRI_K1, S_TRI_D1, S_TRI_K2, S_TRI_D2, S_TRI_ST1, S_TRI_I1, S_TRI_ST2, S_TRI_I2, /* orbm_search_for_triangulation | tri_core */
+    S_TRI_S1, S_TRI_U1, S_TRI_S2, S_TRI_U2, S_TRI_PA, S_TRI_PB, S_TRI_M12, S_TRI_BIN, S_TRI_HIST,
+    S_UND_IN, S_UND_OUT, S_RGBD_KEYS, S_RGBD_KEYSUN, S_RGBD_DEPTH, S_RGBD_OUT, S_DIS_DESC, S_DIS_START, S_DIS_BEST,   // orbm_undistort_keypoints, _compute_stereo_from_rgbd, _distinctive_descriptors
+    S_BLOCK,                                                // THE ONE SHARED NAME: the packed upload of orbl_core, orbl_fuse_core and orbc_core, which never nest
+    S_LF_PAIR, S_LF_TILES, S_LF_HITS, S_LF_STATUS,          // orbc_core besides S_BLOCK
+    T_STAGE, /* device twin of the pinned staging block: bow_core and proj_core (orbt_host.inc) | proj_core, call scratch */ T_OFF, T_CAND, T_QRES, T_TSCR,
+    // PERSISTENT -- these live ACROSS calls and are the projection search's alone.  T_FS / T_PREP: the scratch frame and the upload orbm_projection_prepare
+    // leaves for the next search.  T_STATS: proj_core's candidate counter, zeroed when the block is first made (slot_cap() == 0), left zero by every resolve
+    T_FS, T_PREP, T_STATS,
+    ORBM_SLOT_COUNT
+};
 struct FrameBlock { void* p; size_t bytes; };
 struct orbm_handle {
     int device = -1;
     hipStream_t stream = nullptr;
     int chainIdx = -1;                   // >= 0: `stream` is one of the device's shared chain streams (chain_stream_acquire), not owned
-    // growable scratch
-    void* d_buf[32] = {nullptr};
-    size_t d_cap[32] = {0};
+    void* d_buf[ORBM_SLOT_COUNT] = {nullptr};   // growable scratch, one block per OrbmSlot
+    size_t d_cap[ORBM_SLOT_COUNT] = {0};
     // one packed upload / download per call (orbt_host.inc)
     void* h_stage = nullptr; size_t h_stageCap = 0;   // (+ 64 bytes behind it: the flag of stage_down_wait)
     int32_t stageSeq = 0;
@@ -98,7 +122,13 @@ struct orbm_handle {
 };
 static std::atomic<int64_t> g_orbmHandlesMade{0};
 
-static int orbm_reserve(orbm_handle* h, int slot, size_t bytes) { return grow_device(h->d_buf[slot], h->d_cap[slot], bytes, 4096, nullptr, &h->nDevAlloc); }
+// the only code that indexes d_buf / d_cap: grow a block (or several, in order), its pointer, its capacity, a copy into it on the handle's stream
+static int orbm_reserve(orbm_handle* h, OrbmSlot s, size_t bytes) { return grow_device(h->d_buf[s], h->d_cap[s], bytes, 4096, nullptr, &h->nDevAlloc); }
+struct SlotBytes { OrbmSlot slot; size_t bytes; };
+static int orbm_reserve(orbm_handle* h, std::initializer_list<SlotBytes> blocks) { for (const SlotBytes& b : blocks) if (int rc = orbm_reserve(h, b.slot, b.bytes)) return rc; return ORBX_OK; }
+template <class T = void> static T* slot_ptr(const orbm_handle* h, OrbmSlot s) { return (T*)h->d_buf[s]; }
+static size_t slot_cap(const orbm_handle* h, OrbmSlot s) { return h->d_cap[s]; }
+static int slot_upload(orbm_handle* h, OrbmSlot s, const void* src, size_t bytes) { HIPCHK(hipMemcpyAsync(h->d_buf[s], src, bytes, hipMemcpyHostToDevice, h->stream)); return ORBX_OK; }
 
 // own_stream: a queue of the handle's own (orbm_create); otherwise one of the device's four chain streams, shared with the
 // latency extractors (DESIGN.md section 4: every queue a process owns takes part in the GPU's rotation, busy or not -- a
@@ -303,15 +333,14 @@ extern "C" int orbm_distance_matrix(orbm_t* h, const uint8_t* q, int nq, const u
     if (rc) return rc;
     if (nq < 0 || nt < 0 || (nq && !q) || (nt && !t) || !dist) return fail(ORBX_E_INVALID, "bad argument");
     if (nq == 0 || nt == 0) return ORBX_OK;
-    if ((rc = orbm_reserve(h, 0, (size_t)nq * 32)) || (rc = orbm_reserve(h, 1, (size_t)nt * 32)) ||
-        (rc = orbm_reserve(h, 2, (size_t)nq * nt * 4))) return rc;
+    if ((rc = orbm_reserve(h, {{S_DM_Q, (size_t)nq * 32}, {S_DM_T, (size_t)nt * 32}, {S_DM_DIST, (size_t)nq * nt * 4}}))) return rc;
     hipStream_t s = h->stream;
-    HIPCHK(hipMemcpyAsync(h->d_buf[0], q, (size_t)nq * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->d_buf[1], t, (size_t)nt * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(slot_ptr(h, S_DM_Q), q, (size_t)nq * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(slot_ptr(h, S_DM_T), t, (size_t)nt * 32, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(orbm::k_distance_matrix, dim3((nq + 255) / 256, std::min(nt, 64)), dim3(256), 0, s,
-                       (const uint8_t*)h->d_buf[0], nq, (const uint8_t*)h->d_buf[1], nt, (int32_t*)h->d_buf[2]);
+                       slot_ptr<const uint8_t>(h, S_DM_Q), nq, slot_ptr<const uint8_t>(h, S_DM_T), nt, slot_ptr<int32_t>(h, S_DM_DIST));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dist, h->d_buf[2], (size_t)nq * nt * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(dist, slot_ptr(h, S_DM_DIST), (size_t)nq * nt * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return ORBX_OK;
 }
@@ -325,47 +354,44 @@ extern "C" int orbm_match_bruteforce(orbm_t* h, const uint8_t* qdesc, const floa
     if (nq < 0 || nt < 0 || (nq && (!qdesc || !qangle || !match)) || (nt && (!tdesc || !tangle))) return fail(ORBX_E_INVALID, "bad argument");
     if (nmatches) *nmatches = 0;
     if (nq == 0) return ORBX_OK;
-    // slots: 0 qdesc, 1 tdesc, 2 qangle, 3 tangle, 4 counts(2), 5 match, 6 binOf, 7 hist(32)+nmatch
-    if ((rc = orbm_reserve(h, 0, (size_t)nq * 32)) || (rc = orbm_reserve(h, 1, (size_t)std::max(nt, 1) * 32)) ||
-        (rc = orbm_reserve(h, 2, (size_t)nq * 4)) || (rc = orbm_reserve(h, 3, (size_t)std::max(nt, 1) * 4)) ||
-        (rc = orbm_reserve(h, 4, 16)) || (rc = orbm_reserve(h, 5, (size_t)nq * 4)) || (rc = orbm_reserve(h, 6, (size_t)nq)) ||
-        (rc = orbm_reserve(h, 7, 34 * 4))) return rc;
+    if ((rc = orbm_reserve(h, {{S_BF_QD, (size_t)nq * 32}, {S_BF_TD, (size_t)std::max(nt, 1) * 32}, {S_BF_QA, (size_t)nq * 4}, {S_BF_TA, (size_t)std::max(nt, 1) * 4},
+                               {S_BF_CNT, 16}, {S_BF_MATCH, (size_t)nq * 4}, {S_BF_BIN, (size_t)nq}, {S_BF_HIST, 34 * 4}}))) return rc;
     hipStream_t s = h->stream;
     const int32_t counts[2] = {nq, nt};
-    HIPCHK(hipMemcpyAsync(h->d_buf[0], qdesc, (size_t)nq * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->d_buf[2], qangle, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(slot_ptr(h, S_BF_QD), qdesc, (size_t)nq * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(slot_ptr(h, S_BF_QA), qangle, (size_t)nq * 4, hipMemcpyHostToDevice, s));
     if (nt) {
-        HIPCHK(hipMemcpyAsync(h->d_buf[1], tdesc, (size_t)nt * 32, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->d_buf[3], tangle, (size_t)nt * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(slot_ptr(h, S_BF_TD), tdesc, (size_t)nt * 32, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(slot_ptr(h, S_BF_TA), tangle, (size_t)nt * 4, hipMemcpyHostToDevice, s));
     }
-    HIPCHK(hipMemcpyAsync(h->d_buf[4], counts, sizeof counts, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(h->d_buf[7], 0, 34 * 4, s));
-    orbm::MatchIO q{(const uint8_t*)h->d_buf[0], 0, (const float*)h->d_buf[2], 0, 1, (const int32_t*)h->d_buf[4]};
-    orbm::MatchIO t{(const uint8_t*)h->d_buf[1], 0, (const float*)h->d_buf[3], 0, 1, (const int32_t*)h->d_buf[4] + 1};
-    int32_t* d_hist = (int32_t*)h->d_buf[7];
-    if ((rc = orbm_reserve(h, 8, (size_t)nq * kMatchChunks * sizeof(uint2)))) return rc;
+    HIPCHK(hipMemcpyAsync(slot_ptr(h, S_BF_CNT), counts, sizeof counts, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(slot_ptr(h, S_BF_HIST), 0, 34 * 4, s));
+    orbm::MatchIO q{slot_ptr<const uint8_t>(h, S_BF_QD), 0, slot_ptr<const float>(h, S_BF_QA), 0, 1, slot_ptr<const int32_t>(h, S_BF_CNT)};
+    orbm::MatchIO t{slot_ptr<const uint8_t>(h, S_BF_TD), 0, slot_ptr<const float>(h, S_BF_TA), 0, 1, slot_ptr<const int32_t>(h, S_BF_CNT) + 1};
+    int32_t* d_hist = slot_ptr<int32_t>(h, S_BF_HIST);
+    if ((rc = orbm_reserve(h, S_BF_BEST2, (size_t)nq * kMatchChunks * sizeof(uint2)))) return rc;
     const bool mfma = nt < 65536;  // the MFMA scan packs the train index into 16 bits of its key
-    orbm::AcceptArgs aa = {q, t, 0, 0, nnratio, th_low, check_ori, (int32_t*)h->d_buf[5], (int64_t)nq, (uint8_t*)h->d_buf[6], d_hist};
+    orbm::AcceptArgs aa = {q, t, 0, 0, nnratio, th_low, check_ori, slot_ptr<int32_t>(h, S_BF_MATCH), (int64_t)nq, slot_ptr<uint8_t>(h, S_BF_BIN), d_hist};
     if (mfma) {
         const int64_t xPitch = (int64_t)align_up(std::max(nq, nt), orbm::kMfmaRowsPerBlock) * orbm::kMfmaDescBytes;
-        if ((rc = orbm_reserve(h, 9, (size_t)2 * xPitch))) return rc;
-        hipLaunchKernelGGL(orbm::k_expand_desc, dim3((unsigned)(xPitch / 4096), 1), dim3(256), 0, s, q, 0, 0, (uint8_t*)h->d_buf[9], xPitch);
-        hipLaunchKernelGGL(orbm::k_expand_desc, dim3((unsigned)(xPitch / 4096), 1), dim3(256), 0, s, t, 0, 1, (uint8_t*)h->d_buf[9], xPitch);
+        if ((rc = orbm_reserve(h, S_BF_XDESC, (size_t)2 * xPitch))) return rc;
+        hipLaunchKernelGGL(orbm::k_expand_desc, dim3((unsigned)(xPitch / 4096), 1), dim3(256), 0, s, q, 0, 0, slot_ptr<uint8_t>(h, S_BF_XDESC), xPitch);
+        hipLaunchKernelGGL(orbm::k_expand_desc, dim3((unsigned)(xPitch / 4096), 1), dim3(256), 0, s, t, 0, 1, slot_ptr<uint8_t>(h, S_BF_XDESC), xPitch);
         // slot table {nq, nt}: query slot 0, train slot 1 (angles keep their own slot 0 via pitch 0)
         orbm::AcceptArgs am = aa;
         am.tslot0 = 1;
         const int nqb = (nq + orbm::kMfmaRowsPerBlock - 1) / orbm::kMfmaRowsPerBlock;
-        hipLaunchKernelGGL(orbm::k_match_mfma, dim3(8 * nqb), dim3(orbm::kMfmaThreads), orbm::kMfmaLdsBytes, s, (const uint8_t*)h->d_buf[9], xPitch, am, nqb, 1, (uint2*)nullptr, (int64_t)0);
+        hipLaunchKernelGGL(orbm::k_match_mfma, dim3(8 * nqb), dim3(orbm::kMfmaThreads), orbm::kMfmaLdsBytes, s, slot_ptr<const uint8_t>(h, S_BF_XDESC), xPitch, am, nqb, 1, (uint2*)nullptr, (int64_t)0);
     } else {
         hipLaunchKernelGGL(orbm::k_match_best2, dim3((nq + 255) / 256, 1, kMatchChunks), dim3(256), 0, s, q, t, 0, 0, kMatchChunks,
-                           (uint2*)h->d_buf[8], (int64_t)nq);
-        hipLaunchKernelGGL(orbm::k_match_accept, dim3((nq + 255) / 256, 1), dim3(256), 0, s, aa, kMatchChunks, (const uint2*)h->d_buf[8], (int64_t)nq);
+                           slot_ptr<uint2>(h, S_BF_BEST2), (int64_t)nq);
+        hipLaunchKernelGGL(orbm::k_match_accept, dim3((nq + 255) / 256, 1), dim3(256), 0, s, aa, kMatchChunks, slot_ptr<const uint2>(h, S_BF_BEST2), (int64_t)nq);
     }
-    hipLaunchKernelGGL(orbm::k_match_prune, dim3(1), dim3(256), 0, s, q, 0, check_ori, (int32_t*)h->d_buf[5], (int64_t)nq,
-                       (const uint8_t*)h->d_buf[6], d_hist, d_hist + 32);
+    hipLaunchKernelGGL(orbm::k_match_prune, dim3(1), dim3(256), 0, s, q, 0, check_ori, slot_ptr<int32_t>(h, S_BF_MATCH), (int64_t)nq,
+                       slot_ptr<const uint8_t>(h, S_BF_BIN), d_hist, d_hist + 32);
     HIPCHK(hipGetLastError());
     int32_t nm = 0;
-    HIPCHK(hipMemcpyAsync(match, h->d_buf[5], (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(match, slot_ptr(h, S_BF_MATCH), (size_t)nq * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&nm, d_hist + 32, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (nmatches) *nmatches = nm;
@@ -413,8 +439,6 @@ extern "C" int orbm_search_by_bow(orbm_t* h,
 }
 
 // ------------------------------------------------------------------ grid + SearchByProjection
-enum { G_KEYS = 16, G_CNT, G_START, G_FILL, G_IDX };
-
 // grid of n device-resident keys into (d_cnt, d_start, d_fill: ncell(+1) ints, d_idx: n ints), on stream s
 static int grid_build_device(const OrbmGrid* grid, const orbm::KeyDev* dk, int n, int32_t* d_cnt, int32_t* d_start,
                              int32_t* d_fill, int32_t* d_idx, hipStream_t s, orbm::GridDev& gd)
@@ -438,13 +462,12 @@ static int orbm_build_grid(orbm_handle* h, const OrbmGrid* grid, const OrbxKeyPo
     if (!grid || grid->cols < 1 || grid->rows < 1 || grid->cols * grid->rows > (1 << 20)) return fail(ORBX_E_INVALID, "bad grid");
     int rc;
     const int ncell = grid->cols * grid->rows;
-    if ((rc = orbm_reserve(h, G_KEYS, (size_t)std::max(n, 1) * sizeof(OrbxKeyPoint))) || (rc = orbm_reserve(h, G_CNT, (size_t)ncell * 4)) ||
-        (rc = orbm_reserve(h, G_START, (size_t)(ncell + 1) * 4)) || (rc = orbm_reserve(h, G_FILL, (size_t)ncell * 4)) ||
-        (rc = orbm_reserve(h, G_IDX, (size_t)std::max(n, 1) * 4))) return rc;
+    if ((rc = orbm_reserve(h, {{G_KEYS, (size_t)std::max(n, 1) * sizeof(OrbxKeyPoint)}, {G_CNT, (size_t)ncell * 4}, {G_START, (size_t)(ncell + 1) * 4},
+                               {G_FILL, (size_t)ncell * 4}, {G_IDX, (size_t)std::max(n, 1) * 4}}))) return rc;
     hipStream_t s = h->stream;
-    if (n) HIPCHK(hipMemcpyAsync(h->d_buf[G_KEYS], keys, (size_t)n * sizeof(OrbxKeyPoint), hipMemcpyHostToDevice, s));
-    return grid_build_device(grid, (const orbm::KeyDev*)h->d_buf[G_KEYS], n, (int32_t*)h->d_buf[G_CNT], (int32_t*)h->d_buf[G_START],
-                             (int32_t*)h->d_buf[G_FILL], (int32_t*)h->d_buf[G_IDX], s, gd);
+    if (n) HIPCHK(hipMemcpyAsync(slot_ptr(h, G_KEYS), keys, (size_t)n * sizeof(OrbxKeyPoint), hipMemcpyHostToDevice, s));
+    return grid_build_device(grid, slot_ptr<const orbm::KeyDev>(h, G_KEYS), n, slot_ptr<int32_t>(h, G_CNT), slot_ptr<int32_t>(h, G_START),
+                             slot_ptr<int32_t>(h, G_FILL), slot_ptr<int32_t>(h, G_IDX), s, gd);
 }
 
 extern "C" int orbm_features_in_area(orbm_t* h, const OrbmGrid* grid, const OrbxKeyPoint* keys_un, int n,
@@ -456,18 +479,18 @@ extern "C" int orbm_features_in_area(orbm_t* h, const OrbmGrid* grid, const Orbx
     if (n < 0 || (n && !keys_un) || cap < 0 || (cap && !out)) return fail(ORBX_E_INVALID, "bad argument");
     orbm::GridDev gd;
     if ((rc = orbm_build_grid(h, grid, keys_un, n, gd))) return rc;
-    if ((rc = orbm_reserve(h, 0, (size_t)std::max(cap, 1) * 4)) || (rc = orbm_reserve(h, 1, 16))) return rc;
+    if ((rc = orbm_reserve(h, S_FA_OUT, (size_t)std::max(cap, 1) * 4)) || (rc = orbm_reserve(h, S_FA_CNT, 16))) return rc;
     hipStream_t s = h->stream;
-    hipLaunchKernelGGL(orbm::k_features_in_area, dim3(1), dim3(1), 0, s, gd, (const orbm::KeyDev*)h->d_buf[G_KEYS],
-                       (const int32_t*)h->d_buf[G_START], (const int32_t*)h->d_buf[G_IDX], x, y, r, minLevel, maxLevel,
-                       (int32_t*)h->d_buf[0], cap, (int32_t*)h->d_buf[1]);
+    hipLaunchKernelGGL(orbm::k_features_in_area, dim3(1), dim3(1), 0, s, gd, slot_ptr<const orbm::KeyDev>(h, G_KEYS),
+                       slot_ptr<const int32_t>(h, G_START), slot_ptr<const int32_t>(h, G_IDX), x, y, r, minLevel, maxLevel,
+                       slot_ptr<int32_t>(h, S_FA_OUT), cap, slot_ptr<int32_t>(h, S_FA_CNT));
     HIPCHK(hipGetLastError());
     int32_t cnt = 0;
-    HIPCHK(hipMemcpyAsync(&cnt, h->d_buf[1], 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&cnt, slot_ptr(h, S_FA_CNT), 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (n_out) *n_out = cnt;
     if (cnt > cap) return fail(ORBX_E_CAPACITY, "%d features in area, capacity %d", cnt, cap);
-    if (cnt) HIPCHK(hipMemcpy(out, h->d_buf[0], (size_t)cnt * 4, hipMemcpyDeviceToHost));
+    if (cnt) HIPCHK(hipMemcpy(out, slot_ptr(h, S_FA_OUT), (size_t)cnt * 4, hipMemcpyDeviceToHost));
     return ORBX_OK;
 }
 
@@ -496,7 +519,7 @@ static int bow_core(orbm_handle* h, const BowSide& q, const uint8_t* qvalid, con
     const size_t total = pk.off;
     if ((rc = orbm_pinned(h, total)) || (rc = orbm_reserve(h, T_STAGE, total))) return rc;
     uint8_t* hs = (uint8_t*)h->h_stage;
-    uint8_t* ds = (uint8_t*)h->d_buf[T_STAGE];
+    uint8_t* ds = slot_ptr<uint8_t>(h, T_STAGE);
     // lock-step walk of the two sorted node-id lists: host side, it only decides WHICH node pairs are searched
     int npairs = 0;
     {
@@ -754,32 +777,30 @@ extern "C" int orbm_search_by_projection_frame(orbm_t* h, const OrbmProjParams* 
     return proj_core(h, pp, q_uvr, q_lvl, qdesc, qangle, qvalid, q_obs_pos, nq, &tr, nullptr, nt, t_occ, assign, nmatches);
 }
 
-#define UP(slot, src, bytes) HIPCHK(hipMemcpyAsync(h->d_buf[slot], src, bytes, hipMemcpyHostToDevice, s))
 // train side of a windowed best search, resident in HBM
 static int window_core(orbm_handle* h, const float* q_uvr, const float* q_ur, const int8_t* q_pred, const uint8_t* qdesc,
                        const uint8_t* qvalid, int nq, const ProjTrain& tr, const float* d_turight, const float* inv_sigma2,
                        int nlevels, int chi2, int32_t* best_idx, int32_t* best_dist)
 {
     int rc;
-    enum { S_UVR, S_UR, S_PRED, S_QD, S_QV, S_TD, S_TUR, S_SIG, S_BI, S_BD };
-    const size_t sizes[] = {(size_t)nq * 12, (size_t)nq * 4, (size_t)nq, (size_t)nq * 32, (size_t)nq, 16, 16, 64, (size_t)nq * 4, (size_t)nq * 4};
-    for (int i = 0; i < 10; i++) if (i != S_TD && i != S_TUR && (rc = orbm_reserve(h, i, sizes[i]))) return rc;
+    if ((rc = orbm_reserve(h, {{S_WIN_UVR, (size_t)nq * 12}, {S_WIN_UR, (size_t)nq * 4}, {S_WIN_PRED, (size_t)nq}, {S_WIN_QD, (size_t)nq * 32},
+                               {S_WIN_QV, (size_t)nq}, {S_WIN_SIG, 64}, {S_WIN_BI, (size_t)nq * 4}, {S_WIN_BD, (size_t)nq * 4}}))) return rc;
     hipStream_t s = h->stream;
-    UP(S_UVR, q_uvr, (size_t)nq * 12); UP(S_PRED, q_pred, (size_t)nq); UP(S_QD, qdesc, (size_t)nq * 32);
-    if (q_ur) UP(S_UR, q_ur, (size_t)nq * 4);
-    if (qvalid) UP(S_QV, qvalid, (size_t)nq);
-    if (chi2) UP(S_SIG, inv_sigma2, (size_t)nlevels * 4);
+    if ((rc = slot_upload(h, S_WIN_UVR, q_uvr, (size_t)nq * 12)) || (rc = slot_upload(h, S_WIN_PRED, q_pred, (size_t)nq)) ||
+        (rc = slot_upload(h, S_WIN_QD, qdesc, (size_t)nq * 32)) ||
+        (q_ur && (rc = slot_upload(h, S_WIN_UR, q_ur, (size_t)nq * 4))) || (qvalid && (rc = slot_upload(h, S_WIN_QV, qvalid, (size_t)nq))) ||
+        (chi2 && (rc = slot_upload(h, S_WIN_SIG, inv_sigma2, (size_t)nlevels * 4)))) return rc;
     orbm::WinArgs a{};
     a.grid = tr.gd;
     a.tkeys = tr.keys;
     a.cellStart = tr.cellStart; a.cellIdx = tr.cellIdx;
-    a.quvr = (const float*)h->d_buf[S_UVR]; a.qur = q_ur ? (const float*)h->d_buf[S_UR] : nullptr;
-    a.qpred = (const int8_t*)h->d_buf[S_PRED]; a.qdesc = (const uint8_t*)h->d_buf[S_QD];
-    a.qvalid = qvalid ? (const uint8_t*)h->d_buf[S_QV] : nullptr;
+    a.quvr = slot_ptr<const float>(h, S_WIN_UVR); a.qur = q_ur ? slot_ptr<const float>(h, S_WIN_UR) : nullptr;
+    a.qpred = slot_ptr<const int8_t>(h, S_WIN_PRED); a.qdesc = slot_ptr<const uint8_t>(h, S_WIN_QD);
+    a.qvalid = qvalid ? slot_ptr<const uint8_t>(h, S_WIN_QV) : nullptr;
     a.tdesc = tr.desc; a.turight = d_turight;
-    a.invSigma2 = (const float*)h->d_buf[S_SIG];
+    a.invSigma2 = slot_ptr<const float>(h, S_WIN_SIG);
     a.nq = nq; a.chi2 = chi2;
-    a.bestIdx = (int32_t*)h->d_buf[S_BI]; a.bestDist = (int32_t*)h->d_buf[S_BD];
+    a.bestIdx = slot_ptr<int32_t>(h, S_WIN_BI); a.bestDist = slot_ptr<int32_t>(h, S_WIN_BD);
     hipLaunchKernelGGL(orbm::k_window_best, dim3((nq + 63) / 64), dim3(64), 0, s, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(best_idx, a.bestIdx, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
@@ -813,16 +834,13 @@ extern "C" int orbm_window_best(orbm_t* h, const float* q_uvr, const float* q_ur
     if (nq == 0 || nt == 0) return ORBX_OK;
     ProjTrain tr;
     if ((rc = orbm_build_grid(h, grid, t_keys_un, nt, tr.gd))) return rc;
-    enum { S_TD = 5, S_TUR = 6 };
-    if ((rc = orbm_reserve(h, S_TD, (size_t)nt * 32)) || (rc = orbm_reserve(h, S_TUR, (size_t)nt * 4))) return rc;
-    hipStream_t s = h->stream;
-    UP(S_TD, tdesc, (size_t)nt * 32);
-    if (t_uright) UP(S_TUR, t_uright, (size_t)nt * 4);
-    tr.keys = (const orbm::KeyDev*)h->d_buf[G_KEYS];
-    tr.cellStart = (const int32_t*)h->d_buf[G_START]; tr.cellIdx = (const int32_t*)h->d_buf[G_IDX];
-    tr.desc = (const uint8_t*)h->d_buf[S_TD];
+    if ((rc = orbm_reserve(h, S_WIN_TD, (size_t)nt * 32)) || (rc = orbm_reserve(h, S_WIN_TUR, (size_t)nt * 4))) return rc;
+    if ((rc = slot_upload(h, S_WIN_TD, tdesc, (size_t)nt * 32)) || (t_uright && (rc = slot_upload(h, S_WIN_TUR, t_uright, (size_t)nt * 4)))) return rc;
+    tr.keys = slot_ptr<const orbm::KeyDev>(h, G_KEYS);
+    tr.cellStart = slot_ptr<const int32_t>(h, G_START); tr.cellIdx = slot_ptr<const int32_t>(h, G_IDX);
+    tr.desc = slot_ptr<const uint8_t>(h, S_WIN_TD);
     tr.nt = nt;
-    return window_core(h, q_uvr, q_ur, q_pred, qdesc, qvalid, nq, tr, t_uright ? (const float*)h->d_buf[S_TUR] : nullptr, inv_sigma2,
+    return window_core(h, q_uvr, q_ur, q_pred, qdesc, qvalid, nq, tr, t_uright ? slot_ptr<const float>(h, S_WIN_TUR) : nullptr, inv_sigma2,
                        nlevels, chi2, best_idx, best_dist);
 }
 
@@ -850,26 +868,24 @@ static int init_core(orbm_handle* h, const float* q_xy, float window_size, const
     std::vector<float> uvr((size_t)nq * 3);
     std::vector<int8_t> lvl((size_t)nq * 2, 0);
     for (int i = 0; i < nq; i++) { uvr[3 * i] = q_xy[2 * i]; uvr[3 * i + 1] = q_xy[2 * i + 1]; uvr[3 * i + 2] = window_size; }
-    enum { S_UVR, S_LVL, S_CNT = 6, S_OFF, S_KEY, S_CIDX, S_M12, S_M21, S_NM, S_PUSHT, S_PUSHB };
-    const int slots[] = {S_UVR, S_LVL, S_CNT, S_OFF, S_KEY, S_CIDX, S_M12, S_M21, S_NM, S_PUSHT, S_PUSHB};
-    const size_t sizes[] = {(size_t)nq * 12, (size_t)nq * 2, (size_t)nq * 4, (size_t)(nq + 1) * 4, 16, 16, (size_t)nq * 4, (size_t)nt * 4, 16,
-                            (size_t)nq * 4, (size_t)nq};
-    for (int i = 0; i < 11; i++) if ((rc = orbm_reserve(h, slots[i], sizes[i]))) return rc;
+    if ((rc = orbm_reserve(h, {{S_INI_UVR, (size_t)nq * 12}, {S_INI_LVL, (size_t)nq * 2}, {S_INI_CNT, (size_t)nq * 4}, {S_INI_OFF, (size_t)(nq + 1) * 4},
+                               {S_INI_KEY, 16}, {S_INI_CIDX, 16}, {S_INI_M12, (size_t)nq * 4}, {S_INI_M21, (size_t)nt * 4}, {S_INI_NM, 16},
+                               {S_INI_PUSHT, (size_t)nq * 4}, {S_INI_PUSHB, (size_t)nq}}))) return rc;
     hipStream_t s = h->stream;
-    UP(S_UVR, uvr.data(), (size_t)nq * 12); UP(S_LVL, lvl.data(), (size_t)nq * 2);
+    if ((rc = slot_upload(h, S_INI_UVR, uvr.data(), (size_t)nq * 12)) || (rc = slot_upload(h, S_INI_LVL, lvl.data(), (size_t)nq * 2))) return rc;
     orbm::ProjArgs a{};
     a.grid = tr.gd;
     a.tkeys = tr.keys;
     a.cellStart = tr.cellStart; a.cellIdx = tr.cellIdx;
-    a.quvr = (const float*)h->d_buf[S_UVR]; a.qlvl = (const int8_t*)h->d_buf[S_LVL];
+    a.quvr = slot_ptr<const float>(h, S_INI_UVR); a.qlvl = slot_ptr<const int8_t>(h, S_INI_LVL);
     a.qdesc = d_qdesc; a.qang = d_qang;
     a.qvalid = d_qvalid; a.qobs = nullptr;
     a.tdesc = tr.desc;
     a.nq = nq; a.nt = nt;
-    a.candCnt = (int32_t*)h->d_buf[S_CNT]; a.candOff = (int32_t*)h->d_buf[S_OFF];
+    a.candCnt = slot_ptr<int32_t>(h, S_INI_CNT); a.candOff = slot_ptr<int32_t>(h, S_INI_OFF);
     a.candKey = nullptr; a.candIdx = nullptr;
-    a.tocc = nullptr; a.assign = nullptr; a.nmatch = (int32_t*)h->d_buf[S_NM];
-    a.pushT = (int32_t*)h->d_buf[S_PUSHT]; a.pushBin = (uint8_t*)h->d_buf[S_PUSHB];
+    a.tocc = nullptr; a.assign = nullptr; a.nmatch = slot_ptr<int32_t>(h, S_INI_NM);
+    a.pushT = slot_ptr<int32_t>(h, S_INI_PUSHT); a.pushBin = slot_ptr<uint8_t>(h, S_INI_PUSHB);
     a.mode = 7; a.nnratio = nnratio; a.checkOri = check_ori; a.thDist = 50;
     hipLaunchKernelGGL(orbm::k_proj_candidates, dim3((nq + 63) / 64), dim3(64), 0, s, a, 0);
     hipLaunchKernelGGL(orbm::k_scan_small, dim3(1), dim3(1024), 0, s, (const int32_t*)a.candCnt, nq, a.candOff);
@@ -877,15 +893,15 @@ static int init_core(orbm_handle* h, const float* q_xy, float window_size, const
     int32_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, a.candOff + nq, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if ((rc = orbm_reserve(h, S_KEY, (size_t)std::max(total, 1) * 4)) || (rc = orbm_reserve(h, S_CIDX, (size_t)std::max(total, 1) * 4))) return rc;
-    a.candKey = (uint32_t*)h->d_buf[S_KEY]; a.candIdx = (int32_t*)h->d_buf[S_CIDX];
+    if ((rc = orbm_reserve(h, S_INI_KEY, (size_t)std::max(total, 1) * 4)) || (rc = orbm_reserve(h, S_INI_CIDX, (size_t)std::max(total, 1) * 4))) return rc;
+    a.candKey = slot_ptr<uint32_t>(h, S_INI_KEY); a.candIdx = slot_ptr<int32_t>(h, S_INI_CIDX);
     hipLaunchKernelGGL(orbm::k_proj_candidates, dim3((nq + 63) / 64), dim3(64), 0, s, a, 1);
     const size_t lds = ((size_t)nt * 2 + 3) & ~(size_t)3;
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)orbm::k_init_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(orbm::k_init_resolve, dim3(1), dim3(64), lds, s, a, (int32_t*)h->d_buf[S_M12], (int32_t*)h->d_buf[S_M21]);
+    hipLaunchKernelGGL(orbm::k_init_resolve, dim3(1), dim3(64), lds, s, a, slot_ptr<int32_t>(h, S_INI_M12), slot_ptr<int32_t>(h, S_INI_M21));
     HIPCHK(hipGetLastError());
     int32_t nm = 0;
-    HIPCHK(hipMemcpyAsync(matches12, h->d_buf[S_M12], (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(matches12, slot_ptr(h, S_INI_M12), (size_t)nq * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&nm, a.nmatch, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (nmatches) *nmatches = nm;
@@ -909,16 +925,14 @@ extern "C" int orbm_search_for_initialization(orbm_t* h, const float* q_xy, floa
     std::vector<float> ang(nq);
     std::vector<uint8_t> valid(nq);
     for (int i = 0; i < nq; i++) { valid[i] = q_keys_un[i].octave <= 0; ang[i] = q_keys_un[i].angle; }
-    enum { S_QD = 2, S_QA, S_QV, S_TD };
-    if ((rc = orbm_reserve(h, S_QD, (size_t)nq * 32)) || (rc = orbm_reserve(h, S_QA, (size_t)nq * 4)) || (rc = orbm_reserve(h, S_QV, (size_t)nq)) ||
-        (rc = orbm_reserve(h, S_TD, (size_t)nt * 32))) return rc;
-    hipStream_t s = h->stream;
-    UP(S_QD, qdesc, (size_t)nq * 32); UP(S_QA, ang.data(), (size_t)nq * 4); UP(S_QV, valid.data(), (size_t)nq); UP(S_TD, tdesc, (size_t)nt * 32);
-    tr.keys = (const orbm::KeyDev*)h->d_buf[G_KEYS];
-    tr.cellStart = (const int32_t*)h->d_buf[G_START]; tr.cellIdx = (const int32_t*)h->d_buf[G_IDX];
-    tr.desc = (const uint8_t*)h->d_buf[S_TD];
+    if ((rc = orbm_reserve(h, {{S_INI_QD, (size_t)nq * 32}, {S_INI_QA, (size_t)nq * 4}, {S_INI_QV, (size_t)nq}, {S_INI_TD, (size_t)nt * 32}}))) return rc;
+    if ((rc = slot_upload(h, S_INI_QD, qdesc, (size_t)nq * 32)) || (rc = slot_upload(h, S_INI_QA, ang.data(), (size_t)nq * 4)) ||
+        (rc = slot_upload(h, S_INI_QV, valid.data(), (size_t)nq)) || (rc = slot_upload(h, S_INI_TD, tdesc, (size_t)nt * 32))) return rc;
+    tr.keys = slot_ptr<const orbm::KeyDev>(h, G_KEYS);
+    tr.cellStart = slot_ptr<const int32_t>(h, G_START); tr.cellIdx = slot_ptr<const int32_t>(h, G_IDX);
+    tr.desc = slot_ptr<const uint8_t>(h, S_INI_TD);
     tr.nt = nt;
-    return init_core(h, q_xy, window_size, (const uint8_t*)h->d_buf[S_QD], (const float*)h->d_buf[S_QA], (const uint8_t*)h->d_buf[S_QV], nq, tr,
+    return init_core(h, q_xy, window_size, slot_ptr<const uint8_t>(h, S_INI_QD), slot_ptr<const float>(h, S_INI_QA), slot_ptr<const uint8_t>(h, S_INI_QV), nq, tr,
                      nnratio, check_ori, matches12, nmatches);
 }
 
@@ -935,10 +949,10 @@ extern "C" int orbm_search_for_initialization_frames(orbm_t* h, const float* q_x
     for (int i = 0; i < nq; i++) matches12[i] = -1;
     if (nmatches) *nmatches = 0;
     if (nq == 0 || nt == 0) return ORBX_OK;
-    if ((rc = orbm_reserve(h, 4, (size_t)nq))) return rc;
-    hipLaunchKernelGGL(orbm::k_octave0_flags, dim3((nq + 255) / 256), dim3(256), 0, h->stream, (const orbm::KeyDev*)f1->d_keysUn, nq, (uint8_t*)h->d_buf[4]);
+    if ((rc = orbm_reserve(h, S_INI_QV, (size_t)nq))) return rc;
+    hipLaunchKernelGGL(orbm::k_octave0_flags, dim3((nq + 255) / 256), dim3(256), 0, h->stream, (const orbm::KeyDev*)f1->d_keysUn, nq, slot_ptr<uint8_t>(h, S_INI_QV));
     const ProjTrain tr = {f2->gd, f2->d_keysUn, f2->d_start, f2->d_idx, f2->d_desc, nt};
-    return init_core(h, q_xy, window_size, f1->d_desc, f1->d_ang, (const uint8_t*)h->d_buf[4], nq, tr, nnratio, check_ori, matches12, nmatches);
+    return init_core(h, q_xy, window_size, f1->d_desc, f1->d_ang, slot_ptr<const uint8_t>(h, S_INI_QV), nq, tr, nnratio, check_ori, matches12, nmatches);
 }
 
 // one side of SearchForTriangulation resident in HBM (node ids on the host for the lock-step walk)
@@ -964,30 +978,26 @@ static int tri_core(orbm_handle* h, const TriSide& A, const TriSide& B, const fl
     }
     const int npairs = (int)pa.size();
     if (npairs == 0) return ORBX_OK;
-    enum { S_S1 = 2, S_U1 = 3, S_S2 = 6, S_U2 = 7, S_PA = 12, S_PB = 13, S_M12 = 14, S_BIN = 15, S_HIST = 23 };
-    const int slots[] = {S_S1, S_U1, S_S2, S_U2, S_PA, S_PB, S_M12, S_BIN, S_HIST};
-    const size_t sizes[] = {(size_t)n1, (size_t)n1 * 4, (size_t)n2, (size_t)n2 * 4, (size_t)npairs * 4, (size_t)npairs * 4, (size_t)n1 * 4, (size_t)n1, 34 * 4};
-    for (int i = 0; i < 9; i++) if ((rc = orbm_reserve(h, slots[i], sizes[i]))) return rc;
+    if ((rc = orbm_reserve(h, {{S_TRI_S1, (size_t)n1}, {S_TRI_U1, (size_t)n1 * 4}, {S_TRI_S2, (size_t)n2}, {S_TRI_U2, (size_t)n2 * 4}, {S_TRI_PA, (size_t)npairs * 4},
+                               {S_TRI_PB, (size_t)npairs * 4}, {S_TRI_M12, (size_t)n1 * 4}, {S_TRI_BIN, (size_t)n1}, {S_TRI_HIST, 34 * 4}}))) return rc;
     hipStream_t s = h->stream;
-    if (A.skip) UP(S_S1, A.skip, (size_t)n1);
-    if (B.skip) UP(S_S2, B.skip, (size_t)n2);
-    if (A.uright) UP(S_U1, A.uright, (size_t)n1 * 4);
-    if (B.uright) UP(S_U2, B.uright, (size_t)n2 * 4);
-    UP(S_PA, pa.data(), (size_t)npairs * 4); UP(S_PB, pb.data(), (size_t)npairs * 4);
-    HIPCHK(hipMemsetAsync(h->d_buf[S_M12], 0xFF, (size_t)n1 * 4, s));
-    HIPCHK(hipMemsetAsync(h->d_buf[S_HIST], 0, 34 * 4, s));
+    if ((A.skip && (rc = slot_upload(h, S_TRI_S1, A.skip, (size_t)n1))) || (B.skip && (rc = slot_upload(h, S_TRI_S2, B.skip, (size_t)n2))) ||
+        (A.uright && (rc = slot_upload(h, S_TRI_U1, A.uright, (size_t)n1 * 4))) || (B.uright && (rc = slot_upload(h, S_TRI_U2, B.uright, (size_t)n2 * 4))) ||
+        (rc = slot_upload(h, S_TRI_PA, pa.data(), (size_t)npairs * 4)) || (rc = slot_upload(h, S_TRI_PB, pb.data(), (size_t)npairs * 4))) return rc;
+    HIPCHK(hipMemsetAsync(slot_ptr(h, S_TRI_M12), 0xFF, (size_t)n1 * 4, s));
+    HIPCHK(hipMemsetAsync(slot_ptr(h, S_TRI_HIST), 0, 34 * 4, s));
     orbm::TriArgs a{};
     a.k1 = A.keys; a.d1 = A.desc;
-    a.skip1 = A.skip ? (const uint8_t*)h->d_buf[S_S1] : nullptr; a.ur1 = A.uright ? (const float*)h->d_buf[S_U1] : nullptr;
+    a.skip1 = A.skip ? slot_ptr<const uint8_t>(h, S_TRI_S1) : nullptr; a.ur1 = A.uright ? slot_ptr<const float>(h, S_TRI_U1) : nullptr;
     a.k2 = B.keys; a.d2 = B.desc;
-    a.skip2 = B.skip ? (const uint8_t*)h->d_buf[S_S2] : nullptr; a.ur2 = B.uright ? (const float*)h->d_buf[S_U2] : nullptr;
+    a.skip2 = B.skip ? slot_ptr<const uint8_t>(h, S_TRI_S2) : nullptr; a.ur2 = B.uright ? slot_ptr<const float>(h, S_TRI_U2) : nullptr;
     a.start1 = A.d_start; a.idx1 = A.d_idx; a.start2 = B.d_start; a.idx2 = B.d_idx;
-    a.pairA = (const int32_t*)h->d_buf[S_PA]; a.pairB = (const int32_t*)h->d_buf[S_PB];
+    a.pairA = slot_ptr<const int32_t>(h, S_TRI_PA); a.pairB = slot_ptr<const int32_t>(h, S_TRI_PB);
     for (int i = 0; i < 9; i++) a.F[i] = F12[i];
     a.ex = ex; a.ey = ey;
     for (int i = 0; i < 16; i++) { a.sf2[i] = i < nlevels ? sf2[i] : 0.f; a.sigma2[i] = i < nlevels ? sigma2_2[i] : 0.f; }
     a.onlyStereo = only_stereo; a.checkOri = check_ori;
-    a.m12 = (int32_t*)h->d_buf[S_M12]; a.binOf = (uint8_t*)h->d_buf[S_BIN]; a.hist = (int32_t*)h->d_buf[S_HIST];
+    a.m12 = slot_ptr<int32_t>(h, S_TRI_M12); a.binOf = slot_ptr<uint8_t>(h, S_TRI_BIN); a.hist = slot_ptr<int32_t>(h, S_TRI_HIST);
     hipLaunchKernelGGL(orbm::k_triangulation_pairs, dim3(npairs), dim3(64), 0, s, a);
     hipLaunchKernelGGL(orbm::k_prune_flat, dim3(1), dim3(256), 0, s, a.m12, n1, check_ori, (const uint8_t*)a.binOf, a.hist, a.hist + 32);
     HIPCHK(hipGetLastError());
@@ -1018,21 +1028,17 @@ extern "C" int orbm_search_for_triangulation(orbm_t* h,
     const int ni1 = fv1->start[fv1->n_nodes], ni2 = fv2->start[fv2->n_nodes];
     for (int i = 0; i < ni1; i++) if (fv1->idx[i] < 0 || fv1->idx[i] >= n1) return fail(ORBX_E_INVALID, "feature index out of range");
     for (int i = 0; i < ni2; i++) if (fv2->idx[i] < 0 || fv2->idx[i] >= n2) return fail(ORBX_E_INVALID, "feature index out of range");
-    enum { S_K1 = 0, S_D1 = 1, S_K2 = 4, S_D2 = 5, S_ST1 = 8, S_I1 = 9, S_ST2 = 10, S_I2 = 11 };
-    const int slots[] = {S_K1, S_D1, S_K2, S_D2, S_ST1, S_I1, S_ST2, S_I2};
-    const size_t sizes[] = {(size_t)n1 * 28, (size_t)n1 * 32, (size_t)n2 * 28, (size_t)n2 * 32, (size_t)(fv1->n_nodes + 1) * 4,
-                            (size_t)std::max(ni1, 1) * 4, (size_t)(fv2->n_nodes + 1) * 4, (size_t)std::max(ni2, 1) * 4};
-    for (int i = 0; i < 8; i++) if ((rc = orbm_reserve(h, slots[i], sizes[i]))) return rc;
-    hipStream_t s = h->stream;
-    UP(S_K1, k1, (size_t)n1 * 28); UP(S_D1, d1, (size_t)n1 * 32); UP(S_K2, k2, (size_t)n2 * 28); UP(S_D2, d2, (size_t)n2 * 32);
-    UP(S_ST1, fv1->start, (size_t)(fv1->n_nodes + 1) * 4);
-    if (ni1) UP(S_I1, fv1->idx, (size_t)ni1 * 4);
-    UP(S_ST2, fv2->start, (size_t)(fv2->n_nodes + 1) * 4);
-    if (ni2) UP(S_I2, fv2->idx, (size_t)ni2 * 4);
-    const TriSide A = {(const orbm::KeyDev*)h->d_buf[S_K1], (const uint8_t*)h->d_buf[S_D1], n1, (const int32_t*)h->d_buf[S_ST1],
-                       (const int32_t*)h->d_buf[S_I1], fv1->node_id, fv1->n_nodes, skip1, uright1};
-    const TriSide B = {(const orbm::KeyDev*)h->d_buf[S_K2], (const uint8_t*)h->d_buf[S_D2], n2, (const int32_t*)h->d_buf[S_ST2],
-                       (const int32_t*)h->d_buf[S_I2], fv2->node_id, fv2->n_nodes, skip2, uright2};
+    if ((rc = orbm_reserve(h, {{S_TRI_K1, (size_t)n1 * 28}, {S_TRI_D1, (size_t)n1 * 32}, {S_TRI_K2, (size_t)n2 * 28}, {S_TRI_D2, (size_t)n2 * 32},
+                               {S_TRI_ST1, (size_t)(fv1->n_nodes + 1) * 4}, {S_TRI_I1, (size_t)std::max(ni1, 1) * 4},
+                               {S_TRI_ST2, (size_t)(fv2->n_nodes + 1) * 4}, {S_TRI_I2, (size_t)std::max(ni2, 1) * 4}}))) return rc;
+    if ((rc = slot_upload(h, S_TRI_K1, k1, (size_t)n1 * 28)) || (rc = slot_upload(h, S_TRI_D1, d1, (size_t)n1 * 32)) ||
+        (rc = slot_upload(h, S_TRI_K2, k2, (size_t)n2 * 28)) || (rc = slot_upload(h, S_TRI_D2, d2, (size_t)n2 * 32)) ||
+        (rc = slot_upload(h, S_TRI_ST1, fv1->start, (size_t)(fv1->n_nodes + 1) * 4)) || (ni1 && (rc = slot_upload(h, S_TRI_I1, fv1->idx, (size_t)ni1 * 4))) ||
+        (rc = slot_upload(h, S_TRI_ST2, fv2->start, (size_t)(fv2->n_nodes + 1) * 4)) || (ni2 && (rc = slot_upload(h, S_TRI_I2, fv2->idx, (size_t)ni2 * 4)))) return rc;
+    const TriSide A = {slot_ptr<const orbm::KeyDev>(h, S_TRI_K1), slot_ptr<const uint8_t>(h, S_TRI_D1), n1, slot_ptr<const int32_t>(h, S_TRI_ST1),
+                       slot_ptr<const int32_t>(h, S_TRI_I1), fv1->node_id, fv1->n_nodes, skip1, uright1};
+    const TriSide B = {slot_ptr<const orbm::KeyDev>(h, S_TRI_K2), slot_ptr<const uint8_t>(h, S_TRI_D2), n2, slot_ptr<const int32_t>(h, S_TRI_ST2),
+                       slot_ptr<const int32_t>(h, S_TRI_I2), fv2->node_id, fv2->n_nodes, skip2, uright2};
     return tri_core(h, A, B, F12, ex, ey, sf2, sigma2_2, nlevels, only_stereo, check_ori, matches12, nmatches);
 }
 
@@ -1054,7 +1060,6 @@ extern "C" int orbm_search_for_triangulation_frames(orbm_t* h, orbm_frame_t* f1,
     const TriSide B = {f2->d_keysUn, f2->d_desc, f2->n, f2->d_fvStart, f2->d_fvIdx, f2->fvNode.data(), f2->fvNodes, skip2, nullptr};
     return tri_core(h, A, B, F12, ex, ey, sf2, sigma2_2, nlevels, 0, check_ori, matches12, nmatches);
 }
-#undef UP
 
 extern "C" int orbm_undistort_keypoints(orbm_t* h, const OrbxKeyPoint* keys, int n, const float K[4], const float D[5],
                                         OrbxKeyPoint* keys_un)
@@ -1064,14 +1069,14 @@ extern "C" int orbm_undistort_keypoints(orbm_t* h, const OrbxKeyPoint* keys, int
     if (n < 0 || !K || !D || (n && (!keys || !keys_un))) return fail(ORBX_E_INVALID, "bad argument");
     if (n == 0) return ORBX_OK;
     if (D[0] == 0.0f) { memcpy(keys_un, keys, (size_t)n * sizeof(OrbxKeyPoint)); return ORBX_OK; }  // mvKeysUn = mvKeys (Frame.cc:406-410)
-    if ((rc = orbm_reserve(h, 0, (size_t)n * sizeof(OrbxKeyPoint))) || (rc = orbm_reserve(h, 1, (size_t)n * sizeof(OrbxKeyPoint)))) return rc;
+    if ((rc = orbm_reserve(h, S_UND_IN, (size_t)n * sizeof(OrbxKeyPoint))) || (rc = orbm_reserve(h, S_UND_OUT, (size_t)n * sizeof(OrbxKeyPoint)))) return rc;
     hipStream_t s = h->stream;
-    HIPCHK(hipMemcpyAsync(h->d_buf[0], keys, (size_t)n * sizeof(OrbxKeyPoint), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(slot_ptr(h, S_UND_IN), keys, (size_t)n * sizeof(OrbxKeyPoint), hipMemcpyHostToDevice, s));
     orbm::UndistArgs a = {K[0], K[1], K[2], K[3], D[0], D[1], D[2], D[3], D[4]};
-    hipLaunchKernelGGL(orbm::k_undistort, dim3((n + 255) / 256), dim3(256), 0, s, (const orbm::KeyDev*)h->d_buf[0], n, a,
-                       (orbm::KeyDev*)h->d_buf[1]);
+    hipLaunchKernelGGL(orbm::k_undistort, dim3((n + 255) / 256), dim3(256), 0, s, slot_ptr<const orbm::KeyDev>(h, S_UND_IN), n, a,
+                       slot_ptr<orbm::KeyDev>(h, S_UND_OUT));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(keys_un, h->d_buf[1], (size_t)n * sizeof(OrbxKeyPoint), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(keys_un, slot_ptr(h, S_UND_OUT), (size_t)n * sizeof(OrbxKeyPoint), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return ORBX_OK;
 }
@@ -1084,14 +1089,14 @@ extern "C" int orbm_compute_stereo_from_rgbd(orbm_t* h, const OrbxKeyPoint* keys
     if (n < 0 || w < 1 || hh < 1 || stride < w || !depth || (n && (!keys || !keys_un || !uright || !depth_out))) return fail(ORBX_E_INVALID, "bad argument");
     if (n == 0) return ORBX_OK;
     const size_t kb = (size_t)n * sizeof(OrbxKeyPoint), db = (size_t)stride * hh * 4;
-    if ((rc = orbm_reserve(h, 0, kb)) || (rc = orbm_reserve(h, 1, kb)) || (rc = orbm_reserve(h, 2, db)) || (rc = orbm_reserve(h, 3, (size_t)n * 8))) return rc;
+    if ((rc = orbm_reserve(h, S_RGBD_KEYS, kb)) || (rc = orbm_reserve(h, S_RGBD_KEYSUN, kb)) || (rc = orbm_reserve(h, S_RGBD_DEPTH, db)) || (rc = orbm_reserve(h, S_RGBD_OUT, (size_t)n * 8))) return rc;
     hipStream_t s = h->stream;
-    HIPCHK(hipMemcpyAsync(h->d_buf[0], keys, kb, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->d_buf[1], keys_un, kb, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->d_buf[2], depth, db, hipMemcpyHostToDevice, s));
-    float* out = (float*)h->d_buf[3];
-    hipLaunchKernelGGL(orbm::k_stereo_from_rgbd, dim3((n + 255) / 256), dim3(256), 0, s, (const orbm::KeyDev*)h->d_buf[0], (const orbm::KeyDev*)h->d_buf[1], n,
-                       (const float*)h->d_buf[2], w, hh, stride, mbf, out, out + n);
+    HIPCHK(hipMemcpyAsync(slot_ptr(h, S_RGBD_KEYS), keys, kb, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(slot_ptr(h, S_RGBD_KEYSUN), keys_un, kb, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(slot_ptr(h, S_RGBD_DEPTH), depth, db, hipMemcpyHostToDevice, s));
+    float* out = slot_ptr<float>(h, S_RGBD_OUT);
+    hipLaunchKernelGGL(orbm::k_stereo_from_rgbd, dim3((n + 255) / 256), dim3(256), 0, s, slot_ptr<const orbm::KeyDev>(h, S_RGBD_KEYS), slot_ptr<const orbm::KeyDev>(h, S_RGBD_KEYSUN), n,
+                       slot_ptr<const float>(h, S_RGBD_DEPTH), w, hh, stride, mbf, out, out + n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(uright, out, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(depth_out, out + n, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -1113,17 +1118,16 @@ extern "C" int orbm_distinctive_descriptors(orbm_t* h, const uint8_t* desc, cons
     }
     if (total && !desc) return fail(ORBX_E_INVALID, "null descriptors");
     if ((size_t)maxN * 4 > 150 * 1024) return fail(ORBX_E_UNSUPPORTED, "more than 38400 observations of one map point");
-    if ((rc = orbm_reserve(h, 0, (size_t)std::max(total, 1) * 32)) || (rc = orbm_reserve(h, 1, (size_t)(npoints + 1) * 4)) ||
-        (rc = orbm_reserve(h, 2, (size_t)npoints * 4))) return rc;
+    if ((rc = orbm_reserve(h, {{S_DIS_DESC, (size_t)std::max(total, 1) * 32}, {S_DIS_START, (size_t)(npoints + 1) * 4}, {S_DIS_BEST, (size_t)npoints * 4}}))) return rc;
     hipStream_t s = h->stream;
-    if (total) HIPCHK(hipMemcpyAsync(h->d_buf[0], desc, (size_t)total * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->d_buf[1], start, (size_t)(npoints + 1) * 4, hipMemcpyHostToDevice, s));
+    if (total) HIPCHK(hipMemcpyAsync(slot_ptr(h, S_DIS_DESC), desc, (size_t)total * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(slot_ptr(h, S_DIS_START), start, (size_t)(npoints + 1) * 4, hipMemcpyHostToDevice, s));
     const size_t lds = (size_t)std::max(maxN, 1) * 4;
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)orbm::k_distinctive, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(orbm::k_distinctive, dim3(npoints), dim3(64), lds, s, (const uint8_t*)h->d_buf[0], (const int32_t*)h->d_buf[1],
-                       (int32_t*)h->d_buf[2]);
+    hipLaunchKernelGGL(orbm::k_distinctive, dim3(npoints), dim3(64), lds, s, slot_ptr<const uint8_t>(h, S_DIS_DESC), slot_ptr<const int32_t>(h, S_DIS_START),
+                       slot_ptr<int32_t>(h, S_DIS_BEST));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(best_idx, h->d_buf[2], (size_t)npoints * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(best_idx, slot_ptr(h, S_DIS_BEST), (size_t)npoints * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return ORBX_OK;
 }

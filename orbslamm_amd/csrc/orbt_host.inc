@@ -6,8 +6,6 @@
 // The frame-set entries keep B frames and the results of B searches in HBM and make no host sync at all.
 
 // ------------------------------------------------------------------ staging
-enum { T_STAGE = 24, T_OFF, T_CAND, T_QRES, T_STATS, T_FS, T_TSCR, T_PREP };
-
 static int orbm_pinned(orbm_handle* h, size_t bytes) { return grow_pinned(h->h_stage, h->h_stageCap, bytes, true, nullptr, &h->nHostAlloc); }
 
 // The two ends of a drop-in call (host arrays in, host arrays out) ride on the call's own compute queue: the staging
@@ -138,7 +136,7 @@ static int frame_build_big(orbm_handle* h, const orbt::FrameBuildArgs& fa, int n
             HIPCHK(hipMemcpy2DAsync(fa.fs.ang + (int64_t)slot * fa.fs.cap, 4, (const uint8_t*)sk + 12, sizeof(OrbxKeyPoint), 4, (size_t)n, hipMemcpyDeviceToDevice, s));
         }
         orbm::GridDev gd;
-        if ((rc = grid_build_device(&grid, dk, n, (int32_t*)h->d_buf[G_CNT], cs, (int32_t*)h->d_buf[G_FILL], ci, s, gd))) return rc;
+        if ((rc = grid_build_device(&grid, dk, n, slot_ptr<int32_t>(h, G_CNT), cs, slot_ptr<int32_t>(h, G_FILL), ci, s, gd))) return rc;
         if (n) hipLaunchKernelGGL(orbm::k_grid_records, dim3((n + 255) / 256), dim3(256), 0, s, (const orbm::KeyDev*)dk, (const int32_t*)cs, ncell, (const int32_t*)ci,
                                   fa.fs.rec + (int64_t)slot * fa.fs.cap);
         HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(fa.fs.n + slot), n, 1, s));
@@ -234,12 +232,12 @@ extern "C" int orbm_projection_prepare(orbm_t* h, const OrbmGrid* grid, const Or
         (rc = orbm_reserve(h, T_PREP, up)))
         return rc;
     uint8_t* hp = (uint8_t*)h->h_prep;
-    uint8_t* dp = (uint8_t*)h->d_buf[T_PREP];
+    uint8_t* dp = slot_ptr<uint8_t>(h, T_PREP);
     memcpy(hp, t_keys_un, (size_t)nt * sizeof(OrbxKeyPoint));
     memcpy(hp + kb, tdesc, db);
     hipLaunchKernelGGL(k_upload, dim3((unsigned)((up / 16 + 255) / 256)), dim3(256), 0, s, (const uint4*)hp, (uint4*)dp, (int)(up / 16));
     orbt::FrameBuildArgs fa{};
-    fa.fs = scratch_frame_dev((uint8_t*)h->d_buf[T_FS], lay, nt, ncell);
+    fa.fs = scratch_frame_dev(slot_ptr<uint8_t>(h, T_FS), lay, nt, ncell);
     fa.srcKeys = (const orbm::KeyDev*)dp; fa.srcDesc = dp + kb; fa.srcCount = nullptr; fa.srcCap = nt; fa.srcN = nt;
     fa.slot0 = 0; fa.slotMod = 1;
     fa.grid = {grid->minX, grid->minY, grid->invW, grid->invH, grid->cols, grid->rows};
@@ -281,17 +279,15 @@ static int proj_core(orbm_handle* h, const OrbmProjParams* pp, const float* q_uv
     const size_t oAssign = pk.take((size_t)nt * 4), oOcc = pk.take((size_t)nt), oNm = pk.take(16);
     const size_t total = pk.off;
     const ScratchFrame lay = scratch_frame_layout(nt, ncell);
-    const bool freshTotal = h->d_cap[T_STATS] == 0;
-    if ((rc = orbm_pinned(h, total)) || (rc = orbm_reserve(h, T_STAGE, total)) || (rc = orbm_reserve(h, T_OFF, (size_t)nq * 8)) ||
-        (rc = orbm_reserve(h, T_QRES, (size_t)nq * 16)) || (rc = orbm_reserve(h, T_STATS, 16)) ||
-        (rc = orbm_reserve(h, T_CAND, std::max<size_t>((size_t)nq * 64 * 8, 1 << 19))) ||
-        (c.big && (rc = orbm_reserve(h, T_TSCR, (size_t)c.tCap * 12))) ||
-        (trHost && (rc = orbm_reserve(h, T_FS, lay.bytes)))) return rc;
-    if (freshTotal) HIPCHK(hipMemsetAsync(h->d_buf[T_STATS], 0, 16, h->stream));  // the candidate counter: zero on entry, left zero by every resolve
+    const bool freshTotal = slot_cap(h, T_STATS) == 0;
+    if ((rc = orbm_pinned(h, total)) || (rc = orbm_reserve(h, {{T_STAGE, total}, {T_OFF, (size_t)nq * 8}, {T_QRES, (size_t)nq * 16}, {T_STATS, 16},
+                                                               {T_CAND, std::max<size_t>((size_t)nq * 64 * 8, 1 << 19)}})) ||
+        (c.big && (rc = orbm_reserve(h, T_TSCR, (size_t)c.tCap * 12))) || (trHost && (rc = orbm_reserve(h, T_FS, lay.bytes)))) return rc;
+    if (freshTotal) HIPCHK(hipMemsetAsync(slot_ptr(h, T_STATS), 0, 16, h->stream));  // the candidate counter: zero on entry, left zero by every resolve
 
     for (int attempt = 0; attempt < 2; attempt++) {
         uint8_t* hs = (uint8_t*)h->h_stage;
-        uint8_t* ds = (uint8_t*)h->d_buf[T_STAGE];
+        uint8_t* ds = slot_ptr<uint8_t>(h, T_STAGE);
         hipStream_t s = h->stream;
         memcpy(hs + oUvr, q_uvr, (size_t)nq * 12); memcpy(hs + oLvl, q_lvl, (size_t)nq * 2); memcpy(hs + oQd, qdesc, (size_t)nq * 32);
         if (qangle) memcpy(hs + oQa, qangle, (size_t)nq * 4);
@@ -304,7 +300,7 @@ static int proj_core(orbm_handle* h, const OrbmProjParams* pp, const float* q_uv
         ProjTrain tr;
         orbt::FrameBuildArgs fa{};
         if (trHost) {
-            fa.fs = scratch_frame_dev((uint8_t*)h->d_buf[T_FS], lay, nt, ncell);
+            fa.fs = scratch_frame_dev(slot_ptr<uint8_t>(h, T_FS), lay, nt, ncell);
             fa.srcKeys = (const orbm::KeyDev*)(ds + oTk); fa.srcDesc = ds + oTd; fa.srcCount = nullptr; fa.srcCap = nt; fa.srcN = nt;
             fa.slot0 = 0; fa.slotMod = 1;
             fa.grid = {g->minX, g->minY, g->invW, g->invH, g->cols, g->rows};
@@ -323,10 +319,10 @@ static int proj_core(orbm_handle* h, const OrbmProjParams* pp, const float* q_uv
         P.toccIn = ds + oOcc; P.toccOut = ds + oOcc;
         P.assign = (int32_t*)(ds + oAssign); P.initAssign = 0;
         P.nmatch = (int32_t*)(ds + oNm);
-        P.total = (int32_t*)h->d_buf[T_STATS];
-        P.candOff = (int32_t*)h->d_buf[T_OFF]; P.candCnt = P.candOff + nq; P.cand = (uint2*)h->d_buf[T_CAND]; P.candCap = (int)(h->d_cap[T_CAND] / 8);
-        P.qres = (int32_t*)h->d_buf[T_QRES]; P.qscr = P.qres + nq; P.stats = (int32_t*)(ds + oNm) + 1;
-        P.tscr = c.big ? (int32_t*)h->d_buf[T_TSCR] : nullptr;
+        P.total = slot_ptr<int32_t>(h, T_STATS);
+        P.candOff = slot_ptr<int32_t>(h, T_OFF); P.candCnt = P.candOff + nq; P.cand = slot_ptr<uint2>(h, T_CAND); P.candCap = (int)(slot_cap(h, T_CAND) / 8);
+        P.qres = slot_ptr<int32_t>(h, T_QRES); P.qscr = P.qres + nq; P.stats = (int32_t*)(ds + oNm) + 1;
+        P.tscr = c.big ? slot_ptr<int32_t>(h, T_TSCR) : nullptr;
         memcpy(hs + oPair, &P, sizeof P);
         if ((rc = stage_up(h, s, ds, hs, total))) return rc;
         if (upTrain && (rc = frame_build_launch(h, fa, 1))) return rc;   // (prepared: built already, ahead of this call on the same stream)

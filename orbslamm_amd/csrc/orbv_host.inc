@@ -2,6 +2,9 @@
 // Frame::ComputeBoW and SearchByBoW on device-resident frames.
 
 // ------------------------------------------------------------------ vocabulary (SURVEY 8f.2)
+// The list of a vocabulary's device scratch blocks (OrbmSlot's rule: one name per role, no numbers), all used under orbv_handle::mu.  SV_DESC .. SV_KEYS: a
+// transform's (SV_OUT holds the results until the caller has taken them).  SV_SCORE: orbv_score's packed block (orbk_host.inc).
+enum OrbvSlot { SV_DESC, SV_WORD, SV_NODE, SV_W, SV_OUT, SV_KEYS, SV_SCORE, SV_COUNT };
 struct orbv_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -10,7 +13,7 @@ struct orbv_handle {
     std::vector<int> nodesAtLevel;   // [0 .. deepest]: how many nodes the tree has at each depth (root = 0)
     int32_t* d_childStart = nullptr; int32_t* d_childIdx = nullptr; uint8_t* d_desc = nullptr;
     int32_t* d_wordId = nullptr; double* d_weight = nullptr;
-    void* d_buf[10] = {nullptr}; size_t d_cap[10] = {0};
+    void* d_buf[SV_COUNT] = {nullptr}; size_t d_cap[SV_COUNT] = {0};
     // ONE vocabulary serves every thread of a System (Frame::ComputeBoW on the Tracking thread, KeyFrame::ComputeBoW on
     // LocalMapping's and LoopClosing's, all through the same ORBVocabulary*): a transform owns the scratch for its duration
     std::mutex mu;
@@ -19,7 +22,8 @@ struct orbv_handle {
     size_t aggLds[2] = {0, 0};           // dynamic LDS already granted to k_voc_aggregate<false / true>
 };
 
-static int orbv_reserve(orbv_handle* h, int slot, size_t bytes) { return grow_device(h->d_buf[slot], h->d_cap[slot], bytes, 4096); }
+static int orbv_reserve(orbv_handle* h, OrbvSlot s, size_t bytes) { return grow_device(h->d_buf[s], h->d_cap[s], bytes, 4096); }
+template <class T = void> static T* slot_ptr(const orbv_handle* h, OrbvSlot s) { return (T*)h->d_buf[s]; }
 
 extern "C" void orbv_destroy(orbv_t* h)
 {
@@ -148,7 +152,6 @@ extern "C" int orbv_load_text(int device, const char* path, orbv_t** out)
 
 // transform of n device-resident descriptors; the results stay in the handle's scratch: ONE block (VocOut) that a host
 // caller takes home in one copy, counts = {words, fv nodes}
-enum { SV_DESC, SV_WORD, SV_NODE, SV_W, SV_OUT, SV_KEYS };
 constexpr int kVocMaxFeatures = 1 << 20;   // (the sort key holds the feature index in 32 bits; a bound on the scratch, not on the algorithm)
 struct VocOut {
     size_t oCnt, oOv, oOw, oFn, oFs, oFi, bytes;
@@ -177,20 +180,20 @@ static int voc_transform_launch(orbv_handle* h, const uint8_t* d_desc, int n, in
     int P = 2;
     while (P < n) P <<= 1;
     out = voc_out_layout(n, nullptr);
-    const size_t sizes[] = {0, (size_t)n * 4, (size_t)n * 4, (size_t)n * 8, out.bytes};
     int rc;
-    for (int i = 1; i < 5; i++) if ((rc = orbv_reserve(h, i, sizes[i]))) return rc;
-    out.base = (uint8_t*)h->d_buf[SV_OUT];
+    if ((rc = orbv_reserve(h, SV_WORD, (size_t)n * 4)) || (rc = orbv_reserve(h, SV_NODE, (size_t)n * 4)) || (rc = orbv_reserve(h, SV_W, (size_t)n * 8)) ||
+        (rc = orbv_reserve(h, SV_OUT, out.bytes))) return rc;
+    out.base = slot_ptr<uint8_t>(h, SV_OUT);
     hipStream_t s = h->stream;
     orbv::VocDev v{h->d_childStart, h->d_childIdx, h->d_desc, h->d_wordId, h->d_weight, h->L, h->scoring, h->weighting};
     hipLaunchKernelGGL(orbv::k_voc_descend, dim3((n + 63) / 64), dim3(64), 0, s, v, d_desc, n, levelsup,
-                       (uint32_t*)h->d_buf[SV_WORD], (uint32_t*)h->d_buf[SV_NODE], (double*)h->d_buf[SV_W]);
+                       slot_ptr<uint32_t>(h, SV_WORD), slot_ptr<uint32_t>(h, SV_NODE), slot_ptr<double>(h, SV_W));
     if (P > 8192) {
         // more descriptors than the sort's keys fit a CU's LDS for: the same kernel body on a scratch block in memory
         if ((rc = orbv_reserve(h, SV_KEYS, (size_t)P * 12))) return rc;
-        hipLaunchKernelGGL(orbv::k_voc_aggregate_mem, dim3(1), dim3(orbv::kAggThreads), 0, s, v, n, P, (const uint32_t*)h->d_buf[SV_WORD],
-                           (const uint32_t*)h->d_buf[SV_NODE], (const double*)h->d_buf[SV_W], out.ow(), out.ov(), out.fn(), out.fs(), out.fi(), out.cnt(),
-                           (uint64_t*)h->d_buf[SV_KEYS]);
+        hipLaunchKernelGGL(orbv::k_voc_aggregate_mem, dim3(1), dim3(orbv::kAggThreads), 0, s, v, n, P, slot_ptr<const uint32_t>(h, SV_WORD),
+                           slot_ptr<const uint32_t>(h, SV_NODE), slot_ptr<const double>(h, SV_W), out.ow(), out.ov(), out.fn(), out.fs(), out.fi(), out.cnt(),
+                           slot_ptr<uint64_t>(h, SV_KEYS));
         HIPCHK(hipGetLastError());
         return ORBX_OK;
     }
@@ -201,8 +204,8 @@ static int voc_transform_launch(orbv_handle* h, const uint8_t* d_desc, int n, in
         HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         h->aggLds[accLds] = lds;
     }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(orbv::kAggThreads), lds, s, v, n, P, (const uint32_t*)h->d_buf[SV_WORD],
-                       (const uint32_t*)h->d_buf[SV_NODE], (const double*)h->d_buf[SV_W], out.ow(), out.ov(), out.fn(), out.fs(), out.fi(), out.cnt());
+    hipLaunchKernelGGL(kern, dim3(1), dim3(orbv::kAggThreads), lds, s, v, n, P, slot_ptr<const uint32_t>(h, SV_WORD),
+                       slot_ptr<const uint32_t>(h, SV_NODE), slot_ptr<const double>(h, SV_W), out.ow(), out.ov(), out.fn(), out.fs(), out.fi(), out.cnt());
     HIPCHK(hipGetLastError());
     return ORBX_OK;
 }
@@ -240,9 +243,9 @@ extern "C" int orbv_transform(orbv_t* h, const uint8_t* desc, int n, int levelsu
     uint8_t* hs = (uint8_t*)h->h_stage;
     hipStream_t s = h->stream;
     memcpy(hs, desc, (size_t)n * 32);
-    hipLaunchKernelGGL(k_upload, dim3((unsigned)((inBytes / 16 + 255) / 256)), dim3(256), 0, s, (const uint4*)hs, (uint4*)h->d_buf[SV_DESC], (int)(inBytes / 16));
+    hipLaunchKernelGGL(k_upload, dim3((unsigned)((inBytes / 16 + 255) / 256)), dim3(256), 0, s, (const uint4*)hs, slot_ptr<uint4>(h, SV_DESC), (int)(inBytes / 16));
     VocOut out;
-    if ((rc = voc_transform_launch(h, (const uint8_t*)h->d_buf[SV_DESC], n, levelsup, out))) return rc;
+    if ((rc = voc_transform_launch(h, slot_ptr<const uint8_t>(h, SV_DESC), n, levelsup, out))) return rc;
     volatile int32_t* flag = (volatile int32_t*)(hs + h->h_stageCap);
     const int32_t want = ++h->stageSeq;
     hipLaunchKernelGGL(k_upload, dim3((unsigned)((out.bytes / 16 + 255) / 256)), dim3(256), 0, s, (const uint4*)out.base, (uint4*)(hs + inBytes), (int)(out.bytes / 16));

@@ -457,3 +457,125 @@ def test_frame_settle_then_the_inputs_may_be_recycled(gpu, oracle):
     assert gn == wn and np.array_equal(ga, wa) and np.array_equal(gocc, wocc) and wn > 100
     m.frame_destroy(frame)
     m.close(); gex.close()
+
+
+def _one_handle_calls(oracle, owner, gex, voc, n):
+    """every entry that draws from the handle's scratch table, at about n features a side: a list of (name, call(matcher) ->
+    arrays and counts).  Frames belong to `owner`, a matcher that runs none of the calls."""
+    import fuse_cases as fc
+    import loopfuse_cases as lc
+    import newpoints_cases as nc
+    from matcher_cases import make_init_case, make_tri_case
+    from orbslamm_amd import local_mapping as lm, loop_closing as lo, make_grid
+    rng = np.random.default_rng(9000 + n)
+    q, t = random_descriptors(rng, n), random_descriptors(rng, n + 5)
+    qa, ta = rng.uniform(0, 360, n).astype(np.float32), rng.uniform(0, 360, n + 5).astype(np.float32)
+    bow = make_bow_case(rng, n, n + 3, max(1, n // 20))
+    pc, pd = make_proj_case(rng, n, n + 7), make_proj_case(rng, n, n + 7)
+    g = make_grid(0.0, 0.0, pc["w"], pc["h"])
+    a0 = np.full(n + 7, -1, np.int32)
+    pred = np.clip(pc["lvl"][:, 0] + 1, 0, 7).astype(np.int8)
+    inv = (1.0 / (np.float32(1.2) ** np.arange(8)) ** 2).astype(np.float32)
+    t_ur = np.where(rng.uniform(size=n + 7) < 0.6, pc["tk"]["x"] - rng.uniform(5, 40, n + 7), -1).astype(np.float32)
+    q_ur = (pc["uvr"][:, 0] - rng.uniform(5, 40, n)).astype(np.float32)
+    ic = make_init_case(rng, n, n + 1)
+    gi = make_grid(0.0, 0.0, ic["w"], ic["h"])
+    tc = make_tri_case(rng, n, n + 3, max(1, n // 20))
+    tb = tc["c"]
+    sizes = [0, 1, 2, 65] + rng.integers(1, 6, n // 4).tolist()
+    dstart = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    ddesc = random_descriptors(rng, int(dstart[-1]))
+    K, D = [517.306408, 516.469215, 318.643040, 255.313989], [0.262383, -0.953104, -0.005358, 0.002628, 1.163314]
+    depth = rng.uniform(0.5, 6.0, (int(ic["h"]), int(ic["w"]))).astype(np.float32)
+    # the two frames of the initialisation case, resident, with their BoW (zero distortion: mvKeysUn = mvKeys)
+    frames = []
+    for keys, desc in ((ic["k1"], ic["d1"]), (ic["k2"], ic["d2"])):
+        dk = gex.upload_frames(np.ascontiguousarray(keys).view(np.uint8).reshape(1, 1, -1))[0]
+        dd = gex.upload_frames(np.ascontiguousarray(desc).reshape(1, 1, -1))[0]
+        F = owner.frame_from_device(dk, dd, len(keys), K[:4], [0, 0, 0, 0, 0], gi)
+        owner.frame_compute_bow(F, voc, 4)
+        frames.append(F)
+    s1, s2 = (rng.uniform(size=n) < 0.3).astype(np.uint8), (rng.uniform(size=n + 1) < 0.3).astype(np.uint8)
+    sf = (np.float32(1.2) ** np.arange(8)).astype(np.float32)
+    F12 = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32)
+    wq = np.stack([ic["k2"]["x"][:n], ic["k2"]["y"][:n], 3.0 * sf[ic["k2"]["octave"][:n]]], axis=1).astype(np.float32)
+    wpred = ic["k2"]["octave"][:n].astype(np.int8)
+    breaks = lm.level_breaks(fc.LOG_SF, fc.NLEVELS)
+    fuse = fc.make_case(n, targets=(2, 2), points=(60, 60), feats=n)
+    loop = lc.make_dense(n + 1, targets=(2, 2), points=(60, 60), feats=n)
+    newp = nc.make_case(n + 2, n=n * 4 // 5, nb=[(o, a, nc.K_A, "true") for o, a in nc._SIDE[:2]], depth=(4, 9), noise=0.25, vis=0.7, skip1=0.1, skip2=0.1)
+
+    def proj(m, c):
+        return m.SearchByProjection(4, 100, c["uvr"], c["lvl"], c["qd"], c["qa"], c["qv"], c["qo"], g, c["tk"], c["td"], c["occ"], a0)
+
+    def prepared(m):
+        m.ProjectionPrepare(g, pc["tk"], pc["td"])
+        return proj(m, pc)
+
+    def prepared_then_other(m):
+        m.ProjectionPrepare(g, pc["tk"], pc["td"])
+        return m.distance_matrix(q, t), proj(m, pc)
+
+    calls = [
+        ("distance_matrix", lambda m: m.distance_matrix(q, t)),
+        ("match_bruteforce", lambda m: m.match_bruteforce(q, qa, t, ta)),
+        ("search_by_bow", lambda m: m.SearchByBoW(bow["qd"], bow["qa"], bow["qv"], bow["qfv"], bow["td"], bow["ta"], None, bow["tfv"], True)),
+        ("search_by_bow_frames", lambda m: m.SearchByBoWFrames(frames[0], s1, frames[1], None, True)),
+        ("features_in_area", lambda m: m.GetFeaturesInArea(g, pc["tk"], 600.0, 180.0, 300.0, 0, 5)),
+        ("search_by_projection", lambda m: proj(m, pd)),
+        ("search_by_projection prepared", prepared),
+        ("search_by_projection prepared, another entry between", prepared_then_other),
+        ("search_by_projection_frame", lambda m: m.SearchByProjectionFrame(4, 100, wq, np.stack([wpred - 1, wpred + 1], axis=1), ic["d2"][:n], ic["k2"]["angle"][:n],
+                                                                           None, None, frames[1], np.zeros(n + 1, np.uint8), np.full(n + 1, -1, np.int32))),
+        ("window_best", lambda m: m.window_best(pc["uvr"], pred, pc["qd"], pc["qv"], g, pc["tk"], pc["td"], inv, False)),
+        ("window_best chi2 stereo", lambda m: m.window_best(pc["uvr"], pred, pc["qd"], None, g, pc["tk"], pc["td"], inv, True, q_ur, t_ur)),
+        ("window_best_frame", lambda m: m.window_best_frame(wq, wpred, ic["d2"][:n], None, frames[1], inv, True)),
+        ("search_for_initialization", lambda m: m.SearchForInitialization(ic["q_xy"], 100.0, ic["k1"], ic["d1"], gi, ic["k2"], ic["d2"])),
+        ("search_for_initialization_frames", lambda m: m.SearchForInitializationFrames(ic["q_xy"], 100.0, frames[0], frames[1])),
+        ("search_for_triangulation", lambda m: m.SearchForTriangulation(tc["k1"], tb["qd"], 1 - tb["qv"], tb["qfv"], tc["k2"], tb["td"], 1 - tb["tv"], tb["tfv"],
+                                                                       tc["F"], tc["ex"], tc["ey"], tc["sf2"], tc["sigma2"])),
+        ("search_for_triangulation_frames", lambda m: m.SearchForTriangulationFrames(frames[0], s1, frames[1], s2, F12, 1.0e6, 240.0, sf, sf * sf)),
+        ("distinctive_descriptors", lambda m: m.ComputeDistinctiveDescriptors(ddesc, dstart)),
+        ("undistort_keypoints", lambda m: m.UndistortKeyPoints(ic["k1"], K, D)),
+        ("compute_stereo_from_rgbd", lambda m: m.ComputeStereoFromRGBD(ic["k1"], ic["k2"][:n], depth, 40.0)),
+        ("create_new_map_points", lambda m: lm.create_new_map_points(m, newp["cur"], newp["nbs"], newp["sf"], newp["sigma2"], newp["scale_factor"])),
+        ("fuse_batch", lambda m: lm.fuse_batch(m, fuse["targets"], fuse["points"], fuse["jobs"], fuse["sf"], fuse["inv_sigma2"], breaks, th=fuse["th"])),
+        ("search_and_fuse", lambda m: lo.search_and_fuse(m, loop["targets"], loop["points"], loop["sf"], breaks, th=loop["th"],
+                                                         capacity=len(loop["targets"]) * len(loop["points"]), want_status=True)),
+    ]
+    return calls, frames
+
+
+def _as_bytes(out):
+    if isinstance(out, (tuple, list)):
+        return b"|".join(_as_bytes(o) for o in out)
+    return np.ascontiguousarray(out).tobytes()
+
+
+def test_one_handle_runs_every_entry_in_any_order(gpu, oracle):
+    """Every entry that takes scratch from the handle's block table (OrbmSlot), interleaved on ONE handle: 96 features (every
+    block at its 4096-byte floor), 700 (every block replaced), 96 again; the list forwards, then backwards.  Each result
+    equals, as bytes, the same call on a handle made for that call alone -- no entry reads what another left in a block,
+    none loses what it keeps across calls (the prepared train side, the candidate counter)."""
+    from vocab_cases import make_vocab
+    from orbslamm_amd import ORBextractor, ORBmatcher, ORBVocabulary
+    voc_ = make_vocab(np.random.default_rng(5), 10, 4)
+    voc = ORBVocabulary(10, 4, 0, 0, voc_["parent"], voc_["is_leaf"], voc_["desc"], voc_["weight"], device=0)
+    gex = ORBextractor(500, 1.2, 8, 20, 7, max_width=320, max_height=240, max_batch=1, device=0)   # (its handle owns the frames' source buffers)
+    owner, H = ORBmatcher(0.8, True, device=0), ORBmatcher(0.8, True, device=0)
+    cases, want = {}, {}
+    for n in (96, 700):
+        cases[n] = _one_handle_calls(oracle, owner, gex, voc, n)
+        for name, call in cases[n][0]:
+            alone = ORBmatcher(0.8, True, device=0)
+            want[n, name] = _as_bytes(call(alone))
+            alone.close()
+    assert len(set(want.values())) > len(want) * 3 // 4   # (the calls do compute something: few results coincide)
+    for order in (1, -1):
+        for n in (96, 700, 96):
+            for name, call in cases[n][0][::order]:
+                assert _as_bytes(call(H)) == want[n, name], (name, n, "forwards" if order > 0 else "backwards")
+    for n in cases:
+        for F in cases[n][1]:
+            owner.frame_destroy(F)
+    H.close(); owner.close(); gex.close()
