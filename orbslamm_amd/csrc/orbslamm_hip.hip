@@ -31,7 +31,7 @@
 #include <type_traits>
 #include <vector>
 #if defined(__x86_64__)
-#include <immintrin.h>  // streaming stores of the pageable-frame staging (orbx_host.inc)
+#include <immintrin.h>  // streaming stores of the pageable-frame staging (orbx_handle.inc: stage_rows)
 #endif
 
 #include "../../include/orbslamm_hip.h"
@@ -185,7 +185,14 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 // The library is ONE translation unit (every kernel is a template or inline function of a header-like .hip file); its host
 // side is split by family (orbx_hostutil.inc above: what they share):
-#include "orbx_host.inc"   // extractor: handle, tables, pipeline, host-buffer entries, stream matching
+// the extractor, in seven parts by concern; each depends on the ones above it only (two forward declarations in orbx_handle.inc)
+#include "orbx_handle.inc"       // environment switches, profiler, staging helpers, the handle and its result-set accessors
+#include "orbx_geometry.inc"     // constructor tables, level / cell / resize geometry, LDS footprints, table queries
+#include "orbx_streams.inc"      // the two stream pools, create / destroy (what a handle owns), draining and joining
+#include "orbx_pipeline.inc"     // configure_shape, Launcher, run_extract (the event graph), device-resident entries
+#include "orbx_hostpath.inc"     // copy streams, slots, pinned memory, submit_core, collect / release, blocking entries
+#include "orbx_streammatch.inc"  // the stream matcher's launches, the roll of the previous frame, match downloads
+#include "orbx_probe.inc"        // stereo, pyramid / candidate read-back, reset, serial, profile entries, orbx_debug_*
 #include "orbm_host.inc"   // matchers (includes orbt_host.inc: the Tracking-shaped searches and frame sets)
 #include "orbv_host.inc"   // vocabulary
 

@@ -103,7 +103,7 @@ def test_multi_robot_example_builds_against_the_abi():
 
 
 def test_staging_row_copy_equals_memcpy():
-    """orbx_debug_stage_rows: the streaming-store row copy of the pageable-frame staging (orbx_host.inc stage_rows) against a
+    """orbx_debug_stage_rows: the streaming-store row copy of the pageable-frame staging (orbx_handle.inc stage_rows) against a
     plain copy -- widths with every tail length, unaligned sources, aligned and unaligned destinations (the latter take memcpy),
     bytes outside the rows untouched"""
     from orbslamm_amd import _lib

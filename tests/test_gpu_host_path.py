@@ -310,3 +310,137 @@ def test_live_handle_chains_of_up_to_eight_frames(gpu, oracle, kind):
         t0 += B
     for p in pins:
         L.orbx_host_free(ex._h, p)
+
+
+# ---- branches of the host path that only a width that is no multiple of 64 (stride != device stride), pinned frames that
+# ---- cannot go up by the copy kernel, or a ticket abandoned in flight reach.  One 324 x 240 stream, one oracle run.
+_W2, _H2, _NF2 = 324, 240, 500
+_ref2_cache = {}
+
+
+def _stream2(oracle):
+    if "v" not in _ref2_cache:
+        fr = frames_for(_W2, _H2, 20, stream=13)
+        fr.setflags(write=False)
+        _ref2_cache["v"] = (fr, _oracle_stream(oracle, fr, _NF2))
+    return _ref2_cache["v"]
+
+
+def _own_pages(a):
+    """a copy of `a` that shares no page with anything else (two registered buffers must not overlap in a page)"""
+    raw = np.empty(a.nbytes + 8192, dtype=np.uint8)
+    off = -raw.ctypes.data % 4096
+    out = raw[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
+    out[...] = a
+    return out
+
+
+def _check_batch(ref, o, got, b):
+    kps, desc, n, m, nm = got
+    for f in range(b):
+        _check(ref[o + f], kps[f], desc[f], int(n[f]), m[f], int(nm[f]))
+
+
+@pytest.mark.parametrize("kind", ["pageable", "registered_tight", "pinned_device_layout"])
+def test_pipelined_batches_width_not_multiple_of_64(gpu, oracle, kind):
+    """test_pipelined_batches' schedule (tickets of 5, 5, 3, 2 frames, three in flight) at 324 x 240: the device rows are
+    384 bytes apart, so a registered tight buffer (stride 324) goes up by the strided engine copy and a pageable one is
+    staged row by row into a wider pitch"""
+    from orbslamm_amd import ORBextractor
+    w, h, nf = _W2, _H2, _NF2
+    sizes = [5, 5, 3, 2]
+    fr, ref = _stream2(oracle)
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=5, device=0)
+    L = ex._L
+    pins, keep, batches, o = [], [], [], 0
+    for b in sizes:
+        chunk = _own_pages(fr[o:o + b])
+        if kind == "pinned_device_layout":
+            p = ex.alloc_pinned_frames(b, w, h)
+            assert p.stride == 384
+            p.fill(chunk)
+            pins.append(p)
+            batches.append(p)
+        elif kind == "registered_tight":
+            assert L.orbx_host_register(ex._h, C.c_void_p(chunk.ctypes.data), C.c_size_t(chunk.nbytes)) == 0
+            keep.append(chunk)
+            batches.append(chunk)
+        else:
+            batches.append(chunk)
+        o += b
+    tickets, got = [], []
+    for b in batches:
+        tickets.append(ex.submit_host(b))
+        if len(tickets) == 3:
+            got.append(ex.collect_host(tickets.pop(0), view=False))
+    while tickets:
+        got.append(ex.collect_host(tickets.pop(0), view=False))
+    o = 0
+    for i, b in enumerate(sizes):
+        _check_batch(ref, o, got[i], b)
+        o += b
+    for a in keep:
+        assert L.orbx_host_unregister(ex._h, C.c_void_p(a.ctypes.data)) == 0
+    for p in pins:
+        p.free()
+
+
+def test_latency_handle_registered_tight_width_not_multiple_of_64(gpu, oracle):
+    """one frame per call on a latency handle, out of a registered tight buffer at 324 x 240: the strided engine copy on the
+    chain's own stream"""
+    from orbslamm_amd import ORBextractor
+    w, h, nf = _W2, _H2, _NF2
+    fr, ref = _stream2(oracle)
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=1, device=0)
+    a = _own_pages(fr[:4])
+    assert ex._L.orbx_host_register(ex._h, C.c_void_p(a.ctypes.data), C.c_size_t(a.nbytes)) == 0
+    for t in range(4):
+        _check_batch(ref, t, ex.extract_match_host(a[t:t + 1], copy=True), 1)
+    assert ex._L.orbx_host_unregister(ex._h, C.c_void_p(a.ctypes.data)) == 0
+
+
+def test_live_handle_pinned_frames_apart_by_engine_copy(gpu, oracle):
+    """a live handle, calls of 3 frames; every frame tight (stride 324) in a pinned block of its own, 4 bytes into the block:
+    neither back to back nor in the device layout, so each frame goes up by an engine copy of its own (not k_upload_frames)"""
+    from orbslamm_amd import ORBextractor
+    w, h, nf = _W2, _H2, _NF2
+    fr, ref = _stream2(oracle)
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=3, device=0, live=True)
+    L = ex._L
+    pins = []
+    for f in fr[:6]:
+        p = C.c_void_p()
+        assert L.orbx_host_alloc(ex._h, C.c_size_t(w * h + 64), C.byref(p)) == 0
+        np.frombuffer((C.c_uint8 * (w * h)).from_address(p.value + 4), dtype=np.uint8).reshape(h, w)[:] = f
+        pins.append(p)
+    for t0 in (0, 3):
+        tk = C.c_int(-1)
+        opts = ex._opts(True, 0.7, 50, True)
+        arr = (C.c_void_p * 3)(*[pins[t0 + i].value + 4 for i in range(3)])
+        assert L.orbx_submit_batch(ex._h, arr, 3, w, h, w, C.byref(opts), C.byref(tk)) == 0, L.orbx_last_error()
+        _check_batch(ref, t0, ex.collect_host(tk.value, view=False), 3)
+    for p in pins:
+        assert L.orbx_host_free(ex._h, p) == 0
+
+
+@pytest.mark.parametrize("max_batch", [1, 4])
+def test_ticket_abandoned_in_flight(gpu, oracle, max_batch):
+    """three tickets submitted, the middle one released without being collected, the other two collected, two more submitted
+    (the freed slot is used again) -- on a latency handle (one frame per ticket) and on a throughput handle (four).  Every
+    collected frame equals the oracle's; the match table of the ticket behind the abandoned one is taken against the
+    abandoned frames, which stay the previous frames of the stream.  Releasing the ticket a second time is refused."""
+    from orbslamm_amd import ORBextractor
+    w, h, nf, b = _W2, _H2, _NF2, max_batch
+    fr, ref = _stream2(oracle)
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=b, device=0)
+    chunks = [np.ascontiguousarray(fr[i * b:(i + 1) * b]) for i in range(5)]
+    t = [ex.submit_host(chunks[i]) for i in range(3)]
+    assert ex._L.orbx_release(ex._h, t[1]) == 0
+    assert ex._L.orbx_release(ex._h, t[1]) == -1
+    got = {i: ex.collect_host(t[i], view=False) for i in (0, 2)}
+    t += [ex.submit_host(chunks[i]) for i in (3, 4)]
+    assert t[4] % 3 == t[1] % 3   # the abandoned ticket's slot
+    for i in (3, 4):
+        got[i] = ex.collect_host(t[i], view=False)
+    for i in (0, 2, 3, 4):
+        _check_batch(ref, i * b, got[i], b)
