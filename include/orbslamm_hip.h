@@ -965,4 +965,8 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 /* LoopClosing::SearchAndFuse and MultiMapper::SearchAndFuse: the dense Sim3 Fuse over all corrected keyframes is the same
  * library's and is declared in orbslamm_loopfuse.h. */
 #include "orbslamm_loopfuse.h"
+
+/* Optimizer::PoseOptimization: the batched motion-only Levenberg (orbo_pose_optimize, orbo_pose_optimize_frames) is the same
+ * library's and is declared in orbslamm_poseopt.h. */
+#include "orbslamm_poseopt.h"
 #endif

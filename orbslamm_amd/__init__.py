@@ -9,4 +9,5 @@ from .keyframe_db import KeyFrameDatabase, KeyFramePool  # noqa: F401
 from .pnp import PnPsolver, make_pnp_sets  # noqa: F401
 from .local_mapping import compute_f12, create_new_map_points, fuse_batch, level_breaks  # noqa: F401
 from .loop_closing import search_and_fuse, decompose_sim3  # noqa: F401
+from .optimizer import pose_optimization, pose_optimization_batch  # noqa: F401
 from ._lib import KP_DTYPE, OrbError  # noqa: F401

@@ -49,6 +49,7 @@
 #include "orbf_kernels.hip"   // the Fuse pieces shared by orbl's k_fuse_batch and orbc's k_loopfuse_search
 #include "orbl_kernels.hip"
 #include "orbc_kernels.hip"
+#include "orbo_kernels.hip"
 
 using namespace orbx;
 
@@ -204,3 +205,4 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbf_host.inc"   // the Fuse staging shared by orbl_fuse_batch* and orbc_search_and_fuse*
 #include "orbl_host.inc"   // CreateNewMapPoints, SearchInNeighbors' batched Fuse
 #include "orbc_host.inc"   // SearchAndFuse
+#include "orbo_host.inc"   // PoseOptimization
