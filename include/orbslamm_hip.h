@@ -266,6 +266,11 @@ int orbx_debug_link_rate(orbx_t* h, size_t up_bytes, size_t down_bytes, int reps
  * Returns 1 if the streaming form ran, 0 for memcpy, < 0 on a bad argument. */
 int orbx_debug_stage_rows(uint8_t* dst, size_t dpitch, const uint8_t* src, size_t spitch, size_t w, int rows);
 
+/* Diagnostics: the four constant matrix-core operands of the Gaussian (orbx_kernels.hip make_blur_ops), 4 x 64 lanes x 4
+ * dwords into dst -- walk = 0: the one-tile kernel's, 1: the column walk's.  Needs no device: the CPU suite rebuilds the
+ * tables from the tap list and the slot mapping.  steps_per_run (may be NULL): the longest run a column is cut into. */
+int orbx_debug_blur_ops(int walk, uint32_t* dst, int* steps_per_run);
+
 /* ---------------------------------------------------------------- matcher
  * replaces class ORBmatcher (include/ORBmatcher.h:37-102).  The object-graph
  * walking (MapPoint flags, mutex-guarded getters, camera projection) stays in the

@@ -52,6 +52,7 @@ struct HostGeom {
     int xoff[ORBX_MAXL], yoff[ORBX_MAXL];
     int tileStrideDw, tileRows, fastListCap, tileRows0, fastListCap0, fastSmapPitch, fastSmapPitch0, nodeCap;
     BlurTiles bt;
+    BlurRuns br;
     KpBlocks kb;
     int kbTotal;
     std::vector<PyrRange> pyrRanges;   // [block][level]
@@ -205,16 +206,23 @@ static int build_geometry(const orbx_handle* h, int w, int h0, HostGeom& out)
             out.tabs.push_back(make_short4((short)clip(sy), (short)clip(sy + 1), sat((1.f - fy) * 2048), sat(fy * 2048)));
         }
     }
-    // blur tiles (kBlurTW x kBlurTH) and orient/desc blocks (kKpPerBlock keypoints) per level
-    int tb = 0, kb = 0;
+    // blur tiles (kBlurTW x kBlurTH), the column walk's runs and orient/desc blocks (kKpPerBlock keypoints) per level
+    int tb = 0, kb = 0, rb = 0;
+    memset(&out.br, 0, sizeof out.br);
     for (int l = 0; l < g.nlevels; l++) {
         out.bt.base[l] = tb;
         out.bt.tilesX[l] = (g.lv[l].w + kBlurTW - 1) / kBlurTW;
         tb += out.bt.tilesX[l] * ((g.lv[l].h + kBlurTH - 1) / kBlurTH);
+        // a column's steps in equal runs of at most kBlurRunSteps (the last may be shorter)
+        const int steps = blur_walk_steps(g.lv[l].h), nruns = (steps + kBlurRunSteps - 1) / kBlurRunSteps;
+        out.br.base[l] = rb;
+        out.br.colsX[l] = out.bt.tilesX[l];
+        out.br.runSteps[l] = (steps + nruns - 1) / nruns;
+        rb += out.br.colsX[l] * ((steps + out.br.runSteps[l] - 1) / out.br.runSteps[l]);
         out.kb.base[l] = kb;
         kb += (g.lv[l].keptCap + kKpPerBlock - 1) / kKpPerBlock;
     }
-    for (int l = g.nlevels; l <= ORBX_MAXL; l++) { out.bt.base[l] = tb; out.kb.base[l] = kb; }
+    for (int l = g.nlevels; l <= ORBX_MAXL; l++) { out.bt.base[l] = tb; out.br.base[l] = rb; out.kb.base[l] = kb; }
     out.kbTotal = kb;
 
     // fused pyramid: every block owns the same fractional rectangle of each level;

@@ -200,6 +200,7 @@ struct orbx_handle {
     int tileStrideDw = 0, tileRows = 0, fastListCap = 0, tileRows0 = 0, fastListCap0 = 0, fastSmapPitch = 0, fastSmapPitch0 = 0;
     int nodeCap = 0;
     BlurTiles blurTiles;
+    BlurRuns blurRuns;
     KpBlocks kpBlocks;
     int kpBlocksTotal = 0;
     int pyrBlocks = 0, pyrBufA = 0, pyrBufB = 0, pyrTabCap = 0;

@@ -5,6 +5,7 @@
 //   k_fast          ComputeKeyPointsOctTree cell loop :789-829 (cv::FAST 9/16 + NMS + minTh retry)
 //   k_distribute    DistributeOctTree :539-763 + DivideNode :481-537
 //   k_blur_mfma     GaussianBlur 7x7 sigma 2 :1085-1086 (two banded int8 products on the matrix cores, exact in int32)
+//   k_blur_walk     the same filter on the throughput path: a workgroup walks a tile column and carries the halo in registers
 //   k_orient_desc   IC_Angle :77-104, computeOrbDescriptor :108-147, scale/pack :837-847,1095-1101
 //
 // Integer/bitwise path, VALU-issue bound: the kernels are shaped to shed instructions (dot4/dot2/perm/min3/med3,
@@ -1368,6 +1369,35 @@ __device__ __forceinline__ int reflect101(int p, int n)
 // 120x32 output tile per 256-thread block; input 128 x 38 (4 px / 3 rows of halo, dword aligned) in LDS.
 constexpr int kBlurTW = 120, kBlurTH = 32;
 
+// Row yy of a level of h >= 4 rows whose distance to the level is at most the 3-row halo: BORDER_REFLECT_101 in one
+// reflection.  Rows further out (the column walk's flush step reads them, they feed no output row) land on a valid row.
+__device__ __forceinline__ int blur_reflect_row(int yy, int h)
+{
+    return min(max(yy < 0 ? -yy : (yy >= h ? 2 * h - 2 - yy : yy), 0), h - 1);
+}
+
+// The halo columns of an input tile (rows x 32 dwords at a pitch of IN_STRIDE dwords, tile column 0 = level column
+// tx0 - 4) that lie outside the level, patched IN LDS after a load of clamped aligned dwords; `left` / `right` are
+// block-uniform.  The caller synchronises before and after.  (blur_load_tile below keeps its own, older text of these
+// two pieces: built on the helpers the latency chain's kernels compile to other code, and that chain is held fixed.)
+template <int IN_STRIDE>
+__device__ __forceinline__ void blur_patch_cols(uint32_t* in, int rows, int w, int tx0, int tid, bool left, bool right)
+{
+    constexpr int IN_DW = (kBlurTW + 8) / 4;
+    uint8_t* const inb = (uint8_t*)in;
+    if (left && tid < rows) {
+        // x = -4 .. -1 (dword column 0) mirror x = 4 .. 1 (BORDER_REFLECT_101)
+        const uint32_t d1 = in[tid * IN_STRIDE + 1], d2 = in[tid * IN_STRIDE + 2];
+        in[tid * IN_STRIDE] = __builtin_amdgcn_perm(d2, d1, 0x01020304u);  // d2.b0, d1.b3, d1.b2, d1.b1
+    }
+    if (right && tid >= 64 && tid < 64 + 4 * rows) {
+        // x = w + k mirrors x = w - 2 - k; only the three columns right of the image are ever read
+        const int r = (tid - 64) >> 2, k = (tid - 64) & 3;
+        const int bd = w + k - (tx0 - 4), bs = w - 2 - k - (tx0 - 4);
+        if (bd < 4 * IN_DW && bs >= 0) inb[r * IN_STRIDE * 4 + bd] = inb[r * IN_STRIDE * 4 + bs];
+    }
+}
+
 // Input tile of k_blur_mfma: (TH+6) rows x 32 dwords at a pitch of IN_STRIDE dwords, every dword XORed with XORV on the way
 // in.  Global traffic is aligned dwords, all loads issued before the first LDS store.  Ends with the tile complete and
 // the workgroup synchronised.
@@ -1450,8 +1480,14 @@ __device__ __forceinline__ void blur_load_tile(uint32_t* __restrict__ in, const 
 //             starts 4 px left of the outputs); slot (h, b) = strip column 16h + b of the first / second 32 columns
 //   [2], [3]  vertical taps, A side: output row m reads tile rows m .. m+6; slot (h, b = 4g + j) = the tile row
 //             8g + 4h + j that accumulator element 4g + j of the horizontal product holds in that lane half
+// The column walk (k_blur_walk, walk = true) has the same [0], [1]; its tile holds 32 rows, output row m of a step lies
+// six rows above tile row m, and its taps reach into the previous step's tile:
+//   [2]       vertical taps on the PREVIOUS step's H: output row m reads its tile rows m+26 .. 31 with taps 0 .. 5-m
+//             (m <= 5); slot (h, b = 4g + j) = tile row p = 8g + 4h + j, tap p - m - 26
+//   [3]       vertical taps on THIS step's H: output row m reads tile rows max(m-6, 0) .. m; the same slots, tile row
+//             r = 8g + 4h + j, tap r - m + 6
 struct BlurOps { uint32_t v[4][64][4]; };
-constexpr BlurOps make_blur_ops()
+constexpr BlurOps make_blur_ops(bool walk)
 {
     constexpr int W[7] = {18, 34, 49, 55, 49, 34, 18};
     BlurOps o{};
@@ -1461,6 +1497,7 @@ constexpr BlurOps make_blur_ops()
             for (int b = 0; b < 16; b++) {
                 int t = 0;
                 if (op < 2) t = (32 * op + 16 * hh + b) - (i + 1);
+                else if (walk) t = (8 * (b >> 2) + 4 * hh + (b & 3)) - i + (op == 2 ? -26 : 6);
                 else t = (32 * (op - 2) + 8 * (b >> 2) + 4 * hh + (b & 3)) - i;
                 const uint32_t val = (t >= 0 && t <= 6) ? (uint32_t)W[t] : 0u;
                 o.v[op][lane][b >> 2] |= val << (8 * (b & 3));
@@ -1468,7 +1505,7 @@ constexpr BlurOps make_blur_ops()
         }
     return o;
 }
-__device__ const BlurOps kBlurOps = make_blur_ops();
+__device__ const BlurOps kBlurOps = make_blur_ops(false), kBlurWalkOps = make_blur_ops(true);
 
 // 7x7 Gaussian as two exact integer matrix products on the matrix cores (v_mfma_i32_32x32x32_i8): the pipeline these
 // kernels run in is bound by VALU issue while the matrix pipe idles, and a separable filter is a
@@ -1577,6 +1614,181 @@ __global__ __launch_bounds__(256, 2) void k_blur_mfma(const Geom* __restrict__ g
     int bx, fr;
     if (!xcd_block_frame(nframes, bx, fr)) return;
     blur_mfma_tile(g, src, bt, bx, fr, true, (int)threadIdx.x, in, outT);
+}
+
+// ---- the throughput path's Gaussian: a workgroup WALKS a 120-pixel tile column of a level top to bottom in steps of
+// kBlurTH rows instead of living for one tile.  Tile row r of step t is the level's row 32t - 3 + r (reflected): every
+// row is loaded and filtered horizontally ONCE per column, the byte planes of the previous step's H stay in eight
+// registers per lane, and step t emits the 32 output rows 32t - 6 .. 32t + 25 whose seven taps lie in {previous H rows
+// 26 .. 31, this H}: the output trails the input by six rows and the last step of a column flushes what is left.
+// What a tile paid once per 32 rows -- operand fragments, accumulator presets, level lookup, border classification --
+// is paid once per column, and the next step's rows travel from global memory into registers while this step's products
+// and stores run.
+//
+// A column of kBlurRunSteps or fewer steps is one workgroup; a taller one is cut into equal runs of at most that many
+// steps, and a run below the top first rebuilds the six H rows above it (one horizontal product on the eight tile rows
+// 24 .. 31 of the step before, nothing emitted).  The arithmetic argued for short runs: a 32-frame launch of whole
+// 1241 x 376 columns is 51 x 32 = 1632 workgroups of 4 .. 12 steps, 6.4 per CU, all resident at once, so the launch
+// lasts as long as its twelve-step columns while the mean column has 8.3; runs of 6 give 85 x 32 workgroups of 3 .. 7
+// step times for 34 warm-ups on 423 steps.  The measurement (docs/experiments.md, "column walk") says otherwise: alone
+// the kernel takes 0.049 ms per 64 frames with runs of 6 as with whole columns (0.053 / 0.055 / 0.062 with runs of 4 /
+// 3 / 2), but the STEP is 181.0 k frames/s with runs of 6 and 184.6 k with whole columns -- beside FAST the tail of a
+// launch of long workgroups is filled by the other stream, the warm-ups are not.  So 12: the workload's tallest column
+// in one piece; only frames taller than 378 rows are cut at all.
+// A walking workgroup is raised above the FAST cells it runs beside (s_setprio 2): every descriptor launch waits for
+// the whole blur, and with whole columns the step went from 184.6 k to 186.5 k frames/s (three A/B rounds, ranges
+// apart); with runs of 6 the priority made no difference, and the one-tile kernel keeps ORBX_BLUR_PRIO.
+#ifndef ORBX_BLUR_RUN
+#define ORBX_BLUR_RUN 12
+#endif
+#ifndef ORBX_BLUR_WALK_PRIO
+#define ORBX_BLUR_WALK_PRIO 2
+#endif
+constexpr int kBlurRunSteps = ORBX_BLUR_RUN;
+struct BlurRuns { int32_t base[ORBX_MAXL + 1]; int32_t colsX[ORBX_MAXL]; int32_t runSteps[ORBX_MAXL]; };   // runs of a level: base[l] + run * colsX[l] + column
+// steps of a column of h rows: the last one, t, is the first with 32t + 25 >= h - 1
+__host__ __device__ constexpr int blur_walk_steps(int h) { return (h + 37) / 32; }
+constexpr int kBlurWalkInWords = kBlurTH * kBlurMfmaInStride + 8;
+
+__global__ __launch_bounds__(256, 2) void k_blur_walk(const Geom* __restrict__ g, FrameSrc src, BlurRuns br, int nframes)
+{
+#if ORBX_BLUR_WALK_PRIO
+    __builtin_amdgcn_s_setprio(ORBX_BLUR_WALK_PRIO);
+#endif
+    constexpr int TW = kBlurTW, TH = kBlurTH;
+    constexpr int IN_STRIDE = kBlurMfmaInStride, OUT_STRIDE = kBlurMfmaOutStride;
+    typedef int b4i __attribute__((ext_vector_type(4)));
+    typedef int b16i __attribute__((ext_vector_type(16)));
+    __shared__ __attribute__((aligned(16))) uint32_t in[kBlurWalkInWords];
+    __shared__ uint32_t outT[kBlurMfmaOutWords];
+    int bx, fr;
+    if (!xcd_block_frame(nframes, bx, fr)) return;
+    const int tid = (int)threadIdx.x;
+    const int f = fr + src.f0;
+    // ---- once per column: level, geometry, border classification, operands, presets
+    int l = 0;
+    while (l + 1 < g->nlevels && bx >= br.base[l + 1]) l++;
+    const int rIdx = bx - br.base[l];
+    const int run = rIdx / br.colsX[l];
+    const int tx0 = (rIdx - run * br.colsX[l]) * TW;
+    const LevelGeom& L = g->lv[l];
+    const int w = L.w, h = L.h;
+    const int tBeg = run * br.runSteps[l], tEnd = min(blur_walk_steps(h), tBeg + br.runSteps[l]);
+    int stride;
+    const uint8_t* S = level_ptr(g, src, f, l, stride);
+    const int wave = tid >> 6, lane = tid & 63, hh = lane >> 5, m = lane & 31;
+    const b4i* ops = (const b4i*)kBlurWalkOps.v;
+    const b4i hB0 = ops[lane], hB1 = ops[64 + lane], vAp = ops[128 + lane], vAc = ops[192 + lane];
+    // loader: dword column c of tile rows r0 + 8k; the three cases of blur_load_tile
+    const int c = tid & 31, r0 = tid >> 5;
+    const int x0 = tx0 - 4 + 4 * c;
+    const bool colIn = tx0 >= 4 && tx0 + TW + 4 <= w;           // no column of the tile lies outside the image
+    const bool big = w >= 12 && h >= 12;                        // one reflection covers the halo
+    const bool patchL = big && tx0 == 0, patchR = big && tx0 + TW + 4 > w;
+    const bool edge = !(x0 >= 0 && x0 + 3 < w);
+    const int xs = min(max(x0, 0), (w - 1) & ~3);               // valid aligned address for every lane (= x0 where colIn)
+    // (uniform base + 32-bit lane offset: a level is far smaller than 4 GB, and the address costs one add per row)
+    auto ld = [&](uint32_t off) { return *(const uint32_t*)(S + off); };
+    uint32_t regs[TH / 8] = {0, 0, 0, 0};
+    // rows of step tt into the registers; warm: only tile rows 24 .. 31 (the others' H is never read)
+    auto fetch = [&](int tt, bool warm) {
+        const int y0 = 32 * tt - 3 + r0;
+        if (colIn && tt > 0 && 32 * tt + 29 <= h) {
+#pragma unroll
+            for (int k = 0; k < TH / 8; k++)
+                if (!warm || k == TH / 8 - 1) regs[k] = ld((uint32_t)(y0 * stride + xs) + (uint32_t)(8 * k * stride));
+        } else if (big) {
+            // rows reflected in the load; columns outside the image are patched in LDS (patchL / patchR)
+#pragma unroll
+            for (int k = 0; k < TH / 8; k++) {
+                const int yy = y0 + 8 * k;
+                if (!warm || k == TH / 8 - 1) regs[k] = ld((uint32_t)(blur_reflect_row(yy, h) * stride + xs));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < TH / 8; k++) {
+                const uint8_t* row = S + (uint32_t)(reflect101(y0 + 8 * k, h) * stride);
+                uint32_t v = *(const uint32_t*)(row + xs);
+                if (edge) {  // dword straddles the image border: reflect byte by byte
+                    v = 0;
+#pragma unroll
+                    for (int b = 0; b < 4; b++) v |= (uint32_t)row[reflect101(x0 + b, w)] << (8 * b);
+                }
+                regs[k] = v;
+            }
+        }
+    };
+    const bool active = tx0 + 32 * wave < w;   // strips right of the image have nothing to add (wave-uniform)
+    const uint8_t* const inb = (const uint8_t*)in + 32 * wave + 16 * hh + m * (IN_STRIDE * 4);
+    uint8_t* const ob = (uint8_t*)outT + (4 * hh) * (OUT_STRIDE * 4) + 32 * wave + m;
+    const int cq = tid & 31, rq = tid >> 5;
+    const bool stores = cq < TW / 4 && tx0 + 4 * cq < w;
+    uint8_t* const D = src.blur + (int64_t)f * g->blurFrameBytes + L.blurOff;   // + row * bstride + xq
+    const int xq = tx0 + 4 * cq;
+    const int bstride = L.blurStride;
+    // the presets are read as C and never written (D != C): set once per column.  (The empty asm keeps the compiler
+    // from rebuilding the constants in front of every product.)
+    b16i c128, cLo;
+#pragma unroll
+    for (int r = 0; r < 16; r++) { c128[r] = 128; cLo[r] = 257 * 32896 + 32768; }
+    asm volatile("" : "+v"(c128), "+v"(cLo));
+    const b16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    b4i loP = {0, 0, 0, 0}, hiP = {0, 0, 0, 0};   // byte planes of the previous step's H
+
+    int t = tBeg > 0 ? tBeg - 1 : 0;
+    fetch(t, tBeg > 0);
+    for (; t < tEnd; t++) {
+        const bool warm = t < tBeg;
+#pragma unroll
+        for (int k = 0; k < TH / 8; k++) in[(r0 + 8 * k) * IN_STRIDE + c] = regs[k] ^ 0x80808080u;
+        __syncthreads();   // the tile is there; the previous step's stores have read outT
+        if (patchL || patchR) {  // block-uniform
+            blur_patch_cols<IN_STRIDE>(in, TH, w, tx0, tid, patchL, patchR);
+            __syncthreads();
+        }
+        if (t + 1 < tEnd) fetch(t + 1, false);   // in flight across the products and the stores below
+        if (active) {
+            const b4i a0 = *(const b4i*)inb, a1 = *(const b4i*)(inb + 32);
+            b16i G = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, hB0, c128, 0, 0, 0);
+            G = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, hB1, G, 0, 0, 0);
+            b4i loC, hiC;
+#pragma unroll
+            for (int gq = 0; gq < 4; gq++) {
+                const uint32_t t0 = __builtin_amdgcn_perm((uint32_t)G[4 * gq + 1], (uint32_t)G[4 * gq], 0x05010400u);
+                const uint32_t t1 = __builtin_amdgcn_perm((uint32_t)G[4 * gq + 3], (uint32_t)G[4 * gq + 2], 0x05010400u);
+                loC[gq] = (int)(__builtin_amdgcn_perm(t1, t0, 0x05040100u) ^ 0x80808080u);
+                hiC[gq] = (int)__builtin_amdgcn_perm(t1, t0, 0x07060302u);
+            }
+            if (!warm) {
+                b16i aHi = __builtin_amdgcn_mfma_i32_32x32x32_i8(vAp, hiP, zero, 0, 0, 0);
+                aHi = __builtin_amdgcn_mfma_i32_32x32x32_i8(vAc, hiC, aHi, 0, 0, 0);
+                b16i aLo = __builtin_amdgcn_mfma_i32_32x32x32_i8(vAp, loP, cLo, 0, 0, 0);
+                aLo = __builtin_amdgcn_mfma_i32_32x32x32_i8(vAc, loC, aLo, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    // (sum + 2^15) >> 16, saturated (the sum can reach 257 * 257 * 255)
+                    const uint32_t v = min((uint32_t)((aHi[r] << 8) + aLo[r]), 0xFFFFFFu);
+                    ob[((r & 3) + 8 * (r >> 2)) * (OUT_STRIDE * 4)] = (uint8_t)(v >> 16);
+                }
+            }
+            loP = loC; hiP = hiC;
+        }
+        __syncthreads();   // outT is complete; every wave has read its fragments of the tile
+        if (!warm && stores) {
+            const int yb = 32 * t - 6 + rq;   // the level's row of output row rq
+            if (t > 0 && 32 * t + 26 <= h) {  // every row of the step lies in the level (uniform)
+#pragma unroll
+                for (int k = 0; k < TH / 8; k++)
+                    *(uint32_t*)(D + ((uint32_t)(yb * bstride + xq) + (uint32_t)(8 * k * bstride))) = outT[(rq + 8 * k) * OUT_STRIDE + cq];
+            } else {
+#pragma unroll
+                for (int k = 0; k < TH / 8; k++) {
+                    const int y = yb + 8 * k;
+                    if (y >= 0 && y < h) *(uint32_t*)(D + (uint32_t)(y * bstride + xq)) = outT[(rq + 8 * k) * OUT_STRIDE + cq];
+                }
+            }
+        }
+    }
 }
 
 // The quadtree and the Gaussian of a robot's live frame in ONE launch: the first blocks of the grid are k_distribute's (one per

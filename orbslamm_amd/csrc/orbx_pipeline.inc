@@ -53,7 +53,7 @@ static int configure_shape(orbx_handle* h, int w, int hh)
     h->tileStrideDw = hg.tileStrideDw; h->tileRows = hg.tileRows; h->fastListCap = hg.fastListCap; h->nodeCap = hg.nodeCap;
     h->tileRows0 = hg.tileRows0; h->fastListCap0 = hg.fastListCap0;
     h->fastSmapPitch = hg.fastSmapPitch; h->fastSmapPitch0 = hg.fastSmapPitch0;
-    h->blurTiles = hg.bt; h->kpBlocks = hg.kb; h->kpBlocksTotal = hg.kbTotal;
+    h->blurTiles = hg.bt; h->blurRuns = hg.br; h->kpBlocks = hg.kb; h->kpBlocksTotal = hg.kbTotal;
     h->curW = w; h->curH = hh;
     // a new shape starts a new stream
     for (int set = 0; set < 2; set++) HIPCHK(hipMemset(r_count(h, set), 0, sizeof(int32_t)));
@@ -153,10 +153,13 @@ struct Launcher {
         hipLaunchKernelGGL(k_distribute_blur, dim3(g.nlevels + (nTiles + 1) / 2, nb), dim3(kDistThreads), dl, s, da, src, h->blurTiles, nTiles);
         return true;
     }
-    void blur(hipStream_t s) const
+    // the column walk; lat = a call of up to latMaxB frames (the latency chain, and the small calls that take the throughput
+    // loop: one level, ORBX_SERIAL) keeps the one-tile kernel: a frame or two want many short workgroups
+    void blur(hipStream_t s, bool lat = false) const
     {
         h->prof.begin(P_BLUR, s);
-        hipLaunchKernelGGL(k_blur_mfma, dim3(h->blurTiles.base[h->geom.nlevels], xcd_grid_y(nb)), dim3(256), 0, s, h->d_geom, src, h->blurTiles, nb);
+        if (lat) hipLaunchKernelGGL(k_blur_mfma, dim3(h->blurTiles.base[h->geom.nlevels], xcd_grid_y(nb)), dim3(256), 0, s, h->d_geom, src, h->blurTiles, nb);
+        else hipLaunchKernelGGL(k_blur_walk, dim3(h->blurRuns.base[h->geom.nlevels], xcd_grid_y(nb)), dim3(256), 0, s, h->d_geom, src, h->blurRuns, nb);
         h->prof.end(s);
     }
     // The output slots of `set` were read by the matching two batches back and by its download (host path); a wait is
@@ -273,7 +276,7 @@ static int run_extract(orbx_handle* h, const uint8_t* d_imgs, int B, int w, int 
             L.fast(sm, 0, g.totalCells);   // every level in one launch (two, level 0 apart, where level 0 can run ahead of the pyramid)
             if (!L.dist_blur(sm)) {
                 L.dist(sm, 0, g.nlevels);
-                L.blur(sm);
+                L.blur(sm, true);
             }
         } else {
             if (evFrames && sIn != sm) HIPCHK(hipStreamWaitEvent(sm, evFrames, 0));
@@ -287,7 +290,7 @@ static int run_extract(orbx_handle* h, const uint8_t* d_imgs, int B, int w, int 
             L.fast(sm, cellsL0, g.totalCells - cellsL0);
             L.dist(sm, 1, g.nlevels - 1);
             HIPCHK(hipStreamWaitEvent(sa, h->evPyr[0], 0));
-            L.blur(sa);
+            L.blur(sa, true);
             HIPCHK(hipEventRecord(h->evFast0[0], sa));  // the aux chain is through
             HIPCHK(hipStreamWaitEvent(sm, h->evFast0[0], 0));
         }
@@ -322,7 +325,7 @@ static int run_extract(orbx_handle* h, const uint8_t* d_imgs, int B, int w, int 
             // blur only needs the pyramid: run it on a second stream beside FAST + quadtree
             HIPCHK(hipEventRecord(h->evPyr[part], s));
             HIPCHK(hipStreamWaitEvent(s2, h->evPyr[part], 0));
-            L.blur(s2);
+            L.blur(s2, B <= h->latMaxB);
             HIPCHK(hipEventRecord(h->evBlur[part], s2));
             // FAST of levels >= 1 behind the pyramid (level 0 went ahead, see above)
             L.fast(s, cellsL0, g.totalCells - cellsL0);

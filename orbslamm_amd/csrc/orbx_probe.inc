@@ -193,6 +193,15 @@ extern "C" int orbx_debug_stage_rows(uint8_t* dst, size_t dpitch, const uint8_t*
     return g_stageNt && w >= 128 && !(((uintptr_t)dst | dpitch) & 31) ? 1 : 0;
 }
 
+extern "C" int orbx_debug_blur_ops(int walk, uint32_t* dst, int* steps_per_run)
+{
+    if (!dst) return fail(ORBX_E_INVALID, "bad argument");
+    static constexpr BlurOps kTile = make_blur_ops(false), kWalk = make_blur_ops(true);
+    memcpy(dst, walk ? kWalk.v : kTile.v, sizeof kTile.v);
+    if (steps_per_run) *steps_per_run = kBlurRunSteps;
+    return ORBX_OK;
+}
+
 extern "C" int orbx_debug_pair_overlap(orbx_t* h, int nb, float target_ms, int* n_kernels, const char** names,
                                        float* alone_ms, float* co_ms, int32_t* lds_bytes, int32_t* wg_threads, int32_t* wgs)
 {
@@ -221,9 +230,9 @@ extern "C" int orbx_debug_pair_overlap(orbx_t* h, int nb, float target_ms, int* 
         const size_t pl = pyr_lds_bytes(h->pyrBufA, h->pyrBufB, h->pyrTabCap);
         const size_t fl = fast_lds_bytes(h->tileRows, h->tileStrideDw, h->fastSmapPitch, h->fastListCap);
         const int nqb = (h->maxKp + orbm::kMfmaRowsPerBlock - 1) / orbm::kMfmaRowsPerBlock;
-        const int32_t l[K] = {(int32_t)pl, (int32_t)fl, (int32_t)(dist_lds_bytes(h->nodeCap, g.maxCellsPerLevel) + 5552), 13464, 31104, orbm::kMfmaLdsBytes};
+        const int32_t l[K] = {(int32_t)pl, (int32_t)fl, (int32_t)(dist_lds_bytes(h->nodeCap, g.maxCellsPerLevel) + 5552), (kBlurWalkInWords + kBlurMfmaOutWords) * 4, 31104, orbm::kMfmaLdsBytes};
         const int32_t t[K] = {256, 64, kDistThreads, 256, 256, 256};
-        const int32_t w[K] = {h->pyrBlocks * nb, g.totalCells * nb, g.nlevels * nb, h->blurTiles.base[g.nlevels] * nb, h->kpBlocksTotal * nb, nqb * nb};
+        const int32_t w[K] = {h->pyrBlocks * nb, g.totalCells * nb, g.nlevels * nb, h->blurRuns.base[g.nlevels] * nb, h->kpBlocksTotal * nb, nqb * nb};
         for (int k = 0; k < K; k++) { lds_bytes[k] = l[k]; wg_threads[k] = t[k]; wgs[k] = w[k]; }
     }
     for (int k = 0; k < K; k++) if (names) names[k] = kNames[k];

@@ -14,6 +14,9 @@ def kernels_sha():
     # under it is not a table of the default build.  (ORBX_SERIAL, under which the counter passes run, only removes overlap.)
     if os.environ.get("ORBX_MATCH_POPCOUNT") == "1":
         h.update(b"ORBX_MATCH_POPCOUNT=1")
+    # another build of the library (an A/B variant compiled with -D forks such as ORBX_BLUR_RUN): not the default build's table either
+    if os.environ.get("ORBSLAMM_HIP_LIB"):
+        h.update(b"ORBSLAMM_HIP_LIB=" + os.environ["ORBSLAMM_HIP_LIB"].encode())
     return h.hexdigest()[:16]
 
 
