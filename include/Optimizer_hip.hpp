@@ -1,6 +1,7 @@
 // Optimizer_hip.hpp -- the reference's Optimizer::PoseOptimization (include/Optimizer.h, src/Optimizer.cc:261-473 of both
-// scenarios), monocular, over the C ABI of liborbslamm_hip.so (orbo_*).  Header-only, C++11.  The rest of
-// Optimizer (the bundle adjustments, the essential graph, Sim3) stays with g2o.
+// scenarios), monocular, over the C ABI of liborbslamm_hip.so (orbo_*), and its Optimizer::OptimizeSim3
+// (src/Optimizer.cc:1348-1543; orbz_*; OptimizeSim3T, below PoseOptimizationT).  Header-only, C++11.  The rest of
+// Optimizer (the bundle adjustments, the essential graph) stays with g2o.
 //
 //   PoseOptimizationT<Frame, MapPoint>::Run(pFrame)
 //       the drop-in for Optimizer::PoseOptimization(pFrame): the reference's walk over mvpMapPoints on the host (:302-341:
@@ -94,6 +95,124 @@ public:
             }
             ret[slot[f]] = out[f].n_good;
             if (results) (*results)[slot[f]] = out[f];
+        }
+        return ret;
+    }
+};
+
+//   OptimizeSim3T<KeyFrame, MapPoint, Sim3>::Run(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale)
+//       the drop-in for Optimizer::OptimizeSim3: the reference's walk over vpMatches1 on the host (:1401-1440: null and bad points
+//       and a negative GetIndexInKeyFrame skipped), ONE device call, then vpMatches1 nulled exactly where the reference nulls it,
+//       g2oS12 written only when the reference writes it (not on the early return of :1514) and nIn returned.  In the reference tree:
+//           int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12,
+//                                       const float th2, const bool bFixScale)
+//           { return iORB_SLAM::OptimizeSim3T<KeyFrame, MapPoint, g2o::Sim3>::Run(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale); }
+//   OptimizeSim3T<...>::RunAll(jobs)
+//       the same for a list of such argument packs in ONE device call and launch: the candidates of one ComputeSim3 (the first Sim3
+//       of every candidate is known once Sim3SolverT::RunAll has run), or every keyframe of every newer map in MultiMapper::Run.
+//       Every job's outputs are written as if Run had been called on it alone; the caller walks them in the reference's candidate
+//       order and stops at the first with >= 20.  All pKF1 of a call must share one level table and all pKF2 another (they may be
+//       the same), as the keyframes of one extractor do.
+//   Sim3 needs rotation() (with coeffs()[0..3], x y z w), translation() (indexable), scale() and a constructor from
+//   (rotation, translation, scale), as g2o::Sim3 has.  KeyFrame needs GetMapPointMatches, GetRotation, GetTranslation, mvKeysUn,
+//   mvuRight, mvInvLevelSigma2 and fx fy cx cy (mK's entries); MapPoint needs isBad, GetIndexInKeyFrame and GetWorldPos.  A used
+//   feature with a stereo observation (mvuRight >= 0) is refused.  Nothing is written before the device call returns: a refusal
+//   throws with every job as it came.
+template <class KeyFrame, class MapPoint, class Sim3>
+class OptimizeSim3T {
+public:
+    struct Job {
+        KeyFrame* pKF1;
+        KeyFrame* pKF2;
+        std::vector<MapPoint*>* vpMatches1;
+        Sim3* g2oS12;
+        float th2;
+        bool bFixScale;
+    };
+
+    static int Run(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, Sim3& g2oS12, const float th2, const bool bFixScale, int device = 0)
+    {
+        Job j;
+        j.pKF1 = pKF1; j.pKF2 = pKF2; j.vpMatches1 = &vpMatches1; j.g2oS12 = &g2oS12; j.th2 = th2; j.bFixScale = bFixScale;
+        return RunAll(std::vector<Job>(1, j), device)[0];
+    }
+
+    static std::vector<int> RunAll(const std::vector<Job>& jobs, int device = 0, std::vector<OrbzResult>* results = nullptr)
+    {
+        const int nj = (int)jobs.size();
+        std::vector<int> ret(jobs.size(), 0);
+        if (results) results->assign(jobs.size(), OrbzResult());
+        if (!nj) return ret;
+        std::vector<OrbzProblem> prob((size_t)nj);
+        std::vector<int32_t> start(1, 0);
+        std::vector<OrbzCorr> corrs;
+        const std::vector<float>& sigma1 = jobs[0].pKF1->mvInvLevelSigma2;
+        const std::vector<float>& sigma2 = jobs[0].pKF2->mvInvLevelSigma2;
+        if (sigma1.size() != sigma2.size()) throw std::runtime_error("OptimizeSim3(HIP): the two keyframes' level tables differ in length");
+        for (int k = 0; k < nj; k++) {
+            const Job& J = jobs[k];
+            KeyFrame* pKF1 = J.pKF1;
+            KeyFrame* pKF2 = J.pKF2;
+            if (pKF1->mvInvLevelSigma2 != sigma1 || pKF2->mvInvLevelSigma2 != sigma2)
+                throw std::runtime_error("OptimizeSim3(HIP): the jobs of one call must share the two keyframes' mvInvLevelSigma2");
+            OrbzProblem& P = prob[k];
+            for (int c = 0; c < 4; c++) P.q[c] = J.g2oS12->rotation().coeffs()[c];
+            for (int c = 0; c < 3; c++) P.t[c] = J.g2oS12->translation()[c];
+            P.s = J.g2oS12->scale();
+            const auto R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation(), R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) { P.R1w[3 * r + c] = R1w.template at<float>(r, c); P.R2w[3 * r + c] = R2w.template at<float>(r, c); }
+                P.t1w[r] = t1w.template at<float>(r, 0); P.t2w[r] = t2w.template at<float>(r, 0);
+            }
+            P.K1[0] = pKF1->fx; P.K1[1] = pKF1->fy; P.K1[2] = pKF1->cx; P.K1[3] = pKF1->cy;
+            P.K2[0] = pKF2->fx; P.K2[1] = pKF2->fy; P.K2[2] = pKF2->cx; P.K2[3] = pKF2->cy;
+            P.th2 = J.th2;
+            P.fix_scale = J.bFixScale ? 1 : 0;
+            // :1401-1440
+            const std::vector<MapPoint*>& vpMatches1 = *J.vpMatches1;
+            const int N = (int)vpMatches1.size();
+            const std::vector<MapPoint*> vpMapPoints1 = pKF1->GetMapPointMatches();
+            for (int i = 0; i < N; i++) {
+                if (!vpMatches1[i]) continue;
+                MapPoint* pMP1 = vpMapPoints1[i];
+                MapPoint* pMP2 = vpMatches1[i];
+                const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+                if (!pMP1 || pMP1->isBad() || pMP2->isBad() || i2 < 0) continue;
+                if (((size_t)i < pKF1->mvuRight.size() && !(pKF1->mvuRight[i] < 0)) || ((size_t)i2 < pKF2->mvuRight.size() && !(pKF2->mvuRight[i2] < 0)))
+                    throw std::runtime_error("OptimizeSim3(HIP): match " + std::to_string(i) + " uses a stereo observation (mvuRight >= 0); the device OptimizeSim3 is monocular");
+                OrbzCorr c;
+                c.idx1 = i;
+                const auto& kp1 = pKF1->mvKeysUn[i];
+                const auto& kp2 = pKF2->mvKeysUn[i2];
+                c.obs1[0] = kp1.pt.x; c.obs1[1] = kp1.pt.y; c.oct1 = kp1.octave;
+                c.obs2[0] = kp2.pt.x; c.obs2[1] = kp2.pt.y; c.oct2 = kp2.octave;
+                const auto X1 = pMP1->GetWorldPos(), X2 = pMP2->GetWorldPos();
+                for (int r = 0; r < 3; r++) { c.X1w[r] = X1.template at<float>(r, 0); c.X2w[r] = X2.template at<float>(r, 0); }
+                corrs.push_back(c);
+            }
+            start.push_back((int32_t)corrs.size());
+        }
+        std::vector<OrbzResult> out((size_t)nj);
+        std::vector<uint8_t> removed(corrs.size() + 1, 0);
+        orbm_t* h = nullptr;
+        detail::check(orbm_thread_handle(device, &h), "OptimizeSim3(HIP): ");
+        detail::check(orbz_optimize_sim3(h, prob.data(), nj, start.data(), corrs.data(), sigma1.data(), sigma2.data(), (int)sigma1.size(), out.data(),
+                                         removed.data()),
+                      "OptimizeSim3(HIP): ");
+        // nothing of any job has been written up to here
+        for (int k = 0; k < nj; k++) {
+            const Job& J = jobs[k];
+            for (int32_t c = start[k]; c < start[k + 1]; c++)
+                if (removed[c]) (*J.vpMatches1)[corrs[c].idx1] = static_cast<MapPoint*>(nullptr);   // :1499, :1533
+            if (out[k].written) {   // :1541; not reached on the early return of :1514
+                auto r = J.g2oS12->rotation();
+                auto t = J.g2oS12->translation();
+                for (int c = 0; c < 4; c++) r.coeffs()[c] = out[k].q[c];
+                for (int c = 0; c < 3; c++) t[c] = out[k].t[c];
+                *J.g2oS12 = Sim3(r, t, out[k].s);
+            }
+            ret[k] = out[k].n_in;
+            if (results) (*results)[k] = out[k];
         }
         return ret;
     }

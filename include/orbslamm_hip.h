@@ -974,4 +974,8 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 /* Optimizer::PoseOptimization: the batched motion-only Levenberg (orbo_pose_optimize, orbo_pose_optimize_frames) is the same
  * library's and is declared in orbslamm_poseopt.h. */
 #include "orbslamm_poseopt.h"
+
+/* Optimizer::OptimizeSim3: the batched 7-dof Levenberg for loop and merge candidates (orbz_optimize_sim3) is the same
+ * library's and is declared in orbslamm_sim3opt.h. */
+#include "orbslamm_sim3opt.h"
 #endif

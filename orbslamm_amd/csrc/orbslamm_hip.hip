@@ -50,6 +50,7 @@
 #include "orbl_kernels.hip"
 #include "orbc_kernels.hip"
 #include "orbo_kernels.hip"
+#include "orbz_kernels.hip"   // after orbo_kernels.hip: it uses its sin / cos, Huber and quaternion pieces
 
 using namespace orbx;
 
@@ -206,3 +207,4 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbl_host.inc"   // CreateNewMapPoints, SearchInNeighbors' batched Fuse
 #include "orbc_host.inc"   // SearchAndFuse
 #include "orbo_host.inc"   // PoseOptimization
+#include "orbz_host.inc"   // OptimizeSim3
