@@ -63,6 +63,27 @@ struct HostGeom {
 // k_pyramid's LDS: the two level buffers (words) and the coefficient tables of one level
 static inline size_t pyr_lds_bytes(int bufA, int bufB, int tabCap) { return ((size_t)bufA + bufB) * 4 + (size_t)tabCap * 16; }
 
+// k_orient_desc's tables as its four-keypoint form builds them in every workgroup (thread i of 256): test i of the sampling
+// pattern as floats, and for item i = (row i >> 3, dword i & 7) of the IC_Angle patch the byte weights u + 16 and the flags of
+// the bytes inside the disc, |u| <= umax[|v|] (v = row - 15; row 31 is loaded and carries none)
+static const int8_t kPatternHost[1024] = {
+#include "brief_pattern.inc"
+};
+static void build_orient_tables(const int umax[16], OrientTables& t)
+{
+    for (int i = 0; i < 256; i++) {
+        t.spat[i] = make_float4((float)kPatternHost[4 * i], (float)kPatternHost[4 * i + 1], (float)kPatternHost[4 * i + 2], (float)kPatternHost[4 * i + 3]);
+        const int v = (i >> 3) - kHalfPatch, u0 = 4 * (i & 7) - 16;
+        const int d = i < 248 ? umax[(v < 0 ? -v : v) & 15] : -1;
+        uint32_t wu = 0, w1 = 0;
+        for (int j = 0; j < 4; j++) {
+            const int u = u0 + j;
+            if (u >= -d && u <= d) { wu |= (uint32_t)(u + 16) << (8 * j); w1 |= 1u << (8 * j); }
+        }
+        t.swu[i] = wu; t.sw1[i] = w1;
+    }
+}
+
 static int build_geometry(const orbx_handle* h, int w, int h0, HostGeom& out)
 {
     Geom& g = out.g;

@@ -1881,21 +1881,36 @@ constexpr DiscItems make_disc_items()
 __device__ const DiscItems kDisc = make_disc_items();
 static_assert(make_disc_items().n <= kDiscLoads * 64 && make_disc_items().n > (kDiscLoads - 1) * 64, "five loads, not four");
 
-// Four keypoints per wave, one per quarter-wave (16 lanes): about half of a keypoint's instructions are
-// quarter-uniform (level and slot bookkeeping, fastAtan2, the binary64 sin/cos, the keypoint record) and cost a
-// full wave instruction however many lanes need them, so one wave now pays them for four keypoints.
-//  * IC_Angle: the 31 x 32 patch as 248 (row, dword) items, 16 per lane, unaligned dword loads all in flight;
+// The block's tables depend on the sampling pattern and on umax alone, both fixed for a handle: the throughput form copies them
+// from a device block made at create time (they lie behind the handle's Geom, orient_tables) instead of building them in every
+// workgroup.  spat: 256 tests x (x0, y0, x1, y1); swu / sw1 per IC_Angle item (row, dword): byte weights u + 16 (0 outside
+// the disc) and disc flags.  build_orient_tables (host) and the KPW = 4 kernel's own build state the same rule.
+struct OrientTables { float4 spat[256]; uint32_t swu[256], sw1[256]; };
+static_assert(sizeof(Geom) % 16 == 0 && sizeof(OrientTables) == 6144, "the tables follow the Geom block, 16-byte aligned");
+__device__ __forceinline__ const OrientTables* orient_tables(const Geom* g) { return (const OrientTables*)(g + 1); }
+
+// KPW keypoints per wave, one per 64 / KPW lanes: about half of a keypoint's instructions are uniform over those lanes
+// (level and slot bookkeeping, fastAtan2, the binary64 sin/cos, the keypoint record) and cost a full wave instruction
+// however many lanes need them, so one wave pays them for KPW keypoints.  KPW = 4 (256 threads) is the latency chain's: a
+// frame or two want many short waves; KPW = 8 (128 threads, the same 16 keypoints and LDS per block) is the throughput path's.
+//  * IC_Angle: the 31 x 32 patch as 248 (row, dword) items, unaligned dword loads all in flight;
 //    the masked moments are v_dot4_u32_u8 sums against per-item byte weights kept in LDS:
-//    m10 = sum dot4(px, u + 16) - 16 * sum dot4(px, 1), m01 = sum v * dot4(px, 1); butterfly over 16 lanes.
-//  * steered BRIEF: lane j of the quarter owns tests j, j + 16, ...; one ballot serves the four keypoints, its
-//    16-bit field of the quarter is descriptor word t, parked in lane t and stored as 16 x 2 bytes.
-__global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g, FrameSrc src, KpBlocks kb,
+//    m10 = sum dot4(px, u + 16) - 16 * sum dot4(px, 1), m01 = sum v * dot4(px, 1); reduce-scatter over the wave.
+//  * steered BRIEF: lane j of a keypoint's lanes owns tests j, j + 64 / KPW, ...; one ballot serves the wave's keypoints.
+//    KPW = 4: the ballot's 16-bit field of the quarter is descriptor word t, parked in lane t and stored as 16 x 2 bytes.
+//    KPW = 8: its 8-bit field of the eighth is descriptor byte t; lane j collects bytes 4j .. 4j + 3 = descriptor dword j.
+template <int KPW>
+__global__ __launch_bounds__(kKpPerBlock / KPW * 64) void k_orient_desc(const Geom* __restrict__ g, FrameSrc src, KpBlocks kb,
                                                     const uint64_t* __restrict__ kept,
                                                     const int32_t* __restrict__ keptCount,
                                                     OrbxKeyPointDev* __restrict__ outKps,
                                                     uint8_t* __restrict__ outDesc, int32_t* __restrict__ outCount, int nframes,
                                                     uint8_t* __restrict__ outX, int64_t xPitch, int64_t xAngOff)
 {
+    static_assert(KPW == 4 || KPW == 8, "a quarter or an eighth of the wave per keypoint");
+    constexpr int EL = 64 / KPW, ELSH = KPW == 4 ? 4 : 3;   // lanes per keypoint
+    constexpr int NT = kKpPerBlock / KPW * 64;              // threads of the block
+    static_assert(NT == 256 || (KPW == 8 && NT == 128), "the tables' 256 entries are built by 256 threads, or copied by 128 or 256");
 #if ORBX_DESC_PRIO
     __builtin_amdgcn_s_setprio(ORBX_DESC_PRIO);
 #endif
@@ -1911,23 +1926,38 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
     constexpr int PR = kDiscR, PDW = 10, PROWS = 2 * PR + 1;  // blurred patch: rows cy-18 .. cy+18, bytes cx-18 .. cx+21, of which the disc is fetched
     __shared__ uint32_t spatch[kKpPerBlock][PROWS * PDW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q = lane >> 4, ql = lane & 15;
+    const int q = lane >> ELSH, ql = lane & (EL - 1);
     int bx, fr;
     if (!xcd_block_frame(nframes, bx, fr)) return;
     const int f = fr + src.f0;
-    // The wave's life is a chain of memory latencies (pattern table -> counts -> record -> patches).  The first three
+    // The wave's life is a chain of memory latencies (tables -> counts -> record -> patches).  The first three
     // are independent and issued together (the record is read unconditionally -- the block grid stays inside the
     // frame's kept segment + slack -- and masked afterwards); the patch loads go out as soon as the record is in, and
     // the block's tables and their barrier are built underneath them.
     int l = 0;
     while (l + 1 < g->nlevels && bx >= kb.base[l + 1]) l++;
-    const int idx = (bx - kb.base[l]) * kKpPerBlock + wave * 4 + q;
+    const int idx = (bx - kb.base[l]) * kKpPerBlock + wave * KPW + q;
     const int nl = g->nlevels;
     const LevelGeom& L = g->lv[l];
     const uint64_t rec0 = kept[(int64_t)f * g->keptFrameRecs + L.keptOff + idx];
-    int32_t pk = ((const int32_t*)d_pattern)[tid];
-    const int tv = (tid >> 3) - kHalfPatch;
-    int um = g->umax[(tv < 0 ? -tv : tv) & 15];
+    int32_t pk = 0;
+    int um = 0;
+    float4 tp0, tp1;   // KPW = 8: this thread's share of the create-time tables
+    uint2 twu, tw1;
+    if constexpr (KPW == 4) {
+        pk = ((const int32_t*)d_pattern)[tid];
+        const int tv = (tid >> 3) - kHalfPatch;
+        um = g->umax[(tv < 0 ? -tv : tv) & 15];
+    } else {
+        const OrientTables* const T = orient_tables(g);
+        if constexpr (NT == 128) {
+            tp0 = T->spat[tid]; tp1 = T->spat[tid + 128];
+            twu = ((const uint2*)T->swu)[tid]; tw1 = ((const uint2*)T->sw1)[tid];
+        } else {
+            tp0 = tp1 = T->spat[tid];
+            twu.x = twu.y = T->swu[tid]; tw1.x = tw1.y = T->sw1[tid];
+        }
+    }
     int before = 0, totalAll = 0, mine = 0;
     for (int i = 0; i < nl; i++) {
         const int c = keptCount[f * nl + i];
@@ -1941,10 +1971,17 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
     int ditem[kDiscLoads];
 #pragma unroll
     for (int i = 0; i < kDiscLoads; i++) ditem[i] = kDisc.rc[64 * i + lane];
-    asm volatile("" : "+v"(pk), "+v"(um), "+v"(ditem[0]), "+v"(ditem[1]), "+v"(ditem[2]), "+v"(ditem[3]), "+v"(ditem[4]));  // landed here: no compiler-tracked load is in flight next to the untracked ones below
-    static_assert(kDiscLoads == 5, "operand list above");
+    // landed here: no compiler-tracked load is in flight next to the untracked ones below
+    if constexpr (KPW == 4) {
+        asm volatile("" : "+v"(pk), "+v"(um), "+v"(ditem[0]), "+v"(ditem[1]), "+v"(ditem[2]), "+v"(ditem[3]), "+v"(ditem[4]));
+    } else {
+        asm volatile("" : "+v"(tp0.x), "+v"(tp0.y), "+v"(tp0.z), "+v"(tp0.w), "+v"(tp1.x), "+v"(tp1.y), "+v"(tp1.z), "+v"(tp1.w),
+                          "+v"(twu.x), "+v"(twu.y), "+v"(tw1.x), "+v"(tw1.y),
+                          "+v"(ditem[0]), "+v"(ditem[1]), "+v"(ditem[2]), "+v"(ditem[3]), "+v"(ditem[4]));
+    }
+    static_assert(kDiscLoads == 5, "operand lists above");
     const int o = before + idx;
-    const bool active = idx < mine && o < g->maxKp;   // uniform over the quarter
+    const bool active = idx < mine && o < g->maxKp;   // uniform over the keypoint's lanes
     const bool anyActive = __builtin_amdgcn_ballot_w64(active) != 0;
     OSTAMP();
     const uint64_t rec = active ? rec0 : 0;
@@ -1953,10 +1990,10 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
     const uint8_t* img = level_ptr(g, src, f, l, stride);
     const int bs = L.blurStride;
     const uint8_t* blur = src.blur + (int64_t)f * g->blurFrameBytes + L.blurOff;
-    const int ctrOff = cy * stride + cx, bctrOff = cy * bs + cx;  // uniform over the quarter
+    const int ctrOff = cy * stride + cx, bctrOff = cy * bs + cx;  // uniform over the keypoint's lanes
 
     OSTAMP();
-    // Both patches of the wave's four keypoints are fetched by ALL 64 lanes, one keypoint after the other: the lane ->
+    // Both patches of the wave's keypoints are fetched by ALL 64 lanes, one keypoint after the other: the lane ->
     // (row, dword) map is then the same for every load, the keypoint's origin is a scalar (v_readlane) and the loads
     // take the SGPR-base form -- no per-load vector address arithmetic (it was a quarter of this kernel's instructions).
     //  * IC_Angle patch: rows cy-15 .. cy+16 x 8 dwords from cx-16, 8 rows per load (row cy+16 carries zero weights)
@@ -1964,19 +2001,19 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
     //    does not depend on the angle, so it is in flight during the moments and lands in LDS before the trigonometry.
     // (16 bytes per lane -- 12 loads instead of 44 -- is slower: the patch origins have byte alignment, and what bounds
     // the kernel is the ~90 cache lines a keypoint touches, not the number of load instructions.)
-    uint32_t dw[4][4];
+    uint32_t dw[KPW][4];
     if (anyActive) {
         const uint32_t voff = (uint32_t)((lane >> 3) * stride + 4 * (lane & 7));
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint8_t* pk = img + (__builtin_amdgcn_readlane(ctrOff, 16 * k) - kHalfPatch * stride - 16);
+        for (int k = 0; k < KPW; k++) {
+            const uint8_t* pk = img + (__builtin_amdgcn_readlane(ctrOff, EL * k) - kHalfPatch * stride - 16);
 #pragma unroll
             for (int j = 0; j < 4; j++) gload_sbase(dw[k][j], voff, pk + 8 * j * stride);
         }
     }
-    // the blurred disc, five loads per keypoint; an idle quarter repeats keypoint 0 (always live)
+    // the blurred disc, five loads per keypoint; idle lanes repeat keypoint 0 (always live)
     constexpr int NPI = kDiscLoads;
-    uint32_t pd[4][NPI];
+    uint32_t pd[KPW][NPI];
     int sidx[NPI];
     if (anyActive) {
         uint32_t voff[NPI];
@@ -1987,15 +2024,15 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
             sidx[i] = r * PDW + c;
         }
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int so = __builtin_amdgcn_readlane((int)active, 16 * k) ? __builtin_amdgcn_readlane(bctrOff, 16 * k) : __builtin_amdgcn_readlane(bctrOff, 0);
+        for (int k = 0; k < KPW; k++) {
+            const int so = __builtin_amdgcn_readlane((int)active, EL * k) ? __builtin_amdgcn_readlane(bctrOff, EL * k) : __builtin_amdgcn_readlane(bctrOff, 0);
             const uint8_t* pk = blur + (so - PR * bs - PR);
 #pragma unroll
             for (int i = 0; i < NPI; i++) gload_sbase(pd[k][i], voff[i], pk);
         }
     }
-    // the block's tables are built while the patches are in flight
-    {
+    // the block's tables go into LDS while the patches are in flight
+    if constexpr (KPW == 4) {
         spat[tid] = make_float4((float)(int8_t)(pk & 0xFF), (float)(int8_t)((pk >> 8) & 0xFF),
                                 (float)(int8_t)((pk >> 16) & 0xFF), (float)(int8_t)((pk >> 24) & 0xFF));
         const int u0 = 4 * (tid & 7) - 16;
@@ -2007,19 +2044,36 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
             if (u >= -d && u <= d) { wu |= (uint32_t)(u + 16) << (8 * j); w1 |= 1u << (8 * j); }
         }
         swu[tid] = wu; sw1[tid] = w1;
+    } else {
+        if constexpr (NT == 128) {
+            spat[tid] = tp0; spat[tid + 128] = tp1;
+            ((uint2*)swu)[tid] = twu; ((uint2*)sw1)[tid] = tw1;
+        } else {
+            spat[tid] = tp0; swu[tid] = twu.x; sw1[tid] = tw1.x;
+        }
     }
     __syncthreads();
     if (!anyActive) return;
     OSTAMP();
     // IC_Angle: m10 = sum u I, m01 = sum v I over the disc, as v_dot4_u32_u8 sums against byte weights u + 16, v + 16
-    // and the disc flags (one set of weights per lane serves the four keypoints)
+    // and the disc flags (one set of weights per lane serves every keypoint of the wave)
     int m10, m01;
-    asm volatile("s_waitcnt vmcnt(20)"  // the 16 IC_Angle dwords are in; the 20 patch dwords may still be in flight
-                 : "+v"(dw[0][0]), "+v"(dw[0][1]), "+v"(dw[0][2]), "+v"(dw[0][3]), "+v"(dw[1][0]), "+v"(dw[1][1]), "+v"(dw[1][2]), "+v"(dw[1][3]),
-                   "+v"(dw[2][0]), "+v"(dw[2][1]), "+v"(dw[2][2]), "+v"(dw[2][3]), "+v"(dw[3][0]), "+v"(dw[3][1]), "+v"(dw[3][2]), "+v"(dw[3][3]));
-    static_assert(4 * NPI == 20, "vmcnt above");
+    // the IC_Angle dwords are in; the KPW x NPI patch dwords may still be in flight
+    if constexpr (KPW == 4) {
+        asm volatile("s_waitcnt vmcnt(20)"
+                     : "+v"(dw[0][0]), "+v"(dw[0][1]), "+v"(dw[0][2]), "+v"(dw[0][3]), "+v"(dw[1][0]), "+v"(dw[1][1]), "+v"(dw[1][2]), "+v"(dw[1][3]),
+                       "+v"(dw[2][0]), "+v"(dw[2][1]), "+v"(dw[2][2]), "+v"(dw[2][3]), "+v"(dw[3][0]), "+v"(dw[3][1]), "+v"(dw[3][2]), "+v"(dw[3][3]));
+    } else {
+        asm volatile("s_waitcnt vmcnt(40)"
+                     : "+v"(dw[0][0]), "+v"(dw[0][1]), "+v"(dw[0][2]), "+v"(dw[0][3]), "+v"(dw[1][0]), "+v"(dw[1][1]), "+v"(dw[1][2]), "+v"(dw[1][3]),
+                       "+v"(dw[2][0]), "+v"(dw[2][1]), "+v"(dw[2][2]), "+v"(dw[2][3]), "+v"(dw[3][0]), "+v"(dw[3][1]), "+v"(dw[3][2]), "+v"(dw[3][3]));
+        asm volatile(""  // (an asm statement takes 30 operands: the other half of the list, behind the same wait)
+                     : "+v"(dw[4][0]), "+v"(dw[4][1]), "+v"(dw[4][2]), "+v"(dw[4][3]), "+v"(dw[5][0]), "+v"(dw[5][1]), "+v"(dw[5][2]), "+v"(dw[5][3]),
+                       "+v"(dw[6][0]), "+v"(dw[6][1]), "+v"(dw[6][2]), "+v"(dw[6][3]), "+v"(dw[7][0]), "+v"(dw[7][1]), "+v"(dw[7][2]), "+v"(dw[7][3]));
+    }
+    static_assert(4 * NPI == 20 && 8 * NPI == 40, "vmcnt above");
     {
-        int A[4], B[4];
+        int A[KPW], B[KPW];
         uint32_t wu[4], w1[4], wv[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -2028,7 +2082,7 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
             wv[j] = w1[j] * (uint32_t)(8 * j + (lane >> 3) + 1);  // (v + 16) per flagged byte, v = row - 15
         }
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
+        for (int k = 0; k < KPW; k++) {
             uint32_t su = 0, sv = 0, s1 = 0;
 #pragma unroll
             for (int j = 0; j < 4; j++) {
@@ -2039,33 +2093,65 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
             A[k] = (int)su - 16 * (int)s1;
             B[k] = (int)sv - 16 * (int)s1;
         }
-        // reduce-scatter over the wave: v_permlane32_swap leaves keypoints {0,1} in lanes 0..31 and {2,3} in 32..63,
-        // v_permlane16_swap leaves keypoint q in quarter q; four row rotations finish the sum inside the quarter
         auto swap32 = [](int a, int b) { const auto r = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)b, false, false); return (int)(r[0] + r[1]); };
         auto swap16 = [](int a, int b) { const auto r = __builtin_amdgcn_permlane16_swap((unsigned)a, (unsigned)b, false, false); return (int)(r[0] + r[1]); };
-        m10 = swap16(swap32(A[0], A[2]), swap32(A[1], A[3]));
-        m01 = swap16(swap32(B[0], B[2]), swap32(B[1], B[3]));
-        m10 += __builtin_amdgcn_update_dpp(0, m10, 0x128, 0xF, 0xF, false);  // row_ror:8
-        m01 += __builtin_amdgcn_update_dpp(0, m01, 0x128, 0xF, 0xF, false);
-        m10 += __builtin_amdgcn_update_dpp(0, m10, 0x124, 0xF, 0xF, false);
-        m01 += __builtin_amdgcn_update_dpp(0, m01, 0x124, 0xF, 0xF, false);
-        m10 += __builtin_amdgcn_update_dpp(0, m10, 0x122, 0xF, 0xF, false);
-        m01 += __builtin_amdgcn_update_dpp(0, m01, 0x122, 0xF, 0xF, false);
-        m10 += __builtin_amdgcn_update_dpp(0, m10, 0x121, 0xF, 0xF, false);
-        m01 += __builtin_amdgcn_update_dpp(0, m01, 0x121, 0xF, 0xF, false);
+        if constexpr (KPW == 4) {
+            // reduce-scatter over the wave: v_permlane32_swap leaves keypoints {0,1} in lanes 0..31 and {2,3} in 32..63,
+            // v_permlane16_swap leaves keypoint q in quarter q; four row rotations finish the sum inside the quarter
+            m10 = swap16(swap32(A[0], A[2]), swap32(A[1], A[3]));
+            m01 = swap16(swap32(B[0], B[2]), swap32(B[1], B[3]));
+            m10 += __builtin_amdgcn_update_dpp(0, m10, 0x128, 0xF, 0xF, false);  // row_ror:8
+            m01 += __builtin_amdgcn_update_dpp(0, m01, 0x128, 0xF, 0xF, false);
+            m10 += __builtin_amdgcn_update_dpp(0, m10, 0x124, 0xF, 0xF, false);
+            m01 += __builtin_amdgcn_update_dpp(0, m01, 0x124, 0xF, 0xF, false);
+            m10 += __builtin_amdgcn_update_dpp(0, m10, 0x122, 0xF, 0xF, false);
+            m01 += __builtin_amdgcn_update_dpp(0, m01, 0x122, 0xF, 0xF, false);
+            m10 += __builtin_amdgcn_update_dpp(0, m10, 0x121, 0xF, 0xF, false);
+            m01 += __builtin_amdgcn_update_dpp(0, m01, 0x121, 0xF, 0xF, false);
+        } else {
+            // reduce-scatter of eight sums: v_permlane32_swap of (k, k + 4) leaves keypoint k in lanes 0..31 and k + 4 in 32..63;
+            // v_permlane16_swap of (j, j + 2) leaves keypoints j, j + 2, j + 4, j + 6 in rows 0..3, so the even keypoints' sums
+            // lie in one register and the odd ones' in the other, keypoint 2r + h in row r.  The split of a row: its half h
+            // keeps the register of parity h and adds the other half's lanes of the same register (which that half holds
+            // as ITS other register: one rotation by 8).  Three exchanges finish the sum inside the eighth.
+            const int e10 = swap16(swap32(A[0], A[4]), swap32(A[2], A[6])), o10 = swap16(swap32(A[1], A[5]), swap32(A[3], A[7]));
+            const int e01 = swap16(swap32(B[0], B[4]), swap32(B[2], B[6])), o01 = swap16(swap32(B[1], B[5]), swap32(B[3], B[7]));
+            const bool odd = (lane & 8) != 0;
+            m10 = (odd ? o10 : e10) + __builtin_amdgcn_update_dpp(0, odd ? e10 : o10, 0x128, 0xF, 0xF, false);  // row_ror:8
+            m01 = (odd ? o01 : e01) + __builtin_amdgcn_update_dpp(0, odd ? e01 : o01, 0x128, 0xF, 0xF, false);
+            m10 += __builtin_amdgcn_update_dpp(0, m10, 0x141, 0xF, 0xF, false);  // row_half_mirror: lane i <-> 7 - i
+            m01 += __builtin_amdgcn_update_dpp(0, m01, 0x141, 0xF, 0xF, false);
+            m10 += __builtin_amdgcn_update_dpp(0, m10, 0xB1, 0xF, 0xF, false);   // quad_perm:[1,0,3,2]
+            m01 += __builtin_amdgcn_update_dpp(0, m01, 0xB1, 0xF, 0xF, false);
+            m10 += __builtin_amdgcn_update_dpp(0, m10, 0x4E, 0xF, 0xF, false);   // quad_perm:[2,3,0,1]
+            m01 += __builtin_amdgcn_update_dpp(0, m01, 0x4E, 0xF, 0xF, false);
+        }
     }
     OSTAMP();
-    asm volatile("s_waitcnt vmcnt(0)"
-                 : "+v"(pd[0][0]), "+v"(pd[0][1]), "+v"(pd[0][2]), "+v"(pd[0][3]), "+v"(pd[0][4]),
-                   "+v"(pd[1][0]), "+v"(pd[1][1]), "+v"(pd[1][2]), "+v"(pd[1][3]), "+v"(pd[1][4]),
-                   "+v"(pd[2][0]), "+v"(pd[2][1]), "+v"(pd[2][2]), "+v"(pd[2][3]), "+v"(pd[2][4]),
-                   "+v"(pd[3][0]), "+v"(pd[3][1]), "+v"(pd[3][2]), "+v"(pd[3][3]), "+v"(pd[3][4]));
-    static_assert(NPI == 5, "operand list above");
+    if constexpr (KPW == 4) {
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(pd[0][0]), "+v"(pd[0][1]), "+v"(pd[0][2]), "+v"(pd[0][3]), "+v"(pd[0][4]),
+                       "+v"(pd[1][0]), "+v"(pd[1][1]), "+v"(pd[1][2]), "+v"(pd[1][3]), "+v"(pd[1][4]),
+                       "+v"(pd[2][0]), "+v"(pd[2][1]), "+v"(pd[2][2]), "+v"(pd[2][3]), "+v"(pd[2][4]),
+                       "+v"(pd[3][0]), "+v"(pd[3][1]), "+v"(pd[3][2]), "+v"(pd[3][3]), "+v"(pd[3][4]));
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(pd[0][0]), "+v"(pd[0][1]), "+v"(pd[0][2]), "+v"(pd[0][3]), "+v"(pd[0][4]),
+                       "+v"(pd[1][0]), "+v"(pd[1][1]), "+v"(pd[1][2]), "+v"(pd[1][3]), "+v"(pd[1][4]),
+                       "+v"(pd[2][0]), "+v"(pd[2][1]), "+v"(pd[2][2]), "+v"(pd[2][3]), "+v"(pd[2][4]),
+                       "+v"(pd[3][0]), "+v"(pd[3][1]), "+v"(pd[3][2]), "+v"(pd[3][3]), "+v"(pd[3][4]));
+        asm volatile(""
+                     : "+v"(pd[4][0]), "+v"(pd[4][1]), "+v"(pd[4][2]), "+v"(pd[4][3]), "+v"(pd[4][4]),
+                       "+v"(pd[5][0]), "+v"(pd[5][1]), "+v"(pd[5][2]), "+v"(pd[5][3]), "+v"(pd[5][4]),
+                       "+v"(pd[6][0]), "+v"(pd[6][1]), "+v"(pd[6][2]), "+v"(pd[6][3]), "+v"(pd[6][4]),
+                       "+v"(pd[7][0]), "+v"(pd[7][1]), "+v"(pd[7][2]), "+v"(pd[7][3]), "+v"(pd[7][4]));
+    }
+    static_assert(NPI == 5, "operand lists above");
     // park the blurred discs
 #pragma unroll
-    for (int k = 0; k < 4; k++)
+    for (int k = 0; k < KPW; k++)
 #pragma unroll
-        for (int i = 0; i < NPI; i++) spatch[wave * 4 + k][sidx[i]] = pd[k][i];
+        for (int i = 0; i < NPI; i++) spatch[wave * KPW + k][sidx[i]] = pd[k][i];
     const float angle = fast_atan2_deg((float)m01, (float)m10);
 
     // steered BRIEF on the blurred level
@@ -2080,7 +2166,7 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
     // v_mad_i32_i24 reads exactly those, and the biases are folded into the patch offset.
     const uint8_t* const sp8 = (const uint8_t*)&spatch[0][0];
     constexpr float kRnd = 12582912.f;  // 0x4B400000
-    const uint32_t adj = (uint32_t)((wave * 4 + q) * (PROWS * PDW * 4) + PR * (PDW * 4) + PR) - 0x400000u * (uint32_t)(PDW * 4) - 0x4B400000u;
+    const uint32_t adj = (uint32_t)((wave * KPW + q) * (PROWS * PDW * 4) + PR * (PDW * 4) + PR) - 0x400000u * (uint32_t)(PDW * 4) - 0x4B400000u;
     static_assert(PDW * 4 == 40, "row pitch is an inline constant of the mad below");
     uint32_t myWord = 0;
     // Round 5: the rotation of a sample point as four packed-fp32 instructions instead of eight scalar ones.  v_pk_mul_f32 /
@@ -2098,9 +2184,11 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
         asm("v_pk_add_f32 %0, %1, %2" : "=v"(Z) : "v"(W), "v"(KR));
         rx = __float_as_int(Z.x); ry = __float_as_int(Z.y);
     };
+    [[maybe_unused]] const uint32_t balShift = 8 * (q & 3);   // KPW = 8: the eighth's byte inside its half of the ballot
+    [[maybe_unused]] uint32_t collect = 0;
 #pragma unroll
-    for (int t = 0; t < 16; t++) {
-        const float4 pt = spat[ql + 16 * t];
+    for (int t = 0; t < 256 / EL; t++) {
+        const float4 pt = spat[ql + EL * t];
         int rx0, ry0, rx1, ry1;
         rot(f2v{pt.x, pt.y}, rx0, ry0);
         rot(f2v{pt.z, pt.w}, rx1, ry1);
@@ -2109,8 +2197,17 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
         asm("v_mad_i32_i24 %0, %1, 40, %2" : "=v"(o1) : "v"(ry1), "v"(rx1));
         const int t0 = sp8[o0 + adj], t1 = sp8[o1 + adj];
         const uint64_t bal = __builtin_amdgcn_ballot_w64(t0 < t1);
-        const uint32_t w16 = (uint32_t)(bal >> (16 * q)) & 0xFFFFu;  // tests 16t .. 16t+15 of this quarter's keypoint
-        if (ql == t) myWord = w16;
+        if constexpr (KPW == 4) {
+            const uint32_t w16 = (uint32_t)(bal >> (16 * q)) & 0xFFFFu;  // tests 16t .. 16t+15 of this quarter's keypoint
+            if (ql == t) myWord = w16;
+        } else {
+            const uint32_t half = q >= 4 ? (uint32_t)(bal >> 32) : (uint32_t)bal;
+            collect |= ((half >> balShift) & 0xFFu) << (8 * (t & 3));    // tests 8t .. 8t+7 of this eighth's keypoint = descriptor byte t
+            if ((t & 3) == 3) {
+                if (ql == (t >> 2)) myWord = collect;
+                collect = 0;
+            }
+        }
     }
     OSTAMP();
 #ifdef ORBX_ORIENT_TIMING
@@ -2118,44 +2215,57 @@ __global__ __launch_bounds__(256) void k_orient_desc(const Geom* __restrict__ g,
         printf("ORIENT bx %d l %d: barrier %.2f counts %.2f rec %.2f moments %.2f trig %.2f brief %.2f us\n", bx, l, (ts[1]-ts[0])/100.0, (ts[2]-ts[1])/100.0, (ts[3]-ts[2])/100.0, (ts[4]-ts[3])/100.0, (ts[5]-ts[4])/100.0, (ts[6]-ts[5])/100.0);
 #endif
     // The +-1 form the stream matcher's matrix-core scan reads (orbm_kernels.hip: E2M1 nibbles in MFMA tile order, 128 bytes
-    // per descriptor), written here instead of by a launch of its own (k_expand_desc: 41 MB of traffic and a kernel per step).
-    // The wave's four descriptors go through its OWN patch words in LDS (no block barrier: nobody else reads them), then
-    // lane (keypoint kq, 32-bit chunk c) expands one chunk to 16 bytes at block (o >> 5), item c * 32 + (o & 31).
-    if (outX) {
-        uint16_t* const sw = (uint16_t*)&spatch[wave * 4 + q][0];
-        sw[ql] = (uint16_t)myWord;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int kq = (lane >> 3) & 3, c = lane & 7;
-        const int oq = __shfl(o, 16 * kq);
-        const bool aq = __shfl((int)active, 16 * kq) != 0;
-        if (lane < 32 && aq) {
-            const uint32_t bits = spatch[wave * 4 + kq][c];
-            auto pm1 = [](uint32_t b8) {  // 8 bits -> 8 nibbles, set = +1 (0x2), clear = -1 (0xA)
-                uint32_t x = (b8 | (b8 << 12)) & 0x000F000Fu;
-                x = (x | (x << 6)) & 0x03030303u;
-                x = (x | (x << 3)) & 0x11111111u;
-                return 0x22222222u | ((x ^ 0x11111111u) << 3);
-            };
-            const uint4 e = make_uint4(pm1(bits & 255), pm1((bits >> 8) & 255), pm1((bits >> 16) & 255), pm1(bits >> 24));
-            *(uint4*)(outX + (int64_t)f * xPitch + (int64_t)(oq >> 5) * 4096 + (int64_t)(c * 32 + (oq & 31)) * 16) = e;
+    // per descriptor), written here instead of by a launch of its own (k_expand_desc: 41 MB of traffic and a kernel per step):
+    // lane (keypoint, 32-bit chunk c) expands one chunk to 16 bytes at block (o >> 5), item c * 32 + (o & 31).
+    auto pm1 = [](uint32_t b8) {  // 8 bits -> 8 nibbles, set = +1 (0x2), clear = -1 (0xA)
+        uint32_t x = (b8 | (b8 << 12)) & 0x000F000Fu;
+        x = (x | (x << 6)) & 0x03030303u;
+        x = (x | (x << 3)) & 0x11111111u;
+        return 0x22222222u | ((x ^ 0x11111111u) << 3);
+    };
+    auto record = [&]() {
+        OrbxKeyPointDev kp;
+        kp.x = __fmul_rn((float)cx, L.scale);  // level 0: scale == 1.0f, identity (:1095-1101)
+        kp.y = __fmul_rn((float)cy, L.scale);
+        kp.size = L.kpSize;
+        kp.angle = angle;
+        kp.response = (float)cand_resp(rec);
+        kp.octave = l;
+        kp.class_id = -1;
+        outKps[(int64_t)f * g->maxKp + o] = kp;
+    };
+    if constexpr (KPW == 4) {
+        // The wave's four descriptors go through its OWN patch words in LDS (no block barrier: nobody else reads them), then
+        // lane (keypoint kq, chunk c) of the wave's first half expands.
+        if (outX) {
+            uint16_t* const sw = (uint16_t*)&spatch[wave * 4 + q][0];
+            sw[ql] = (uint16_t)myWord;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int kq = (lane >> 3) & 3, c = lane & 7;
+            const int oq = __shfl(o, 16 * kq);
+            const bool aq = __shfl((int)active, 16 * kq) != 0;
+            if (lane < 32 && aq) {
+                const uint32_t bits = spatch[wave * 4 + kq][c];
+                const uint4 e = make_uint4(pm1(bits & 255), pm1((bits >> 8) & 255), pm1((bits >> 16) & 255), pm1(bits >> 24));
+                *(uint4*)(outX + (int64_t)f * xPitch + (int64_t)(oq >> 5) * 4096 + (int64_t)(c * 32 + (oq & 31)) * 16) = e;
+            }
         }
-    }
-    if (active) {
-        ((uint16_t*)(outDesc + ((int64_t)f * g->maxKp + o) * 32))[ql] = (uint16_t)myWord;
-        if (ql == 1 && outX) *(float*)(outX + (int64_t)f * xPitch + xAngOff + (int64_t)o * 4) = angle;   // the stream matcher's compact angle array
-        if (ql == 0) {
-            OrbxKeyPointDev kp;
-            kp.x = __fmul_rn((float)cx, L.scale);  // level 0: scale == 1.0f, identity (:1095-1101)
-            kp.y = __fmul_rn((float)cy, L.scale);
-            kp.size = L.kpSize;
-            kp.angle = angle;
-            kp.response = (float)cand_resp(rec);
-            kp.octave = l;
-            kp.class_id = -1;
-            outKps[(int64_t)f * g->maxKp + o] = kp;
+        if (active) {
+            ((uint16_t*)(outDesc + ((int64_t)f * g->maxKp + o) * 32))[ql] = (uint16_t)myWord;
+            if (ql == 1 && outX) *(float*)(outX + (int64_t)f * xPitch + xAngOff + (int64_t)o * 4) = angle;   // the stream matcher's compact angle array
+            if (ql == 0) record();
         }
+    } else if (active) {
+        // (keypoint 0..7) x (chunk 0..7) is the wave: every lane already holds the chunk it expands, its descriptor dword
+        if (outX) {
+            const uint4 e = make_uint4(pm1(myWord & 255), pm1((myWord >> 8) & 255), pm1((myWord >> 16) & 255), pm1(myWord >> 24));
+            *(uint4*)(outX + (int64_t)f * xPitch + (int64_t)(o >> 5) * 4096 + (int64_t)(ql * 32 + (o & 31)) * 16) = e;
+            if (ql == 1) *(float*)(outX + (int64_t)f * xPitch + xAngOff + (int64_t)o * 4) = angle;
+        }
+        ((uint32_t*)(outDesc + ((int64_t)f * g->maxKp + o) * 32))[ql] = myWord;
+        if (ql == 0) record();
     }
 }
 

@@ -164,7 +164,8 @@ struct Launcher {
     }
     // The output slots of `set` were read by the matching two batches back and by its download (host path); a wait is
     // only enqueued when that work sits on another stream (every cross-stream wait costs microseconds of latency).
-    int desc(hipStream_t s, int set, hipEvent_t done = nullptr) const
+    // lat as for blur: such a call keeps four keypoints per wave on 256 threads, every other one runs eight on 128
+    int desc(hipStream_t s, int set, hipEvent_t done = nullptr, bool lat = false) const
     {
         if (h->matchPending[set] && h->matchStream[set] != s) HIPCHK(hipStreamWaitEvent(s, h->evMatch[set], 0));
         if (h->evOutOfSet[set] && h->outStream[set] != s) HIPCHK(hipStreamWaitEvent(s, h->evOutOfSet[set], 0));
@@ -172,8 +173,8 @@ struct Launcher {
         h->evExtReader[set].clear();  // this stream is behind them now, and it is the only writer of the set
         // the +-1 form of the descriptors for the matrix-core scan, slot f + 1 of the set (frames src.f0 ..)
         uint8_t* const xOut = h->fuseExpand ? r_xdesc(h, set) + (size_t)h->xPitch : nullptr;   // (the kernel adds frame * xPitch, like frame * maxKp for the others)
-        return launch_done(h, P_ORIENT_DESC, k_orient_desc, dim3(h->kpBlocksTotal, xcd_grid_y(nb)), dim3(256), 0, s, done, h->d_geom, src, h->kpBlocks, h->d_kept,
-                           h->d_keptCount, r_kps(h, set) + h->maxKp, r_desc(h, set) + (size_t)h->maxKp * 32, r_count(h, set) + 1, nb, xOut, h->xPitch, h->xAngOff);
+        return launch_done(h, P_ORIENT_DESC, lat ? k_orient_desc<4> : k_orient_desc<8>, dim3(h->kpBlocksTotal, xcd_grid_y(nb)), dim3(kKpPerBlock / (lat ? 4 : 8) * 64), 0, s, done, h->d_geom, src,
+                           h->kpBlocks, h->d_kept, h->d_keptCount, r_kps(h, set) + h->maxKp, r_desc(h, set) + (size_t)h->maxKp * 32, r_count(h, set) + 1, nb, xOut, h->xPitch, h->xAngOff);
     }
 };
 
@@ -294,7 +295,7 @@ static int run_extract(orbx_handle* h, const uint8_t* d_imgs, int B, int w, int 
             HIPCHK(hipEventRecord(h->evFast0[0], sa));  // the aux chain is through
             HIPCHK(hipStreamWaitEvent(sm, h->evFast0[0], 0));
         }
-        if ((rc = L.desc(sm, set, lazyDone ? nullptr : h->evPart[0]))) return rc;
+        if ((rc = L.desc(sm, set, lazyDone ? nullptr : h->evPart[0], true))) return rc;
         h->lastParts = 1; h->partLazy = lazyDone; h->partEverRan[0] = true;
     } else {
         for (int part = 0; part < nsplit; part++) {
@@ -332,7 +333,7 @@ static int run_extract(orbx_handle* h, const uint8_t* d_imgs, int B, int w, int 
             if (splitFast) HIPCHK(hipStreamWaitEvent(s, h->evFast0[part], 0));
             L.dist(s, 0, g.nlevels);
             HIPCHK(hipStreamWaitEvent(s, h->evBlur[part], 0));
-            if ((rc = L.desc(s, set))) return rc;
+            if ((rc = L.desc(s, set, nullptr, B <= h->latMaxB))) return rc;
             HIPCHK(hipEventRecord(h->evPart[h->lastParts++], s));
             h->partEverRan[part] = true;
         }

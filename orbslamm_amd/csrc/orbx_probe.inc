@@ -231,7 +231,7 @@ extern "C" int orbx_debug_pair_overlap(orbx_t* h, int nb, float target_ms, int* 
         const size_t fl = fast_lds_bytes(h->tileRows, h->tileStrideDw, h->fastSmapPitch, h->fastListCap);
         const int nqb = (h->maxKp + orbm::kMfmaRowsPerBlock - 1) / orbm::kMfmaRowsPerBlock;
         const int32_t l[K] = {(int32_t)pl, (int32_t)fl, (int32_t)(dist_lds_bytes(h->nodeCap, g.maxCellsPerLevel) + 5552), (kBlurWalkInWords + kBlurMfmaOutWords) * 4, 31104, orbm::kMfmaLdsBytes};
-        const int32_t t[K] = {256, 64, kDistThreads, 256, 256, 256};
+        const int32_t t[K] = {256, 64, kDistThreads, 256, kKpPerBlock / 8 * 64, 256};
         const int32_t w[K] = {h->pyrBlocks * nb, g.totalCells * nb, g.nlevels * nb, h->blurRuns.base[g.nlevels] * nb, h->kpBlocksTotal * nb, nqb * nb};
         for (int k = 0; k < K; k++) { lds_bytes[k] = l[k]; wg_threads[k] = t[k]; wgs[k] = w[k]; }
     }

@@ -253,7 +253,14 @@ static int create_handle(const OrbxParams* params, int max_w, int max_h, int max
     h->candCapFrame = (size_t)hg.g.candFrameRecs + 1024;
     h->keptCapFrame = (size_t)hg.g.keptFrameRecs + 64;
     h->maxKp = hg.g.maxKp + 64;
-    HIPCHK_OR(dev_alloc(h, h->d_geom, sizeof(Geom)), undo());
+    // the geometry block, and behind it k_orient_desc's tables: they depend on the pattern and on umax alone, so they are made
+    // here once (configure_shape rewrites the Geom in front of them for every new shape)
+    HIPCHK_OR(dev_alloc(h, h->d_geom, sizeof(Geom) + sizeof(OrientTables)), undo());
+    {
+        OrientTables ot;
+        build_orient_tables(h->umax, ot);
+        HIPCHK_OR(hipMemcpy(h->d_geom + 1, &ot, sizeof ot, hipMemcpyHostToDevice), undo());
+    }
     HIPCHK_OR(dev_alloc(h, h->d_cells, h->cellsCap * sizeof(Cell)), undo());
     HIPCHK_OR(dev_alloc(h, h->d_tabs, h->tabsCap * sizeof(short4)), undo());
     h->pyrRangesCap = 64 * ORBX_MAXL;
