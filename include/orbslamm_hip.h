@@ -978,4 +978,8 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 /* Optimizer::OptimizeSim3: the batched 7-dof Levenberg for loop and merge candidates (orbz_optimize_sim3) is the same
  * library's and is declared in orbslamm_sim3opt.h. */
 #include "orbslamm_sim3opt.h"
+
+/* Tracking::SearchLocalPoints and TrackWithMotionModel's projections from a map-point pool in HBM (orbw_pool_*,
+ * orbw_view_project, orbw_track_local_map, orbw_track_frame_pose) are the same library's and are declared in orbslamm_mappool.h. */
+#include "orbslamm_mappool.h"
 #endif

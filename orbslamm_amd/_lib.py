@@ -128,11 +128,17 @@ EXPORTS_SIM3OPT = [
     "orbz_optimize_sim3",
 ]
 
+# the map-point pool's block (include/orbslamm_mappool.h, which include/orbslamm_hip.h includes)
+EXPORTS_MAPPOOL = [
+    "orbw_pool_create", "orbw_pool_destroy", "orbw_pool_set", "orbw_pool_set_flags", "orbw_view_project", "orbw_view_project_frame",
+    "orbw_track_local_map", "orbw_track_frame_pose", "orbw_track_status",
+]
+
 
 def build(force=False):
     """hipcc the extension in-tree for gfx950 (cross-compiles without a GPU)."""
     deps = [os.path.join(_PKG, "csrc", f) for f in os.listdir(os.path.join(_PKG, "csrc"))]
-    deps += [os.path.join(_ROOT, "include", f) for f in ("orbslamm_hip.h", "orbslamm_fuse.h", "orbslamm_loopfuse.h", "orbslamm_poseopt.h", "orbslamm_sim3opt.h")]
+    deps += [os.path.join(_ROOT, "include", f) for f in ("orbslamm_hip.h", "orbslamm_fuse.h", "orbslamm_loopfuse.h", "orbslamm_poseopt.h", "orbslamm_sim3opt.h", "orbslamm_mappool.h")]
     if not force and os.path.exists(SO_PATH) and all(os.path.getmtime(SO_PATH) >= os.path.getmtime(d) for d in deps):
         return SO_PATH
     cmd = ["hipcc"] + HIPCC_FLAGS + ["-o", SO_PATH, SRC]
@@ -178,7 +184,7 @@ def lib():
         L = C.CDLL(os.environ.get("ORBSLAMM_HIP_LIB") or SO_PATH)
         L.orbx_last_error.restype = C.c_char_p
         L.orbx_scale_factor.restype = C.c_float
-        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP + EXPORTS_LOCALMAP + EXPORTS_FUSE + EXPORTS_LOOPFUSE + EXPORTS_POSEOPT + EXPORTS_SIM3OPT:
+        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP + EXPORTS_LOCALMAP + EXPORTS_FUSE + EXPORTS_LOOPFUSE + EXPORTS_POSEOPT + EXPORTS_SIM3OPT + EXPORTS_MAPPOOL:
             getattr(L, name)
         L.orbx_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _lib = L

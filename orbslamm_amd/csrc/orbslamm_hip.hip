@@ -51,6 +51,7 @@
 #include "orbc_kernels.hip"
 #include "orbo_kernels.hip"
 #include "orbz_kernels.hip"   // after orbo_kernels.hip: it uses its sin / cos, Huber and quaternion pieces
+#include "orbw_kernels.hip"   // the map-point pool and the projections of the two tracking searches
 
 using namespace orbx;
 
@@ -208,3 +209,4 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbc_host.inc"   // SearchAndFuse
 #include "orbo_host.inc"   // PoseOptimization
 #include "orbz_host.inc"   // OptimizeSim3
+#include "orbw_host.inc"   // the map-point pool: SearchLocalPoints and TrackWithMotionModel's search from resident MapPoints

@@ -371,6 +371,11 @@ struct ResultRecord {
     uint32_t qEpoch = 0;
     size_t total = 0;
     ProjPlan plan{};
+    // queries made on the device from a map-point pool (orbw_host.inc): `total` covers the block's head alone (pair record |
+    // occupancy), the query block behind it is the projection kernel's and stays as it left it -- a replay reads it again,
+    // not the pool; the status bytes lie at oStatus of the set's pinned share
+    bool fromPool = false;
+    size_t oStatus = 0;
 };
 struct ResultRing {   // kSets result sets in rotation: a caller may read up to kSets - 1 calls behind the newest
     static constexpr int kSets = 4;
@@ -718,6 +723,28 @@ static int track_queries_issue(orbm_frameset_t* fs, int set)
     return ORBX_OK;
 }
 
+// result set `set`'s share of the query staging (pinned block + device twin) holds `total` bytes and is free to be written
+static int query_block_take(orbm_frameset_t* fs, int set, size_t total)
+{
+    const ResultRecord& r = fs->res.rec[set];
+    if (total > fs->qBytes) {   // (first call, or a larger local map than any before: the only allocation, behind a drain)
+        HIPCHK(hipStreamSynchronize(fs_stream(fs)));
+        if (fs->h_q) HIPCHK(hipHostFree(fs->h_q));
+        if (fs->d_q) HIPCHK(hipFree(fs->d_q));
+        fs->h_q = nullptr; fs->d_q = nullptr; fs->qBytes = 0;
+        fs->qEpoch++;
+        const size_t want = (total * 3 / 2 + 4095) & ~(size_t)4095;
+        HIPCHK(hipHostMalloc(&fs->h_q, want * ResultRing::kSets, hipHostMallocCoherent));   // (read by the copy kernel where it lies)
+        HIPCHK(hipMalloc(&fs->d_q, want * ResultRing::kSets));
+        fs->qBytes = want;
+    } else if (r.ev && !flags_raised(r, set_tables(fs, set).flag)) {
+        // the search that last read this set's block (four calls ago) must be through: its flags say so without a runtime
+        // call (an event query costs tens of microseconds)
+        HIPCHK(hipEventSynchronize(r.ev));
+    }
+    return ORBX_OK;
+}
+
 // int ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>& vpMapPoints, const float th)   ORBmatcher.cc:45-129,
 // the search Tracking::SearchLocalPoints runs on every frame (Tracking.cc:1242-1249), with the frame resident in the set:
 // the local map's projections (Frame::isInFrustum, Frame.cc:269-325) go up in ONE pinned block, two launches follow on
@@ -742,21 +769,7 @@ static int track_queries(orbm_frameset_t* fs, int slot, int qslot, const OrbmPro
     const size_t oUvr = pk.take((size_t)nq * 12), oLvl = pk.take((size_t)nq * 2), oQd = qslot < 0 ? pk.take((size_t)nq * 32) : 0;
     const size_t oQv = qvalid ? pk.take((size_t)nq) : 0, oQo = q_obs_pos ? pk.take((size_t)nq) : 0, oOcc = t_occ ? pk.take(C) : 0;
     const size_t total = pk.off;
-    if (total > fs->qBytes) {   // (first call, or a larger local map than any before: the only allocation, behind a drain)
-        HIPCHK(hipStreamSynchronize(fs_stream(fs)));
-        if (fs->h_q) HIPCHK(hipHostFree(fs->h_q));
-        if (fs->d_q) HIPCHK(hipFree(fs->d_q));
-        fs->h_q = nullptr; fs->d_q = nullptr; fs->qBytes = 0;
-        fs->qEpoch++;
-        const size_t want = (total * 3 / 2 + 4095) & ~(size_t)4095;
-        HIPCHK(hipHostMalloc(&fs->h_q, want * ResultRing::kSets, hipHostMallocCoherent));   // (read by the copy kernel where it lies)
-        HIPCHK(hipMalloc(&fs->d_q, want * ResultRing::kSets));
-        fs->qBytes = want;
-    } else if (r.ev && !flags_raised(r, set_tables(fs, set).flag)) {
-        // the search that last read this set's block (four calls ago) must be through: its flags say so without a runtime
-        // call (an event query costs tens of microseconds)
-        HIPCHK(hipEventSynchronize(r.ev));
-    }
+    if ((rc = query_block_take(fs, set, total))) return rc;
     if ((rc = fs->res.begin(set))) return rc;
     ProjPlan& pl = r.plan;
     if ((rc = proj_lds_plan(fs->cap, nq, fs->ncell, pl))) return rc;
@@ -790,7 +803,7 @@ static int track_queries(orbm_frameset_t* fs, int slot, int qslot, const OrbmPro
     P.total = fs->d_total; P.candOff = fs->d_candOff; P.candCnt = fs->d_candCnt; query_arena(fs, P);
     P.qres = fs->d_qres; P.qscr = fs->d_qscr; P.tscr = c.big ? fs->d_tscr : nullptr;
     memcpy(hs + oPair, &P, sizeof P);
-    r.pp = *pp; r.builds = fs->builds; r.slot = slot; r.qslot = qslot; r.nq = nq; r.total = total; r.qEpoch = fs->qEpoch;
+    r.pp = *pp; r.builds = fs->builds; r.slot = slot; r.qslot = qslot; r.nq = nq; r.total = total; r.qEpoch = fs->qEpoch; r.fromPool = false;
     if ((rc = track_queries_issue(fs, set))) return rc;
     fs->res.commit(set, ResultRecord::kQueries, 1, ++fs->seq);
     return ORBX_OK;
