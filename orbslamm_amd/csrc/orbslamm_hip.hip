@@ -49,8 +49,9 @@
 #include "orbf_kernels.hip"   // the Fuse pieces shared by orbl's k_fuse_batch and orbc's k_loopfuse_search
 #include "orbl_kernels.hip"
 #include "orbc_kernels.hip"
+#include "orbg_kernels.hip"   // the g2o / Eigen pieces shared by orbo's k_pose_optimize and orbz's k_sim3_optimize
 #include "orbo_kernels.hip"
-#include "orbz_kernels.hip"   // after orbo_kernels.hip: it uses its sin / cos, Huber and quaternion pieces
+#include "orbz_kernels.hip"
 #include "orbw_kernels.hip"   // the map-point pool and the projections of the two tracking searches
 
 using namespace orbx;

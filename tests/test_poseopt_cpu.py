@@ -48,7 +48,7 @@ def test_header_declares_and_library_exports_the_poseopt_block():
     # the kernel and the restatement share no header
     ref = open(os.path.join(ROOT, "tools", "poseopt_ref.hpp")).read()
     assert '#include "' not in ref
-    for name in ("orbo_kernels.hip", "orbo_host.inc"):
+    for name in ("orbg_kernels.hip", "orbo_kernels.hip", "orbo_host.inc"):
         assert "poseopt_ref" not in open(os.path.join(ROOT, "orbslamm_amd", "csrc", name)).read()
 
 

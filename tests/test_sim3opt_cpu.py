@@ -58,7 +58,7 @@ def test_header_declares_and_library_exports_the_sim3opt_block():
     # the kernel and the restatement share no header; the restatement includes poseopt_ref.hpp alone
     ref = open(os.path.join(ROOT, "tools", "sim3opt_ref.hpp")).read()
     assert re.findall(r'#include "([^"]+)"', ref) == ["poseopt_ref.hpp"]
-    for name in ("orbz_kernels.hip", "orbz_host.inc"):
+    for name in ("orbg_kernels.hip", "orbz_kernels.hip", "orbz_host.inc"):
         text = open(os.path.join(ROOT, "orbslamm_amd", "csrc", name)).read()
         assert "sim3opt_ref" not in text and "poseopt_ref" not in text
 
