@@ -83,7 +83,7 @@ enum OrbmSlot {
     S_INI_QD, S_INI_QA, S_INI_QV, S_INI_TD, /* orbm_search_for_initialization (its _frames form: S_INI_QV alone) | init_core */
     S_INI_UVR, S_INI_LVL, S_INI_CNT, S_INI_OFF, S_INI_KEY, S_INI_CIDX, S_INI_M12, S_INI_M21, S_INI_NM, S_INI_PUSHT, S_INI_PUSHB,
     S_TRI_K1, S_TRI_D1, S_TRI_K2, S_TRI_D2, S_TRI_ST1, S_TRI_I1, S_TRI_ST2, S_TRI_I2, /* orbm_search_for_triangulation | tri_core */
-    S_TRI_S1, S_TRI_U1, S_TRI_S2, S_TRI_U2, S_TRI_PA, S_TRI_PB, S_TRI_M12, S_TRI_BIN, S_TRI_HIST,
+    S_TRI_S1, S_TRI_U1, S_TRI_S2, S_TRI_U2, S_TRI_PA, S_TRI_PB, S_TRI_M12, S_TRI_BIN, S_TRI_NMATCH,
     S_UND_IN, S_UND_OUT, S_RGBD_KEYS, S_RGBD_KEYSUN, S_RGBD_DEPTH, S_RGBD_OUT, S_DIS_DESC, S_DIS_START, S_DIS_BEST,   // orbm_undistort_keypoints, _compute_stereo_from_rgbd, _distinctive_descriptors
     S_BLOCK,                                                // THE ONE SHARED NAME: the packed block of orbl_core, orbl_fuse_core, orbc_core, orbo_core and orbw_project_sync, which never nest
     S_LF_PAIR, S_LF_TILES, S_LF_HITS, S_LF_STATUS,          // orbc_core besides S_BLOCK
@@ -514,7 +514,7 @@ static int bow_core(orbm_handle* h, const BowSide& q, const uint8_t* qvalid, con
     const size_t oTs = tHost ? pk.take((size_t)(t.n_nodes + 1) * 4) : 0, oTi = tHost ? pk.take((size_t)std::max(nti, 1) * 4) : 0;
     const size_t oQv = qvalid ? pk.take((size_t)nq) : 0, oTv = tvalid ? pk.take((size_t)nt) : 0;
     const size_t oPq = pk.take((size_t)pairCap * 4), oPt = pk.take((size_t)pairCap * 4);
-    const size_t oMatched = pk.take((size_t)nt), oHist = pk.take(34 * 4), oBin = pk.take((size_t)nout);
+    const size_t oMatched = pk.take((size_t)nt), oBin = pk.take((size_t)nout);
     const size_t oMatch = pk.take((size_t)nout * 4), oNm = pk.take(16);
     const size_t total = pk.off;
     if ((rc = orbm_pinned(h, total)) || (rc = orbm_reserve(h, T_STAGE, total))) return rc;
@@ -542,7 +542,7 @@ static int bow_core(orbm_handle* h, const BowSide& q, const uint8_t* qvalid, con
     }
     if (qvalid) memcpy(hs + oQv, qvalid, (size_t)nq);
     if (tvalid) memcpy(hs + oTv, tvalid, (size_t)nt);
-    memset(hs + oMatched, 0, oBin - oMatched);                 // matched flags + histogram
+    memset(hs + oMatched, 0, oBin - oMatched);                 // matched flags
     memset(hs + oMatch, 0xFF, (size_t)nout * 4);               // match = -1
     memset(hs + oNm, 0, 16);
     hipStream_t s = h->stream;
@@ -555,12 +555,12 @@ static int bow_core(orbm_handle* h, const BowSide& q, const uint8_t* qvalid, con
     a.tstart = tHost ? (const int32_t*)(ds + oTs) : t.d_start; a.tidx = tHost ? (const int32_t*)(ds + oTi) : t.d_idx;
     a.pairQ = (const int32_t*)(ds + oPq); a.pairT = (const int32_t*)(ds + oPt);
     a.matched = ds + oMatched;
-    a.match = (int32_t*)(ds + oMatch); a.binOf = ds + oBin; a.hist = (int32_t*)(ds + oHist);
+    a.match = (int32_t*)(ds + oMatch); a.binOf = ds + oBin;
     a.nnratio = nnratio; a.thLow = 50; a.checkOri = check_ori; a.outByTrain = out_by_train;
     if ((rc = stage_up(h, s, ds, hs, total))) return rc;
     hipLaunchKernelGGL(orbm::k_bow_pairs, dim3(npairs), dim3(64), 0, s, a);
     hipLaunchKernelGGL(orbm::k_prune_flat, dim3(1), dim3(256), 0, s, a.match, nout, check_ori, (const uint8_t*)a.binOf,
-                       a.hist, (int32_t*)(ds + oNm));
+                       (int32_t*)(ds + oNm));
     HIPCHK(hipGetLastError());
     if ((rc = stage_down_wait(h, s, hs + oMatch, ds + oMatch, total - oMatch))) return rc;
     memcpy(match, hs + oMatch, (size_t)nout * 4);
@@ -979,13 +979,12 @@ static int tri_core(orbm_handle* h, const TriSide& A, const TriSide& B, const fl
     const int npairs = (int)pa.size();
     if (npairs == 0) return ORBX_OK;
     if ((rc = orbm_reserve(h, {{S_TRI_S1, (size_t)n1}, {S_TRI_U1, (size_t)n1 * 4}, {S_TRI_S2, (size_t)n2}, {S_TRI_U2, (size_t)n2 * 4}, {S_TRI_PA, (size_t)npairs * 4},
-                               {S_TRI_PB, (size_t)npairs * 4}, {S_TRI_M12, (size_t)n1 * 4}, {S_TRI_BIN, (size_t)n1}, {S_TRI_HIST, 34 * 4}}))) return rc;
+                               {S_TRI_PB, (size_t)npairs * 4}, {S_TRI_M12, (size_t)n1 * 4}, {S_TRI_BIN, (size_t)n1}, {S_TRI_NMATCH, 4}}))) return rc;
     hipStream_t s = h->stream;
     if ((A.skip && (rc = slot_upload(h, S_TRI_S1, A.skip, (size_t)n1))) || (B.skip && (rc = slot_upload(h, S_TRI_S2, B.skip, (size_t)n2))) ||
         (A.uright && (rc = slot_upload(h, S_TRI_U1, A.uright, (size_t)n1 * 4))) || (B.uright && (rc = slot_upload(h, S_TRI_U2, B.uright, (size_t)n2 * 4))) ||
         (rc = slot_upload(h, S_TRI_PA, pa.data(), (size_t)npairs * 4)) || (rc = slot_upload(h, S_TRI_PB, pb.data(), (size_t)npairs * 4))) return rc;
     HIPCHK(hipMemsetAsync(slot_ptr(h, S_TRI_M12), 0xFF, (size_t)n1 * 4, s));
-    HIPCHK(hipMemsetAsync(slot_ptr(h, S_TRI_HIST), 0, 34 * 4, s));
     orbm::TriArgs a{};
     a.k1 = A.keys; a.d1 = A.desc;
     a.skip1 = A.skip ? slot_ptr<const uint8_t>(h, S_TRI_S1) : nullptr; a.ur1 = A.uright ? slot_ptr<const float>(h, S_TRI_U1) : nullptr;
@@ -997,13 +996,13 @@ static int tri_core(orbm_handle* h, const TriSide& A, const TriSide& B, const fl
     a.ex = ex; a.ey = ey;
     for (int i = 0; i < 16; i++) { a.sf2[i] = i < nlevels ? sf2[i] : 0.f; a.sigma2[i] = i < nlevels ? sigma2_2[i] : 0.f; }
     a.onlyStereo = only_stereo; a.checkOri = check_ori;
-    a.m12 = slot_ptr<int32_t>(h, S_TRI_M12); a.binOf = slot_ptr<uint8_t>(h, S_TRI_BIN); a.hist = slot_ptr<int32_t>(h, S_TRI_HIST);
+    a.m12 = slot_ptr<int32_t>(h, S_TRI_M12); a.binOf = slot_ptr<uint8_t>(h, S_TRI_BIN);
     hipLaunchKernelGGL(orbm::k_triangulation_pairs, dim3(npairs), dim3(64), 0, s, a);
-    hipLaunchKernelGGL(orbm::k_prune_flat, dim3(1), dim3(256), 0, s, a.m12, n1, check_ori, (const uint8_t*)a.binOf, a.hist, a.hist + 32);
+    hipLaunchKernelGGL(orbm::k_prune_flat, dim3(1), dim3(256), 0, s, a.m12, n1, check_ori, (const uint8_t*)a.binOf, slot_ptr<int32_t>(h, S_TRI_NMATCH));
     HIPCHK(hipGetLastError());
     int32_t nm = 0;
     HIPCHK(hipMemcpyAsync(matches12, a.m12, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&nm, a.hist + 32, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&nm, slot_ptr<int32_t>(h, S_TRI_NMATCH), 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (nmatches) *nmatches = nm;
     return ORBX_OK;

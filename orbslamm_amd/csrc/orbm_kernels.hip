@@ -10,7 +10,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_common.hpp"
+
 namespace orbm {
+
+using orbx::hamming256;
 
 constexpr int kHistoLength = 30;  // ORBmatcher.cc:39
 
@@ -23,14 +27,6 @@ struct MatchIO {
     const int32_t* count;    // features per slot
 };
 
-__device__ __forceinline__ int hamming256(const uint32_t q[8], const uint32_t* __restrict__ t)
-{
-    int d = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) d += __popc(q[i] ^ t[i]);
-    return d;
-}
-
 // ORBmatcher.cc:238-245: factor = 1.0f/HISTO_LENGTH (sic), round() half away from zero
 __device__ __forceinline__ int rot_bin(float aq, float at)
 {
@@ -42,24 +38,69 @@ __device__ __forceinline__ int rot_bin(float aq, float at)
     return bin;
 }
 
-// ComputeThreeMaxima (ORBmatcher.cc:1603-1644) over the 30 rotation bins in sh[0..31], by the workgroup's FIRST WAVE (call it
-// with tid < 64, all 64 lanes): the bins come in with one LDS trip, the walk -- strict >, ties keep the earlier bin, second /
-// third dropped below a tenth of the first -- runs on wave-uniform values (v_readlane).  One thread reading the bins one
-// after the other cost thirty dependent LDS round trips (3 us) with the whole workgroup waiting at the barrier behind it.
-__device__ __forceinline__ void three_maxima_wave(const int* sh, int* sInd)
+// ---- rotation consistency (ORBmatcher.cc:238-287), stated once: the decision rule, then the workgroup pieces a kernel calls
+// between its own loops (where the bins come from and where the pruned table goes stays with the kernel).
+// ComputeThreeMaxima (ORBmatcher.cc:1603-1644) over the 30 bins bin(0) .. bin(29): strict >, ties keep the earlier bin, second /
+// third dropped below a tenth of the first (compared as floats); -1 = none.
+template <class Bins>
+__host__ __device__ __forceinline__ void three_maxima(Bins bin, int& ind1, int& ind2, int& ind3)
 {
-    const int hl = sh[threadIdx.x & 31];
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    // (the walk keeps its own copies: written through the references, the three exchanges became stores through selected
+    // addresses and the indices lived in scratch)
+    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
 #pragma unroll
     for (int i = 0; i < kHistoLength; i++) {  // :1609-1633
-        const int s = __builtin_amdgcn_readlane(hl, i);
-        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-        else if (s > max3) { max3 = s; ind3 = i; }
+        const int s = bin(i);
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
+        else if (s > max3) { max3 = s; i3 = i; }
     }
-    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-    if ((threadIdx.x & 63) == 0) { sInd[0] = ind1; sInd[1] = ind2; sInd[2] = ind3; }
+    if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+    ind1 = i1; ind2 = i2; ind3 = i3;
+}
+
+// The wave form, over the bins in LDS at sh[0..31]; all 64 lanes call it and all get the three indices.  The bins come in with
+// one LDS trip and the walk runs on wave-uniform values (v_readlane).  One thread reading the bins one after the other cost
+// thirty dependent LDS round trips (3 us) with the whole workgroup waiting at the barrier behind it.
+__device__ __forceinline__ void three_maxima_wave(const int* sh, int& ind1, int& ind2, int& ind3)
+{
+    const int hl = sh[threadIdx.x & 31];
+    three_maxima([hl](int i) { return __builtin_amdgcn_readlane(hl, i); }, ind1, ind2, ind3);
+}
+
+// what a workgroup keeps in LDS for the check: the histogram, the three surviving bins, the count of matches left
+struct RotShared { int bins[32]; int ind[3]; int count; };
+
+__device__ __forceinline__ void rot_clear(RotShared& rs)  // (a barrier before the first use)
+{
+    if (threadIdx.x < 32) rs.bins[threadIdx.x] = 0;
+    if (threadIdx.x == 0) rs.count = 0;
+}
+
+// the three maxima of rs.bins into rs.ind, by the workgroup's first wave; barriers on both sides are the caller's
+__device__ __forceinline__ void rot_three_maxima(RotShared& rs)
+{
+    if (threadIdx.x < 64) {
+        int ind1, ind2, ind3;
+        three_maxima_wave(rs.bins, ind1, ind2, ind3);
+        if (threadIdx.x == 0) { rs.ind[0] = ind1; rs.ind[1] = ind2; rs.ind[2] = ind3; }
+    }
+}
+
+// :269-287: a match whose bin is none of the three goes
+__device__ __forceinline__ bool rot_outlier(const RotShared& rs, int bin)
+{
+    return bin != rs.ind[0] && bin != rs.ind[1] && bin != rs.ind[2];
+}
+
+// every thread's count of surviving matches summed into rs.count (wave shuffle, one LDS atomic per wave); final behind the barrier
+__device__ __forceinline__ void rot_count(RotShared& rs, int local)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d);
+    if ((threadIdx.x & 63) == 0 && local) atomicAdd(&rs.count, local);
+    __syncthreads();
 }
 
 // Brute-force best/second over a CHUNK of the train descriptors.
@@ -516,33 +557,25 @@ __global__ __launch_bounds__(256) void k_match_prune(MatchIO q, int qslot0, int 
                                                     const uint8_t* __restrict__ binOf,
                                                     int32_t* __restrict__ hist, int32_t* __restrict__ nmatch)
 {
-    __shared__ int sh[32];
-    __shared__ int sInd[3];
-    __shared__ int sCnt;
+    __shared__ RotShared rs;
     const int f = blockIdx.x, tid = threadIdx.x;
     const int nq = q.count[qslot0 + f];
-    if (tid < 32) { sh[tid] = hist[f * 32 + tid]; hist[f * 32 + tid] = 0; }
-    if (tid == 0) sCnt = 0;
+    if (tid < 32) { rs.bins[tid] = hist[f * 32 + tid]; hist[f * 32 + tid] = 0; }
+    if (tid == 0) rs.count = 0;
     __syncthreads();
-    if (tid < 64) three_maxima_wave(sh, sInd);
+    rot_three_maxima(rs);
     __syncthreads();
     int local = 0;
     for (int i = tid; i < nq; i += 256) {
         int m = match[(int64_t)f * matchPitch + i];
-        if (m >= 0 && checkOri) {
-            const int bin = binOf[(int64_t)f * matchPitch + i];
-            if (bin != sInd[0] && bin != sInd[1] && bin != sInd[2]) {
-                m = -1;
-                match[(int64_t)f * matchPitch + i] = -1;
-            }
+        if (m >= 0 && checkOri && rot_outlier(rs, binOf[(int64_t)f * matchPitch + i])) {
+            m = -1;
+            match[(int64_t)f * matchPitch + i] = -1;
         }
         local += m >= 0;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d);
-    if ((tid & 63) == 0) atomicAdd(&sCnt, local);
-    __syncthreads();
-    if (tid == 0) nmatch[f] = sCnt;
+    rot_count(rs, local);
+    if (tid == 0) nmatch[f] = rs.count;
 }
 
 // k_match_accept + k_match_prune in one workgroup per frame, for the few-frame (latency) mode: merge of the chunk
@@ -551,13 +584,10 @@ __global__ __launch_bounds__(256) void k_match_prune(MatchIO q, int qslot0, int 
 __global__ __launch_bounds__(1024) void k_match_accept_prune(AcceptArgs a, int nchunks, const uint2* __restrict__ partial,
                                                             int64_t pitch, int32_t* __restrict__ nmatch)
 {
-    __shared__ int sh[32];
-    __shared__ int sInd[3];
-    __shared__ int sCnt;
+    __shared__ RotShared rs;
     const int f = blockIdx.x, tid = threadIdx.x;
     const int nq = a.q.count[a.qslot0 + f];
-    if (tid < 32) sh[tid] = 0;
-    if (tid == 0) sCnt = 0;
+    rot_clear(rs);
     __syncthreads();
     for (int qi = tid; qi < nq; qi += 1024) {
         uint32_t k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu;
@@ -570,28 +600,22 @@ __global__ __launch_bounds__(1024) void k_match_accept_prune(AcceptArgs a, int n
         int bin;
         const int m = accept_decide(a, f, qi, k1, k2, bin);
         a.match[(int64_t)f * a.matchPitch + qi] = m;
-        if (bin >= 0) { a.binOf[(int64_t)f * a.matchPitch + qi] = (uint8_t)bin; atomicAdd(&sh[bin], 1); }
+        if (bin >= 0) { a.binOf[(int64_t)f * a.matchPitch + qi] = (uint8_t)bin; atomicAdd(&rs.bins[bin], 1); }
     }
     __syncthreads();
-    if (tid < 64) three_maxima_wave(sh, sInd);
+    rot_three_maxima(rs);
     __syncthreads();
     int local = 0;
     for (int qi = tid; qi < nq; qi += 1024) {  // the thread re-reads what it wrote above
         int m = a.match[(int64_t)f * a.matchPitch + qi];
-        if (m >= 0 && a.checkOri) {
-            const int bin = a.binOf[(int64_t)f * a.matchPitch + qi];
-            if (bin != sInd[0] && bin != sInd[1] && bin != sInd[2]) {
-                m = -1;
-                a.match[(int64_t)f * a.matchPitch + qi] = -1;
-            }
+        if (m >= 0 && a.checkOri && rot_outlier(rs, a.binOf[(int64_t)f * a.matchPitch + qi])) {
+            m = -1;
+            a.match[(int64_t)f * a.matchPitch + qi] = -1;
         }
         local += m >= 0;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d);
-    if ((tid & 63) == 0) atomicAdd(&sCnt, local);
-    __syncthreads();
-    if (tid == 0) nmatch[f] = sCnt;
+    rot_count(rs, local);
+    if (tid == 0) nmatch[f] = rs.count;
 }
 
 // full distance matrix (DescriptorDistance for every pair)
@@ -627,7 +651,7 @@ struct BowArgs {
     const int32_t* tstart; const int32_t* tidx;   // CSR of the train feature vector
     const int32_t* pairQ; const int32_t* pairT;   // matched node pairs (host lock-step walk :180-266)
     uint8_t* matched;                              // per train feature, zero-initialised
-    int32_t* match; uint8_t* binOf; int32_t* hist; // outputs
+    int32_t* match; uint8_t* binOf;                // outputs
     float nnratio; int32_t thLow; int32_t checkOri; int32_t outByTrain;
 };
 
@@ -711,6 +735,8 @@ __device__ __forceinline__ void bow_pair_body(const BowArgs& a, int nodeQ, int n
                 for (int j = 0; j < kPer; j++) {
                     key[j] = 0xFFFFFFFFu;
                     if (j < ntj) {
+                        // hamming256, written out: both operands are register arrays here, and through the function the compiler
+                        // moves the distance under `tfree` (an exec-mask branch per train slot and query, docs/experiments.md)
                         int d = 0;
 #pragma unroll
                         for (int i = 0; i < 8; i++) d += __popc(tw[j][i] ^ sq[i]);
@@ -793,7 +819,7 @@ constexpr int kBowMaxPairs = 128;
 struct BowSetArgs {
     const uint8_t* desc; const float* ang; const int32_t* n; int32_t cap;       // frame set: slot s at + s * cap (desc: * 32)
     const uint32_t* fvNode; const int32_t* fvStart; const int32_t* fvIdx; const int32_t* counts;  // fvStart: + s * (cap + 1), counts: + 2 s + 1 = nodes
-    uint8_t* matched; int32_t* match; uint8_t* binOf; int32_t* hist;             // per pair p: + p * cap (hist: + p * 32); zero / -1 / - / zero on entry
+    uint8_t* matched; int32_t* match; uint8_t* binOf;                            // per pair p: + p * cap; zero / -1 / - on entry
     float nnratio; int32_t thLow, checkOri;
     int16_t kf[kBowMaxPairs], fr[kBowMaxPairs];
 };
@@ -828,84 +854,78 @@ __global__ __launch_bounds__(64) void k_bow_set(BowSetArgs s)
     a.qstart = s.fvStart + (int64_t)qs * (C + 1); a.qidx = s.fvIdx + qs * C;
     a.tstart = s.fvStart + (int64_t)ts * (C + 1); a.tidx = s.fvIdx + ts * C;
     a.pairQ = nullptr; a.pairT = nullptr;
-    a.matched = s.matched + p * C; a.match = s.match + p * C; a.binOf = s.binOf + p * C; a.hist = s.hist + p * 32;
+    a.matched = s.matched + p * C; a.match = s.match + p * C; a.binOf = s.binOf + p * C;
     a.nnratio = s.nnratio; a.thLow = s.thLow; a.checkOri = s.checkOri; a.outByTrain = 1;
     bow_pair_body(a, nodeQ, lo);
 }
 
-// three maxima + pruning of every pair's match table (k_prune_flat's rule), final table and count to `outMatch` / `outN`
-// (pinned host memory: every entry is written once)
-__global__ __launch_bounds__(256) void k_bow_prune_set(BowSetArgs s, int32_t* __restrict__ outMatch, int32_t* __restrict__ outN)
+// Rotation check of one match table, by one workgroup of 256: the histogram (:238-248) is counted here, in LDS, from binOf (a few
+// hundred matches fall into two or three bins, and as global atomics on those few words they took longer than the search
+// itself), then three maxima, pruning and the count.  InPlace: the pruned entries of `match` are overwritten; else every entry
+// goes to `out`, written once (pinned host memory).
+template <bool InPlace>
+__device__ __forceinline__ void prune_table(int32_t* __restrict__ match, const uint8_t* __restrict__ binOf, int n, int checkOri,
+                                            int32_t* __restrict__ out, int32_t* __restrict__ nmatch)
 {
-    __shared__ int sh[32];
-    __shared__ int sInd[3];
-    __shared__ int sCnt;
-    const int tid = threadIdx.x, p = blockIdx.x;
-    const int64_t C = s.cap;
-    const int n = min(s.n[s.fr[p]], s.cap);
-    // the rotation histogram (:238-248) is counted here, in LDS: a few hundred matches of a pair fall into two or three
-    // bins, and as global atomics on those few words they took longer than the search itself
-    if (tid < 32) sh[tid] = 0;
-    if (tid == 0) sCnt = 0;
-    __syncthreads();
-    if (s.checkOri)
-        for (int i = tid; i < n; i += 256) if (s.match[p * C + i] >= 0) atomicAdd(&sh[s.binOf[p * C + i]], 1);
-    __syncthreads();
-    if (tid < 64) three_maxima_wave(sh, sInd);
-    __syncthreads();
-    int local = 0;
-    for (int i = tid; i < n; i += 256) {
-        int m = s.match[p * C + i];
-        if (m >= 0 && s.checkOri) {
-            const int bin = s.binOf[p * C + i];
-            if (bin != sInd[0] && bin != sInd[1] && bin != sInd[2]) m = -1;
-        }
-        outMatch[p * C + i] = m;
-        local += m >= 0;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d);
-    if ((tid & 63) == 0) atomicAdd(&sCnt, local);
-    __syncthreads();
-    if (tid == 0) outN[p] = sCnt;
-}
-
-// three maxima + pruning over a flat match array (same rule as k_match_prune), one workgroup
-__global__ __launch_bounds__(256) void k_prune_flat(int32_t* __restrict__ match, int n, int checkOri,
-                                                   const uint8_t* __restrict__ binOf, int32_t* __restrict__ hist,
-                                                   int32_t* __restrict__ nmatch)
-{
-    __shared__ int sh[32];
-    __shared__ int sInd[3];
-    __shared__ int sCnt;
+    __shared__ RotShared rs;
     const int tid = threadIdx.x;
-    if (tid < 32) sh[tid] = 0;   // (`hist` is no longer an input: the bins are counted here, in LDS, from binOf)
-    if (tid == 0) sCnt = 0;
+    rot_clear(rs);
     __syncthreads();
     if (checkOri)
-        for (int i = tid; i < n; i += 256) if (match[i] >= 0) atomicAdd(&sh[binOf[i]], 1);
+        for (int i = tid; i < n; i += 256) if (match[i] >= 0) atomicAdd(&rs.bins[binOf[i]], 1);
     __syncthreads();
-    if (tid < 64) three_maxima_wave(sh, sInd);
+    rot_three_maxima(rs);
     __syncthreads();
     int local = 0;
     for (int i = tid; i < n; i += 256) {
         int m = match[i];
-        if (m >= 0 && checkOri) {
-            const int bin = binOf[i];
-            if (bin != sInd[0] && bin != sInd[1] && bin != sInd[2]) { m = -1; match[i] = -1; }
-        }
+        const bool gone = m >= 0 && checkOri && rot_outlier(rs, binOf[i]);
+        if (gone) m = -1;
+        if constexpr (InPlace) { if (gone) match[i] = -1; } else out[i] = m;
         local += m >= 0;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d);
-    if ((tid & 63) == 0) atomicAdd(&sCnt, local);
-    __syncthreads();
-    if (tid == 0) *nmatch = sCnt;
+    rot_count(rs, local);
+    if (tid == 0) *nmatch = rs.count;
+}
+
+// every pair's match table of a frame set's SearchByBoW: final table and count to `outMatch` / `outN` (pinned host memory)
+__global__ __launch_bounds__(256) void k_bow_prune_set(BowSetArgs s, int32_t* __restrict__ outMatch, int32_t* __restrict__ outN)
+{
+    const int p = blockIdx.x;
+    const int64_t C = s.cap;
+    prune_table<false>(s.match + p * C, s.binOf + p * C, min(s.n[s.fr[p]], s.cap), s.checkOri, outMatch + p * C, outN + p);
+}
+
+// a flat match array, in place
+__global__ __launch_bounds__(256) void k_prune_flat(int32_t* __restrict__ match, int n, int checkOri, const uint8_t* __restrict__ binOf,
+                                                   int32_t* __restrict__ nmatch)
+{
+    prune_table<true>(match, binOf, n, checkOri, nullptr, nmatch);
 }
 
 // ------------------------------------------------------------------ Frame grid (Frame.cc:230-245, 327-392)
 struct GridDev { float minX, minY, invW, invH; int32_t cols, rows; };
 struct KeyDev { float x, y, size, angle, response; int32_t octave, class_id; };
+struct AreaWin { int x0, x1, y0, y1; bool check; };
+
+// cell range of GetFeaturesInArea (Frame.cc:332-346); false: the window misses the grid
+__device__ __forceinline__ bool area_window(const GridDev& g, float x, float y, float r, int minLevel, int maxLevel, AreaWin& w)
+{
+    w.x0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, g.minX), r), g.invW));
+    if (w.x0 < 0) w.x0 = 0;
+    if (w.x0 >= g.cols) return false;
+    w.x1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, g.minX), r), g.invW));
+    if (w.x1 > g.cols - 1) w.x1 = g.cols - 1;
+    if (w.x1 < 0) return false;
+    w.y0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, g.minY), r), g.invH));
+    if (w.y0 < 0) w.y0 = 0;
+    if (w.y0 >= g.rows) return false;
+    w.y1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, g.minY), r), g.invH));
+    if (w.y1 > g.rows - 1) w.y1 = g.rows - 1;
+    if (w.y1 < 0) return false;
+    w.check = (minLevel > 0) || (maxLevel >= 0);
+    return true;
+}
 
 __device__ __forceinline__ bool pos_in_grid(const GridDev& g, float x, float y, int& px, int& py)
 {
@@ -926,24 +946,14 @@ __global__ void k_grid_count(GridDev g, const KeyDev* __restrict__ keys, int n, 
 __global__ __launch_bounds__(1024) void k_scan_small(const int32_t* __restrict__ in, int n, int32_t* __restrict__ out)
 {
     __shared__ int wsum[16];
-    __shared__ int carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry = 0;
-    __syncthreads();
+    const int tid = threadIdx.x;
+    int carry = 0;  // (every thread keeps the running total)
     for (int base = 0; base < n; base += 1024) {
         const int i = base + tid;
-        const int v = i < n ? in[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int w = 0; w < 16; w++) { if (w < wave) woff += wsum[w]; tot += wsum[w]; }
-        if (i < n) out[i] = carry + woff + incl - v;
-        __syncthreads();
-        if (tid == 0) carry += tot;
-        __syncthreads();
+        int tot;
+        const int excl = orbx::block_scan_excl<1024>(i < n ? in[i] : 0, wsum, &tot);
+        if (i < n) out[i] = carry + excl;
+        carry += tot;
     }
     if (tid == 0) out[n] = carry;
 }
@@ -992,26 +1002,15 @@ __device__ __forceinline__ void for_each_in_area(const GridDev& g, const KeyDev*
                                                  const int32_t* __restrict__ cellStart, const int32_t* __restrict__ cellIdx,
                                                  float x, float y, float r, int minLevel, int maxLevel, F f)
 {
-    int nMinCellX = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, g.minX), r), g.invW));
-    if (nMinCellX < 0) nMinCellX = 0;
-    if (nMinCellX >= g.cols) return;
-    int nMaxCellX = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, g.minX), r), g.invW));
-    if (nMaxCellX > g.cols - 1) nMaxCellX = g.cols - 1;
-    if (nMaxCellX < 0) return;
-    int nMinCellY = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, g.minY), r), g.invH));
-    if (nMinCellY < 0) nMinCellY = 0;
-    if (nMinCellY >= g.rows) return;
-    int nMaxCellY = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, g.minY), r), g.invH));
-    if (nMaxCellY > g.rows - 1) nMaxCellY = g.rows - 1;
-    if (nMaxCellY < 0) return;
-    const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-    for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
-        for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {
+    AreaWin w;
+    if (!area_window(g, x, y, r, minLevel, maxLevel, w)) return;
+    for (int ix = w.x0; ix <= w.x1; ix++)
+        for (int iy = w.y0; iy <= w.y1; iy++) {
             const int c = ix * g.rows + iy;
             for (int j = cellStart[c]; j < cellStart[c + 1]; j++) {
                 const int i = cellIdx[j];
                 const KeyDev& kp = keys[i];
-                if (bCheckLevels) {
+                if (w.check) {
                     if (kp.octave < minLevel) continue;
                     if (maxLevel >= 0 && kp.octave > maxLevel) continue;
                 }
@@ -1183,17 +1182,10 @@ __global__ __launch_bounds__(64) void k_init_resolve(ProjArgs a, int32_t* __rest
         }
     }
     __syncthreads();
-    if (a.checkOri && lane == 0) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < kHistoLength; i++) {
-            const int s = hist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-        for (int p = 0; p < nPush; p++) {
+    if (a.checkOri) {  // (the block is one wave; a query is pushed once at most)
+        int ind1, ind2, ind3;
+        three_maxima_wave(hist, ind1, ind2, ind3);
+        for (int p = lane; p < nPush; p += 64) {
             const int bin = a.pushBin[p];
             if (bin != ind1 && bin != ind2 && bin != ind3) m12[a.pushT[p]] = -1;
         }
@@ -1217,7 +1209,7 @@ struct TriArgs {
     float F[9]; float ex, ey;
     float sf2[16]; float sigma2[16];
     int32_t onlyStereo, checkOri;
-    int32_t* m12; uint8_t* binOf; int32_t* hist;
+    int32_t* m12; uint8_t* binOf;
 };
 
 __global__ __launch_bounds__(64) void k_triangulation_pairs(TriArgs a)
@@ -1265,11 +1257,7 @@ __global__ __launch_bounds__(64) void k_triangulation_pairs(TriArgs a)
         if (best != 0xFFFFFFFFu && lane == 0) {
             const int t = a.idx2[s2 + (int)(0x3FFFFFu - (best & 0x3FFFFFu))];
             a.m12[q] = t;
-            if (a.checkOri) {
-                const int bin = rot_bin(kp1.angle, a.k2[t].angle);
-                a.binOf[q] = (uint8_t)bin;
-                atomicAdd(&a.hist[bin], 1);
-            }
+            if (a.checkOri) a.binOf[q] = (uint8_t)rot_bin(kp1.angle, a.k2[t].angle);  // (the bins are counted by k_prune_flat, in LDS)
         }
     }
 }
@@ -1311,9 +1299,6 @@ __global__ __launch_bounds__(64) void k_distinctive(const uint8_t* __restrict__ 
 }
 
 // ------------------------------------------------------------------ SURVEY 8(f).3
-// Frame::UndistortKeyPoints (src/Frame.cc:404-434) = cv::undistortPoints(..., mK, mDistCoef, Mat(), mK):
-// 5 fixed-point iterations of the radial-tangential model in double, one thread per keypoint.
-// Every operation is a separately rounded IEEE binary64 op (no contraction), like the host code.
 // queries of SearchForInitialization: only level-0 keypoints search (ORBmatcher.cc:424-426)
 __global__ void k_octave0_flags(const KeyDev* __restrict__ keys, int n, uint8_t* __restrict__ out)
 {
@@ -1337,14 +1322,14 @@ __global__ void k_stereo_from_rgbd(const KeyDev* __restrict__ keys, const KeyDev
     uRight[i] = ok ? __fsub_rn(keysUn[i].x, __fdiv_rn(mbf, d)) : -1.f;
 }
 
+// Frame::UndistortKeyPoints (src/Frame.cc:404-434) = cv::undistortPoints(..., mK, mDistCoef, Mat(), mK) for one point:
+// 5 fixed-point iterations of the radial-tangential model in double.
+// Every operation is a separately rounded IEEE binary64 op (no contraction), like the host code.
 struct UndistArgs { double fx, fy, cx, cy, k1, k2, p1, p2, k3; };
-__global__ void k_undistort(const KeyDev* __restrict__ in, int n, UndistArgs a, KeyDev* __restrict__ out)
+__device__ __forceinline__ void undistort_point(const UndistArgs& a, float& px, float& py)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    KeyDev kp = in[i];
     const double ifx = __ddiv_rn(1.0, a.fx), ify = __ddiv_rn(1.0, a.fy);
-    double x = kp.x, y = kp.y;
+    double x = px, y = py;
     const double x0 = x = __dmul_rn(__dsub_rn(x, a.cx), ifx);
     const double y0 = y = __dmul_rn(__dsub_rn(y, a.cy), ify);
     for (int j = 0; j < 5; j++) {
@@ -1363,8 +1348,17 @@ __global__ void k_undistort(const KeyDev* __restrict__ in, int n, UndistArgs a, 
     const double xx = __dadd_rn(__dadd_rn(__dmul_rn(a.fx, x), __dmul_rn(0.0, y)), a.cx);
     const double yy = __dadd_rn(__dadd_rn(__dmul_rn(0.0, x), __dmul_rn(a.fy, y)), a.cy);
     const double ww = __ddiv_rn(1.0, __dadd_rn(__dadd_rn(__dmul_rn(0.0, x), __dmul_rn(0.0, y)), 1.0));
-    kp.x = (float)__dmul_rn(xx, ww);
-    kp.y = (float)__dmul_rn(yy, ww);
+    px = (float)__dmul_rn(xx, ww);
+    py = (float)__dmul_rn(yy, ww);
+}
+
+// one thread per keypoint
+__global__ void k_undistort(const KeyDev* __restrict__ in, int n, UndistArgs a, KeyDev* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    KeyDev kp = in[i];
+    undistort_point(a, kp.x, kp.y);
     out[i] = kp;
 }
 

@@ -8,8 +8,8 @@ struct orbm_frameset_bow {
     uint32_t *d_word = nullptr, *d_node = nullptr; double* d_w = nullptr;
     uint32_t* d_outWord = nullptr; double* d_outW = nullptr;
     uint32_t* d_fvNode = nullptr; int32_t *d_fvStart = nullptr, *d_fvIdx = nullptr, *d_counts = nullptr;
-    uint8_t* d_zero = nullptr; size_t zeroBytes = 0;     // matched[S][C] | hist[S][32]: cleared before every search
-    uint8_t* d_matched = nullptr; int32_t* d_hist = nullptr; int32_t* d_match = nullptr; uint8_t* d_binOf = nullptr;
+    uint8_t* d_zero = nullptr; size_t zeroBytes = 0;     // matched[S][C]: cleared before every search
+    uint8_t* d_matched = nullptr; int32_t* d_match = nullptr; uint8_t* d_binOf = nullptr;
     uint8_t* h_block = nullptr; int32_t* h_match = nullptr; int32_t* h_n = nullptr;   // pinned, one share per result set
     ResultRing res;   // (searches that write no flags and are never run again)
     int maxNodes = 0, P = 2;
@@ -38,7 +38,7 @@ static int frameset_bow_alloc(orbm_frameset* fs)
     Packer pk;
     const size_t oWd = pk.take(S * C * 4), oNd = pk.take(S * C * 4), oW = pk.take(S * C * 8), oOw = pk.take(S * C * 4), oOv = pk.take(S * C * 8);
     const size_t oFn = pk.take(S * C * 4), oFs = pk.take(S * (C + 1) * 4), oFi = pk.take(S * C * 4), oCt = pk.take(S * 8);
-    const size_t oMa = pk.take(S * C), oHi = pk.take(S * 32 * 4), oMt = pk.take(S * C * 4), oBn = pk.take(S * C);
+    const size_t oMa = pk.take(S * C), oMt = pk.take(S * C * 4), oBn = pk.take(S * C);
     Packer hp;
     const size_t hM = hp.take(ResultRing::kSets * S * C * 4), hN = hp.take(ResultRing::kSets * S * 4);
     if (hipMalloc(&b->d_block, pk.off) != hipSuccess || hipHostMalloc(&b->h_block, hp.off, hipHostMallocDefault) != hipSuccess) {
@@ -51,7 +51,7 @@ static int frameset_bow_alloc(orbm_frameset* fs)
     b->d_outWord = (uint32_t*)(d + oOw); b->d_outW = (double*)(d + oOv);
     b->d_fvNode = (uint32_t*)(d + oFn); b->d_fvStart = (int32_t*)(d + oFs); b->d_fvIdx = (int32_t*)(d + oFi); b->d_counts = (int32_t*)(d + oCt);
     b->d_zero = d + oMa; b->zeroBytes = oMt - oMa;
-    b->d_matched = d + oMa; b->d_hist = (int32_t*)(d + oHi); b->d_match = (int32_t*)(d + oMt); b->d_binOf = d + oBn;
+    b->d_matched = d + oMa; b->d_match = (int32_t*)(d + oMt); b->d_binOf = d + oBn;
     b->h_match = (int32_t*)(b->h_block + hM); b->h_n = (int32_t*)(b->h_block + hN);
     while (b->P < fs->cap) b->P <<= 1;
     b->slotVoc.assign(S, 0);
@@ -151,7 +151,7 @@ extern "C" int orbm_bow_frames(orbm_frameset_t* fs, const int32_t* kf_slots, con
         a.nnratio = nnratio; a.thLow = 50; a.checkOri = check_ori;
         for (int p0 = 0; p0 < npairs; p0 += orbm::kBowMaxPairs) {
             const int nb = std::min(orbm::kBowMaxPairs, npairs - p0);
-            a.matched = b->d_matched + p0 * C; a.match = b->d_match + p0 * C; a.binOf = b->d_binOf + p0 * C; a.hist = b->d_hist + p0 * 32;
+            a.matched = b->d_matched + p0 * C; a.match = b->d_match + p0 * C; a.binOf = b->d_binOf + p0 * C;
             for (int i = 0; i < nb; i++) { a.kf[i] = (int16_t)kf_slots[p0 + i]; a.fr[i] = (int16_t)frame_slots[p0 + i]; }
             hipLaunchKernelGGL(orbm::k_bow_set, dim3(std::max(b->maxNodes, 1), nb), dim3(64), 0, h->stream, a);
             hipLaunchKernelGGL(orbm::k_bow_prune_set, dim3(nb), dim3(256), 0, h->stream, a, b->h_match + (set * S + p0) * C, b->h_n + set * S + p0);

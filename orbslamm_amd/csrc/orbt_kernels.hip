@@ -30,6 +30,8 @@ namespace orbt {
 using orbm::GridDev;
 using orbm::KeyDev;
 using orbm::UndistArgs;
+using orbm::AreaWin;
+using orbm::area_window;
 
 #ifndef ORBT_THREADS
 #define ORBT_THREADS 1024
@@ -53,21 +55,6 @@ __device__ unsigned long long g_orbtBuild[12];   // phases of k_frame_build (blo
 #define ORBT_BMARK(i) do { } while (0)
 #endif
 
-// exclusive scan of one value per thread over the workgroup; returns the exclusive prefix, *total = sum
-__device__ __forceinline__ int block_scan_excl(int v, int* wsum, int* total)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int incl = orbx::wave_incl_scan(v);
-    __syncthreads();  // wsum may still be read from the previous use
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; w++) { const int s = wsum[w]; if (w < wave) woff += s; tot += s; }
-    *total = tot;
-    return woff + incl - v;
-}
-
 // ------------------------------------------------------------------ frame set: B device-resident frames, one launch
 struct FrameSetDev {  // slot s: keysUn + s*cap, desc + s*cap*32, ang + s*cap, cellStart + s*(ncell+1), cellIdx + s*cap, rec + s*cap, n + s
     KeyDev* keysUn; uint8_t* desc; float* ang; int32_t* cellStart; int32_t* cellIdx;
@@ -83,32 +70,6 @@ struct FrameBuildArgs {
     int32_t slot0, slotMod;
     GridDev grid; UndistArgs und; int32_t undistort;
 };
-
-// cv::undistortPoints for one point, as k_undistort (orbm_kernels.hip) does it
-__device__ __forceinline__ void undistort_point(const UndistArgs& a, float& px, float& py)
-{
-    const double ifx = __ddiv_rn(1.0, a.fx), ify = __ddiv_rn(1.0, a.fy);
-    double x = px, y = py;
-    const double x0 = x = __dmul_rn(__dsub_rn(x, a.cx), ifx);
-    const double y0 = y = __dmul_rn(__dsub_rn(y, a.cy), ify);
-    for (int j = 0; j < 5; j++) {
-        const double r2 = __dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y));
-        const double num = __dadd_rn(1.0, __dmul_rn(__dadd_rn(__dmul_rn(__dadd_rn(__dmul_rn(0.0, r2), 0.0), r2), 0.0), r2));
-        const double den = __dadd_rn(1.0, __dmul_rn(__dadd_rn(__dmul_rn(__dadd_rn(__dmul_rn(a.k3, r2), a.k2), r2), a.k1), r2));
-        const double icdist = __ddiv_rn(num, den);
-        const double deltaX = __dadd_rn(__dmul_rn(__dmul_rn(__dmul_rn(2.0, a.p1), x), y),
-                                        __dmul_rn(a.p2, __dadd_rn(r2, __dmul_rn(__dmul_rn(2.0, x), x))));
-        const double deltaY = __dadd_rn(__dmul_rn(a.p1, __dadd_rn(r2, __dmul_rn(__dmul_rn(2.0, y), y))),
-                                        __dmul_rn(__dmul_rn(__dmul_rn(2.0, a.p2), x), y));
-        x = __dmul_rn(__dsub_rn(x0, deltaX), icdist);
-        y = __dmul_rn(__dsub_rn(y0, deltaY), icdist);
-    }
-    const double xx = __dadd_rn(__dadd_rn(__dmul_rn(a.fx, x), __dmul_rn(0.0, y)), a.cx);
-    const double yy = __dadd_rn(__dadd_rn(__dmul_rn(0.0, x), __dmul_rn(a.fy, y)), a.cy);
-    const double ww = __ddiv_rn(1.0, __dadd_rn(__dadd_rn(__dmul_rn(0.0, x), __dmul_rn(0.0, y)), 1.0));
-    px = (float)__dmul_rn(xx, ww);
-    py = (float)__dmul_rn(yy, ww);
-}
 
 // One workgroup per frame: mvKeysUn, the angle column, a private copy of the descriptors and mGrid as CSR
 // (cell-major ix*rows+iy, ascending feature index inside a cell = the reference's push_back order, Frame.cc:236-244).
@@ -145,7 +106,7 @@ __device__ __forceinline__ void frame_build_body(const FrameBuildArgs& a, const 
     ORBT_BMARK(1);
     for (int i = tid; i < n; i += kThreads) {
         KeyDev kp = sk[i];
-        if (a.undistort) undistort_point(a.und, kp.x, kp.y);
+        if (a.undistort) orbm::undistort_point(a.und, kp.x, kp.y);
         dk[i] = kp;
         da[i] = kp.angle;
         kx[i] = kp.x; ky[i] = kp.y; ko[i] = kp.octave;
@@ -169,7 +130,7 @@ __device__ __forceinline__ void frame_build_body(const FrameBuildArgs& a, const 
         const int c0 = min(tid * per, a.fs.ncell), c1 = min(c0 + per, a.fs.ncell);
         int sum = 0;
         for (int c = c0; c < c1; c++) sum += cnt[c];
-        int run = block_scan_excl(sum, wsum, &carry);
+        int run = orbx::block_scan_excl<kThreads>(sum, wsum, &carry);
         for (int c = c0; c < c1; c++) { const int v = cnt[c]; cnt[c] = run; cs[c] = run; run += v; }
     }
     if (tid == 0) { cs[a.fs.ncell] = carry; a.fs.n[slot] = n; }
@@ -332,28 +293,7 @@ constexpr int kCandPasses = 4;                           // columns per slot; a 
 // The train frame's grid in LDS: its features in GRID order as {x, y, index | octave << 24, 0} (one 16-byte read per
 // visit) and the cell starts (uint16).  GetFeaturesInArea becomes a walk at LDS latency, and since cells are stored
 // column-major (ix * rows + iy) one grid column of a window is ONE contiguous run of records in the reference's scan
-// order (Frame.cc:352-376).
-struct AreaWin { int x0, x1, y0, y1; bool check; };
-
-// cell range of GetFeaturesInArea (Frame.cc:332-346); false: the window misses the grid
-__device__ __forceinline__ bool area_window(const GridDev& g, float x, float y, float r, int minLevel, int maxLevel, AreaWin& w)
-{
-    w.x0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, g.minX), r), g.invW));
-    if (w.x0 < 0) w.x0 = 0;
-    if (w.x0 >= g.cols) return false;
-    w.x1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, g.minX), r), g.invW));
-    if (w.x1 > g.cols - 1) w.x1 = g.cols - 1;
-    if (w.x1 < 0) return false;
-    w.y0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, g.minY), r), g.invH));
-    if (w.y0 < 0) w.y0 = 0;
-    if (w.y0 >= g.rows) return false;
-    w.y1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, g.minY), r), g.invH));
-    if (w.y1 > g.rows - 1) w.y1 = g.rows - 1;
-    if (w.y1 < 0) return false;
-    w.check = (minLevel > 0) || (maxLevel >= 0);
-    return true;
-}
-
+// order (Frame.cc:352-376).  The window itself is orbm::area_window.
 template <class CST, class F>
 __device__ __forceinline__ void area_column(const GridDev& g, const uint4* rec, const CST* cst, const AreaWin& w, int ix,
                                             float x, float y, float r, int minLevel, int maxLevel, int seg, int nseg, F f)
@@ -383,21 +323,6 @@ __device__ __forceinline__ int hamming_rows(const uint8_t* __restrict__ qd, uint
     const uint4 a0 = qp[0], a1 = qp[1], b0 = tp[0], b1 = tp[1];
     return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
            __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-// exclusive scan over the 256 threads of a candidate workgroup
-__device__ __forceinline__ int wg_scan_excl(int v, int* wsum, int* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = orbx::wave_incl_scan(v);
-    __syncthreads();  // wsum may still be read from the previous use
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kCandThreads / 64; w++) { const int s = wsum[w]; if (w < wave) woff += s; tot += s; }
-    *total = tot;
-    return woff + incl - v;
 }
 
 // exclusive prefix over the LANES lanes of a query, *tot = their sum
@@ -508,7 +433,7 @@ __device__ __forceinline__ void proj_candidates_body(const ProjPair& P, const Pr
         qtot += ptot;
     }
     int tot;
-    const int qoff = __shfl(wg_scan_excl(lc == 0 ? qtot : 0, wsum, &tot), 0, LANES);
+    const int qoff = __shfl(orbx::block_scan_excl<kCandThreads>(lc == 0 ? qtot : 0, wsum, &tot), 0, LANES);
     if (tot == 0) {  // uniform
         if (q < nq && lc == 0) { P.candOff[q] = 0; P.candCnt[q] = 0; }
         return;
@@ -572,7 +497,7 @@ __device__ __forceinline__ void proj_candidates_body(const ProjPair& P, const Pr
     int qkeep;
     const int kofs = quad_scan_excl<LANES>(keep, lc, &qkeep);
     int ktot;
-    const int kex = __shfl(wg_scan_excl(lc == 0 ? qkeep : 0, wsum, &ktot), 0, LANES);
+    const int kex = __shfl(orbx::block_scan_excl<kCandThreads>(lc == 0 ? qkeep : 0, wsum, &ktot), 0, LANES);
     if (tid == 0) sBase = ktot ? atomicAdd(P.total, ktot) : 0;
     __syncthreads();
     base = sBase;
@@ -608,8 +533,8 @@ constexpr int kTailLive = ORBT_TAIL_LIVE, kTailQueries = ORBT_TAIL_QUERIES;   //
 
 template <bool L>
 __device__ __forceinline__ void proj_resolve_rounds(const ProjPair& P, const ProjCommon& c, int nq, int nt, int total,
-                                                   int32_t* occBy, int32_t* minUnd0, int32_t* winner, int32_t* qtab, int* hist,
-                                                   int* sPending, int* sInd, int* sCount, int* sLive)
+                                                   int32_t* occBy, int32_t* minUnd0, int32_t* winner, int32_t* qtab, orbm::RotShared& rot,
+                                                   int* sPending, int* sLive)
 {
     const int tid = threadIdx.x;
     const bool useRot = c.checkOri && (c.mode == 4 || c.mode == 5);
@@ -830,25 +755,11 @@ __device__ __forceinline__ void proj_resolve_rounds(const ProjPair& P, const Pro
             const int t1 = qres[q];
             if (t1 < 0 || t1 == kFree) continue;
             const int bin = orbm::rot_bin(P.qang ? P.qang[q] : P.qkeys[q].angle, P.tkeys[t1].angle);
-            atomicAdd(&hist[bin], 1);
+            atomicAdd(&rot.bins[bin], 1);
             best1[q] = bin;  // (the table is free now)
         }
         __syncthreads();
-        if (tid < 64) {   // (the first wave: its lanes fetch the bins in ONE LDS trip, lane 0 then walks them in registers --
-                          // thirty dependent LDS reads by one thread were 3 us with the whole workgroup waiting)
-            const int hl = hist[tid & 31];
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-#pragma unroll
-            for (int i = 0; i < orbm::kHistoLength; i++) {
-                const int s = __builtin_amdgcn_readlane(hl, i);
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-            if (tid == 0) { sInd[0] = ind1; sInd[1] = ind2; sInd[2] = ind3; }
-        }
+        orbm::rot_three_maxima(rot);
         __syncthreads();
     }
     // every assign entry is written ONCE (it may live in pinned host memory): the pruning goes through the LDS table
@@ -857,8 +768,7 @@ __device__ __forceinline__ void proj_resolve_rounds(const ProjPair& P, const Pro
         for (int q = tid; q < nq; q += kThreads) {
             const int t1 = qres[q];
             if (t1 < 0 || t1 == kFree) continue;
-            const int bin = best1[q];
-            if (bin != sInd[0] && bin != sInd[1] && bin != sInd[2]) { winner[t1] = -2; nPruned++; }
+            if (orbm::rot_outlier(rot, best1[q])) { winner[t1] = -2; nPruned++; }
         }
     }
     __syncthreads();
@@ -868,14 +778,10 @@ __device__ __forceinline__ void proj_resolve_rounds(const ProjPair& P, const Pro
         else if (P.initAssign || w >= 0) P.assign[t] = w;
         P.toccOut[t] = occBy[t] != kFree;
     }
-    int local = nAcc - nPruned;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d);
-    if ((tid & 63) == 0 && local) atomicAdd(sCount, local);
-    __syncthreads();
+    orbm::rot_count(rot, nAcc - nPruned);
     if (tid == 0) {
         if (nq > 0 && nt > 0) *P.total = 0;  // left zero for the next call's candidate kernel
-        *P.nmatch = *sCount;
+        *P.nmatch = rot.count;
         if (P.stats) { P.stats[0] = (nq > 0 && nt > 0) ? round + 1 : 0; P.stats[1] = total; }
     }
     proj_publish(P);
@@ -884,14 +790,13 @@ __device__ __forceinline__ void proj_resolve_rounds(const ProjPair& P, const Pro
 
 // the resolve's few static words, declared ONCE in the kernel (a __shared__ inside the templated body would be laid out once per
 // instantiation, and every byte of static LDS comes off the dynamic budget the plan hands out: kProjLdsBudget)
-struct ResolveShared { int hist[32]; int sPending[3]; int sInd[3]; int sCount; int sLive[2]; };
+struct ResolveShared { orbm::RotShared rot; int sPending[3]; int sLive[2]; };
 
 template <bool TLDS>
 __device__ __forceinline__ void proj_resolve_body(const ProjPair& P, const ProjCommon& c, ResolveShared& rs)
 {
     extern __shared__ __attribute__((aligned(16))) int32_t tl[];
-    int* const hist = rs.hist; int* const sPending = rs.sPending; int* const sInd = rs.sInd; int* const sLive = rs.sLive;
-    int& sCount = rs.sCount;
+    int* const sPending = rs.sPending; int* const sLive = rs.sLive;
     int32_t* occBy;                        // kFree, -1 (occupied on entry) or the blocking query that took the feature
     if constexpr (TLDS) occBy = tl; else occBy = P.tscr;
     int32_t* minUnd0 = occBy + c.tCap;     // keyed by round (proj_resolve_rounds)
@@ -907,17 +812,16 @@ __device__ __forceinline__ void proj_resolve_body(const ProjPair& P, const ProjC
         minUnd0[t] = 0;   // (no round has posted yet)
         winner[t] = -1;
     }
-    if (tid < 32) hist[tid] = 0;
+    orbm::rot_clear(rs.rot);
     if (tid < 3) sPending[tid] = 0;
-    if (tid == 0) sCount = 0;
     if (total > P.candCap) {  // nothing was listed past the arena; the caller grows it and calls again
         __syncthreads();
         if (tid == 0) { *P.total = 0; *P.nmatch = -total - 1; if (P.stats) { P.stats[0] = 0; P.stats[1] = total; } }
         proj_publish(P);
         return;
     }
-    if (TLDS && total <= c.ldsCand && nq <= c.qCap) proj_resolve_rounds<true>(P, c, nq, nt, total, occBy, minUnd0, winner, qtab, hist, sPending, sInd, &sCount, sLive);
-    else proj_resolve_rounds<false>(P, c, nq, nt, total, occBy, minUnd0, winner, qtab, hist, sPending, sInd, &sCount, sLive);
+    if (TLDS && total <= c.ldsCand && nq <= c.qCap) proj_resolve_rounds<true>(P, c, nq, nt, total, occBy, minUnd0, winner, qtab, rs.rot, sPending, sLive);
+    else proj_resolve_rounds<false>(P, c, nq, nt, total, occBy, minUnd0, winner, qtab, rs.rot, sPending, sLive);
 }
 
 __global__ __launch_bounds__(kCandThreads) void k_proj_candidates(const ProjPair* __restrict__ pairs, ProjCommon c)

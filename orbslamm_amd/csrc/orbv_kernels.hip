@@ -25,14 +25,6 @@ struct VocDev {
     int32_t L, scoring, weighting;
 };
 
-__device__ __forceinline__ int ham256(const uint32_t q[8], const uint32_t* __restrict__ t)
-{
-    int d = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) d += __popc(q[i] ^ t[i]);
-    return d;
-}
-
 // one thread per feature: L sequential k-way Hamming argmins, first child wins ties
 __global__ void k_voc_descend(VocDev v, const uint8_t* __restrict__ desc, int n, int levelsup,
                               uint32_t* __restrict__ word, uint32_t* __restrict__ node, double* __restrict__ w)
@@ -50,9 +42,9 @@ __global__ void k_voc_descend(VocDev v, const uint8_t* __restrict__ desc, int n,
         ++level;
         const int cs = v.childStart[finalId], ce = v.childStart[finalId + 1];
         finalId = cs;
-        int best = ham256(q, (const uint32_t*)(v.desc + (int64_t)cs * 32));
+        int best = orbx::hamming256(q, (const uint32_t*)(v.desc + (int64_t)cs * 32));
         for (int c = cs + 1; c < ce; c++) {
-            const int d = ham256(q, (const uint32_t*)(v.desc + (int64_t)c * 32));
+            const int d = orbx::hamming256(q, (const uint32_t*)(v.desc + (int64_t)c * 32));
             if (d < best) { best = d; finalId = c; }
         }
         if (level == nidLevel) nid = (uint32_t)v.childIdx[finalId];
@@ -362,9 +354,9 @@ __global__ void k_voc_descend_set(VocDev v, VocSetArgs a, int levelsup)
         ++level;
         const int cs = v.childStart[finalId], ce = v.childStart[finalId + 1];
         finalId = cs;
-        int best = ham256(q, (const uint32_t*)(v.desc + (int64_t)cs * 32));
+        int best = orbx::hamming256(q, (const uint32_t*)(v.desc + (int64_t)cs * 32));
         for (int c = cs + 1; c < ce; c++) {
-            const int d = ham256(q, (const uint32_t*)(v.desc + (int64_t)c * 32));
+            const int d = orbx::hamming256(q, (const uint32_t*)(v.desc + (int64_t)c * 32));
             if (d < best) { best = d; finalId = c; }
         }
         if (level == nidLevel) nid = (uint32_t)v.childIdx[finalId];

@@ -106,4 +106,30 @@ __device__ __forceinline__ int wave_incl_scan(int v)
     return v;
 }
 
+// Exclusive scan of one value per thread over a workgroup of Threads; returns the exclusive prefix, *total = the sum.  wsum:
+// Threads / 64 ints of LDS.  Every thread of the workgroup must call it (two barriers).
+template <int Threads>
+__device__ __forceinline__ int block_scan_excl(int v, int* wsum, int* total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int incl = wave_incl_scan(v);
+    __syncthreads();  // wsum may still be read from the previous use
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int woff = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < Threads / 64; w++) { const int s = wsum[w]; if (w < wave) woff += s; tot += s; }
+    *total = tot;
+    return woff + incl - v;
+}
+
+// DescriptorDistance (ORBmatcher.cc:1649-1665) of two 256-bit descriptors as 8 dwords: 8 x (v_xor + v_bcnt)
+__device__ __forceinline__ int hamming256(const uint32_t q[8], const uint32_t* __restrict__ t)
+{
+    int d = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) d += __popc(q[i] ^ t[i]);
+    return d;
+}
+
 }  // namespace orbx

@@ -2420,9 +2420,7 @@ __global__ __launch_bounds__(256) void k_stereo_match(StereoArgs a)
             if (r.octave < levelL - 1 || r.octave > levelL + 1) continue;
             if (!(r.x >= minU && r.x <= maxU)) continue;
             const uint32_t* tp = (const uint32_t*)(a.dR + (int64_t)j * 32);
-            int d = 0;
-#pragma unroll
-            for (int i = 0; i < 8; i++) d += __popc(q[i] ^ tp[i]);
+            const int d = hamming256(q, tp);
             if (d < 100) key = min(key, ((uint32_t)d << 16) | (uint32_t)j);  // bestDist starts at TH_HIGH, strict <
         }
     }
