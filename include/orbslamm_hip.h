@@ -982,4 +982,6 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 /* Tracking::SearchLocalPoints and TrackWithMotionModel's projections from a map-point pool in HBM (orbw_pool_*,
  * orbw_view_project, orbw_track_local_map, orbw_track_frame_pose) are the same library's and are declared in orbslamm_mappool.h. */
 #include "orbslamm_mappool.h"
+/* Tracking::UpdateLocalMap from a keyframe store beside that pool (orbu_*, orbw_track_local_map_resident): orbslamm_localmap.h. */
+#include "orbslamm_localmap.h"
 #endif

@@ -53,6 +53,7 @@
 #include "orbo_kernels.hip"
 #include "orbz_kernels.hip"
 #include "orbw_kernels.hip"   // the map-point pool and the projections of the two tracking searches
+#include "orbu_kernels.hip"   // UpdateLocalMap: the keyframe vote, the local keyframe list, the local point list
 
 using namespace orbx;
 
@@ -211,3 +212,4 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbo_host.inc"   // PoseOptimization
 #include "orbz_host.inc"   // OptimizeSim3
 #include "orbw_host.inc"   // the map-point pool: SearchLocalPoints and TrackWithMotionModel's search from resident MapPoints
+#include "orbu_host.inc"   // the keyframe store beside the pool: UpdateLocalMap, and SearchLocalPoints from its resident list

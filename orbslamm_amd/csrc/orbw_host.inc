@@ -259,12 +259,15 @@ extern "C" int orbw_view_project_frame(orbm_frameset_t* fs, int last_slot, orbw_
 
 // track_queries (orbt_host.inc) with the query block made on the device: the set's staging holds pair record | occupancy (the
 // head, brought up by the projection kernel's last workgroups) | ids (read where they lie); the device twin holds the query
-// block behind them; the status bytes go straight into the pinned share.  qslot >= 0: the frame/frame gate set
+// block behind them; the status bytes go straight into the pinned share.  qslot >= 0: the frame/frame gate set.  devIds: the
+// ids lie on the device already (a keyframe store's S, orbu_host.inc: made there from set slots, so not checked again); `ids`
+// is then null and nothing per query goes up
 static int orbw_track(orbm_frameset_t* fs, int slot, int qslot, orbw_pool* pool, const OrbmProjParams* pp, const OrbwView* view, const int32_t* ids,
-                      int nq, float th, const float* scale_factors, const float* level_breaks, int nlevels, const uint8_t* t_occ)
+                      int nq, float th, const float* scale_factors, const float* level_breaks, int nlevels, const uint8_t* t_occ,
+                      const int32_t* devIds = nullptr)
 {
     const bool frame = qslot >= 0;
-    int rc = orbw_check_args(view, ids, nq, scale_factors, level_breaks, frame ? 1 : nlevels, frame);
+    int rc = orbw_check_args(view, devIds ? devIds : ids, nq, scale_factors, level_breaks, frame ? 1 : nlevels, frame);
     if (rc) return rc;
     if (!pp) return fail(ORBX_E_INVALID, "null argument");
     if ((rc = frameset_check(fs)) || (rc = orbw_pool_check(pool))) return rc;
@@ -276,7 +279,7 @@ static int orbw_track(orbm_frameset_t* fs, int slot, int qslot, orbw_pool* pool,
     const size_t C = (size_t)fs->cap, S = (size_t)fs->slots;
     if ((size_t)nq > S * C || nq > orbt::kMaxQueryIters * orbt::kThreads)
         return fail(ORBX_E_UNSUPPORTED, "%d queries: the set's scratch holds slots x cap = %zu", nq, S * C);
-    {   // (set bits are never cleared: ids good now are good at the launch below)
+    if (!devIds) {   // (set bits are never cleared: ids good now are good at the launch below)
         std::lock_guard<std::mutex> l(pool->mu);
         if ((rc = orbw_check_ids(pool, ids, nq, frame))) return rc;
     }
@@ -284,7 +287,7 @@ static int orbw_track(orbm_frameset_t* fs, int slot, int qslot, orbw_pool* pool,
     ResultRecord& r = fs->res.rec[set];
     Packer pk;
     const size_t oPair = pk.take(sizeof(orbt::ProjPair)), oOcc = t_occ ? pk.take(C) : 0, head = pk.off;
-    const size_t oIds = pk.take((size_t)nq * 4);
+    const size_t oIds = pk.take(devIds ? 0 : (size_t)nq * 4);
     const size_t oUvr = pk.take((size_t)nq * 12), oLvl = pk.take((size_t)nq * 2), oQd = frame ? 0 : pk.take((size_t)nq * 32);
     const size_t oQv = pk.take((size_t)nq), oQo = pk.take((size_t)nq), oSt = pk.take((size_t)nq);
     const size_t total = pk.off;
@@ -300,7 +303,7 @@ static int orbw_track(orbm_frameset_t* fs, int slot, int qslot, orbw_pool* pool,
     if (!c.big) c.lanes = cand_lanes(1);
     uint8_t* hs = fs->h_q + (size_t)set * fs->qBytes;
     uint8_t* ds = fs->d_q + (size_t)set * fs->qBytes;
-    if (nq) memcpy(hs + oIds, ids, (size_t)nq * 4);
+    if (nq && !devIds) memcpy(hs + oIds, ids, (size_t)nq * 4);
     if (t_occ) memcpy(hs + oOcc, t_occ, C);
     const SetTables t = set_tables(fs, set);
     orbt::ProjPair P{};
@@ -322,7 +325,7 @@ static int orbw_track(orbm_frameset_t* fs, int slot, int qslot, orbw_pool* pool,
     r.pp = *pp; r.builds = fs->builds; r.slot = slot; r.qslot = qslot; r.nq = nq; r.total = head; r.qEpoch = fs->qEpoch;
     r.fromPool = true; r.oStatus = oSt;
     orbw::ProjectArgs a{};
-    a.pool = pool->dev; a.ids = (const int32_t*)(hs + oIds); a.nq = nq;
+    a.pool = pool->dev; a.ids = devIds ? devIds : (const int32_t*)(hs + oIds); a.nq = nq;
     a.lastKeys = frame ? fs->fs.keysUn + (size_t)qslot * C : nullptr; a.lastN = frame ? fs->fs.n + qslot : nullptr;
     a.quvr = (float*)(ds + oUvr); a.qlvl = (int8_t*)(ds + oLvl); a.qdesc = frame ? nullptr : (uint4*)(ds + oQd); a.qvalid = ds + oQv; a.qobs = ds + oQo;
     a.viewcos = nullptr; a.status = hs + oSt;

@@ -165,3 +165,172 @@ class MapPool:
         if n.value == 0:
             return np.zeros(0, np.uint8)
         return np.ctypeslib.as_array(C.cast(st, C.POINTER(C.c_uint8)), shape=(n.value,))
+
+
+# ---- Tracking::UpdateLocalMap from a keyframe store beside the pool (include/orbslamm_localmap.h)
+ENTRY_NO_VOTE = 1 << 30
+KF_BAD, KF_SET = 1, 2
+MAX_NEIGHBOURS = 10
+LOCAL_OK, LOCAL_NO_VOTES = 0, 1
+
+
+class OrbuKeyFrames(C.Structure):
+    _fields_ = [("nkf", C.c_int32), ("slot", C.c_void_p), ("flags", C.c_void_p), ("n", C.c_void_p), ("entries", C.c_void_p), ("neigh", C.c_void_p),
+                ("parent", C.c_void_p), ("nchildren", C.c_void_p), ("children", C.c_void_p)]
+
+
+class OrbuResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("kf_max", C.c_int32), ("nkf", C.c_int32), ("nL", C.c_int32), ("nS", C.c_int32), ("kf", C.c_void_p),
+                ("L", C.c_void_p), ("seen", C.c_void_p), ("votes", C.c_void_p)]
+
+
+def _setup_store(L):
+    if getattr(L, "_orbu_ready", False):
+        return
+    vp = C.c_void_p
+    L.orbu_store_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.orbu_store_destroy.argtypes = [vp]
+    L.orbu_kf_set.argtypes = [vp, vp]
+    L.orbu_kf_set_graph.argtypes = [vp, vp]
+    L.orbu_kf_set_flags.argtypes = [vp, vp, vp, C.c_int]
+    L.orbu_kf_set_entries.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+    L.orbu_update_local_map.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    L.orbu_local_points.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
+    L.orbu_debug_set_generation.argtypes = [vp, C.c_uint32]
+    L.orbu_debug_resident_list.argtypes = [vp, vp, C.c_int, vp]
+    L.orbw_track_local_map_resident.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_float, vp, vp, C.c_int, vp]
+    L._orbu_ready = True
+
+
+def _concat(lists):
+    lists = [_ids(a) for a in lists]
+    n = np.array([a.shape[0] for a in lists], np.int32)
+    flat = np.concatenate(lists).astype(np.int32) if len(lists) and n.sum() else np.zeros(0, np.int32)
+    return n, np.ascontiguousarray(flat)
+
+
+class LocalMap:
+    """what orbu_update_local_map / orbu_local_points left in the store's pinned block: status, kf_max, nkf, nL, nS, and the arrays
+    kf (the local keyframes), L (mvpLocalMapPoints), seen, S (= L[seen == 0], derived on the host; KeyFrameStore.resident_list() is the device's own)
+    and votes (per slot, update only; else None).  An array is copied out of the block when it is first read: read it before the
+    store's next call"""
+
+    def __init__(self, r, kf_capacity, store=None):
+        self._store = store
+        self.status, self.kf_max, self.nkf, self.nL, self.nS = r.status, r.kf_max, r.nkf, r.nL, r.nS
+        self._r, self._kfcap, self._got = r, kf_capacity, {}
+
+    def _arr(self, name, p, n, ct, dt):
+        if name not in self._got:
+            self._got[name] = np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).astype(dt, copy=True) if p and n else np.zeros(0, dt)
+        return self._got[name]
+
+    kf = property(lambda self: self._arr("kf", self._r.kf, self.nkf, C.c_int32, np.int32))
+    L = property(lambda self: self._arr("L", self._r.L, self.nL, C.c_int32, np.int32))
+    seen = property(lambda self: self._arr("seen", self._r.seen, self.nL, C.c_uint8, np.uint8))
+    S = property(lambda self: self.L[self.seen == 0])
+    resident = property(lambda self: self._store.resident_list())   # the device's own S (a copy down: for tests)
+    votes = property(lambda self: self._arr("votes", self._r.votes, self._kfcap, C.c_int32, np.int32) if self._r.votes else None)
+
+
+class KeyFrameStore:
+    """`kf_capacity` keyframes (match lists of `stride` pool ids, flags, covisibility / spanning-tree records) in HBM beside
+    a MapPool (orbu_*)."""
+
+    def __init__(self, pool, kf_capacity, stride, max_children, max_local_points):
+        self._L = lib()
+        _setup_store(self._L)
+        self._pool = pool
+        self.kf_capacity, self.stride, self.max_children, self.max_local_points = int(kf_capacity), int(stride), int(max_children), int(max_local_points)
+        self._h = C.c_void_p()
+        check(self._L.orbu_store_create(pool._h, self.kf_capacity, self.stride, self.max_children, self.max_local_points, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.orbu_store_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _records(self, slots, flags, entries, neigh, parent, children):
+        slots = _ids(slots)
+        nkf = slots.shape[0]
+        keep = [slots]
+        rec = OrbuKeyFrames(nkf=nkf, slot=ptr(slots))
+        if flags is not None:
+            fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+            n, ent = _concat(entries)
+            assert fl.shape[0] == nkf and n.shape[0] == nkf
+            rec.flags, rec.n, rec.entries = ptr(fl), ptr(n), ptr(ent)
+            keep += [fl, n, ent]
+        ng = np.full((nkf, MAX_NEIGHBOURS), -1, np.int32)
+        for i, row in enumerate(neigh):
+            row = _ids(row)
+            assert row.shape[0] <= MAX_NEIGHBOURS
+            ng[i, :row.shape[0]] = row
+        par = _ids(parent)
+        nc, ch = _concat(children)
+        assert par.shape[0] == nkf and nc.shape[0] == nkf
+        rec.neigh, rec.parent, rec.nchildren, rec.children = ptr(ng), ptr(par), ptr(nc), ptr(ch)
+        keep += [ng, par, nc, ch]
+        return rec, keep
+
+    def set(self, slots, flags, entries, neigh, parent, children):
+        """orbu_kf_set: whole records.  entries[i]: keyframe i's GetMapPointMatches() as pool ids (-1 empty, | ENTRY_NO_VOTE);
+        neigh[i]: up to 10 slots; parent[i]: slot or -1; children[i]: slots"""
+        rec, keep = self._records(slots, flags, entries, neigh, parent, children)
+        check(self._L.orbu_kf_set(self._h, C.byref(rec)))
+
+    def set_graph(self, slots, neigh, parent, children):
+        rec, keep = self._records(slots, None, None, neigh, parent, children)
+        check(self._L.orbu_kf_set_graph(self._h, C.byref(rec)))
+
+    def set_flags(self, slots, flags):
+        slots = _ids(slots)
+        fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+        assert fl.shape[0] == slots.shape[0]
+        check(self._L.orbu_kf_set_flags(self._h, ptr(slots), ptr(fl), slots.shape[0]))
+
+    def set_entries(self, slot, idx, vals):
+        idx, vals = _ids(idx), _ids(vals)
+        assert idx.shape[0] == vals.shape[0]
+        check(self._L.orbu_kf_set_entries(self._h, int(slot), ptr(idx), ptr(vals), idx.shape[0]))
+
+    def update(self, frame_ids, max_keyframes=80):
+        """orbu_update_local_map -> LocalMap (status LOCAL_NO_VOTES: nothing else is meaningful)"""
+        ids = _ids(frame_ids)
+        r = OrbuResult()
+        check(self._L.orbu_update_local_map(self._h, ptr(ids), ids.shape[0], int(max_keyframes), C.byref(r)))
+        return LocalMap(r, self.kf_capacity, self)
+
+    def local_points(self, kf_list, frame_ids):
+        """orbu_local_points: UpdateLocalPoints alone over the caller's keyframe list"""
+        kf, ids = _ids(kf_list), _ids(frame_ids)
+        r = OrbuResult()
+        check(self._L.orbu_local_points(self._h, ptr(kf), kf.shape[0], ptr(ids), ids.shape[0], C.byref(r)))
+        return LocalMap(r, self.kf_capacity, self)
+
+    def debug_set_generation(self, generation):
+        check(self._L.orbu_debug_set_generation(self._h, C.c_uint32(int(generation))))
+
+    def resident_list(self):
+        """orbu_debug_resident_list: the S of the last completed update as it lies on the device"""
+        out, n = np.zeros(self.max_local_points, np.int32), C.c_int(0)
+        check(self._L.orbu_debug_resident_list(self._h, ptr(out), out.shape[0], C.byref(n)))
+        return out[:n.value].copy()
+
+    def track_local_map(self, fs, slot, view_rec, th, scale_factors, breaks, t_occ=None, th_dist=100, nnratio=0.8, mode=3):
+        """orbw_track_local_map_resident: MapPool.track_local_map with ids = the S of this store's last update, read where it
+        lies; assign[t] = position in S"""
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32)
+        br = np.ascontiguousarray(breaks, dtype=np.float32)
+        assert br.shape[0] == sf.shape[0] + 1
+        v = np.ascontiguousarray(view_rec, dtype=VIEW_DTYPE)
+        pp = OrbmProjParams(int(mode), float(nnratio), 0, int(th_dist))
+        occ = MapPool._occ(fs, t_occ)
+        check(self._L.orbw_track_local_map_resident(fs._h, int(slot), self._pool._h, self._h, C.byref(pp), ptr(v), C.c_float(th), ptr(sf), ptr(br),
+                                                    sf.shape[0], ptr(occ)))
