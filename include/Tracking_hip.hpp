@@ -28,6 +28,24 @@
 // order: the frame's bad matches nulled (:1306), the keyframes' and points' mnTrackReferenceForFrame (:1335, :1358, :1373, :1385,
 // :1282), the two vectors, mpReferenceKF / F.mpReferenceKF (:1392-1396).  On ORBU_NO_VOTES the lists of keyframes stay (:1311) and
 // UpdateLocalPoints runs over the old one (orbu_local_points).  A refusal throws with nothing touched.
+//
+// And for the line behind the search in Tracking::TrackWithMotionModel (:947-977) and Tracking::TrackLocalMap (:990-1023), monocular, on
+// orbq_track_pose (include/orbslamm_trackpose.h): PoseOptimization from the pool, the resident frame and the search's own
+// table, and the loop behind it.
+//
+//   iORB_SLAM::TrackWithMotionModelT<Frame, MapPoint>::Finish(h, fs, slot, pool, mCurrentFrame, mLastFrame.mvpMapPoints, mbOnlyTracking);
+//   iORB_SLAM::TrackLocalMapT<Frame, KeyFrame, MapPoint>::Finish(h, fs, slot, pool, mCurrentFrame, baseIds, idOfPoint, verdict);
+//   iORB_SLAM::TrackLocalMapT<Frame, KeyFrame, MapPoint>::Run(h, fs, slot, cap, pool, store, mCurrentFrame, mvpLocalKeyFrames,
+//                                                             mvpLocalMapPoints, mpReferenceKF, idOfPoint, slotOfKF, kfOfSlot, pointOfId, opt);
+//
+// TrackWithMotionModelT::Finish stands behind orbw_track_frame_pose issued against (fs, slot) with mLastFrame's ids and `nmatches >= 20`
+// (:944, the caller's, from orbm_track_results): it merges the table into mvpMapPoints (ORBmatcher.cc:1430), and writes back in the
+// reference's order what PoseOptimization and :952-969 write: mvbOutlier, SetPose, the discarded slots, mbTrackInView and mnLastFrameSeen
+// of the discarded points.  TrackLocalMapT::Finish stands behind SearchLocalPointsT::Run / RunResident, which has merged the table already:
+// mvbOutlier, SetPose, IncreaseFound(1) on the inliers (:1000), mnMatchesInliers and the verdict of :1017-1023, the mnLastRelocFrameId rule
+// applied from arguments.  Run composes UpdateLocalMapT::Run, SearchLocalPointsT::RunResident and Finish.  The counts come from the
+// device (the pool's observed bit): the pool's update rule keeps it equal to Observations() > 0.  A refusal throws with the frame's pose,
+// flags and points as the step before left them.
 #pragma once
 
 #include <algorithm>
@@ -235,6 +253,142 @@ struct UpdateLocalMapT {
         }
         Result res; res.status = noVotes ? ORBU_NO_VOTES : ORBU_OK; res.nkf = (int)vpLocalKeyFrames.size(); res.nL = r.nL; res.nS = r.nS;
         return res;
+    }
+};
+
+namespace detail {
+
+// mTcw and the camera of a frame as orbq_track_pose takes them
+template <class Frame>
+inline OrbqJob track_pose_job(orbm_frameset_t* fs, int slot, int back, const int32_t* baseIds, int discard, const Frame& F)
+{
+    OrbqJob J;
+    J.fs = fs; J.slot = slot; J.back = back; J.base_ids = baseIds; J.n = F.N; J.discard = discard;
+    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) J.frame.Tcw[4 * r + c] = F.mTcw.template at<float>(r, c);
+    J.frame.K[0] = Frame::fx; J.frame.K[1] = Frame::fy; J.frame.K[2] = Frame::cx; J.frame.K[3] = Frame::cy;
+    return J;
+}
+
+// Optimizer.cc:470: pFrame->SetPose(pose) -- reached only with 3 correspondences or more (:386)
+template <class Frame>
+inline void set_pose(Frame& F, const OrboResult& opt)
+{
+    if (opt.rounds <= 0) return;
+    auto pose = F.mTcw.clone();
+    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) pose.template at<float>(r, c) = opt.Tcw[4 * r + c];
+    F.SetPose(pose);
+}
+
+}  // namespace detail
+
+template <class Frame, class MapPoint>
+struct TrackWithMotionModelT {
+    struct Result { bool ok; bool vo; int nmatches; int nmatchesMap; OrboResult opt; };
+
+    // vpLastMapPoints: mLastFrame.mvpMapPoints, the queries of the search (orbw_track_frame_pose's last_ids are their pool ids);
+    // back: which of the set's last searches that was.  result.vo is mbVO as :973 would set it (meaningful under onlyTracking)
+    static Result Finish(orbm_t* h, orbm_frameset_t* fs, int slot, orbw_pool_t* pool, Frame& F, const std::vector<MapPoint*>& vpLastMapPoints,
+                         bool onlyTracking, int back = 0)
+    {
+        const char* who = "TrackWithMotionModel(HIP): ";
+        const int32_t* assign = nullptr;
+        detail::check(orbm_track_results(fs, back, &assign, nullptr, nullptr, nullptr), who);
+        const int N = F.N;
+        for (int t = 0; t < N; t++)
+            if (assign[t] >= (int)vpLastMapPoints.size()) throw std::runtime_error(std::string(who) + "the search's table names a query the list does not hold");
+        const OrbqJob J = detail::track_pose_job(fs, slot, back, nullptr, 1, F);
+        OrbqResult r;
+        std::vector<int32_t> ids((size_t)N + 1);
+        std::vector<uint8_t> outlier((size_t)N + 1);
+        int32_t* pi = ids.data(); uint8_t* po = outlier.data();
+        detail::check(orbq_track_pose(h, pool, &J, 1, F.mvInvLevelSigma2.data(), (int)F.mvInvLevelSigma2.size(), &r, &pi, &po), who);
+        // the device merged the table into NULLs (:940's fill) and discarded the outliers: the frame must have been filled with NULL
+        // before the search, and the ids that come back must be the table's matches without the flagged ones
+        for (int t = 0; t < N; t++) {
+            if (assign[t] < 0 && F.mvpMapPoints[t]) throw std::runtime_error(std::string(who) + "mvpMapPoints was not filled with NULL before the search (Tracking.cc:940)");
+            if ((ids[t] >= 0) != (assign[t] >= 0 && !outlier[t]) || (outlier[t] && assign[t] < 0))
+                throw std::runtime_error(std::string(who) + "the ids returned are not the search's matches without the outliers");
+        }
+        // ---- the replay, in the reference's order
+        for (int t = 0; t < N; t++)
+            if (assign[t] >= 0) F.mvpMapPoints[t] = vpLastMapPoints[(size_t)assign[t]];   // ORBmatcher.cc:1430
+        for (int i = 0; i < N; i++)
+            if (F.mvpMapPoints[i]) F.mvbOutlier[i] = outlier[i] != 0;   // Optimizer.cc:310, :410, :416
+        detail::set_pose(F, r.opt);   // :470
+        for (int i = 0; i < N; i++) {   // Tracking.cc:952-969
+            if (!F.mvpMapPoints[i] || !F.mvbOutlier[i]) continue;
+            MapPoint* pMP = F.mvpMapPoints[i];
+            F.mvpMapPoints[i] = static_cast<MapPoint*>(NULL);
+            F.mvbOutlier[i] = false;
+            pMP->mbTrackInView = false;
+            pMP->mnLastFrameSeen = F.mnId;
+        }
+        Result res;
+        res.opt = r.opt; res.nmatches = r.n_matches; res.nmatchesMap = r.n_matches_map;
+        res.vo = r.n_matches_map < 10;                                          // :973
+        res.ok = onlyTracking ? r.n_matches > 20 : r.n_matches_map >= 10;       // :974, :977
+        return res;
+    }
+};
+
+template <class Frame, class KeyFrame, class MapPoint>
+struct TrackLocalMapT {
+    struct Verdict {
+        bool onlyTracking = false;                 // mbOnlyTracking
+        long unsigned int lastRelocFrameId = 0;    // mnLastRelocFrameId
+        int maxFrames = 30;                        // mMaxFrames
+    };
+    struct Options {
+        Verdict verdict;
+        typename SearchLocalPointsT<Frame, MapPoint>::Options search;
+        int maxKeyFrames = 80;
+    };
+    struct Result { bool ok; int nMatchesInliers; int nMatches; int nMatchesMap; OrboResult opt; };
+
+    // baseIds[t]: the pool id of mvpMapPoints[t] as the search was issued (-1 = NULL), F.N of them; F.mvpMapPoints holds the search's
+    // matches already (SearchLocalPointsT's replay); back: which of the set's last searches that was
+    template <class IdOf>
+    static Result Finish(orbm_t* h, orbm_frameset_t* fs, int slot, orbw_pool_t* pool, Frame& F, const std::vector<int32_t>& baseIds, IdOf idOfPoint,
+                         const Verdict& v = Verdict(), int back = 0)
+    {
+        const char* who = "TrackLocalMap(HIP): ";
+        const int N = F.N;
+        if ((int)baseIds.size() < N) throw std::runtime_error(std::string(who) + "fewer ids than the frame has features");
+        const OrbqJob J = detail::track_pose_job(fs, slot, back, baseIds.data(), 0, F);
+        OrbqResult r;
+        std::vector<int32_t> ids((size_t)N + 1);
+        std::vector<uint8_t> outlier((size_t)N + 1);
+        int32_t* pi = ids.data(); uint8_t* po = outlier.data();
+        detail::check(orbq_track_pose(h, pool, &J, 1, F.mvInvLevelSigma2.data(), (int)F.mvInvLevelSigma2.size(), &r, &pi, &po), who);
+        for (int i = 0; i < N; i++)
+            if ((F.mvpMapPoints[i] ? (int32_t)idOfPoint(F.mvpMapPoints[i]) : -1) != ids[i])
+                throw std::runtime_error(std::string(who) + "the frame's points are not the merge of baseIds and that search");
+        // ---- the replay, in the reference's order
+        for (int i = 0; i < N; i++)
+            if (F.mvpMapPoints[i]) F.mvbOutlier[i] = outlier[i] != 0;   // Optimizer.cc:310, :410, :416
+        detail::set_pose(F, r.opt);   // :470
+        for (int i = 0; i < N; i++)   // Tracking.cc:994-1013
+            if (F.mvpMapPoints[i] && !F.mvbOutlier[i]) F.mvpMapPoints[i]->IncreaseFound(1);
+        Result res;
+        res.opt = r.opt; res.nMatches = r.n_matches; res.nMatchesMap = r.n_matches_map;
+        res.nMatchesInliers = v.onlyTracking ? r.n_matches : r.n_matches_map;   // :1001-1007
+        res.ok = !(F.mnId < v.lastRelocFrameId + (long unsigned int)v.maxFrames && res.nMatchesInliers < 50) && !(res.nMatchesInliers < 20);   // :1017-1023
+        return res;
+    }
+
+    // Tracking::TrackLocalMap: UpdateLocalMap, SearchLocalPoints from the list the update left on the device, PoseOptimization, the verdict
+    template <class IdOf, class SlotOf, class KfOf, class PointOf>
+    static Result Run(orbm_t* h, orbm_frameset_t* fs, int slot, int cap, orbw_pool_t* pool, orbu_store_t* store, Frame& F,
+                      std::vector<KeyFrame*>& vpLocalKeyFrames, std::vector<MapPoint*>& vpLocalMapPoints, KeyFrame*& pReferenceKF, IdOf idOfPoint,
+                      SlotOf slotOfKF, KfOf kfOfSlot, PointOf pointOfId, const Options& opt = Options())
+    {
+        UpdateLocalMapT<Frame, KeyFrame, MapPoint>::Run(store, F, vpLocalKeyFrames, vpLocalMapPoints, pReferenceKF, idOfPoint, slotOfKF, kfOfSlot, pointOfId,
+                                                        opt.maxKeyFrames);   // :985
+        std::vector<int32_t> baseIds((size_t)F.N, -1);   // (the update's replay has nulled the bad matches: what is left is what the search sees)
+        for (int i = 0; i < F.N; i++)
+            if (F.mvpMapPoints[i]) baseIds[(size_t)i] = (int32_t)idOfPoint(F.mvpMapPoints[i]);
+        SearchLocalPointsT<Frame, MapPoint>::RunResident(fs, slot, cap, pool, store, F, vpLocalMapPoints, opt.search);   // :987
+        return Finish(h, fs, slot, pool, F, baseIds, idOfPoint, opt.verdict);   // :990-1023
     }
 };
 

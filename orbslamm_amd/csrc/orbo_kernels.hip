@@ -198,46 +198,28 @@ struct Problem {
     __device__ __forceinline__ double chi2(const Pose& cand) const { return pass_chi2(a, e0, n, lane, cand, K, robust); }
 };
 
-__global__ __launch_bounds__(kLanes) void k_pose_optimize(Args a, int nFrames)
+// PoseOptimization behind its gather (:343-473): the frame's n edges lie in a.pw / a.uv from e0 on with their outlier bytes 0,
+// edge e written where lane e % 64 reads it (by that lane, or by another with a workgroup barrier in between).  Tcw and K4 are
+// the caller's pose and fx fy cx cy in memory; anyBad: an edge's octave (or, for orbq's prologue, a point) was refused -- the
+// record then says rounds = -1 and the host refuses the call.  Shared by k_pose_optimize and orbq::k_track_pose.
+__device__ __forceinline__ void solve_frame(const Args& a, const float* Tcw, const float* K4, int e0, int n, bool anyBad, OrboResult* out,
+                                            orbg::LmShared<6>& sLm, int lane)
 {
-    __shared__ orbg::LmShared<6> sLm;
-    const int f = blockIdx.x, lane = threadIdx.x;
-    if (f >= nFrames) return;
-    const FrameIn& F = a.frames[f];
-    const int e0 = F.e0, n = F.n;
-    OrboResult* out = a.out + f;
-    // the gather (Optimizer.cc:302-341): observation, information, world position of the lane's edges; mvbOutlier = false
-    bool bad = false;
-    for (int k = 0; k < kMaxEdgesPerLane; k++) {
-        const int e = lane + k * kLanes;
-        if (e >= n) break;
-        const OrboEdge ed = a.edges[e0 + e];
-        float u, v;
-        int oct;
-        if (F.keys) { const orbm::KeyDev kp = F.keys[ed.feature]; u = kp.x; v = kp.y; oct = kp.octave; }
-        else { const Obs o = a.obs[e0 + e]; u = o.u; v = o.v; oct = o.octave; }
-        const bool okOct = oct >= 0 && oct < a.nlevels;
-        bad |= !okOct;
-        a.pw[e0 + e] = make_float4(ed.Xw[0], ed.Xw[1], ed.Xw[2], okOct ? a.invSigma2[oct] : 0.f);
-        a.uv[e0 + e] = make_float2(u, v);
-        a.outlier[e0 + e] = 0;
-    }
-    const bool anyBad = __any(bad);
     if (lane == 0) {
-        for (int i = 0; i < 16; i++) out->Tcw[i] = F.Tcw[i];
+        for (int i = 0; i < 16; i++) out->Tcw[i] = Tcw[i];
         out->n_initial = n; out->n_good = 0; out->rounds = anyBad ? -1 : 0;   // (-1: an octave outside nlevels; the host refuses)
         for (int r = 0; r < kRounds; r++) { out->iterations[r] = 0; out->trials[r] = 0; out->lambda[r] = 0.0; out->chi2[r] = 0.0; }
     }
     if (anyBad || n < 3) return;   // :386
 
-    const Cam K = {(double)F.K[0], (double)F.K[1], (double)F.K[2], (double)F.K[3]};
-    Pose est = pose_of_tcw(F.Tcw);
+    const Cam K = {(double)K4[0], (double)K4[1], (double)K4[2], (double)K4[3]};
+    Pose est = pose_of_tcw(Tcw);
     Problem p = {a, e0, n, lane, K, true, est, est};
     orbg::LmState<6> lm;   // lambda, growth, flatSteps and the solver's x: they live across the rounds
     int nBad = 0, rounds = 0;
     for (int it = 0; it < kRounds; it++) {
         // every round starts from the caller's pose: mTcw is written only at the end (:399, :470)
-        est = pose_of_tcw(F.Tcw);
+        est = pose_of_tcw(Tcw);
         p.err = est;
         int nActive = 0;
         for (int k = 0; k < kMaxEdgesPerLane; k++) {
@@ -288,6 +270,32 @@ __global__ __launch_bounds__(kLanes) void k_pose_optimize(Args a, int nFrames)
         out->n_good = n - nBad;
         out->rounds = rounds;
     }
+}
+
+__global__ __launch_bounds__(kLanes) void k_pose_optimize(Args a, int nFrames)
+{
+    __shared__ orbg::LmShared<6> sLm;
+    const int f = blockIdx.x, lane = threadIdx.x;
+    if (f >= nFrames) return;
+    const FrameIn& F = a.frames[f];
+    const int e0 = F.e0, n = F.n;
+    // the gather (Optimizer.cc:302-341): observation, information, world position of the lane's edges; mvbOutlier = false
+    bool bad = false;
+    for (int k = 0; k < kMaxEdgesPerLane; k++) {
+        const int e = lane + k * kLanes;
+        if (e >= n) break;
+        const OrboEdge ed = a.edges[e0 + e];
+        float u, v;
+        int oct;
+        if (F.keys) { const orbm::KeyDev kp = F.keys[ed.feature]; u = kp.x; v = kp.y; oct = kp.octave; }
+        else { const Obs o = a.obs[e0 + e]; u = o.u; v = o.v; oct = o.octave; }
+        const bool okOct = oct >= 0 && oct < a.nlevels;
+        bad |= !okOct;
+        a.pw[e0 + e] = make_float4(ed.Xw[0], ed.Xw[1], ed.Xw[2], okOct ? a.invSigma2[oct] : 0.f);
+        a.uv[e0 + e] = make_float2(u, v);
+        a.outlier[e0 + e] = 0;
+    }
+    solve_frame(a, F.Tcw, F.K, e0, n, __any(bad), a.out + f, sLm, lane);
 }
 
 }  // namespace orbo

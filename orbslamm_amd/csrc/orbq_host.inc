@@ -1,0 +1,140 @@
+// orbq_host.inc -- host side of PoseOptimization fed from the map-point pool (part of orbslamm_hip.hip; kernel:
+// orbq_kernels.hip, ABI: include/orbslamm_trackpose.h, DESIGN.md §8s).  One call = the checks, one packed upload (job records |
+// the frames' ids before the search), ONE launch for all jobs on the handle's stream, one copy down (results | ids | outlier
+// bytes), one synchronise.  The searches' tables and ids are read where the searches left them: nothing per match goes up.
+
+static_assert(sizeof(OrbqJob) == 112 && sizeof(OrbqResult) == 184, "orbslamm_trackpose.h layouts");
+static_assert(ORBW_FLAG_OBSERVED == 2, "k_track_pose reads the observed bit");
+static_assert(sizeof(orbq::JobDev) == 136 && sizeof(orbo::FrameIn) == 104, "the per-frame upload sizes tools/trackpose_bench.py computes with");
+
+// what needs neither a handle nor a GPU.  Zero jobs are settled by the caller before this
+static int orbq_check_args(const OrbqJob* jobs, int n_jobs, const float* inv_level_sigma2, int nlevels, const OrbqResult* out,
+                           int32_t* const* ids_out, uint8_t* const* outlier_out)
+{
+    if (n_jobs < 0) return fail(ORBX_E_INVALID, "negative job count");
+    if (n_jobs > ORBO_MAX_FRAMES) return fail(ORBX_E_UNSUPPORTED, "%d jobs: above %d", n_jobs, ORBO_MAX_FRAMES);
+    if (!jobs || !out || !ids_out || !outlier_out) return fail(ORBX_E_INVALID, "null argument");
+    if (!inv_level_sigma2 || nlevels < 1 || nlevels > ORBX_MAX_LEVELS) return fail(ORBX_E_INVALID, "nlevels %d outside [1, %d] or no sigma table", nlevels, ORBX_MAX_LEVELS);
+    int64_t total = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const OrbqJob& J = jobs[j];
+        if (!J.fs) return fail(ORBX_E_INVALID, "job %d: null frame set", j);
+        if (J.n < 0) return fail(ORBX_E_INVALID, "job %d: negative feature count", j);
+        if (J.n > ORBO_MAX_EDGES) return fail(ORBX_E_UNSUPPORTED, "job %d: %d features: above %d", j, J.n, ORBO_MAX_EDGES);
+        if (J.back < -1 || J.back >= ResultRing::kSets) return fail(ORBX_E_INVALID, "job %d: back %d outside [-1, %d]", j, J.back, ResultRing::kSets - 1);
+        if (J.discard != 0 && J.discard != 1) return fail(ORBX_E_INVALID, "job %d: discard is 0 or 1", j);
+        if (J.n && (!ids_out[j] || !outlier_out[j])) return fail(ORBX_E_INVALID, "job %d: null output array", j);
+        total += J.n;
+        if (total > ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "more than %d features in one call (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
+    }
+    return ORBX_OK;
+}
+
+// (the pool's mutex is held) job j's search can still be read: its record, then where its table and its ids lie
+static int orbq_job_source(orbw_pool* pool, const OrbqJob& J, int j, orbq::JobDev& D)
+{
+    orbm_frameset* fs = J.fs;
+    D.assign = nullptr; D.ids = nullptr; D.nq = 0;
+    if (J.back < 0) return ORBX_OK;
+    const int set = fs->res.back(J.back);
+    const ResultRecord& r = fs->res.rec[set];
+    if (!r.ev || r.kind != ResultRecord::kQueries || !r.fromPool) return fail(ORBX_E_INVALID, "job %d: that search was not issued from a map-point pool", j);
+    if (r.slot != J.slot) return fail(ORBX_E_INVALID, "job %d: that search ran against slot %d, not %d", j, r.slot, J.slot);
+    if (r.pool != pool || r.poolSerial != pool->serial) return fail(ORBX_E_INVALID, "job %d: that search was issued from another pool", j);
+    if (!r.accepted) return fail(ORBX_E_INVALID, "job %d: that search has not been received through orbm_track_results", j);
+    if (r.qEpoch != fs->qEpoch) return fail(ORBX_E_CAPACITY, "job %d: a larger query search issued behind it reallocated the search's staging", j);
+    if (fs->slotBuilt[(size_t)J.slot] > r.builds) return fail(ORBX_E_CAPACITY, "job %d: slot %d has been rebuilt since the search was issued", j, J.slot);
+    if (r.store) {
+        const orbu_store* s = (const orbu_store*)r.store;
+        if (!live_has(s) || s->serial != r.storeSerial) return fail(ORBX_E_CAPACITY, "job %d: the keyframe store whose list the search read was destroyed", j);
+        if (s->updates != r.storeUpdates) return fail(ORBX_E_CAPACITY, "job %d: the keyframe store completed another update since the search was issued", j);
+        D.ids = s->out.S;
+    } else
+        D.ids = (const int32_t*)(fs->h_q + (size_t)set * fs->qBytes + r.oIds);
+    D.assign = set_tables(fs, set).assign;
+    D.nq = r.nq;
+    return ORBX_OK;
+}
+
+extern "C" int orbq_track_pose(orbm_t* h, orbw_pool_t* pool, const OrbqJob* jobs, int n_jobs, const float* inv_level_sigma2, int nlevels,
+                               OrbqResult* out, int32_t* const* ids_out, uint8_t* const* outlier_out)
+{
+    if (n_jobs == 0) return ORBX_OK;   // nothing to do: no argument is read, no handle needed
+    int rc = orbq_check_args(jobs, n_jobs, inv_level_sigma2, nlevels, out, ids_out, outlier_out);
+    if (rc) return rc;
+    if ((rc = orbm_check(h)) || (rc = orbw_pool_check(pool))) return rc;
+    if (pool->h->device != h->device) return fail(ORBX_E_INVALID, "the pool and the handle must share the device");
+    size_t total = 0, nBase = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const OrbqJob& J = jobs[j];
+        if ((rc = frameset_check(J.fs))) return rc;
+        if (J.fs->owner != h) return fail(ORBX_E_INVALID, "job %d: the frame set belongs to another handle", j);
+        if (J.slot < 0 || J.slot >= J.fs->slots) return fail(ORBX_E_INVALID, "job %d: slot %d outside the frame set", j, J.slot);
+        if (J.n > J.fs->cap) return fail(ORBX_E_INVALID, "job %d: %d features for a frame of at most %d", j, J.n, J.fs->cap);
+        // no search to stand behind: the slot's build may still run on the set's own stream
+        if (J.back < 0 && fs_stream(J.fs) != h->stream) HIPCHK(hipStreamSynchronize(fs_stream(J.fs)));
+        total += (size_t)J.n;
+        if (J.base_ids) nBase += (size_t)J.n;
+    }
+    Packer pk;
+    const size_t oJobs = pk.take((size_t)n_jobs * sizeof(orbq::JobDev)), oBase = pk.take(nBase * 4), upBytes = pk.off;
+    const size_t oPw = pk.take(total * sizeof(float4)), oUv = pk.take(total * sizeof(float2)), oFlags = pk.take(total), oMerged = pk.take(total * 4);
+    const size_t oOut = pk.take((size_t)n_jobs * sizeof(OrbqResult)), oIds = pk.take(total * 4), oOutl = pk.take(total), work = pk.off;
+    const size_t downBytes = work - oOut;
+    if ((rc = orbm_reserve(h, S_BLOCK, work)) || (rc = orbm_pinned(h, std::max(upBytes, downBytes)))) return rc;
+    uint8_t* hs = (uint8_t*)h->h_stage;
+    uint8_t* d = slot_ptr<uint8_t>(h, S_BLOCK);
+    orbq::JobDev* hj = (orbq::JobDev*)(hs + oJobs);
+    std::lock_guard<std::mutex> l(pool->mu);   // (held to the synchronise: no setter and no store update runs under the gather)
+    size_t f0 = 0, b0 = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const OrbqJob& J = jobs[j];
+        orbq::JobDev& D = hj[j];
+        if ((rc = orbq_job_source(pool, J, j, D))) return rc;
+        if (J.base_ids) {
+            for (int t = 0; t < J.n; t++) {
+                const int id = J.base_ids[t];
+                if (id == -1) continue;
+                if (id < 0 || id >= pool->cap) return fail(ORBX_E_INVALID, "job %d: base_ids[%d] = %d outside the pool of %d", j, t, id, pool->cap);
+                if (!pool->isSet(id)) return fail(ORBX_E_INVALID, "job %d: base_ids[%d] = %d was never set", j, t, id);
+            }
+            if (J.n) memcpy(hs + oBase + b0 * 4, J.base_ids, (size_t)J.n * 4);
+        }
+        memcpy(D.Tcw, J.frame.Tcw, sizeof D.Tcw);
+        memcpy(D.K, J.frame.K, sizeof D.K);
+        D.keys = J.fs->fs.keysUn + (size_t)J.slot * J.fs->cap;
+        D.nKeys = J.fs->fs.n + J.slot;
+        D.base = J.base_ids ? (const int32_t*)(d + oBase) + b0 : nullptr;
+        D.n = J.n; D.f0 = (int32_t)f0; D.discard = J.discard;
+        f0 += (size_t)J.n;
+        if (J.base_ids) b0 += (size_t)J.n;
+    }
+    orbq::Args a{};
+    a.o.pw = (float4*)(d + oPw); a.o.uv = (float2*)(d + oUv); a.o.outlier = d + oFlags;
+    for (int lv = 0; lv < ORBX_MAX_LEVELS; lv++) a.o.invSigma2[lv] = lv < nlevels ? inv_level_sigma2[lv] : 0.f;
+    a.o.nlevels = nlevels;
+    a.jobs = (const orbq::JobDev*)(d + oJobs);
+    a.pool = pool->dev;
+    a.merged = (int32_t*)(d + oMerged); a.idsOut = (int32_t*)(d + oIds); a.outlierOut = d + oOutl; a.out = (OrbqResult*)(d + oOut);
+    hipStream_t s = h->stream;
+    HIPCHK(hipMemcpyAsync(d, hs, upBytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d + oOut, 0, (size_t)n_jobs * sizeof(OrbqResult), s));   // (the records' padding word too: the same bytes every call)
+    hipLaunchKernelGGL(orbq::k_track_pose, dim3((unsigned)n_jobs), dim3(orbq::kLanes), 0, s, a, n_jobs);
+    HIPCHK(hipGetLastError());
+    if ((rc = orbw_mark_reader(pool, s))) return rc;
+    HIPCHK(hipMemcpyAsync(hs, d + oOut, downBytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const OrbqResult* hr = (const OrbqResult*)hs;
+    for (int j = 0; j < n_jobs; j++)
+        if (hr[j].opt.rounds < 0)
+            return fail(ORBX_E_INVALID, "job %d: an edge's octave lies outside [0, %d), or a feature at or above the slot's device count (or a match without a point of the pool) holds a point",
+                        j, nlevels);
+    memcpy(out, hr, (size_t)n_jobs * sizeof(OrbqResult));
+    f0 = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const size_t n = (size_t)jobs[j].n;
+        if (n) { memcpy(ids_out[j], hs + (oIds - oOut) + f0 * 4, n * 4); memcpy(outlier_out[j], hs + (oOutl - oOut) + f0, n); }
+        f0 += n;
+    }
+    return ORBX_OK;
+}

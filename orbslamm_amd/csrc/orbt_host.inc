@@ -376,6 +376,14 @@ struct ResultRecord {
     // not the pool; the status bytes lie at oStatus of the set's pinned share
     bool fromPool = false;
     size_t oStatus = 0;
+    // what orbq_track_pose (orbq_host.inc) needs to read the search's ids where they lie: the pool, the ids block's offset in
+    // the set's pinned share, or the keyframe store whose S they are with the count of its updates at the issue; `accepted`: the
+    // host has received the table through orbm_track_results with ORBX_OK
+    const void* pool = nullptr; uint64_t poolSerial = 0;     // (the serial: an object made later at the same address is another)
+    size_t oIds = 0;
+    const void* store = nullptr; uint64_t storeSerial = 0;
+    uint32_t storeUpdates = 0;
+    bool accepted = false;
 };
 struct ResultRing {   // kSets result sets in rotation: a caller may read up to kSets - 1 calls behind the newest
     static constexpr int kSets = 4;
@@ -385,7 +393,7 @@ struct ResultRing {   // kSets result sets in rotation: a caller may read up to 
     int back(int b) const { return (newest + kSets - b) % kSets; }
     int begin(int set)
     {
-        rec[set].kind = ResultRecord::kNone; rec[set].pairs = 0; rec[set].flagValue = 0;
+        rec[set].kind = ResultRecord::kNone; rec[set].pairs = 0; rec[set].flagValue = 0; rec[set].accepted = false;
         if (!rec[set].ev) HIPCHK(hipEventCreateWithFlags(&rec[set].ev, hipEventDisableTiming));
         return ORBX_OK;
     }
@@ -882,6 +890,7 @@ extern "C" int orbm_track_results(orbm_frameset_t* fs, int back, const int32_t**
     }
     for (int p = 0; p < r.pairs; p++)
         if (t.nmatch[p] < 0) return fail(ORBX_E_CAPACITY, "pair %d: %d candidates exceed the arena of %d", p, -t.nmatch[p] - 1, fs->candCapPair);
+    r.accepted = true;
     if (assign) *assign = t.assign;
     if (nmatches) *nmatches = t.nmatch;
     if (npairs) *npairs = r.pairs;

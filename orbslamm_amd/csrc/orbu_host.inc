@@ -13,6 +13,7 @@ constexpr size_t kStoreMaxEntries = (size_t)1 << 28;   // kf_capacity * pitch: p
 constexpr size_t kStoreStageBytes = (size_t)8 << 20;   // a setter launch's staged records
 
 struct orbu_store {
+    uint64_t serial = ++g_poolSerial;
     orbw_pool* pool = nullptr;
     int kfcap = 0, stride = 0, pitch = 0, maxc = 0, maxcP = 0, maxL = 0;
     uint8_t* d_block = nullptr;
@@ -27,6 +28,7 @@ struct orbu_store {
     int hi = 0;                                        // the highest set slot + 1
     uint32_t gen = 0;
     bool updated = false; int nS = 0;                  // the last update completed: S holds nS ids
+    uint32_t updates = 0;                              // updates begun so far: each overwrites S
     unsigned blocks = 1;                               // the point walk's grid at the most: one block a chunk of the whole store, <= 1 024
     int lastNkf = 0;                                   // the local keyframes of the last update: sizes the next update's grid
 };
@@ -314,7 +316,7 @@ static int orbu_run(orbu_store* s, bool given, const int32_t* kf_list, int nkf, 
     const size_t oIds = pk.take((size_t)n * 4), oList = pk.take((size_t)nkf * 4);
     if ((rc = grow_pinned(s->h_stage, s->stageCap, pk.off + 16, true, nullptr, &p->h->nHostAlloc))) return rc;
     if ((rc = orbw_wait_readers(p))) return rc;   // a resident search in flight reads S
-    s->updated = false;
+    s->updated = false; s->updates++;
     hipStream_t st = p->stream;
     if (s->gen == 0xffffffffu) {   // the tag wraps: one clear, and the tags start over
         HIPCHK(hipMemsetAsync(s->scr.stamp, 0, (size_t)p->cap * 8, st));
@@ -375,10 +377,11 @@ extern "C" int orbw_track_local_map_resident(orbm_frameset_t* fs, int slot, orbw
     if ((rc = orbu_store_check(store))) return rc;
     if (store->pool != pool) return fail(ORBX_E_INVALID, "the store belongs to another pool");
     int nS;
+    uint32_t updates;
     {
         std::lock_guard<std::mutex> l(pool->mu);
         if (!store->updated) return fail(ORBX_E_INVALID, "the store has no completed update");
-        nS = store->nS;
+        nS = store->nS; updates = store->updates;
     }
-    return orbw_track(fs, slot, -1, pool, pp, view, nullptr, nS, th, scale_factors, level_breaks, nlevels, t_occ, store->out.S);
+    return orbw_track(fs, slot, -1, pool, pp, view, nullptr, nS, th, scale_factors, level_breaks, nlevels, t_occ, store->out.S, store, store->serial, updates);
 }

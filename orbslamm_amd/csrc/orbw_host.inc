@@ -13,7 +13,10 @@ static_assert(ORBW_ST_BAD == orbw::ST_BAD && ORBW_ST_DEPTH == orbw::ST_DEPTH && 
 
 constexpr int kPoolChunk = 1 << 16;   // records per setter launch: the pinned staging is 5 MB at the most
 
+static std::atomic<uint64_t> g_poolSerial{0};   // pools and the stores beside them: one number each, never given twice
+
 struct orbw_pool {
+    uint64_t serial = ++g_poolSerial;
     orbm_handle* h = nullptr;   // device; a reference is held
     int cap = 0;
     uint8_t* d_block = nullptr;
@@ -261,10 +264,10 @@ extern "C" int orbw_view_project_frame(orbm_frameset_t* fs, int last_slot, orbw_
 // head, brought up by the projection kernel's last workgroups) | ids (read where they lie); the device twin holds the query
 // block behind them; the status bytes go straight into the pinned share.  qslot >= 0: the frame/frame gate set.  devIds: the
 // ids lie on the device already (a keyframe store's S, orbu_host.inc: made there from set slots, so not checked again); `ids`
-// is then null and nothing per query goes up
+// is then null and nothing per query goes up; store / storeUpdates name that store and its update in the search's record
 static int orbw_track(orbm_frameset_t* fs, int slot, int qslot, orbw_pool* pool, const OrbmProjParams* pp, const OrbwView* view, const int32_t* ids,
                       int nq, float th, const float* scale_factors, const float* level_breaks, int nlevels, const uint8_t* t_occ,
-                      const int32_t* devIds = nullptr)
+                      const int32_t* devIds = nullptr, const void* store = nullptr, uint64_t storeSerial = 0, uint32_t storeUpdates = 0)
 {
     const bool frame = qslot >= 0;
     int rc = orbw_check_args(view, devIds ? devIds : ids, nq, scale_factors, level_breaks, frame ? 1 : nlevels, frame);
@@ -323,7 +326,7 @@ static int orbw_track(orbm_frameset_t* fs, int slot, int qslot, orbw_pool* pool,
     P.qres = fs->d_qres; P.qscr = fs->d_qscr; P.tscr = c.big ? fs->d_tscr : nullptr;
     memcpy(hs + oPair, &P, sizeof P);
     r.pp = *pp; r.builds = fs->builds; r.slot = slot; r.qslot = qslot; r.nq = nq; r.total = head; r.qEpoch = fs->qEpoch;
-    r.fromPool = true; r.oStatus = oSt;
+    r.fromPool = true; r.oStatus = oSt; r.pool = pool; r.poolSerial = pool->serial; r.oIds = oIds; r.store = store; r.storeSerial = storeSerial; r.storeUpdates = storeUpdates;
     orbw::ProjectArgs a{};
     a.pool = pool->dev; a.ids = devIds ? devIds : (const int32_t*)(hs + oIds); a.nq = nq;
     a.lastKeys = frame ? fs->fs.keysUn + (size_t)qslot * C : nullptr; a.lastN = frame ? fs->fs.n + qslot : nullptr;

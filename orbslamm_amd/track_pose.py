@@ -1,0 +1,79 @@
+"""ctypes mirror of orbq_track_pose (include/orbslamm_trackpose.h): Optimizer::PoseOptimization as Tracking calls
+it right behind a pool search, with the loop that follows it, for any number of frames in one launch.
+
+    pool.track_local_map(fs, slot, view, ids, 1.0, sf, breaks); fs.results()          # or store.track_local_map / track_frame_pose
+    r, = track_pose(matcher, pool, [dict(fs=fs, slot=slot, back=0, base_ids=frame_ids, n=N, discard=0, Tcw=Tcw, K=K)], inv_level_sigma2)
+
+back: which of the set's last searches to merge, as fs.results(back) counts them, or -1 for none; base_ids: the pool id of
+mvpMapPoints[t] before that search (-1 = NULL; None = all NULL); discard: 1 for TrackWithMotionModel's loop, 0 for TrackLocalMap's.
+Each result is a dict: Tcw (what SetPose gets), ids (mvpMapPoints as pool ids after the loop), outlier (mvbOutlier as
+PoseOptimization left it), n_matches, n_matches_map, n_good, n_initial, rounds, iterations, trials, lambda_, chi2."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import K4, check, lib, ptr
+from .optimizer import FRAME_DTYPE, RESULT_DTYPE
+
+JOB_DTYPE = np.dtype([("fs", "<u8"), ("slot", "<i4"), ("back", "<i4"), ("base_ids", "<u8"), ("n", "<i4"), ("discard", "<i4"), ("frame", FRAME_DTYPE)])
+TRACK_RESULT_DTYPE = np.dtype([("opt", RESULT_DTYPE), ("n_matches", "<i4"), ("n_matches_map", "<i4")])
+assert JOB_DTYPE.itemsize == 112 and TRACK_RESULT_DTYPE.itemsize == 184
+
+
+def _setup(L):
+    if getattr(L, "_orbq_ready", False):
+        return
+    vp = C.c_void_p
+    L.orbq_track_pose.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    L._orbq_ready = True
+
+
+def pack_jobs(jobs):
+    """(JOB_DTYPE array, the arrays it points into) from job dicts: fs (a FrameSet, or a raw handle value), slot, back, base_ids, n,
+    discard, Tcw, K"""
+    rec = np.zeros(len(jobs), dtype=JOB_DTYPE)
+    keep = []
+    for i, j in enumerate(jobs):
+        fs = j["fs"]
+        h = getattr(fs, "_h", fs)
+        rec["fs"][i] = (h.value if isinstance(h, C.c_void_p) else h) or 0
+        rec["slot"][i], rec["back"][i], rec["n"][i], rec["discard"][i] = j["slot"], j.get("back", 0), j["n"], j.get("discard", 0)
+        base = j.get("base_ids")
+        if base is not None:
+            base = np.ascontiguousarray(base, dtype=np.int32).reshape(-1)
+            assert base.shape[0] >= j["n"]
+            keep.append(base)
+            rec["base_ids"][i] = base.ctypes.data
+        rec["frame"]["Tcw"][i] = np.asarray(j["Tcw"], dtype=np.float32).reshape(16)
+        rec["frame"]["K"][i] = K4(j["K"])
+    return rec, keep
+
+
+def track_pose_raw(handle, pool_handle, jobs, inv_level_sigma2, nlevels=None, n_jobs=None, fill=None):
+    """the C entry as it is: jobs a JOB_DTYPE array (or None).  Returns (rc, results, [ids per job], [outlier per job]); no exception
+    on a refusal.  fill: the byte the output arrays hold before the call (to see that a refusal leaves them alone)"""
+    L = lib()
+    _setup(L)
+    nj = (0 if jobs is None else jobs.shape[0]) if n_jobs is None else int(n_jobs)
+    real = 0 if jobs is None else jobs.shape[0]
+    sig = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, dtype=np.float32)
+    nl = (0 if sig is None else sig.shape[0]) if nlevels is None else int(nlevels)
+    out = np.zeros(max(real, 1), dtype=TRACK_RESULT_DTYPE)
+    ids = [np.full(max(int(jobs["n"][i]), 1), -2 if fill is None else fill, np.int32) for i in range(real)]
+    flags = [np.full(max(int(jobs["n"][i]), 1), 0 if fill is None else fill, np.uint8) for i in range(real)]
+    pi = (C.c_void_p * max(real, 1))(*[a.ctypes.data for a in ids])
+    pf = (C.c_void_p * max(real, 1))(*[a.ctypes.data for a in flags])
+    rc = L.orbq_track_pose(handle, pool_handle, ptr(jobs), nj, ptr(sig), nl, ptr(out), pi, pf)
+    return rc, out[:real], [a[:max(int(jobs["n"][i]), 0)] for i, a in enumerate(ids)], [a[:max(int(jobs["n"][i]), 0)] for i, a in enumerate(flags)]
+
+
+def track_pose(matcher, pool, jobs, inv_level_sigma2):
+    """orbq_track_pose over job dicts (see the module's head); one result dict per job"""
+    rec, keep = pack_jobs(jobs)
+    rc, out, ids, flags = track_pose_raw(matcher._h, pool._h, rec, inv_level_sigma2)
+    check(rc)
+    o = out["opt"]
+    return [dict(Tcw=o["Tcw"][i].reshape(4, 4).copy(), ids=ids[i], outlier=flags[i].astype(bool), n_matches=int(out["n_matches"][i]),
+                 n_matches_map=int(out["n_matches_map"][i]), n_good=int(o["n_good"][i]), n_initial=int(o["n_initial"][i]), rounds=int(o["rounds"][i]),
+                 iterations=o["iterations"][i].copy(), trials=o["trials"][i].copy(), lambda_=o["lambda_"][i].copy(), chi2=o["chi2"][i].copy())
+            for i in range(len(jobs))]
