@@ -38,6 +38,9 @@
 //   iORB_SLAM::TrackLocalMapT<Frame, KeyFrame, MapPoint>::Run(h, fs, slot, cap, pool, store, mCurrentFrame, mvpLocalKeyFrames,
 //                                                             mvpLocalMapPoints, mpReferenceKF, idOfPoint, slotOfKF, kfOfSlot, pointOfId, opt);
 //
+//   iORB_SLAM::TrackReferenceKeyFrameT<Frame, KeyFrame, MapPoint>::Run(h, fs, kfSlot, slot, pool, store, kf, mCurrentFrame, mpReferenceKF,
+//                                                                      mLastFrame.mTcw);            // Tracking.cc:802-844
+//
 // TrackWithMotionModelT::Finish stands behind orbw_track_frame_pose issued against (fs, slot) with mLastFrame's ids and `nmatches >= 20`
 // (:944, the caller's, from orbm_track_results): it merges the table into mvpMapPoints (ORBmatcher.cc:1430), and writes back in the
 // reference's order what PoseOptimization and :952-969 write: mvbOutlier, SetPose, the discarded slots, mbTrackInView and mnLastFrameSeen
@@ -389,6 +392,70 @@ struct TrackLocalMapT {
             if (F.mvpMapPoints[i]) baseIds[(size_t)i] = (int32_t)idOfPoint(F.mvpMapPoints[i]);
         SearchLocalPointsT<Frame, MapPoint>::RunResident(fs, slot, cap, pool, store, F, vpLocalMapPoints, opt.search);   // :987
         return Finish(h, fs, slot, pool, F, baseIds, idOfPoint, opt.verdict);   // :990-1023
+    }
+};
+
+// Tracking::TrackReferenceKeyFrame (Tracking.cc:802-844, monocular) on orbq_track_reference (include/orbslamm_trackpose.h, DESIGN.md
+// §8t): SearchByBoW with the validity rule, the merge, the gate, PoseOptimization and the discard loop in ONE call.  The caller has the
+// current frame in `slot` and pReferenceKF in `kfSlot` of fs with orbm_frameset_compute_bow run on both (:805 ComputeBoW), the
+// keyframe's match list in slot `kf` of the store (UpdateLocalMapT::SyncKeyFrame) and its points in the pool.  Run makes the device
+// call first and replays the host-visible effects afterwards, in the reference's order; on ORBQ_REF_TOO_FEW (:814) it returns false
+// and writes nothing to the frame.  A refusal throws with nothing touched.
+template <class Frame, class KeyFrame, class MapPoint>
+struct TrackReferenceKeyFrameT {
+    struct Options {
+        float nnratio = 0.7f;     // ORBmatcher matcher(0.7,true), :808
+        bool checkOri = true;
+        int minMatches = 15;      // :814
+    };
+    struct Result { bool ok; int status; int nBow; int nmatches; int nmatchesMap; OrboResult opt; };
+
+    // lastTcw: mLastFrame.mTcw (:818)
+    template <class MatT>
+    static Result Run(orbm_t* h, orbm_frameset_t* fs, int kfSlot, int slot, orbw_pool_t* pool, orbu_store_t* store, int kf, Frame& F, KeyFrame* pKF,
+                      const MatT& lastTcw, const Options& o = Options())
+    {
+        const char* who = "TrackReferenceKeyFrame(HIP): ";
+        const int N = F.N;
+        OrbqRefJob J;
+        J.fs = fs; J.kf_slot = kfSlot; J.slot = slot; J.kf = kf; J.n = N; J.solve = 1;
+        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) J.frame.Tcw[4 * r + c] = lastTcw.template at<float>(r, c);
+        J.frame.K[0] = Frame::fx; J.frame.K[1] = Frame::fy; J.frame.K[2] = Frame::cx; J.frame.K[3] = Frame::cy;
+        OrbqRefResult r;
+        std::vector<int32_t> ids((size_t)N + 1), match((size_t)N + 1);
+        std::vector<uint8_t> outlier((size_t)N + 1);
+        int32_t* pi = ids.data(); uint8_t* po = outlier.data(); int32_t* pm = match.data();
+        detail::check(orbq_track_reference(h, pool, store, &J, 1, o.nnratio, o.checkOri ? 1 : 0, o.minMatches, F.mvInvLevelSigma2.data(),
+                                           (int)F.mvInvLevelSigma2.size(), &r, &pi, &po, &pm), who);
+        Result res;
+        res.status = r.status; res.nBow = r.n_bow; res.nmatches = r.track.n_matches; res.nmatchesMap = r.track.n_matches_map; res.opt = r.track.opt;
+        res.ok = false;
+        if (r.status == ORBQ_REF_TOO_FEW) return res;   // :814-815: before the frame is touched
+        // the pointers are the keyframe's own (ORBmatcher.cc:187 vpMapPointsKF = pKF->GetMapPointMatches(), :236)
+        const std::vector<MapPoint*> vpMapPointsKF = pKF->GetMapPointMatches();
+        for (int t = 0; t < N; t++) {
+            if (match[t] >= (int)vpMapPointsKF.size() || (match[t] >= 0 && !vpMapPointsKF[(size_t)match[t]]))
+                throw std::runtime_error(std::string(who) + "the table names a keyframe feature without a MapPoint: the store is behind the keyframe");
+            if ((ids[t] >= 0) != (match[t] >= 0 && !outlier[t]) || (outlier[t] && match[t] < 0))
+                throw std::runtime_error(std::string(who) + "the ids returned are not the search's matches without the outliers");
+        }
+        // ---- the replay, in the reference's order
+        for (int t = 0; t < N; t++)   // :817 mCurrentFrame.mvpMapPoints = vpMapPointMatches
+            F.mvpMapPoints[t] = match[t] >= 0 ? vpMapPointsKF[(size_t)match[t]] : static_cast<MapPoint*>(NULL);
+        F.SetPose(lastTcw);   // :818
+        for (int i = 0; i < N; i++)
+            if (F.mvpMapPoints[i]) F.mvbOutlier[i] = outlier[i] != 0;   // Optimizer.cc:310, :410, :416
+        detail::set_pose(F, r.track.opt);   // :470
+        for (int i = 0; i < N; i++) {   // Tracking.cc:824-841
+            if (!F.mvpMapPoints[i] || !F.mvbOutlier[i]) continue;
+            MapPoint* pMP = F.mvpMapPoints[i];
+            F.mvpMapPoints[i] = static_cast<MapPoint*>(NULL);
+            F.mvbOutlier[i] = false;
+            pMP->mbTrackInView = false;
+            pMP->mnLastFrameSeen = F.mnId;
+        }
+        res.ok = r.track.n_matches_map >= 10;   // :843
+        return res;
     }
 };
 

@@ -1,6 +1,6 @@
 /* orbslamm_trackpose.h -- the block of liborbslamm_hip.so's C ABI that closes Tracking::TrackLocalMap and
- * Tracking::TrackWithMotionModel on the device.  Included by orbslamm_hip.h, whose types it uses
- * (orbm_t, orbm_frameset_t, orbw_pool_t, OrboFrame, OrboResult, the ORBX_* codes); including either gives both. */
+ * Tracking::TrackWithMotionModel and Tracking::TrackReferenceKeyFrame (section 8t) on the device.  Included by orbslamm_hip.h, whose types it uses
+ * (orbm_t, orbm_frameset_t, orbw_pool_t, orbu_store_t, OrboFrame, OrboResult, the ORBX_* codes); including either gives both. */
 #ifndef ORBSLAMM_TRACKPOSE_H
 #define ORBSLAMM_TRACKPOSE_H
 #include "orbslamm_hip.h"
@@ -58,6 +58,69 @@ typedef struct {
 typedef struct { OrboResult opt; int32_t n_matches, n_matches_map; } OrbqResult;
 int orbq_track_pose(orbm_t* h, orbw_pool_t* pool, const OrbqJob* jobs, int n_jobs, const float* inv_level_sigma2, int nlevels,
                     OrbqResult* out, int32_t* const* ids_out /* [n_jobs][n] */, uint8_t* const* outlier_out /* [n_jobs][n] */);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Tracking::TrackReferenceKeyFrame (Tracking.cc:802-844), from SearchByBoW to the loop behind PoseOptimization, for any number of
+ * (keyframe, frame) pairs in ONE call; with solve = 0 the first loop of Tracking::Relocalization
+ * (Tracking.cc:1428-1449: one lost frame against every candidate keyframe).  Everything read is resident: both frames'
+ * descriptors, angles, FeatureVectors and mvKeysUn in the frame set, the keyframe's match list in the keyframe store, the
+ * points' bad bit and positions in the pool.
+ *
+ * Validity (ORBmatcher.cc:191-197: if(!pMP) continue; if(pMP->isBad()) continue;): keyframe feature q takes part when
+ *   e = entries[kf][q] is not -1 and the pool record of e & ~ORBU_ENTRY_NO_VOTE carries no ORBW_FLAG_BAD.  An entry with
+ *   ORBU_ENTRY_NO_VOTE is a point in the match slot: it takes part.  A feature at or above the store's stride holds no point.
+ *   The keyframe's own bad flag is not consulted (Relocalization tests it before the call, :1431: that stays with the caller).
+ * Search (ORBmatcher.cc:159-290): orbm_bow_frames' search with that validity, TH_LOW = 50 (:214), the call's nnratio (:220; 0.7
+ *   at Tracking.cc:808, 0.75 at :1425) and check_ori (:222-233, :268-287).  match[t] = the keyframe feature matched to frame
+ *   feature t, or -1, behind the rotation pruning; n_bow its count over t < n (the nmatches :289 returns when n is the slot's
+ *   feature count, mCurrentFrame.N; the search itself always runs over the whole slot, and with a smaller n the features behind
+ *   n take no part in the count, the gate, the merge or the solve).  With every feature valid the table is the one
+ *   orbm_bow_frames returns for the pair.
+ * Merge (ORBmatcher.cc:236 vpMapPointMatches[bestIdxF]=pMP; Tracking.cc:817 mCurrentFrame.mvpMapPoints = vpMapPointMatches):
+ *   merged[t] = entries[kf][match[t]] with bit 30 cleared where match[t] >= 0, else -1.  There are no base ids: the assignment
+ *   replaces mvpMapPoints whole.
+ * Gate (Tracking.cc:814 if(nmatches<15) return false; :1436 if(nmatches<15) { vbDiscarded[i] = true; continue; }): n_bow <
+ *   min_matches gives status ORBQ_REF_TOO_FEW (the reference's value is 15); else solve = 0 gives ORBQ_REF_SEARCH_ONLY.  In both
+ *   no solve runs: track.opt is zero but for Tcw, the pose as it came; ids_out[t] = merged[t], outlier_out[t] = 0,
+ *   n_matches = n_bow, n_matches_map = 0.  (The reference returns before it touches the frame: a drop-in must not write it.)
+ * Solve and loop (Tracking.cc:818-841): otherwise orbq_track_pose's path with discard = 1 -- the edges in ascending t (:818
+ *   SetPose(mLastFrame.mTcw) is job.frame, :820 PoseOptimization), the loop of :824-841 (the same as :950-969): an outlier gets
+ *   ids_out[t] = -1 (:832) and keeps its byte at 1; n_matches, n_matches_map from the pool's observed bit (:838-839).  Status
+ *   ORBQ_REF_TRACKED.  The verdict nmatchesMap >= 10 (:843) is the caller's.
+ * The call: synchronous, one synchronise; one packed upload (the job records) and one copy down (results | ids | outlier bytes |
+ *   the match tables that were asked for); nothing per feature or per match goes up.  Jobs may name different frame sets of h,
+ *   the same keyframe or the same frame several times; a job's bytes do not depend on its neighbours, and the same call twice
+ *   gives the same bytes.  The scratch is the handle's own: no result set of the frame set's BoW ring is taken or disturbed.
+ *   The pool's mutex (the store shares it) is held from the checks to the synchronise, and the call leaves the reader event
+ *   orbw_pool_set* and orbu_* wait for.  It runs on the handle's stream, behind the slots' builds and
+ *   orbm_frameset_compute_bow as orbm_bow_frames does.
+ * match_out may be null, or hold nulls: those tables are not copied down.
+ * Refusals (never truncations; the argument checks come first and need no GPU):
+ *   n_jobs == 0: ORBX_OK at once.
+ *   ORBX_E_UNSUPPORTED above ORBO_MAX_FRAMES jobs, n above ORBO_MAX_EDGES, more than ORBO_MAX_CALL_EDGES features a call, or jobs
+ *   whose frame sets' caps add up to more than ORBO_MAX_CALL_EDGES (the search's scratch is 11 bytes a feature of the cap).
+ *   ORBX_E_INVALID for null arguments, n < 0 or above the set's cap, solve outside {0, 1}, min_matches < 0, nlevels outside
+ *   [1, 16], a slot outside the set, a frame set of another handle, a store of another pool, kf outside the store or not set,
+ *   orbm_frameset_compute_bow has not run; and, found by the kernel and reported behind it with the outputs unwritten: an
+ *   edge's octave outside [0, nlevels), or a feature with a point at or above the slot's device count.
+ *   No CPU fallback. */
+typedef struct {
+    orbm_frameset_t* fs;
+    int32_t kf_slot;   /* the reference keyframe as a slot of fs: descriptors, angles, FeatureVector */
+    int32_t slot;      /* mCurrentFrame */
+    int32_t kf;        /* the keyframe's slot in the store: entries[kf][q] = pool id of its feature q */
+    int32_t n;         /* mCurrentFrame.N */
+    int32_t solve;     /* 1: TrackReferenceKeyFrame; 0: the search and the merge only (Relocalization's first loop) */
+    OrboFrame frame;   /* mLastFrame.mTcw and K, as orbo_* take them (read when solve = 1) */
+} OrbqRefJob;
+#define ORBQ_REF_TRACKED 0
+#define ORBQ_REF_TOO_FEW 1
+#define ORBQ_REF_SEARCH_ONLY 2
+typedef struct { OrbqResult track; int32_t n_bow; int32_t status; } OrbqRefResult;
+int orbq_track_reference(orbm_t* h, orbw_pool_t* pool, orbu_store_t* store, const OrbqRefJob* jobs, int n_jobs,
+                         float nnratio, int check_ori, int min_matches,
+                         const float* inv_level_sigma2, int nlevels, OrbqRefResult* out,
+                         int32_t* const* ids_out, uint8_t* const* outlier_out, int32_t* const* match_out /* may be null, or hold nulls */);
 
 #ifdef __cplusplus
 }

@@ -142,7 +142,7 @@ EXPORTS_LOCALMAP_UPDATE = [
 
 # the block that closes TrackLocalMap / TrackWithMotionModel (include/orbslamm_trackpose.h, which include/orbslamm_hip.h includes)
 EXPORTS_TRACKPOSE = [
-    "orbq_track_pose",
+    "orbq_track_pose", "orbq_track_reference",
 ]
 
 

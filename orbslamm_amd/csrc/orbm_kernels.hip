@@ -820,6 +820,7 @@ struct BowSetArgs {
     const uint8_t* desc; const float* ang; const int32_t* n; int32_t cap;       // frame set: slot s at + s * cap (desc: * 32)
     const uint32_t* fvNode; const int32_t* fvStart; const int32_t* fvIdx; const int32_t* counts;  // fvStart: + s * (cap + 1), counts: + 2 s + 1 = nodes
     uint8_t* matched; int32_t* match; uint8_t* binOf;                            // per pair p: + p * cap; zero / -1 / - on entry
+    const uint8_t* qvalid;                                                       // per pair p: + p * cap, a byte per KeyFrame feature (0: no good MapPoint, :191-197); null: all valid
     float nnratio; int32_t thLow, checkOri;
     int16_t kf[kBowMaxPairs], fr[kBowMaxPairs];
 };
@@ -849,7 +850,7 @@ __global__ __launch_bounds__(64) void k_bow_set(BowSetArgs s)
     }
     if (lo < 0) return;
     BowArgs a;
-    a.qdesc = s.desc + qs * C * 32; a.qang = s.ang + qs * C; a.qvalid = nullptr;
+    a.qdesc = s.desc + qs * C * 32; a.qang = s.ang + qs * C; a.qvalid = s.qvalid ? s.qvalid + p * C : nullptr;
     a.tdesc = s.desc + ts * C * 32; a.tang = s.ang + ts * C; a.tvalid = nullptr;
     a.qstart = s.fvStart + (int64_t)qs * (C + 1); a.qidx = s.fvIdx + qs * C;
     a.tstart = s.fvStart + (int64_t)ts * (C + 1); a.tidx = s.fvIdx + ts * C;
@@ -862,7 +863,7 @@ __global__ __launch_bounds__(64) void k_bow_set(BowSetArgs s)
 // Rotation check of one match table, by one workgroup of 256: the histogram (:238-248) is counted here, in LDS, from binOf (a few
 // hundred matches fall into two or three bins, and as global atomics on those few words they took longer than the search
 // itself), then three maxima, pruning and the count.  InPlace: the pruned entries of `match` are overwritten; else every entry
-// goes to `out`, written once (pinned host memory).
+// goes to `out`, written once (pinned host memory, or device memory that the next kernel reads in stream order).
 template <bool InPlace>
 __device__ __forceinline__ void prune_table(int32_t* __restrict__ match, const uint8_t* __restrict__ binOf, int n, int checkOri,
                                             int32_t* __restrict__ out, int32_t* __restrict__ nmatch)
@@ -888,7 +889,8 @@ __device__ __forceinline__ void prune_table(int32_t* __restrict__ match, const u
     if (tid == 0) *nmatch = rs.count;
 }
 
-// every pair's match table of a frame set's SearchByBoW: final table and count to `outMatch` / `outN` (pinned host memory)
+// every pair's match table of a frame set's SearchByBoW: final table and count to `outMatch` / `outN` (orbm_bow_frames: pinned host
+// memory; orbq_track_reference: device memory, read by orbq::k_track_reference behind it)
 __global__ __launch_bounds__(256) void k_bow_prune_set(BowSetArgs s, int32_t* __restrict__ outMatch, int32_t* __restrict__ outN)
 {
     const int p = blockIdx.x;

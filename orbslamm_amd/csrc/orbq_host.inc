@@ -138,3 +138,155 @@ extern "C" int orbq_track_pose(orbm_t* h, orbw_pool_t* pool, const OrbqJob* jobs
     }
     return ORBX_OK;
 }
+
+// ------------------------------------------------------------------ Tracking::TrackReferenceKeyFrame (DESIGN.md §8t)
+// One call = the checks, one packed upload (the job records), per run of jobs on one frame set the set search with the validity
+// block (k_ref_valid, k_bow_set, k_bow_prune_set into device memory), ONE k_track_reference launch for all jobs, one copy down
+// (results | ids | outlier bytes | the match tables asked for), one synchronise.
+
+static_assert(sizeof(OrbqRefJob) == 112 && sizeof(OrbqRefResult) == 192, "orbslamm_trackpose.h layouts");
+static_assert(ORBW_FLAG_BAD == 1, "k_ref_valid reads the bad bit");
+static_assert(sizeof(orbq::RefJobDev) == 152, "the per-job upload size tools/trackref_bench.py computes with");
+
+// what needs neither a handle nor a GPU.  Zero jobs are settled by the caller before this
+static int orbq_ref_check_args(const void* h, const void* pool, const void* store, const OrbqRefJob* jobs, int n_jobs, int min_matches,
+                               const float* inv_level_sigma2, int nlevels, const OrbqRefResult* out, int32_t* const* ids_out, uint8_t* const* outlier_out)
+{
+    if (n_jobs < 0) return fail(ORBX_E_INVALID, "negative job count");
+    if (n_jobs > ORBO_MAX_FRAMES) return fail(ORBX_E_UNSUPPORTED, "%d jobs: above %d", n_jobs, ORBO_MAX_FRAMES);
+    if (!jobs || !out || !ids_out || !outlier_out) return fail(ORBX_E_INVALID, "null argument");
+    if (!inv_level_sigma2 || nlevels < 1 || nlevels > ORBX_MAX_LEVELS) return fail(ORBX_E_INVALID, "nlevels %d outside [1, %d] or no sigma table", nlevels, ORBX_MAX_LEVELS);
+    if (min_matches < 0) return fail(ORBX_E_INVALID, "min_matches %d is negative", min_matches);
+    int64_t total = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const OrbqRefJob& J = jobs[j];
+        if (!J.fs) return fail(ORBX_E_INVALID, "job %d: null frame set", j);
+        if (J.n < 0) return fail(ORBX_E_INVALID, "job %d: negative feature count", j);
+        if (J.n > ORBO_MAX_EDGES) return fail(ORBX_E_UNSUPPORTED, "job %d: %d features: above %d", j, J.n, ORBO_MAX_EDGES);
+        if (J.solve != 0 && J.solve != 1) return fail(ORBX_E_INVALID, "job %d: solve is 0 or 1", j);
+        if (J.kf_slot < 0 || J.slot < 0 || J.kf < 0) return fail(ORBX_E_INVALID, "job %d: negative slot", j);
+        if (J.n && (!ids_out[j] || !outlier_out[j])) return fail(ORBX_E_INVALID, "job %d: null output array", j);
+        total += J.n;
+        if (total > ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "more than %d features in one call (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
+    }
+    if (!h || !pool || !store) return fail(ORBX_E_INVALID, "null handle, pool or store");
+    return ORBX_OK;
+}
+
+extern "C" int orbq_track_reference(orbm_t* h, orbw_pool_t* pool, orbu_store_t* store, const OrbqRefJob* jobs, int n_jobs,
+                                    float nnratio, int check_ori, int min_matches, const float* inv_level_sigma2, int nlevels,
+                                    OrbqRefResult* out, int32_t* const* ids_out, uint8_t* const* outlier_out, int32_t* const* match_out)
+{
+    if (n_jobs == 0) return ORBX_OK;   // nothing to do: no argument is read, no handle needed
+    int rc = orbq_ref_check_args(h, pool, store, jobs, n_jobs, min_matches, inv_level_sigma2, nlevels, out, ids_out, outlier_out);
+    if (rc) return rc;
+    if ((rc = orbm_check(h)) || (rc = orbw_pool_check(pool)) || (rc = orbu_store_check(store))) return rc;
+    if (pool->h->device != h->device) return fail(ORBX_E_INVALID, "the pool and the handle must share the device");
+    if (store->pool != pool) return fail(ORBX_E_INVALID, "the store stands beside another pool");
+    size_t total = 0, sumCap = 0, nAsked = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const OrbqRefJob& J = jobs[j];
+        if ((rc = frameset_check(J.fs))) return rc;
+        if (J.fs->owner != h) return fail(ORBX_E_INVALID, "job %d: the frame set belongs to another handle", j);
+        if (J.slot >= J.fs->slots || J.kf_slot >= J.fs->slots) return fail(ORBX_E_INVALID, "job %d: slot %d or %d outside the frame set", j, J.kf_slot, J.slot);
+        if (J.n > J.fs->cap) return fail(ORBX_E_INVALID, "job %d: %d features for a frame of at most %d", j, J.n, J.fs->cap);
+        sumCap += (size_t)J.fs->cap;
+        // (the search's scratch is 11 bytes a feature of the set's CAP, whatever n is: bounded like the features)
+        if (sumCap > (size_t)ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "the jobs' frame sets hold more than %d features together (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
+        if (!J.fs->bow || !J.fs->bow->computed) return fail(ORBX_E_INVALID, "job %d: orbm_frameset_compute_bow has not run", j);
+        if (J.kf >= store->kfcap) return fail(ORBX_E_INVALID, "job %d: keyframe %d outside the store of %d", j, J.kf, store->kfcap);
+        // (a set that builds on a stream of its own: the slots' builds may still run there)
+        if (fs_stream(J.fs) != h->stream) HIPCHK(hipStreamSynchronize(fs_stream(J.fs)));
+        total += (size_t)J.n;
+        if (match_out && match_out[j]) nAsked += (size_t)J.n;
+    }
+    Packer pk;
+    const size_t oJobs = pk.take((size_t)n_jobs * sizeof(orbq::RefJobDev)), upBytes = pk.off;
+    const size_t oMatched = pk.take(sumCap), oValid = pk.take(sumCap), oBin = pk.take(sumCap), oRaw = pk.take(sumCap * 4), oTable = pk.take(sumCap * 4),
+                 oNBow = pk.take((size_t)n_jobs * 4);
+    const size_t oPw = pk.take(total * sizeof(float4)), oUv = pk.take(total * sizeof(float2)), oFlags = pk.take(total), oMerged = pk.take(total * 4);
+    const size_t oOut = pk.take((size_t)n_jobs * sizeof(OrbqRefResult)), oIds = pk.take(total * 4), oOutl = pk.take(total), oMatch = pk.take(nAsked * 4), work = pk.off;
+    const size_t downBytes = work - oOut;
+    if ((rc = orbm_reserve(h, S_BLOCK, work)) || (rc = orbm_pinned(h, std::max(upBytes, downBytes)))) return rc;
+    uint8_t* hs = (uint8_t*)h->h_stage;
+    uint8_t* d = slot_ptr<uint8_t>(h, S_BLOCK);
+    orbq::RefJobDev* hj = (orbq::RefJobDev*)(hs + oJobs);
+    std::lock_guard<std::mutex> l(pool->mu);   // (held to the synchronise: no setter and no store update runs under the reads)
+    size_t f0 = 0, c0 = 0, m0 = 0;
+    int maxCap = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const OrbqRefJob& J = jobs[j];
+        if (!store->kfSet[(size_t)J.kf]) return fail(ORBX_E_INVALID, "job %d: keyframe %d was never set", j, J.kf);
+        orbq::RefJobDev& D = hj[j];
+        memset(&D, 0, sizeof D);
+        memcpy(D.Tcw, J.frame.Tcw, sizeof D.Tcw);
+        memcpy(D.K, J.frame.K, sizeof D.K);
+        D.keys = J.fs->fs.keysUn + (size_t)J.slot * J.fs->cap;
+        D.nKeys = J.fs->fs.n + J.slot;
+        D.entries = store->dev.entries + (size_t)J.kf * store->pitch;
+        D.valid = d + oValid + c0;
+        D.table = (const int32_t*)(d + oTable) + c0;
+        D.nBow = (const int32_t*)(d + oNBow) + j;
+        D.n = J.n; D.f0 = (int32_t)f0; D.solve = J.solve; D.cap = J.fs->cap;
+        const bool asked = match_out && match_out[j];
+        D.matchAt = asked ? (int32_t)m0 : -1;
+        f0 += (size_t)J.n; c0 += (size_t)J.fs->cap;
+        if (asked) m0 += (size_t)J.n;
+        maxCap = std::max(maxCap, J.fs->cap);
+    }
+    orbq::RefArgs a{};
+    a.q.o.pw = (float4*)(d + oPw); a.q.o.uv = (float2*)(d + oUv); a.q.o.outlier = d + oFlags;
+    for (int lv = 0; lv < ORBX_MAX_LEVELS; lv++) a.q.o.invSigma2[lv] = lv < nlevels ? inv_level_sigma2[lv] : 0.f;
+    a.q.o.nlevels = nlevels;
+    a.q.pool = pool->dev;
+    a.q.merged = (int32_t*)(d + oMerged); a.q.idsOut = (int32_t*)(d + oIds); a.q.outlierOut = d + oOutl;
+    a.jobs = (const orbq::RefJobDev*)(d + oJobs);
+    a.out = (OrbqRefResult*)(d + oOut);
+    a.matchOut = (int32_t*)(d + oMatch);
+    a.stride = store->stride; a.minMatches = min_matches;
+    hipStream_t s = h->stream;
+    HIPCHK(hipMemcpyAsync(d, hs, upBytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d + oMatched, 0, sumCap, s));
+    HIPCHK(hipMemsetAsync(d + oRaw, 0xFF, oNBow - oRaw, s));   // the raw and the pruned tables: -1
+    HIPCHK(hipMemsetAsync(d + oOut, 0, (size_t)n_jobs * sizeof(OrbqRefResult), s));   // (the records' padding too: the same bytes every call)
+    hipLaunchKernelGGL(orbq::k_ref_valid, dim3((unsigned)((maxCap + 255) / 256), (unsigned)n_jobs), dim3(256), 0, s, a.jobs, pool->dev, store->stride);
+    // the set search of orbm_bow_frames, per run of consecutive jobs on one frame set, in batches of kBowMaxPairs
+    c0 = 0;
+    for (int j0 = 0; j0 < n_jobs;) {
+        orbm_frameset* fs = jobs[j0].fs;
+        int nb = 1;
+        while (j0 + nb < n_jobs && nb < orbm::kBowMaxPairs && jobs[j0 + nb].fs == fs) nb++;
+        const orbm_frameset_bow* b = fs->bow;
+        orbm::BowSetArgs ba{};
+        ba.desc = fs->fs.desc; ba.ang = fs->fs.ang; ba.n = fs->fs.n; ba.cap = fs->cap;
+        ba.fvNode = b->d_fvNode; ba.fvStart = b->d_fvStart; ba.fvIdx = b->d_fvIdx; ba.counts = b->d_counts;
+        ba.matched = d + oMatched + c0; ba.match = (int32_t*)(d + oRaw) + c0; ba.binOf = d + oBin + c0; ba.qvalid = d + oValid + c0;
+        ba.nnratio = nnratio; ba.thLow = 50; ba.checkOri = check_ori;
+        for (int i = 0; i < nb; i++) { ba.kf[i] = (int16_t)jobs[j0 + i].kf_slot; ba.fr[i] = (int16_t)jobs[j0 + i].slot; }
+        hipLaunchKernelGGL(orbm::k_bow_set, dim3((unsigned)std::max(b->maxNodes, 1), (unsigned)nb), dim3(64), 0, s, ba);
+        hipLaunchKernelGGL(orbm::k_bow_prune_set, dim3((unsigned)nb), dim3(256), 0, s, ba, (int32_t*)(d + oTable) + c0, (int32_t*)(d + oNBow) + j0);
+        c0 += (size_t)nb * fs->cap;
+        j0 += nb;
+    }
+    hipLaunchKernelGGL(orbq::k_track_reference, dim3((unsigned)n_jobs), dim3(orbq::kLanes), 0, s, a, n_jobs);
+    HIPCHK(hipGetLastError());
+    if ((rc = orbw_mark_reader(pool, s))) return rc;
+    HIPCHK(hipMemcpyAsync(hs, d + oOut, downBytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const OrbqRefResult* hr = (const OrbqRefResult*)hs;
+    for (int j = 0; j < n_jobs; j++)
+        if (hr[j].track.opt.rounds < 0)
+            return fail(ORBX_E_INVALID, "job %d: an edge's octave lies outside [0, %d), or a feature at or above the slot's device count (or a match without a point of the pool) holds a point",
+                        j, nlevels);
+    memcpy(out, hr, (size_t)n_jobs * sizeof(OrbqRefResult));
+    f0 = 0; m0 = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const size_t n = (size_t)jobs[j].n;
+        const bool asked = match_out && match_out[j];
+        if (n) { memcpy(ids_out[j], hs + (oIds - oOut) + f0 * 4, n * 4); memcpy(outlier_out[j], hs + (oOutl - oOut) + f0, n); }
+        if (n && asked) memcpy(match_out[j], hs + (oMatch - oOut) + m0 * 4, n * 4);
+        f0 += n;
+        if (asked) m0 += n;
+    }
+    return ORBX_OK;
+}

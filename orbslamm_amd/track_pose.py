@@ -1,4 +1,4 @@
-"""ctypes mirror of orbq_track_pose (include/orbslamm_trackpose.h): Optimizer::PoseOptimization as Tracking calls
+"""ctypes mirror of orbq_track_pose and orbq_track_reference (include/orbslamm_trackpose.h): Optimizer::PoseOptimization as Tracking calls
 it right behind a pool search, with the loop that follows it, for any number of frames in one launch.
 
     pool.track_local_map(fs, slot, view, ids, 1.0, sf, breaks); fs.results()          # or store.track_local_map / track_frame_pose
@@ -76,4 +76,75 @@ def track_pose(matcher, pool, jobs, inv_level_sigma2):
     return [dict(Tcw=o["Tcw"][i].reshape(4, 4).copy(), ids=ids[i], outlier=flags[i].astype(bool), n_matches=int(out["n_matches"][i]),
                  n_matches_map=int(out["n_matches_map"][i]), n_good=int(o["n_good"][i]), n_initial=int(o["n_initial"][i]), rounds=int(o["rounds"][i]),
                  iterations=o["iterations"][i].copy(), trials=o["trials"][i].copy(), lambda_=o["lambda_"][i].copy(), chi2=o["chi2"][i].copy())
+            for i in range(len(jobs))]
+
+
+# ------------------------------------------------------------------ orbq_track_reference
+REF_JOB_DTYPE = np.dtype([("fs", "<u8"), ("kf_slot", "<i4"), ("slot", "<i4"), ("kf", "<i4"), ("n", "<i4"), ("solve", "<i4"), ("frame", FRAME_DTYPE)], align=True)
+REF_RESULT_DTYPE = np.dtype([("track", TRACK_RESULT_DTYPE), ("n_bow", "<i4"), ("status", "<i4")])
+assert REF_JOB_DTYPE.itemsize == 112 and REF_RESULT_DTYPE.itemsize == 192
+REF_TRACKED, REF_TOO_FEW, REF_SEARCH_ONLY = 0, 1, 2
+
+
+def _setup_ref(L):
+    if getattr(L, "_orbq_ref_ready", False):
+        return
+    vp = C.c_void_p
+    L.orbq_track_reference.argtypes = [vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L._orbq_ref_ready = True
+
+
+def pack_ref_jobs(jobs):
+    """REF_JOB_DTYPE array from job dicts: fs (a FrameSet, or a raw handle value), kf_slot, slot, kf, n, solve (default 1), Tcw, K"""
+    rec = np.zeros(len(jobs), dtype=REF_JOB_DTYPE)
+    for i, j in enumerate(jobs):
+        fs = j["fs"]
+        h = getattr(fs, "_h", fs)
+        rec["fs"][i] = (h.value if isinstance(h, C.c_void_p) else h) or 0
+        rec["kf_slot"][i], rec["slot"][i], rec["kf"][i], rec["n"][i], rec["solve"][i] = j["kf_slot"], j["slot"], j["kf"], j["n"], j.get("solve", 1)
+        rec["frame"]["Tcw"][i] = np.asarray(j.get("Tcw", np.eye(4)), dtype=np.float32).reshape(16)
+        rec["frame"]["K"][i] = K4(j.get("K", [1, 1, 0, 0]))
+    return rec
+
+
+def track_reference_raw(handle, pool_handle, store_handle, jobs, nnratio, check_ori, min_matches, inv_level_sigma2, nlevels=None, n_jobs=None,
+                        fill=None, want_match=True):
+    """the C entry as it is: jobs a REF_JOB_DTYPE array (or None).  Returns (rc, results, [ids per job], [outlier per job], [match table
+    per job, or None]); no exception on a refusal.  fill: the byte the output arrays hold before the call.  want_match: True, False (a
+    null match_out) or one bool per job (nulls inside it)"""
+    L = lib()
+    _setup_ref(L)
+    nj = (0 if jobs is None else jobs.shape[0]) if n_jobs is None else int(n_jobs)
+    real = 0 if jobs is None else jobs.shape[0]
+    sig = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, dtype=np.float32)
+    nl = (0 if sig is None else sig.shape[0]) if nlevels is None else int(nlevels)
+    out = np.zeros(max(real, 1), dtype=REF_RESULT_DTYPE)
+    ns = [max(int(jobs["n"][i]), 0) for i in range(real)]
+    ids = [np.full(max(n, 1), -2 if fill is None else fill, np.int32) for n in ns]
+    flags = [np.full(max(n, 1), 0 if fill is None else fill, np.uint8) for n in ns]
+    per = [bool(want_match)] * real if isinstance(want_match, bool) else [bool(w) for w in want_match]
+    match = [np.full(max(n, 1), -2 if fill is None else fill, np.int32) if per[i] else None for i, n in enumerate(ns)]
+    pi = (C.c_void_p * max(real, 1))(*[a.ctypes.data for a in ids])
+    pf = (C.c_void_p * max(real, 1))(*[a.ctypes.data for a in flags])
+    pm = (C.c_void_p * max(real, 1))(*[None if a is None else a.ctypes.data for a in match]) if any(per) or not isinstance(want_match, bool) else None
+    rc = L.orbq_track_reference(handle, pool_handle, store_handle, ptr(jobs), nj, float(nnratio), int(bool(check_ori)), int(min_matches), ptr(sig), nl,
+                                ptr(out), pi, pf, pm)
+    return (rc, out[:real], [a[:ns[i]] for i, a in enumerate(ids)], [a[:ns[i]] for i, a in enumerate(flags)],
+            [None if a is None else a[:ns[i]] for i, a in enumerate(match)])
+
+
+def track_reference(matcher, pool, store, jobs, inv_level_sigma2, nnratio=0.7, check_ori=True, min_matches=15, want_match=True):
+    """orbq_track_reference over job dicts (fs, kf_slot, slot, kf, n, solve, Tcw, K): Tracking::TrackReferenceKeyFrame from SearchByBoW to
+    the loop behind PoseOptimization (solve = 0: Relocalization's first loop).  One result dict per job: status (REF_TRACKED, REF_TOO_FEW,
+    REF_SEARCH_ONLY), n_bow, match (the keyframe feature per frame feature, or None), and track_pose's fields; the verdict
+    n_matches_map >= 10 is the caller's"""
+    rec = pack_ref_jobs(jobs)
+    rc, out, ids, flags, match = track_reference_raw(matcher._h, pool._h, store._h, rec, nnratio, check_ori, min_matches, inv_level_sigma2, want_match=want_match)
+    check(rc)
+    t = out["track"]
+    o = t["opt"]
+    return [dict(status=int(out["status"][i]), n_bow=int(out["n_bow"][i]), match=match[i], Tcw=o["Tcw"][i].reshape(4, 4).copy(), ids=ids[i],
+                 outlier=flags[i].astype(bool), n_matches=int(t["n_matches"][i]), n_matches_map=int(t["n_matches_map"][i]), n_good=int(o["n_good"][i]),
+                 n_initial=int(o["n_initial"][i]), rounds=int(o["rounds"][i]), iterations=o["iterations"][i].copy(), trials=o["trials"][i].copy(),
+                 lambda_=o["lambda_"][i].copy(), chi2=o["chi2"][i].copy())
             for i in range(len(jobs))]
