@@ -411,9 +411,33 @@ class OrcPyramid(C.Structure):
     _fields_ = [("nlevels", C.c_int), ("data", C.c_void_p * 16), ("w", C.c_int * 16), ("h", C.c_int * 16), ("stride", C.c_int * 16)]
 
 
-def compute_stereo_matches(keysL, descL, keysR, descR, levelsL, levelsR, scale, inv_scale, mb, mbf, L=None):
+# the branches of orb_stereo.c's restatement, in the order of its census counters
+STEREO_BRANCHES = ("row_outside",            # (int)vL not a row of the image
+                   "row_empty",              # no right keypoint's band covers the row (Frame.cc:511)
+                   "maxu_negative",          # uL - minD < 0
+                   "octave_gate",            # per candidate: more than one octave apart
+                   "ur_below_minu",          # per candidate: uR < uL - maxD
+                   "ur_above_maxu",          # per candidate: uR > uL - minD
+                   "no_descriptor",          # no candidate under TH_HIGH
+                   "window_left",            # the left 11 x 11 patch leaves the level
+                   "window_ref_right",       # the reference's own iniu / endu check (:565-568)
+                   "window_right",           # the right 11 x 21 strip leaves the level
+                   "bestinc_at_end",         # least SAD at -L or +L
+                   "delta_nan",              # parabola 0 / 0
+                   "delta_beyond_one",       # |deltaR| > 1
+                   "disparity_negative",     # fails `disparity >= 0` (:610)
+                   "disparity_ge_maxd",      # fails `disparity < maxD` (:610)
+                   "clamp",                  # disparity <= 0 -> 0.01, uL - 0.01 in double (:612-616)
+                   "median_removed",         # dropped by the 1.5 * 1.4 * median filter (:626-637)
+                   "minr_clipped",           # a right keypoint's row band cut at row 0
+                   "maxr_clipped",           # ... at the last row
+                   "accepted")               # matches before the median filter
+
+
+def compute_stereo_matches(keysL, descL, keysR, descR, levelsL, levelsR, scale, inv_scale, mb, mbf, L=None, census=False):
     """Frame::ComputeStereoMatches (Frame.cc:466-638); levelsL / levelsR: lists of contiguous uint8 images (the
-    un-blurred pyramid levels).  Returns (mvuRight, mvDepth, accepted before the median filter)."""
+    un-blurred pyramid levels).  Returns (mvuRight, mvDepth, accepted before the median filter), and with census=True a
+    fourth item: dict of STEREO_BRANCHES -> how often the branch was taken."""
     L = L or lib()
     keysL = np.ascontiguousarray(keysL); keysR = np.ascontiguousarray(keysR)
     descL = np.ascontiguousarray(descL, dtype=np.uint8); descR = np.ascontiguousarray(descR, dtype=np.uint8)
@@ -433,10 +457,16 @@ def compute_stereo_matches(keysL, descL, keysR, descR, levelsL, levelsR, scale, 
     pr, k2 = pyr(levelsR)
     sc = np.ascontiguousarray(scale, dtype=np.float32); isc = np.ascontiguousarray(inv_scale, dtype=np.float32)
     ur = np.zeros(max(len(keysL), 1), dtype=np.float32); dp = np.zeros(max(len(keysL), 1), dtype=np.float32)
-    L.orc_compute_stereo_matches.restype = C.c_int
-    n = L.orc_compute_stereo_matches(_p(keysL), _p(descL), len(keysL), _p(keysR), _p(descR), len(keysR), C.byref(pl), C.byref(pr),
-                                     _p(sc), _p(isc), C.c_float(mb), C.c_float(mbf), _p(ur), _p(dp))
-    return ur[:len(keysL)], dp[:len(keysL)], n
+    args = (_p(keysL), _p(descL), len(keysL), _p(keysR), _p(descR), len(keysR), C.byref(pl), C.byref(pr),
+            _p(sc), _p(isc), C.c_float(mb), C.c_float(mbf), _p(ur), _p(dp))
+    if not census:
+        L.orc_compute_stereo_matches.restype = C.c_int
+        n = L.orc_compute_stereo_matches(*args)
+        return ur[:len(keysL)], dp[:len(keysL)], n
+    cnt = np.zeros(len(STEREO_BRANCHES), dtype=np.int32)
+    L.orc_compute_stereo_matches_census.restype = C.c_int
+    n = L.orc_compute_stereo_matches_census(*args, _p(cnt))
+    return ur[:len(keysL)], dp[:len(keysL)], n, dict(zip(STEREO_BRANCHES, (int(c) for c in cnt)))
 
 
 def build_ref():

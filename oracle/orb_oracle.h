@@ -237,6 +237,14 @@ int  orc_compute_stereo_matches(const OrcKeyPoint* keysL, const uint8_t* descL, 
                                 const OrcPyramid* pyrL, const OrcPyramid* pyrR,
                                 const float* mvScaleFactors, const float* mvInvScaleFactors,
                                 float mb, float mbf, float* mvuRight, float* mvDepth);
+/* the same function with a census of its branches: census is NULL or ORC_STEREO_NBRANCH counters that are added to
+ * (binding.STEREO_BRANCHES names them in order).  The outputs do not depend on it. */
+#define ORC_STEREO_NBRANCH 20
+int  orc_compute_stereo_matches_census(const OrcKeyPoint* keysL, const uint8_t* descL, int N,
+                                       const OrcKeyPoint* keysR, const uint8_t* descR, int Nr,
+                                       const OrcPyramid* pyrL, const OrcPyramid* pyrR,
+                                       const float* mvScaleFactors, const float* mvInvScaleFactors,
+                                       float mb, float mbf, float* mvuRight, float* mvDepth, int32_t* census);
 
 /* Frame::UndistortKeyPoints (src/Frame.cc:404-434), OpenCV 3.0 undistortPoints (unpinned) */
 void orc_stereo_from_rgbd(const OrcKeyPoint* keys, const OrcKeyPoint* keysUn, int n, const float* depth, int w, int h, int stride,

@@ -114,7 +114,9 @@ def main():
             print("DIFFERENCE stereo extraction", dict(round=r, w=w, h=h, nf=nf, seed=seed))
             return 1
         sfo = oex.scale_factors()
-        mbf = float(rng.uniform(20, 400)); mb = mbf / float(rng.uniform(300, 800))
+        # maxD = mbf / mb log-uniform over 8 .. 800 px: about four pairs in nine have bands (0 .. 59 px) beyond it, so the
+        # soak crosses `disparity < maxD` and `uR >= minU` as well as the wide-open range
+        mbf = float(rng.uniform(20, 400)); mb = mbf / float(np.exp(rng.uniform(np.log(8.0), np.log(800.0))))
         want_u, want_d, _ = ob.compute_stereo_matches(oL["kps"], oL["desc"], oR["kps"], oR["desc"], levels_of(oex, oL["pyramid"], w, h, 8),
                                                       levels_of(oex, oR["pyramid"], w, h, 8), sfo, (1.0 / sfo).astype(np.float32), mb, mbf)
         got_u, got_d = exL.compute_stereo_matches(exR, mb, mbf)

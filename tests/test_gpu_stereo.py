@@ -56,6 +56,55 @@ def test_compute_stereo_matches_parity(gpu, oracle, w, h, nf, mb, mbf):
     assert np.allclose(got_d[matched], np.float32(mbf) / np.maximum(disp, 0.01), rtol=1e-5)
 
 
+def _stereo_on(exL, exR, r):
+    """one scene of stereo_cases through a pair of handles, bytes against the oracle's run `r`"""
+    kL, _ = exL(r["left"])
+    kR, _ = exR(r["right"])
+    assert kL.tobytes() == r["oL"]["kps"].tobytes() and kR.tobytes() == r["oR"]["kps"].tobytes()
+    got_u, got_d = exL.compute_stereo_matches(exR, r["mb"], r["mbf"])
+    assert len(got_u) == len(kL) and len(got_d) == len(kL)
+    assert got_u.tobytes() == r["u"].tobytes()
+    assert got_d.tobytes() == r["d"].tobytes()
+    return kL, got_u, got_d
+
+
+def test_stereo_branch_scenes_on_one_pair_of_handles(gpu, oracle):
+    """the scenes of stereo_cases.py (test_stereo_cpu.py holds the branches they reach to floors) in sequence through one
+    pair of extractors: N and Nr fall to 0 and rise again under the same d_stereo scratch and median LDS grant"""
+    import stereo_cases as sc
+    from orbslamm_amd import ORBextractor
+    exL = ORBextractor(sc.NF, *sc.EXTRACTOR, max_width=sc.W, max_height=sc.H, max_batch=1, device=0)
+    exR = ORBextractor(sc.NF, *sc.EXTRACTOR, max_width=sc.W, max_height=sc.H, max_batch=1, device=0)
+    assert set(sc.SCENE_ORDER) == set(sc.SCENES)
+    for name in sc.SCENE_ORDER:
+        r = sc.scene(oracle, name)
+        kL, got_u, got_d = _stereo_on(exL, exR, r)
+        if name == "zero":
+            # Frame.cc:612-616 observed: disparity 0 -> 0.01, mvuRight = uL - 0.01 (a double subtraction), kept by the median
+            clamped = got_d == np.float32(r["mbf"]) / np.float32(0.01)
+            assert clamped.sum() >= 10
+            assert np.array_equal(got_u[clamped], (kL["x"][clamped].astype(np.float64) - 0.01).astype(np.float32))
+        if name == "right_blank":
+            assert len(got_u) > 400 and np.all(got_u == -1) and np.all(got_d == -1)
+        if name == "left_blank":
+            assert len(got_u) == 0 and len(got_d) == 0
+    exL.close(); exR.close()
+
+
+def test_stereo_small_accepted_sets(gpu, oracle):
+    """k_stereo_median's n / 2 on accepted sets of 1, 2, 3, 5 and 6 (stereo_cases.SMALL_SETS)"""
+    import stereo_cases as sc
+    from orbslamm_amd import ORBextractor
+    for nf, accepted in sc.SMALL_SETS.items():
+        r = sc.scene(oracle, "small_sets:%d" % nf)
+        assert r["accepted"] == accepted
+        exL = ORBextractor(nf, *sc.EXTRACTOR, max_width=sc.W, max_height=sc.H, max_batch=1, device=0)
+        exR = ORBextractor(nf, *sc.EXTRACTOR, max_width=sc.W, max_height=sc.H, max_batch=1, device=0)
+        _, got_u, _ = _stereo_on(exL, exR, r)
+        assert 1 <= (got_u >= 0).sum() <= accepted
+        exL.close(); exR.close()
+
+
 def test_stereo_argument_errors(gpu):
     from orbslamm_amd import ORBextractor, OrbError
     a = ORBextractor(500, 1.2, 8, 20, 7, max_width=320, max_height=240, max_batch=1, device=0)
