@@ -43,6 +43,16 @@
 //       MapPoint::mfMinDistance / mfMaxDistance are read raw (the library forms the invariance bounds and PredictScale's
 //       ratio itself); they are protected in the reference: INTEGRATION.md.  predict: the tree's own PredictScale as
 //       (ratio, logScaleFactor) -> level where its log resolves to the double overload; null: the float form.
+//
+//   KeyFrameCullingT<KeyFrame, MapPoint>::Run(pool, store, mpCurrentKeyFrame, idOfPoint, slotOfKF)
+//       the drop-in for the body of LocalMapping::KeyFrameCulling (:632-698, monocular; orbn_culling_counts) over
+//       the keyframe store and its pool; SyncOctaves(store, pKF, slotOfKF) sends mvKeysUn[i].octave of a keyframe once, behind
+//       its first UpdateLocalMapT::SyncKeyFrame.  It asks the counts of GetVectorCovisibleKeyFrames() without mnId == 0 and
+//       isOtherMapFirst() (:643) in ONE call and walks the list in order; at the first redundant keyframe it calls the
+//       keyframe's own SetBadFlag() (:696), whose effects it then sends up -- the keyframe's entries without their vote, the
+//       points that EraseObservation turned bad and the match slots they left, the bad flag, the graph records of the
+//       keyframes SetBadFlag rewired -- and, when anything went up, asks again for the rest of the list: the one serial
+//       dependency of the loop, so the verdicts are the serial loop's.  SetBadFlag's spanning-tree repair stays the reference's.
 #pragma once
 
 #include <map>
@@ -51,6 +61,7 @@
 #include <string>
 #include <vector>
 
+#include "KeyFrame_hip.hpp"
 #include "orbslamm_dropin.hpp"
 #include "orbslamm_hip.h"
 
@@ -300,6 +311,100 @@ private:
     }
 
     static void check(int rc) { detail::check(rc, "orbslamm_hip: "); }
+};
+
+template <class KeyFrame, class MapPoint>
+struct KeyFrameCullingT {
+    struct Result { int nCulled; int nCalls; };
+
+    template <class SlotOf>
+    static void SyncOctaves(orbu_store_t* store, KeyFrame* pKF, SlotOf slotOfKF)
+    {
+        std::vector<uint8_t> oct(pKF->mvKeysUn.size());
+        for (size_t i = 0; i < oct.size(); i++) oct[i] = (uint8_t)pKF->mvKeysUn[i].octave;
+        detail::check(orbu_kf_set_octaves(store, (int)slotOfKF(pKF), oct.data(), (int)oct.size()), "KeyFrameCulling(HIP) SyncOctaves: ");
+    }
+
+    template <class IdOf, class SlotOf>
+    static Result Run(orbw_pool_t* pool, orbu_store_t* store, KeyFrame* pCurrentKF, IdOf idOfPoint, SlotOf slotOfKF, int thObs = 3)
+    {
+        const char* who = "KeyFrameCulling(HIP): ";
+        Result res; res.nCulled = 0; res.nCalls = 0;
+        const std::vector<KeyFrame*> vpLocalKeyFrames = pCurrentKF->GetVectorCovisibleKeyFrames();   // :638
+        std::vector<KeyFrame*> list;
+        for (size_t i = 0; i < vpLocalKeyFrames.size(); i++)
+            if (!(vpLocalKeyFrames[i]->mnId == 0 || vpLocalKeyFrames[i]->isOtherMapFirst())) list.push_back(vpLocalKeyFrames[i]);   // :643
+        size_t from = 0;
+        while (from < list.size()) {
+            std::vector<int32_t> targets;
+            for (size_t i = from; i < list.size(); i++) targets.push_back((int32_t)slotOfKF(list[i]));
+            OrbnCulling r;
+            detail::check(orbn_culling_counts(store, targets.data(), (int)targets.size(), thObs, &r), who);
+            res.nCalls++;
+            const std::vector<uint8_t> redundant(r.redundant, r.redundant + r.K);   // (the view ends at the store's next call)
+            bool again = false;
+            const size_t base = from;
+            for (size_t i = base; i < list.size() && !again; i++) {
+                from = i + 1;
+                if (!redundant[i - base]) continue;   // :695
+                again = Cull(pool, store, list[i], idOfPoint, slotOfKF, who);
+                res.nCulled++;
+            }
+        }
+        return res;
+    }
+
+    // pKF->SetBadFlag() (:696) and its effects into the pool and the store; false when nothing changed there
+    template <class IdOf, class SlotOf>
+    static bool Cull(orbw_pool_t* pool, orbu_store_t* store, KeyFrame* pKF, IdOf idOfPoint, SlotOf slotOfKF, const char* who)
+    {
+        // ---- as it is: the keyframe's points with their observations, the keyframes whose graph record SetBadFlag may rewrite
+        const std::vector<MapPoint*> vpMPs = pKF->GetMapPointMatches();
+        std::vector<std::map<KeyFrame*, size_t> > obs(vpMPs.size());
+        std::vector<bool> wasBad(vpMPs.size(), true), voted(vpMPs.size(), false);
+        for (size_t i = 0; i < vpMPs.size(); i++)
+            if (vpMPs[i]) { obs[i] = vpMPs[i]->GetObservations(); wasBad[i] = vpMPs[i]->isBad(); voted[i] = vpMPs[i]->IsInKeyFrame(pKF); }
+        const bool kfWasBad = pKF->isBad();
+        detail::GraphWatch<KeyFrame, SlotOf> watch(slotOfKF);
+        watch.watch(pKF);
+        watch.watch(pKF->GetParent());
+        const std::set<KeyFrame*> connected = pKF->GetConnectedKeyFrames(), childs = pKF->GetChilds();
+        for (typename std::set<KeyFrame*>::const_iterator sit = connected.begin(); sit != connected.end(); sit++) watch.watch(*sit);
+        for (typename std::set<KeyFrame*>::const_iterator sit = childs.begin(); sit != childs.end(); sit++) watch.watch(*sit);
+        pKF->SetBadFlag();
+        // ---- what changed, into the pool and the store
+        bool changed = false;
+        std::vector<int32_t> badIds;
+        std::vector<uint8_t> badFlags;
+        std::map<KeyFrame*, std::vector<std::pair<int32_t, int32_t> > > slots;   // keyframe -> (idx, value) of its rewritten match slots
+        const std::vector<MapPoint*> now = pKF->GetMapPointMatches();
+        for (size_t i = 0; i < vpMPs.size(); i++) {
+            MapPoint* pMP = vpMPs[i];
+            if (!pMP) continue;
+            if (!wasBad[i] && pMP->isBad()) {   // MapPoint::SetBadFlag through EraseObservation: the observers' match slots are nulled
+                badIds.push_back((int32_t)idOfPoint(pMP)); badFlags.push_back(ORBW_FLAG_BAD);
+                for (typename std::map<KeyFrame*, size_t>::const_iterator mit = obs[i].begin(); mit != obs[i].end(); mit++)
+                    if (mit->first != pKF) slots[mit->first].push_back(std::make_pair((int32_t)mit->second, (int32_t)-1));
+            }
+            const int32_t value = i < now.size() && now[i] ? ((int32_t)idOfPoint(now[i]) | (now[i]->IsInKeyFrame(pKF) ? 0 : ORBU_ENTRY_NO_VOTE)) : -1;
+            const int32_t was = (int32_t)idOfPoint(pMP) | (voted[i] ? 0 : ORBU_ENTRY_NO_VOTE);
+            if (value != was) slots[pKF].push_back(std::make_pair((int32_t)i, value));
+        }
+        if (!badIds.empty()) { detail::check(orbw_pool_set_flags(pool, badIds.data(), badFlags.data(), (int)badIds.size()), who); changed = true; }
+        for (typename std::map<KeyFrame*, std::vector<std::pair<int32_t, int32_t> > >::const_iterator it = slots.begin(); it != slots.end(); it++) {
+            std::vector<int32_t> idx, vals;
+            for (size_t q = 0; q < it->second.size(); q++) { idx.push_back(it->second[q].first); vals.push_back(it->second[q].second); }
+            detail::check(orbu_kf_set_entries(store, (int)slotOfKF(it->first), idx.data(), vals.data(), (int)idx.size()), who);
+            changed = true;
+        }
+        if (pKF->isBad() != kfWasBad) {
+            const int32_t slot = (int32_t)slotOfKF(pKF);
+            const uint8_t flags = pKF->isBad() ? ORBU_KF_BAD : 0;
+            detail::check(orbu_kf_set_flags(store, &slot, &flags, 1), who);
+        }
+        watch.push(store, who);
+        return changed;
+    }
 };
 
 }  // namespace iORB_SLAM

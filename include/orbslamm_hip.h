@@ -984,6 +984,8 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 #include "orbslamm_mappool.h"
 /* Tracking::UpdateLocalMap from a keyframe store beside that pool (orbu_*, orbw_track_local_map_resident): orbslamm_localmap.h. */
 #include "orbslamm_localmap.h"
+/* KeyFrame::UpdateConnections and KeyFrameCulling's counts over that store (orbn_*, orbu_kf_set_octaves): orbslamm_covis.h. */
+#include "orbslamm_covis.h"
 /* PoseOptimization behind those searches, fed from the pool, the frame set and the search's own table (orbq_track_pose):
  * orbslamm_trackpose.h. */
 #include "orbslamm_trackpose.h"

@@ -140,6 +140,11 @@ EXPORTS_LOCALMAP_UPDATE = [
     "orbu_update_local_map", "orbu_local_points", "orbu_debug_set_generation", "orbu_debug_resident_list", "orbw_track_local_map_resident",
 ]
 
+# the covisibility block over the keyframe store (include/orbslamm_covis.h, which include/orbslamm_hip.h includes)
+EXPORTS_COVIS = [
+    "orbu_kf_set_octaves", "orbn_update_connections", "orbn_culling_counts",
+]
+
 # the block that closes TrackLocalMap / TrackWithMotionModel (include/orbslamm_trackpose.h, which include/orbslamm_hip.h includes)
 EXPORTS_TRACKPOSE = [
     "orbq_track_pose", "orbq_track_reference",
@@ -149,7 +154,7 @@ EXPORTS_TRACKPOSE = [
 def build(force=False):
     """hipcc the extension in-tree for gfx950 (cross-compiles without a GPU)."""
     deps = [os.path.join(_PKG, "csrc", f) for f in os.listdir(os.path.join(_PKG, "csrc"))]
-    deps += [os.path.join(_ROOT, "include", f) for f in ("orbslamm_hip.h", "orbslamm_fuse.h", "orbslamm_loopfuse.h", "orbslamm_poseopt.h", "orbslamm_sim3opt.h", "orbslamm_mappool.h", "orbslamm_localmap.h", "orbslamm_trackpose.h")]
+    deps += [os.path.join(_ROOT, "include", f) for f in ("orbslamm_hip.h", "orbslamm_fuse.h", "orbslamm_loopfuse.h", "orbslamm_poseopt.h", "orbslamm_sim3opt.h", "orbslamm_mappool.h", "orbslamm_localmap.h", "orbslamm_covis.h", "orbslamm_trackpose.h")]
     if not force and os.path.exists(SO_PATH) and all(os.path.getmtime(SO_PATH) >= os.path.getmtime(d) for d in deps):
         return SO_PATH
     cmd = ["hipcc"] + HIPCC_FLAGS + ["-o", SO_PATH, SRC]
@@ -195,7 +200,7 @@ def lib():
         L = C.CDLL(os.environ.get("ORBSLAMM_HIP_LIB") or SO_PATH)
         L.orbx_last_error.restype = C.c_char_p
         L.orbx_scale_factor.restype = C.c_float
-        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP + EXPORTS_LOCALMAP + EXPORTS_FUSE + EXPORTS_LOOPFUSE + EXPORTS_POSEOPT + EXPORTS_SIM3OPT + EXPORTS_MAPPOOL + EXPORTS_LOCALMAP_UPDATE + EXPORTS_TRACKPOSE:
+        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP + EXPORTS_LOCALMAP + EXPORTS_FUSE + EXPORTS_LOOPFUSE + EXPORTS_POSEOPT + EXPORTS_SIM3OPT + EXPORTS_MAPPOOL + EXPORTS_LOCALMAP_UPDATE + EXPORTS_COVIS + EXPORTS_TRACKPOSE:
             getattr(L, name)
         L.orbx_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _lib = L

@@ -54,6 +54,7 @@
 #include "orbz_kernels.hip"
 #include "orbw_kernels.hip"   // the map-point pool and the projections of the two tracking searches
 #include "orbu_kernels.hip"   // UpdateLocalMap: the keyframe vote, the local keyframe list, the local point list
+#include "orbn_kernels.hip"   // covisibility: UpdateConnections' counter and ordered list, KeyFrameCulling's counts, over the store
 #include "orbq_kernels.hip"   // PoseOptimization from the pool: merge, ordered edge list, orbo's solve, Tracking's loop behind it
 
 using namespace orbx;
@@ -214,4 +215,5 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbz_host.inc"   // OptimizeSim3
 #include "orbw_host.inc"   // the map-point pool: SearchLocalPoints and TrackWithMotionModel's search from resident MapPoints
 #include "orbu_host.inc"   // the keyframe store beside the pool: UpdateLocalMap, and SearchLocalPoints from its resident list
+#include "orbn_host.inc"   // the covisibility entries over the store: batched UpdateConnections and KeyFrameCulling counts
 #include "orbq_host.inc"   // PoseOptimization behind the pool searches: TrackWithMotionModel's and TrackLocalMap's verdicts

@@ -12,6 +12,11 @@ static_assert(ORBU_ENTRY_NO_VOTE == orbu::kNoVote && ORBU_MAX_KEYFRAMES == orbu:
 constexpr size_t kStoreMaxEntries = (size_t)1 << 28;   // kf_capacity * pitch: positions of the point walk fit 32 bits with room
 constexpr size_t kStoreStageBytes = (size_t)8 << 20;   // a setter launch's staged records
 
+struct orbn_blocks;                                    // orbn_host.inc: the covisibility entries' blocks, made at their first call
+struct orbu_store;
+static void orbn_release(orbu_store* s);
+static int orbn_clear_marks(orbu_store* s, hipStream_t st);
+
 struct orbu_store {
     uint64_t serial = ++g_poolSerial;
     orbw_pool* pool = nullptr;
@@ -31,6 +36,10 @@ struct orbu_store {
     uint32_t updates = 0;                              // updates begun so far: each overwrites S
     unsigned blocks = 1;                               // the point walk's grid at the most: one block a chunk of the whole store, <= 1 024
     int lastNkf = 0;                                   // the local keyframes of the last update: sizes the next update's grid
+    orbn_blocks* covis = nullptr;                      // orbn_*: null until the first call
+    uint8_t* d_oct = nullptr;                          // orbu_kf_set_octaves: [kfcap * pitch] bytes, null until the first call
+    std::vector<uint8_t> kfOct;                        // the slots that have octaves
+    uint8_t octSeen[256] = {};                         // the octave values the store has been given
 };
 
 static int orbu_store_check(orbu_store* s)
@@ -103,6 +112,7 @@ extern "C" int orbu_store_destroy(orbu_store_t* s)
         for (auto& r : s->pool->readers) (void)hipEventSynchronize(r.ev);   // a resident search may still read S
         (void)hipStreamSynchronize(s->pool->stream);
     }
+    orbn_release(s);
     (void)hipFree(s->d_block);
     (void)hipHostFree(s->h_res);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
@@ -321,6 +331,7 @@ static int orbu_run(orbu_store* s, bool given, const int32_t* kf_list, int nkf, 
     if (s->gen == 0xffffffffu) {   // the tag wraps: one clear, and the tags start over
         HIPCHK(hipMemsetAsync(s->scr.stamp, 0, (size_t)p->cap * 8, st));
         HIPCHK(hipMemsetAsync(s->scr.first, 0xff, (size_t)p->cap * 8, st));
+        if ((rc = orbn_clear_marks(s, st))) return rc;
         s->gen = 0;
     }
     s->scr.gen = ++s->gen;

@@ -184,10 +184,65 @@ class OrbuResult(C.Structure):
                 ("L", C.c_void_p), ("seen", C.c_void_p), ("votes", C.c_void_p)]
 
 
+# ---- KeyFrame::UpdateConnections and KeyFrameCulling's counts over the store (include/orbslamm_covis.h)
+COVIS_OK, COVIS_EMPTY = 0, 1
+MAX_OCTAVE_VALUES = 16
+
+
+class OrbnConnections(C.Structure):
+    _fields_ = [("K", C.c_int32), ("status", C.c_void_p), ("kf_max", C.c_void_p), ("n_max", C.c_void_p), ("cnt_start", C.c_void_p), ("cnt_kf", C.c_void_p),
+                ("cnt_w", C.c_void_p), ("ord_start", C.c_void_p), ("ord_kf", C.c_void_p), ("ord_w", C.c_void_p)]
+
+
+class OrbnCulling(C.Structure):
+    _fields_ = [("K", C.c_int32), ("n_mps", C.c_void_p), ("n_redundant", C.c_void_p), ("redundant", C.c_void_p)]
+
+
+def _copy(p, n, ct, dt):
+    return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).astype(dt, copy=True) if p and n else np.zeros(0, dt)
+
+
+class Connections:
+    """orbn_update_connections' arrays, copied out of the store's blocks: status, kf_max, n_max per target; the counter rows
+    (cnt_start, cnt_kf, cnt_w: mConnectedKeyFrameWeights, ascending kf) and the ordered rows (ord_start, ord_kf, ord_w:
+    mvpOrderedConnectedKeyFrames / mvOrderedWeights) as CSR"""
+    NAMES = ("status", "kf_max", "n_max", "cnt_start", "cnt_kf", "cnt_w", "ord_start", "ord_kf", "ord_w")
+
+    def __init__(self, r):
+        K = self.K = r.K
+        i32 = lambda p, n: _copy(p, n, C.c_int32, np.int32)
+        self.status, self.kf_max, self.n_max = i32(r.status, K), i32(r.kf_max, K), i32(r.n_max, K)
+        self.cnt_start = i32(r.cnt_start, K + 1) if K else np.zeros(1, np.int32)
+        self.ord_start = i32(r.ord_start, K + 1) if K else np.zeros(1, np.int32)
+        self.cnt_kf, self.cnt_w = i32(r.cnt_kf, int(self.cnt_start[-1])), i32(r.cnt_w, int(self.cnt_start[-1]))
+        self.ord_kf, self.ord_w = i32(r.ord_kf, int(self.ord_start[-1])), i32(r.ord_w, int(self.ord_start[-1]))
+
+    def counter(self, t):
+        a, b = self.cnt_start[t], self.cnt_start[t + 1]
+        return self.cnt_kf[a:b], self.cnt_w[a:b]
+
+    def ordered(self, t):
+        a, b = self.ord_start[t], self.ord_start[t + 1]
+        return self.ord_kf[a:b], self.ord_w[a:b]
+
+
+class Culling:
+    """orbn_culling_counts' arrays, copied out: n_mps, n_redundant, redundant per target"""
+    NAMES = ("n_mps", "n_redundant", "redundant")
+
+    def __init__(self, r):
+        self.K = r.K
+        self.n_mps, self.n_redundant = _copy(r.n_mps, r.K, C.c_int32, np.int32), _copy(r.n_redundant, r.K, C.c_int32, np.int32)
+        self.redundant = _copy(r.redundant, r.K, C.c_uint8, np.uint8)
+
+
 def _setup_store(L):
     if getattr(L, "_orbu_ready", False):
         return
     vp = C.c_void_p
+    L.orbu_kf_set_octaves.argtypes = [vp, C.c_int, vp, C.c_int]
+    L.orbn_update_connections.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    L.orbn_culling_counts.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     L.orbu_store_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.orbu_store_destroy.argtypes = [vp]
     L.orbu_kf_set.argtypes = [vp, vp]
@@ -299,6 +354,25 @@ class KeyFrameStore:
         idx, vals = _ids(idx), _ids(vals)
         assert idx.shape[0] == vals.shape[0]
         check(self._L.orbu_kf_set_entries(self._h, int(slot), ptr(idx), ptr(vals), idx.shape[0]))
+
+    def set_octaves(self, slot, octaves):
+        """orbu_kf_set_octaves: mvKeysUn[i].octave of a set keyframe, one byte per feature"""
+        o = np.ascontiguousarray(octaves, dtype=np.uint8).reshape(-1)
+        check(self._L.orbu_kf_set_octaves(self._h, int(slot), ptr(o), o.shape[0]))
+
+    def update_connections(self, targets, th=15):
+        """orbn_update_connections: KeyFrame::UpdateConnections' counter and ordered list of every target -> Connections"""
+        tg = _ids(targets)
+        r = OrbnConnections()
+        check(self._L.orbn_update_connections(self._h, ptr(tg), tg.shape[0], int(th), C.byref(r)))
+        return Connections(r)
+
+    def culling_counts(self, targets, th_obs=3):
+        """orbn_culling_counts: KeyFrameCulling's nMPs, nRedundantObservations and verdict of every target -> Culling"""
+        tg = _ids(targets)
+        r = OrbnCulling()
+        check(self._L.orbn_culling_counts(self._h, ptr(tg), tg.shape[0], int(th_obs), C.byref(r)))
+        return Culling(r)
 
     def update(self, frame_ids, max_keyframes=80):
         """orbu_update_local_map -> LocalMap (status LOCAL_NO_VOTES: nothing else is meaningful)"""
