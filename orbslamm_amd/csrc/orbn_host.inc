@@ -4,7 +4,8 @@
 //                 keys on the device, the chunk's rows in pinned memory; the histograms at the first culling call; the octave
 //                 bytes at the first orbu_kf_set_octaves.  The result arrays are host vectors that keep their capacity.
 //   a call        targets kChunk at a time, each chunk under a generation tag of its own (the store's counter, shared with
-//                 orbu_update_local_map, whose scratch a larger tag leaves valid)
+//                 orbu_update_local_map, whose scratch a larger tag leaves valid).  The tag, the slot checks and the writer's
+//                 opening: orbx_poolutil.inc
 
 static_assert(ORBN_MAX_OCTAVE_VALUES == orbn::kBins, "orbslamm_covis.h constants");
 
@@ -27,28 +28,7 @@ static void orbn_release(orbu_store* s)
     if (s->covis->d_hist) (void)hipFree(s->covis->d_hist);
     if (s->covis->h_rows) (void)hipHostFree(s->covis->h_rows);
     delete s->covis;
-    s->covis = nullptr;
-}
-
-// (the pool's mutex is held) the tag wraps: the marks start over with orbu's scratch
-static int orbn_clear_marks(orbu_store* s, hipStream_t st)
-{
-    if (s->covis) HIPCHK(hipMemsetAsync(s->covis->dev.mark, 0, (size_t)s->pool->cap * 8, st));
-    return ORBX_OK;
-}
-
-// (the pool's mutex is held) the next generation tag
-static int orbn_next_generation(orbu_store* s, hipStream_t st)
-{
-    if (s->gen == 0xffffffffu) {
-        HIPCHK(hipMemsetAsync(s->scr.stamp, 0, (size_t)s->pool->cap * 8, st));
-        HIPCHK(hipMemsetAsync(s->scr.first, 0xff, (size_t)s->pool->cap * 8, st));
-        int rc = orbn_clear_marks(s, st);
-        if (rc) return rc;
-        s->gen = 0;
-    }
-    s->covis->dev.gen = ++s->gen;
-    return ORBX_OK;
+    s->covis = nullptr; s->marks = nullptr;   // (marks is b->dev.mark: the two go together, here and in orbn_blocks_ensure)
 }
 
 // (the pool's mutex is held)
@@ -75,7 +55,7 @@ static int orbn_blocks_ensure(orbu_store* s, bool hist)
         b->out.hdr = (int32_t*)(b->h_rows + hHdr); b->out.cntKf = (int32_t*)(b->h_rows + hCk); b->out.cntW = (int32_t*)(b->h_rows + hCw);
         b->out.ordKf = (int32_t*)(b->h_rows + hOk); b->out.ordW = (int32_t*)(b->h_rows + hOw);
         p->h->nDevAlloc++; p->h->nHostAlloc++;
-        s->covis = b;
+        s->covis = b; s->marks = b->dev.mark;   // (what orbu_next_generation clears at the wrap: set with covis, dropped with it in orbn_release)
     }
     if (hist && !s->covis->d_hist) {
         HIPCHK(hipMalloc((void**)&s->covis->d_hist, (size_t)p->cap * orbn::kBins * 4));
@@ -95,7 +75,7 @@ extern "C" int orbu_kf_set_octaves(orbu_store_t* s, int slot, const uint8_t* oct
     if (rc) return rc;
     orbw_pool* p = s->pool;
     std::lock_guard<std::mutex> l(p->mu);
-    if (slot >= s->kfcap || !s->kfSet[slot]) return fail(ORBX_E_INVALID, "keyframe slot %d is outside the store of %d or was never set", slot, s->kfcap);
+    if ((rc = orbu_check_slot(s, "slot", 0, slot, true))) return rc;
     if (n > s->stride) return fail(ORBX_E_UNSUPPORTED, "%d octaves for a stride of %d", n, s->stride);
     {   // the distinct values the store has been given: the histograms have a bin for each
         bool seen[256];
@@ -116,8 +96,7 @@ extern "C" int orbu_kf_set_octaves(orbu_store_t* s, int slot, const uint8_t* oct
         if (e != hipSuccess) { (void)hipFree(s->d_oct); s->d_oct = nullptr; return fail(ORBX_E_HIP, "clearing the octave block failed: %s", hipGetErrorString(e)); }
         s->kfOct.assign((size_t)s->kfcap, 0);
     }
-    if ((rc = grow_pinned(s->h_stage, s->stageCap, (size_t)s->pitch, true, nullptr, &p->h->nHostAlloc))) return rc;
-    if ((rc = orbw_wait_readers(p))) return rc;
+    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, (size_t)s->pitch))) return rc;
     if (n) memcpy(s->h_stage, octaves, (size_t)n);
     memset(s->h_stage + n, 0, (size_t)(s->pitch - n));
     HIPCHK(hipMemcpyAsync(s->d_oct + (size_t)slot * s->pitch, s->h_stage, (size_t)s->pitch, hipMemcpyHostToDevice, p->stream));
@@ -143,12 +122,9 @@ static int orbn_check_call(orbu_store* s, const int32_t* targets, int K, int th,
 // (the pool's mutex is held)
 static int orbn_check_targets(const orbu_store* s, const int32_t* targets, int K)
 {
-    for (int i = 0; i < K; i++) {
-        const int k = targets[i];
-        if (k < 0 || k >= s->kfcap) return fail(ORBX_E_INVALID, "targets[%d] = %d outside the store of %d", i, k, s->kfcap);
-        if (!s->kfSet[k]) return fail(ORBX_E_INVALID, "targets[%d] = %d was never set", i, k);
-    }
-    return ORBX_OK;
+    int rc = ORBX_OK;
+    for (int i = 0; i < K && !rc; i++) rc = orbu_check_slot(s, "targets", i, targets[i], true);
+    return rc;
 }
 
 extern "C" int orbn_update_connections(orbu_store_t* s, const int32_t* targets, int K, int th, OrbnConnections* result)
@@ -160,8 +136,7 @@ extern "C" int orbn_update_connections(orbu_store_t* s, const int32_t* targets, 
     std::lock_guard<std::mutex> l(p->mu);
     if ((rc = orbn_check_targets(s, targets, K))) return rc;
     if ((rc = orbn_blocks_ensure(s, false))) return rc;
-    if ((rc = grow_pinned(s->h_stage, s->stageCap, (size_t)K * 4, true, nullptr, &p->h->nHostAlloc))) return rc;
-    if ((rc = orbw_wait_readers(p))) return rc;
+    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, (size_t)K * 4))) return rc;
     orbn_blocks* b = s->covis;
     hipStream_t st = p->stream;
     memcpy(s->h_stage, targets, (size_t)K * 4);
@@ -172,7 +147,7 @@ extern "C" int orbn_update_connections(orbu_store_t* s, const int32_t* targets, 
     const unsigned walkBlocks = (unsigned)((s->hi + orbn::kWaves - 1) / orbn::kWaves);
     for (int c0 = 0; c0 < K; c0 += orbn::kChunk) {
         const int nC = std::min(orbn::kChunk, K - c0);
-        if ((rc = orbn_next_generation(s, st))) return rc;
+        if ((rc = orbu_next_generation(s, st, &b->dev.gen))) return rc;
         hipLaunchKernelGGL(orbn::k_mark, dim3((unsigned)nC), dim3(orbn::kThreads), 0, st, s->dev, b->dev, tg + c0, 0);
         hipLaunchKernelGGL(orbn::k_conn_walk, dim3(walkBlocks), dim3(orbn::kThreads), 0, st, s->dev, b->dev, tg + c0, nC, s->hi);
         hipLaunchKernelGGL(orbn::k_conn_select, dim3((unsigned)nC), dim3(orbn::kThreads), 0, st, s->dev, b->dev, s->hi, th, b->out);
@@ -215,8 +190,7 @@ extern "C" int orbn_culling_counts(orbu_store_t* s, const int32_t* targets, int 
     Packer pk;
     const size_t oTg = pk.take((size_t)K * 4), oBin = pk.take(256), oUpto = pk.take(257), oMps = pk.take((size_t)K * 4), oRed = pk.take((size_t)K * 4),
                  oFlag = pk.take((size_t)K);
-    if ((rc = grow_pinned(s->h_stage, s->stageCap, pk.off, true, nullptr, &p->h->nHostAlloc))) return rc;
-    if ((rc = orbw_wait_readers(p))) return rc;
+    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, pk.off))) return rc;
     orbn_blocks* b = s->covis;
     hipStream_t st = p->stream;
     memcpy(s->h_stage + oTg, targets, (size_t)K * 4);
@@ -233,7 +207,7 @@ extern "C" int orbn_culling_counts(orbu_store_t* s, const int32_t* targets, int 
     const unsigned walkBlocks = (unsigned)((s->hi + orbn::kWaves - 1) / orbn::kWaves);
     for (int c0 = 0; c0 < K; c0 += orbn::kChunk) {
         const int nC = std::min(orbn::kChunk, K - c0);
-        if ((rc = orbn_next_generation(s, st))) return rc;
+        if ((rc = orbu_next_generation(s, st, &b->dev.gen))) return rc;
         hipLaunchKernelGGL(orbn::k_mark, dim3((unsigned)nC), dim3(orbn::kThreads), 0, st, s->dev, b->dev, tg + c0, 1);
         hipLaunchKernelGGL(orbn::k_hist_walk, dim3(walkBlocks), dim3(orbn::kThreads), 0, st, s->dev, b->dev, (const uint8_t*)(s->h_stage + oBin), s->hi);
         hipLaunchKernelGGL(orbn::k_cull, dim3((unsigned)nC), dim3(orbn::kThreads), 0, st, s->dev, b->dev, tg + c0, th_obs, (const int8_t*)(s->h_stage + oUpto),

@@ -2,6 +2,8 @@
 // orbq_kernels.hip, ABI: include/orbslamm_trackpose.h, DESIGN.md §8s).  One call = the checks, one packed upload (job records |
 // the frames' ids before the search), ONE launch for all jobs on the handle's stream, one copy down (results | ids | outlier
 // bytes), one synchronise.  The searches' tables and ids are read where the searches left them: nothing per match goes up.
+// The pool's and the store's checks, the id and slot checkers, the reader mark: orbx_poolutil.inc.  orbq_track_reference (below)
+// repeats this entry's frame: a shared scaffold came out no shorter (docs/experiments.md).
 
 static_assert(sizeof(OrbqJob) == 112 && sizeof(OrbqResult) == 184, "orbslamm_trackpose.h layouts");
 static_assert(ORBW_FLAG_OBSERVED == 2, "k_track_pose reads the observed bit");
@@ -92,12 +94,7 @@ extern "C" int orbq_track_pose(orbm_t* h, orbw_pool_t* pool, const OrbqJob* jobs
         orbq::JobDev& D = hj[j];
         if ((rc = orbq_job_source(pool, J, j, D))) return rc;
         if (J.base_ids) {
-            for (int t = 0; t < J.n; t++) {
-                const int id = J.base_ids[t];
-                if (id == -1) continue;
-                if (id < 0 || id >= pool->cap) return fail(ORBX_E_INVALID, "job %d: base_ids[%d] = %d outside the pool of %d", j, t, id, pool->cap);
-                if (!pool->isSet(id)) return fail(ORBX_E_INVALID, "job %d: base_ids[%d] = %d was never set", j, t, id);
-            }
+            if ((rc = orbw_check_ids(pool, "base_ids", J.base_ids, J.n, true))) return fail(rc, "job %d: %s", j, g_err.c_str());
             if (J.n) memcpy(hs + oBase + b0 * 4, J.base_ids, (size_t)J.n * 4);
         }
         memcpy(D.Tcw, J.frame.Tcw, sizeof D.Tcw);
@@ -194,7 +191,7 @@ extern "C" int orbq_track_reference(orbm_t* h, orbw_pool_t* pool, orbu_store_t* 
         // (the search's scratch is 11 bytes a feature of the set's CAP, whatever n is: bounded like the features)
         if (sumCap > (size_t)ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "the jobs' frame sets hold more than %d features together (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
         if (!J.fs->bow || !J.fs->bow->computed) return fail(ORBX_E_INVALID, "job %d: orbm_frameset_compute_bow has not run", j);
-        if (J.kf >= store->kfcap) return fail(ORBX_E_INVALID, "job %d: keyframe %d outside the store of %d", j, J.kf, store->kfcap);
+        if ((rc = orbu_check_slot(store, "kf of job", j, J.kf, false))) return rc;   // (kfcap never changes; the set byte: under the mutex, below)
         // (a set that builds on a stream of its own: the slots' builds may still run there)
         if (fs_stream(J.fs) != h->stream) HIPCHK(hipStreamSynchronize(fs_stream(J.fs)));
         total += (size_t)J.n;
@@ -216,7 +213,7 @@ extern "C" int orbq_track_reference(orbm_t* h, orbw_pool_t* pool, orbu_store_t* 
     int maxCap = 0;
     for (int j = 0; j < n_jobs; j++) {
         const OrbqRefJob& J = jobs[j];
-        if (!store->kfSet[(size_t)J.kf]) return fail(ORBX_E_INVALID, "job %d: keyframe %d was never set", j, J.kf);
+        if ((rc = orbu_check_slot(store, "kf of job", j, J.kf, true))) return rc;
         orbq::RefJobDev& D = hj[j];
         memset(&D, 0, sizeof D);
         memcpy(D.Tcw, J.frame.Tcw, sizeof D.Tcw);

@@ -213,6 +213,7 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbc_host.inc"   // SearchAndFuse
 #include "orbo_host.inc"   // PoseOptimization
 #include "orbz_host.inc"   // OptimizeSim3
+#include "orbx_poolutil.inc"   // the pool and the store as the host holds them; what orbw, orbu, orbn and orbq share on the host
 #include "orbw_host.inc"   // the map-point pool: SearchLocalPoints and TrackWithMotionModel's search from resident MapPoints
 #include "orbu_host.inc"   // the keyframe store beside the pool: UpdateLocalMap, and SearchLocalPoints from its resident list
 #include "orbn_host.inc"   // the covisibility entries over the store: batched UpdateConnections and KeyFrameCulling counts

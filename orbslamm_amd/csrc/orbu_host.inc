@@ -1,7 +1,6 @@
 // orbu_host.inc -- host side of Tracking::UpdateLocalMap on the device (part of orbslamm_hip.hip; kernels: orbu_kernels.hip,
 // ABI: include/orbslamm_localmap.h, DESIGN.md §8r).
-//   the store     keyframe match lists, flags and graph records in HBM beside ONE map-point pool, whose mutex and stream it
-//                 uses; a "set" byte per slot on the host; all blocks of a fixed size made at create, the staging grow-only
+//   the store     struct orbu_store, the slot and entry checks, the generation tag, the last-wins staging: orbx_poolutil.inc
 //   the call      stamp, vote, select, mark, count, scan, write on the pool's stream, one synchronisation; the kernels leave
 //                 the result in the store's pinned block themselves
 //   the search    orbw_track (orbw_host.inc) reading the store's S where it lies
@@ -10,44 +9,7 @@ static_assert(ORBU_ENTRY_NO_VOTE == orbu::kNoVote && ORBU_MAX_KEYFRAMES == orbu:
               "orbslamm_localmap.h constants");
 
 constexpr size_t kStoreMaxEntries = (size_t)1 << 28;   // kf_capacity * pitch: positions of the point walk fit 32 bits with room
-constexpr size_t kStoreStageBytes = (size_t)8 << 20;   // a setter launch's staged records
-
-struct orbn_blocks;                                    // orbn_host.inc: the covisibility entries' blocks, made at their first call
-struct orbu_store;
-static void orbn_release(orbu_store* s);
-static int orbn_clear_marks(orbu_store* s, hipStream_t st);
-
-struct orbu_store {
-    uint64_t serial = ++g_poolSerial;
-    orbw_pool* pool = nullptr;
-    int kfcap = 0, stride = 0, pitch = 0, maxc = 0, maxcP = 0, maxL = 0;
-    uint8_t* d_block = nullptr;
-    orbu::StoreDev dev{};
-    orbu::Scratch scr{};
-    orbu::Out out{};
-    uint8_t* h_res = nullptr;                          // pinned, coherent: header | list | votes | L | seen
-    uint8_t* h_stage = nullptr; size_t stageCap = 0;   // pinned, coherent: a setter's records, or a call's ids and list
-    std::vector<uint8_t> kfSet, kfSeen;                // kfSeen: a setter's scratch, all zero between calls
-    std::vector<uint8_t> idxSeen;
-    std::vector<int64_t> eOff, cOff; std::vector<int> lastOf;   // orbu_kf_write's scratch: they keep their capacity between calls
-    int hi = 0;                                        // the highest set slot + 1
-    uint32_t gen = 0;
-    bool updated = false; int nS = 0;                  // the last update completed: S holds nS ids
-    uint32_t updates = 0;                              // updates begun so far: each overwrites S
-    unsigned blocks = 1;                               // the point walk's grid at the most: one block a chunk of the whole store, <= 1 024
-    int lastNkf = 0;                                   // the local keyframes of the last update: sizes the next update's grid
-    orbn_blocks* covis = nullptr;                      // orbn_*: null until the first call
-    uint8_t* d_oct = nullptr;                          // orbu_kf_set_octaves: [kfcap * pitch] bytes, null until the first call
-    std::vector<uint8_t> kfOct;                        // the slots that have octaves
-    uint8_t octSeen[256] = {};                         // the octave values the store has been given
-};
-
-static int orbu_store_check(orbu_store* s)
-{
-    if (!s) return fail(ORBX_E_INVALID, "null store");
-    if (!live_has(s)) return fail(ORBX_E_INVALID, "the store was destroyed");
-    return orbw_pool_check(s->pool);
-}
+static void orbn_release(orbu_store* s);   // orbn_host.inc
 
 extern "C" int orbu_store_create(orbw_pool_t* pool, int kf_capacity, int stride, int max_children, int max_local_points, orbu_store_t** out)
 {
@@ -91,7 +53,7 @@ extern "C" int orbu_store_create(orbw_pool_t* pool, int kf_capacity, int stride,
     s->out.L = (int32_t*)(d + oL); s->out.S = (int32_t*)(d + oS);
     s->out.hHdr = (int32_t*)(s->h_res + hHdr); s->out.hList = (int32_t*)(s->h_res + hList); s->out.hVotes = (int32_t*)(s->h_res + hVotes);
     s->out.hL = (int32_t*)(s->h_res + hL); s->out.hSeen = s->h_res + hSeen; s->out.maxL = s->maxL;
-    s->kfSet.assign(K, 0); s->kfSeen.assign(K, 0); s->idxSeen.assign((size_t)stride, 0);
+    s->kfSet.assign(K, 0); s->kfSeen.assign((K + 63) / 64, 0); s->idxSeen.assign(((size_t)stride + 63) / 64, 0);
     s->blocks = (unsigned)std::min<size_t>(nchunks, 1024);
     pool->h->refs++;
     pool->h->nDevAlloc++; pool->h->nHostAlloc++;
@@ -121,16 +83,6 @@ extern "C" int orbu_store_destroy(orbu_store_t* s)
     return ORBX_OK;
 }
 
-// (the pool's mutex is held) an entry value: -1, or a pool id that is set, bit 30 aside
-static int orbu_check_entry(const orbu_store* s, int32_t v, const char* what, int i)
-{
-    if (v == -1) return ORBX_OK;
-    const int32_t id = v & ~ORBU_ENTRY_NO_VOTE;
-    if (v < 0 || id >= s->pool->cap) return fail(ORBX_E_INVALID, "%s[%d] = %d outside the pool of %d", what, i, v, s->pool->cap);
-    if (!s->pool->isSet(id)) return fail(ORBX_E_INVALID, "%s[%d]: pool id %d was never set", what, i, id);
-    return ORBX_OK;
-}
-
 // orbu_kf_set (whole = true) and orbu_kf_set_graph
 static int orbu_kf_write(orbu_store* s, const OrbuKeyFrames* kfs, bool whole)
 {
@@ -149,71 +101,50 @@ static int orbu_kf_write(orbu_store* s, const OrbuKeyFrames* kfs, bool whole)
     int rc = orbu_store_check(s);
     if (rc) return rc;
     std::lock_guard<std::mutex> l(s->pool->mu);
-    // every id, on the host, before any launch
-    {
-        int64_t e0 = 0, c0 = 0;
-        for (int i = 0; i < nkf; i++) {
-            const int k = kfs->slot[i];
-            if (k < 0 || k >= s->kfcap) return fail(ORBX_E_INVALID, "slot[%d] = %d outside the store of %d", i, k, s->kfcap);
-            if (!whole && !s->kfSet[k]) return fail(ORBX_E_INVALID, "slot[%d] = %d was never set", i, k);
-            if (whole && kfs->n[i] > s->stride) return fail(ORBX_E_UNSUPPORTED, "record %d: %d entries for a stride of %d", i, kfs->n[i], s->stride);
-            if (kfs->nchildren[i] > s->maxc) return fail(ORBX_E_UNSUPPORTED, "record %d: %d children, at most %d", i, kfs->nchildren[i], s->maxc);
-            if (whole)
-                for (int e = 0; e < kfs->n[i]; e++)
-                    if ((rc = orbu_check_entry(s, kfs->entries[e0 + e], "entries", (int)(e0 + e)))) return rc;
-            for (int j = 0; j < ORBU_MAX_NEIGHBOURS; j++) {
-                const int nb = kfs->neigh[(size_t)i * ORBU_MAX_NEIGHBOURS + j];
-                if (nb < -1 || nb >= s->kfcap) return fail(ORBX_E_INVALID, "record %d: neighbour %d outside the store of %d", i, nb, s->kfcap);
-            }
-            if (kfs->parent[i] < -1 || kfs->parent[i] >= s->kfcap) return fail(ORBX_E_INVALID, "record %d: parent %d outside the store of %d", i, kfs->parent[i], s->kfcap);
-            for (int c = 0; c < kfs->nchildren[i]; c++) {
-                const int ch = kfs->children[c0 + c];
-                if (ch < 0 || ch >= s->kfcap) return fail(ORBX_E_INVALID, "record %d: child %d outside the store of %d", i, ch, s->kfcap);
-            }
-            if (whole) e0 += kfs->n[i];
-            c0 += kfs->nchildren[i];
-        }
+    // every id, on the host, before any launch; where record i's entries and children start
+    s->eOff.resize((size_t)nkf); s->cOff.resize((size_t)nkf);
+    int64_t e0 = 0, c0 = 0;
+    for (int i = 0; i < nkf; i++) {
+        if ((rc = orbu_check_slot(s, "slot", i, kfs->slot[i], !whole))) return rc;
+        if (whole && kfs->n[i] > s->stride) return fail(ORBX_E_UNSUPPORTED, "record %d: %d entries for a stride of %d", i, kfs->n[i], s->stride);
+        if (kfs->nchildren[i] > s->maxc) return fail(ORBX_E_UNSUPPORTED, "record %d: %d children, at most %d", i, kfs->nchildren[i], s->maxc);
+        for (int e = 0; whole && e < kfs->n[i]; e++)
+            if ((rc = orbw_check_id(s->pool, "entries", (int)(e0 + e), kfs->entries[e0 + e], true, true))) return rc;
+        for (int j = 0; j < ORBU_MAX_NEIGHBOURS; j++)
+            if ((rc = orbu_check_slot(s, "a neighbour of record", i, kfs->neigh[(size_t)i * ORBU_MAX_NEIGHBOURS + j], false, true))) return rc;
+        if ((rc = orbu_check_slot(s, "parent", i, kfs->parent[i], false, true))) return rc;
+        for (int c = 0; c < kfs->nchildren[i]; c++)
+            if ((rc = orbu_check_slot(s, "children", (int)(c0 + c), kfs->children[c0 + c], false))) return rc;
+        s->eOff[i] = e0; s->cOff[i] = c0;
+        if (whole) e0 += kfs->n[i];
+        c0 += kfs->nchildren[i];
     }
-    const int recInts = orbu::kRecHead + s->maxcP + (whole ? s->pitch : 0);
+    const int maxcP = s->maxcP, pitch = s->pitch, recInts = orbu::kRecHead + maxcP + (whole ? pitch : 0);
     const int perLaunch = (int)std::max<size_t>(1, std::min<size_t>((size_t)nkf, kStoreStageBytes / ((size_t)recInts * 4)));
-    if ((rc = grow_pinned(s->h_stage, s->stageCap, (size_t)perLaunch * recInts * 4, true, nullptr, &s->pool->h->nHostAlloc))) return rc;
-    if ((rc = orbw_wait_readers(s->pool))) return rc;
-    // the last record of a repeated slot wins: keep a slot's last sighting
-    std::vector<int64_t>&eOff = s->eOff, &cOff = s->cOff;
-    eOff.resize((size_t)nkf); cOff.resize((size_t)nkf);
-    {
-        int64_t e0 = 0, c0 = 0;
-        for (int i = 0; i < nkf; i++) { eOff[i] = e0; cOff[i] = c0; if (whole) e0 += kfs->n[i]; c0 += kfs->nchildren[i]; }
-    }
-    std::vector<int>& lastOf = s->lastOf;
-    lastOf.clear();
-    for (int i = nkf - 1; i >= 0; i--) { uint8_t& b = s->kfSeen[kfs->slot[i]]; if (!b) { b = 1; lastOf.push_back(i); } }
-    for (int i = 0; i < nkf; i++) s->kfSeen[kfs->slot[i]] = 0;
-    int m = 0;
+    if ((rc = orbw_begin_write(s->pool, s->h_stage, s->stageCap, (size_t)perLaunch * recInts * 4))) return rc;
+    // (all by value, as orbw_pool_write's: captured by reference, the staged loop reloads them behind every store into the staging)
     int32_t* stage = (int32_t*)s->h_stage;
-    auto flush = [&]() -> int {
-        if (!m) return ORBX_OK;
-        hipLaunchKernelGGL(orbu::k_kf_scatter, dim3((unsigned)m), dim3(orbu::kThreads), 0, s->pool->stream, s->dev, (const int32_t*)stage, recInts, s->maxcP, whole ? 0 : 1);
+    const OrbuKeyFrames k = *kfs;
+    const int64_t *eOff = s->eOff.data(), *cOff = s->cOff.data();
+    auto emit = [=](int i, int m) {
+        int32_t* rec = stage + (size_t)m * recInts;
+        rec[0] = k.slot[i]; rec[1] = whole ? ((k.flags[i] & ORBU_KF_BAD) | ORBU_KF_SET) : 0;
+        for (int j = 0; j < ORBU_MAX_NEIGHBOURS; j++) rec[2 + j] = k.neigh[(size_t)i * ORBU_MAX_NEIGHBOURS + j];
+        rec[12] = k.parent[i]; rec[13] = k.nchildren[i]; rec[14] = rec[15] = 0;
+        for (int c = 0; c < maxcP; c++) rec[orbu::kRecHead + c] = c < k.nchildren[i] ? k.children[cOff[i] + c] : -1;
+        if (whole) {
+            int32_t* ent = rec + orbu::kRecHead + maxcP;
+            if (k.n[i]) memcpy(ent, k.entries + eOff[i], (size_t)k.n[i] * 4);
+            for (int e = k.n[i]; e < pitch; e++) ent[e] = -1;
+        }
+    };
+    auto flush = [=](int m) -> int {
+        hipLaunchKernelGGL(orbu::k_kf_scatter, dim3((unsigned)m), dim3(orbu::kThreads), 0, s->pool->stream, s->dev, (const int32_t*)stage, recInts, maxcP, whole ? 0 : 1);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s->pool->stream));   // (the staging is the next launch's; the call returns with the update complete)
-        m = 0;
+        HIPCHK(hipStreamSynchronize(s->pool->stream));
         return ORBX_OK;
     };
-    for (size_t q = 0; q < lastOf.size(); q++) {
-        const int i = lastOf[q];
-        int32_t* rec = stage + (size_t)m * recInts;
-        rec[0] = kfs->slot[i]; rec[1] = whole ? ((kfs->flags[i] & ORBU_KF_BAD) | ORBU_KF_SET) : 0;
-        for (int j = 0; j < ORBU_MAX_NEIGHBOURS; j++) rec[2 + j] = kfs->neigh[(size_t)i * ORBU_MAX_NEIGHBOURS + j];
-        rec[12] = kfs->parent[i]; rec[13] = kfs->nchildren[i]; rec[14] = rec[15] = 0;
-        for (int c = 0; c < s->maxcP; c++) rec[orbu::kRecHead + c] = c < kfs->nchildren[i] ? kfs->children[cOff[i] + c] : -1;
-        if (whole) {
-            int32_t* ent = rec + orbu::kRecHead + s->maxcP;
-            if (kfs->n[i]) memcpy(ent, kfs->entries + eOff[i], (size_t)kfs->n[i] * 4);
-            for (int e = kfs->n[i]; e < s->pitch; e++) ent[e] = -1;
-        }
-        if (++m == perLaunch && (rc = flush())) return rc;
-    }
-    if ((rc = flush())) return rc;
+    if ((rc = stage_last_wins(k.slot, nkf, nkf, perLaunch, s->kfSeen, emit, flush))) return rc;   // (one window: a slot is staged once however often the call repeats it)
     if (whole)
         for (int i = 0; i < nkf; i++) { s->kfSet[kfs->slot[i]] = 1; s->hi = std::max(s->hi, kfs->slot[i] + 1); }
     return ORBX_OK;
@@ -232,37 +163,26 @@ static int orbu_pairs_write(orbu_store* s, int slot, const int32_t* a, const int
     int rc = orbu_store_check(s);
     if (rc) return rc;
     std::lock_guard<std::mutex> l(s->pool->mu);
-    if (ent && (slot >= s->kfcap || !s->kfSet[slot])) return fail(ORBX_E_INVALID, "keyframe slot %d is outside the store of %d or was never set", slot, s->kfcap);
+    if (ent && (rc = orbu_check_slot(s, "slot", 0, slot, true))) return rc;
     for (int i = 0; i < n; i++) {
         if (ent) {
             if (a[i] < 0) return fail(ORBX_E_INVALID, "idx[%d] = %d", i, a[i]);
             if (a[i] >= s->stride) return fail(ORBX_E_UNSUPPORTED, "idx[%d] = %d for a stride of %d", i, a[i], s->stride);
-            if ((rc = orbu_check_entry(s, vals[i], "vals", i))) return rc;
-        } else {
-            if (a[i] < 0 || a[i] >= s->kfcap) return fail(ORBX_E_INVALID, "slots[%d] = %d outside the store of %d", i, a[i], s->kfcap);
-            if (!s->kfSet[a[i]]) return fail(ORBX_E_INVALID, "slots[%d] = %d was never set", i, a[i]);
-        }
+            if ((rc = orbw_check_id(s->pool, "vals", i, vals[i], true, true))) return rc;
+        } else if ((rc = orbu_check_slot(s, "slots", i, a[i], true))) return rc;
     }
     const int perLaunch = (int)std::min<size_t>((size_t)n, kStoreStageBytes / 8);
-    if ((rc = grow_pinned(s->h_stage, s->stageCap, (size_t)perLaunch * 8, true, nullptr, &s->pool->h->nHostAlloc))) return rc;
-    if ((rc = orbw_wait_readers(s->pool))) return rc;
-    std::vector<uint8_t>& seen = ent ? s->idxSeen : s->kfSeen;
+    if ((rc = orbw_begin_write(s->pool, s->h_stage, s->stageCap, (size_t)perLaunch * 8))) return rc;
     int2* stage = (int2*)s->h_stage;
-    for (int c0 = 0; c0 < n; c0 += perLaunch) {
-        const int c1 = std::min(n, c0 + perLaunch);
-        int m = 0;
-        for (int i = c1 - 1; i >= c0; i--) {   // the last value of a repeated index wins (later launches land later)
-            if (seen[a[i]]) continue;
-            seen[a[i]] = 1;
-            stage[m++] = make_int2(a[i], ent ? vals[i] : ((flags[i] & ORBU_KF_BAD) | ORBU_KF_SET));
-        }
-        for (int i = c0; i < c1; i++) seen[a[i]] = 0;
+    auto emit = [=](int i, int m) { stage[m] = make_int2(a[i], ent ? vals[i] : ((flags[i] & ORBU_KF_BAD) | ORBU_KF_SET)); };   // (by value, as orbw_pool_write's)
+    auto flush = [=](int m) -> int {
         hipLaunchKernelGGL(orbu::k_pair_scatter, dim3((unsigned)((m + orbu::kThreads - 1) / orbu::kThreads)), dim3(orbu::kThreads), 0, s->pool->stream,
                            s->dev, (const int2*)stage, m, ent ? slot : 0, ent ? 0 : 1);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s->pool->stream));
-    }
-    return ORBX_OK;
+        return ORBX_OK;
+    };
+    return stage_last_wins(a, n, perLaunch, perLaunch, ent ? s->idxSeen : s->kfSeen, emit, flush);
 }
 
 extern "C" int orbu_kf_set_flags(orbu_store_t* store, const int32_t* slots, const uint8_t* flags, int n)
@@ -315,26 +235,14 @@ static int orbu_run(orbu_store* s, bool given, const int32_t* kf_list, int nkf, 
     std::lock_guard<std::mutex> l(p->mu);
     if (given && nkf > s->kfcap) return fail(ORBX_E_INVALID, "%d keyframes for a store of %d", nkf, s->kfcap);
     for (int i = 0; i < nkf; i++)
-        if (kf_list[i] < 0 || kf_list[i] >= s->kfcap) return fail(ORBX_E_INVALID, "kf_list[%d] = %d outside the store of %d", i, kf_list[i], s->kfcap);
-    for (int i = 0; i < n; i++) {
-        const int id = frame_ids[i];
-        if (id == -1) continue;
-        if (id < 0 || id >= p->cap) return fail(ORBX_E_INVALID, "frame_ids[%d] = %d outside the pool of %d", i, id, p->cap);
-        if (!p->isSet(id)) return fail(ORBX_E_INVALID, "frame_ids[%d] = %d was never set", i, id);
-    }
+        if ((rc = orbu_check_slot(s, "kf_list", i, kf_list[i], false))) return rc;
+    if ((rc = orbw_check_ids(p, "frame_ids", frame_ids, n, true))) return rc;
     Packer pk;
     const size_t oIds = pk.take((size_t)n * 4), oList = pk.take((size_t)nkf * 4);
-    if ((rc = grow_pinned(s->h_stage, s->stageCap, pk.off + 16, true, nullptr, &p->h->nHostAlloc))) return rc;
-    if ((rc = orbw_wait_readers(p))) return rc;   // a resident search in flight reads S
+    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, pk.off + 16))) return rc;   // (a resident search in flight reads S)
     s->updated = false; s->updates++;
     hipStream_t st = p->stream;
-    if (s->gen == 0xffffffffu) {   // the tag wraps: one clear, and the tags start over
-        HIPCHK(hipMemsetAsync(s->scr.stamp, 0, (size_t)p->cap * 8, st));
-        HIPCHK(hipMemsetAsync(s->scr.first, 0xff, (size_t)p->cap * 8, st));
-        if ((rc = orbn_clear_marks(s, st))) return rc;
-        s->gen = 0;
-    }
-    s->scr.gen = ++s->gen;
+    if ((rc = orbu_next_generation(s, st, &s->scr.gen))) return rc;
     if (n) memcpy(s->h_stage + oIds, frame_ids, (size_t)n * 4);
     if (nkf) memcpy(s->h_stage + oList, kf_list, (size_t)nkf * 4);
     const int32_t* ids = (const int32_t*)(s->h_stage + oIds);

@@ -1,7 +1,6 @@
 // orbw_host.inc -- host side of the map-point pool and of the two tracking searches that run from it (part of
 // orbslamm_hip.hip; kernels: orbw_kernels.hip, ABI: include/orbslamm_mappool.h, DESIGN.md §8q).
-//   the pool      four device arrays (68 bytes a slot), one "set" bit per slot on the host, a mutex, a stream of its own for
-//                 the setters, and one event per stream that has issued a search against it
+//   the pool      struct orbw_pool, its checks, the reader / writer steps and the last-wins staging: orbx_poolutil.inc
 //   the searches  orbm_track_local_points / orbm_track_frame_projected (orbt_host.inc: track_queries) with the query block
 //                 made by k_view_project instead of uploaded: the same result ring, the same two search launches
 
@@ -10,25 +9,6 @@ static_assert(sizeof(orbw::StagedPoint) == 80, "a staged record is five 16-byte 
 static_assert(ORBW_ST_BAD == orbw::ST_BAD && ORBW_ST_DEPTH == orbw::ST_DEPTH && ORBW_ST_OUT_OF_IMAGE == orbw::ST_OUT_OF_IMAGE &&
               ORBW_ST_DISTANCE == orbw::ST_DISTANCE && ORBW_ST_VIEW_ANGLE == orbw::ST_VIEW_ANGLE && ORBW_ST_LEVEL_RANGE == orbw::ST_LEVEL_RANGE &&
               ORBW_ST_IN_VIEW == orbw::ST_IN_VIEW && ORBW_ST_NO_POINT == orbw::ST_NO_POINT, "orbw status codes");
-
-constexpr int kPoolChunk = 1 << 16;   // records per setter launch: the pinned staging is 5 MB at the most
-
-static std::atomic<uint64_t> g_poolSerial{0};   // pools and the stores beside them: one number each, never given twice
-
-struct orbw_pool {
-    uint64_t serial = ++g_poolSerial;
-    orbm_handle* h = nullptr;   // device; a reference is held
-    int cap = 0;
-    uint8_t* d_block = nullptr;
-    orbw::PoolDev dev{};
-    std::vector<uint64_t> setBits, seen;   // seen: a setter's scratch, all zero between calls
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    uint8_t* h_stage = nullptr; size_t stageCap = 0;   // pinned and coherent: k_pool_scatter reads it where it lies
-    struct Reader { hipStream_t stream; hipEvent_t ev; };
-    std::vector<Reader> readers;   // per stream: behind the projection kernel of the last search issued on it
-    bool isSet(int id) const { return (setBits[(size_t)id >> 6] >> (id & 63)) & 1; }
-};
 
 extern "C" int orbw_pool_create(orbm_t* h, int capacity, orbw_pool_t** out)
 {
@@ -76,32 +56,6 @@ extern "C" int orbw_pool_destroy(orbw_pool_t* p)
     return ORBX_OK;
 }
 
-static int orbw_pool_check(orbw_pool* p)
-{
-    if (!p) return fail(ORBX_E_INVALID, "null pool");
-    if (!live_has(p)) return fail(ORBX_E_INVALID, "the pool was destroyed");
-    HIPCHK(hipSetDevice(p->h->device));
-    return ORBX_OK;
-}
-
-// (the pool's mutex is held) every search issued so far has read the pool
-static int orbw_wait_readers(orbw_pool* p)
-{
-    for (auto& r : p->readers) HIPCHK(hipEventSynchronize(r.ev));
-    return ORBX_OK;
-}
-
-// (the pool's mutex is held) stream `st` has just been given a kernel that reads the pool
-static int orbw_mark_reader(orbw_pool* p, hipStream_t st)
-{
-    for (auto& r : p->readers) if (r.stream == st) { HIPCHK(hipEventRecord(r.ev, st)); return ORBX_OK; }
-    hipEvent_t ev = nullptr;
-    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    p->readers.push_back({st, ev});
-    HIPCHK(hipEventRecord(ev, st));
-    return ORBX_OK;
-}
-
 // both setters: pts != null writes whole records, else flags alone
 static int orbw_pool_write(orbw_pool* p, const int32_t* ids, const OrbwPoint* pts, const uint8_t* flags, int n)
 {
@@ -111,40 +65,30 @@ static int orbw_pool_write(orbw_pool* p, const int32_t* ids, const OrbwPoint* pt
     int rc = orbw_pool_check(p);
     if (rc) return rc;
     std::lock_guard<std::mutex> l(p->mu);
-    for (int i = 0; i < n; i++) {
-        if (ids[i] < 0 || ids[i] >= p->cap) return fail(ORBX_E_INVALID, "ids[%d] = %d outside the pool of %d", i, ids[i], p->cap);
-        if (!pts && !p->isSet(ids[i])) return fail(ORBX_E_INVALID, "ids[%d] = %d was never set", i, ids[i]);
-    }
+    if ((rc = orbw_check_ids(p, "ids", ids, n, false, !pts))) return rc;
     const size_t rec = pts ? sizeof(orbw::StagedPoint) : sizeof(uint2);
-    if ((rc = grow_pinned(p->h_stage, p->stageCap, (size_t)std::min(n, kPoolChunk) * rec, true, nullptr, &p->h->nHostAlloc))) return rc;
-    if ((rc = orbw_wait_readers(p))) return rc;
-    for (int c0 = 0; c0 < n; c0 += kPoolChunk) {
-        const int c1 = std::min(n, c0 + kPoolChunk);
-        // the last record of a repeated id wins: walk the chunk backwards, keep an id's first sighting (chunks follow each
-        // other on the stream, so a later chunk's record lands last as well)
-        int m = 0;
-        for (int i = c1 - 1; i >= c0; i--) {
-            const int id = ids[i];
-            uint64_t& w = p->seen[(size_t)id >> 6];
-            if ((w >> (id & 63)) & 1) continue;
-            w |= 1ull << (id & 63);
-            if (pts) {
-                orbw::StagedPoint& s = ((orbw::StagedPoint*)p->h_stage)[m];
-                const OrbwPoint& P = pts[i];
-                s.a = make_float4(P.pos[0], P.pos[1], P.pos[2], P.min_distance);
-                s.b = make_float4(P.normal[0], P.normal[1], P.normal[2], P.max_distance);
-                memcpy(&s.d0, P.desc, 16); memcpy(&s.d1, P.desc + 16, 16);
-                s.flags = P.flags; s.id = (uint32_t)id; s.pad[0] = s.pad[1] = 0;
-            } else
-                ((uint2*)p->h_stage)[m] = make_uint2((uint32_t)id, flags[i]);
-            m++;
-        }
-        for (int i = c0; i < c1; i++) p->seen[(size_t)ids[i] >> 6] = 0;
-        hipLaunchKernelGGL(orbw::k_pool_scatter, dim3((unsigned)((m + orbw::kThreads - 1) / orbw::kThreads)), dim3(orbw::kThreads), 0, p->stream,
-                           p->dev, (const void*)p->h_stage, m, pts ? 0 : 1);
+    if ((rc = orbw_begin_write(p, p->h_stage, p->stageCap, (size_t)std::min(n, kPoolChunk) * rec))) return rc;
+    // (captured by value: the staged loop keeps the pointers in registers across its byte copies)
+    uint8_t* const stage = p->h_stage; const orbw::PoolDev dev = p->dev; hipStream_t const st = p->stream;
+    auto emit = [=](int i, int m) {
+        if (pts) {
+            orbw::StagedPoint& s = ((orbw::StagedPoint*)stage)[m];
+            const OrbwPoint& P = pts[i];
+            s.a = make_float4(P.pos[0], P.pos[1], P.pos[2], P.min_distance);
+            s.b = make_float4(P.normal[0], P.normal[1], P.normal[2], P.max_distance);
+            memcpy(&s.d0, P.desc, 16); memcpy(&s.d1, P.desc + 16, 16);
+            s.flags = P.flags; s.id = (uint32_t)ids[i]; s.pad[0] = s.pad[1] = 0;
+        } else
+            ((uint2*)stage)[m] = make_uint2((uint32_t)ids[i], flags[i]);
+    };
+    auto flush = [=](int m) -> int {
+        hipLaunchKernelGGL(orbw::k_pool_scatter, dim3((unsigned)((m + orbw::kThreads - 1) / orbw::kThreads)), dim3(orbw::kThreads), 0, st,
+                           dev, (const void*)stage, m, pts ? 0 : 1);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(p->stream));   // (the staging is the next chunk's; the call returns with the update complete)
-    }
+        HIPCHK(hipStreamSynchronize(st));
+        return ORBX_OK;
+    };
+    if ((rc = stage_last_wins(ids, n, kPoolChunk, kPoolChunk, p->seen, emit, flush))) return rc;
     if (pts) for (int i = 0; i < n; i++) p->setBits[(size_t)ids[i] >> 6] |= 1ull << (ids[i] & 63);
     return ORBX_OK;
 }
@@ -170,18 +114,6 @@ static int orbw_check_args(const OrbwView* view, const int32_t* ids, int nq, con
     if (!frame)
         for (int j = 0; j < nlevels; j++)
             if (!(level_breaks[j] < level_breaks[j + 1])) return fail(ORBX_E_INVALID, "the break table does not ascend strictly at %d", j);
-    return ORBX_OK;
-}
-
-// (the pool's mutex is held) every id is a set slot of the pool; the frame/frame list may hold -1
-static int orbw_check_ids(const orbw_pool* p, const int32_t* ids, int nq, bool frame)
-{
-    for (int i = 0; i < nq; i++) {
-        const int id = ids[i];
-        if (frame && id == -1) continue;
-        if (id < 0 || id >= p->cap) return fail(ORBX_E_INVALID, "ids[%d] = %d outside the pool of %d", i, id, p->cap);
-        if (!p->isSet(id)) return fail(ORBX_E_INVALID, "ids[%d] = %d was never set", i, id);
-    }
     return ORBX_OK;
 }
 
@@ -215,7 +147,7 @@ static int orbw_project_sync(orbm_handle* h, hipStream_t st, orbw_pool* pool, co
     uint8_t* d = slot_ptr<uint8_t>(h, S_BLOCK);
     memcpy(hs, ids, (size_t)nq * 4);
     std::lock_guard<std::mutex> l(pool->mu);
-    if ((rc = orbw_check_ids(pool, ids, nq, V.frame != 0))) return rc;
+    if ((rc = orbw_check_ids(pool, "ids", ids, nq, V.frame != 0))) return rc;
     orbw::ProjectArgs a{};
     a.pool = pool->dev; a.ids = (const int32_t*)(d + oIds); a.nq = nq; a.lastKeys = lastKeys; a.lastN = lastN;
     a.quvr = (float*)(d + oUvr); a.qlvl = (int8_t*)(d + oLvl); a.qdesc = nullptr; a.qvalid = d + oQv; a.qobs = d + oQo;
@@ -284,7 +216,7 @@ static int orbw_track(orbm_frameset_t* fs, int slot, int qslot, orbw_pool* pool,
         return fail(ORBX_E_UNSUPPORTED, "%d queries: the set's scratch holds slots x cap = %zu", nq, S * C);
     if (!devIds) {   // (set bits are never cleared: ids good now are good at the launch below)
         std::lock_guard<std::mutex> l(pool->mu);
-        if ((rc = orbw_check_ids(pool, ids, nq, frame))) return rc;
+        if ((rc = orbw_check_ids(pool, "ids", ids, nq, frame))) return rc;
     }
     const int set = fs->res.next();
     ResultRecord& r = fs->res.rec[set];

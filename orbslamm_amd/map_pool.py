@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import K4, OrbmProjParams, check, lib, ptr
+from ._solver import Handle
 
 MAX_CAPACITY = 1 << 22
 FLAG_BAD, FLAG_OBSERVED = 1, 2
@@ -71,8 +72,24 @@ def _ids(ids):
     return np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
 
 
-class MapPool:
+def _track_args(fs, view_rec, scale_factors, breaks, t_occ, mode, nnratio, check_ori, th_dist):
+    """what the track_* calls marshal alike: (the view record, the scale factors, the break table or None, OrbmProjParams, t_occ
+    padded to the frame set's cap or None)"""
+    sf = np.ascontiguousarray(scale_factors, dtype=np.float32)
+    br = occ = None
+    if breaks is not None:
+        br = np.ascontiguousarray(breaks, dtype=np.float32)
+        assert br.shape[0] == sf.shape[0] + 1
+    if t_occ is not None:
+        occ = np.zeros(fs.cap, np.uint8)
+        occ[:len(t_occ)] = t_occ
+    pp = OrbmProjParams(int(mode), float(nnratio), int(bool(check_ori)), int(th_dist))
+    return np.ascontiguousarray(view_rec, dtype=VIEW_DTYPE), sf, br, pp, occ
+
+
+class MapPool(Handle):
     """`capacity` MapPoint slots in HBM on the matcher's device (orbw_pool_*)."""
+    _destroy = "orbw_pool_destroy"
 
     def __init__(self, matcher, capacity):
         self._L = lib()
@@ -81,17 +98,6 @@ class MapPool:
         self.capacity = int(capacity)
         self._h = C.c_void_p()
         check(self._L.orbw_pool_create(matcher._h, self.capacity, C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.orbw_pool_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set(self, ids, points):
         """orbw_pool_set: returns with the records in HBM; a repeated id takes the last record"""
@@ -125,24 +131,11 @@ class MapPool:
                                             ptr(uvr), ptr(lvl), ptr(cos), ptr(st)))
         return uvr, lvl, cos, st
 
-    @staticmethod
-    def _occ(fs, t_occ):
-        if t_occ is None:
-            return None
-        occ = np.zeros(fs.cap, np.uint8)
-        occ[:len(t_occ)] = t_occ
-        return occ
-
     def track_local_map(self, fs, slot, view_rec, ids, th, scale_factors, breaks, t_occ=None, th_dist=100, nnratio=0.8, mode=3):
         """orbw_track_local_map: SearchLocalPoints' search against the frame in `slot` of frame set fs; asynchronous, the table
         comes back through fs.results() as one pair (assign[t] = position in ids), the status bytes through track_status"""
         ids = _ids(ids)
-        sf = np.ascontiguousarray(scale_factors, dtype=np.float32)
-        br = np.ascontiguousarray(breaks, dtype=np.float32)
-        assert br.shape[0] == sf.shape[0] + 1
-        v = np.ascontiguousarray(view_rec, dtype=VIEW_DTYPE)
-        pp = OrbmProjParams(int(mode), float(nnratio), 0, int(th_dist))
-        occ = self._occ(fs, t_occ)
+        v, sf, br, pp, occ = _track_args(fs, view_rec, scale_factors, breaks, t_occ, mode, nnratio, 0, th_dist)
         check(self._L.orbw_track_local_map(fs._h, int(slot), self._h, C.byref(pp), ptr(v), ptr(ids), ids.shape[0], C.c_float(th), ptr(sf), ptr(br),
                                            sf.shape[0], ptr(occ)))
 
@@ -151,10 +144,7 @@ class MapPool:
         """orbw_track_frame_pose: SearchByProjection(CurrentFrame, LastFrame) with CurrentFrame's pose; last_ids[i] = the pool id
         of LastFrame feature i's MapPoint or -1"""
         ids = _ids(last_ids)
-        sf = np.ascontiguousarray(scale_factors, dtype=np.float32)
-        v = np.ascontiguousarray(view_rec, dtype=VIEW_DTYPE)
-        pp = OrbmProjParams(int(mode), float(nnratio), int(bool(check_ori)), int(th_dist))
-        occ = self._occ(fs, t_occ)
+        v, sf, _, pp, occ = _track_args(fs, view_rec, scale_factors, None, t_occ, mode, nnratio, check_ori, th_dist)
         check(self._L.orbw_track_frame_pose(fs._h, int(cur_slot), int(last_slot), self._h, C.byref(pp), ptr(v), ptr(ids), ids.shape[0],
                                             C.c_float(th), ptr(sf), ptr(occ)))
 
@@ -288,9 +278,10 @@ class LocalMap:
     votes = property(lambda self: self._arr("votes", self._r.votes, self._kfcap, C.c_int32, np.int32) if self._r.votes else None)
 
 
-class KeyFrameStore:
+class KeyFrameStore(Handle):
     """`kf_capacity` keyframes (match lists of `stride` pool ids, flags, covisibility / spanning-tree records) in HBM beside
     a MapPool (orbu_*)."""
+    _destroy = "orbu_store_destroy"
 
     def __init__(self, pool, kf_capacity, stride, max_children, max_local_points):
         self._L = lib()
@@ -299,17 +290,6 @@ class KeyFrameStore:
         self.kf_capacity, self.stride, self.max_children, self.max_local_points = int(kf_capacity), int(stride), int(max_children), int(max_local_points)
         self._h = C.c_void_p()
         check(self._L.orbu_store_create(pool._h, self.kf_capacity, self.stride, self.max_children, self.max_local_points, C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.orbu_store_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _records(self, slots, flags, entries, neigh, parent, children):
         slots = _ids(slots)
@@ -400,11 +380,6 @@ class KeyFrameStore:
     def track_local_map(self, fs, slot, view_rec, th, scale_factors, breaks, t_occ=None, th_dist=100, nnratio=0.8, mode=3):
         """orbw_track_local_map_resident: MapPool.track_local_map with ids = the S of this store's last update, read where it
         lies; assign[t] = position in S"""
-        sf = np.ascontiguousarray(scale_factors, dtype=np.float32)
-        br = np.ascontiguousarray(breaks, dtype=np.float32)
-        assert br.shape[0] == sf.shape[0] + 1
-        v = np.ascontiguousarray(view_rec, dtype=VIEW_DTYPE)
-        pp = OrbmProjParams(int(mode), float(nnratio), 0, int(th_dist))
-        occ = MapPool._occ(fs, t_occ)
+        v, sf, br, pp, occ = _track_args(fs, view_rec, scale_factors, breaks, t_occ, mode, nnratio, 0, th_dist)
         check(self._L.orbw_track_local_map_resident(fs._h, int(slot), self._pool._h, self._h, C.byref(pp), ptr(v), C.c_float(th), ptr(sf), ptr(br),
                                                     sf.shape[0], ptr(occ)))

@@ -8,6 +8,7 @@ back: which of the set's last searches to merge, as fs.results(back) counts them
 mvpMapPoints[t] before that search (-1 = NULL; None = all NULL); discard: 1 for TrackWithMotionModel's loop, 0 for TrackLocalMap's.
 Each result is a dict: Tcw (what SetPose gets), ids (mvpMapPoints as pool ids after the loop), outlier (mvbOutlier as
 PoseOptimization left it), n_matches, n_matches_map, n_good, n_initial, rounds, iterations, trials, lambda_, chi2."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -49,22 +50,47 @@ def pack_jobs(jobs):
     return rec, keep
 
 
+def _table(arrays):
+    """the pointer table of per-job arrays (None: a null inside it)"""
+    return (C.c_void_p * max(len(arrays), 1))(*[None if a is None else a.ctypes.data for a in arrays])
+
+
+def _cut(arrays, ns):
+    return [None if a is None else a[:n] for a, n in zip(arrays, ns)]
+
+
+_Raw = collections.namedtuple("_Raw", "n_jobs nlevels sigma out ns ids flags")
+
+
+def _raw_arrays(jobs, inv_level_sigma2, nlevels, n_jobs, fill, result_dtype):
+    """what both *_raw calls build alike: n_jobs and nlevels as the C entry gets them, the sigma table, one result record per job the
+    array holds (`out`), its n per job (`ns`) and the per-job output arrays `ids` and `flags`, which hold `fill` (ids: -2, outlier: 0
+    without one) and at least one element"""
+    real = 0 if jobs is None else jobs.shape[0]
+    sig = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, dtype=np.float32)
+    ns = [max(int(jobs["n"][i]), 0) for i in range(real)]
+    return _Raw(n_jobs=real if n_jobs is None else int(n_jobs), nlevels=(0 if sig is None else sig.shape[0]) if nlevels is None else int(nlevels),
+                sigma=sig, out=np.zeros(max(real, 1), dtype=result_dtype), ns=ns,
+                ids=[np.full(max(n, 1), -2 if fill is None else fill, np.int32) for n in ns],
+                flags=[np.full(max(n, 1), 0 if fill is None else fill, np.uint8) for n in ns])
+
+
+def _track_fields(t, ids, flags, i):
+    """the fields of a result dict that both entries fill from a TRACK_RESULT_DTYPE record"""
+    o = t["opt"]
+    return dict(Tcw=o["Tcw"][i].reshape(4, 4).copy(), ids=ids[i], outlier=flags[i].astype(bool), n_matches=int(t["n_matches"][i]),
+                n_matches_map=int(t["n_matches_map"][i]), n_good=int(o["n_good"][i]), n_initial=int(o["n_initial"][i]), rounds=int(o["rounds"][i]),
+                iterations=o["iterations"][i].copy(), trials=o["trials"][i].copy(), lambda_=o["lambda_"][i].copy(), chi2=o["chi2"][i].copy())
+
+
 def track_pose_raw(handle, pool_handle, jobs, inv_level_sigma2, nlevels=None, n_jobs=None, fill=None):
     """the C entry as it is: jobs a JOB_DTYPE array (or None).  Returns (rc, results, [ids per job], [outlier per job]); no exception
     on a refusal.  fill: the byte the output arrays hold before the call (to see that a refusal leaves them alone)"""
     L = lib()
     _setup(L)
-    nj = (0 if jobs is None else jobs.shape[0]) if n_jobs is None else int(n_jobs)
-    real = 0 if jobs is None else jobs.shape[0]
-    sig = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, dtype=np.float32)
-    nl = (0 if sig is None else sig.shape[0]) if nlevels is None else int(nlevels)
-    out = np.zeros(max(real, 1), dtype=TRACK_RESULT_DTYPE)
-    ids = [np.full(max(int(jobs["n"][i]), 1), -2 if fill is None else fill, np.int32) for i in range(real)]
-    flags = [np.full(max(int(jobs["n"][i]), 1), 0 if fill is None else fill, np.uint8) for i in range(real)]
-    pi = (C.c_void_p * max(real, 1))(*[a.ctypes.data for a in ids])
-    pf = (C.c_void_p * max(real, 1))(*[a.ctypes.data for a in flags])
-    rc = L.orbq_track_pose(handle, pool_handle, ptr(jobs), nj, ptr(sig), nl, ptr(out), pi, pf)
-    return rc, out[:real], [a[:max(int(jobs["n"][i]), 0)] for i, a in enumerate(ids)], [a[:max(int(jobs["n"][i]), 0)] for i, a in enumerate(flags)]
+    a = _raw_arrays(jobs, inv_level_sigma2, nlevels, n_jobs, fill, TRACK_RESULT_DTYPE)
+    rc = L.orbq_track_pose(handle, pool_handle, ptr(jobs), a.n_jobs, ptr(a.sigma), a.nlevels, ptr(a.out), _table(a.ids), _table(a.flags))
+    return rc, a.out[:len(a.ns)], _cut(a.ids, a.ns), _cut(a.flags, a.ns)
 
 
 def track_pose(matcher, pool, jobs, inv_level_sigma2):
@@ -72,11 +98,7 @@ def track_pose(matcher, pool, jobs, inv_level_sigma2):
     rec, keep = pack_jobs(jobs)
     rc, out, ids, flags = track_pose_raw(matcher._h, pool._h, rec, inv_level_sigma2)
     check(rc)
-    o = out["opt"]
-    return [dict(Tcw=o["Tcw"][i].reshape(4, 4).copy(), ids=ids[i], outlier=flags[i].astype(bool), n_matches=int(out["n_matches"][i]),
-                 n_matches_map=int(out["n_matches_map"][i]), n_good=int(o["n_good"][i]), n_initial=int(o["n_initial"][i]), rounds=int(o["rounds"][i]),
-                 iterations=o["iterations"][i].copy(), trials=o["trials"][i].copy(), lambda_=o["lambda_"][i].copy(), chi2=o["chi2"][i].copy())
-            for i in range(len(jobs))]
+    return [_track_fields(out, ids, flags, i) for i in range(len(jobs))]
 
 
 # ------------------------------------------------------------------ orbq_track_reference
@@ -114,23 +136,13 @@ def track_reference_raw(handle, pool_handle, store_handle, jobs, nnratio, check_
     null match_out) or one bool per job (nulls inside it)"""
     L = lib()
     _setup_ref(L)
-    nj = (0 if jobs is None else jobs.shape[0]) if n_jobs is None else int(n_jobs)
-    real = 0 if jobs is None else jobs.shape[0]
-    sig = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, dtype=np.float32)
-    nl = (0 if sig is None else sig.shape[0]) if nlevels is None else int(nlevels)
-    out = np.zeros(max(real, 1), dtype=REF_RESULT_DTYPE)
-    ns = [max(int(jobs["n"][i]), 0) for i in range(real)]
-    ids = [np.full(max(n, 1), -2 if fill is None else fill, np.int32) for n in ns]
-    flags = [np.full(max(n, 1), 0 if fill is None else fill, np.uint8) for n in ns]
-    per = [bool(want_match)] * real if isinstance(want_match, bool) else [bool(w) for w in want_match]
-    match = [np.full(max(n, 1), -2 if fill is None else fill, np.int32) if per[i] else None for i, n in enumerate(ns)]
-    pi = (C.c_void_p * max(real, 1))(*[a.ctypes.data for a in ids])
-    pf = (C.c_void_p * max(real, 1))(*[a.ctypes.data for a in flags])
-    pm = (C.c_void_p * max(real, 1))(*[None if a is None else a.ctypes.data for a in match]) if any(per) or not isinstance(want_match, bool) else None
-    rc = L.orbq_track_reference(handle, pool_handle, store_handle, ptr(jobs), nj, float(nnratio), int(bool(check_ori)), int(min_matches), ptr(sig), nl,
-                                ptr(out), pi, pf, pm)
-    return (rc, out[:real], [a[:ns[i]] for i, a in enumerate(ids)], [a[:ns[i]] for i, a in enumerate(flags)],
-            [None if a is None else a[:ns[i]] for i, a in enumerate(match)])
+    a = _raw_arrays(jobs, inv_level_sigma2, nlevels, n_jobs, fill, REF_RESULT_DTYPE)
+    per = [bool(want_match)] * len(a.ns) if isinstance(want_match, bool) else [bool(w) for w in want_match]
+    match = [np.full(max(n, 1), -2 if fill is None else fill, np.int32) if per[i] else None for i, n in enumerate(a.ns)]
+    pm = _table(match) if any(per) or not isinstance(want_match, bool) else None
+    rc = L.orbq_track_reference(handle, pool_handle, store_handle, ptr(jobs), a.n_jobs, float(nnratio), int(bool(check_ori)), int(min_matches),
+                                ptr(a.sigma), a.nlevels, ptr(a.out), _table(a.ids), _table(a.flags), pm)
+    return rc, a.out[:len(a.ns)], _cut(a.ids, a.ns), _cut(a.flags, a.ns), _cut(match, a.ns)
 
 
 def track_reference(matcher, pool, store, jobs, inv_level_sigma2, nnratio=0.7, check_ori=True, min_matches=15, want_match=True):
@@ -141,10 +153,4 @@ def track_reference(matcher, pool, store, jobs, inv_level_sigma2, nnratio=0.7, c
     rec = pack_ref_jobs(jobs)
     rc, out, ids, flags, match = track_reference_raw(matcher._h, pool._h, store._h, rec, nnratio, check_ori, min_matches, inv_level_sigma2, want_match=want_match)
     check(rc)
-    t = out["track"]
-    o = t["opt"]
-    return [dict(status=int(out["status"][i]), n_bow=int(out["n_bow"][i]), match=match[i], Tcw=o["Tcw"][i].reshape(4, 4).copy(), ids=ids[i],
-                 outlier=flags[i].astype(bool), n_matches=int(t["n_matches"][i]), n_matches_map=int(t["n_matches_map"][i]), n_good=int(o["n_good"][i]),
-                 n_initial=int(o["n_initial"][i]), rounds=int(o["rounds"][i]), iterations=o["iterations"][i].copy(), trials=o["trials"][i].copy(),
-                 lambda_=o["lambda_"][i].copy(), chi2=o["chi2"][i].copy())
-            for i in range(len(jobs))]
+    return [dict(_track_fields(out["track"], ids, flags, i), status=int(out["status"][i]), n_bow=int(out["n_bow"][i]), match=match[i]) for i in range(len(jobs))]

@@ -280,6 +280,45 @@ def test_pool_semantics(rig):
     pool.close()
 
 
+def last_of_each(keys):
+    """the index of the last record of every key: the records that win a setter call"""
+    keys = np.asarray(keys)
+    return np.array([np.flatnonzero(keys == k)[-1] for k in np.unique(keys)])
+
+
+def test_a_repeated_id_on_both_sides_of_a_staging_chunk(rig):
+    """one orbw_pool_set and one orbw_pool_set_flags of 65 536 + 4 records (a setter launch stages 65 536) whose ids cycle over a
+    pool of 8: ids 0 .. 3 repeat behind the chunk's end.  A fresh pool given the eight last records alone projects to the same bytes"""
+    n = (1 << 16) + 4
+    i = np.arange(n)
+    ids = (i % 8).astype(np.int32)
+    view = lc.make_view()
+    K = lc.K_A.astype(np.float64)
+    z = np.where(i % 3 == 0, -1.0, 2.0 + (i % 5) * 0.25)
+    Xc = np.stack([(20 + i * 37 % 600 - K[2]) / K[0] * z, (20 + i * 53 % 440 - K[3]) / K[1] * z, z], axis=1)
+    dist = np.linalg.norm(Xc, axis=1)
+    desc = ((i[:, None] * (np.arange(32) + 1) >> 3) & 255).astype(np.uint8)
+    pts = np.zeros(n, lc.POINT_DTYPE)
+    pts["pos"], pts["normal"], pts["desc"], pts["flags"] = Xc, Xc / dist[:, None], desc, lc.FLAG_OBSERVED
+    pts["max_distance"] = dist * 1.5
+    pts["min_distance"] = pts["max_distance"] / lc.SF[-1]
+    fl = np.where(i % 5 == 0, lc.FLAG_BAD, lc.FLAG_OBSERVED * (i % 2)).astype(np.uint8)
+    win = last_of_each(ids)
+    assert (win >= 1 << 16).sum() == 4 and (win < 1 << 16).sum() == 4            # winners in the second launch and in the first
+    x, y = new_pool(rig, 8), new_pool(rig, 8)
+    x.set(ids, pts)
+    x.set_flags(ids, fl)
+    y.set(ids[win], pts[win])
+    y.set_flags(ids[win], fl[win])
+    q = np.arange(8, dtype=np.int32)
+    gx, gy = x.view_project(view, q, 3.0, rig.sf, rig.breaks), y.view_project(view, q, 3.0, rig.sf, rig.breaks)
+    for a, b, name in zip(gx, gy, ("uvr", "lvl", "viewcos", "status")):
+        assert a.tobytes() == b.tobytes(), name
+    assert len(np.unique(gx[3])) >= 2, gx[3]
+    x.close()
+    y.close()
+
+
 def test_localmap_dropin_on_mock_tracking(gpu, tmp_path):
     """include/Tracking_hip.hpp (SearchLocalPointsT::Run) on mock frames and MapPoints (tests/cpp/localmap_dropin_gpu.cpp) against the
     serial reference loop over the same mocks"""

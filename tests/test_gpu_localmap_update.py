@@ -315,6 +315,72 @@ def test_set_update_set_entries_update(matcher):
     pool.close()
 
 
+def small_pool(matcher, n=8):
+    from orbslamm_amd import MapPool
+    from orbslamm_amd.map_pool import POINT_DTYPE
+    pool = MapPool(matcher, n)
+    pool.set(np.arange(n), np.zeros(n, POINT_DTYPE))
+    return pool
+
+
+def last_of_each(keys):
+    """the index of the last record of every key: the records that win a setter call"""
+    keys = np.asarray(keys)
+    return np.array([np.flatnonzero(keys == k)[-1] for k in np.unique(keys)])
+
+
+def test_a_repeated_index_on_both_sides_of_a_staging_launch_of_pairs(matcher):
+    """one orbu_kf_set_entries of 2^20 + 4 pairs (a setter launch stages 8 MB: 2^20 pairs) whose indices cycle over a stride of 8:
+    indices 0 .. 3 repeat behind the launch's end.  A fresh store given the eight last pairs alone answers with the same bytes"""
+    from orbslamm_amd import KeyFrameStore
+    n = (1 << 20) + 4
+    i = np.arange(n)
+    idx = (i % 8).astype(np.int32)
+    vals = ((i * 5 + i // 8) % 8).astype(np.int32)
+    vals[i % 11 == 0] |= uc.NO_VOTE
+    vals[i % 7 == 0] = -1
+    win = last_of_each(idx)
+    assert (win >= 1 << 20).sum() == 4 and (win < 1 << 20).sum() == 4
+    assert (vals[win[win >= 1 << 20]] != vals[win[win >= 1 << 20] - 8]).any()        # were the first launch to land last, it would show
+    pool = small_pool(matcher)
+    got = []
+    for whole in (True, False):
+        store = KeyFrameStore(pool, 1, 8, 0, 16)
+        store.set([0], [0], [np.full(8, 3, np.int32)], [[]], [-1], [[]])
+        store.set_entries(0, idx if whole else idx[win], vals if whole else vals[win])
+        r = store.local_points([0], [1, -1, 5])
+        got.append((r.L.tobytes(), r.seen.tobytes(), r.nL, r.nS, r.resident.tobytes()))
+        store.close()
+    assert got[0] == got[1] and got[0][2] > 0
+    pool.close()
+
+
+def test_a_repeated_slot_on_both_sides_of_a_staging_launch_of_records(matcher):
+    """one orbu_kf_set of 104 857 + 3 records (80 bytes each at stride 4 without children: 104 857 fill a launch's 8 MB) whose slots
+    cycle over a store of 8.  A fresh store given the eight last records alone answers an update with the same bytes"""
+    from orbslamm_amd import KeyFrameStore
+    per = (8 << 20) // 80
+    n = per + 3
+    i = np.arange(n)
+    slots = (i % 8).astype(np.int32)
+    flags = np.where(i % 9 == 0, uc.KF_BAD, 0).astype(np.uint8)
+    ent = np.where((i[:, None] + np.arange(4)) % 5 == 0, -1, (i[:, None] + 3 * np.arange(4)) % 8).astype(np.int32)
+    neigh = ((i + 1) % 8).astype(np.int32).reshape(-1, 1)
+    parent = np.full(n, -1, np.int32)
+    win = last_of_each(slots)
+    assert per == 104857 and (win >= per).any() and (win < per).any()
+    pool = small_pool(matcher)
+    got = []
+    for w in (i, win):
+        store = KeyFrameStore(pool, 8, 4, 0, 16)
+        store.set(slots[w], flags[w], list(ent[w]), list(neigh[w]), parent[w], [()] * len(w))
+        r = store.update([0, 1, -1, 2, 5, 7])
+        got.append((r.status, r.kf.tobytes(), r.L.tobytes(), r.seen.tobytes(), r.votes.tobytes()))
+        store.close()
+    assert got[0] == got[1] and got[0][0] == 0 and len(got[0][1]) > 4
+    pool.close()
+
+
 def test_pool_ids_that_were_never_set_are_refused(matcher):
     from orbslamm_amd import KeyFrameStore, MapPool, OrbError
     from orbslamm_amd.map_pool import POINT_DTYPE

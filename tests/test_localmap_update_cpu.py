@@ -226,3 +226,18 @@ def test_refusals_that_need_no_gpu():
     assert b"ascend" in L.orbx_last_error()
     assert res_track(None, 0, None, None, C.byref(pp), ptr(view), f, ptr(lc.SF), ptr(br), lc.NLEVELS, None) == ORBX_E_INVALID
     assert b"null store" in L.orbx_last_error()
+
+
+def test_last_wins_staging_on_the_host_under_the_sanitizers(tmp_path):
+    """stage_last_wins (orbslamm_amd/csrc/orbx_lastwins.hpp, under the three setters) with in-memory emit and flush, built with
+    -fsanitize=address,undefined (tests/cpp/lastwins_host.cpp): window == launch and one window with more survivors than a launch
+    (the flush inside a window), held to the last record of every key; a failing flush leaves the scratch zero"""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "lastwins_host")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror",
+                           os.path.join(root, "tests", "cpp", "lastwins_host.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "lastwins ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    assert "Sanitizer" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-4000:]
