@@ -212,4 +212,134 @@ private:
     static void check(int rc) { detail::check(rc, "orbslamm_hip: "); }
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+//   ComputeSim3T<KeyFrame, MapPoint, Sim3>::RunAll(h, pool, store, jobs, idOf)
+//       what LoopClosing::ComputeSim3 (src/LoopClosing.cc:316-331) and MultiMapper::Run do per candidate behind Sim3Solver::iterate --
+//       matcher.SearchBySim3(pKF1, pKF2, vpMapPointMatches, s, R, t, 7.5) and Optimizer::OptimizeSim3(pKF1, pKF2, vpMapPointMatches,
+//       gScm, 10, mbFixScale) -- for a list of candidates in ONE device call (orby_compute_sim3, include/orbslamm_computesim3.h,
+//       DESIGN.md section 8v).  The caller has both keyframes of a job in two slots of one frame set, their match lists in the keyframe
+//       store (UpdateLocalMapT::SyncKeyFrame) and their points in the pool; idOf(MapPoint*) is a point's pool id.  Per job RunAll builds
+//       m12_id / m12_idx2 from vpMapPointMatches as it enters (the solver's inliers, :319-324: the pool id and
+//       GetIndexInKeyFrame(pKF2)), and writes back vpMapPointMatches, gScm (only when the reference writes it: not on the early return
+//       of Optimizer.cc:1514) and nInliers as if SearchBySim3 followed by OptimizeSim3T::Run had run on that job alone.  The caller
+//       walks the results in the reference's candidate order and stops at the first with nInliers >= 20 (:333); the jobs behind the
+//       accepted one have run, which the reference does not do -- their outputs are simply not read (OptimizeSim3T::RunAll's note).
+//       All pKF1 of a call share one set of level tables and all pKF2 another.  Monocular: a keyframe with a stereo observation is
+//       refused.  Nothing is written before the device call returns: a refusal throws with everything as it came.
+//       PRECONDITION (orbslamm_computesim3.h): a point that votes at slot q of a keyframe's store row has GetIndexInKeyFrame == q.
+template <class KeyFrame, class MapPoint, class Sim3>
+class ComputeSim3T {
+public:
+    struct Job {
+        orbm_frameset_t* fs; int slot1, slot2;   // the two keyframes as slots of one resident frame set
+        int kf1, kf2;                            // ... and as slots of the keyframe store
+        KeyFrame* pKF1;                          // mpCurrentKF
+        KeyFrame* pKF2;                          // the candidate
+        std::vector<MapPoint*>* vpMapPointMatches;
+        float R12[9], t12[3], s12;               // pSolver->GetEstimatedRotation / Translation / Scale (setSim3)
+        Sim3* gScm;                              // g2o::Sim3(toMatrix3d(R), toVector3d(t), s), :329
+        bool bFixScale;
+        float th, th2;                           // 7.5 and 10 in both callers
+        template <class Mat> void setSim3(const Mat& R, const Mat& t, float s)
+        {
+            for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R12[3 * r + c] = R.template at<float>(r, c); t12[r] = t.template at<float>(r, 0); }
+            s12 = s;
+        }
+    };
+    struct Result { int nFound; int nInliers; OrbzResult opt; };
+
+    template <class IdOf>
+    static std::vector<Result> RunAll(orbm_t* h, orbw_pool_t* pool, orbu_store_t* store, const std::vector<Job>& jobs, IdOf idOf,
+                                      orbl_predict_fn predict = nullptr)
+    {
+        const char* who = "ComputeSim3(HIP): ";
+        const int nj = (int)jobs.size();
+        std::vector<Result> ret(jobs.size());
+        if (!nj) return ret;
+        KeyFrame* first1 = jobs[0].pKF1;
+        KeyFrame* first2 = jobs[0].pKF2;
+        const int nlevels = (int)first1->mvScaleFactors.size();
+        if ((int)first2->mvScaleFactors.size() != nlevels) throw std::runtime_error(std::string(who) + "the two keyframes' level tables differ in length");
+        std::vector<float> breaks1((size_t)nlevels + 1), breaks2((size_t)nlevels + 1);
+        detail::check(orbl_level_breaks(first1->mfLogScaleFactor, nlevels, predict, breaks1.data()), who);
+        detail::check(orbl_level_breaks(first2->mfLogScaleFactor, nlevels, predict, breaks2.data()), who);
+        std::vector<OrbyJob> rec((size_t)nj);
+        std::vector<std::vector<int32_t> > id((size_t)nj), idx2((size_t)nj), matchOut((size_t)nj), idsOut((size_t)nj);
+        std::vector<int32_t*> pMatch((size_t)nj), pIds((size_t)nj);
+        for (int k = 0; k < nj; k++) {
+            const Job& J = jobs[k];
+            KeyFrame* pKF1 = J.pKF1;
+            KeyFrame* pKF2 = J.pKF2;
+            if (pKF1->mvScaleFactors != first1->mvScaleFactors || pKF2->mvScaleFactors != first2->mvScaleFactors ||
+                pKF1->mvInvLevelSigma2 != first1->mvInvLevelSigma2 || pKF2->mvInvLevelSigma2 != first2->mvInvLevelSigma2 ||
+                pKF1->mfLogScaleFactor != first1->mfLogScaleFactor || pKF2->mfLogScaleFactor != first2->mfLogScaleFactor)
+                throw std::runtime_error(std::string(who) + "the jobs of one call must share the two keyframes' level tables");
+            for (size_t i = 0; i < pKF1->mvuRight.size(); i++)
+                if (!(pKF1->mvuRight[i] < 0)) throw std::runtime_error(std::string(who) + "pKF1 holds a stereo observation (mvuRight >= 0); the device ComputeSim3 is monocular");
+            for (size_t i = 0; i < pKF2->mvuRight.size(); i++)
+                if (!(pKF2->mvuRight[i] < 0)) throw std::runtime_error(std::string(who) + "pKF2 holds a stereo observation (mvuRight >= 0); the device ComputeSim3 is monocular");
+            const std::vector<MapPoint*>& vp = *J.vpMapPointMatches;
+            const int N1 = (int)vp.size(), N2 = (int)pKF2->GetMapPointMatches().size();
+            OrbyJob& R = rec[(size_t)k];
+            R.fs = J.fs; R.slot1 = J.slot1; R.slot2 = J.slot2; R.kf1 = J.kf1; R.kf2 = J.kf2; R.n1 = N1; R.n2 = N2;
+            OrbzProblem& P = R.prob;
+            for (int c = 0; c < 4; c++) P.q[c] = J.gScm->rotation().coeffs()[c];
+            for (int c = 0; c < 3; c++) P.t[c] = J.gScm->translation()[c];
+            P.s = J.gScm->scale();
+            const auto R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation(), R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) { P.R1w[3 * r + c] = R1w.template at<float>(r, c); P.R2w[3 * r + c] = R2w.template at<float>(r, c); }
+                P.t1w[r] = t1w.template at<float>(r, 0); P.t2w[r] = t2w.template at<float>(r, 0);
+            }
+            P.K1[0] = pKF1->fx; P.K1[1] = pKF1->fy; P.K1[2] = pKF1->cx; P.K1[3] = pKF1->cy;
+            P.K2[0] = pKF2->fx; P.K2[1] = pKF2->fy; P.K2[2] = pKF2->cx; P.K2[3] = pKF2->cy;
+            P.th2 = J.th2;
+            P.fix_scale = J.bFixScale ? 1 : 0;
+            for (int c = 0; c < 9; c++) R.R12[c] = J.R12[c];
+            for (int c = 0; c < 3; c++) R.t12[c] = J.t12[c];
+            R.s12 = J.s12;
+            R.bounds1[0] = (float)pKF1->mnMinX; R.bounds1[1] = (float)pKF1->mnMaxX; R.bounds1[2] = (float)pKF1->mnMinY; R.bounds1[3] = (float)pKF1->mnMaxY;
+            R.bounds2[0] = (float)pKF2->mnMinX; R.bounds2[1] = (float)pKF2->mnMaxX; R.bounds2[2] = (float)pKF2->mnMinY; R.bounds2[3] = (float)pKF2->mnMaxY;
+            R.th = J.th;
+            // LoopClosing.cc:319-324 as it reaches SearchBySim3 (ORBmatcher.cc:1131-1144) and OptimizeSim3 (Optimizer.cc:1412)
+            id[(size_t)k].assign((size_t)N1 + 1, -1);
+            idx2[(size_t)k].assign((size_t)N1 + 1, -1);
+            for (int i = 0; i < N1; i++)
+                if (vp[(size_t)i]) { id[(size_t)k][(size_t)i] = (int32_t)idOf(vp[(size_t)i]); idx2[(size_t)k][(size_t)i] = (int32_t)vp[(size_t)i]->GetIndexInKeyFrame(pKF2); }
+            R.m12_id = id[(size_t)k].data(); R.m12_idx2 = idx2[(size_t)k].data();
+            matchOut[(size_t)k].assign((size_t)N1 + 1, -1); idsOut[(size_t)k].assign((size_t)N1 + 1, -1);
+            pMatch[(size_t)k] = matchOut[(size_t)k].data(); pIds[(size_t)k] = idsOut[(size_t)k].data();
+        }
+        std::vector<OrbyResult> out((size_t)nj);
+        detail::check(orby_compute_sim3(h, pool, store, rec.data(), nj, first1->mvScaleFactors.data(), first2->mvScaleFactors.data(), breaks1.data(),
+                                        breaks2.data(), first1->mvInvLevelSigma2.data(), first2->mvInvLevelSigma2.data(), nlevels, out.data(), pMatch.data(),
+                                        pIds.data(), nullptr, nullptr, nullptr),
+                      who);
+        // nothing of any job has been written up to here
+        for (int k = 0; k < nj; k++) {
+            const Job& J = jobs[k];
+            std::vector<MapPoint*>& vp = *J.vpMapPointMatches;
+            const std::vector<MapPoint*> vpMapPoints2 = J.pKF2->GetMapPointMatches();
+            for (size_t i = 0; i < vp.size(); i++) {
+                if (idsOut[(size_t)k][i] < 0) { vp[i] = static_cast<MapPoint*>(nullptr); continue; }   // no match, or nulled by a check (Optimizer.cc:1497, :1532)
+                if (vp[i]) continue;                                                                      // an entering match that stays
+                const int m = matchOut[(size_t)k][i];
+                if (m < 0 || m >= (int)vpMapPoints2.size() || !vpMapPoints2[(size_t)m])
+                    throw std::runtime_error(std::string(who) + "a new match names a feature of pKF2 without a MapPoint: the store is behind the keyframe");
+                vp[i] = vpMapPoints2[(size_t)m];   // ORBmatcher.cc:1318
+            }
+            const OrbzResult& o = out[(size_t)k].opt;
+            if (o.written) {   // Optimizer.cc:1541; not reached on the early return of :1514
+                auto r = J.gScm->rotation();
+                auto t = J.gScm->translation();
+                for (int c = 0; c < 4; c++) r.coeffs()[c] = o.q[c];
+                for (int c = 0; c < 3; c++) t[c] = o.t[c];
+                *J.gScm = Sim3(r, t, o.s);
+            }
+            ret[(size_t)k].nFound = out[(size_t)k].n_found; ret[(size_t)k].nInliers = o.n_in; ret[(size_t)k].opt = o;
+        }
+        return ret;
+    }
+};
+
 }  // namespace iORB_SLAM

@@ -4,6 +4,8 @@
 //   FuseTgt, FusePt, FST_*   a target keyframe and a map point as both kernels read them, and the status byte of a pair
 //   project_gates            the five projection gates and PredictScale of ONE (target, point) pair (ORBmatcher.cc:855-892
 //                            and :1010-1051: the same statements)
+//   sim3_gates               the gates of ONE point in one direction of SearchBySim3 (:1160-1191, :1240-1271; orby_kernels.hip)
+//   predict_level            PredictScale through the break table, under both gate sets
 //   window_best<Lpp>         the window walk of ONE survivor by Lpp lanes without the chi-square test (:1053-1081);
 //                            k_fuse_batch keeps its own walk with the test (:894-951), see there
 //   block_rank<Threads>      the rank of a flag inside a workgroup by ballot and wave counts
@@ -24,6 +26,17 @@ struct FuseTgt {
     int32_t n;
 };
 struct FusePt { float pos[3], normal[3], minDistance, maxDistance; uint32_t desc[8]; };       // OrblFusePoint
+
+// PredictScale (MapPoint.cc:385-394) through the break table: the breaks below ratio = maxDistance / dist3D (a NaN ratio is above
+// none).  True: the level lies inside [0, nlevels).
+__device__ __forceinline__ bool predict_level(float maxDistance, float dist3D, int nlevels, const float* breaks, int& level)
+{
+    const float ratio = __fdiv_rn(maxDistance, dist3D);
+    int c = 0;
+    for (int j = 0; j <= nlevels; j++) c += ratio > breaks[j] ? 1 : 0;
+    level = c - 1;
+    return c >= 1 && c <= nlevels;
+}
 
 // The projection gates of one pair.  True: the pair reaches the window search at (u, v) and `level`.  False: `st` names
 // the gate that ended it (u, v set once the depth gate is passed, level once PredictScale has run).
@@ -51,13 +64,34 @@ __device__ __forceinline__ bool project_gates(const FuseTgt& T, const FusePt& P,
     for (int i = 0; i < 3; i++) dt += (double)PO[i] * (double)P.normal[i];
     st = FST_VIEW_ANGLE;
     if (dt < 0.5 * (double)dist3D) return false;
-    // PredictScale: the breaks below ratio (a NaN ratio is above none)
-    const float ratio = __fdiv_rn(P.maxDistance, dist3D);
-    int c = 0;
-    for (int j = 0; j <= nlevels; j++) c += ratio > breaks[j] ? 1 : 0;
-    level = c - 1;
     st = FST_LEVEL_RANGE;
-    return c >= 1 && c <= nlevels;
+    return predict_level(P.maxDistance, dist3D, nlevels, breaks, level);
+}
+
+// The gates of one point in one direction of SearchBySim3 (ORBmatcher.cc:1160-1191 and :1240-1271: the same statements): X, the
+// point in the camera frame of the keyframe it comes FROM, moved by (sR, t) into the keyframe searched; K1 = pKF1's fx fy cx cy in
+// both directions (:1107-1110, sic); bounds = mnMinX, mnMaxX, mnMinY, mnMaxY of the keyframe searched (KeyFrame::IsInImage: >= min,
+// < max); minD, maxD the point's raw mfMinDistance, mfMaxDistance.  No viewing-angle gate.  `failed` counts the gates passed before
+// the one that ended it: 0 depth, 1 image, 2 distance, 3 level; true: (u, v) and level stand.
+__device__ __forceinline__ bool sim3_gates(const float* sR, const float* t, const float* X, const float* K1, const float* bounds, float minD,
+                                           float maxD, int nlevels, const float* breaks, float& u, float& v, int& level, int& failed)
+{
+    u = 0.f; v = 0.f; level = -1; failed = 0;
+    float pt[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) pt[i] = cvm::gemm3_elem(sR[3 * i], sR[3 * i + 1], sR[3 * i + 2], X[0], X[1], X[2], 1.0, t[i], 1.0);
+    if (pt[2] < 0.0f) return false;
+    const float invz = (float)(1.0 / (double)pt[2]);   // :1168
+    const float x = pt[0] * invz, y = pt[1] * invz;
+    u = K1[0] * x + K1[2]; v = K1[1] * y + K1[3];
+    failed = 1;
+    if (!(u >= bounds[0] && u < bounds[1] && v >= bounds[2] && v < bounds[3])) return false;
+    const float maxDistance = 1.2f * maxD, minDistance = 0.8f * minD;
+    const float dist3D = (float)cvm::norm3(pt);
+    failed = 2;
+    if (dist3D < minDistance || dist3D > maxDistance) return false;
+    failed = 3;
+    return predict_level(maxD, dist3D, nlevels, breaks, level);
 }
 
 // The window walk of one survivor in GetFeaturesInArea's order, levels pred - 1..pred, no chi-square test (:1053-1081).

@@ -56,6 +56,7 @@
 #include "orbu_kernels.hip"   // UpdateLocalMap: the keyframe vote, the local keyframe list, the local point list
 #include "orbn_kernels.hip"   // covisibility: UpdateConnections' counter and ordered list, KeyFrameCulling's counts, over the store
 #include "orbq_kernels.hip"   // PoseOptimization from the pool: merge, ordered edge list, orbo's solve, Tracking's loop behind it
+#include "orby_kernels.hip"   // ComputeSim3 behind the solver: SearchBySim3's two passes, the agreement, OptimizeSim3's walk, orbz's solve
 
 using namespace orbx;
 
@@ -218,3 +219,4 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbu_host.inc"   // the keyframe store beside the pool: UpdateLocalMap, and SearchLocalPoints from its resident list
 #include "orbn_host.inc"   // the covisibility entries over the store: batched UpdateConnections and KeyFrameCulling counts
 #include "orbq_host.inc"   // PoseOptimization behind the pool searches: TrackWithMotionModel's and TrackLocalMap's verdicts
+#include "orby_host.inc"   // SearchBySim3 and OptimizeSim3 from the pool, the store and the frame set: ComputeSim3's verdict per candidate

@@ -14,6 +14,8 @@
 // the edge record are orbg_kernels.hip's, shared with PoseOptimization.
 // Binary64 throughout, -ffp-contract=off, no atomics; every loop is bounded at compile time (2 passes, 5 / 10
 // iterations, 10 trials, kMaxEdgesPerLane edges).  A lane reads back only per-edge words that the same lane wrote.
+// The two passes, the checks and the result are a device function (solve_problem) so that k_compute_sim3 (orby_kernels.hip, DESIGN.md
+// §8v) runs them behind its own gather: the same bytes for the same correspondence list.
 #pragma once
 
 namespace orbz {
@@ -233,39 +235,19 @@ struct Problem {
     }
 };
 
-__global__ __launch_bounds__(kLanes) void k_sim3_optimize(Args a, int nProblems)
+// One problem from its estimate to its result (Optimizer.cc:1484-1541): the two optimize() passes, the two checks, the early return
+// of :1514 and the recovered Sim3.  The problem's n correspondences own the edges 2 c0 .. 2 (c0 + n) of a.pw / a.uv / a.off, filled
+// by the caller's gather (edge 2c: e12, edge 2c + 1: e21; nothing removed yet, a.removed zero) and made visible to the wave before
+// the call.  sRec: the records, [j][side] at (2 j + side) * 8, j = 0 the estimate, 1 + 2 d the +delta step of dimension d, 2 + 2 d
+// the -delta step; side 0 the Sim3 itself (e12 edges), side 1 its inverse (e21 edges).  The body of k_sim3_optimize, which is its
+// first caller; k_compute_sim3 (orby_kernels.hip) is the second.
+__device__ __forceinline__ void solve_problem(const Args& a, const OrbzProblem& P, double delta, int c0, int n, OrbzResult* out, double* sRec,
+                                              orbg::LmShared<7>& sLm, int lane)
 {
-    // the records: [j][side] at (2 j + side) * 8, j = 0 the estimate, 1 + 2 d the +delta step of dimension d, 2 + 2 d the -delta
-    // step; side 0 the Sim3 itself (e12 edges), side 1 its inverse (e21 edges)
-    __shared__ double sRec[kRecords * 8];
-    __shared__ orbg::LmShared<7> sLm;
-    const int pIdx = blockIdx.x, lane = threadIdx.x, side = lane & 1;
-    if (pIdx >= nProblems) return;
-    const ProblemIn& P = a.problems[pIdx];
-    const int c0 = P.c0, n = P.n, e0 = 2 * c0, nE = 2 * n;
-    OrbzResult* out = a.out + pIdx;
-    // the gather (Optimizer.cc:1401-1481): the observation, its level's information and the OTHER keyframe's point in ITS camera
-    // frame (R * Xw + t through gemm's small branch, as orbs_create takes it); nothing removed yet
-    for (int k = 0; k < kMaxEdgesPerLane; k++) {
-        const int e = lane + k * kLanes;
-        if (e >= nE) break;
-        const OrbzCorr c = a.corrs[c0 + (e >> 1)];
-        const float* R = side ? P.p.R1w : P.p.R2w;
-        const float* t = side ? P.p.t1w : P.p.t2w;
-        const float* Xw = side ? c.X1w : c.X2w;
-        const int oct = side ? c.oct2 : c.oct1;
-        float X[3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) X[r] = cvm::gemm3_elem(R[r * 3], R[r * 3 + 1], R[r * 3 + 2], Xw[0], Xw[1], Xw[2], 1.0, t[r], 1.0);
-        const bool okOct = oct >= 0 && oct < a.nlevels;   // (the host has refused anything else)
-        a.pw[e0 + e] = make_float4(X[0], X[1], X[2], okOct ? a.invSigma2[side * ORBX_MAX_LEVELS + oct] : 0.f);
-        a.uv[e0 + e] = side ? make_float2(c.obs2[0], c.obs2[1]) : make_float2(c.obs1[0], c.obs1[1]);
-        a.off[e0 + e] = 0;
-        if (!side) a.removed[c0 + (e >> 1)] = 0;
-    }
+    const int side = lane & 1, e0 = 2 * c0, nE = 2 * n;
     S3 est0;
-    est0.q.x = P.p.q[0]; est0.q.y = P.p.q[1]; est0.q.z = P.p.q[2]; est0.q.w = P.p.q[3];
-    est0.tx = P.p.t[0]; est0.ty = P.p.t[1]; est0.tz = P.p.t[2]; est0.s = P.p.s;
+    est0.q.x = P.q[0]; est0.q.y = P.q[1]; est0.q.z = P.q[2]; est0.q.w = P.q[3];
+    est0.tx = P.t[0]; est0.ty = P.t[1]; est0.tz = P.t[2]; est0.s = P.s;
     if (lane == 0) {
         out->q[0] = est0.q.x; out->q[1] = est0.q.y; out->q[2] = est0.q.z; out->q[3] = est0.q.w;
         out->t[0] = est0.tx; out->t[1] = est0.ty; out->t[2] = est0.tz; out->s = est0.s;
@@ -274,9 +256,9 @@ __global__ __launch_bounds__(kLanes) void k_sim3_optimize(Args a, int nProblems)
     }
     if (n == 0) return;   // no edge: no vertex is found, no iteration runs, and 0 - 0 < 10 (:1514)
 
-    const float* Kf = side ? P.p.K2 : P.p.K1;   // cam_map1 for e12, cam_map2 for e21
-    const double th2 = (double)P.p.th2;
-    Problem p = {a, e0, nE, lane, side, {(double)Kf[0], (double)Kf[1], (double)Kf[2], (double)Kf[3]}, P.p.fix_scale != 0, P.delta, P.delta * P.delta, sRec, est0, est0};
+    const float* Kf = side ? P.K2 : P.K1;   // cam_map1 for e12, cam_map2 for e21
+    const double th2 = (double)P.th2;
+    Problem p = {a, e0, nE, lane, side, {(double)Kf[0], (double)Kf[1], (double)Kf[2], (double)Kf[3]}, P.fix_scale != 0, delta, delta * delta, sRec, est0, est0};
     orbg::LmState<7> lm;   // lambda, growth, flatSteps and the solver's x: they live across the passes
     int nBad = 0, nIn = 0;
     const int kEdgeRounds = (nE + kLanes - 1) / kLanes;
@@ -328,6 +310,36 @@ __global__ __launch_bounds__(kLanes) void k_sim3_optimize(Args a, int nProblems)
         out->written = 1;
         out->n_in = nIn;
     }
+}
+
+__global__ __launch_bounds__(kLanes) void k_sim3_optimize(Args a, int nProblems)
+{
+    __shared__ double sRec[kRecords * 8];
+    __shared__ orbg::LmShared<7> sLm;
+    const int pIdx = blockIdx.x, lane = threadIdx.x, side = lane & 1;
+    if (pIdx >= nProblems) return;
+    const ProblemIn& P = a.problems[pIdx];
+    const int c0 = P.c0, n = P.n, e0 = 2 * c0, nE = 2 * n;
+    // the gather (Optimizer.cc:1401-1481): the observation, its level's information and the OTHER keyframe's point in ITS camera
+    // frame (R * Xw + t through gemm's small branch, as orbs_create takes it); nothing removed yet
+    for (int k = 0; k < kMaxEdgesPerLane; k++) {
+        const int e = lane + k * kLanes;
+        if (e >= nE) break;
+        const OrbzCorr c = a.corrs[c0 + (e >> 1)];
+        const float* R = side ? P.p.R1w : P.p.R2w;
+        const float* t = side ? P.p.t1w : P.p.t2w;
+        const float* Xw = side ? c.X1w : c.X2w;
+        const int oct = side ? c.oct2 : c.oct1;
+        float X[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) X[r] = cvm::gemm3_elem(R[r * 3], R[r * 3 + 1], R[r * 3 + 2], Xw[0], Xw[1], Xw[2], 1.0, t[r], 1.0);
+        const bool okOct = oct >= 0 && oct < a.nlevels;   // (the host has refused anything else)
+        a.pw[e0 + e] = make_float4(X[0], X[1], X[2], okOct ? a.invSigma2[side * ORBX_MAX_LEVELS + oct] : 0.f);
+        a.uv[e0 + e] = side ? make_float2(c.obs2[0], c.obs2[1]) : make_float2(c.obs1[0], c.obs1[1]);
+        a.off[e0 + e] = 0;
+        if (!side) a.removed[c0 + (e >> 1)] = 0;
+    }
+    solve_problem(a, P.p, P.delta, c0, n, a.out + pIdx, sRec, sLm, lane);
 }
 
 }  // namespace orbz
