@@ -278,8 +278,14 @@ def search_by_bow(qdesc, qangle, qvalid, qfv, tdesc, tangle, tvalid, tfv, nnrati
     return match[:(nt if out_by_train else nq)], n
 
 
+def _census(cnt):
+    return dict(zip(MATCH_BRANCHES, (int(c) for c in cnt)))
+
+
 def search_by_projection(mode, nnratio, check_ori, th_dist, q_uvr, q_lvl, qdesc, qangle, qvalid, q_obs_pos,
-                         gp, t_keys_un, start, idx, tdesc, t_occ, assign, L=None):
+                         gp, t_keys_un, start, idx, tdesc, t_occ, assign, L=None, q_ur=None, t_uright=None, census=False):
+    """q_ur / t_uright: the stereo gate of modes 3 and 4 (both None: mono).  census=True: a fourth item, dict of
+    MATCH_BRANCHES -> how often the branch was taken."""
     L = L or lib()
     pp = OrcProjParams(int(mode), float(nnratio), int(bool(check_ori)), int(th_dist))
     q_uvr = np.ascontiguousarray(q_uvr, dtype=np.float32)
@@ -292,14 +298,24 @@ def search_by_projection(mode, nnratio, check_ori, th_dist, q_uvr, q_lvl, qdesc,
     tdesc = np.ascontiguousarray(tdesc, dtype=np.uint8)
     t_occ = np.ascontiguousarray(t_occ, dtype=np.uint8).copy()
     assign = np.ascontiguousarray(assign, dtype=np.int32).copy()
-    n = L.orc_search_by_projection(C.byref(pp), _p(q_uvr), _p(q_lvl), _p(qdesc), _p(qangle), _p(qv), _p(qo),
-                                   q_uvr.shape[0], C.byref(gp), _p(t_keys_un), _p(start), _p(idx),
-                                   _p(tdesc), t_keys_un.shape[0], _p(t_occ), _p(assign))
-    return assign, t_occ, n
+    if q_ur is None and t_uright is None and not census:
+        n = L.orc_search_by_projection(C.byref(pp), _p(q_uvr), _p(q_lvl), _p(qdesc), _p(qangle), _p(qv), _p(qo),
+                                       q_uvr.shape[0], C.byref(gp), _p(t_keys_un), _p(start), _p(idx),
+                                       _p(tdesc), t_keys_un.shape[0], _p(t_occ), _p(assign))
+        return assign, t_occ, n
+    qur = None if q_ur is None else np.ascontiguousarray(q_ur, dtype=np.float32)
+    tur = None if t_uright is None else np.ascontiguousarray(t_uright, dtype=np.float32)
+    args = (C.byref(pp), _p(q_uvr), _p(qur), _p(q_lvl), _p(qdesc), _p(qangle), _p(qv), _p(qo), q_uvr.shape[0], C.byref(gp),
+            _p(t_keys_un), _p(start), _p(idx), _p(tdesc), _p(tur), t_keys_un.shape[0], _p(t_occ), _p(assign))
+    if not census:
+        return assign, t_occ, L.orc_search_by_projection_stereo(*args)
+    cnt = np.zeros(len(MATCH_BRANCHES), dtype=np.int32)
+    n = L.orc_search_by_projection_stereo_census(*args, _p(cnt))
+    return assign, t_occ, n, _census(cnt)
 
 
 def window_best(q_uvr, q_pred, qdesc, qvalid, gp, t_keys_un, start, idx, tdesc, inv_sigma2=None, chi2=False,
-                q_ur=None, t_uright=None, L=None):
+                q_ur=None, t_uright=None, L=None, census=False):
     L = L or lib()
     q_uvr = np.ascontiguousarray(q_uvr, dtype=np.float32)
     q_pred = np.ascontiguousarray(q_pred, dtype=np.int8)
@@ -313,12 +329,18 @@ def window_best(q_uvr, q_pred, qdesc, qvalid, gp, t_keys_un, start, idx, tdesc, 
     nq = q_uvr.shape[0]
     bi = np.full(max(nq, 1), -1, np.int32)
     bd = np.full(max(nq, 1), 256, np.int32)
-    L.orc_window_best(_p(q_uvr), _p(qur), _p(q_pred), _p(qdesc), _p(qv), nq, C.byref(gp), _p(t_keys_un), _p(start), _p(idx),
-                      _p(tdesc), _p(tur), t_keys_un.shape[0], _p(sig), int(bool(chi2)), _p(bi), _p(bd))
-    return bi[:nq], bd[:nq]
+    args = (_p(q_uvr), _p(qur), _p(q_pred), _p(qdesc), _p(qv), nq, C.byref(gp), _p(t_keys_un), _p(start), _p(idx),
+            _p(tdesc), _p(tur), t_keys_un.shape[0], _p(sig), int(bool(chi2)), _p(bi), _p(bd))
+    if not census:
+        L.orc_window_best(*args)
+        return bi[:nq], bd[:nq]
+    cnt = np.zeros(len(MATCH_BRANCHES), dtype=np.int32)
+    L.orc_window_best_census(*args, _p(cnt))
+    return bi[:nq], bd[:nq], _census(cnt)
 
 
-def search_for_initialization(q_xy, window, q_keys_un, qdesc, gp, t_keys_un, start, idx, tdesc, nnratio, check_ori, L=None):
+def search_for_initialization(q_xy, window, q_keys_un, qdesc, gp, t_keys_un, start, idx, tdesc, nnratio, check_ori, L=None,
+                              census=False):
     L = L or lib()
     q_xy = np.ascontiguousarray(q_xy, dtype=np.float32)
     q_keys_un = np.ascontiguousarray(q_keys_un, dtype=KP_DTYPE)
@@ -327,14 +349,17 @@ def search_for_initialization(q_xy, window, q_keys_un, qdesc, gp, t_keys_un, sta
     tdesc = np.ascontiguousarray(tdesc, dtype=np.uint8)
     nq = q_keys_un.shape[0]
     m12 = np.full(max(nq, 1), -1, np.int32)
-    n = L.orc_search_for_initialization(_p(q_xy), C.c_float(window), _p(q_keys_un), _p(qdesc), nq, C.byref(gp), _p(t_keys_un),
-                                        _p(start), _p(idx), _p(tdesc), t_keys_un.shape[0], C.c_float(nnratio),
-                                        int(bool(check_ori)), _p(m12))
-    return m12[:nq], n
+    args = (_p(q_xy), C.c_float(window), _p(q_keys_un), _p(qdesc), nq, C.byref(gp), _p(t_keys_un), _p(start), _p(idx), _p(tdesc),
+            t_keys_un.shape[0], C.c_float(nnratio), int(bool(check_ori)), _p(m12))
+    if not census:
+        return m12[:nq], L.orc_search_for_initialization(*args)
+    cnt = np.zeros(len(MATCH_BRANCHES), dtype=np.int32)
+    n = L.orc_search_for_initialization_census(*args, _p(cnt))
+    return m12[:nq], n, _census(cnt)
 
 
 def search_for_triangulation(k1, d1, skip1, fv1, k2, d2, skip2, fv2, F12, ex, ey, sf2, sigma2_2, only_stereo, check_ori,
-                             uright1=None, uright2=None, L=None):
+                             uright1=None, uright2=None, L=None, census=False):
     L = L or lib()
     k1 = np.ascontiguousarray(k1, dtype=KP_DTYPE)
     k2 = np.ascontiguousarray(k2, dtype=KP_DTYPE)
@@ -351,10 +376,13 @@ def search_for_triangulation(k1, d1, skip1, fv1, k2, d2, skip2, fv2, F12, ex, ey
     f2, keep2 = _featvec(*fv2)
     n1 = k1.shape[0]
     m12 = np.full(max(n1, 1), -1, np.int32)
-    n = L.orc_search_for_triangulation(_p(k1), _p(d1), _p(s1), _p(u1), n1, C.byref(f1), _p(k2), _p(d2), _p(s2), _p(u2),
-                                       k2.shape[0], C.byref(f2), _p(F), C.c_float(ex), C.c_float(ey), _p(sf2), _p(sg2),
-                                       int(bool(only_stereo)), int(bool(check_ori)), _p(m12))
-    return m12[:n1], n
+    args = (_p(k1), _p(d1), _p(s1), _p(u1), n1, C.byref(f1), _p(k2), _p(d2), _p(s2), _p(u2), k2.shape[0], C.byref(f2), _p(F),
+            C.c_float(ex), C.c_float(ey), _p(sf2), _p(sg2), int(bool(only_stereo)), int(bool(check_ori)), _p(m12))
+    if not census:
+        return m12[:n1], L.orc_search_for_triangulation(*args)
+    cnt = np.zeros(len(MATCH_BRANCHES), dtype=np.int32)
+    n = L.orc_search_for_triangulation_census(*args, _p(cnt))
+    return m12[:n1], n, _census(cnt)
 
 
 class Vocabulary:
@@ -432,6 +460,83 @@ STEREO_BRANCHES = ("row_outside",            # (int)vL not a row of the image
                    "minr_clipped",           # a right keypoint's row band cut at row 0
                    "maxr_clipped",           # ... at the last row
                    "accepted")               # matches before the median filter
+
+
+# the branches of orb_match.c's window searches, in the order of their census counters.  area_*: the candidate gathering
+# (Frame::GetFeaturesInArea) under whichever entry ran; proj_*: SearchByProjection modes 3 - 6; win_*: the windowed best of
+# Fuse / SearchBySim3; init_*: SearchForInitialization; tri_*: SearchForTriangulation
+MATCH_BRANCHES = ("area_min_x_beyond",        # the window lies wholly right of the grid (Frame.cc:340)
+                  "area_max_x_negative",      # ... wholly left of it (:344)
+                  "area_min_y_beyond",        # ... wholly below it (:348)
+                  "area_max_y_negative",      # ... wholly above it (:352)
+                  "area_cut_left", "area_cut_right", "area_cut_top", "area_cut_bottom",   # the window is cut by a border
+                  "area_no_level_check",      # minLevel <= 0 and maxLevel < 0: (-1,-1) and (0,-1) alike (:355)
+                  "area_level_below",         # per feature of a visited cell: octave < minLevel
+                  "area_level_above",         # ... octave > maxLevel >= 0
+                  "area_on_edge",             # ... |dx| == r or |dy| == r with the other axis within: excluded by the strict <
+                  "area_outside",             # ... beyond the window
+                  "area_inside",              # ... a candidate
+                  "area_empty_cell",          # per visited cell: no feature
+                  "area_cell_over_64",        # ... more than 64 features
+                  "proj_invalid",             # qvalid == 0
+                  "proj_no_candidate",        # empty window
+                  "proj_occupied",            # per candidate: the feature is taken (on entry or by an earlier query)
+                  "proj_stereo_beyond",       # ... |q_ur - mvuRight| > r (ORBmatcher.cc:91-96, :1409-1415)
+                  "proj_stereo_at_radius",    # ... == r: kept
+                  "proj_stereo_within",       # ... < r
+                  "proj_new_best", "proj_new_second",
+                  "proj_equal_best",          # ... at the best's distance: becomes the second, the first in scan order stays
+                  "proj_equal_second",        # ... at the second's distance: ignored
+                  "proj_best_at_th",          # best == th_dist: accepted by the <=
+                  "proj_best_above_th",       # best > th_dist
+                  "proj_none_free",           # candidates, all of them occupied, gated out or at 256
+                  "proj_single",              # accepted with no second (best2 = 256, bestLevel2 = -1)
+                  "proj_ratio_reject",        # mode 3: same level and best > nnratio * best2 (:120-121)
+                  "proj_ratio_equal",         # mode 3: same level and best == nnratio * best2 in binary32: accepted
+                  "proj_ratio_pass",          # mode 3: same level and best < nnratio * best2
+                  "proj_cross_level_pass",    # mode 3: best > nnratio * best2 on different levels: accepted
+                  "proj_accept",
+                  "proj_blocks",              # the accepted feature is occupied from now on
+                  "proj_leaves_free",         # modes 3 / 4, q_obs_pos == 0: it stays free
+                  "proj_retaken",             # accepted on a feature an earlier query of this call had taken: both are counted
+                  "proj_overwrites_entry",    # accepted on a feature whose assign entry was set on entry
+                  "proj_pruned",              # per push in a rotation bin that is not kept
+                  "proj_pruned_retaken",      # ... of a feature pushed more than once
+                  "win_invalid", "win_none",
+                  "win_level_below",          # per candidate: octave < pred - 1
+                  "win_level_above",          # ... octave > pred
+                  "win_mono_reject", "win_mono_pass",       # chi2: e2 * invSigma2 > 5.99 or not
+                  "win_stereo_reject", "win_stereo_pass",   # chi2 with mvuRight >= 0: > 7.8 or not
+                  "win_new_best",
+                  "win_equal_best",           # at the best's distance: the first in scan order stays
+                  "init_octave_skip",         # query octave > 0 (:421-422)
+                  "init_no_candidate",
+                  "init_held_better",         # per candidate: vMatchedDistance < dist (:441)
+                  "init_held_equal",          # ... == dist: skipped as well
+                  "init_new_best", "init_new_second",
+                  "init_equal_best",          # ... at the best's distance: becomes the second
+                  "init_best_at_th",          # bestDist == TH_LOW
+                  "init_best_above_th",
+                  "init_ratio_reject",        # bestDist > bestDist2 * nnratio
+                  "init_ratio_equal",         # == in binary32: rejected by the strict <
+                  "init_accept",
+                  "init_steal",               # the feature had an owner: revoked (:466-470)
+                  "init_pruned",              # per push outside the kept bins whose match still stands
+                  "init_prune_already_revoked",   # ... whose match a thief had revoked: no second decrement (:506-510)
+                  "tri_node_one_side",        # a node on one side only: lower_bound
+                  "tri_skip1", "tri_skip2",
+                  "tri_only_stereo_1", "tri_only_stereo_2",   # bOnlyStereo and no right coordinate (:702-704, :724-726)
+                  "tri_above_th",             # per candidate: dist > TH_LOW
+                  "tri_above_best",           # ... dist > bestDist
+                  "tri_equal_best",           # ... dist == bestDist of an earlier passing candidate: still examined
+                  "tri_no_epipole_test",      # ... either side stereo: the epipole test is not made
+                  "tri_epipole_near",         # ... inside 100 * scaleFactor of the epipole: skipped (:738-739)
+                  "tri_epipole_on",           # ... exactly on it: kept by the strict <
+                  "tri_den_zero",             # the epipolar line degenerates (:150-151)
+                  "tri_line_fail", "tri_line_pass",
+                  "tri_later_pass",           # a passing candidate replaces an earlier one
+                  "tri_equal_replaces",       # ... at an equal distance: the last of equals wins
+                  "tri_match", "tri_pruned")
 
 
 def compute_stereo_matches(keysL, descL, keysR, descR, levelsL, levelsR, scale, inv_scale, mb, mbf, L=None, census=False):

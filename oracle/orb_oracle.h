@@ -223,6 +223,39 @@ int  orc_search_for_triangulation(const OrcKeyPoint* k1, const uint8_t* d1, cons
                                   const float* sf2, const float* sigma2_2,
                                   int only_stereo, int check_ori, int32_t* matches12);
 
+/* The four window searches above with a census of their branches (the candidate gathering of orc_features_in_area
+ * counted inside them): census is NULL or ORC_MATCH_NBRANCH counters that are added to (binding.MATCH_BRANCHES names them
+ * in order).  The outputs do not depend on it; the plain entries are these with NULL. */
+#define ORC_MATCH_NBRANCH 84
+int  orc_search_by_projection_stereo_census(const OrcProjParams* pp,
+                              const float* q_uvr, const float* q_ur, const int8_t* q_lvl,
+                              const uint8_t* qdesc, const float* qangle,
+                              const uint8_t* qvalid, const uint8_t* q_obs_pos, int nq,
+                              const OrcGridParams* gp, const OrcKeyPoint* t_keys_un,
+                              const int32_t* cell_start, const int32_t* cell_idx,
+                              const uint8_t* tdesc, const float* t_uright, int nt,
+                              uint8_t* t_occ, int32_t* assign, int32_t* census);
+int  orc_window_best_census(const float* q_uvr, const float* q_ur, const int8_t* q_pred,
+                            const uint8_t* qdesc, const uint8_t* qvalid, int nq,
+                            const OrcGridParams* gp, const OrcKeyPoint* tk,
+                            const int32_t* cell_start, const int32_t* cell_idx,
+                            const uint8_t* tdesc, const float* t_uright, int nt,
+                            const float* inv_sigma2, int chi2,
+                            int32_t* best_idx, int32_t* best_dist, int32_t* census);
+int  orc_search_for_initialization_census(const float* q_xy, float window, const OrcKeyPoint* qk,
+                                          const uint8_t* qdesc, int nq,
+                                          const OrcGridParams* gp, const OrcKeyPoint* tk,
+                                          const int32_t* cell_start, const int32_t* cell_idx,
+                                          const uint8_t* tdesc, int nt,
+                                          float nnratio, int check_ori, int32_t* matches12, int32_t* census);
+int  orc_search_for_triangulation_census(const OrcKeyPoint* k1, const uint8_t* d1, const uint8_t* skip1,
+                                         const float* uright1, int n1, const OrcFeatVec* fv1,
+                                         const OrcKeyPoint* k2, const uint8_t* d2, const uint8_t* skip2,
+                                         const float* uright2, int n2, const OrcFeatVec* fv2,
+                                         const float F12[9], float ex, float ey,
+                                         const float* sf2, const float* sigma2_2,
+                                         int only_stereo, int check_ori, int32_t* matches12, int32_t* census);
+
 /* SURVEY.md 8(f) rank 1, last item: Frame::ComputeStereoMatches (src/Frame.cc:466-638), orb_stereo.c.
  * pyramids: per level a tight or strided 8-bit image (the un-blurred levels of ComputePyramid, no border needed:
  * the 11 x 21 search window stays inside the level for keypoints >= 16 px from its edge).

@@ -684,7 +684,7 @@ __device__ __forceinline__ void proj_resolve_rounds(const ProjPair& P, const Pro
             for (int u = 0; u < 2; u++) {
                 b1[u] = k1[u] == kFree ? 256 : k1[u] >> 22;
                 go[u] = und[u] && !(b1[u] > c.thDist || b1[u] >= 256);
-                has2[u] = go[u] && c.mode == 3 && k2[u] != kFree;
+                has2[u] = go[u] && c.mode == 3 && k2[u] != kFree && (k2[u] >> 22) < 256;   // (`dist < bestDist2` from 256, :110: a runner-up at 256 is none)
                 const int off = qoff[qq[u]];
                 e1[u] = go[u] ? entry(off + (k1[u] & 0x3FFFFF)).x : 0u;
                 e2[u] = has2[u] ? entry(off + (k2[u] & 0x3FFFFF)).x : 0u;

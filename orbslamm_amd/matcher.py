@@ -94,8 +94,9 @@ class ORBmatcher:
         return match[:nout], n.value
 
     def SearchByProjection(self, mode, th_dist, q_uvr, q_lvl, qdesc, qangle, qvalid, q_obs_pos,
-                           grid, t_keys_un, tdesc, t_occ, assign):
-        """The four SearchByProjection overloads, flattened (mode 3/4/5/6, see orbslamm_hip.h)."""
+                           grid, t_keys_un, tdesc, t_occ, assign, q_ur=None, t_uright=None):
+        """The four SearchByProjection overloads, flattened (mode 3/4/5/6, see orbslamm_hip.h).  q_ur / t_uright: the stereo
+        gate of modes 3 and 4 (orbm_search_by_projection_stereo); both None is the mono call."""
         pp = OrbmProjParams(int(mode), self.mfNNratio, int(self.mbCheckOrientation), int(th_dist))
         q_uvr = np.ascontiguousarray(q_uvr, dtype=np.float32)
         q_lvl = np.ascontiguousarray(q_lvl, dtype=np.int8)
@@ -108,9 +109,16 @@ class ORBmatcher:
         t_occ = np.ascontiguousarray(t_occ, dtype=np.uint8).copy()
         assign = np.ascontiguousarray(assign, dtype=np.int32).copy()
         n = C.c_int(0)
-        check(self._L.orbm_search_by_projection(self._h, C.byref(pp), ptr(q_uvr), ptr(q_lvl), ptr(qdesc), ptr(qangle),
-                                                ptr(qv), ptr(qo), q_uvr.shape[0], C.byref(grid), ptr(t_keys_un),
-                                                ptr(tdesc), t_keys_un.shape[0], ptr(t_occ), ptr(assign), C.byref(n)))
+        if q_ur is None and t_uright is None:
+            check(self._L.orbm_search_by_projection(self._h, C.byref(pp), ptr(q_uvr), ptr(q_lvl), ptr(qdesc), ptr(qangle),
+                                                    ptr(qv), ptr(qo), q_uvr.shape[0], C.byref(grid), ptr(t_keys_un),
+                                                    ptr(tdesc), t_keys_un.shape[0], ptr(t_occ), ptr(assign), C.byref(n)))
+            return assign, t_occ, n.value
+        qur = np.ascontiguousarray(q_ur, dtype=np.float32)
+        tur = np.ascontiguousarray(t_uright, dtype=np.float32)
+        check(self._L.orbm_search_by_projection_stereo(self._h, C.byref(pp), ptr(q_uvr), ptr(qur), ptr(q_lvl), ptr(qdesc), ptr(qangle),
+                                                       ptr(qv), ptr(qo), q_uvr.shape[0], C.byref(grid), ptr(t_keys_un),
+                                                       ptr(tdesc), ptr(tur), t_keys_un.shape[0], ptr(t_occ), ptr(assign), C.byref(n)))
         return assign, t_occ, n.value
 
     def ProjectionPrepare(self, grid, t_keys_un, tdesc):

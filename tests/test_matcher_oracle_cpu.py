@@ -147,3 +147,196 @@ def test_stereo_from_rgbd_semantics(oracle):
     want = [np.float32(4.0) - np.float32(40.0) / np.float32(38.0), np.float32(11.0) - np.float32(40.0) / np.float32(105.0), -1.0, -1.0,
             np.float32(8.5) - np.float32(40.0) / np.float32(142.0)]
     assert ur.tolist() == [float(np.float32(x)) for x in want]
+
+
+# ------------------------------------------------------------------ the designed window scenes (tests/window_cases.py)
+# Each scene family is built to take one branch of oracle/orb_match.c; the census says whether it does.  What is asserted here is a
+# condition on the scenes and the oracle alone: tests/test_gpu_window_rules.py sends the same scenes through the device entries.
+AREA = ("area_min_x_beyond", "area_max_x_negative", "area_min_y_beyond", "area_max_y_negative", "area_cut_left", "area_cut_right", "area_cut_top",
+        "area_cut_bottom", "area_on_edge", "area_outside", "area_inside", "area_empty_cell", "area_cell_over_64")
+
+
+def _need(cen, names, where):
+    missing = [n for n in names if cen[n] < 1]
+    assert not missing, (where, missing)
+
+
+def _same(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def _taken(c, assign, role):
+    """(train feature, distance) the query of that role holds in a by-train table, or None"""
+    q = c["roles"][role]
+    t = np.nonzero(assign == q)[0]
+    return (int(t[0]), int(np.unpackbits(c["qd"][q] ^ c["td"][t[0]]).sum())) if len(t) else None
+
+
+def test_match_branches_are_named_once(oracle):
+    assert len(oracle.MATCH_BRANCHES) == len(set(oracle.MATCH_BRANCHES)) == 84   # ORC_MATCH_NBRANCH
+
+
+def test_window_scenes_keep_their_groups_apart(oracle):
+    """the exact distances hold inside a group only: no window may hold a feature of another group"""
+    import window_cases as wc
+    scenes = [wc.proj_scene(oracle, r) for r in wc.PROJ_RUNS] + [wc.make_window_scene(oracle, True), wc.make_init_scene(oracle)]
+    for c in scenes:
+        assert c["nq"] <= 512 and c["nt"] <= 512
+        for q in range(c["nq"]):
+            got = oracle.features_in_area(c["gp"], c["tk"], c["start"], c["idx"], *c["uvr"][q], -1, -1)
+            assert (c["tg"][got] == c["qg"][q]).all(), q
+
+
+def test_projection_census_on_the_designed_scenes(oracle):
+    import window_cases as wc
+    for run in wc.PROJ_RUNS:
+        c = wc.proj_scene(oracle, run)
+        plain = wc.proj_oracle(oracle, c, run)
+        a, occ, n, cen = wc.proj_oracle(oracle, c, run, census=True)
+        assert _same(plain, (a, occ, n)), run                                   # the census changes nothing
+        mode, th = run["mode"], run["th"]
+        if run["ratio"] < 0.5:   # the run made for one family: at 0.2 the ratio rule rejects most of the others' matches
+            assert _taken(c, a, "second at 256")[1] == 60 and cen["proj_ratio_reject"] > 10
+            continue
+        _need(cen, AREA + ("area_no_level_check", "area_level_below", "area_level_above"), run)
+        _need(cen, ("proj_invalid", "proj_no_candidate", "proj_occupied", "proj_new_best", "proj_new_second", "proj_equal_best", "proj_equal_second",
+                    "proj_best_at_th", "proj_best_above_th", "proj_none_free", "proj_single", "proj_accept", "proj_blocks", "proj_overwrites_entry"), run)
+        if mode == 3:
+            _need(cen, ("proj_ratio_reject", "proj_ratio_pass", "proj_ratio_equal", "proj_cross_level_pass"), run)
+            # 30/40 at 0.75 is exact; 40/50 at 0.8f and 45/50 at 0.9f round to 40 and 45 in binary32: `>` does not reject
+            eq = {0.75: "ratio 30/40 same", 0.8: "ratio 40/50 same", 0.9: "ratio 45/50 same"}[run["ratio"]]
+            assert _taken(c, a, eq) is not None, run
+            assert _taken(c, a, "second at 256")[1] == min(th, 60), run
+            assert _taken(c, a, "tie same level") is None and _taken(c, a, "tie cross level") is not None
+        else:
+            # unreachable outside mode 3: the ratio rule is mode 3's alone (ORBmatcher.cc:120-121)
+            assert cen["proj_ratio_reject"] == cen["proj_ratio_pass"] == cen["proj_ratio_equal"] == cen["proj_cross_level_pass"] == 0
+            t = _taken(c, a, "tie same level")
+            assert t is not None and c["tk"]["x"][t[0]] < c["uvr"][c["roles"]["tie same level"], 0] and t[0] > 0   # first in cell order, not the lower index
+        if mode in (3, 4):
+            _need(cen, ("proj_leaves_free", "proj_retaken"), run)
+        else:
+            assert cen["proj_leaves_free"] == cen["proj_retaken"] == 0             # unreachable: modes 5 / 6 always block (:1557, :375)
+        if run["ori"] and mode in (4, 5):
+            _need(cen, ("proj_pruned",), run)
+            if mode == 4:
+                _need(cen, ("proj_pruned_retaken",), run)
+                assert n != (a >= 0).sum()                                          # a feature pushed twice is subtracted twice
+        else:
+            assert cen["proj_pruned"] == 0                                         # unreachable: no rotation check in modes 3 / 6 or without check_ori
+        if run["stereo"]:
+            _need(cen, ("proj_stereo_beyond", "proj_stereo_at_radius", "proj_stereo_within"), run)
+            assert _taken(c, a, "stereo at r")[1] == 10 and _taken(c, a, "stereo beyond r")[1] == 30
+            assert _taken(c, a, "stereo uright 0")[1] == 10 and _taken(c, a, "stereo uright -1")[1] == 10
+        # what the families say in words
+        for k in range(4):
+            assert _taken(c, a, "edge %d" % k)[1] == 10                             # neither the feature on the edge (5) nor the far one (40)
+        assert _taken(c, a, "dropped 0")[1] == 30 and _taken(c, a, "dropped 1")[1] == 30
+        assert _taken(c, a, "at th")[1] == th and _taken(c, a, "at th, both sides flipped")[1] == th and _taken(c, a, "th + 1") is None
+        assert _taken(c, a, "invalid") is None and _taken(c, a, "none free") is None
+        assert a[np.nonzero(c["assign0"] == 7)[0][0]] == 7 and a[np.nonzero(c["assign0"] == 11)[0][0]] == 11 and a[np.nonzero(c["assign0"] == 9)[0][0]] != 9
+        if not (run["ori"] and mode in (4, 5)):
+            assert [_taken(c, a, "chain %d" % k)[1] for k in range(5)] == [10, 12, 14, 16, 18]   # each takes the feature after the one it preferred
+            if mode in (3, 4):   # nobody blocks: the second takes what the first took, the first's entry is overwritten
+                assert _taken(c, a, "free chain 0") is None and _taken(c, a, "free chain 1")[1] == 10 and _taken(c, a, "free chain 2")[1] == 20
+            else:
+                assert [_taken(c, a, "free chain %d" % k)[1] for k in range(3)] == [10, 20, 40]
+        lv = {"levels -1,-1": 6, "levels 0,-1": 6, "levels 0,0": 30, "levels -1,0": 30, "levels 3,5": 18, "levels 7,8": 6}
+        for role, d in lv.items():
+            got = _taken(c, a, role)
+            assert (got[1] == d) if d <= th else (got is None), (run, role)
+
+
+def test_window_best_census_on_the_designed_scenes(oracle):
+    import window_cases as wc
+    for run in wc.WINDOW_RUNS:
+        c = wc.make_window_scene(oracle, run["stereo"])
+        bi, bd, cen = wc.window_oracle(oracle, c, run, census=True)
+        assert _same(wc.window_oracle(oracle, c, run), (bi, bd)), run
+        _need(cen, AREA + ("area_no_level_check", "win_invalid", "win_none", "win_level_below", "win_level_above", "win_new_best", "win_equal_best"), run)
+        assert cen["area_level_below"] == cen["area_level_above"] == 0             # unreachable: the window is gathered with (-1, -1)
+        R = c["roles"]
+        if run["chi2"]:
+            _need(cen, ("win_mono_reject", "win_mono_pass"), run)
+            assert all(bd[R["chi2 mono %d" % o]] == 10 for o in range(8))          # the feature one step outside the gate (5) is refused
+            if run["stereo"]:
+                _need(cen, ("win_stereo_reject", "win_stereo_pass"), run)
+                assert all(bd[R["chi2 stereo %d" % o]] == 10 for o in (0, 3, 7))
+                assert bd[R["chi2 uright 0"]] == 30 and bd[R["chi2 uright -1"]] == 5   # 0 is a right coordinate, -1 is none
+            else:
+                assert cen["win_stereo_reject"] == cen["win_stereo_pass"] == 0     # unreachable without t_uright
+        else:
+            assert cen["win_mono_reject"] == cen["win_mono_pass"] == cen["win_stereo_reject"] == cen["win_stereo_pass"] == 0   # unreachable without chi2
+            assert all(bd[R["chi2 mono %d" % o]] == 5 for o in range(8))
+        tie = R["tie inside the gate"]
+        assert bd[tie] == 20 and c["tk"]["x"][bi[tie]] < c["uvr"][tie, 0] and c["tk"]["x"][bi[tie] - 1] > c["uvr"][tie, 0]   # first in cell order, the higher index
+        assert (bi[R["empty window"]], bd[R["empty window"]]) == (-1, 256) and bi[R["no level fits"]] == -1 and bi[R["invalid"]] == -1
+        assert bd[R["pred 0"]] == 20 and bd[R["pred 3"]] == 20 and bd[R["pred 7"]] == 20 and bd[R["pred 7, below only"]] == 15
+    # the gates' edges really are neighbours in binary32
+    for o in range(8):
+        p, f = wc.adjacent(lambda tx: wc._chi2_mono(30.0, tx, o), 31.0, 42.0)
+        assert np.nextafter(p, np.float32(np.inf)) == f
+
+
+def test_initialization_census_on_the_designed_scene(oracle):
+    import window_cases as wc
+    c = wc.make_init_scene(oracle)
+    R = c["roles"]
+    for run in wc.INIT_RUNS:
+        m, n, cen = wc.init_oracle(oracle, c, run, census=True)
+        assert _same(wc.init_oracle(oracle, c, run), (m, n)), run
+        _need(cen, AREA + ("area_level_above",), run)
+        assert cen["area_no_level_check"] == cen["area_level_below"] == 0          # unreachable: the level window is (0, 0) for an octave-0 query
+        _need(cen, ("init_octave_skip", "init_no_candidate", "init_held_better", "init_held_equal", "init_new_best", "init_new_second", "init_equal_best",
+                    "init_best_at_th", "init_best_above_th", "init_ratio_reject", "init_ratio_equal", "init_accept", "init_steal"), run)
+        if run["ori"]:
+            _need(cen, ("init_pruned", "init_prune_already_revoked"), run)
+            assert m[R["lone pruned"]] == -1 and m[R["victim pruned 0"]] == -1 and m[R["victim pruned 1"]] >= 0 and m[R["victim kept 1"]] == -1
+        else:
+            assert cen["init_pruned"] == cen["init_prune_already_revoked"] == 0    # unreachable without check_ori
+        assert n == (m >= 0).sum()
+        assert m[R["steal 0"]] == -1 and m[R["steal 1"]] >= 0
+        assert m[R["held better 0"]] >= 0 and m[R["held better 1"]] == -1
+        assert m[R["equal 0"]] >= 0 and m[R["equal 1"]] == m[R["equal 0"]] + 1     # skipped at the equal distance: its second choice, at 50
+        assert m[R["chain 0"]] == -1 and m[R["chain 1"]] == -1 and m[R["chain 2"]] >= 0
+        assert R["stride 1"] - R["stride 0"] > 64 and m[R["stride 0"]] == -1 and m[R["stride 1"]] >= 0
+        assert m[R["at 50 0"]] >= 0 and m[R["at 51 0"]] == -1 and m[R["equal best 0"]] == -1
+        assert m[R["query octave 2"]] == -1 and c["tk"]["octave"][m[R["train octave 1"]]] == 0 and m[R["moved"]] >= 0
+        for k in range(4):
+            assert np.unpackbits(c["qd"][R["edge %d" % k]] ^ c["td"][m[R["edge %d" % k]]]).sum() == 10
+    z = np.zeros(0, oracle.KP_DTYPE)
+    m, n = oracle.search_for_initialization(np.zeros((0, 2), np.float32), 10.0, z, np.zeros((0, 32), np.uint8), c["gp"], c["tk"], c["start"], c["idx"], c["td"], 0.9, True)
+    assert n == 0 and len(m) == 0
+    s0, i0 = oracle.grid_build(c["gp"], z)
+    m, n = oracle.search_for_initialization(c["q_xy"], 10.0, c["qk"], c["qd"], c["gp"], z, s0, i0, np.zeros((0, 32), np.uint8), 0.9, True)
+    assert n == 0 and (m == -1).all()
+
+
+def test_triangulation_census_on_the_designed_scene(oracle):
+    import window_cases as wc
+    for run in wc.TRI_RUNS:
+        c = wc.make_tri_scene(oracle, run["stereo"])
+        m, n, cen = wc.tri_oracle(oracle, c, run, census=True)
+        assert _same(wc.tri_oracle(oracle, c, run), (m, n)), run
+        assert all(cen[k] == 0 for k in cen if not k.startswith("tri_"))           # unreachable: no window is gathered here
+        _need(cen, ("tri_node_one_side", "tri_skip1", "tri_match"), run)
+        if run["only"]:
+            _need(cen, ("tri_only_stereo_1", "tri_only_stereo_2", "tri_no_epipole_test", "tri_line_pass"), run)
+            q, t = c["roles"]["only stereo"]
+            assert n == 1 and m[q] == t
+            continue
+        assert cen["tri_only_stereo_1"] == cen["tri_only_stereo_2"] == 0           # unreachable without bOnlyStereo
+        _need(cen, ("tri_skip2", "tri_above_th", "tri_above_best", "tri_equal_best", "tri_epipole_near", "tri_epipole_on", "tri_den_zero", "tri_line_fail",
+                    "tri_line_pass", "tri_later_pass", "tri_equal_replaces"), run)
+        if run["stereo"]:
+            _need(cen, ("tri_no_epipole_test",), run)
+        else:
+            assert cen["tri_no_epipole_test"] == 0                                 # unreachable without a right coordinate on either side
+        if run["ori"]:
+            _need(cen, ("tri_pruned",), run)
+        else:
+            assert cen["tri_pruned"] == 0                                          # unreachable without check_ori
+        for role, (q, t) in c["roles"].items():
+            if role == "only stereo":
+                continue
+            assert m[q] == (-1 if role == "lone pruned" and run["ori"] else t), (run, role)
