@@ -992,4 +992,7 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 /* LoopClosing::ComputeSim3 behind the Sim3Solver, per candidate: SearchBySim3 and OptimizeSim3 from the pool, the store and the
  * frame set (orby_compute_sim3): orbslamm_computesim3.h. */
 #include "orbslamm_computesim3.h"
+/* MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth over that store, refreshing the pool's records in place
+ * (orbr_refresh_points, orbu_kf_set_descriptors / _centres, orbw_debug_pool_get): orbslamm_refresh.h. */
+#include "orbslamm_refresh.h"
 #endif

@@ -38,6 +38,7 @@ def _setup(L):
     L.orbw_track_local_map.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp, C.c_int, vp]
     L.orbw_track_frame_pose.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp]
     L.orbw_track_status.argtypes = [vp, C.c_int, vp, vp]
+    L.orbw_debug_pool_get.argtypes = [vp, vp, C.c_int, vp]
     L._orbw_ready = True
 
 
@@ -111,6 +112,13 @@ class MapPool(Handle):
         fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
         assert fl.shape[0] == ids.shape[0]
         check(self._L.orbw_pool_set_flags(self._h, ptr(ids), ptr(fl), ids.shape[0]))
+
+    def debug_get(self, ids):
+        """orbw_debug_pool_get: the pool's records of set ids, copied down (POINT_DTYPE)"""
+        ids = _ids(ids)
+        out = np.zeros(ids.shape[0], POINT_DTYPE)
+        check(self._L.orbw_debug_pool_get(self._h, ptr(ids), ids.shape[0], ptr(out)))
+        return out
 
     def view_project(self, view_rec, ids, th, scale_factors, breaks, last=None):
         """orbw_view_project: the projection kernel alone -> (uvr[nq, 3], lvl[nq, 2], viewcos[nq], status[nq]).
@@ -188,6 +196,16 @@ class OrbnCulling(C.Structure):
     _fields_ = [("K", C.c_int32), ("n_mps", C.c_void_p), ("n_redundant", C.c_void_p), ("redundant", C.c_void_p)]
 
 
+# ---- MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth over the store (include/orbslamm_refresh.h)
+REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH = 1, 2
+REFRESH_MAX_OBS = 1024
+RST_NOT_ASKED, RST_DONE, RST_BAD, RST_NO_OBSERVATION, RST_ALL_KF_BAD, RST_NO_REF, RST_LEVEL_RANGE = range(7)
+REFRESH_DTYPE = np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3), ("min_distance", "<f4"), ("max_distance", "<f4"), ("desc", "u1", 32),
+                          ("n_obs", "<i4"), ("n_desc", "<i4"), ("best_kf", "<i4"), ("best_idx", "<i4"), ("st_descriptor", "u1"),
+                          ("st_normal_depth", "u1"), ("pad", "u1", 2)])
+assert REFRESH_DTYPE.itemsize == 84
+
+
 def _copy(p, n, ct, dt):
     return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).astype(dt, copy=True) if p and n else np.zeros(0, dt)
 
@@ -233,6 +251,10 @@ def _setup_store(L):
     L.orbu_kf_set_octaves.argtypes = [vp, C.c_int, vp, C.c_int]
     L.orbn_update_connections.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     L.orbn_culling_counts.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    L.orbu_kf_set_descriptors.argtypes = [vp, C.c_int, vp, C.c_int]
+    L.orbu_kf_set_descriptors_frame.argtypes = [vp, C.c_int, vp, C.c_int]
+    L.orbu_kf_set_centres.argtypes = [vp, vp, vp, C.c_int]
+    L.orbr_refresh_points.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
     L.orbu_store_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.orbu_store_destroy.argtypes = [vp]
     L.orbu_kf_set.argtypes = [vp, vp]
@@ -339,6 +361,36 @@ class KeyFrameStore(Handle):
         """orbu_kf_set_octaves: mvKeysUn[i].octave of a set keyframe, one byte per feature"""
         o = np.ascontiguousarray(octaves, dtype=np.uint8).reshape(-1)
         check(self._L.orbu_kf_set_octaves(self._h, int(slot), ptr(o), o.shape[0]))
+
+    def set_descriptors(self, slot, desc):
+        """orbu_kf_set_descriptors: mDescriptors of a set keyframe, n x 32 bytes"""
+        d = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        check(self._L.orbu_kf_set_descriptors(self._h, int(slot), ptr(d), d.shape[0]))
+
+    def set_descriptors_frame(self, slot, fs, fs_slot):
+        """orbu_kf_set_descriptors_frame: the descriptors of slot fs_slot of a frame set, device to device"""
+        check(self._L.orbu_kf_set_descriptors_frame(self._h, int(slot), fs._h, int(fs_slot)))
+
+    def set_centres(self, slots, Ow):
+        """orbu_kf_set_centres: GetCameraCenter() of set keyframes, three floats each; a repeated slot takes the last"""
+        slots = _ids(slots)
+        c = np.ascontiguousarray(Ow, dtype=np.float32).reshape(-1, 3)
+        assert c.shape[0] == slots.shape[0]
+        check(self._L.orbu_kf_set_centres(self._h, ptr(slots), ptr(c), slots.shape[0]))
+
+    def refresh_points(self, ids, ref_kf, scale_factors, what=REFRESH_DESCRIPTOR | REFRESH_NORMAL_DEPTH, new_pos=None, commit=True):
+        """orbr_refresh_points: ComputeDistinctiveDescriptors and / or UpdateNormalAndDepth of the listed pool ids, written into the
+        pool when commit -> a REFRESH_DTYPE array, one record per id"""
+        ids, ref = _ids(ids), _ids(ref_kf)
+        assert ref.shape[0] == ids.shape[0]
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32)
+        pos = None
+        if new_pos is not None:
+            pos = np.ascontiguousarray(new_pos, dtype=np.float32).reshape(-1, 3)
+            assert pos.shape[0] == ids.shape[0]
+        out = np.zeros(ids.shape[0], REFRESH_DTYPE)
+        check(self._L.orbr_refresh_points(self._h, ptr(ids), ptr(ref), ptr(pos), ids.shape[0], int(what), ptr(sf), sf.shape[0], int(bool(commit)), ptr(out)))
+        return out
 
     def update_connections(self, targets, th=15):
         """orbn_update_connections: KeyFrame::UpdateConnections' counter and ordered list of every target -> Connections"""

@@ -1,0 +1,239 @@
+"""MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth without a GPU (orbr_*): the restatement
+(tools/refresh_ref.hpp) against an independent numpy model, bytes and floats as bits, over every scene family and seeds 1..10;
+every family forcing its branch; OrbrPoint's layout against the mirror; the refusals that need no GPU, `out` untouched; the
+drop-in compiled against its mocks."""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import refresh_cases as rc
+from orbslamm_amd import _lib
+from orbslamm_amd._lib import ORBX_E_INVALID, ORBX_OK, lib, ptr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32, f64 = np.float32, np.float64
+
+
+# ---- the model: numpy float32 operations taken one at a time, float64 for the norm, np.unpackbits for the distances
+def norm3(v):
+    s = f64(0)
+    for c in range(3):
+        s = s + f64(v[c]) * f64(v[c])
+    return np.sqrt(s)
+
+
+def model(r, ids, ref_kf, what=rc.BOTH, new_pos=None, sf=rc.SF):
+    s = r.s
+    voting = (s.entries >= 0) & ((s.entries & rc.NO_VOTE) == 0) & ((s.kf_flags & rc.KF_SET) != 0)[:, None]
+    obs = {}
+    for k, i in np.argwhere(voting):                                  # (row-major: ascending (k, i))
+        obs.setdefault(int(s.entries[k, i]), []).append((int(k), int(i)))
+    out = np.zeros(len(ids), rc.POINT_DTYPE)
+    nlevels = len(sf)
+    with np.errstate(all="ignore"):
+        for n, (pt, ref) in enumerate(zip(ids, ref_kf)):
+            o = out[n]
+            P = (r.pos[pt] if new_pos is None else np.asarray(new_pos, f32).reshape(-1, 3)[n]).astype(f32)
+            o["pos"], o["normal"], o["min_distance"], o["max_distance"], o["desc"] = P, r.normal[pt], r.min_d[pt], r.max_d[pt], r.pt_desc[pt]
+            o["best_kf"] = o["best_idx"] = -1
+            lst = obs.get(int(pt), [])
+            good = [(k, i) for k, i in lst if not (s.kf_flags[k] & rc.KF_BAD)]
+            o["n_obs"], o["n_desc"] = len(lst), len(good)
+            bad = bool(s.pt_bad[pt] & 1)
+            if what & rc.DESCRIPTOR:
+                if bad:
+                    o["st_descriptor"] = rc.ST_BAD
+                elif not lst:
+                    o["st_descriptor"] = rc.ST_NO_OBSERVATION
+                elif not good:
+                    o["st_descriptor"] = rc.ST_ALL_KF_BAD
+                else:
+                    bits = np.unpackbits(np.stack([r.desc[k, i] for k, i in good]), axis=1).astype(np.int32)
+                    dist = bits @ (1 - bits).T + (1 - bits) @ bits.T
+                    med = np.sort(dist, axis=1)[:, (len(good) - 1) // 2]
+                    w = int(np.argmin(med))                          # the first of the smallest
+                    o["st_descriptor"], o["desc"] = rc.ST_DONE, r.desc[good[w]]
+                    o["best_kf"], o["best_idx"] = good[w]
+            if what & rc.NORMAL_DEPTH:
+                refq = [i for k, i in lst if k == ref]
+                if bad:
+                    o["st_normal_depth"] = rc.ST_BAD
+                elif not lst:
+                    o["st_normal_depth"] = rc.ST_NO_OBSERVATION
+                elif ref < 0 or not refq:
+                    o["st_normal_depth"] = rc.ST_NO_REF
+                elif int(s.octaves[ref, refq[0]]) >= nlevels:
+                    o["st_normal_depth"] = rc.ST_LEVEL_RANGE
+                else:
+                    normal = np.zeros(3, f32)
+                    for k, _ in lst:
+                        v = P - r.centres[k]
+                        a = f32(f64(1.0) / norm3(v))
+                        for c in range(3):
+                            t = v[c] * a
+                            normal[c] = t + normal[c]
+                    alpha = 1.0 / len(lst)
+                    for c in range(3):
+                        normal[c] = normal[c] + f32(0) if alpha == 1.0 else f32(f64(normal[c]) * f64(alpha))
+                    dist = f32(norm3(P - r.centres[ref]))
+                    mx = dist * sf[int(s.octaves[ref, refq[0]])]
+                    o["st_normal_depth"], o["normal"], o["max_distance"], o["min_distance"] = rc.ST_DONE, normal, mx, mx / sf[nlevels - 1]
+    return out
+
+
+def bits_equal(a, b):
+    return a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def assert_ref_is_model(r, tag):
+    ids = np.arange(r.pool_cap, dtype=np.int32)
+    ref = rc.Ref(r)
+    moved = (r.pos + f32(0.25)).astype(f32)
+    for what, pos in ((rc.BOTH, None), (rc.DESCRIPTOR, None), (rc.NORMAL_DEPTH, None), (rc.NORMAL_DEPTH, moved), (rc.BOTH, moved)):
+        got, want = ref.refresh(ids, r.ref_kf, what, pos), model(r, ids, r.ref_kf, what, pos)
+        for n in rc.POINT_DTYPE.names:
+            assert bits_equal(got[n], want[n]), (tag, what, pos is not None, n, np.flatnonzero((got[n] != want[n]).reshape(len(ids), -1).any(axis=1))[:8])
+    return ref
+
+
+@pytest.mark.parametrize("family", sorted(rc.FAMILIES))
+def test_the_restatement_equals_the_model_and_the_family_forces_its_branch(family):
+    for seed in range(1, 11):
+        r = rc.family_scene(family, seed)
+        ref = assert_ref_is_model(r, (family, seed))
+        seen = ref.seen()
+        for b in rc.FAMILIES[family]:
+            assert seen[b] > 0, (family, seed, b, seen)
+
+
+def test_every_named_branch_is_forced_by_some_family():
+    assert sorted(set(b for v in rc.FAMILIES.values() for b in v)) == sorted(rc.BRANCHES)
+
+
+def test_what_the_families_must_show_beyond_their_counters():
+    ids = lambda r, *names: np.array([r.named[n] for n in names], np.int32)
+    one = lambda r, n="p", what=rc.BOTH: rc.Ref(r).refresh(ids(r, n), r.ref_kf[ids(r, n)], what)[0]
+    for n in rc.OBSERVER_COUNTS:
+        o = one(rc.family_scene("observers_%d" % n, 1))
+        assert o["n_obs"] == o["n_desc"] == n and o["st_descriptor"] == o["st_normal_depth"] == rc.ST_DONE
+    for fam in ("equal_medians", "identical_descriptors"):        # the first of the equal medians wins
+        o = one(rc.family_scene(fam, 2))
+        assert o["best_kf"] == rc.T0 and o["st_descriptor"] == rc.ST_DONE
+    r = rc.family_scene("complement", 3)
+    o = one(r, "q")
+    assert o["best_kf"] == rc.T0 + 1                              # the row of the lone descriptor has the median 256
+    o = one(rc.family_scene("bad_keyframe_among", 1))
+    assert (o["n_obs"], o["n_desc"]) == (5, 4) and o["st_normal_depth"] == rc.ST_DONE
+    o = one(rc.family_scene("all_observers_bad", 1))
+    assert (o["n_obs"], o["n_desc"], o["st_descriptor"], o["st_normal_depth"]) == (3, 0, rc.ST_ALL_KF_BAD, rc.ST_DONE)
+    o = one(rc.family_scene("bad_point", 1))
+    assert o["st_descriptor"] == o["st_normal_depth"] == rc.ST_BAD and o["n_obs"] == 4
+    o = one(rc.family_scene("no_vote_only", 1))
+    assert o["st_descriptor"] == o["st_normal_depth"] == rc.ST_NO_OBSERVATION and o["n_obs"] == 0
+    o = one(rc.family_scene("twice_in_one_keyframe", 1))
+    assert o["n_obs"] == 4
+    for fam in ("ref_minus_1", "ref_not_observing"):
+        o = one(rc.family_scene(fam, 1))
+        assert (o["st_descriptor"], o["st_normal_depth"]) == (rc.ST_DONE, rc.ST_NO_REF)
+    r = rc.family_scene("ref_octave_edges", 1)
+    assert one(r, "p")["st_normal_depth"] == rc.ST_DONE and one(r, "q")["st_normal_depth"] == rc.ST_LEVEL_RANGE
+    o = one(rc.family_scene("at_camera_centre", 1))
+    assert o["st_normal_depth"] == rc.ST_DONE and np.isnan(o["normal"]).all()       # 0 * inf, as the arithmetic gives
+    o = one(rc.family_scene("bad_point", 1), what=rc.DESCRIPTOR)
+    assert o["st_normal_depth"] == rc.ST_NOT_ASKED
+
+
+@pytest.mark.parametrize("nobs", [rc.MAX_OBS, rc.MAX_OBS + 1])
+def test_the_restatement_equals_the_model_at_the_observation_ceiling(nobs):
+    r = rc.long_scene(nobs)
+    assert_ref_is_model(r, nobs)
+    assert rc.Ref(r).refresh([r.named["p"]], [r.ref_kf[r.named["p"]]])[0]["n_obs"] == nobs
+
+
+def test_record_layout_agrees_with_the_mirror():
+    from orbslamm_amd import map_pool as mp
+    names = [n for n in mp.REFRESH_DTYPE.names]
+    src = "#include \"orbslamm_refresh.h\"\n#include <stddef.h>\nextern \"C\" int layout(int i) {\n    const int v[] = {(int)sizeof(OrbrPoint), " + \
+          ", ".join("(int)offsetof(OrbrPoint, %s)" % n for n in names) + \
+          ", ORBR_DESCRIPTOR, ORBR_NORMAL_DEPTH, ORBR_MAX_OBS, ORBR_ST_NOT_ASKED, ORBR_ST_DONE, ORBR_ST_BAD, ORBR_ST_NO_OBSERVATION, ORBR_ST_ALL_KF_BAD, " \
+          "ORBR_ST_NO_REF, ORBR_ST_LEVEL_RANGE};\n    return v[i];\n}\n"
+    d = tempfile.mkdtemp(prefix="refresh_layout_")
+    with open(os.path.join(d, "layout.cpp"), "w") as f:
+        f.write(src)
+    so = os.path.join(d, "liblayout.so")
+    subprocess.check_call(["g++", "-std=c++11", "-fPIC", "-shared", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(d, "layout.cpp"), "-o", so])
+    L = C.CDLL(so)
+    got = [L.layout(i) for i in range(1 + len(names) + 10)]
+    want = [mp.REFRESH_DTYPE.itemsize] + [mp.REFRESH_DTYPE.fields[n][1] for n in names]
+    want += [mp.REFRESH_DESCRIPTOR, mp.REFRESH_NORMAL_DEPTH, mp.REFRESH_MAX_OBS, mp.RST_NOT_ASKED, mp.RST_DONE, mp.RST_BAD, mp.RST_NO_OBSERVATION,
+             mp.RST_ALL_KF_BAD, mp.RST_NO_REF, mp.RST_LEVEL_RANGE]
+    assert got == want
+    assert mp.REFRESH_DTYPE == rc.POINT_DTYPE and rc.shim().rfr_point_size() == mp.REFRESH_DTYPE.itemsize
+    assert (rc.DESCRIPTOR, rc.NORMAL_DEPTH, rc.MAX_OBS) == (mp.REFRESH_DESCRIPTOR, mp.REFRESH_NORMAL_DEPTH, mp.REFRESH_MAX_OBS)
+
+
+def test_the_symbols_are_exported():
+    import orbslamm_amd
+    L = lib()
+    for name in ("orbu_kf_set_descriptors", "orbu_kf_set_descriptors_frame", "orbu_kf_set_centres", "orbw_debug_pool_get", "orbr_refresh_points"):
+        assert name in _lib.EXPORTS_REFRESH and hasattr(L, name)
+    for name in ("set_descriptors", "set_descriptors_frame", "set_centres", "refresh_points"):
+        assert hasattr(orbslamm_amd.KeyFrameStore, name)
+    assert hasattr(orbslamm_amd.MapPool, "debug_get") and orbslamm_amd.REFRESH_DTYPE.itemsize == 84
+
+
+def test_refusals_that_need_no_gpu():
+    """argument checks come before the handle's: with a NULL store the entries still name the bad argument, zero counts return
+    ORBX_OK, and `out` keeps its bytes"""
+    from orbslamm_amd import map_pool as mp
+    L = lib()
+    mp._setup(L)
+    mp._setup_store(L)
+    ids, ref, sf = np.zeros(2, np.int32), np.full(2, -1, np.int32), rc.SF.copy()
+    ids[1] = 1
+    pos = np.zeros((2, 3), np.float32)
+    out = np.zeros(2, mp.REFRESH_DTYPE)
+    out.view(np.uint8)[:] = 0xAB
+    f = L.orbr_refresh_points
+    good = dict(ids=ptr(ids), ref=ptr(ref), pos=None, n=2, what=3, sf=ptr(sf), nlevels=8, commit=1, out=ptr(out))
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return f(None, a["ids"], a["ref"], a["pos"], a["n"], a["what"], a["sf"], a["nlevels"], a["commit"], a["out"])
+
+    for kw in (dict(ids=None), dict(ref=None), dict(sf=None), dict(out=None), dict(n=-1), dict(what=0), dict(what=4), dict(what=7), dict(nlevels=0),
+               dict(nlevels=17)):
+        assert call(**kw) == ORBX_E_INVALID, kw
+        assert b"null store" not in L.orbx_last_error(), kw
+    for bad in (np.nan, np.inf, -np.inf):
+        pos[1, 2] = bad
+        assert call(pos=ptr(pos)) == ORBX_E_INVALID and b"not finite" in L.orbx_last_error()
+    pos[1, 2] = 0
+    assert call(pos=ptr(pos)) == ORBX_E_INVALID and b"null store" in L.orbx_last_error()
+    assert call() == ORBX_E_INVALID and b"null store" in L.orbx_last_error()
+    assert call(n=0, ids=None, ref=None, sf=None, out=None) == ORBX_OK
+    assert (out.view(np.uint8) == 0xAB).all()
+    # the setters and the debug reader
+    d, c, one = np.zeros((4, 32), np.uint8), np.zeros((1, 3), np.float32), np.zeros(1, np.int32)
+    sd, sc, sfm, dg = L.orbu_kf_set_descriptors, L.orbu_kf_set_centres, L.orbu_kf_set_descriptors_frame, L.orbw_debug_pool_get
+    assert sd(None, 0, ptr(d), -1) == ORBX_E_INVALID and sd(None, -1, ptr(d), 4) == ORBX_E_INVALID and sd(None, 0, None, 4) == ORBX_E_INVALID
+    assert sd(None, 0, ptr(d), 4) == ORBX_E_INVALID and b"null store" in L.orbx_last_error()
+    assert sc(None, ptr(one), ptr(c), -1) == ORBX_E_INVALID and sc(None, None, ptr(c), 1) == ORBX_E_INVALID and sc(None, ptr(one), None, 1) == ORBX_E_INVALID
+    assert sc(None, ptr(one), ptr(c), 1) == ORBX_E_INVALID and b"null store" in L.orbx_last_error()
+    assert sc(None, None, None, 0) == ORBX_OK
+    assert sfm(None, -1, None, 0) == ORBX_E_INVALID and sfm(None, 0, None, 0) == ORBX_E_INVALID
+    rec = np.zeros(1, mp.POINT_DTYPE)
+    rec.view(np.uint8)[:] = 0xCD
+    assert dg(None, ptr(one), -1, ptr(rec)) == ORBX_E_INVALID and dg(None, None, 1, ptr(rec)) == ORBX_E_INVALID and dg(None, ptr(one), 1, None) == ORBX_E_INVALID
+    assert dg(None, ptr(one), 1, ptr(rec)) == ORBX_E_INVALID and b"null pool" in L.orbx_last_error()
+    assert dg(None, None, 0, None) == ORBX_OK and (rec.view(np.uint8) == 0xCD).all()
+
+
+@pytest.mark.parametrize("name", ["refresh_dropin_gpu"])
+def test_the_dropin_compiles_against_the_mocks(name):
+    """include/MapPoint_hip.hpp over tests/cpp/mock_refresh.hpp, warnings as errors (syntax and types only: nothing is linked or run)"""
+    subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", name + ".cpp")])
