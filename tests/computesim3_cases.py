@@ -17,7 +17,7 @@ import trackpose_cases as tc
 from matcher_cases import noisy_copies
 from orbslamm_amd._lib import KP_DTYPE
 from poseopt_cases import inv_level_sigma2
-from ref_shim import build_ref_shim, p
+from ref_shim import cached_shim, p
 
 f32 = np.float32
 N = 300
@@ -196,15 +196,17 @@ BRANCH = {
 
 
 # ------------------------------------------------------------------ the restatement
-@functools.lru_cache(maxsize=1)
-def ref_lib():
-    L = build_ref_shim("computesim3_ref")
+def _declare(L):
     assert [L.computesim3ref_sizes(i) for i in range(5)] == [REF_KEY.itemsize, REF_GRID.itemsize, sc.REF_PROBLEM.itemsize, REF_RESULT.itemsize, 4 * len(BRANCH_NAMES)]
     vp, ci, cf = C.c_void_p, C.c_int, C.c_float
     L.computesim3ref_run.argtypes = ([vp] * 5 + [ci] + [vp, vp, ci, vp, ci, vp] * 2 + [vp] * 6 + [ci] + [vp] * 4 + [cf, cf] + [vp] * 9)
     L.computesim3ref_run.restype = None
     L.computesim3ref_verdict.argtypes = [ci]
-    return L
+
+
+def ref_lib():
+    """the restatement as a shared object (built once per process)"""
+    return cached_shim("computesim3_ref", _declare)
 
 
 def ref_keys(keys):

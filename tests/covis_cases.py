@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ref_shim import build_ref_shim, p
+from ref_shim import cached_shim, p
 
 NO_VOTE = 1 << 30
 KF_BAD, KF_SET = 1, 2
@@ -206,20 +206,18 @@ class RefStore(C.Structure):
                 ("poolCap", C.c_int)]
 
 
-_shim = None
+def _declare(L):
+    L.cov_open.restype = C.c_void_p
+    L.cov_open.argtypes = [C.c_void_p]
+    L.cov_close.argtypes = [C.c_void_p]
+    L.cov_connections.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
+    L.cov_culling.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+    L.cov_culling.restype = None
 
 
 def shim():
-    global _shim
-    if _shim is None:
-        _shim = build_ref_shim("covis_ref")
-        _shim.cov_open.restype = C.c_void_p
-        _shim.cov_open.argtypes = [C.c_void_p]
-        _shim.cov_close.argtypes = [C.c_void_p]
-        _shim.cov_connections.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p]
-        _shim.cov_culling.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
-        _shim.cov_culling.restype = None
-    return _shim
+    """the restatement as a shared object (built once per process)"""
+    return cached_shim("covis_ref", _declare)
 
 
 class Ref:

@@ -8,10 +8,9 @@
 
 #include "ORBextractor_hip.hpp"
 #include "ORBmatcher_hip.hpp"
+#include "dropin_test.hpp"
 #include "../../oracle/orb_oracle.h"
 
-static int fails = 0;
-#define EXPECT(c) do { if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); fails++; } } while (0)
 
 static bool l0_is_frame(iORB_SLAM::ORBextractor& ex, const std::vector<uint8_t>& img, int W, int H)
 {
@@ -34,9 +33,9 @@ int main()
     orc_extractor_init(&oex, 1000, 1.2f, 8, 20, 7);
     std::vector<OrcKeyPoint> okps(2000); std::vector<uint8_t> odesc(2000 * 32);
     const int on = orc_extract(&oex, img.data(), W, H, W, okps.data(), odesc.data(), 2000, nullptr, nullptr, nullptr);
-    EXPECT(on > 100 && (size_t)on == kps.size());
-    EXPECT(std::memcmp(okps.data(), kps.data(), (size_t)on * 28) == 0);
-    EXPECT(std::memcmp(odesc.data(), desc.data(), (size_t)on * 32) == 0);
+    CHECK(on > 100 && (size_t)on == kps.size());
+    CHECK(std::memcmp(okps.data(), kps.data(), (size_t)on * 28) == 0);
+    CHECK(std::memcmp(odesc.data(), desc.data(), (size_t)on * 32) == 0);
 
     // SearchByBoW on a std::map-shaped FeatureVector
     const int n = (int)kps.size();
@@ -54,9 +53,9 @@ int main()
     OrcFeatVec oq = {fq.view().n_nodes, fq.node_id.data(), fq.start.data(), fq.idx.data()};
     OrcFeatVec ot = {ft.view().n_nodes, ft.node_id.data(), ft.start.data(), ft.idx.data()};
     const int onm = orc_search_by_bow(desc.data(), ang.data(), nullptr, n, &oq, d2.data(), ang.data(), nullptr, n, &ot, 0.75f, 1, 1, omatch.data());
-    EXPECT(nm == onm && nm > 100);
-    EXPECT(std::memcmp(match.data(), omatch.data(), (size_t)n * 4) == 0);
-    EXPECT(m.DescriptorDistance(desc.data(), d2.data()) == orc_descriptor_distance(desc.data(), d2.data()));
+    CHECK(nm == onm && nm > 100);
+    CHECK(std::memcmp(match.data(), omatch.data(), (size_t)n * 4) == 0);
+    CHECK(m.DescriptorDistance(desc.data(), d2.data()) == orc_descriptor_distance(desc.data(), d2.data()));
 
     // SearchForInitialization against the same frame shifted in descriptor space
     OrbmGrid g = {0.f, 0.f, 64.f / 640.f, 48.f / 480.f, 64, 48};
@@ -69,8 +68,8 @@ int main()
     orc_grid_build(&og, (const OrcKeyPoint*)kps.data(), n, cs.data(), ci.data());
     const int oni = orc_search_for_initialization(xy.data(), 100.f, (const OrcKeyPoint*)kps.data(), desc.data(), n, &og,
                                                   (const OrcKeyPoint*)kps.data(), cs.data(), ci.data(), d2.data(), n, 0.75f, 1, om12.data());
-    EXPECT(ni == oni && ni > 50);
-    EXPECT(std::memcmp(m12.data(), om12.data(), (size_t)n * 4) == 0);
+    CHECK(ni == oni && ni > 50);
+    CHECK(std::memcmp(m12.data(), om12.data(), (size_t)n * 4) == 0);
     // device-resident frames: the frame just extracted and a second, noisier one never leave HBM
     {
         const OrbxKeyPoint* dk = nullptr; const uint8_t* dd = nullptr;
@@ -86,15 +85,15 @@ int main()
         auto F2 = m.makeFrame(dk, dd, n2, K, D0, g);
         std::vector<OrbxKeyPoint> un1;
         F1->keysUn(un1);
-        EXPECT((int)un1.size() == n && std::memcmp(un1.data(), kps.data(), (size_t)n * 28) == 0);  // D = 0: mvKeysUn = mvKeys
+        CHECK((int)un1.size() == n && std::memcmp(un1.data(), kps.data(), (size_t)n * 28) == 0);  // D = 0: mvKeysUn = mvKeys
         std::vector<int> f12;
         const int nf = m.SearchForInitialization(xy.data(), 100, *F1, *F2, f12);
         std::vector<int32_t> cs2(64 * 48 + 1), ci2(n2), of12(n);
         orc_grid_build(&og, (const OrcKeyPoint*)kps2.data(), n2, cs2.data(), ci2.data());
         const int onf = orc_search_for_initialization(xy.data(), 100.f, (const OrcKeyPoint*)kps.data(), desc.data(), n, &og,
                                                       (const OrcKeyPoint*)kps2.data(), cs2.data(), ci2.data(), desc2.data(), n2, 0.75f, 1, of12.data());
-        EXPECT(nf == onf && nf > 50);
-        EXPECT(std::memcmp(f12.data(), of12.data(), (size_t)n * 4) == 0);
+        CHECK(nf == onf && nf > 50);
+        CHECK(std::memcmp(f12.data(), of12.data(), (size_t)n * 4) == 0);
         std::printf("device frames: %d / %d features, %d init matches\n", n, n2, nf);
     }
     // Ownership: matchers are stack temporaries; the device state is the calling thread's.
@@ -105,7 +104,7 @@ int main()
     //  * frame blocks are recycled: a frame per image allocates nothing in steady state.
     {
         orbm_t* mine = nullptr;
-        EXPECT(orbm_thread_handle(0, &mine) == ORBX_OK && mine == m.handle());
+        CHECK(orbm_thread_handle(0, &mine) == ORBX_OK && mine == m.handle());
         int64_t a0 = 0, b0 = 0, c0 = 0, a1 = 0, b1 = 0, c1 = 0;
         std::vector<int32_t> mt;
         { iORB_SLAM::FlatMatcher w(0.75f, true, 0); w.SearchByBoW(desc.data(), ang.data(), nullptr, n, fq, d2.data(), ang.data(), nullptr, n, ft, true, mt); }
@@ -113,10 +112,10 @@ int main()
         for (int rep = 0; rep < 20; rep++) {
             iORB_SLAM::FlatMatcher tmp(0.75f, true, 0);   // the reference's `ORBmatcher matcher(0.75, true);` on the stack
             const int k = tmp.SearchByBoW(desc.data(), ang.data(), nullptr, n, fq, d2.data(), ang.data(), nullptr, n, ft, true, mt);
-            EXPECT(k == onm && std::memcmp(mt.data(), omatch.data(), (size_t)n * 4) == 0);
+            CHECK(k == onm && std::memcmp(mt.data(), omatch.data(), (size_t)n * 4) == 0);
         }
         orbm_alloc_stats(mine, &a1, &b1, &c1);
-        EXPECT(a0 == a1 && b0 == b1 && c0 == c1);
+        CHECK(a0 == a1 && b0 == b1 && c0 == c1);
         // frames: the first few take blocks, later ones recycle them
         const OrbxKeyPoint* dk = nullptr; const uint8_t* dd = nullptr;
         ex(img.data(), W, H, W, kps, desc);
@@ -130,11 +129,11 @@ int main()
             if (rep % 10 == 0) {
                 std::vector<int> f12;
                 const int nf = m.SearchForInitialization(xy.data(), 100, *Fa, *Fa, f12);
-                EXPECT(nf > 50);
+                CHECK(nf > 50);
             }
         }
         orbm_alloc_stats(mine, &a1, &b1, &c1);
-        EXPECT(a0 == a1 && b0 == b1 && c0 == c1);
+        CHECK(a0 == a1 && b0 == b1 && c0 == c1);
         // threads: each its own handle, the same answers; a frame handed from a thread that ends to one that goes on
         std::unique_ptr<iORB_SLAM::DeviceFrame> handed;
         int64_t madeBefore = 0, madeAfter = 0;
@@ -153,19 +152,19 @@ int main()
             });
         for (auto& t : th) t.join();
         orbm_alloc_stats(nullptr, nullptr, nullptr, &madeAfter);
-        EXPECT(madeAfter - madeBefore == 4);   // one handle per thread, not one per matcher object
-        for (int t = 0; t < 4; t++) EXPECT(tfails[(size_t)t] == 0);
-        EXPECT(handed && handed->size() == n);
+        CHECK(madeAfter - madeBefore == 4);   // one handle per thread, not one per matcher object
+        for (int t = 0; t < 4; t++) CHECK(tfails[(size_t)t] == 0);
+        CHECK(handed && handed->size() == n);
         {
             std::vector<int> f12;
             auto Fm = m.makeFrame(dk, dd, n, K, D0, g);
             const int nf = m.SearchForInitialization(xy.data(), 100, *handed, *Fm, f12);   // thread 0's frame through this thread's handle
             std::vector<int> g12;
             const int ng = m.SearchForInitialization(xy.data(), 100, *Fm, *Fm, g12);
-            EXPECT(nf == ng && f12 == g12);
+            CHECK(nf == ng && f12 == g12);
             std::vector<OrbxKeyPoint> un;
             handed->keysUn(un);
-            EXPECT((int)un.size() == n && std::memcmp(un.data(), kps.data(), (size_t)n * 28) == 0);
+            CHECK((int)un.size() == n && std::memcmp(un.data(), kps.data(), (size_t)n * 28) == 0);
         }
         handed.reset();   // the last reference to thread 0's handle goes here
         std::printf("ownership: 20 + 40 matcher temporaries, 100 recycled frames, no handle or allocation made in steady state\n");
@@ -183,10 +182,10 @@ int main()
         ex(img2.data(), W, H, W, kb, db);
         fs.build(1, ex.handle());
         std::vector<OrbxKeyPoint> un; std::vector<uint8_t> dd2;
-        EXPECT(fs.download(1, un, dd2) == (int)kb.size() && std::memcmp(un.data(), kb.data(), kb.size() * 28) == 0 && dd2 == db);
+        CHECK(fs.download(1, un, dd2) == (int)kb.size() && std::memcmp(un.data(), kb.data(), kb.size() * 28) == 0 && dd2 == db);
         fs.track({1}, {0}, 15.f);
         const int32_t* assign = nullptr; const int32_t* nmv = nullptr;
-        EXPECT(fs.results(assign, nmv) == 1);
+        CHECK(fs.results(assign, nmv) == 1);
         const int na = (int)ka.size(), nb = (int)kb.size();
         std::vector<float> uvr((size_t)na * 3); std::vector<int8_t> lvl((size_t)na * 2); std::vector<float> ang((size_t)na);
         const std::vector<float> sf = ex.GetScaleFactors();
@@ -201,8 +200,8 @@ int main()
         OrcProjParams opp = {4, 0.9f, 1, 100};
         const int wn = orc_search_by_projection(&opp, uvr.data(), lvl.data(), da.data(), ang.data(), nullptr, nullptr, na, &og,
                                                 (const OrcKeyPoint*)kb.data(), cs3.data(), ci3.data(), db.data(), nb, occ.data(), want.data());
-        EXPECT(nmv[0] == wn && wn > 100);
-        EXPECT(std::memcmp(assign, want.data(), (size_t)nb * 4) == 0);
+        CHECK(nmv[0] == wn && wn > 100);
+        CHECK(std::memcmp(assign, want.data(), (size_t)nb * 4) == 0);
         std::printf("frame set: %d / %d features, %d projection matches\n", na, nb, wn);
     }
     // mvImagePyramid (ORBextractor.h:85): a public member again, filled on first use after operator(), each level inside
@@ -210,7 +209,7 @@ int main()
     {
         std::vector<OrbxKeyPoint> k3; std::vector<uint8_t> d3;
         ex(img.data(), W, H, W, k3, d3);
-        EXPECT(ex.mvImagePyramid.size() == 8);
+        CHECK(ex.mvImagePyramid.size() == 8);
         std::vector<uint8_t> opyr((size_t)W * H * 4);
         orc_extract(&oex, img.data(), W, H, W, okps.data(), odesc.data(), 2000, opyr.data(), nullptr, nullptr);
         size_t off = 0;
@@ -218,17 +217,17 @@ int main()
             iORB_SLAM::PyramidLevel& P = ex.mvImagePyramid[(size_t)l];
             int lw = 0, lh = 0;
             orc_level_size(&oex, W, H, l, &lw, &lh);
-            EXPECT(P.cols == lw && P.rows == lh && P.step == (size_t)lw + 38);
+            CHECK(P.cols == lw && P.rows == lh && P.step == (size_t)lw + 38);
             bool same = true, border = true;
             for (int y = 0; y < lh && same; y++) same = std::memcmp(P.data + (size_t)y * P.step, &opyr[off + (size_t)y * lw], (size_t)lw) == 0;
             for (int d = 1; d <= 19; d++) {   // reflect-101: pixel -d mirrors pixel +d, pixel n-1+d mirrors n-1-d
                 border = border && P.data[-d] == P.data[d] && P.data[(ptrdiff_t)(lh - 1 + d) * (ptrdiff_t)P.step + 5] == P.data[(size_t)(lh - 1 - d) * P.step + 5];
                 border = border && P.data[-(ptrdiff_t)d * (ptrdiff_t)P.step - d] == P.data[(size_t)d * P.step + d];
             }
-            EXPECT(same); EXPECT(border);
+            CHECK(same); CHECK(border);
             off += (size_t)lw * lh;
         }
-        EXPECT(l0_is_frame(ex, img, W, H));
+        CHECK(l0_is_frame(ex, img, W, H));
     }
     // three robots' extractors on ONE hub (MultipleRobotsScenario: an ORBextractor per robot, a tracking thread each): every
     // robot gets the keypoints and descriptors of ITS frames, whatever went through the GPU beside them
@@ -236,7 +235,7 @@ int main()
         orbslamm::CameraHub::Config hc;
         hc.prm = OrbxParams{1000, 1.2f, 8, 20, 7}; hc.w = W; hc.h = H; hc.cameras = 3; hc.device = 0; hc.track = false; hc.wait_us = 500;
         std::shared_ptr<orbslamm::CameraHub> hub(new orbslamm::CameraHub());
-        EXPECT(hub->open(hc) == ORBX_OK);
+        CHECK(hub->open(hc) == ORBX_OK);
         const int R = 3, F = 4;
         std::vector<std::vector<uint8_t> > frames((size_t)R * F, std::vector<uint8_t>((size_t)W * H));
         for (int r = 0; r < R; r++)
@@ -253,9 +252,9 @@ int main()
         for (auto& t : th) t.join();
         for (int i = 0; i < R * F; i++) {
             const int n2 = orc_extract(&oex, frames[(size_t)i].data(), W, H, W, okps.data(), odesc.data(), 2000, nullptr, nullptr, nullptr);
-            EXPECT(n2 > 100 && (size_t)n2 == gk[(size_t)i].size());
-            EXPECT((size_t)n2 == gk[(size_t)i].size() && std::memcmp(okps.data(), gk[(size_t)i].data(), (size_t)n2 * 28) == 0);
-            EXPECT((size_t)n2 * 32 == gd[(size_t)i].size() && std::memcmp(odesc.data(), gd[(size_t)i].data(), (size_t)n2 * 32) == 0);
+            CHECK(n2 > 100 && (size_t)n2 == gk[(size_t)i].size());
+            CHECK((size_t)n2 == gk[(size_t)i].size() && std::memcmp(okps.data(), gk[(size_t)i].data(), (size_t)n2 * 28) == 0);
+            CHECK((size_t)n2 * 32 == gd[(size_t)i].size() && std::memcmp(odesc.data(), gd[(size_t)i].data(), (size_t)n2 * 32) == 0);
         }
     }
     std::printf(fails ? "adapter_gpu: %d failures\n" : "adapter_gpu ok (%d keypoints, %d BoW matches, %d init matches)\n", fails ? fails : on, nm, ni);

@@ -21,10 +21,6 @@ typedef iORB_SLAM::ORBmatcherT<mock::Frame, KeyFrame, MapPoint> ORBmatcher;
 typedef iORB_SLAM::OptimizeSim3T<KeyFrame, MapPoint, s3mock::Sim3> OptSim3;
 typedef iORB_SLAM::ComputeSim3T<KeyFrame, MapPoint, s3mock::Sim3> ComputeSim3;
 
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { printf("FAILED %s (line %d)\n", #c, __LINE__); fails++; } } while (0)
-#define OX(call) do { const int rc_ = (call); if (rc_) { printf("%s -> %d: %s\n", #call, rc_, orbx_last_error()); return 2; } } while (0)
-
 static const int N = 300, CAP = 320, NPAIR = 3;
 
 static s3mock::Sim3 startSim3(const cmock::Pair& P)

@@ -17,15 +17,11 @@
 #include "LocalMapping_hip.hpp"
 #include "Tracking_hip.hpp"
 #include "mock_covis.hpp"
+#include "dropin_test.hpp"
 
 using cmock::KeyFrame;
 using cmock::MapPoint;
 using namespace std;
-
-#define OX(call)                                                                               \
-    do {                                                                                       \
-        if ((call) != ORBX_OK) { fprintf(stderr, "%s: %s\n", #call, orbx_last_error()); return 2; } \
-    } while (0)
 
 // ---- the two members, serially
 static void UpdateConnections(KeyFrame* self)   // KeyFrame.cc:300-400

@@ -14,15 +14,13 @@
 
 #include "LocalMapping_hip.hpp"
 #include "mock_fuse.hpp"
+#include "dropin_test.hpp"
 #include "../../oracle/orb_oracle.h"
 #include "../../tools/fuse_ref.hpp"
 
 typedef iORB_SLAM::SearchInNeighborsT<fmock::KeyFrame, fmock::MapPoint, fmock::Mat> Neighbors;
 
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { if (fails < 20) printf("FAILED %s (line %d)\n", #c, __LINE__); fails++; } } while (0)
 
-template <class T> static void rd(FILE* f, T* p, size_t n) { if (n && fread(p, sizeof(T), n, f) != n) { printf("short scene file\n"); exit(2); } }
 
 struct KfData { fuse_ref::Target rec; std::vector<fuse_ref::KeyPt> keys; std::vector<uint8_t> desc; std::vector<int32_t> covis; };
 

@@ -8,31 +8,16 @@
 #include <vector>
 
 #include "Initializer_hip.hpp"
+#include "dropin_test.hpp"
 #include "../../tools/init_ref.hpp"
 
 namespace imock {
 struct KeyPoint { float x, y, size, angle, response; int32_t octave, class_id; };
-struct Mat {
-    int rows = 0, cols = 0;
-    std::vector<float> d;
-    Mat() {}
-    Mat(int r, int c, int /*type*/) : rows(r), cols(c), d((size_t)r * c, 0.f) {}
-    template <class T> T& at(int r, int c) { return d[(size_t)r * cols + c]; }
-    template <class T> const T& at(int r, int c) const { return d[(size_t)r * cols + c]; }
-};
 struct Point3f { float x, y, z; Point3f(float a, float b, float c) : x(a), y(b), z(c) {} };
-struct Frame { std::vector<KeyPoint> mvKeysUn; Mat mK; };
-// Thirdparty/DBoW2/DUtils/Random.cpp's SeedRandOnce / RandomInt
-struct Random {
-    static bool& seeded() { static bool s = false; return s; }
-    static void SeedRandOnce(int seed) { if (!seeded()) { srand(seed); seeded() = true; } }
-    static int RandomInt(int min, int max) { const int d = max - min + 1; return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min; }
-};
+struct Frame { std::vector<KeyPoint> mvKeysUn; Mat32 mK; };
 }  // namespace imock
 
 static const float K4[4] = {517.3f, 516.5f, 318.6f, 255.3f};
-
-static double urand(unsigned& s) { s = s * 1664525u + 1013904223u; return (s >> 8) / 16777216.0; }
 
 // n1 / n2 keys, nm matched (30 % of them outliers), general or planar scene seen from two poses
 static void scene(unsigned seed, bool planar, int n1, int n2, int nm, imock::Frame& f1, imock::Frame& f2, std::vector<int>& m12)
@@ -42,7 +27,7 @@ static void scene(unsigned seed, bool planar, int n1, int n2, int nm, imock::Fra
     const double t[3] = {0.6, 0.05, 0.1};
     f1.mvKeysUn.clear(); f2.mvKeysUn.clear();
     m12.assign((size_t)n1, -1);
-    f1.mK = imock::Mat(3, 3, 5);
+    f1.mK = Mat32(3, 3, 5);
     f1.mK.at<float>(0, 0) = K4[0]; f1.mK.at<float>(1, 1) = K4[1]; f1.mK.at<float>(0, 2) = K4[2]; f1.mK.at<float>(1, 2) = K4[3]; f1.mK.at<float>(2, 2) = 1.f;
     f2.mK = f1.mK;
     auto key = [&](double x, double y) { imock::KeyPoint k = {(float)x, (float)y, 31.f, (float)(360 * urand(s)), 1.f, 0, -1}; return k; };
@@ -70,9 +55,9 @@ static int run_case(unsigned seed, bool planar)
     scene(seed, planar, 900, 850, 400, f1, f2, m12);
     // the drop-in: its draws move the process's rand() stream
     srand(12345 + seed);
-    imock::Random::seeded() = false;                       // (a fresh process: SeedRandOnce(0) seeds)
-    iORB_SLAM::InitializerT<imock::Frame, imock::Mat, imock::Point3f, imock::Random, kHF> ini(f1, 1.0, 200);
-    imock::Mat R21, t21;
+    Random::seeded() = false;                       // (a fresh process: SeedRandOnce(0) seeds)
+    iORB_SLAM::InitializerT<imock::Frame, Mat32, imock::Point3f, Random, kHF> ini(f1, 1.0, 200);
+    Mat32 R21, t21;
     std::vector<imock::Point3f> P;
     std::vector<bool> tri;
     const bool ok = ini.Initialize(f2, m12, R21, t21, P, tri);
@@ -92,8 +77,8 @@ static int run_case(unsigned seed, bool planar)
     std::vector<float> rP;
     std::vector<uint8_t> rT;
     const bool rok = ref.Initialize(k2, m12, sets, res, rP, rT);
-    int bad = 0;
-#define EXPECT(c) do { if (!(c)) { printf("seed %u planar %d hf %d: %s failed\n", seed, (int)planar, (int)kHF, #c); bad++; } } while (0)
+    const int before = fails;
+#define EXPECT(c) CHECKF(c, "seed %u planar %d hf %d", seed, (int)planar, (int)kHF)
     EXPECT(nextAfterDropin == nextAfterRef);
     EXPECT(ok == rok);
     EXPECT(std::memcmp(&ini.lastResult(), &res, sizeof res) == 0);
@@ -101,14 +86,15 @@ static int run_case(unsigned seed, bool planar)
         EXPECT(R21.rows == 3 && t21.rows == 3);
         EXPECT(std::memcmp(R21.d.data(), res.R21, 36) == 0 && std::memcmp(t21.d.data(), res.t21, 12) == 0);
         EXPECT(P.size() == f1.mvKeysUn.size() && tri.size() == f1.mvKeysUn.size());
-        for (size_t i = 0; i < P.size() && !bad; i++) {
+        for (size_t i = 0; i < P.size() && fails == before; i++) {
             EXPECT(std::memcmp(&P[i].x, &rP[3 * i], 4) == 0 && std::memcmp(&P[i].y, &rP[3 * i + 1], 4) == 0 && std::memcmp(&P[i].z, &rP[3 * i + 2], 4) == 0);
             EXPECT(tri[i] == (rT[i] != 0));
         }
     } else if (res.rtState == 1)
         EXPECT(R21.rows == 0 && t21.rows == 0);
     printf("seed %u planar %d hf %d: ok %d reconH %d nGood best %d\n", seed, (int)planar, (int)kHF, (int)ok, res.reconH, res.best >= 0 ? res.nGood[res.best] : -1);
-    return bad;
+    return fails - before;
+#undef EXPECT
 }
 
 int main()

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "KeyFrameDatabase_hip.hpp"
+#include "dropin_test.hpp"
 #include "../../tools/kfdb_ref.hpp"
 
 namespace kfmock {
@@ -60,8 +61,6 @@ std::vector<KeyFrame*> KeyFrame::GetBestCovisibilityKeyFrames(const int& N)
 template class orbslamm_hip::KeyFrameDatabaseT<kfmock::KeyFrame, kfmock::Frame>;
 template class orbslamm_hip::ORBVocabularyScoreT<kfmock::BowVector>;
 
-static int fails = 0;
-#define EXPECT(c, ...) do { if (!(c)) { fails++; printf("FAIL %s:%d ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } while (0)
 
 static std::vector<int> idx_of(const std::vector<kfmock::KeyFrame*>& v)
 {
@@ -133,7 +132,7 @@ int main()
             F.mBowVec = make_bow(rng() % PLACES);
             const std::vector<int> a = idx_of(dbs[d]->DetectRelocalizationCandidates(&F));
             const std::vector<int> b = idx_of(rdbs[d]->DetectRelocalizationCandidates(&F));
-            EXPECT(a == b, "step %d: relocalisation candidates differ (%zu vs %zu)", step, a.size(), b.size());
+            CHECKF(a == b, "step %d: relocalisation candidates differ (%zu vs %zu)", step, a.size(), b.size());
             nReloc++; nCand += (int)b.size();
         } else {
             const float minScore = (rng() % 100) / 1000.f;
@@ -141,10 +140,10 @@ int main()
             dev.kfs[k].mnId = ref.kfs[k].mnId = id;
             const std::vector<int> a = idx_of(dbs[d]->DetectLoopCandidates(&dev.kfs[k], minScore));
             const std::vector<int> b = idx_of(rdbs[d]->DetectLoopCandidates(&ref.kfs[k], minScore));
-            EXPECT(a == b, "step %d: loop candidates differ (%zu vs %zu)", step, a.size(), b.size());
+            CHECKF(a == b, "step %d: loop candidates differ (%zu vs %zu)", step, a.size(), b.size());
             nLoop++; nCand += (int)b.size();
         }
-        EXPECT(dbs[d]->size() == rdbs[d]->size() && dbs[d]->empty() == rdbs[d]->empty(), "step %d: size", step);
+        CHECKF(dbs[d]->size() == rdbs[d]->size() && dbs[d]->empty() == rdbs[d]->empty(), "step %d: size", step);
         if (fails > 10) break;
     }
     orbslamm_hip::ORBVocabularyScoreT<kfmock::BowVector> sc(voc);
@@ -152,7 +151,7 @@ int main()
         const kfmock::BowVector& a = bows[rng() % NKF];
         const kfmock::BowVector& b = bows[rng() % NKF];
         const double x = sc.score(a, b), y = kfdb_ref::l1_score(a, b);
-        EXPECT(memcmp(&x, &y, 8) == 0, "score %d: %.17g vs %.17g", i, x, y);
+        CHECKF(memcmp(&x, &y, 8) == 0, "score %d: %.17g vs %.17g", i, x, y);
     }
     {
         DB::Pool cpool(voc);
@@ -183,8 +182,8 @@ int main()
             }
         });
         ta.join(); tb.join(); tc.join();
-        EXPECT(foreign == 0, "%d candidates outside the world", foreign.load());
-        EXPECT(c0.size() == 100 && c1.size() == 200, "concurrent sizes %d %d", c0.size(), c1.size());
+        CHECKF(foreign == 0, "%d candidates outside the world", foreign.load());
+        CHECKF(c0.size() == 100 && c1.size() == 200, "concurrent sizes %d %d", c0.size(), c1.size());
         printf("concurrent: %d queries, %d candidates\n", nConc.load(), nConcCand.load());
     }
     orbv_destroy(voc);

@@ -9,16 +9,12 @@
 
 #include "Tracking_hip.hpp"
 #include "mock_tracking.hpp"
+#include "dropin_test.hpp"
 
 using tmock::Frame;
 using tmock::MapPoint;
 using mock::KeyPoint;
 using mock::Mat;
-
-#define OX(call)                                                                               \
-    do {                                                                                       \
-        if ((call) != ORBX_OK) { fprintf(stderr, "%s: %s\n", #call, orbx_last_error()); return 2; } \
-    } while (0)
 
 static const int W = 640, H = 480, NLEVELS = 8, TH_HIGH = 100;
 

@@ -14,16 +14,12 @@
 
 #include "Tracking_hip.hpp"
 #include "mock_localmap_update.hpp"
+#include "dropin_test.hpp"
 
 using umock::Frame;
 using umock::KeyFrame;
 using umock::MapPoint;
 using namespace std;
-
-#define OX(call)                                                                               \
-    do {                                                                                       \
-        if ((call) != ORBX_OK) { fprintf(stderr, "%s: %s\n", #call, orbx_last_error()); return 2; } \
-    } while (0)
 
 struct Tracking {
     Frame mCurrentFrame;

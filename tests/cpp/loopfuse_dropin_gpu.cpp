@@ -16,15 +16,13 @@
 
 #include "LoopClosing_hip.hpp"
 #include "mock_loopfuse.hpp"
+#include "dropin_test.hpp"
 #include "../../tools/loopfuse_ref.hpp"
 
 typedef iORB_SLAM::SearchAndFuseT<lmock::KeyFrame, lmock::MapPoint, lmock::Mat> LoopFuse;
 namespace lr = loopfuse_ref;
 
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { if (fails < 20) printf("FAILED %s (line %d)\n", #c, __LINE__); fails++; } } while (0)
 
-template <class T> static void rd(FILE* f, T* p, size_t n) { if (n && fread(p, sizeof(T), n, f) != n) { printf("short scene file\n"); exit(2); } }
 
 struct KfData { lr::Target rec; std::vector<lr::KeyPt> keys; std::vector<uint8_t> desc; };
 struct Scene {

@@ -14,13 +14,12 @@
 
 #include "ORBmatcher_hip.hpp"
 #include "mock_slam.hpp"
+#include "dropin_test.hpp"
 #include "../../oracle/orb_oracle.h"
 
 using namespace mock;
 typedef iORB_SLAM::ORBmatcherT<Frame, KeyFrame, MapPoint> ORBmatcher;  // the typedef INTEGRATION.md asks the maintainer for
 
-static int fails = 0;
-#define EXPECT(c) do { if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); fails++; } } while (0)
 
 static const int W = 640, H = 480, NLEVELS = 8;
 static const float FX = 520.f, FY = 515.f, CX = 318.f, CY = 243.f, SCALE = 1.2f;
@@ -248,10 +247,10 @@ static void check_projection(const ORBmatcher::FlatCall& c, float nnratio, bool 
     const int n = orc_search_by_projection_stereo(&pp, c.q_uvr.data(), stereo ? c.q_ur.data() : nullptr, c.q_lvl.data(), c.qdesc.data(), c.qangle.data(),
                                                   nullptr, c.qobs.data(), c.nq, &G.gp, (const OrcKeyPoint*)c.tkeys, G.start.data(), G.idx.data(),
                                                   c.tdesc, c.turight, c.nt, occ.data(), assignOut.data());
-    EXPECT(n == c.nmatches);
-    EXPECT(assignOut == c.assign);
-    EXPECT(occ == c.tocc);
-    EXPECT((int)c.q_uvr.size() == 3 * c.nq && (int)c.qdesc.size() == 32 * c.nq && (int)c.qidx.size() == c.nq);
+    CHECK(n == c.nmatches);
+    CHECK(assignOut == c.assign);
+    CHECK(occ == c.tocc);
+    CHECK((int)c.q_uvr.size() == 3 * c.nq && (int)c.qdesc.size() == 32 * c.nq && (int)c.qidx.size() == c.nq);
 }
 static void check_window(const ORBmatcher::FlatCall& c, const std::vector<float>& invSigma2, std::vector<int32_t>& bi, std::vector<int32_t>& bd)
 {
@@ -260,8 +259,8 @@ static void check_window(const ORBmatcher::FlatCall& c, const std::vector<float>
     orc_window_best(c.q_uvr.data(), c.chi2 ? c.q_ur.data() : nullptr, c.q_pred.data(), c.qdesc.data(), nullptr, c.nq, &G.gp, (const OrcKeyPoint*)c.tkeys,
                     G.start.data(), G.idx.data(), c.tdesc, c.chi2 ? c.turight : nullptr, c.nt, invSigma2.data(), c.chi2, bi.data(), bd.data());
     bi.resize(c.nq); bd.resize(c.nq);
-    EXPECT(bi == c.bestIdx);
-    EXPECT(bd == c.bestDist);
+    CHECK(bi == c.bestIdx);
+    CHECK(bd == c.bestDist);
 }
 
 // deep copy of the world's object graph (ids keep their meaning) for replaying write-backs
@@ -354,20 +353,20 @@ int main(int argc, char** argv)
         const ORBmatcher::FlatCall& c = m.last();
         std::vector<int32_t> as;
         check_projection(c, 0.8f, true, as);
-        EXPECT(c.nq == expectQueries && c.mode == 3 && c.thDist == 100 && n == c.nmatches && SC(n > 250));
-        EXPECT((c.turight != nullptr) == stereo);
+        CHECK(c.nq == expectQueries && c.mode == 3 && c.thDist == 100 && n == c.nmatches && SC(n > 250));
+        CHECK((c.turight != nullptr) == stereo);
         for (int q = 0; q < c.nq; q++) {  // (3) the flattening
             MapPoint* p = vp[c.qidx[q]];
             const float r = (p->mTrackViewCos > 0.998 ? 2.5f : 4.0f) * (th != 1.0f ? th : 1.0f);
-            EXPECT(c.q_uvr[3 * q] == p->mTrackProjX && c.q_uvr[3 * q + 1] == p->mTrackProjY && c.q_uvr[3 * q + 2] == r * w.scaleFactors[p->mnTrackScaleLevel]);
-            EXPECT(c.q_lvl[2 * q] == p->mnTrackScaleLevel - 1 && c.q_lvl[2 * q + 1] == p->mnTrackScaleLevel);
-            EXPECT(std::memcmp(&c.qdesc[(size_t)q * 32], p->mDescriptor.ptr<uint8_t>(0), 32) == 0 && c.qobs[q] == (p->Observations() > 0));
-            if (q) EXPECT(c.qidx[q] > c.qidx[q - 1]);
+            CHECK(c.q_uvr[3 * q] == p->mTrackProjX && c.q_uvr[3 * q + 1] == p->mTrackProjY && c.q_uvr[3 * q + 2] == r * w.scaleFactors[p->mnTrackScaleLevel]);
+            CHECK(c.q_lvl[2 * q] == p->mnTrackScaleLevel - 1 && c.q_lvl[2 * q + 1] == p->mnTrackScaleLevel);
+            CHECK(std::memcmp(&c.qdesc[(size_t)q * 32], p->mDescriptor.ptr<uint8_t>(0), 32) == 0 && c.qobs[q] == (p->Observations() > 0));
+            if (q) CHECK(c.qidx[q] > c.qidx[q - 1]);
         }
         for (int t = 0; t < F.N; t++) {   // (2) the write-back (:123)
             MapPoint* want = as[t] >= 0 ? vp[c.qidx[as[t]]] : before[t];
-            EXPECT(F.mvpMapPoints[t] == want);
-            EXPECT(c.tocc_in[t] == (before[t] && before[t]->Observations() > 0));
+            CHECK(F.mvpMapPoints[t] == want);
+            CHECK(c.tocc_in[t] == (before[t] && before[t]->Observations() > 0));
         }
         for (size_t j = 0; j < w.mps.size(); j++) w.mps[j]->mbBad = false;
         std::printf("1.%d SearchByProjection(Frame, MapPoints, th=%g%s): %d queries, %d matches\n", variant, th, stereo ? ", stereo" : "", c.nq, n);
@@ -397,32 +396,32 @@ int main(int argc, char** argv)
         const ORBmatcher::FlatCall& c = m.last();
         std::vector<int32_t> as;
         check_projection(c, 0.9f, true, as);
-        EXPECT(c.mode == 4 && c.thDist == 100 && n == c.nmatches && SC(n > 150) && SC(c.nq > 300) && c.nq <= nLastPts);
-        EXPECT((c.turight != nullptr) == !bMono);
+        CHECK(c.mode == 4 && c.thDist == 100 && n == c.nmatches && SC(n > 150) && SC(c.nq > 300) && c.nq <= nLastPts);
+        CHECK((c.turight != nullptr) == !bMono);
         // the camera's motion along the last frame's optical axis against the baseline mb (:1349-1350); Last sits at the origin
         double Oc[3]; cam_center(Pc, Oc);
         const bool fwd = !bMono && Oc[2] > Cur.mb, bwd = !bMono && -Oc[2] > Cur.mb;
-        EXPECT(variant == 0 ? (!fwd && !bwd) : (variant == 1 ? bwd : fwd));
+        CHECK(variant == 0 ? (!fwd && !bwd) : (variant == 1 ? bwd : fwd));
         int pruned = 0;
         for (int q = 0; q < c.nq; q++) {
             const int i = c.qidx[q];
             const int j = Last.mvpMapPoints[i]->id;
             double u, v, z;
             project(Pc, &w.X[3 * j], u, v, z);   // independent projection, double precision
-            EXPECT(std::fabs(c.q_uvr[3 * q] - u) < 2e-2 && std::fabs(c.q_uvr[3 * q + 1] - v) < 2e-2);
+            CHECK(std::fabs(c.q_uvr[3 * q] - u) < 2e-2 && std::fabs(c.q_uvr[3 * q + 1] - v) < 2e-2);
             const int oct = Last.mvKeys[i].octave;
-            EXPECT(c.q_uvr[3 * q + 2] == th * w.scaleFactors[oct] && !Last.mvbOutlier[i] && c.qangle[q] == Last.mvKeysUn[i].angle);
-            if (fwd) EXPECT(c.q_lvl[2 * q] == oct && c.q_lvl[2 * q + 1] == -1);            // GetFeaturesInArea(u, v, radius, nLastOctave)
-            else if (bwd) EXPECT(c.q_lvl[2 * q] == 0 && c.q_lvl[2 * q + 1] == oct);       // (.., 0, nLastOctave)
-            else EXPECT(c.q_lvl[2 * q] == oct - 1 && c.q_lvl[2 * q + 1] == oct + 1);
-            if (!bMono) EXPECT(std::fabs(c.q_ur[q] - (u - 40.0 / z)) < 2e-2);
+            CHECK(c.q_uvr[3 * q + 2] == th * w.scaleFactors[oct] && !Last.mvbOutlier[i] && c.qangle[q] == Last.mvKeysUn[i].angle);
+            if (fwd) CHECK(c.q_lvl[2 * q] == oct && c.q_lvl[2 * q + 1] == -1);            // GetFeaturesInArea(u, v, radius, nLastOctave)
+            else if (bwd) CHECK(c.q_lvl[2 * q] == 0 && c.q_lvl[2 * q + 1] == oct);       // (.., 0, nLastOctave)
+            else CHECK(c.q_lvl[2 * q] == oct - 1 && c.q_lvl[2 * q + 1] == oct + 1);
+            if (!bMono) CHECK(std::fabs(c.q_ur[q] - (u - 40.0 / z)) < 2e-2);
         }
         for (int t = 0; t < Cur.N; t++) {   // :1430 and the pruning :1462
             MapPoint* want = as[t] >= 0 ? Last.mvpMapPoints[c.qidx[as[t]]] : (as[t] == -1 ? nullptr : before[t]);
-            EXPECT(Cur.mvpMapPoints[t] == want);
+            CHECK(Cur.mvpMapPoints[t] == want);
             pruned += as[t] == -1;
         }
-        EXPECT(SC(pruned > 0));
+        CHECK(SC(pruned > 0));
         std::printf("2.%d SearchByProjection(Cur, Last, th=%g, bMono=%d): %d queries, %d matches, %d pruned by rotation\n", variant, th, (int)bMono, c.nq, n, pruned);
     }
 
@@ -441,18 +440,18 @@ int main(int argc, char** argv)
         const ORBmatcher::FlatCall& c = m.last();
         std::vector<int32_t> as;
         check_projection(c, 0.9f, true, as);
-        EXPECT(c.mode == 5 && c.thDist == ORBdist && n == c.nmatches && SC(n > 100));
+        CHECK(c.mode == 5 && c.thDist == ORBdist && n == c.nmatches && SC(n > 100));
         for (int q = 0; q < c.nq; q++) {
             MapPoint* p = kf0->mvpMapPoints[c.qidx[q]];
-            EXPECT(p && !found.count(p) && c.qangle[q] == kf0->mvKeysUn[c.qidx[q]].angle);
+            CHECK(p && !found.count(p) && c.qangle[q] == kf0->mvKeysUn[c.qidx[q]].angle);
             double u, v, z; project(P1, &w.X[3 * p->id], u, v, z);
-            EXPECT(std::fabs(c.q_uvr[3 * q] - u) < 2e-2 && std::fabs(c.q_uvr[3 * q + 1] - v) < 2e-2);
-            EXPECT(c.q_lvl[2 * q + 1] - c.q_lvl[2 * q] == 2);
+            CHECK(std::fabs(c.q_uvr[3 * q] - u) < 2e-2 && std::fabs(c.q_uvr[3 * q + 1] - v) < 2e-2);
+            CHECK(c.q_lvl[2 * q + 1] - c.q_lvl[2 * q] == 2);
         }
         for (int t = 0; t < Cur.N; t++) {
             MapPoint* want = as[t] >= 0 ? kf0->mvpMapPoints[c.qidx[as[t]]] : (as[t] == -1 ? nullptr : before[t]);
-            EXPECT(Cur.mvpMapPoints[t] == want);
-            EXPECT(c.tocc_in[t] == (before[t] != nullptr));
+            CHECK(Cur.mvpMapPoints[t] == want);
+            CHECK(c.tocc_in[t] == (before[t] != nullptr));
         }
         std::printf("3.%d SearchByProjection(Cur, KF, found, th=%g, ORBdist=%d): %d queries, %d matches\n", variant, th, ORBdist, c.nq, n);
     }
@@ -472,16 +471,16 @@ int main(int argc, char** argv)
         const ORBmatcher::FlatCall& c = m.last();
         std::vector<int32_t> as;
         check_projection(c, 0.75f, true, as);
-        EXPECT(c.mode == 6 && c.thDist == 50 && n == c.nmatches && SC(n > 200));
+        CHECK(c.mode == 6 && c.thDist == 50 && n == c.nmatches && SC(n > 200));
         std::set<MapPoint*> already(before.begin(), before.end());
         for (int q = 0; q < c.nq; q++) {
             MapPoint* p = vpPoints[c.qidx[q]];
-            EXPECT(!already.count(p));
+            CHECK(!already.count(p));
             double u, v, z; project(P1, &w.X[3 * p->id], u, v, z);    // Scw / scw is the plain pose again
-            EXPECT(std::fabs(c.q_uvr[3 * q] - u) < 5e-2 && std::fabs(c.q_uvr[3 * q + 1] - v) < 5e-2);
-            EXPECT(c.q_lvl[2 * q + 1] - c.q_lvl[2 * q] == 1);
+            CHECK(std::fabs(c.q_uvr[3 * q] - u) < 5e-2 && std::fabs(c.q_uvr[3 * q + 1] - v) < 5e-2);
+            CHECK(c.q_lvl[2 * q + 1] - c.q_lvl[2 * q] == 1);
         }
-        for (int t = 0; t < kf1->N; t++) EXPECT(vpMatched[t] == (as[t] >= 0 ? vpPoints[c.qidx[as[t]]] : before[t]));
+        for (int t = 0; t < kf1->N; t++) CHECK(vpMatched[t] == (as[t] >= 0 ? vpPoints[c.qidx[as[t]]] : before[t]));
         std::printf("4   SearchByProjection(KF, Scw, points, matched, 10): %d queries, %d matches\n", c.nq, n);
     }
 
@@ -498,14 +497,14 @@ int main(int argc, char** argv)
         OrcFeatVec a = ofv(c.qfv), b = ofv(c.tfv);
         const int on = orc_search_by_bow(kf0->mDescriptors.ptr<uint8_t>(0), c.qangle.data(), c.qvalid.data(), c.nq, &a, F.mDescriptors.ptr<uint8_t>(0),
                                          c.tangle.data(), nullptr, c.nt, &b, 0.7f, 1, 1, om.data());
-        EXPECT(on == n && SC(n > 150) && (int)out.size() == F.N && om == c.match);
-        for (int i = 0; i < c.nq; i++) EXPECT(c.qvalid[i] == (kf0->mvpMapPoints[i] && !kf0->mvpMapPoints[i]->mbBad) && c.qangle[i] == kf0->mvKeysUn[i].angle);
+        CHECK(on == n && SC(n > 150) && (int)out.size() == F.N && om == c.match);
+        for (int i = 0; i < c.nq; i++) CHECK(c.qvalid[i] == (kf0->mvpMapPoints[i] && !kf0->mvpMapPoints[i]->mbBad) && c.qangle[i] == kf0->mvKeysUn[i].angle);
         int right = 0;
         for (int t = 0; t < F.N; t++) {
-            EXPECT(out[t] == (om[t] >= 0 ? kf0->mvpMapPoints[om[t]] : nullptr));
+            CHECK(out[t] == (om[t] >= 0 ? kf0->mvpMapPoints[om[t]] : nullptr));
             right += out[t] && owner[t] >= 0 && w.origin[owner[t]] == w.origin[out[t]->id];
         }
-        EXPECT(SC(right > n * 8 / 10));   // the scenario is meaningful: matches are mostly the true correspondences (twins sit on unrelated features of kf0)
+        CHECK(SC(right > n * 8 / 10));   // the scenario is meaningful: matches are mostly the true correspondences (twins sit on unrelated features of kf0)
         w.mps[5]->mbBad = false; w.mps[77]->mbBad = false;
         std::printf("5   SearchByBoW(KF, Frame): %d matches (%d true correspondences)\n", n, right);
     }
@@ -520,9 +519,9 @@ int main(int argc, char** argv)
         OrcFeatVec a = ofv(c.qfv), b = ofv(c.tfv);
         const int on = orc_search_by_bow(kf0->mDescriptors.ptr<uint8_t>(0), c.qangle.data(), c.qvalid.data(), c.nq, &a, kf1->mDescriptors.ptr<uint8_t>(0),
                                          c.tangle.data(), c.tvalid.data(), c.nt, &b, 0.8f, 1, 0, om.data());
-        EXPECT(on == n && SC(n > 100) && (int)out.size() == kf0->N && om == c.match);
-        for (int i = 0; i < c.nt; i++) EXPECT(c.tvalid[i] == (kf1->mvpMapPoints[i] && !kf1->mvpMapPoints[i]->mbBad));
-        for (int i = 0; i < kf0->N; i++) EXPECT(out[i] == (om[i] >= 0 ? kf1->mvpMapPoints[om[i]] : nullptr));
+        CHECK(on == n && SC(n > 100) && (int)out.size() == kf0->N && om == c.match);
+        for (int i = 0; i < c.nt; i++) CHECK(c.tvalid[i] == (kf1->mvpMapPoints[i] && !kf1->mvpMapPoints[i]->mbBad));
+        for (int i = 0; i < kf0->N; i++) CHECK(out[i] == (om[i] >= 0 ? kf1->mvpMapPoints[om[i]] : nullptr));
         w.mps[9]->mbBad = false;
         std::printf("6   SearchByBoW(KF, KF): %d matches\n", n);
     }
@@ -542,11 +541,11 @@ int main(int argc, char** argv)
         std::vector<int32_t> om(F1.N, -1);
         const int on = orc_search_for_initialization(c.q_xy.data(), 100.f, (const OrcKeyPoint*)c.qkeys, F1.mDescriptors.ptr<uint8_t>(0), c.nq, &G.gp,
                                                      (const OrcKeyPoint*)c.tkeys, G.start.data(), G.idx.data(), F2.mDescriptors.ptr<uint8_t>(0), c.nt, 0.9f, 1, om.data());
-        EXPECT(on == n && SC(n > 40) && (int)m12.size() == F1.N);
+        CHECK(on == n && SC(n > 40) && (int)m12.size() == F1.N);
         for (int i = 0; i < F1.N; i++) {
-            EXPECT(m12[i] == om[i]);
-            if (m12[i] >= 0) EXPECT(prev[i].x == F2.mvKeysUn[m12[i]].pt.x && prev[i].y == F2.mvKeysUn[m12[i]].pt.y);  // :517-519
-            else EXPECT(prev[i].x == prev0[i].x && prev[i].y == prev0[i].y);
+            CHECK(m12[i] == om[i]);
+            if (m12[i] >= 0) CHECK(prev[i].x == F2.mvKeysUn[m12[i]].pt.x && prev[i].y == F2.mvKeysUn[m12[i]].pt.y);  // :517-519
+            else CHECK(prev[i].x == prev0[i].x && prev[i].y == prev0[i].y);
         }
         std::printf("7   SearchForInitialization: %d matches\n", n);
     }
@@ -576,12 +575,12 @@ int main(int argc, char** argv)
         const int on = orc_search_for_triangulation((const OrcKeyPoint*)c.qkeys, A->mDescriptors.ptr<uint8_t>(0), c.skip1.data(), A->mvuRight.data(), A->N, &a,
                                                     (const OrcKeyPoint*)c.tkeys, B->mDescriptors.ptr<uint8_t>(0), c.skip2.data(), B->mvuRight.data(), B->N, &b,
                                                     c.F12.data(), c.ex, c.ey, B->mvScaleFactors.data(), B->mvLevelSigma2.data(), 0, variant == 0, om.data());
-        EXPECT(on == n && SC(n > 20) && (int)pairs.size() == n);
+        CHECK(on == n && SC(n > 20) && (int)pairs.size() == n);
         size_t k = 0;
-        for (int i = 0; i < A->N; i++) if (om[i] >= 0) { EXPECT(k < pairs.size() && pairs[k].first == (size_t)i && pairs[k].second == (size_t)om[i]); k++; }
-        for (int i = 0; i < A->N; i++) EXPECT(c.skip1[i] == (A->mvpMapPoints[i] != nullptr));
+        for (int i = 0; i < A->N; i++) if (om[i] >= 0) { CHECK(k < pairs.size() && pairs[k].first == (size_t)i && pairs[k].second == (size_t)om[i]); k++; }
+        for (int i = 0; i < A->N; i++) CHECK(c.skip1[i] == (A->mvpMapPoints[i] != nullptr));
         double e[3]; for (int i = 0; i < 3; i++) e[i] = PB.R[3 * i] * OA[0] + PB.R[3 * i + 1] * OA[1] + PB.R[3 * i + 2] * OA[2] + PB.t[i];
-        EXPECT(std::fabs(c.ex - (FX * e[0] / e[2] + CX)) < 0.5 + 1e-3 * std::fabs(c.ex) && std::fabs(c.ey - (FY * e[1] / e[2] + CY)) < 0.5 + 1e-3 * std::fabs(c.ey));
+        CHECK(std::fabs(c.ex - (FX * e[0] / e[2] + CX)) < 0.5 + 1e-3 * std::fabs(c.ex) && std::fabs(c.ey - (FY * e[1] / e[2] + CY)) < 0.5 + 1e-3 * std::fabs(c.ey));
         std::printf("8.%d SearchForTriangulation: %d pairs\n", variant, n);
     }
     // ------------------------------------------------------------ 9. Fuse(KeyFrame*, vector<MapPoint*>&, th)
@@ -598,7 +597,7 @@ int main(int argc, char** argv)
         const ORBmatcher::FlatCall& c = m.last();
         std::vector<int32_t> bi, bd;
         check_window(c, kf->mvInvLevelSigma2, bi, bd);
-        EXPECT(c.chi2 == 1 && c.turight == kf->mvuRight.data());
+        CHECK(c.chi2 == 1 && c.turight == kf->mvuRight.data());
         // (2) the reference's loop :842-972 replayed on the copy with the checker's results
         KeyFrame* skf = sh.kf(kf);
         int q = 0, want = 0, replaced = 0, added = 0;
@@ -615,8 +614,8 @@ int main(int argc, char** argv)
                 want++;
             }
         }
-        EXPECT(q == c.nq && n == want && SC(n > 100) && SC(replaced > 10) && SC(added > 10));
-        EXPECT(same_state(w, sh));
+        CHECK(q == c.nq && n == want && SC(n > 100) && SC(replaced > 10) && SC(added > 10));
+        CHECK(same_state(w, sh));
         w.mps[21]->mbBad = false;
         std::printf("9.%d Fuse(KF, MapPoints, 3): %d queries, %d fused (%d replaced, %d added)\n", variant, c.nq, n, replaced, added);
     }
@@ -639,7 +638,7 @@ int main(int argc, char** argv)
         int want = 0;
         const std::set<MapPoint*> inKF = kf0->GetMapPoints();
         for (int q = 0; q < c.nq; q++) {
-            EXPECT(q == 0 || c.qidx[q] > c.qidx[q - 1]);
+            CHECK(q == 0 || c.qidx[q] > c.qidx[q - 1]);
             if (bd[q] <= 50 && bi[q] >= 0) {
                 MapPoint* p = sh.mp(pts[c.qidx[q]]);
                 MapPoint* in = skf->GetMapPoint(bi[q]);
@@ -648,9 +647,9 @@ int main(int argc, char** argv)
                 want++;
             }
         }
-        EXPECT(n == want && SC(n > 30));
-        for (size_t i = 0; i < pts.size(); i++) EXPECT((repl[i] ? repl[i]->id : -1) == wantRepl[i]);
-        EXPECT(same_state(w, sh));
+        CHECK(n == want && SC(n > 30));
+        for (size_t i = 0; i < pts.size(); i++) CHECK((repl[i] ? repl[i]->id : -1) == wantRepl[i]);
+        CHECK(same_state(w, sh));
         std::printf("10  Fuse(KF, Scw, points, 4, replace): %d queries, %d fused\n", c.nq, n);
     }
     // ------------------------------------------------------------ 11. SearchBySim3
@@ -682,22 +681,22 @@ int main(int argc, char** argv)
         for (int i = 0; i < kf0->N; i++) {
             MapPoint* exp = before[i];
             if (v1[i] >= 0 && v2[v1[i]] == i) { exp = kf1->mvpMapPoints[v1[i]]; want++; }
-            EXPECT(m12[i] == exp);
+            CHECK(m12[i] == exp);
         }
-        EXPECT(n == want && SC(n > 30) && pre == 25);
+        CHECK(n == want && SC(n > 30) && pre == 25);
         for (int q = 0; q < m.last().nq; q++) {
-            EXPECT(!before[m.last().qidx[q]]);
+            CHECK(!before[m.last().qidx[q]]);
             MapPoint* p = kf0->mvpMapPoints[m.last().qidx[q]];
             double u, v, z; project(P1, &w.X[3 * p->id], u, v, z);
-            EXPECT(std::fabs(m.last().q_uvr[3 * q] - u) < 5e-2 && std::fabs(m.last().q_uvr[3 * q + 1] - v) < 5e-2);
+            CHECK(std::fabs(m.last().q_uvr[3 * q] - u) < 5e-2 && std::fabs(m.last().q_uvr[3 * q + 1] - v) < 5e-2);
         }
         std::printf("11  SearchBySim3: %d + %d queries, %d mutual matches\n", m.last().nq, m.last2().nq, n);
     }
     // ------------------------------------------------------------ static DescriptorDistance
     {
         Mat a = w.mps[1]->GetDescriptor(), b = w.mps[2]->GetDescriptor();
-        EXPECT(ORBmatcher::DescriptorDistance(a, b) == orc_descriptor_distance(a.ptr<uint8_t>(0), b.ptr<uint8_t>(0)));
-        EXPECT(ORBmatcher::DescriptorDistance(a, a) == 0);
+        CHECK(ORBmatcher::DescriptorDistance(a, b) == orc_descriptor_distance(a.ptr<uint8_t>(0), b.ptr<uint8_t>(0)));
+        CHECK(ORBmatcher::DescriptorDistance(a, a) == 0);
     }
     if (fails) { std::printf("matcher_dropin_gpu: %d FAILURES\n", fails); return 1; }
     std::printf("matcher_dropin_gpu ok\n");

@@ -7,6 +7,7 @@
 #include <memory>
 #include <vector>
 
+#include "dropin_test.hpp"
 #include "mock_sim3opt.hpp"
 
 namespace cmock {
@@ -22,15 +23,6 @@ struct Pair {
     std::vector<int> true2;          // pKF2's feature of pKF1's feature i
     float R12[9], t12[3], s12;       // the Sim3 a solver would hand over: the truth a little off
 };
-
-inline double urand(unsigned& s) { s = s * 1664525u + 1013904223u; return (s >> 8) / 16777216.0; }
-
-inline void eulerR(double ax, double ay, double az, double R[9])
-{
-    const double cx = cos(ax), sx = sin(ax), cy = cos(ay), sy = sin(ay), cz = cos(az), sz = sin(az);
-    const double M[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
-    for (int k = 0; k < 9; k++) R[k] = M[k];
-}
 
 inline void initKeyFrame(mock::KeyFrame& K, int n, const double R[9], const double t[3])
 {

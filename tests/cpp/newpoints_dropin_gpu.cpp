@@ -13,13 +13,12 @@
 
 #include "LocalMapping_hip.hpp"
 #include "mock_localmap.hpp"
+#include "dropin_test.hpp"
 #include "../../oracle/orb_oracle.h"
 #include "../../tools/newpoints_ref.hpp"
 
 typedef iORB_SLAM::CreateNewMapPointsT<lmock::KeyFrame, lmock::MapPoint, lmock::Map, lmock::Mat> NewPoints;
 
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { printf("FAILED %s (line %d)\n", #c, __LINE__); fails++; } } while (0)
 
 struct SideData {
     int n = 0;
@@ -30,7 +29,6 @@ struct SideData {
     newpoints_ref::KeyFrame kf;
 };
 
-template <class T> static void rd(FILE* f, T* p, size_t n) { if (n && fread(p, sizeof(T), n, f) != n) { printf("short scene file\n"); exit(2); } }
 
 static void readSide(FILE* f, SideData& s)
 {

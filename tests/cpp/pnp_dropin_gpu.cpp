@@ -12,33 +12,17 @@
 
 #include "PnPsolver_hip.hpp"
 #include "mock_slam.hpp"
+#include "dropin_test.hpp"
 #include "../../tools/pnp_ref.hpp"
 
 namespace pmock {
-struct Mat {
-    int rows = 0, cols = 0;
-    std::vector<float> d;
-    Mat() {}
-    Mat(int r, int c, int /*type*/) : rows(r), cols(c), d((size_t)r * c, 0.f) {}
-    bool empty() const { return d.empty(); }
-    template <class T> T& at(int r, int c) { return d[(size_t)r * cols + c]; }
-    template <class T> const T& at(int r, int c) const { return d[(size_t)r * cols + c]; }
-};
-// Thirdparty/DBoW2/DUtils/Random.cpp's RandomInt
-struct Random {
-    static int RandomInt(int min, int max) { const int d = max - min + 1; return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min; }
-};
 // mock::Frame has no mvLevelSigma2 (Frame.h:150); the template binds to it
 struct Frame : mock::Frame {
     std::vector<float> mvLevelSigma2;
 };
 }  // namespace pmock
 
-typedef iORB_SLAM::PnPsolverT<pmock::Frame, mock::MapPoint, pmock::Mat, pmock::Random> Solver;
-
-static double urand(unsigned& s) { s = s * 1664525u + 1013904223u; return (s >> 8) / 16777216.0; }
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { printf("FAILED %s (line %d)\n", #c, __LINE__); fails++; } } while (0)
+typedef iORB_SLAM::PnPsolverT<pmock::Frame, mock::MapPoint, Mat32, Random> Solver;
 
 // the restatement's solver from the same frame, by the reference's walk
 static pnp_ref::PnPsolver* refSolver(const pmock::Frame& F, const std::vector<mock::MapPoint*>& m)
@@ -68,8 +52,8 @@ int main()
     for (int l = 0; l < 8; l++) { F.mvLevelSigma2.push_back(s2); s2 *= 1.44f; }
     // the frame's true pose and the map points its keys see
     const double ax = 0.05, ay = -0.2, az = 0.03, t[3] = {0.3, -0.1, 0.4};
-    const double cx = cos(ax), sx = sin(ax), cy = cos(ay), sy = sin(ay), cz = cos(az), sz = sin(az);
-    const double R[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
+    double R[9];
+    eulerR(ax, ay, az, R);
     std::vector<std::unique_ptr<mock::MapPoint> > pts;
     std::vector<mock::MapPoint*> seen(nkeys);
     for (int i = 0; i < nkeys; i++) {
@@ -144,7 +128,7 @@ int main()
             int nInliers = -1;
             bool bNoMore = false;
             std::vector<bool> vbInliers;
-            pmock::Mat Tcw = list[i]->iterate(5, bNoMore, vbInliers, nInliers);
+            Mat32 Tcw = list[i]->iterate(5, bNoMore, vbInliers, nInliers);
             pnp_ref::Result rr;
             std::vector<uint8_t> rin(nkeys, 0);
             const int rc = refs[i]->iterate(5, rsets[i].data(), (int)rsets[i].size() / 4, rr, rin.data(), nullptr);
@@ -175,7 +159,7 @@ int main()
         a.SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991);
         std::vector<bool> in;
         int n = 0;
-        pmock::Mat T = a.find(in, n);
+        Mat32 T = a.find(in, n);
         srand(5);
         std::unique_ptr<pnp_ref::PnPsolver> r(refSolver(F, matches[2]));
         r->SetRansacParameters(0.99, 10, 300, 4, 0.5f, 5.991f);
@@ -197,7 +181,7 @@ int main()
         std::vector<Out> outs;
         for (int call = 0; call < 41; call++) {
             Out o;
-            pmock::Mat T = call < 40 ? a.iterate(5, o.noMore, o.in, o.n) : a.find(o.in, o.n);
+            Mat32 T = call < 40 ? a.iterate(5, o.noMore, o.in, o.n) : a.find(o.in, o.n);
             if (call == 40) o.noMore = a.lastResult().no_more != 0;
             o.T = T.d; o.its = a.lastResult().iterations;
             outs.push_back(o);

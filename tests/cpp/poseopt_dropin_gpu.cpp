@@ -11,13 +11,11 @@
 
 #include "Optimizer_hip.hpp"
 #include "mock_poseopt.hpp"
+#include "dropin_test.hpp"
 #include "../../tools/poseopt_ref.hpp"
 
 typedef iORB_SLAM::PoseOptimizationT<pomock::Frame, mock::MapPoint> PoseOpt;
 
-static double urand(unsigned& s) { s = s * 1664525u + 1013904223u; return (s >> 8) / 16777216.0; }
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { printf("FAILED %s (line %d)\n", #c, __LINE__); fails++; } } while (0)
 
 struct Scene {
     pomock::Frame F;
@@ -37,8 +35,8 @@ static void makeScene(Scene& S, unsigned seed, int nkeys, int every, int limit, 
     float s2 = 1.f;
     for (int l = 0; l < 8; l++) { F.mvInvLevelSigma2.push_back(1.f / s2); s2 *= 1.44f; }
     const double ax = 0.05 + 0.1 * urand(s), ay = -0.2, az = 0.03, t[3] = {0.3, -0.1, 0.4};
-    const double cx = cos(ax), sx = sin(ax), cy = cos(ay), sy = sin(ay), cz = cos(az), sz = sin(az);
-    const double R[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
+    double R[9];
+    eulerR(ax, ay, az, R);
     for (int i = 0; i < nkeys; i++) {
         const double z = 3 + 5 * urand(s), Xc[3] = {(-0.4 + 0.8 * urand(s)) * z, (-0.3 + 0.6 * urand(s)) * z, z};
         F.mvKeysUn[i].octave = (int)(urand(s) * 8) % 8;
@@ -55,9 +53,8 @@ static void makeScene(Scene& S, unsigned seed, int nkeys, int every, int limit, 
         F.mvpMapPoints[i] = S.pts.back().get();
     }
     // the start pose: the true one, a little off
-    const double bx = ax + 0.02, by = ay - 0.015;
-    const double c2x = cos(bx), s2x = sin(bx), c2y = cos(by), s2y = sin(by);
-    const double Rs[9] = {cz * c2y, cz * s2y * s2x - sz * c2x, cz * s2y * c2x + sz * s2x, sz * c2y, sz * s2y * s2x + cz * c2x, sz * s2y * c2x - cz * s2x, -s2y, c2y * s2x, c2y * c2x};
+    double Rs[9];
+    eulerR(ax + 0.02, ay - 0.015, az, Rs);
     for (int r = 0; r < 3; r++) {
         for (int c = 0; c < 3; c++) F.mTcw.at<float>(r, c) = (float)Rs[3 * r + c];
         F.mTcw.at<float>(r, 3) = (float)(t[r] + 0.03 * (r - 1));

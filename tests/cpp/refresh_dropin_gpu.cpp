@@ -15,6 +15,7 @@
 
 #include "MapPoint_hip.hpp"
 #include "mock_refresh.hpp"
+#include "dropin_test.hpp"
 
 using rmock::KeyFrame;
 using rmock::MapPoint;
@@ -23,16 +24,7 @@ static uint32_t g_rng = 12345u;
 static uint32_t rnd() { g_rng = g_rng * 1664525u + 1013904223u; return g_rng >> 8; }
 static float rndf(float lo, float hi) { return lo + (hi - lo) * (float)(rnd() % 10000) / 10000.f; }
 
-#define CHECK(expr) do { if (!(expr)) { std::printf("FAILED %s (line %d): %s\n", #expr, __LINE__, orbx_last_error()); return 1; } } while (0)
-
 // ---- the two members, serially, on the mocks
-static int DescriptorDistance(const uint8_t* a, const uint8_t* b)
-{
-    int d = 0;
-    for (int k = 0; k < 32; k++) d += __builtin_popcount((unsigned)(a[k] ^ b[k]));
-    return d;
-}
-
 static void ComputeDistinctiveDescriptors(MapPoint* p)
 {
     if (p->mbBad) return;                                                     // :251
@@ -44,7 +36,7 @@ static void ComputeDistinctiveDescriptors(MapPoint* p)
     const size_t N = vDescriptors.size();
     std::vector<float> Distances(N * N, 0.f);
     for (size_t i = 0; i < N; i++)
-        for (size_t j = i + 1; j < N; j++) Distances[i * N + j] = Distances[j * N + i] = (float)DescriptorDistance(vDescriptors[i], vDescriptors[j]);
+        for (size_t j = i + 1; j < N; j++) Distances[i * N + j] = Distances[j * N + i] = (float)descriptorDistance(vDescriptors[i], vDescriptors[j]);
     int BestMedian = INT_MAX, BestIdx = 0;
     for (size_t i = 0; i < N; i++) {
         std::vector<int> vDists(Distances.begin() + (long)(i * N), Distances.begin() + (long)(i * N + N));
@@ -145,9 +137,9 @@ int main()
     orbm_t* h = nullptr;
     orbw_pool_t* pool = nullptr;
     orbu_store_t* store = nullptr;
-    CHECK(orbm_create(0, &h) == ORBX_OK);
-    CHECK(orbw_pool_create(h, NPT, &pool) == ORBX_OK);
-    CHECK(orbu_store_create(pool, NKF, NF, 4, NKF * NF, &store) == ORBX_OK);
+    REQUIRE(orbm_create(0, &h) == ORBX_OK);
+    REQUIRE(orbw_pool_create(h, NPT, &pool) == ORBX_OK);
+    REQUIRE(orbu_store_create(pool, NKF, NF, 4, NKF * NF, &store) == ORBX_OK);
     std::vector<int32_t> ids((size_t)NPT);
     std::vector<OrbwPoint> recs((size_t)NPT);
     for (int p = 0; p < NPT; p++) {
@@ -160,7 +152,7 @@ int main()
         std::memcpy(r.desc, P.mDescriptor, 32);
         r.flags = (uint8_t)((P.mbBad ? ORBW_FLAG_BAD : 0) | (P.mObservations.empty() ? 0 : ORBW_FLAG_OBSERVED));
     }
-    CHECK(orbw_pool_set(pool, ids.data(), recs.data(), NPT) == ORBX_OK);
+    REQUIRE(orbw_pool_set(pool, ids.data(), recs.data(), NPT) == ORBX_OK);
     std::vector<int32_t> slots((size_t)NKF), nent((size_t)NKF, NF), entries, neigh((size_t)NKF * ORBU_MAX_NEIGHBOURS, -1), parent((size_t)NKF, -1), nch((size_t)NKF, 0);
     std::vector<uint8_t> flags((size_t)NKF);
     std::vector<float> centres;
@@ -172,14 +164,14 @@ int main()
     OrbuKeyFrames rec;
     rec.nkf = NKF; rec.slot = slots.data(); rec.flags = flags.data(); rec.n = nent.data(); rec.entries = entries.data(); rec.neigh = neigh.data();
     rec.parent = parent.data(); rec.nchildren = nch.data(); rec.children = nullptr;
-    CHECK(orbu_kf_set(store, &rec) == ORBX_OK);
+    REQUIRE(orbu_kf_set(store, &rec) == ORBX_OK);
     for (int k = 0; k < NKF; k++) {
         std::vector<uint8_t> oct((size_t)NF);
         for (int i = 0; i < NF; i++) oct[(size_t)i] = (uint8_t)kfs[(size_t)k].mvOctaves[(size_t)i];
-        CHECK(orbu_kf_set_octaves(store, k, oct.data(), NF) == ORBX_OK);
-        CHECK(orbu_kf_set_descriptors(store, k, kfs[(size_t)k].mDescriptors.data(), NF) == ORBX_OK);
+        REQUIRE(orbu_kf_set_octaves(store, k, oct.data(), NF) == ORBX_OK);
+        REQUIRE(orbu_kf_set_descriptors(store, k, kfs[(size_t)k].mDescriptors.data(), NF) == ORBX_OK);
     }
-    CHECK(orbu_kf_set_centres(store, slots.data(), centres.data(), NKF) == ORBX_OK);
+    REQUIRE(orbu_kf_set_centres(store, slots.data(), centres.data(), NKF) == ORBX_OK);
     // ---- round 0: both halves as they stand; round 1: every point moved, normal and depth alone
     Hooks hooks;
     std::vector<MapPoint*> list;
@@ -195,12 +187,12 @@ int main()
         }
         const iORB_SLAM::RefreshMapPointsT<KeyFrame, MapPoint>::Result res =
             iORB_SLAM::RefreshMapPointsT<KeyFrame, MapPoint>::Run(store, list, round == 0 ? ORBR_DESCRIPTOR | ORBR_NORMAL_DEPTH : ORBR_NORMAL_DEPTH, round == 1, sf, hooks);
-        CHECK(res.nUndefined == undefinedHost && undefinedHost > 0);
-        CHECK(res.nNormals > NPT / 2 && (round == 1 || res.nDescriptors > NPT / 2));
+        REQUIRE(res.nUndefined == undefinedHost && undefinedHost > 0);
+        REQUIRE(res.nNormals > NPT / 2 && (round == 1 || res.nDescriptors > NPT / 2));
         for (int p = 0; p < NPT; p++)
             if (!same_members(dev[(size_t)p], host[(size_t)p])) { std::printf("round %d: point %d differs from the members\n", round, p); return 1; }
         std::vector<OrbwPoint> now((size_t)NPT);
-        CHECK(orbw_debug_pool_get(pool, ids.data(), NPT, now.data()) == ORBX_OK);
+        REQUIRE(orbw_debug_pool_get(pool, ids.data(), NPT, now.data()) == ORBX_OK);
         for (int p = 0; p < NPT; p++) {
             const MapPoint& P = dev[(size_t)p];
             const OrbwPoint& r = now[(size_t)p];
@@ -211,8 +203,8 @@ int main()
             }
         }
     }
-    CHECK(orbu_store_destroy(store) == ORBX_OK);
-    CHECK(orbw_pool_destroy(pool) == ORBX_OK);
+    REQUIRE(orbu_store_destroy(store) == ORBX_OK);
+    REQUIRE(orbw_pool_destroy(pool) == ORBX_OK);
     orbm_destroy(h);
     std::printf("refresh drop-in: ok\n");
     return 0;

@@ -11,43 +11,15 @@
 
 #include "Sim3Solver_hip.hpp"
 #include "mock_slam.hpp"
+#include "dropin_test.hpp"
 #include "../../tools/sim3_ref.hpp"
 
-namespace smock {
-struct Mat {
-    int rows = 0, cols = 0;
-    std::vector<float> d;
-    Mat() {}
-    Mat(int r, int c, int /*type*/) : rows(r), cols(c), d((size_t)r * c, 0.f) {}
-    bool empty() const { return d.empty(); }
-    template <class T> T& at(int r, int c) { return d[(size_t)r * cols + c]; }
-    template <class T> const T& at(int r, int c) const { return d[(size_t)r * cols + c]; }
-};
-// Thirdparty/DBoW2/DUtils/Random.cpp's RandomInt
-struct Random {
-    static int RandomInt(int min, int max) { const int d = max - min + 1; return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min; }
-};
-}  // namespace smock
-
-typedef iORB_SLAM::Sim3SolverT<mock::KeyFrame, mock::MapPoint, smock::Mat, smock::Random> Solver;
-
-static double urand(unsigned& s) { s = s * 1664525u + 1013904223u; return (s >> 8) / 16777216.0; }
-static int fails = 0;
-#define CHECK(c) do { if (!(c)) { printf("FAILED %s (line %d)\n", #c, __LINE__); fails++; } } while (0)
+typedef iORB_SLAM::Sim3SolverT<mock::KeyFrame, mock::MapPoint, Mat32, Random> Solver;
 
 struct World {
     std::vector<std::unique_ptr<mock::MapPoint> > pts;
     std::vector<std::unique_ptr<mock::KeyFrame> > kfs;
 };
-
-static void setPose(mock::KeyFrame* kf, double ax, double ay, double az, double tx, double ty, double tz)
-{
-    const double cx = cos(ax), sx = sin(ax), cy = cos(ay), sy = sin(ay), cz = cos(az), sz = sin(az);
-    const double R[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
-    const double t[3] = {tx, ty, tz};
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) kf->Tcw.at<float>(r, c) = (float)R[3 * r + c]; kf->Tcw.at<float>(r, 3) = (float)t[r]; }
-    kf->Tcw.at<float>(3, 3) = 1.f;
-}
 
 static mock::KeyFrame* newKF(World& w, int nkeys, unsigned& s)
 {
@@ -100,7 +72,7 @@ int main()
     World w;
     const int nkeys = 400;
     mock::KeyFrame* cur = newKF(w, nkeys, s);
-    setPose(cur, 0.05, -0.1, 0.02, 0.3, -0.2, 0.5);
+    setPoseEuler(*cur, 0.05, -0.1, 0.02, 0.3, -0.2, 0.5);
     // the current keyframe sees nkeys points of map A; each candidate keyframe lives in map B = a similarity of map A
     std::vector<double> XA((size_t)nkeys * 3);
     for (int i = 0; i < nkeys; i++) {
@@ -121,7 +93,7 @@ int main()
     std::vector<std::vector<mock::MapPoint*> > matched(nCand);
     for (int c = 0; c < nCand; c++) {
         mock::KeyFrame* kf = newKF(w, nkeys, s);
-        setPose(kf, 0.02 * c, 0.3 - 0.1 * c, -0.05, -8.0 + c, 3.0, -1.0 + 0.5 * c);
+        setPoseEuler(*kf, 0.02 * c, 0.3 - 0.1 * c, -0.05, -8.0 + c, 3.0, -1.0 + 0.5 * c);
         cands.push_back(kf);
         matched[c].assign(nkeys, nullptr);
         // candidate c matches 60 + 50 c of the current keyframe's points; the share of wrong matches grows with c; candidate 0
@@ -187,7 +159,7 @@ int main()
                 int nInliers = -1;
                 bool bNoMore = false;
                 std::vector<bool> vbInliers;
-                smock::Mat Scm = list[i]->iterate(5, bNoMore, vbInliers, nInliers);
+                Mat32 Scm = list[i]->iterate(5, bNoMore, vbInliers, nInliers);
                 sim3_ref::Result rr;
                 std::vector<uint8_t> rin(nkeys, 0);
                 refs[i]->iterate(5, rsets[i].data(), rr, rin.data(), nullptr);
@@ -198,7 +170,7 @@ int main()
                 CHECK((int)vbInliers.size() == nkeys);
                 for (int k = 0; k < nkeys; k++) CHECK(vbInliers[k] == (rin[k] != 0));
                 if (!Scm.empty()) CHECK(memcmp(Scm.d.data(), rr.T12, 64) == 0);
-                const smock::Mat R = list[i]->GetEstimatedRotation(), t = list[i]->GetEstimatedTranslation();
+                const Mat32 R = list[i]->GetEstimatedRotation(), t = list[i]->GetEstimatedTranslation();
                 CHECK(R.empty() == (rr.hasBest == 0));
                 if (!R.empty()) {
                     CHECK(memcmp(R.d.data(), rr.bestR, 36) == 0 && memcmp(t.d.data(), rr.bestT, 12) == 0 && t.rows == 3 && t.cols == 1);
@@ -226,7 +198,7 @@ int main()
         a.SetRansacParameters(0.99, 20, 300);
         std::vector<bool> in;
         int n = 0;
-        smock::Mat T = a.find(in, n);
+        Mat32 T = a.find(in, n);
         srand(5);
         std::unique_ptr<sim3_ref::Sim3Solver> r(refSolver(cur, cands[2], matched[2], false));
         r->SetRansacParameters(0.99, 20, 300);

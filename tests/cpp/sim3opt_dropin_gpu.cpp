@@ -11,21 +11,12 @@
 
 #include "Optimizer_hip.hpp"
 #include "mock_sim3opt.hpp"
+#include "dropin_test.hpp"
 #include "../../tools/sim3opt_ref.hpp"
 
 typedef iORB_SLAM::OptimizeSim3T<mock::KeyFrame, mock::MapPoint, s3mock::Sim3> OptSim3;
 
-static double urand(unsigned& s) { s = s * 1664525u + 1013904223u; return (s >> 8) / 16777216.0; }
-static int fails = 0;
 static bool refOnly = false;   // --ref-only: print the restatement's figures for the scenes and touch no GPU
-#define CHECK(c) do { if (!(c)) { printf("FAILED %s (line %d)\n", #c, __LINE__); fails++; } } while (0)
-
-static void eulerR(double ax, double ay, double az, double R[9])
-{
-    const double cx = cos(ax), sx = sin(ax), cy = cos(ay), sy = sin(ay), cz = cos(az), sz = sin(az);
-    const double M[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
-    memcpy(R, M, sizeof M);
-}
 
 struct Scene {
     mock::KeyFrame K1, K2;

@@ -17,6 +17,7 @@
 #include "Tracking_hip.hpp"
 #include "mock_trackpose.hpp"
 #include "ref_tracking_loops.hpp"
+#include "dropin_test.hpp"
 #include "../../tools/poseopt_ref.hpp"
 
 using qmock::Frame;
@@ -25,11 +26,6 @@ using qmock::MapPoint;
 using mock::KeyPoint;
 using mock::Mat;
 using namespace std;
-
-#define OX(call)                                                                               \
-    do {                                                                                       \
-        if ((call) != ORBX_OK) { fprintf(stderr, "%s: %s\n", #call, orbx_last_error()); return 2; } \
-    } while (0)
 
 static const int W = 640, H = 480, NLEVELS = 8, TH_HIGH = refloops::TH_HIGH, CAP = 512, NKF = 3;
 

@@ -15,6 +15,7 @@
 
 #include "Tracking_hip.hpp"
 #include "mock_trackref.hpp"
+#include "dropin_test.hpp"
 #include "../../tools/poseopt_ref.hpp"
 
 using rmock::Frame;
@@ -25,19 +26,7 @@ using mock::KeyPoint;
 using mock::Mat;
 using namespace std;
 
-#define OX(call)                                                                               \
-    do {                                                                                       \
-        if ((call) != ORBX_OK) { fprintf(stderr, "%s: %s\n", #call, orbx_last_error()); return 2; } \
-    } while (0)
-
 static const int W = 640, H = 480, NLEVELS = 8, CAP = 512, TH_LOW = 50, HISTO_LENGTH = 30, VOC_K = 6, LEVELSUP = 1;
-
-static int descriptorDistance(const unsigned char* a, const unsigned char* b)
-{
-    int d = 0;
-    for (int i = 0; i < 32; i++) d += __builtin_popcount((unsigned)(a[i] ^ b[i]));
-    return d;
-}
 
 static void computeThreeMaxima(const vector<int>* histo, int L, int& ind1, int& ind2, int& ind3)   // ORBmatcher.cc:1596-1645
 {

@@ -3,15 +3,18 @@ a small C shim (tests/cpp/fuse_ref_capi.cpp), seeded scene families on 640 x 480
 reference (the restatement's projection, then the oracle's window_best with the chi-square gate) and a float64 numpy
 recount of the four projection gates and of the level that shares no code with the restatement."""
 import ctypes as C
+import functools
 
 import numpy as np
 
 from matcher_cases import noisy_copies
-from ref_shim import build_ref_shim, p as _p
+from ref_shim import cached_shim, p as _p, rot_axis_angle as _rot, same
 from orbslamm_amd._lib import KP_DTYPE
 from orbslamm_amd.local_mapping import (FUSE_POINT_DTYPE, FUSE_RESULT_DTYPE, FUSE_ST_DEPTH, FUSE_ST_DISTANCE, FUSE_ST_FOUND,
                                         FUSE_ST_LEVEL_RANGE, FUSE_ST_NO_CANDIDATE, FUSE_ST_OUTSIDE_IMAGE, FUSE_ST_VIEW_ANGLE,
                                         FUSE_TARGET_DTYPE, fuse_points, fuse_target)
+
+rot_axis_angle = functools.partial(_rot, scale_first=True)   # (how this module's scenes were generated: ref_shim.rot_axis_angle)
 
 f32, f64 = np.float32, np.float64
 W, H = 640.0, 480.0
@@ -39,46 +42,36 @@ BAND = dict(z=4 * 2.17e-7, uv=4 * 9.26e-4, dist=4 * 1.16e-7, dot=4 * 7.83e-8, le
 BAND_SHARE_CAP = 0.02
 SEEDS = range(5)
 
-_ref = None
+def _declare(L):
+    vp = C.c_void_p
+    L.fuseref_project.argtypes = [vp, vp, vp, C.c_int, C.c_float, vp, C.c_int, C.c_float, vp, vp]
+    L.fuseref_project.restype = None
+    L.fuseref_target.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, C.c_int, C.c_float, vp]
+    L.fuseref_target.restype = None
+    L.fuseref_level_sweep.argtypes = [C.c_float, C.c_int, vp, C.c_uint32, C.c_uint32, vp]
+    L.fuseref_level_sweep.restype = C.c_int64
+    L.fuseref_model_new.argtypes = [C.c_float, vp, vp, C.c_int, C.c_float]
+    L.fuseref_model_new.restype = vp
+    L.fuseref_model_free.argtypes = [vp]
+    L.fuseref_model_free.restype = None
+    L.fuseref_add_keyframe.argtypes = [vp, vp, vp, vp, C.c_int]
+    L.fuseref_set_covisibles.argtypes = [vp, C.c_int, vp, C.c_int]
+    L.fuseref_set_covisibles.restype = None
+    L.fuseref_add_map_point.argtypes = [vp, vp]
+    L.fuseref_add_observation.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.fuseref_add_observation.restype = None
+    L.fuseref_search_in_neighbors.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
+    L.fuseref_search_in_neighbors.restype = None
+    L.fuseref_keyframe_slots.argtypes = [vp, C.c_int, vp]
+    L.fuseref_keyframe_slots.restype = None
+    L.fuseref_map_point.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int]
+    assert [L.fuseref_sizes(i) for i in range(5)] == [FUSE_TARGET_DTYPE.itemsize, FUSE_POINT_DTYPE.itemsize, FUSE_RESULT_DTYPE.itemsize,
+                                                      KP_DTYPE.itemsize, GATES_DTYPE.itemsize]
 
 
 def ref_lib():
     """the restatement as a shared object (built once per process)"""
-    global _ref
-    if _ref is None:
-        L = build_ref_shim("fuse_ref")
-        vp = C.c_void_p
-        L.fuseref_project.argtypes = [vp, vp, vp, C.c_int, C.c_float, vp, C.c_int, C.c_float, vp, vp]
-        L.fuseref_project.restype = None
-        L.fuseref_target.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, vp, vp, C.c_int, C.c_float, vp]
-        L.fuseref_target.restype = None
-        L.fuseref_level_sweep.argtypes = [C.c_float, C.c_int, vp, C.c_uint32, C.c_uint32, vp]
-        L.fuseref_level_sweep.restype = C.c_int64
-        L.fuseref_model_new.argtypes = [C.c_float, vp, vp, C.c_int, C.c_float]
-        L.fuseref_model_new.restype = vp
-        L.fuseref_model_free.argtypes = [vp]
-        L.fuseref_model_free.restype = None
-        L.fuseref_add_keyframe.argtypes = [vp, vp, vp, vp, C.c_int]
-        L.fuseref_set_covisibles.argtypes = [vp, C.c_int, vp, C.c_int]
-        L.fuseref_set_covisibles.restype = None
-        L.fuseref_add_map_point.argtypes = [vp, vp]
-        L.fuseref_add_observation.argtypes = [vp, C.c_int, C.c_int, C.c_int]
-        L.fuseref_add_observation.restype = None
-        L.fuseref_search_in_neighbors.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
-        L.fuseref_search_in_neighbors.restype = None
-        L.fuseref_keyframe_slots.argtypes = [vp, C.c_int, vp]
-        L.fuseref_keyframe_slots.restype = None
-        L.fuseref_map_point.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int]
-        assert [L.fuseref_sizes(i) for i in range(5)] == [FUSE_TARGET_DTYPE.itemsize, FUSE_POINT_DTYPE.itemsize, FUSE_RESULT_DTYPE.itemsize,
-                                                          KP_DTYPE.itemsize, GATES_DTYPE.itemsize]
-        _ref = L
-    return _ref
-
-
-def same(a, b):
-    """equal as bits"""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    return cached_shim("fuse_ref", _declare)
 
 
 # ------------------------------------------------------------------------------------------------ the references
@@ -139,13 +132,6 @@ def reference(oracle, case):
 
 
 # ------------------------------------------------------------------------------------------------ scenes
-def rot_axis_angle(axis, angle):
-    a = np.asarray(axis, f64)
-    a = a / np.linalg.norm(a)
-    Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * Kx @ Kx
-
-
 def grid_tuple(cols=64, rows=48, minX=0.0, minY=0.0, maxX=W, maxY=H):
     """Frame.cc:212-213 in float"""
     return (f32(minX), f32(minY), f32(cols) / f32(f32(maxX) - f32(minX)), f32(rows) / f32(f32(maxY) - f32(minY)), cols, rows)

@@ -6,28 +6,24 @@ import os
 
 import numpy as np
 
-from ref_shim import build_ref_shim, p as _p
+from ref_shim import cached_shim, p as _p
 from orbslamm_amd._lib import KP_DTYPE
 from orbslamm_amd.initializer import OrbiResult, result_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 K_TUM = np.array([517.3, 516.5, 318.6, 255.3], dtype=np.float32)
-_ref = None
+def _declare(L):
+    vp = C.c_void_p
+    L.initref_initialize.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, vp, vp, C.POINTER(OrbiResult), vp, vp]
+    L.initref_svd.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.initref_normalize.argtypes = [vp, C.c_int, vp, vp]
+    L.initref_draw_sets.argtypes = [C.c_int, C.c_int, vp]
+    L.initref_random_int.argtypes = [C.c_int, C.c_int]
 
 
 def ref_lib():
     """the restatement as a shared object (built once per process)"""
-    global _ref
-    if _ref is None:
-        L = build_ref_shim("init_ref")
-        vp = C.c_void_p
-        L.initref_initialize.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, vp, vp, C.POINTER(OrbiResult), vp, vp]
-        L.initref_svd.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
-        L.initref_normalize.argtypes = [vp, C.c_int, vp, vp]
-        L.initref_draw_sets.argtypes = [C.c_int, C.c_int, vp]
-        L.initref_random_int.argtypes = [C.c_int, C.c_int]
-        _ref = L
-    return _ref
+    return cached_shim("init_ref", _declare)
 
 
 def ref_initialize(keys1, keys2, m12, sets, K=K_TUM, sigma=1.0, model="HF"):
@@ -127,7 +123,8 @@ def make_scene(rng, n_match=500, n1=1000, n2=1000, planar=False, noise=0.5, outl
 
 
 def same(a, b):
-    """bit-equal float32 arrays (NaN payloads included)"""
+    """bit-equal float32 arrays (NaN payloads included).  Not ref_shim.same: this one takes ctypes arrays and lists and
+    converts them, so it compares neither dtype nor shape."""
     return np.asarray(a, np.float32).tobytes() == np.asarray(b, np.float32).tobytes()
 
 

@@ -2,10 +2,13 @@
 scene family, the restatement's answers (tools/frustum_ref.hpp through tests/cpp/frustum_ref_capi.cpp) and a float64 numpy
 model of the same geometry written here.  Shared by tests/test_localmap_cpu.py and tests/test_gpu_localmap.py."""
 import ctypes as C
+import functools
 
 import numpy as np
 
-from ref_shim import build_ref_shim, p
+from ref_shim import cached_shim, p, rot_axis_angle as _rot
+
+rot_axis_angle = functools.partial(_rot, scale_first=True)   # (how this module's scenes were generated: ref_shim.rot_axis_angle)
 
 f32 = np.float32
 W, H = 640, 480
@@ -31,19 +34,17 @@ VIEW_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3), (
 MARGIN = 1e-3
 SEEDS = range(1, 11)
 
-_ref = None
+def _declare(L):
+    vp = C.c_void_p
+    L.frustum_local.argtypes = [vp, vp, vp, C.c_int, C.c_float, vp, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]
+    L.frustum_frame.argtypes = [vp, vp, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]
+    L.frustum_local.restype = None
+    L.frustum_frame.restype = None
 
 
 def ref_lib():
-    global _ref
-    if _ref is None:
-        _ref = build_ref_shim("frustum_ref")
-        vp = C.c_void_p
-        _ref.frustum_local.argtypes = [vp, vp, vp, C.c_int, C.c_float, vp, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]
-        _ref.frustum_frame.argtypes = [vp, vp, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]
-        _ref.frustum_local.restype = None
-        _ref.frustum_frame.restype = None
-    return _ref
+    """the restatement as a shared object (built once per process)"""
+    return cached_shim("frustum_ref", _declare)
 
 
 def ref_local(view, points, ids, th, sf=SF, log_sf=LOG_SF):
@@ -70,13 +71,6 @@ def ref_frame(view, points, last_ids, octaves, th, sf=SF):
     ref_lib().frustum_frame(p(view), p(pts), p(ids), p(octs), n, C.c_float(th), p(sf), p(out["uvr"]), p(out["lvl"]), p(out["valid"]), p(out["obs"]),
                             p(out["status"]))
     return out
-
-
-def rot_axis_angle(axis, angle):
-    a = np.asarray(axis, np.float64)
-    a = a / np.linalg.norm(a)
-    Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * Kx @ Kx
 
 
 def make_view(R=None, t=None, K=K_A, bounds=BOUNDS, cos_limit=0.5):

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ref_shim import build_ref_shim, p
+from ref_shim import cached_shim, p
 
 NO_VOTE = 1 << 30
 KF_BAD, KF_SET = 1, 2
@@ -229,17 +229,15 @@ class RefStore(C.Structure):
                 ("parent", C.c_void_p), ("nchildren", C.c_void_p), ("children", C.c_void_p), ("ptBad", C.c_void_p), ("poolCap", C.c_int)]
 
 
-_shim = None
+def _declare(L):
+    L.lmu_keyframes.restype = None
+    L.lmu_points.restype = None
+    L.lmu_keyframes_obs.restype = None
 
 
 def shim():
-    global _shim
-    if _shim is None:
-        _shim = build_ref_shim("localmap_update_ref")
-        _shim.lmu_keyframes.restype = None
-        _shim.lmu_points.restype = None
-        _shim.lmu_keyframes_obs.restype = None
-    return _shim
+    """the restatement as a shared object (built once per process)"""
+    return cached_shim("localmap_update_ref", _declare)
 
 
 def _ref_store(s):

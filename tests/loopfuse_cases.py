@@ -9,7 +9,7 @@ import numpy as np
 
 import fuse_cases as fc
 from fuse_cases import grid_tuple, make_case, rot_axis_angle  # noqa: F401
-from ref_shim import build_ref_shim, p as _p
+from ref_shim import cached_shim, p as _p
 from orbslamm_amd._lib import KP_DTYPE
 from orbslamm_amd.local_mapping import (FUSE_POINT_DTYPE, FUSE_RESULT_DTYPE, FUSE_ST_DEPTH, FUSE_ST_DISTANCE, FUSE_ST_FOUND,
                                         FUSE_ST_LEVEL_RANGE, FUSE_ST_NO_CANDIDATE, FUSE_ST_OUTSIDE_IMAGE, FUSE_ST_VIEW_ANGLE,
@@ -36,37 +36,33 @@ BAND = {k: 4 * v for k, v in MEASURED.items()}
 BAND_SHARE_CAP = 0.02
 SEEDS = range(5)
 
-_ref = None
+def _declare(L):
+    vp = C.c_void_p
+    L.loopref_project.argtypes = [vp, vp, C.c_int, C.c_float, vp, C.c_int, C.c_float, vp, vp]
+    L.loopref_project.restype = None
+    L.loopref_target.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, C.c_float, vp]
+    L.loopref_target.restype = None
+    L.loopref_invz_sweep.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.loopref_invz_sweep.restype = C.c_int64
+    L.loopref_model_new.argtypes = [vp, C.c_int, C.c_float]
+    L.loopref_model_new.restype = vp
+    L.loopref_model_free.argtypes = [vp]
+    L.loopref_model_free.restype = None
+    L.loopref_add_keyframe.argtypes = [vp, vp, vp, vp, C.c_int]
+    L.loopref_add_map_point.argtypes = [vp, vp]
+    L.loopref_add_observation.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.loopref_add_observation.restype = None
+    L.loopref_search_and_fuse.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, vp, vp]
+    L.loopref_keyframe_slots.argtypes = [vp, C.c_int, vp]
+    L.loopref_keyframe_slots.restype = None
+    L.loopref_map_point.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int]
+    assert [L.loopref_sizes(i) for i in range(6)] == [FUSE_TARGET_DTYPE.itemsize, FUSE_POINT_DTYPE.itemsize, FUSE_RESULT_DTYPE.itemsize,
+                                                      KP_DTYPE.itemsize, GATES_DTYPE.itemsize, HIT_DTYPE.itemsize]
 
 
 def ref_lib():
     """the restatement as a shared object (built once per process)"""
-    global _ref
-    if _ref is None:
-        L = build_ref_shim("loopfuse_ref")
-        vp = C.c_void_p
-        L.loopref_project.argtypes = [vp, vp, C.c_int, C.c_float, vp, C.c_int, C.c_float, vp, vp]
-        L.loopref_project.restype = None
-        L.loopref_target.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, C.c_float, vp]
-        L.loopref_target.restype = None
-        L.loopref_invz_sweep.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp]
-        L.loopref_invz_sweep.restype = C.c_int64
-        L.loopref_model_new.argtypes = [vp, C.c_int, C.c_float]
-        L.loopref_model_new.restype = vp
-        L.loopref_model_free.argtypes = [vp]
-        L.loopref_model_free.restype = None
-        L.loopref_add_keyframe.argtypes = [vp, vp, vp, vp, C.c_int]
-        L.loopref_add_map_point.argtypes = [vp, vp]
-        L.loopref_add_observation.argtypes = [vp, C.c_int, C.c_int, C.c_int]
-        L.loopref_add_observation.restype = None
-        L.loopref_search_and_fuse.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, vp, vp]
-        L.loopref_keyframe_slots.argtypes = [vp, C.c_int, vp]
-        L.loopref_keyframe_slots.restype = None
-        L.loopref_map_point.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int]
-        assert [L.loopref_sizes(i) for i in range(6)] == [FUSE_TARGET_DTYPE.itemsize, FUSE_POINT_DTYPE.itemsize, FUSE_RESULT_DTYPE.itemsize,
-                                                          KP_DTYPE.itemsize, GATES_DTYPE.itemsize, HIT_DTYPE.itemsize]
-        _ref = L
-    return _ref
+    return cached_shim("loopfuse_ref", _declare)
 
 
 # ------------------------------------------------------------------------------------------------ the references

@@ -3,14 +3,17 @@
 SERIAL reference loop over the oracle's SearchForTriangulation and the restatement, and a float64 numpy check that shares
 no code with the restatement."""
 import ctypes as C
+import functools
 
 import numpy as np
 
 from matcher_cases import noisy_copies
-from ref_shim import build_ref_shim, p as _p
+from ref_shim import cached_shim, p as _p, rot_axis_angle as _rot, same
 from orbslamm_amd._lib import KP_DTYPE
 from orbslamm_amd.local_mapping import (KF_DTYPE, NEWPOINT_DTYPE, ST_ACCEPTED, ST_DIST_ZERO, ST_FEATURE_SKIPPED, ST_NEIGHBOUR_SKIPPED,
                                         ST_NO_MATCH, ST_PARALLAX, ST_REPROJ1, ST_REPROJ2, ST_SCALE, ST_X3D_ZERO, ST_Z1, ST_Z2, keyframe)
+
+rot_axis_angle = functools.partial(_rot, scale_first=True)   # (how this module's scenes were generated: ref_shim.rot_axis_angle)
 
 f32, f64 = np.float32, np.float64
 W, H = 640.0, 480.0
@@ -40,29 +43,19 @@ BAND = dict(cos=4 * 9.04e-8, z=4 * 9.51e-6, e=4 * 7.94e-5, ratio=4 * 2.41e-6)
 BAND_SHARE_CAP = 0.02   # the share of a case's triangulated pairs that may fall inside the band (undecided)
 SEEDS = range(5)        # the seeds measured; the tests use these
 
-_ref = None
+def _declare(L):
+    vp = C.c_void_p
+    L.npref_compute_f12.argtypes = [vp, vp, vp, vp]
+    L.npref_compute_f12.restype = None
+    L.npref_baseline_too_short.argtypes = [vp, vp]
+    L.npref_pair.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp]
+    L.npref_neighbour.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp]
+    assert (L.npref_sizes(0), L.npref_sizes(1), L.npref_sizes(2)) == (KF_DTYPE.itemsize, NEWPOINT_DTYPE.itemsize, KP_DTYPE.itemsize)
 
 
 def ref_lib():
     """the restatement as a shared object (built once per process)"""
-    global _ref
-    if _ref is None:
-        L = build_ref_shim("newpoints_ref")
-        vp = C.c_void_p
-        L.npref_compute_f12.argtypes = [vp, vp, vp, vp]
-        L.npref_compute_f12.restype = None
-        L.npref_baseline_too_short.argtypes = [vp, vp]
-        L.npref_pair.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp]
-        L.npref_neighbour.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp]
-        assert (L.npref_sizes(0), L.npref_sizes(1), L.npref_sizes(2)) == (KF_DTYPE.itemsize, NEWPOINT_DTYPE.itemsize, KP_DTYPE.itemsize)
-        _ref = L
-    return _ref
-
-
-def same(a, b):
-    """equal as bits"""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    return cached_shim("newpoints_ref", _declare)
 
 
 def ref_f12(kf1, kf2):
@@ -160,13 +153,6 @@ def resolved_reference(oracle, case):
 
 
 # ------------------------------------------------------------------------------------------------ scenes
-def rot_axis_angle(axis, angle):
-    a = np.asarray(axis, f64)
-    a = a / np.linalg.norm(a)
-    Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * Kx @ Kx
-
-
 def _featvec(nodes):
     """mFeatVec as CSR: node ids ascending, the features of a node in index order"""
     nodes = np.asarray(nodes, np.int64)

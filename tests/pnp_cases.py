@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from ref_shim import build_ref_shim, p as _p
+from ref_shim import cached_shim, p as _p, rot_axis_angle, same
 from orbslamm_amd.pnp import EXTRA_SETS, HYP_DTYPE, OrbpResult, make_pnp_sets, result_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,42 +30,32 @@ BAND_REL = 4 * 7.68e-6
 BAND_SHARE_CAP = 0.02   # the share of a case's points that may fall inside the band (undecided)
 SEEDS = range(10)       # the seeds measured; the tests use these
 
-_ref = None
+def _declare(L):
+    vp = C.c_void_p
+    L.pnpref_svd.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    L.pnpref_solve_svd.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    L.pnpref_invert3.argtypes = [vp, vp]
+    L.pnpref_qr_solve.argtypes = [vp, vp, vp]
+    L.pnpref_mul_transposed.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.pnpref_draw_sets.argtypes = [C.c_int, C.c_int, vp]
+    L.pnpref_create.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L.pnpref_create.restype = vp
+    L.pnpref_destroy.argtypes = [vp]
+    L.pnpref_destroy.restype = None
+    L.pnpref_set_ransac.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
+    for f in ("max_iterations", "min_inliers", "iterations"):
+        getattr(L, "pnpref_" + f).argtypes = [vp]
+    L.pnpref_epsilon.argtypes = [vp]
+    L.pnpref_epsilon.restype = C.c_float
+    L.pnpref_thresholds.argtypes = [vp, vp]
+    L.pnpref_iterate.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(OrbpResult), vp, vp, C.c_int]
+    L.pnpref_compute_pose.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.pnpref_compute_pose.restype = C.c_double
 
 
 def ref_lib():
     """the restatement as a shared object (built once per process)"""
-    global _ref
-    if _ref is None:
-        L = build_ref_shim("pnp_ref")
-        vp = C.c_void_p
-        L.pnpref_svd.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
-        L.pnpref_solve_svd.argtypes = [vp, C.c_int, C.c_int, vp, vp]
-        L.pnpref_invert3.argtypes = [vp, vp]
-        L.pnpref_qr_solve.argtypes = [vp, vp, vp]
-        L.pnpref_mul_transposed.argtypes = [vp, C.c_int, C.c_int, vp]
-        L.pnpref_draw_sets.argtypes = [C.c_int, C.c_int, vp]
-        L.pnpref_create.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, vp]
-        L.pnpref_create.restype = vp
-        L.pnpref_destroy.argtypes = [vp]
-        L.pnpref_destroy.restype = None
-        L.pnpref_set_ransac.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
-        for f in ("max_iterations", "min_inliers", "iterations"):
-            getattr(L, "pnpref_" + f).argtypes = [vp]
-        L.pnpref_epsilon.argtypes = [vp]
-        L.pnpref_epsilon.restype = C.c_float
-        L.pnpref_thresholds.argtypes = [vp, vp]
-        L.pnpref_iterate.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(OrbpResult), vp, vp, C.c_int]
-        L.pnpref_compute_pose.argtypes = [vp, vp, C.c_int, vp, vp]
-        L.pnpref_compute_pose.restype = C.c_double
-        _ref = L
-    return _ref
-
-
-def same(a, b):
-    """equal as bits (NaNs included)"""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    return cached_shim("pnp_ref", _declare)
 
 
 def ref_svd(A):
@@ -181,13 +171,6 @@ def full_table_empty():
 
 
 # ------------------------------------------------------------------------------------------------ scenes
-def rot_axis_angle(axis, angle):
-    axis = np.asarray(axis, dtype=np.float64)
-    axis = axis / np.linalg.norm(axis)
-    Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * (Kx @ Kx)
-
-
 def make_case(rng, n=100, R=None, t=None, shape="general", depth=(4.0, 9.0), wrong=0.0, noise=0.0, behind=0, octaves=1, ransac=TRACKING, n_all=None):
     """n correspondences of a frame with pose Xc = R Xw + t.  shape: general | planar | collinear (the camera-frame layout).
     depth: the range of camera depths.  wrong: the share of matches whose keypoint is replaced by a random image point.

@@ -7,7 +7,7 @@ import functools
 import numpy as np
 
 from orbslamm_amd._lib import KP_DTYPE
-from ref_shim import build_ref_shim, p
+from ref_shim import cached_shim, p, rot_axis_angle
 
 K_TUM = np.array([517.3, 516.5, 318.6, 255.3], dtype=np.float32)
 W, H = 640.0, 480.0
@@ -42,13 +42,6 @@ def inv_level_sigma2(nlevels=NLEVELS):
     for i in range(1, nlevels):
         sf[i] = np.float32(sf[i - 1] * np.float32(1.2))
     return (np.float32(1.0) / (sf * sf)).astype(np.float32)
-
-
-def rot_axis_angle(axis, angle):
-    a = np.asarray(axis, dtype=np.float64)
-    a = a / np.linalg.norm(a)
-    Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * (Kx @ Kx)
 
 
 def tcw_of(R, t):
@@ -130,15 +123,17 @@ def open_cases(family):
 
 
 # ------------------------------------------------------------------ the restatement
-@functools.lru_cache(maxsize=1)
-def ref_lib():
-    L = build_ref_shim("poseopt_ref")
+def _declare(L):
     assert [L.poseoptref_sizes(i) for i in range(3)] == [REF_FRAME.itemsize, REF_EDGE.itemsize, REF_RESULT.itemsize]
     L.poseoptref_run.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
     L.poseoptref_run.restype = None
     L.poseoptref_sincos.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.poseoptref_sincos_sweep.argtypes = [C.c_double, C.c_double, C.c_int64, C.c_void_p, C.c_void_p]
-    return L
+
+
+def ref_lib():
+    """the restatement as a shared object (built once per process)"""
+    return cached_shim("poseopt_ref", _declare)
 
 
 SERIAL, DEFINED = 0, 1

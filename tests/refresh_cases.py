@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 import covis_cases as cc
-from ref_shim import build_ref_shim, p
+from ref_shim import cached_shim, p
 
 NO_VOTE, KF_BAD, KF_SET = cc.NO_VOTE, cc.KF_BAD, cc.KF_SET
 DESCRIPTOR, NORMAL_DEPTH, BOTH = 1, 2, 3
@@ -203,19 +203,17 @@ class RefStore(C.Structure):
                 ("ptDesc", C.c_void_p), ("ptFlags", C.c_void_p)]
 
 
-_shim = None
+def _declare(L):
+    L.rfr_open.restype = C.c_void_p
+    L.rfr_open.argtypes = [C.c_void_p]
+    L.rfr_close.argtypes = [C.c_void_p]
+    L.rfr_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.rfr_refresh.restype = None
 
 
 def shim():
-    global _shim
-    if _shim is None:
-        _shim = build_ref_shim("refresh_ref")
-        _shim.rfr_open.restype = C.c_void_p
-        _shim.rfr_open.argtypes = [C.c_void_p]
-        _shim.rfr_close.argtypes = [C.c_void_p]
-        _shim.rfr_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        _shim.rfr_refresh.restype = None
-    return _shim
+    """the restatement as a shared object (built once per process)"""
+    return cached_shim("refresh_ref", _declare)
 
 
 class Ref:

@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from ref_shim import build_ref_shim, p as _p
+from ref_shim import cached_shim, p as _p, rot_axis_angle, same
 from orbslamm_amd.sim3 import HYP_DTYPE, OrbsResult, make_sim3_sets, result_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,35 +31,25 @@ BAND_REL = 4 * 5.04e-5
 BAND_SHARE_CAP = 0.02   # the share of a case's points that may fall inside the band (undecided)
 SEEDS = range(10)       # the seeds measured; the tests use these
 
-_ref = None
+def _declare(L):
+    vp = C.c_void_p
+    L.sim3ref_eigen.argtypes = [vp, vp, vp]
+    L.sim3ref_rodrigues.argtypes = [vp, vp]
+    L.sim3ref_draw_sets.argtypes = [C.c_int, C.c_int, vp]
+    L.sim3ref_create.argtypes = [C.c_int, vp, C.c_int] + [vp] * 10 + [C.c_int]
+    L.sim3ref_create.restype = vp
+    L.sim3ref_destroy.argtypes = [vp]
+    L.sim3ref_destroy.restype = None
+    L.sim3ref_set_ransac.argtypes = [vp, C.c_double, C.c_int, C.c_int]
+    L.sim3ref_max_iterations.argtypes = [vp]
+    L.sim3ref_iterate.argtypes = [vp, C.c_int, vp, C.POINTER(OrbsResult), vp, vp]
+    L.sim3ref_thresholds.argtypes = [vp, vp, vp]
+    L.sim3ref_compute.argtypes = [vp, vp, C.c_int, vp]
 
 
 def ref_lib():
     """the restatement as a shared object (built once per process)"""
-    global _ref
-    if _ref is None:
-        L = build_ref_shim("sim3_ref")
-        vp = C.c_void_p
-        L.sim3ref_eigen.argtypes = [vp, vp, vp]
-        L.sim3ref_rodrigues.argtypes = [vp, vp]
-        L.sim3ref_draw_sets.argtypes = [C.c_int, C.c_int, vp]
-        L.sim3ref_create.argtypes = [C.c_int, vp, C.c_int] + [vp] * 10 + [C.c_int]
-        L.sim3ref_create.restype = vp
-        L.sim3ref_destroy.argtypes = [vp]
-        L.sim3ref_destroy.restype = None
-        L.sim3ref_set_ransac.argtypes = [vp, C.c_double, C.c_int, C.c_int]
-        L.sim3ref_max_iterations.argtypes = [vp]
-        L.sim3ref_iterate.argtypes = [vp, C.c_int, vp, C.POINTER(OrbsResult), vp, vp]
-        L.sim3ref_thresholds.argtypes = [vp, vp, vp]
-        L.sim3ref_compute.argtypes = [vp, vp, C.c_int, vp]
-        _ref = L
-    return _ref
-
-
-def same(a, b):
-    """equal as bits (NaNs included)"""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+    return cached_shim("sim3_ref", _declare)
 
 
 def ref_eigen(a):
@@ -151,13 +141,6 @@ class RefSolver:
 
 
 # ------------------------------------------------------------------------------------------------ scenes
-def rot_axis_angle(axis, angle):
-    axis = np.asarray(axis, dtype=np.float64)
-    axis = axis / np.linalg.norm(axis)
-    Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    return np.eye(3) + np.sin(angle) * Kx + (1 - np.cos(angle)) * (Kx @ Kx)
-
-
 def make_case(rng, n=100, s=1.0, R=None, t=None, fix_scale=False, shape="general", outliers=0.0, noise=0.0, identity_cameras=False,
               grid=False, ransac=(0.99, 6, 300), n1=None, behind=0, zero_depth=0):
     """n correspondences of two keyframes whose camera-frame points obey X1c = s R X2c + t.  shape: general | planar |

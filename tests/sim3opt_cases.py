@@ -8,7 +8,7 @@ import functools
 import numpy as np
 
 from poseopt_cases import K_TUM, inv_level_sigma2, rot_axis_angle
-from ref_shim import build_ref_shim, p
+from ref_shim import cached_shim, p
 
 W, H = 640.0, 480.0
 NLEVELS = 8
@@ -128,16 +128,18 @@ def sim3_distance(a, b):
 
 
 # ------------------------------------------------------------------ the restatement
-@functools.lru_cache(maxsize=1)
-def ref_lib():
-    L = build_ref_shim("sim3opt_ref")
+def _declare(L):
     assert [L.sim3optref_sizes(i) for i in range(3)] == [REF_PROBLEM.itemsize, REF_CORR.itemsize, REF_RESULT.itemsize]
     L.sim3optref_run.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
     L.sim3optref_run.restype = None
     L.sim3optref_exp.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.sim3optref_quat.argtypes = [C.c_void_p, C.c_void_p]
     L.sim3optref_exp_sweep.argtypes = [C.c_double, C.c_double, C.c_int64, C.c_void_p, C.c_void_p]
-    return L
+
+
+def ref_lib():
+    """the restatement as a shared object (built once per process)"""
+    return cached_shim("sim3opt_ref", _declare)
 
 
 SERIAL, DEFINED, DEFINED_CACHED = 0, 1, 2

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import covis_cases as cc
+import dropin
 from orbslamm_amd import _lib
 from orbslamm_amd._lib import ORBX_E_INVALID, ORBX_E_UNSUPPORTED, ORBX_OK, lib, ptr
 
@@ -193,4 +194,4 @@ def test_refusals_that_need_no_gpu():
 def test_the_dropins_compile_against_the_mocks(name):
     """include/KeyFrame_hip.hpp and KeyFrameCullingT of include/LocalMapping_hip.hpp over tests/cpp/mock_covis.hpp, warnings as errors
     (syntax and types only: nothing is linked or run)"""
-    subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", name + ".cpp")])
+    dropin.syntax_only(name)

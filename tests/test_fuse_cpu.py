@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import fuse_cases as fc
+import ref_shim
 from orbslamm_amd import local_mapping as lm
 from orbslamm_amd._lib import KP_DTYPE, ORBX_E_INVALID, OrbError
 from ref_shim import p as _p
@@ -36,6 +37,7 @@ def test_header_declares_and_library_exports_the_fuse_block():
         assert hasattr(L, name), name
     import orbslamm_amd
     assert orbslamm_amd.fuse_batch is lm.fuse_batch and orbslamm_amd.level_breaks is lm.level_breaks
+    ref_shim.assert_shares_no_code_with_the_library(os.path.join(ROOT, "tools", "fuse_ref.hpp"))
 
 
 def bits(x):

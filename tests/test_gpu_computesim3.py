@@ -4,17 +4,15 @@ path (the matcher's resident window_best run twice, host agreement and walk, opt
 features; 8 jobs over two frame sets against the 8 single calls, and the same call twice; a pool update between two calls; the
 refusals that need handles; and the drop-in on mocks.  A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import computesim3_cases as cc
+import dropin
 import localmap_cases as lc
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = lc.W, lc.H
 D0 = [0, 0, 0, 0, 0]
 CAP = 320
@@ -244,17 +242,7 @@ def test_refusals_that_need_handles(rig):
     store2.close(); pool2.close(); store.close(); pool.close()
 
 
-def test_computesim3_dropin_on_mock_keyframes(gpu, tmp_path):
+def test_computesim3_dropin_on_mock_keyframes(gpu):
     """include/LoopClosing_hip.hpp (ComputeSim3T::RunAll) on mocks (tests/cpp/computesim3_dropin_gpu.cpp, mock_computesim3.hpp) over three
     candidates against ORBmatcherT::SearchBySim3 + OptimizeSim3T::Run per candidate, the early-return job among them"""
-    from orbslamm_amd import _lib
-    _lib.build()
-    exe = str(tmp_path / "computesim3_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), "-I", os.path.join(ROOT, "tools"),
-                           os.path.join(ROOT, "tests", "cpp", "computesim3_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "computesim3 dropin ok" in r.stdout
+    dropin.run(dropin.build("computesim3_dropin_gpu"), timeout=120, marker="computesim3 dropin ok")

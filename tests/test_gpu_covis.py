@@ -5,17 +5,14 @@ repeated targets, a target alone against the same target in a batch, ordered lis
 generation wrap, the setters' effects between two calls, two stores on one pool, orbu_update_local_map around the calls, and both
 drop-ins against the members written serially.
 A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import covis_cases as cc
+import dropin
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = 31           # orbn::kChunk: targets per pass over the store
 SORT_TILE = 256      # orbn::kSortTile: keys of the ordered list per LDS tile
 
@@ -264,10 +261,4 @@ def test_culling_is_refused_while_a_set_keyframe_lacks_octaves(matcher):
 def test_the_dropins_equal_the_members_written_serially(matcher, gpu):
     """tests/cpp/covis_dropin_gpu.cpp: UpdateConnectionsT::RunAll over 30 keyframes and a KeyFrameCullingT::Run in which two keyframes
     are culled and the first cull changes the second one's verdict, against the two members over the same mocks"""
-    from orbslamm_amd import _lib
-    exe = os.path.join(tempfile.mkdtemp(prefix="covis_dropin_"), "covis_dropin_gpu")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "covis_dropin_gpu.cpp"),
-                           "-o", exe, _lib.SO_PATH, "-Wl,-rpath," + os.path.dirname(_lib.SO_PATH)])
-    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    text = out.stdout.decode(errors="replace")
-    assert out.returncode == 0 and "covis drop-ins: ok" in text, text[-2000:]
+    dropin.run(dropin.build("covis_dropin_gpu", pthread=False), timeout=120, marker="covis drop-ins: ok")

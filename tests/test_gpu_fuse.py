@@ -5,18 +5,16 @@ field of every OrblFuseResult, over the scene families, both entries (host array
 the refusals; against the library's own window_best fed with
 the restatement's projections; and the C++ drop-in on mock keyframes."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import fuse_cases as fc
 from orbslamm_amd import local_mapping as lm
 from orbslamm_amd._lib import KP_DTYPE, OrbmGrid
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -260,17 +258,6 @@ def test_fuse_dropin_on_mock_keyframes(gpu, oracle, tmp_path):
     """include/LocalMapping_hip.hpp (SearchInNeighborsT) on mock keyframes and map points (tests/cpp/fuse_dropin_gpu.cpp): the
     replay leaves the object graph and the Replace / AddObservation sequences of the reference loop on the restatement's
     model, with repeated second neighbours and at least one dirty re-score"""
-    from orbslamm_amd import _lib
-    _lib.build()
     scene = str(tmp_path / "scene.bin")
     fc.write_dropin_scene(fc.dropin_scene(0), scene)
-    exe = str(tmp_path / "fuse_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "fuse_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip", "-L", os.path.join(ROOT, "oracle"), "-lorb_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"),
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe, scene], capture_output=True, text=True, timeout=600)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "fuse dropin ok" in r.stdout
+    print(dropin.run(dropin.build("fuse_dropin_gpu", oracle=True), scene, timeout=600, marker="fuse dropin ok"))

@@ -1,16 +1,14 @@
 """The device Initializer (orbi_*) against the restatement (tools/init_ref.hpp via tests/init_cases.py): R21, t21, vP3D,
 vbTriangulated, the return value and every diagnostic (SH, SF, RH, the winning hypotheses, their iterations and inlier
 counts, every candidate's nGood and parallax) equal as bits."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import init_cases as ic
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -194,19 +192,10 @@ def test_resident_chain_extractor_to_initialize(gpu):
         m.frame_destroy(f)
 
 
-def test_initializer_dropin_on_mock_frames(gpu, tmp_path):
+def test_initializer_dropin_on_mock_frames(gpu):
     """include/Initializer_hip.hpp (InitializerT) on mock frames (tests/cpp/init_dropin_gpu.cpp) against
     tools/init_ref.hpp, and the process's rand() stream after Initialize"""
-    from orbslamm_amd import _lib
-    _lib.build()
-    exe = str(tmp_path / "init_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "init_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "init dropin ok" in r.stdout
+    dropin.run(dropin.build("init_dropin_gpu"), timeout=600, marker="init dropin ok")
 
 
 # ------------------------------------------------------------------------------------------------ scene families, sizes

@@ -1,17 +1,15 @@
 """The device keyframe database (orbk_* / orbv_score) against the restatement (tests/kfdb_cases.py): candidate lists equal
 in order, scored lists and the six query fields of every keyframe equal as bits."""
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import kfdb_cases as kc
 from vocab_cases import make_vocab
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TUM_K = [517.3, 516.5, 318.6, 255.3]
 
 
@@ -324,16 +322,9 @@ def test_mixed_devices_are_refused(gpu):
     fs1.close()
 
 
-def test_keyframe_database_dropin_runs(gpu, tmp_path):
+def test_keyframe_database_dropin_runs(gpu):
     """include/KeyFrameDatabase_hip.hpp on mock keyframes (tests/cpp/kfdb_dropin_gpu.cpp) against tools/kfdb_ref.hpp"""
-    exe = str(tmp_path / "kfdb_dropin_gpu")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "kfdb_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-4000:] + out.stderr[-2000:]
-    assert "kfdb_dropin_gpu ok" in out.stdout
+    dropin.run(dropin.build("kfdb_dropin_gpu"), timeout=600, marker="kfdb_dropin_gpu ok")
 
 
 def test_loop_batch_returns_more_candidates_than_the_staging_block(gpu):

@@ -3,16 +3,14 @@ BITS for both gate sets over every scene family, the query counts 0, 1, 63, 64, 
 capacity - 1, th of 1, 3 and 5 and two level tables; the two searches against the host-array path fed with the restatement's
 arrays; the pool's update semantics; the drop-in on mocks.
 A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import localmap_cases as lc
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, NF = lc.W, lc.H, 500
 D0 = [0, 0, 0, 0, 0]
 
@@ -319,17 +317,7 @@ def test_a_repeated_id_on_both_sides_of_a_staging_chunk(rig):
     y.close()
 
 
-def test_localmap_dropin_on_mock_tracking(gpu, tmp_path):
+def test_localmap_dropin_on_mock_tracking(gpu):
     """include/Tracking_hip.hpp (SearchLocalPointsT::Run) on mock frames and MapPoints (tests/cpp/localmap_dropin_gpu.cpp) against the
     serial reference loop over the same mocks"""
-    from orbslamm_amd import _lib
-    _lib.build()
-    exe = str(tmp_path / "localmap_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), "-I", os.path.join(ROOT, "tools"),
-                           os.path.join(ROOT, "tests", "cpp", "localmap_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "localmap dropin ok" in r.stdout
+    dropin.run(dropin.build("localmap_dropin_gpu"), timeout=300, marker="localmap dropin ok")

@@ -4,17 +4,15 @@ against the restatement (tools/localmap_update_ref.hpp), element for element, ov
 and one entry behind a compaction chunk, the capacity edge, a forced generation wrap, the setters' semantics, two stores on one
 pool, and the search from the resident list against orbw_track_local_map given the restatement's S.
 A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import localmap_cases as lc
 import localmap_update_cases as uc
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = 1024     # orbu::kChunk: positions per block of the ordered compaction
 
 
@@ -468,27 +466,13 @@ def test_the_search_from_the_resident_list(gpu):
     pool.close()
 
 
-def run_cpp(tmp_path, name, says):
-    from orbslamm_amd import _lib
-    _lib.build()
-    exe = str(tmp_path / name)
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), "-I", os.path.join(ROOT, "tools"),
-                           os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert says in r.stdout
-
-
-def test_update_dropin_on_mock_tracking(gpu, tmp_path):
+def test_update_dropin_on_mock_tracking(gpu):
     """include/Tracking_hip.hpp (UpdateLocalMapT::SyncKeyFrame / Run) on mock keyframes, MapPoints and frames
     (tests/cpp/localmap_update_dropin_gpu.cpp) against the serial reference loop over the same mocks: both vectors, the stamps,
     mpReferenceKF, the nulled bad matches, the frame nobody votes for, a refusal"""
-    run_cpp(tmp_path, "localmap_update_dropin_gpu", "localmap update dropin ok")
+    dropin.run(dropin.build("localmap_update_dropin_gpu"), timeout=300, marker="localmap update dropin ok")
 
 
-def test_resident_dropin_on_mock_tracking(gpu, tmp_path):
+def test_resident_dropin_on_mock_tracking(gpu):
     """SearchLocalPointsT::RunResident (tests/cpp/localmap_resident_dropin_gpu.cpp) against the serial SearchLocalPoints"""
-    run_cpp(tmp_path, "localmap_resident_dropin_gpu", "localmap resident dropin ok")
+    dropin.run(dropin.build("localmap_resident_dropin_gpu"), timeout=300, marker="localmap resident dropin ok")

@@ -4,12 +4,11 @@ hit, hit_start, n_hits and every status byte, over the scene families, both entr
 the shapes around the tile sizes, the empty cases, 200 targets, a target of 9000 features, the capacity refusal and the
 refusals that need a handle; against orbl_fuse_batch with its chi-square gate disabled; and the C++ drop-in on mock keyframes."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import fuse_cases as fc
 import loopfuse_cases as lc
 from orbslamm_amd import local_mapping as lm
@@ -17,7 +16,6 @@ from orbslamm_amd import loop_closing as lo
 from orbslamm_amd._lib import KP_DTYPE, ORBX_E_CAPACITY, ORBX_E_INVALID, ORBX_E_UNSUPPORTED, OrbError, OrbmGrid
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -282,16 +280,8 @@ def test_loopfuse_dropin_on_mock_keyframes(gpu, tmp_path):
     """include/LoopClosing_hip.hpp (SearchAndFuseT) on mock keyframes and map points (tests/cpp/loopfuse_dropin_gpu.cpp): the
     replay leaves the object graph, the total and the Replace / AddObservation sequences of the serial loop on the
     restatement's model, under Scw of scale 0.5, 2 and 1; with the stale re-score disabled it does not"""
-    from orbslamm_amd import _lib
-    _lib.build()
     scene = str(tmp_path / "scene.bin")
     lc.write_map_scene(lc.map_scene(0), scene)
-    exe = str(tmp_path / "loopfuse_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "loopfuse_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip", "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe, scene], capture_output=True, text=True, timeout=600)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "loopfuse dropin ok" in r.stdout and "share" in r.stdout
+    out = dropin.run(dropin.build("loopfuse_dropin_gpu"), scene, timeout=600, marker="loopfuse dropin ok")
+    print(out)
+    assert "share" in out

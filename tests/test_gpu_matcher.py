@@ -1,7 +1,10 @@
 """GPU parity of the matcher entry points (through the C ABI) against the oracle."""
+import os
+
 import numpy as np
 import pytest
 
+import dropin
 from conftest import random_descriptors
 from matcher_cases import make_bow_case, make_proj_case, noisy_copies
 
@@ -291,67 +294,27 @@ def test_distinctive_descriptors_parity(gm, oracle):
     assert got[0] == -1 and got[1] == 0
 
 
-def test_cpp_adapters_on_gpu(gpu, tmp_path):
+def test_cpp_adapters_on_gpu(gpu):
     """the C++ ORBextractor / ORBmatcher adapters (include/*.hpp) driven from a C++ program,
     checked bit-for-bit against the C oracle linked into the test binary"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    from oracle import binding as ob
-    ob.build()
-    exe = str(tmp_path / "adapter_gpu")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-pthread", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "adapter_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(root, "orbslamm_amd"), "-lorbslamm_hip", "-L", os.path.join(root, "oracle"), "-lorb_oracle",
-                           "-Wl,-rpath," + os.path.join(root, "orbslamm_amd"), "-Wl,-rpath," + os.path.join(root, "oracle"),
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "adapter_gpu ok" in out.stdout
+    dropin.run(dropin.build("adapter_gpu", oracle=True), marker="adapter_gpu ok")
 
 
-def test_extractor_dropin_reference_signature(gpu, tmp_path):
+def test_extractor_dropin_reference_signature(gpu):
     """include/ORBextractor_hip.hpp under -DORBSLAMM_WITH_OPENCV: the reference's own operator() signature
     (InputArray, InputArray, vector<KeyPoint>&, OutputArray; include/ORBextractor.h:57-58) compiled against the
     data-holder cv:: types of tests/cpp/mock_opencv and called the way Frame::ExtractORB calls it (Frame.cc:247-253),
     keypoint records and descriptor rows against the C oracle; empty and featureless images (:1046-1047, :1064-1065)"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    from oracle import binding as ob
-    ob.build()
-    exe = str(tmp_path / "adapter_cv_gpu")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-DORBSLAMM_WITH_OPENCV", "-I", os.path.join(root, "include"),
-                           "-I", os.path.join(root, "tests", "cpp", "mock_opencv"),
-                           os.path.join(root, "tests", "cpp", "adapter_cv_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(root, "orbslamm_amd"), "-lorbslamm_hip", "-L", os.path.join(root, "oracle"), "-lorb_oracle",
-                           "-Wl,-rpath," + os.path.join(root, "orbslamm_amd"), "-Wl,-rpath," + os.path.join(root, "oracle"),
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "adapter_cv_gpu ok" in out.stdout
+    dropin.run(dropin.build("adapter_cv_gpu", extra=["-DORBSLAMM_WITH_OPENCV", "-I", os.path.join(dropin.CPP, "mock_opencv")], oracle=True), marker="adapter_cv_gpu ok")
 
 
-def test_orbmatcher_dropin_all_eleven_signatures(gpu, tmp_path):
+def test_orbmatcher_dropin_all_eleven_signatures(gpu):
     """include/ORBmatcher_hip.hpp: ORBmatcherT<Frame, KeyFrame, MapPoint> -- the reference's eleven ORBmatcher members
     (ORBmatcher.h:48-83) instantiated on mock objects with the reference's member names, run on the GPU; the flattened
     arrays each member produced go through the C oracle (identical device results), the write-back into the object
     graph is replayed on a copy of the world, the projections are recomputed in double (tests/cpp/matcher_dropin_gpu.cpp)"""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    from oracle import binding as ob
-    ob.build()
-    exe = str(tmp_path / "matcher_dropin_gpu")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-Wall", "-Werror", "-I", os.path.join(root, "include"),
-                           os.path.join(root, "tests", "cpp", "matcher_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(root, "orbslamm_amd"), "-lorbslamm_hip", "-L", os.path.join(root, "oracle"), "-lorb_oracle",
-                           "-Wl,-rpath," + os.path.join(root, "orbslamm_amd"), "-Wl,-rpath," + os.path.join(root, "oracle"),
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout[-4000:] + out.stderr[-2000:]
-    assert "matcher_dropin_gpu ok" in out.stdout
-    assert out.stdout.count("\n") >= 17  # one line per member variant
+    out = dropin.run(dropin.build("matcher_dropin_gpu", oracle=True), marker="matcher_dropin_gpu ok")
+    assert out.count("\n") >= 17  # one line per member variant
 
 
 def test_undistort_keypoints_parity(gm, oracle):

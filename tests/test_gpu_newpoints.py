@@ -3,17 +3,15 @@ restatement tools/newpoints_ref.hpp, one neighbour after the other: tests/newpoi
 OrblNewPoint, the whole status table and the F12 / epipole each neighbour's search used -- over the scene families, both
 entries (host arrays, device-resident frames), 20 neighbours x 2000 features, more than 8192 features per keyframe, the
 hand-made degenerate pairs, the empty cases and the refusals; and the C++ drop-in on mock keyframes."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import newpoints_cases as nc
 from orbslamm_amd import local_mapping as lm
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -259,16 +257,6 @@ def test_newpoints_dropin_on_mock_keyframes(gpu, oracle, tmp_path):
     """include/LocalMapping_hip.hpp (CreateNewMapPointsT) on mock keyframes and map points (tests/cpp/newpoints_dropin_gpu.cpp):
     the replay leaves the object graph of the reference loop written out there over the C oracle and the restatement; with
     the CheckNewKeyFrames predicate firing at neighbour 3, exactly neighbours 0..2"""
-    from orbslamm_amd import _lib
-    _lib.build()
     scene = str(tmp_path / "scene.bin")
     nc.write_scene(nc.family_case("general", 0), scene)
-    exe = str(tmp_path / "newpoints_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "newpoints_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip", "-L", os.path.join(ROOT, "oracle"), "-lorb_oracle",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"),
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe, scene], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "newpoints dropin ok" in r.stdout
+    dropin.run(dropin.build("newpoints_dropin_gpu", oracle=True), scene, timeout=600, marker="newpoints dropin ok")

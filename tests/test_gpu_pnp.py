@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import dropin
 import pnp_cases as pc
 
 pytestmark = pytest.mark.gpu
@@ -175,19 +176,10 @@ def test_refusals(matcher):
     assert code(lambda: run_all([dev], [good])) == ORBX_E_UNSUPPORTED   # it has iterated and has no table to continue
 
 
-def test_pnp_dropin_on_mock_frames(gpu, tmp_path):
+def test_pnp_dropin_on_mock_frames(gpu):
     """include/PnPsolver_hip.hpp (PnPsolverT, RunAll) on a mock frame (tests/cpp/pnp_dropin_gpu.cpp) through
     Tracking::Relocalization's round-robin loop against tools/pnp_ref.hpp, and the process's rand() position after RunAll"""
-    from orbslamm_amd import _lib
-    _lib.build()
-    exe = str(tmp_path / "pnp_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "pnp_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "pnp dropin ok" in r.stdout
+    dropin.run(dropin.build("pnp_dropin_gpu"), timeout=600, marker="pnp dropin ok")
 
 
 def test_soak_slice(gpu):

@@ -4,18 +4,16 @@ bytes, over every scene family x 3 seeds x the edge counts 0, 2, 3, 9, 10, 63, 6
 `< 10` break, the lane boundary of the one wave that serves a frame, many edges per lane); batches against single frames;
 the host-array and resident-frame entries against each other; the same call twice; the drop-in on the mock.
 A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import poseopt_cases as pc
 from orbslamm_amd import optimizer as opt
 from orbslamm_amd._lib import ORBX_E_INVALID, lib
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIG = pc.inv_level_sigma2()
 
 
@@ -135,16 +133,7 @@ def test_resident_frames_give_the_host_arrays_bytes(matcher):
         matcher.frame_destroy(F)
 
 
-def test_poseopt_dropin_on_mock_frames(gpu, tmp_path):
+def test_poseopt_dropin_on_mock_frames(gpu):
     """include/Optimizer_hip.hpp (PoseOptimizationT::Run, RunAll) on mock frames (tests/cpp/poseopt_dropin_gpu.cpp) against
     tools/poseopt_ref.hpp run on the same mocks"""
-    from orbslamm_amd import _lib
-    _lib.build()
-    exe = str(tmp_path / "poseopt_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "poseopt_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "poseopt dropin ok" in r.stdout
+    dropin.run(dropin.build("poseopt_dropin_gpu"), timeout=300, marker="poseopt dropin ok")

@@ -6,17 +6,14 @@ drop-in against the two members written serially.
 Floats are compared as bits; two NaNs are equal whatever their sign and payload, which IEEE 754 leaves to the implementation (a
 point exactly at a camera centre: 0 * inf).
 A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import dropin
 import refresh_cases as rc
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -350,10 +347,4 @@ def test_the_refusals_with_a_store(matcher):
 def test_the_dropin_equals_the_members_written_serially(matcher, gpu):
     """tests/cpp/refresh_dropin_gpu.cpp: RefreshMapPointsT::Run over the mocks against ComputeDistinctiveDescriptors and
     UpdateNormalAndDepth written serially on the same mocks, their maps ordered by mnId"""
-    from orbslamm_amd import _lib
-    exe = os.path.join(tempfile.mkdtemp(prefix="refresh_dropin_"), "refresh_dropin_gpu")
-    subprocess.check_call(["g++", "-std=c++11", "-O1", "-ffp-contract=off", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "refresh_dropin_gpu.cpp"), "-o", exe, _lib.SO_PATH, "-Wl,-rpath," + os.path.dirname(_lib.SO_PATH)])
-    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    text = out.stdout.decode(errors="replace")
-    assert out.returncode == 0 and "refresh drop-in: ok" in text, text[-2000:]
+    dropin.run(dropin.build("refresh_dropin_gpu", pthread=False), timeout=120, marker="refresh drop-in: ok")

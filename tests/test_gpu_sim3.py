@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+import dropin
 import sim3_cases as sc
 
 pytestmark = pytest.mark.gpu
@@ -275,19 +276,10 @@ def test_end_to_end_bow_matches_to_sim3_to_window_search(gpu):
         m.frame_destroy(F)
 
 
-def test_sim3_dropin_on_mock_keyframes(gpu, tmp_path):
+def test_sim3_dropin_on_mock_keyframes(gpu):
     """include/Sim3Solver_hip.hpp (Sim3SolverT, RunAll) on mock keyframes (tests/cpp/sim3_dropin_gpu.cpp) through
     MultiMapper's round-robin loop against tools/sim3_ref.hpp, and the process's rand() position after RunAll"""
-    from orbslamm_amd import _lib
-    _lib.build()
-    exe = str(tmp_path / "sim3_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "sim3_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "sim3 dropin ok" in r.stdout
+    dropin.run(dropin.build("sim3_dropin_gpu"), timeout=600, marker="sim3 dropin ok")
 
 
 def test_soak_slice(gpu):

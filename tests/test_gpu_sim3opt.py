@@ -4,18 +4,16 @@ family x 3 seeds x both fix_scale x the correspondence counts 0, 1, 9, 10, 31, 3
 border; 64 edges, the border of the partials; 32 edges on a lane); batches against single problems; the same call twice; two
 keyframes with different K and level tables; the drop-in on the mock.
 A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import sim3opt_cases as sc
 from orbslamm_amd import optimizer as opt
 from orbslamm_amd._lib import lib
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIG = sc.inv_level_sigma2()
 FIELDS = ("q", "t", "s", "written", "n_corr", "n_bad", "n_in", "iterations", "trials", "lambda_", "chi2")
 
@@ -115,16 +113,7 @@ def test_two_cameras_and_two_level_tables(matcher):
     assert r["removed"].tobytes() == ref_flags[0].tobytes()
 
 
-def test_sim3opt_dropin_on_mock_keyframes(gpu, tmp_path):
+def test_sim3opt_dropin_on_mock_keyframes(gpu):
     """include/Optimizer_hip.hpp (OptimizeSim3T::Run, RunAll) on mock keyframes (tests/cpp/sim3opt_dropin_gpu.cpp) against
     tools/sim3opt_ref.hpp run on the same mocks"""
-    from orbslamm_amd import _lib
-    _lib.build()
-    exe = str(tmp_path / "sim3opt_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "sim3opt_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "sim3opt dropin ok" in r.stdout
+    dropin.run(dropin.build("sim3opt_dropin_gpu"), timeout=300, marker="sim3opt dropin ok")

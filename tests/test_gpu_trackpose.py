@@ -6,18 +6,16 @@ orbo_pose_optimize_frames given the host-made edge list of the same merge, over 
 by the kernel, a pool update between two calls, and the drop-in on mocks.
 A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import localmap_cases as lc
 import localmap_update_cases as uc
 import trackpose_cases as tc
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, NF = lc.W, lc.H, 500
 D0 = [0, 0, 0, 0, 0]
 CAP = 320                      # the custom frame sets' cap: five chunks of 64 features
@@ -504,17 +502,7 @@ def test_a_pool_update_between_two_calls(rig):
     pool.close()
 
 
-def test_trackpose_dropin_on_mock_tracking(gpu, tmp_path):
+def test_trackpose_dropin_on_mock_tracking(gpu):
     """include/Tracking_hip.hpp (TrackWithMotionModelT::Finish, TrackLocalMapT::Run) on mocks (tests/cpp/trackpose_dropin_gpu.cpp) against
     the reference loops written serially over the same mocks"""
-    from orbslamm_amd import _lib
-    _lib.build()
-    exe = str(tmp_path / "trackpose_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), "-I", os.path.join(ROOT, "tools"),
-                           os.path.join(ROOT, "tests", "cpp", "trackpose_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "trackpose dropin ok" in r.stdout
+    dropin.run(dropin.build("trackpose_dropin_gpu"), timeout=300, marker="trackpose dropin ok")

@@ -6,18 +6,16 @@ nnratio; solve and min_matches; 1, 2 and 9 jobs over two frame sets with keyfram
 twice; the BoW ring left alone; a pool update between two calls; the refusals that need handles; and the drop-in on mocks.
 A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import localmap_cases as lc
 import trackpose_cases as tc
 import trackref_cases as rc
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = lc.W, lc.H
 D0 = [0, 0, 0, 0, 0]
 CAP = 320
@@ -325,17 +323,7 @@ def test_refusals_that_need_handles(rig):
     store2.close(); pool2.close(); store.close(); pool.close()
 
 
-def test_trackref_dropin_on_mock_tracking(gpu, tmp_path):
+def test_trackref_dropin_on_mock_tracking(gpu):
     """include/Tracking_hip.hpp (TrackReferenceKeyFrameT::Run) on mocks (tests/cpp/trackref_dropin_gpu.cpp, mock_trackref.hpp) against
     Tracking::TrackReferenceKeyFrame written serially over the same mocks"""
-    from orbslamm_amd import _lib
-    _lib.build()
-    exe = str(tmp_path / "trackref_dropin")
-    subprocess.check_call(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-pthread", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), "-I", os.path.join(ROOT, "tools"),
-                           os.path.join(ROOT, "tests", "cpp", "trackref_dropin_gpu.cpp"), "-o", exe,
-                           "-L", os.path.join(ROOT, "orbslamm_amd"), "-lorbslamm_hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "orbslamm_amd"), "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "trackref dropin ok" in r.stdout
+    dropin.run(dropin.build("trackref_dropin_gpu"), timeout=120, marker="trackref dropin ok")

@@ -5,13 +5,14 @@ model on two hand-made scenes, and the parallel rule (device hits + survivor set
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import fuse_cases as fc
 import loopfuse_cases as lc
+import ref_shim
 from orbslamm_amd import local_mapping as lm
 from orbslamm_amd import loop_closing as lo
 from orbslamm_amd._lib import KP_DTYPE, ORBX_E_INVALID, ORBX_E_UNSUPPORTED
@@ -39,17 +40,14 @@ def test_header_declares_and_library_exports_the_loopfuse_block():
     import orbslamm_amd
     assert orbslamm_amd.search_and_fuse is lo.search_and_fuse
     assert lo.HIT_DTYPE.itemsize == 16 and lo.HIT_DTYPE.names == ("target", "point", "best_idx", "best_dist")
-    # the kernels and the restatement share no header
-    ref = open(os.path.join(ROOT, "tools", "loopfuse_ref.hpp")).read()
-    assert '#include "' not in ref
+    ref_shim.assert_shares_no_code_with_the_library(os.path.join(ROOT, "tools", "loopfuse_ref.hpp"))
     for name in ("orbc_kernels.hip", "orbc_host.inc"):
         assert "loopfuse_ref" not in open(os.path.join(ROOT, "orbslamm_amd", "csrc", name)).read()
 
 
 def test_dropin_header_compiles_against_the_mocks():
     """include/LoopClosing_hip.hpp instantiated on the mocks of tests/cpp/mock_loopfuse.hpp (the GPU test runs it)"""
-    subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "loopfuse_dropin_gpu.cpp")])
+    dropin.syntax_only("loopfuse_dropin_gpu")
     hdr = open(os.path.join(ROOT, "include", "LoopClosing_hip.hpp")).read()
     for member in ("SearchAndFuseT", "Run(", "rescored"):
         assert member in hdr, member

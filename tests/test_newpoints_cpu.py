@@ -5,12 +5,13 @@ wins), and the ABI."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import newpoints_cases as nc
+import ref_shim
 from orbslamm_amd import local_mapping as lm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -205,16 +206,14 @@ def test_structs_and_the_restatement_stands_alone():
     assert lm.KF_DTYPE.itemsize == 80 and lm.NEWPOINT_DTYPE.itemsize == 44 and lm.MAX_NEIGHBOURS == 32
     L = nc.ref_lib()
     assert (L.npref_sizes(0), L.npref_sizes(1)) == (80, 44)
-    src = open(os.path.join(ROOT, "tools", "newpoints_ref.hpp")).read()
-    assert "#include \"" not in src and "orbx_cvmath" not in src.split("#pragma once")[1]   # shares no header with the library
+    ref_shim.assert_shares_no_code_with_the_library(os.path.join(ROOT, "tools", "newpoints_ref.hpp"))
     for name in ("orbl_kernels.hip", "orbl_host.inc"):
         assert "newpoints_ref.hpp" not in open(os.path.join(ROOT, "orbslamm_amd", "csrc", name)).read()
 
 
 def test_dropin_header_compiles_against_the_mocks():
     """include/LocalMapping_hip.hpp instantiated on mocks derived from tests/cpp/mock_slam.hpp (the GPU test runs it)"""
-    subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "newpoints_dropin_gpu.cpp")])
+    dropin.syntax_only("newpoints_dropin_gpu")
     hdr = open(os.path.join(ROOT, "include", "LocalMapping_hip.hpp")).read()
     for member in ("CreateNewMapPointsT", "GetBestCovisibilityKeyFrames", "ComputeSceneMedianDepth", "checkNewKeyFrames()"):
         assert member in hdr, member

@@ -8,7 +8,9 @@ import re
 import numpy as np
 import pytest
 
+import dropin
 import pnp_cases as pc
+import ref_shim
 from orbslamm_amd._lib import RAND_MAX, libc, random_int, seed_rand
 from orbslamm_amd.pnp import EXTRA_SETS, make_pnp_sets
 
@@ -316,17 +318,14 @@ def test_header_declares_and_library_exports_the_orbp_block():
 def test_result_structs_and_the_restatement_stands_alone():
     from orbslamm_amd.pnp import HYP_DTYPE, OrbpHypothesis, OrbpResult
     assert C.sizeof(OrbpHypothesis) == 208 == HYP_DTYPE.itemsize and C.sizeof(OrbpResult) == 160
-    src = open(os.path.join(ROOT, "tools", "pnp_ref.hpp")).read()
-    assert "#include \"" not in src and "orbx_cvmath" not in src.split("#pragma once")[1]   # shares no header with the library
+    ref_shim.assert_shares_no_code_with_the_library(os.path.join(ROOT, "tools", "pnp_ref.hpp"))
     for name in ("orbp_kernels.hip", "orbp_host.inc"):
         assert "pnp_ref.hpp" not in open(os.path.join(ROOT, "orbslamm_amd", "csrc", name)).read()
 
 
 def test_dropin_header_compiles_against_the_mocks():
     """include/PnPsolver_hip.hpp instantiated on mocks derived from tests/cpp/mock_slam.hpp (the GPU test runs it)"""
-    import subprocess
-    subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "pnp_dropin_gpu.cpp")])
+    dropin.syntax_only("pnp_dropin_gpu")
     hdr = open(os.path.join(ROOT, "include", "PnPsolver_hip.hpp")).read()
     for member in ("SetRansacParameters", "find(", "iterate(", "RunAll"):
         assert member in hdr, member

@@ -10,12 +10,13 @@ Figures measured on x86-64 / glibc (recorded in DESIGN.md §8o) and asserted her
   Serial against the Gauss-Newton on the ground-truth inliers: see GN_ROT_MEASURED / GN_TRANS_MEASURED below."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
 import poseopt_cases as pc
+import ref_shim
 from orbslamm_amd import optimizer as opt
 from orbslamm_amd._lib import KP_DTYPE, ORBX_E_INVALID, ORBX_E_UNSUPPORTED
 
@@ -45,17 +46,14 @@ def test_header_declares_and_library_exports_the_poseopt_block():
     import orbslamm_amd
     assert orbslamm_amd.pose_optimization is opt.pose_optimization and orbslamm_amd.pose_optimization_batch is opt.pose_optimization_batch
     assert opt.RESULT_DTYPE.itemsize == pc.REF_RESULT.itemsize == 176
-    # the kernel and the restatement share no header
-    ref = open(os.path.join(ROOT, "tools", "poseopt_ref.hpp")).read()
-    assert '#include "' not in ref
+    ref_shim.assert_shares_no_code_with_the_library(os.path.join(ROOT, "tools", "poseopt_ref.hpp"))
     for name in ("orbg_kernels.hip", "orbo_kernels.hip", "orbo_host.inc"):
         assert "poseopt_ref" not in open(os.path.join(ROOT, "orbslamm_amd", "csrc", name)).read()
 
 
 def test_dropin_header_compiles_against_the_mock():
     """include/Optimizer_hip.hpp instantiated on tests/cpp/mock_poseopt.hpp (the GPU test runs it)"""
-    subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "poseopt_dropin_gpu.cpp")])
+    dropin.syntax_only("poseopt_dropin_gpu")
     hdr = open(os.path.join(ROOT, "include", "Optimizer_hip.hpp")).read()
     for member in ("PoseOptimizationT", "Run(", "RunAll(", "stereo"):
         assert member in hdr, member

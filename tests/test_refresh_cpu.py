@@ -10,6 +10,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import dropin
 import refresh_cases as rc
 from orbslamm_amd import _lib
 from orbslamm_amd._lib import ORBX_E_INVALID, ORBX_OK, lib, ptr
@@ -236,4 +237,4 @@ def test_refusals_that_need_no_gpu():
 @pytest.mark.parametrize("name", ["refresh_dropin_gpu"])
 def test_the_dropin_compiles_against_the_mocks(name):
     """include/MapPoint_hip.hpp over tests/cpp/mock_refresh.hpp, warnings as errors (syntax and types only: nothing is linked or run)"""
-    subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", name + ".cpp")])
+    dropin.syntax_only(name)

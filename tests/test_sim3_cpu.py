@@ -9,6 +9,8 @@ import re
 import numpy as np
 import pytest
 
+import dropin
+import ref_shim
 import sim3_cases as sc
 from orbslamm_amd.sim3 import make_sim3_sets
 
@@ -347,15 +349,12 @@ def test_header_declares_and_library_exports_the_orbs_block():
 def test_result_structs_match_the_restatement():
     from orbslamm_amd.sim3 import HYP_DTYPE, OrbsHypothesis, OrbsResult
     assert C.sizeof(OrbsHypothesis) == 120 == HYP_DTYPE.itemsize and C.sizeof(OrbsResult) == 36 * 4
-    src = open(os.path.join(ROOT, "tools", "sim3_ref.hpp")).read()
-    assert "orbslamm_hip.h" not in src.split("#pragma once")[1] and "#include \"" not in src   # shares no header with the library
+    ref_shim.assert_shares_no_code_with_the_library(os.path.join(ROOT, "tools", "sim3_ref.hpp"))
 
 
 def test_dropin_header_compiles_against_the_mocks():
     """include/Sim3Solver_hip.hpp instantiated on tests/cpp/mock_slam.hpp's KeyFrame / MapPoint (the GPU test runs it)"""
-    import subprocess
-    subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "sim3_dropin_gpu.cpp")])
+    dropin.syntax_only("sim3_dropin_gpu")
     hdr = open(os.path.join(ROOT, "include", "Sim3Solver_hip.hpp")).read()
     for member in ("SetRansacParameters", "find(", "iterate(", "GetEstimatedRotation", "GetEstimatedTranslation", "GetEstimatedScale", "RunAll"):
         assert member in hdr, member

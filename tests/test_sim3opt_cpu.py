@@ -11,11 +11,12 @@ Figures measured on x86-64 / glibc (recorded in DESIGN.md §8p) and asserted her
   Serial against the Gauss-Newton on the ground-truth inliers: 6.9e-6 rad / 3.2e-5 / 7.1e-5 in scale (GN_*_MEASURED below)."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import dropin
+import ref_shim
 import sim3opt_cases as sc
 from orbslamm_amd import optimizer as opt
 from orbslamm_amd._lib import ORBX_E_INVALID, ORBX_E_UNSUPPORTED
@@ -55,9 +56,10 @@ def test_header_declares_and_library_exports_the_sim3opt_block():
     assert orbslamm_amd.sim3_from_rts is opt.sim3_from_rts
     assert opt.SIM3_PROBLEM_DTYPE.itemsize == sc.REF_PROBLEM.itemsize == 200 and opt.SIM3_CORR_DTYPE.itemsize == 52
     assert opt.SIM3_RESULT_DTYPE.itemsize == sc.REF_RESULT.itemsize == 128
-    # the kernel and the restatement share no header; the restatement includes poseopt_ref.hpp alone
-    ref = open(os.path.join(ROOT, "tools", "sim3opt_ref.hpp")).read()
-    assert re.findall(r'#include "([^"]+)"', ref) == ["poseopt_ref.hpp"]
+    # the restatement includes poseopt_ref.hpp alone
+    ref = os.path.join(ROOT, "tools", "sim3opt_ref.hpp")
+    ref_shim.assert_shares_no_code_with_the_library(ref)
+    assert ref_shim.quoted_includes(ref)[1:] == [os.path.join(ROOT, "tools", "poseopt_ref.hpp")]
     for name in ("orbg_kernels.hip", "orbz_kernels.hip", "orbz_host.inc"):
         text = open(os.path.join(ROOT, "orbslamm_amd", "csrc", name)).read()
         assert "sim3opt_ref" not in text and "poseopt_ref" not in text
@@ -65,8 +67,7 @@ def test_header_declares_and_library_exports_the_sim3opt_block():
 
 def test_dropin_header_compiles_against_the_mocks():
     """include/Optimizer_hip.hpp's OptimizeSim3T instantiated on tests/cpp/mock_sim3opt.hpp (the GPU test runs it)"""
-    subprocess.check_call(["g++", "-std=c++11", "-fsyntax-only", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           "-I", os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "sim3opt_dropin_gpu.cpp")])
+    dropin.syntax_only("sim3opt_dropin_gpu")
     hdr = open(os.path.join(ROOT, "include", "Optimizer_hip.hpp")).read()
     for member in ("OptimizeSim3T", "PoseOptimizationT", "struct Job", "stereo", "orbz_optimize_sim3"):
         assert member in hdr, member

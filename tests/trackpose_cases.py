@@ -12,7 +12,7 @@ import numpy as np
 import localmap_cases as lc
 import poseopt_cases as pc
 from orbslamm_amd._lib import KP_DTYPE
-from ref_shim import build_ref_shim, p
+from ref_shim import cached_shim, p
 
 NLEVELS = lc.NLEVELS
 FLAG_BAD, FLAG_OBSERVED = lc.FLAG_BAD, lc.FLAG_OBSERVED
@@ -150,15 +150,17 @@ BRANCH = {
 
 
 # ------------------------------------------------------------------ the restatement
-@functools.lru_cache(maxsize=1)
-def ref_lib():
-    L = build_ref_shim("trackpose_ref")
+def _declare(L):
     assert [L.trackposeref_sizes(i) for i in range(3)] == [REF_KEY.itemsize, REF_RESULT.itemsize, 4 * len(BRANCH_NAMES)]
     vp = C.c_void_p
     L.trackposeref_run.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     L.trackposeref_motion_model_verdict.argtypes = [C.c_int, C.c_int, C.c_int, vp]
     L.trackposeref_local_map_verdict.argtypes = [C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long]
-    return L
+
+
+def ref_lib():
+    """the restatement as a shared object (built once per process)"""
+    return cached_shim("trackpose_ref", _declare)
 
 
 def ref_keys(keys):

@@ -13,7 +13,7 @@ import numpy as np
 import trackpose_cases as tc
 from matcher_cases import noisy_copies
 from orbslamm_amd import synth
-from ref_shim import build_ref_shim, p
+from ref_shim import cached_shim, p
 
 FLAG_BAD, FLAG_OBSERVED = tc.FLAG_BAD, tc.FLAG_OBSERVED
 NO_VOTE = 1 << 30
@@ -113,16 +113,18 @@ BRANCH = {
 
 
 # ------------------------------------------------------------------ the restatement
-@functools.lru_cache(maxsize=1)
-def ref_lib():
-    L = build_ref_shim("trackref_ref")
+def _declare(L):
     assert [L.trackrefref_sizes(i) for i in range(3)] == [tc.REF_KEY.itemsize, REF_RESULT.itemsize, 4 * len(BRANCH_NAMES)]
     vp, ci = C.c_void_p, C.c_int
     L.trackrefref_validity.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp]
     L.trackrefref_validity.restype = None
     L.trackrefref_run.argtypes = [vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp]
     L.trackrefref_verdict.argtypes = [ci, ci]
-    return L
+
+
+def ref_lib():
+    """the restatement as a shared object (built once per process)"""
+    return cached_shim("trackref_ref", _declare)
 
 
 def _pool_arrays(case, pool):

@@ -7,6 +7,11 @@
 // includes no header of the library and is built with g++ -ffp-contract=off (every operation one IEEE op).  The OpenCV
 // pieces are restated from the published 3.0 source and are UNPINNED.
 //
+// Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:979-1102) is the same code except at three points.  Two are parameters here,
+// which tools/loopfuse_ref.hpp sets: invz (`1/z` in float here, `1.0/z` rounded to float there: project's Invz) and the 5.99
+// chi-square test of the window (absent there: a null invLevelSigma2).  The third, what a hit does to the map, belongs to the
+// serial loop each caller models (Model::fuse here, loopfuse_ref::Model::apply there).
+//
 // PredictScale is the DIRECT formula here, ceil(log(ratio)/logScaleFactor) in float (tests/cpp/mock_slam.hpp:65-68), not a
 // break table.  Defined choices, the same on the device:
 //   - a level that is NaN or outside [0, nlevels) ends the pair (LEVEL_RANGE; the reference reads mvScaleFactors out of
@@ -21,7 +26,9 @@
 #include <cstring>
 #include <vector>
 
-namespace fuse_ref {
+// The records live in a namespace of their own, so that argument-dependent lookup on them finds no function: loopfuse_ref
+// re-exports them and defines a `project` of its own, and a call of either one, unqualified, must not see the other.
+namespace fuse_records {
 
 struct KeyPt { float x, y, size, angle, response; int32_t octave, class_id; };   // cv::KeyPoint's layout
 struct Grid { float minX, minY, invW, invH; int32_t cols, rows; };
@@ -30,15 +37,30 @@ struct Point { float pos[3], normal[3], minDistance, maxDistance; uint8_t desc[3
 struct Result { int32_t bestIdx, bestDist; float u, v; int8_t level; uint8_t status, pad[2]; };  // OrblFuseResult's layout
 struct Gates { float z, dist3D, minDistance, maxDistance, ratio, radius; double dot; };           // what the gates compared
 
+}  // namespace fuse_records
+
+namespace fuse_ref {
+
+using fuse_records::KeyPt;
+using fuse_records::Grid;
+using fuse_records::Target;
+using fuse_records::Point;
+using fuse_records::Result;
+using fuse_records::Gates;
+
 enum Status : uint8_t { DEPTH = 0, OUTSIDE_IMAGE, DISTANCE, VIEW_ANGLE, LEVEL_RANGE, NO_CANDIDATE, FOUND };
 const int TH_LOW = 50;
 
 // MapPoint::PredictScale's expression (MapPoint.cc:393) as a float; the caller range-checks before any conversion
 inline float predictLevel(float ratio, float logScaleFactor) { return std::ceil(std::log(ratio) / logScaleFactor); }
 
+// :862 `const float invz = 1/p3Dc.at<float>(2);`: a float division
+typedef float (*Invz)(float);
+inline float invzFloatDivision(float z) { return 1.0f / z; }
+
 // :855-892 for one pair.  Returns true when the pair reaches the window search; r holds u, v, level and the gate's status
 inline bool project(const Target& T, const Point& P, float th, const float* scaleFactors, int nlevels, float logScaleFactor, Result& r,
-                    Gates* g = nullptr)
+                    Gates* g = nullptr, Invz invzOf = invzFloatDivision)
 {
     r.bestIdx = -1; r.bestDist = 256; r.u = 0.f; r.v = 0.f; r.level = -1; r.status = DEPTH; r.pad[0] = r.pad[1] = 0;
     if (g) { g->z = g->dist3D = g->minDistance = g->maxDistance = g->ratio = g->radius = NAN; g->dot = NAN; }
@@ -51,7 +73,7 @@ inline bool project(const Target& T, const Point& P, float th, const float* scal
     }
     if (g) g->z = pc[2];
     if (pc[2] < 0.0f) return false;
-    const float invz = 1 / pc[2];
+    const float invz = invzOf(pc[2]);
     const float x = pc[0] * invz, y = pc[1] * invz;
     const float u = T.K[0] * x + T.K[2], v = T.K[1] * y + T.K[3];
     r.u = u; r.v = v;
@@ -128,7 +150,9 @@ inline int descriptorDistance(const uint8_t* a, const uint8_t* b)
     return d;
 }
 
-// :894-951 for a pair that passed project(): the best feature of the window under the point's descriptor
+// :894-951 for a pair that passed project(): the best feature of the window under the point's descriptor; a null
+// invLevelSigma2 leaves the chi-square test out (bestDist starts at INT_MAX in the reference: reported as 256, above every
+// distance)
 inline void searchWindow(const CellGrid& grid, const KeyPt* keys, const uint8_t* desc, float u, float v, float radius, int pred,
                          const float* invLevelSigma2, const uint8_t* dMP, int& bestIdx, int& bestDist)
 {
@@ -140,9 +164,11 @@ inline void searchWindow(const CellGrid& grid, const KeyPt* keys, const uint8_t*
         const KeyPt& kp = keys[idx];
         const int kpLevel = kp.octave;
         if (kpLevel < pred - 1 || kpLevel > pred) continue;
-        const float ex = u - kp.x, ey = v - kp.y;
-        const float e2 = ex * ex + ey * ey;
-        if (e2 * invLevelSigma2[kpLevel] > 5.99) continue;
+        if (invLevelSigma2) {
+            const float ex = u - kp.x, ey = v - kp.y;
+            const float e2 = ex * ex + ey * ey;
+            if (e2 * invLevelSigma2[kpLevel] > 5.99) continue;
+        }
         const int dist = descriptorDistance(dMP, desc + (size_t)idx * 32);
         if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
     }
@@ -150,10 +176,11 @@ inline void searchWindow(const CellGrid& grid, const KeyPt* keys, const uint8_t*
 
 // :855-951 for one (target, point) pair
 inline Result pair(const Target& T, const CellGrid& grid, const KeyPt* keys, const uint8_t* desc, const Point& P, float th,
-                   const float* scaleFactors, const float* invLevelSigma2, int nlevels, float logScaleFactor, Gates* g = nullptr)
+                   const float* scaleFactors, const float* invLevelSigma2, int nlevels, float logScaleFactor, Gates* g = nullptr,
+                   Invz invzOf = invzFloatDivision)
 {
     Result r;
-    if (!project(T, P, th, scaleFactors, nlevels, logScaleFactor, r, g)) return r;
+    if (!project(T, P, th, scaleFactors, nlevels, logScaleFactor, r, g, invzOf)) return r;
     int bi, bd;
     searchWindow(grid, keys, desc, r.u, r.v, th * scaleFactors[r.level], r.level, invLevelSigma2, P.desc, bi, bd);
     r.bestIdx = bi; r.bestDist = bd;

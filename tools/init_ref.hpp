@@ -2,8 +2,8 @@
 // pieces it calls: SVD (JacobiSVDImpl_<float> behind cv::SVD::compute / cv::SVDecomp), gemm's small-matrix and
 // transposed branches, 3x3 invert / determinant, MatExpr scaling, addWeighted, norm and dot on CV_32F.  It is the checker
 // of the device Initializer (orbslamm_amd/csrc/orbi_kernels.hip): it shares no header with the library and is built with
-// g++ -ffp-contract=off (every operation one IEEE op).  The OpenCV pieces are restated from the published 3.0 source and
-// are UNPINNED: no OpenCV exists to compare against.
+// g++ -ffp-contract=off (every operation one IEEE op).  The OpenCV pieces it has in common with the other restatements
+// are cv_ref.hpp's (which says how far they can be trusted); the SVD and the transposed gemm branches are here.
 //
 // Defined choices, the same on the device:
 //   - hypot inside the Jacobi rotation: lapack.cpp's written-out binary64 formula, not libm's
@@ -21,6 +21,8 @@
 #include <cstring>
 #include <utility>
 #include <vector>
+
+#include "cv_ref.hpp"
 
 namespace init_ref {
 
@@ -41,16 +43,12 @@ inline Mat eye3() { Mat m(3, 3); m.at(0, 0) = m.at(1, 1) = m.at(2, 2) = 1.f; ret
 inline Mat transpose(const Mat& a) { Mat o(a.cols, a.rows); for (int r = 0; r < a.rows; r++) for (int c = 0; c < a.cols; c++) o.at(c, r) = a.at(r, c); return o; }
 
 // ------------------------------------------------------------------------------------------------ OpenCV arithmetic
-// gemm(A, B, alpha, noArray(), 0) with flags == 0 and len == 3 (matmul.cpp's small-matrix branch): the three products
-// summed in float, left to right, then d = (float)(t*alpha + c*beta) with c = 0, beta = 0 (so -0 becomes +0)
+// gemm(A, B, alpha, noArray(), 0) with flags == 0 and len == 3: cv_ref::gemmElem per element, C absent
 inline Mat mul(const Mat& A, const Mat& B, double alpha = 1.0)
 {
     Mat o(A.rows, B.cols);
     for (int i = 0; i < A.rows; i++)
-        for (int j = 0; j < B.cols; j++) {
-            const float t = A.at(i, 0) * B.at(0, j) + A.at(i, 1) * B.at(1, j) + A.at(i, 2) * B.at(2, j);
-            o.at(i, j) = (float)((double)t * alpha + (double)0.f * 0.0);
-        }
+        for (int j = 0; j < B.cols; j++) o.at(i, j) = cv_ref::gemmElem(&A.d[(size_t)i * 3], &B.d[j], B.cols, alpha, 0.f, 0.0);
     return o;
 }
 // A*B + C (MatExpr folds it into one gemm(A, B, 1, C, 1)): the same branch with beta = 1
@@ -58,10 +56,7 @@ inline Mat mulAdd(const Mat& A, const Mat& B, const Mat& Cm)
 {
     Mat o(A.rows, B.cols);
     for (int i = 0; i < A.rows; i++)
-        for (int j = 0; j < B.cols; j++) {
-            const float t = A.at(i, 0) * B.at(0, j) + A.at(i, 1) * B.at(1, j) + A.at(i, 2) * B.at(2, j);
-            o.at(i, j) = (float)((double)t * 1.0 + (double)Cm.at(i, j) * 1.0);
-        }
+        for (int j = 0; j < B.cols; j++) o.at(i, j) = cv_ref::gemmElem(&A.d[(size_t)i * 3], &B.d[j], B.cols, 1.0, Cm.at(i, j), 1.0);
     return o;
 }
 // GEMM_1_T / GEMM_2_T take the generic kernel, GEMMSingleMul<float, double>: double sums in k order, d = (float)(s*alpha)
@@ -87,47 +82,16 @@ inline Mat mulT2(const Mat& A, const Mat& B)   // A*B.t()
         }
     return o;
 }
-// a MatExpr `alpha*A` (or A/s, -A) assigned to a Mat (MatOp_AddEx::assign): alpha 1 -> add(A, 0), alpha -1 ->
-// subtract(0, A), else convertTo with a double scale
-inline float exprScale(float x, double alpha)
-{
-    if (alpha == 1.0) return x + 0.f;
-    if (alpha == -1.0) return 0.f - x;
-    return (float)((double)x * alpha);
-}
+// a MatExpr `alpha*A` (or A/s, -A) assigned to a Mat: cv_ref::exprScale per element
+using cv_ref::exprScale;
 inline Mat exprScale(const Mat& a, double alpha) { Mat o = a; for (float& v : o.d) v = exprScale(v, alpha); return o; }
 // Mat::operator*=(double): convertTo in place, a copy when alpha is 1
 inline void scaleInPlace(Mat& a, double alpha) { if (alpha != 1.0) for (float& v : a.d) v = (float)((double)v * alpha); }
 inline Mat sub(const Mat& a, const Mat& b) { Mat o = a; for (size_t i = 0; i < o.d.size(); i++) o.d[i] = a.d[i] - b.d[i]; return o; }
-// cv::norm (normL2_<float, double>) and Mat::dot: double accumulation
-inline double norm(const Mat& a) { double s = 0; for (float v : a.d) s += (double)v * (double)v; return std::sqrt(s); }
-inline double dot(const Mat& a, const Mat& b) { double s = 0; for (size_t i = 0; i < a.d.size(); i++) s += (double)a.d[i] * (double)b.d[i]; return s; }
-// determinant / invert of a 3x3 CV_32F (lapack.cpp: det3 in double; invert's n == 3 branch, zeros when singular)
-inline double det3(const Mat& m)
-{
-    return m.at(0, 0) * ((double)m.at(1, 1) * m.at(2, 2) - (double)m.at(1, 2) * m.at(2, 1)) -
-           m.at(0, 1) * ((double)m.at(1, 0) * m.at(2, 2) - (double)m.at(1, 2) * m.at(2, 0)) +
-           m.at(0, 2) * ((double)m.at(1, 0) * m.at(2, 1) - (double)m.at(1, 1) * m.at(2, 0));
-}
-inline Mat inv3(const Mat& S)
-{
-    Mat D(3, 3);
-    double d = det3(S);
-    if (d == 0.) return D;
-    d = 1. / d;
-    const double t[9] = {
-        ((double)S.at(1, 1) * S.at(2, 2) - (double)S.at(1, 2) * S.at(2, 1)) * d,
-        ((double)S.at(0, 2) * S.at(2, 1) - (double)S.at(0, 1) * S.at(2, 2)) * d,
-        ((double)S.at(0, 1) * S.at(1, 2) - (double)S.at(0, 2) * S.at(1, 1)) * d,
-        ((double)S.at(1, 2) * S.at(2, 0) - (double)S.at(1, 0) * S.at(2, 2)) * d,
-        ((double)S.at(0, 0) * S.at(2, 2) - (double)S.at(0, 2) * S.at(2, 0)) * d,
-        ((double)S.at(0, 2) * S.at(1, 0) - (double)S.at(0, 0) * S.at(1, 2)) * d,
-        ((double)S.at(1, 0) * S.at(2, 1) - (double)S.at(1, 1) * S.at(2, 0)) * d,
-        ((double)S.at(0, 1) * S.at(2, 0) - (double)S.at(0, 0) * S.at(2, 1)) * d,
-        ((double)S.at(0, 0) * S.at(1, 1) - (double)S.at(0, 1) * S.at(1, 0)) * d};
-    for (int i = 0; i < 9; i++) D.d[i] = (float)t[i];
-    return D;
-}
+inline double norm(const Mat& a) { return cv_ref::norm(a.d.data(), (int)a.d.size()); }
+inline double dot(const Mat& a, const Mat& b) { return cv_ref::dot(a.d.data(), b.d.data(), (int)a.d.size()); }
+inline double det3(const Mat& m) { return cv_ref::det3(m.d.data()); }
+inline Mat inv3(const Mat& S) { Mat D(3, 3); cv_ref::inv33(S.d.data(), D.d.data()); return D; }
 
 // cv::RNG
 struct Rng {
@@ -135,16 +99,6 @@ struct Rng {
     explicit Rng(uint64_t s) : state(s ? s : 0xffffffffu) {}
     unsigned next() { state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32); return (unsigned)state; }
 };
-
-// lapack.cpp's hypot
-inline double hypotCv(double a, double b)
-{
-    a = std::abs(a);
-    b = std::abs(b);
-    if (a > b) { b /= a; return a * std::sqrt(1 + b * b); }
-    if (b > 0) { a /= b; return b * std::sqrt(1 + a * a); }
-    return 0;
-}
 
 // JacobiSVDImpl_<float>(At, astep, W, Vt, vstep, m, n, n1, FLT_MIN, FLT_EPSILON*2), steps in elements
 inline void jacobiSVD(float* At, int astep, float* Wout, float* Vt, int vstep, int m, int n, int n1)
@@ -169,7 +123,7 @@ inline void jacobiSVD(float* At, int astep, float* Wout, float* Vt, int vstep, i
                 for (int k = 0; k < m; k++) p += (double)Ai[k] * Aj[k];
                 if (std::abs(p) <= eps * std::sqrt((double)a * b)) continue;
                 p *= 2;
-                const double beta = a - b, gamma = hypotCv(p, beta);
+                const double beta = a - b, gamma = cv_ref::hypotCv(p, beta);
                 float c, s;
                 if (beta < 0) {
                     const double delta = (gamma - beta) * 0.5;
@@ -270,7 +224,7 @@ inline void svd(const Mat& src, bool fullUV, Mat& w, Mat& u, Mat& vt)
 // Thirdparty/DBoW2/DUtils/Random.cpp over the process's rand()
 inline bool& alreadySeeded() { static bool s = false; return s; }
 inline void seedRandOnce(int seed) { if (!alreadySeeded()) { srand(seed); alreadySeeded() = true; } }
-inline int randomInt(int min, int max) { const int d = max - min + 1; return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min; }
+using cv_ref::randomInt;
 // Initialize's set drawing (:67-97) for N matches: `iterations` sets of 8, flattened
 inline std::vector<int32_t> drawSets(int N, int iterations)
 {
@@ -292,7 +246,7 @@ inline std::vector<int32_t> drawSets(int N, int iterations)
 }
 
 // ------------------------------------------------------------------------------------------------ Initializer
-// Initialize's outputs and diagnostics; the layout equals OrbiResult of include/orbslamm_hip.h field for field
+// Initialize's outputs and diagnostics; the layout equals OrbiResult of the C ABI field for field
 struct Result {
     int32_t ok = 0;
     int32_t reconH = 0;      // 1: ReconstructH ran, 0: ReconstructF (or neither: nCand 0, rtState 0)

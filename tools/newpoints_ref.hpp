@@ -4,8 +4,8 @@
 // call: gemm's small-matrix and transposed branches, the 3x3 invert, MatExpr scaling, addWeighted, norm and dot on CV_32F,
 // and JacobiSVDImpl_<float> behind cv::SVD::compute.  It is the checker of the device CreateNewMapPoints
 // (orbslamm_amd/csrc/orbl_kernels.hip): it includes no header of the library and is built with g++ -ffp-contract=off
-// (every operation one IEEE op).  The OpenCV pieces are restated from the published 3.0 source and are UNPINNED (DESIGN.md
-// section 2).
+// (every operation one IEEE op).  The OpenCV pieces it has in common with the other restatements are cv_ref.hpp's (which
+// says how far they can be trusted); the 4x4 Jacobi SVD and the transposed gemm are here.
 //
 // The neighbour loop here is SERIAL, as the reference's: neighbour() handles one neighbour given the match list that
 // SearchForTriangulation returned under the skip flags as they stand, and folds its successes into the flags before the
@@ -24,6 +24,8 @@
 #include <cstdint>
 #include <cstring>
 
+#include "cv_ref.hpp"
+
 namespace newpoints_ref {
 
 struct KeyPt { float x, y, size, angle, response; int32_t octave, class_id; };   // cv::KeyPoint's layout
@@ -33,13 +35,7 @@ struct NewPoint { int32_t neighbour, idx1, idx2; float pos[3], normal[3], minDis
 enum Status : uint8_t { NEIGHBOUR_SKIPPED = 0, FEATURE_SKIPPED, NO_MATCH, PARALLAX, X3D_ZERO, Z1, Z2, REPROJ1, REPROJ2, DIST_ZERO, SCALE, ACCEPTED };
 
 // ------------------------------------------------------------------------------------------------ OpenCV arithmetic
-// gemm with flags == 0 and len == 3 (matmul.cpp's small-matrix branch): three float products summed left to right, then
-// d = (float)(t*alpha + c*beta)
-inline float gemmElem(const float* a, const float* b, int bstep, double alpha, float c, double beta)
-{
-    const float t = a[0] * b[0] + a[1] * b[bstep] + a[2] * b[2 * bstep];
-    return (float)((double)t * alpha + (double)c * beta);
-}
+using cv_ref::gemmElem;   // gemm with flags == 0 and len == 3, one element
 inline void mul33(const float* A, const float* B, float* D)
 {
     float o[9];
@@ -56,40 +52,11 @@ inline void mulT2(const float* A, const float* B, double alpha, float* D)
             D[3 * i + j] = (float)(s * alpha);
         }
 }
-// a MatExpr alpha*A assigned to a Mat (MatOp_AddEx::assign): 1 -> A + 0, -1 -> 0 - A, else convertTo with a double scale
-inline float exprScale(float x, double alpha)
-{
-    if (alpha == 1.0) return x + 0.f;
-    if (alpha == -1.0) return 0.f - x;
-    return (float)((double)x * alpha);
-}
-// cv::scaleAdd(a, alpha, b) on CV_32F: the scale converted to float, a float product, a float sum
-inline float scaleAdd(float a, double alpha, float b) { const float fa = (float)alpha; return a * fa + b; }
-inline double norm3(const float* v) { double s = 0; for (int i = 0; i < 3; i++) s += (double)v[i] * (double)v[i]; return std::sqrt(s); }
-inline double dot3(const float* a, const float* b) { double s = 0; for (int i = 0; i < 3; i++) s += (double)a[i] * (double)b[i]; return s; }
-// cv::invert's n == 3 branch (det3 and the cofactors in double, zeros when singular)
-inline void inv33(const float* S, float* D)
-{
-    double d = S[0] * ((double)S[4] * S[8] - (double)S[5] * S[7]) - S[1] * ((double)S[3] * S[8] - (double)S[5] * S[6]) +
-               S[2] * ((double)S[3] * S[7] - (double)S[4] * S[6]);
-    if (d == 0.) { for (int i = 0; i < 9; i++) D[i] = 0.f; return; }
-    d = 1. / d;
-    const double t[9] = {((double)S[4] * S[8] - (double)S[5] * S[7]) * d, ((double)S[2] * S[7] - (double)S[1] * S[8]) * d,
-                         ((double)S[1] * S[5] - (double)S[2] * S[4]) * d, ((double)S[5] * S[6] - (double)S[3] * S[8]) * d,
-                         ((double)S[0] * S[8] - (double)S[2] * S[6]) * d, ((double)S[2] * S[3] - (double)S[0] * S[5]) * d,
-                         ((double)S[3] * S[7] - (double)S[4] * S[6]) * d, ((double)S[1] * S[6] - (double)S[0] * S[7]) * d,
-                         ((double)S[0] * S[4] - (double)S[1] * S[3]) * d};
-    for (int i = 0; i < 9; i++) D[i] = (float)t[i];
-}
-// lapack.cpp's hypot
-inline double hypotCv(double a, double b)
-{
-    a = std::fabs(a);
-    b = std::fabs(b);
-    if (a > b) { b /= a; return a * std::sqrt(1 + b * b); }
-    if (b > 0) { a /= b; return b * std::sqrt(1 + a * a); }
-    return 0;
-}
+using cv_ref::exprScale;
+using cv_ref::scaleAdd;
+using cv_ref::inv33;
+inline double norm3(const float* v) { return cv_ref::norm(v, 3); }
+inline double dot3(const float* a, const float* b) { return cv_ref::dot(a, b, 3); }
 // JacobiSVDImpl_<float> on a 4x4: At (rows = columns of the source), Vt; the rotations and the sort (the random
 // completion of a zero singular value touches only At, which CreateNewMapPoints does not read)
 inline void jacobi4(float At[16], float Vt[16])
@@ -113,7 +80,7 @@ inline void jacobi4(float At[16], float Vt[16])
                 for (int k = 0; k < n; k++) p += (double)Ai[k] * Aj[k];
                 if (std::fabs(p) <= eps * std::sqrt((double)a * b)) continue;
                 p *= 2;
-                const double beta = a - b, gamma = hypotCv(p, beta);
+                const double beta = a - b, gamma = cv_ref::hypotCv(p, beta);
                 float c, s;
                 if (beta < 0) {
                     const double delta = (gamma - beta) * 0.5;

@@ -19,17 +19,12 @@
 #include <cstring>
 #include <vector>
 
+#include "cv_ref.hpp"
+
 namespace pnp_ref {
 
 // ------------------------------------------------------------------ OpenCV 3.0, binary64
-inline double hypotCv(double a, double b)
-{
-    a = std::fabs(a);
-    b = std::fabs(b);
-    if (a > b) { b /= a; return a * std::sqrt(1 + b * b); }
-    if (b > 0) { a /= b; return b * std::sqrt(1 + a * a); }
-    return 0;
-}
+using cv_ref::hypotCv;   // lapack.cpp's hypot, in binary64 here
 
 // JacobiSVDImpl_<double>(At, W, Vt, m, n, n1 = n, DBL_MIN, DBL_EPSILON*10): At holds n rows of m (the transposed source),
 // on return row i is the i-th left singular vector; Vt (n x n) row i the i-th right one; W descending.
@@ -498,27 +493,8 @@ struct Result {
     float Tcw[16], best_Tcw[16];
 };
 
-// DUtils::Random::RandomInt(0, k - 1) over libc's rand()
-inline int randomInt(int k) { return (int)(((double)std::rand() / ((double)RAND_MAX + 1.0)) * k); }
-
-// the draw of ref:191-201: vAvailableIndices[idx] = back() with idx the drawn VALUE, so a set can repeat a point
-inline std::vector<int32_t> drawSets(int n, int iters)
-{
-    std::vector<int32_t> out((size_t)iters * 4);
-    std::vector<int32_t> avail(n);
-    for (int it = 0; it < iters; it++) {
-        for (int i = 0; i < n; i++) avail[i] = i;
-        int live = n;
-        for (int j = 0; j < 4; j++) {
-            const int randi = randomInt(live);
-            const int idx = avail[randi];
-            out[(size_t)it * 4 + j] = idx;
-            avail[idx] = avail[live - 1];
-            live--;
-        }
-    }
-    return out;
-}
+// the draw of ref:191-201: `iters` sets of 4
+inline std::vector<int32_t> drawSets(int n, int iters) { return cv_ref::drawSets(n, iters, 4); }
 
 class PnPsolver {
 public:

@@ -3,8 +3,8 @@
 // to matrix (cvRodrigues2), cv::reduce SUM over columns, cv::pow(., 2), gemm's small-matrix and transposed branches,
 // MatExpr scaling, norm and dot on CV_32F.  It is the checker of the device Sim3Solver (orbslamm_amd/csrc/
 // orbs_kernels.hip): it shares no header with the library and is built with g++ -ffp-contract=off (every operation one
-// IEEE operation).  The OpenCV pieces are restated from the published 3.0 algorithm and are UNPINNED:
-// no OpenCV exists to compare against.
+// IEEE operation).  The OpenCV pieces it has in common with the other restatements, and the set draw it has in common
+// with pnp_ref, are cv_ref.hpp's (which says how far they can be trusted); cv::eigen, Rodrigues and reduce are here.
 //
 // Kept as the reference has them:
 //   - mvnMaxError1/2 are vector<size_t>: the threshold is (size_t)(9.210 * (double)sigma2), compared as a float
@@ -26,21 +26,19 @@
 #include <cstring>
 #include <vector>
 
+#include "cv_ref.hpp"
+
 namespace sim3_ref {
 
 // ------------------------------------------------------------------------------------------------ OpenCV arithmetic
-// gemm(A, B, alpha, C, beta) with flags == 0 and len == 3 (matmul.cpp's small-matrix branch): the three products summed
-// in float, left to right, then d = (float)(t*alpha + c*beta) in double; C absent: c = 0, beta = 0.
+// gemm(A, B, alpha, C, beta) with flags == 0 and len == 3: cv_ref::gemmElem per element; C absent: c = 0, beta = 0.
 // A is 3x3 row-major, B and C are 3 x cols row-major.
 inline void gemm3(const float* A, const float* B, int cols, double alpha, const float* Cm, double beta, float* D)
 {
     float o[9];
     for (int i = 0; i < 3; i++)
-        for (int j = 0; j < cols; j++) {
-            const float t = A[i * 3 + 0] * B[0 * cols + j] + A[i * 3 + 1] * B[1 * cols + j] + A[i * 3 + 2] * B[2 * cols + j];
-            const float c = Cm ? Cm[i * cols + j] : 0.f;
-            o[i * cols + j] = (float)((double)t * alpha + (double)c * (Cm ? beta : 0.0));
-        }
+        for (int j = 0; j < cols; j++)
+            o[i * cols + j] = cv_ref::gemmElem(A + i * 3, B + j, cols, alpha, Cm ? Cm[i * cols + j] : 0.f, Cm ? beta : 0.0);
     std::memcpy(D, o, sizeof(float) * 3 * cols);
 }
 // A*B.t() (GEMM_2_T takes the generic kernel, GEMMSingleMul<float, double>): double sums in k order, d = (float)(s*alpha)
@@ -53,17 +51,9 @@ inline void gemm3T2(const float* A, const float* B, float* D)
             D[i * 3 + j] = (float)(s * 1.0);
         }
 }
-// a MatExpr `alpha*A` (or A/s) assigned to a Mat (MatOp_AddEx::assign): alpha 1 -> add(A, 0), alpha -1 -> subtract(0, A),
-// else convertTo with a double scale
-inline float exprScale(float x, double alpha)
-{
-    if (alpha == 1.0) return x + 0.f;
-    if (alpha == -1.0) return 0.f - x;
-    return (float)((double)x * alpha);
-}
-// cv::norm (normL2_<float, double>) and Mat::dot: double accumulation in element order
-inline double norm(const float* a, int n) { double s = 0; for (int i = 0; i < n; i++) s += (double)a[i] * (double)a[i]; return std::sqrt(s); }
-inline double dot(const float* a, const float* b, int n) { double s = 0; for (int i = 0; i < n; i++) s += (double)a[i] * (double)b[i]; return s; }
+using cv_ref::exprScale;
+using cv_ref::norm;
+using cv_ref::dot;
 
 // cv::reduce(P, C, 1, CV_REDUCE_SUM) on a 3x3 CV_32F (reduceC_<float, float, OpAdd<float>>): per row a0 = p[0], a1 = p[1],
 // the tail loop adds p[2] to a0, then a0 + a1
@@ -75,16 +65,6 @@ inline void reduceSumCols3(const float* P, float* C)
         a0 = a0 + P[r * 3 + 2];
         C[r] = a0 + a1;
     }
-}
-
-// lapack.cpp's hypot, instantiated for float
-inline float hypotCv(float a, float b)
-{
-    a = std::abs(a);
-    b = std::abs(b);
-    if (a > b) { b /= a; return a * std::sqrt(1 + b * b); }
-    if (b > 0) { a /= b; return b * std::sqrt(1 + a * a); }
-    return 0;
 }
 
 // cv::eigen(src, evals, evects) on an n x n symmetric CV_32F: JacobiImpl_<float> on a copy of src (only its upper
@@ -136,8 +116,8 @@ inline void eigenSym(const float* src, int n, float* W, float* V)
         const float p = A[astep * k + l];
         if (std::abs(p) <= eps) break;
         const float y = (float)((W[l] - W[k]) * 0.5);
-        float t = std::abs(y) + hypotCv(p, y);
-        float s = hypotCv(p, t);
+        float t = std::abs(y) + cv_ref::hypotCv(p, y);
+        float s = cv_ref::hypotCv(p, t);
         const float c = t / s;
         s = p / s; t = (p / t) * p;
         if (y < 0) s = -s, t = -t;
@@ -200,29 +180,8 @@ inline void rodrigues(const float* v, float* Rout)
     for (int k = 0; k < 9; k++) Rout[k] = (float)(c * I[k] + c1 * rrt[k] + s * r_x[k]);
 }
 
-// ------------------------------------------------------------------------------------------------ DUtils::Random
-inline int randomInt(int min, int max) { const int d = max - min + 1; return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min; }
-
-// one set of iterate's draw (Sim3Solver.cc:163-177) on an array of N with a live length
-inline void drawSet(int N, std::vector<int32_t>& avail, int32_t out[3])
-{
-    avail.resize((size_t)N);
-    for (int i = 0; i < N; i++) avail[i] = i;
-    int live = N;
-    for (short i = 0; i < 3; ++i) {
-        const int randi = randomInt(0, live - 1);
-        const int idx = avail[randi];
-        out[i] = idx;
-        avail[idx] = avail[live - 1];   // idx is the drawn VALUE, as the reference has it
-        live--;
-    }
-}
-inline std::vector<int32_t> drawSets(int N, int iterations)
-{
-    std::vector<int32_t> sets((size_t)iterations * 3, 0), avail;
-    for (int it = 0; it < iterations; it++) drawSet(N, avail, &sets[(size_t)it * 3]);
-    return sets;
-}
+// iterate's set draw (Sim3Solver.cc:163-177): `iterations` sets of 3
+inline std::vector<int32_t> drawSets(int N, int iterations) { return cv_ref::drawSets(N, iterations, 3); }
 
 // x86's double -> int (cvttsd2si)
 inline int toInt(double v) { return (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
