@@ -44,6 +44,11 @@
 //       MapPoint::mfMinDistance / mfMaxDistance are read raw, as SearchInNeighborsT does.  predict: the
 //       tree's own PredictScale as (ratio, logScaleFactor) -> level where its log resolves to the double overload; null: the
 //       float form.  Monocular only.  Every call runs on the calling thread's matcher handle (orbm_thread_handle).
+//
+//   CorrectLoopPosesT<KeyFrame, MapPoint, Sim3>::Run(store, keyframes, pCurrentKF, Scw, alreadyCorrected, scaleFactors,
+//                                                    CorrectedSim3, NonCorrectedSim3, hooks)
+//       the drop-in for LoopClosing.cc:455-524 and MultiMapper.cc:523-595 (orbe_correct_sim3, include/orbslamm_correct.h,
+//       DESIGN.md §8x): documented at the class, below.
 #pragma once
 
 #include <algorithm>
@@ -339,6 +344,96 @@ public:
             ret[(size_t)k].nFound = out[(size_t)k].n_found; ret[(size_t)k].nInliers = o.n_in; ret[(size_t)k].opt = o;
         }
         return ret;
+    }
+};
+
+// CorrectLoopPosesT -- the correction of LoopClosing::CorrectLoop (src/LoopClosing.cc:455-524) and of
+// MultiMapper::UpdatePosesAndAdd (src/MultiMapper.cc:523-595) in ONE device call over the keyframe store (orbe_correct_sim3):
+//     KeyFrameAndPose CorrectedSim3, NonCorrectedSim3;                       // :444; :445 and :446 are the call's
+//     { unique_lock<mutex> lock(mpMap->mMutexMapUpdate);                     // :451
+//       CorrectLoopPosesT<KeyFrame, MapPoint, g2o::Sim3>::Run(store, mvpCurrentConnectedKFs, mpCurrentKF, mg2oScw, {}, mvScaleFactors,
+//                                                            CorrectedSim3, NonCorrectedSim3, hooks);
+//       ... :523 pKFi->UpdateConnections() of every listed keyframe stays the caller's (it reads no pose: orbn_update_connections
+//       serves it in one call), then :526 the loop fusion as before }
+// keyframes: mvpCurrentConnectedKFs with mpCurrentKF pushed back (:441-442), or mvpCurrentMapKFs; slot = mnId, as the other
+// drop-ins.  alreadyCorrected: the MapPoints that carry mnCorrectedByKF == pCurrentKF->mnId from an earlier call (:496; none in
+// a first correction by this keyframe).  The store must hold every listed keyframe's match slots, every set keyframe's centre and
+// octaves as they are NOW, and mpRefKF of the points (orbu_point_set_ref_kf).  Run fills the two maps (:469, :476), calls
+// SetPose with the corrected poses (:520), and writes SetWorldPos, mnCorrectedByKF, mnCorrectedReference (:505-507) and, where
+// UpdateNormalAndDepth is defined and ran (:508), the normal and the bounds of every moved point from the call's records; the
+// pool's records and the store's centres are committed by the same call.  Where the reference walks map<KeyFrame*, g2o::Sim3> in
+// heap-address order the device takes ascending mnId: the DEFINED choice of the headers.  `hooks` is the caller's object:
+//   int32_t SlotOfKF(KeyFrame*); int32_t IdOfPoint(MapPoint*); MapPoint* PointOfId(int32_t)
+//   void Pose(KeyFrame*, float Tiw[12])              GetPose() as three rows [R | t]
+//   void SetPose(KeyFrame*, const float Tiw[12])     pKFi->SetPose(correctedTiw)
+//   void SetWorldPos(MapPoint*, const float[3]); void SetNormalAndDepth(MapPoint*, const float normal[3], float minD, float maxD)
+// A refusal of the library throws std::runtime_error with every keyframe and point as it came.  Monocular.
+template <class KeyFrame, class MapPoint, class Sim3>
+struct CorrectLoopPosesT {
+    struct Result {
+        int nMoved, nNormals;                 // the points moved; those whose normal and bounds were written
+        int nUndefined;                       // ORBR_ST_NO_REF + ORBR_ST_LEVEL_RANGE, where the reference is undefined
+        std::vector<OrbeKeyFrame> keyframes;  // in the order of `keyframes`
+        std::vector<OrbePoint> points;        // in the reference's visiting order
+    };
+
+    static Sim3 MakeSim3(const Sim3& like, const double* v)
+    {
+        auto r = like.rotation();
+        auto t = like.translation();
+        for (int c = 0; c < 4; c++) r.coeffs()[c] = v[c];
+        for (int c = 0; c < 3; c++) t[c] = v[4 + c];
+        return Sim3(r, t, v[7]);
+    }
+
+    template <class Map, class Hooks>
+    static Result Run(orbu_store_t* store, const std::vector<KeyFrame*>& keyframes, KeyFrame* pCurrentKF, const Sim3& Scw, const std::vector<MapPoint*>& alreadyCorrected,
+                      const std::vector<float>& scaleFactors, Map& CorrectedSim3, Map& NonCorrectedSim3, Hooks& hooks)
+    {
+        const char* who = "CorrectLoopPoses(HIP): ";
+        Result res; res.nMoved = 0; res.nNormals = 0; res.nUndefined = 0;
+        const size_t K = keyframes.size();
+        std::vector<int32_t> slots(K), skip(alreadyCorrected.size());
+        std::vector<float> Tiw(12 * K);
+        int anchor = -1;
+        size_t room = 0;
+        for (size_t i = 0; i < K; i++) {
+            slots[i] = hooks.SlotOfKF(keyframes[i]);
+            hooks.Pose(keyframes[i], &Tiw[12 * i]);
+            if (keyframes[i] == pCurrentKF) anchor = (int)i;
+            room += keyframes[i]->GetMapPointMatches().size();
+        }
+        if (anchor < 0) throw std::runtime_error(std::string(who) + "the current keyframe is not among the listed ones");
+        for (size_t i = 0; i < skip.size(); i++) skip[i] = hooks.IdOfPoint(alreadyCorrected[i]);
+        double S[8];
+        for (int c = 0; c < 4; c++) S[c] = Scw.rotation().coeffs()[c];
+        for (int c = 0; c < 3; c++) S[4 + c] = Scw.translation()[c];
+        S[7] = Scw.scale();
+        // ---- the device call, with nothing touched
+        res.keyframes.resize(K);
+        res.points.resize(room);
+        int n = 0;
+        detail::check(orbe_correct_sim3(store, slots.data(), Tiw.data(), (int)K, anchor, S, skip.data(), (int)skip.size(), scaleFactors.data(), (int)scaleFactors.size(), 1,
+                                        res.keyframes.data(), res.points.data(), (int)room, &n), who);
+        res.points.resize((size_t)n);
+        // ---- the host objects
+        for (size_t i = 0; i < K; i++) {
+            const OrbeKeyFrame& k = res.keyframes[i];
+            CorrectedSim3[keyframes[i]] = MakeSim3(Scw, k.corrected);          // :445, :469
+            NonCorrectedSim3[keyframes[i]] = MakeSim3(Scw, k.non_corrected);   // :476
+            hooks.SetPose(keyframes[i], k.Tiw);                                // :520
+        }
+        for (size_t i = 0; i < res.points.size(); i++) {
+            const OrbePoint& o = res.points[i];
+            MapPoint* pMP = hooks.PointOfId(o.id);
+            hooks.SetWorldPos(pMP, o.pos);                                     // :505
+            pMP->mnCorrectedByKF = pCurrentKF->mnId;                           // :506
+            pMP->mnCorrectedReference = (long unsigned int)o.owner_slot;       // :507 (slot = mnId)
+            if (o.status == ORBR_ST_DONE) { hooks.SetNormalAndDepth(pMP, o.normal, o.min_distance, o.max_distance); res.nNormals++; }   // :508
+            if (o.status == ORBR_ST_NO_REF || o.status == ORBR_ST_LEVEL_RANGE) res.nUndefined++;
+            res.nMoved++;
+        }
+        return res;
     }
 };
 

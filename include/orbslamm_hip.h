@@ -995,4 +995,7 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 /* MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth over that store, refreshing the pool's records in place
  * (orbr_refresh_points, orbu_kf_set_descriptors / _centres, orbw_debug_pool_get): orbslamm_refresh.h. */
 #include "orbslamm_refresh.h"
+/* LoopClosing::CorrectLoop's correction and MultiMapper::UpdatePosesAndAdd's over that store: the Sim3 propagated, the points
+ * moved once, their normals and depths, the new poses and centres (orbe_correct_sim3, orbu_point_set_ref_kf): orbslamm_correct.h. */
+#include "orbslamm_correct.h"
 #endif

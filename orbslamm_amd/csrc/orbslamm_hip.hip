@@ -57,6 +57,7 @@
 #include "orbn_kernels.hip"   // covisibility: UpdateConnections' counter and ordered list, KeyFrameCulling's counts, over the store
 #include "orbq_kernels.hip"   // PoseOptimization from the pool: merge, ordered edge list, orbo's solve, Tracking's loop behind it
 #include "orbr_kernels.hip"   // the map-point refresh: ComputeDistinctiveDescriptors and UpdateNormalAndDepth over the store, into the pool
+#include "orbe_kernels.hip"   // the loop correction: the Sim3 propagated, the points moved once, orbr's normals with mixed centres, the commit
 #include "orby_kernels.hip"   // ComputeSim3 behind the solver: SearchBySim3's two passes, the agreement, OptimizeSim3's walk, orbz's solve
 
 using namespace orbx;
@@ -220,5 +221,6 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbu_host.inc"   // the keyframe store beside the pool: UpdateLocalMap, and SearchLocalPoints from its resident list
 #include "orbn_host.inc"   // the covisibility entries over the store: batched UpdateConnections and KeyFrameCulling counts
 #include "orbr_host.inc"   // the refresh entry, the store's descriptor and centre setters, orbw_debug_pool_get
+#include "orbe_host.inc"   // the loop correction's entry, and mpRefKF resident beside the pool
 #include "orbq_host.inc"   // PoseOptimization behind the pool searches: TrackWithMotionModel's and TrackLocalMap's verdicts
 #include "orby_host.inc"   // SearchBySim3 and OptimizeSim3 from the pool, the store and the frame set: ComputeSim3's verdict per candidate

@@ -11,6 +11,7 @@ static_assert(ORBU_ENTRY_NO_VOTE == orbu::kNoVote && ORBU_MAX_KEYFRAMES == orbu:
 constexpr size_t kStoreMaxEntries = (size_t)1 << 28;   // kf_capacity * pitch: positions of the point walk fit 32 bits with room
 static void orbn_release(orbu_store* s);   // orbn_host.inc
 static void orbr_release(orbu_store* s);   // orbr_host.inc
+static void orbe_release(orbu_store* s);   // orbe_host.inc
 
 extern "C" int orbu_store_create(orbw_pool_t* pool, int kf_capacity, int stride, int max_children, int max_local_points, orbu_store_t** out)
 {
@@ -77,6 +78,7 @@ extern "C" int orbu_store_destroy(orbu_store_t* s)
     }
     orbn_release(s);
     orbr_release(s);
+    orbe_release(s);
     (void)hipFree(s->d_block);
     (void)hipHostFree(s->h_res);
     if (s->h_stage) (void)hipHostFree(s->h_stage);

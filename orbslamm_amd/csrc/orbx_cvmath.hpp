@@ -20,6 +20,12 @@ __host__ __device__ __forceinline__ float gemm3_elem(float a0, float a1, float a
     const float t = a0 * b0 + a1 * b1 + a2 * b2;
     return (float)((double)t * alpha + (double)c * beta);
 }
+// the same branch with len 4 (a 4x4 pose product): four float products summed left to right
+__host__ __device__ __forceinline__ float gemm4_elem(float a0, float a1, float a2, float a3, float b0, float b1, float b2, float b3, double alpha, float c, double beta)
+{
+    const float t = a0 * b0 + a1 * b1 + a2 * b2 + a3 * b3;
+    return (float)((double)t * alpha + (double)c * beta);
+}
 __host__ __device__ inline void mm3(const float* A, const float* B, float* D, double alpha = 1.0)
 {
     float o[9];

@@ -1,5 +1,5 @@
 // orbx_poolutil.inc -- what the host files of the map-point pool's families share (part of orbslamm_hip.hip, in front of
-// orbw_host.inc, orbu_host.inc, orbn_host.inc, orbr_host.inc and orbq_host.inc): the pool and the keyframe store as the host holds them, the
+// orbw_host.inc, orbu_host.inc, orbn_host.inc, orbr_host.inc, orbe_host.inc and orbq_host.inc): the pool and the keyframe store as the host holds them, the
 // steps of the concurrency rule (DESIGN.md §8q), the id and slot checks, the store's generation tag, the last-wins staging.
 
 constexpr int kPoolChunk = 1 << 16;                    // records per pool setter launch: the pinned staging is 5 MB at the most
@@ -26,6 +26,7 @@ struct orbw_pool {
 
 struct orbn_blocks;   // orbn_host.inc: the covisibility entries' blocks, made at their first call
 struct orbr_blocks;   // orbr_host.inc: the map-point refresh's blocks, made at its first call
+struct orbe_blocks;   // orbe_host.inc: the loop correction's blocks, made at its first call
 
 // keyframe match lists, flags and graph records in HBM beside ONE map-point pool, whose mutex and stream it uses; a "set" byte per
 // slot on the host; all blocks of a fixed size made at create, the staging grow-only
@@ -58,6 +59,9 @@ struct orbu_store {
     uint8_t* d_desc = nullptr;                         // orbu_kf_set_descriptors*: [kfcap * pitch * 32] bytes, null until the first call
     float* d_ctr = nullptr;                            // orbu_kf_set_centres: [kfcap * 3], null until the first call
     std::vector<uint8_t> kfDesc, kfCtr;                // the slots that have descriptors, a centre
+    int32_t* d_refKf = nullptr;                        // orbu_point_set_ref_kf: mpRefKF per pool id [pool capacity], null until the first call
+    orbe_blocks* correct = nullptr;                    // orbe_correct_sim3: null until the first call
+    unsigned long long* emarks = nullptr; size_t emarkBytes = 0;   // ... and its pool-sized claim words: set and dropped with correct (orbe_host.inc)
 };
 
 static int orbw_pool_check(orbw_pool* p)
@@ -151,6 +155,7 @@ static int orbu_next_generation(orbu_store* s, hipStream_t st, uint32_t* tag)
         HIPCHK(hipMemsetAsync(s->scr.first, 0xff, bytes, st));
         if (s->marks) HIPCHK(hipMemsetAsync(s->marks, 0, bytes, st));
         if (s->rmarks) HIPCHK(hipMemsetAsync(s->rmarks, 0, bytes, st));
+        if (s->emarks) HIPCHK(hipMemsetAsync(s->emarks, 0, s->emarkBytes, st));
         s->gen = 0;
     }
     *tag = ++s->gen;

@@ -205,6 +205,12 @@ REFRESH_DTYPE = np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3), ("min_distanc
                           ("st_normal_depth", "u1"), ("pad", "u1", 2)])
 assert REFRESH_DTYPE.itemsize == 84
 
+# ---- the correction of LoopClosing::CorrectLoop / MultiMapper::UpdatePosesAndAdd over the store (include/orbslamm_correct.h)
+CORRECT_KF_DTYPE = np.dtype([("corrected", "<f8", 8), ("non_corrected", "<f8", 8), ("Tiw", "<f4", 12), ("Ow", "<f4", 3), ("n_points", "<i4")])
+CORRECT_POINT_DTYPE = np.dtype([("id", "<i4"), ("owner_slot", "<i4"), ("owner_idx", "<i4"), ("pos", "<f4", 3), ("normal", "<f4", 3), ("min_distance", "<f4"),
+                                ("max_distance", "<f4"), ("n_obs", "<i4"), ("status", "u1"), ("pad", "u1", 3)])
+assert CORRECT_KF_DTYPE.itemsize == 192 and CORRECT_POINT_DTYPE.itemsize == 52
+
 
 def _copy(p, n, ct, dt):
     return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,)).astype(dt, copy=True) if p and n else np.zeros(0, dt)
@@ -255,6 +261,8 @@ def _setup_store(L):
     L.orbu_kf_set_descriptors_frame.argtypes = [vp, C.c_int, vp, C.c_int]
     L.orbu_kf_set_centres.argtypes = [vp, vp, vp, C.c_int]
     L.orbr_refresh_points.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.orbu_point_set_ref_kf.argtypes = [vp, vp, vp, C.c_int]
+    L.orbe_correct_sim3.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
     L.orbu_store_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.orbu_store_destroy.argtypes = [vp]
     L.orbu_kf_set.argtypes = [vp, vp]
@@ -391,6 +399,29 @@ class KeyFrameStore(Handle):
         out = np.zeros(ids.shape[0], REFRESH_DTYPE)
         check(self._L.orbr_refresh_points(self._h, ptr(ids), ptr(ref), ptr(pos), ids.shape[0], int(what), ptr(sf), sf.shape[0], int(bool(commit)), ptr(out)))
         return out
+
+    def set_ref_kf(self, ids, kf_slots):
+        """orbu_point_set_ref_kf: mpRefKF of pool ids as store slots (-1: none), resident beside the pool; a repeated id takes the last"""
+        ids, kf = _ids(ids), _ids(kf_slots)
+        assert kf.shape[0] == ids.shape[0]
+        check(self._L.orbu_point_set_ref_kf(self._h, ptr(ids), ptr(kf), ids.shape[0]))
+
+    def correct_sim3(self, slots, Tiw, anchor, Scw, scale_factors, skip_ids=(), commit=True, pts_cap=None):
+        """orbe_correct_sim3: the loop Sim3 `Scw` (q x y z w, t, s) propagated over the keyframes `slots` whose poses are Tiw (rows
+        [R | t], or 4x4), slots[anchor] being the current keyframe; every point they hold moved once, its normal and depth
+        refreshed; written into the pool and the store's centres when commit -> (CORRECT_KF_DTYPE[K] in the caller's order,
+        CORRECT_POINT_DTYPE[n] in the reference's visiting order).  pts_cap: room for the moved points (default: the most there can be)"""
+        slots, skip = _ids(slots), _ids(skip_ids)
+        K = slots.shape[0]
+        T = np.asarray(Tiw, dtype=np.float32)
+        T = np.ascontiguousarray(T.reshape(K, 4, 4)[:, :3, :] if T.size == 16 * K and K else T.reshape(K, 12))
+        S = np.ascontiguousarray(Scw, dtype=np.float64).reshape(8)
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32)
+        cap = min(self._pool.capacity, K * self.stride) if pts_cap is None else int(pts_cap)
+        kf, pts, n = np.zeros(K, CORRECT_KF_DTYPE), np.zeros(cap, CORRECT_POINT_DTYPE), C.c_int(0)
+        check(self._L.orbe_correct_sim3(self._h, ptr(slots), ptr(T), K, int(anchor), ptr(S), ptr(skip), skip.shape[0], ptr(sf), sf.shape[0], int(bool(commit)),
+                                        ptr(kf), ptr(pts), cap, C.byref(n)))
+        return kf, pts[:n.value].copy()
 
     def update_connections(self, targets, th=15):
         """orbn_update_connections: KeyFrame::UpdateConnections' counter and ordered list of every target -> Connections"""
