@@ -1,12 +1,14 @@
 // orbe_host.inc -- host side of the loop correction over a keyframe store (part of orbslamm_hip.hip; kernels:
 // orbe_kernels.hip, ABI: include/orbslamm_correct.h, DESIGN.md §8x).
-//   the store     the resident mpRefKF array is made at the first orbu_point_set_ref_kf; the claim words (pool-sized) at the first
-//                 correction; the per-keyframe and per-point arrays grow with the largest
-//                 K and the largest count of moved points seen.  The observation index and its per-point arrays are orbr_host.inc's
+//   the store     the columns it reads (centres, octaves) and the resident mpRefKF array are the store's: set in orbu_host.inc,
+//                 freed by orbu_store_destroy
+//   the blocks    the claim words (pool-sized) at the first correction; the per-keyframe and per-point arrays grow with the largest
+//                 K and the largest count of moved points seen.  This file owns these alone: the observation index and its
+//                 per-point arrays are orbr_host.inc's
 //   a call        poses, claim, count, scan, the total down, the FIRST synchronisation (the count of moved points sizes what
-//                 follows and answers ORBX_E_CAPACITY); place, move, orbr's mark / count / segments / place and its two refresh
-//                 kernels, the records, orbr's header down, the second synchronisation; the error word
-//                 checked; then the commit as a launch of its own, the records down into the outputs, the last synchronisation
+//                 follows and answers ORBX_E_CAPACITY); place, move, orbr_issue (orbr's mark / count / segments / place and its
+//                 two refresh kernels), the records, orbr's header down, the second synchronisation; orbr_check_header;
+//                 then the commit as a launch of its own, the records down into the outputs, the last synchronisation
 
 static_assert(sizeof(OrbePoint) == 4 * orbe::kPointWords && sizeof(OrbeKeyFrame) == sizeof(orbe::KfRec) && sizeof(OrbeKeyFrame) == 192, "orbslamm_correct.h layouts");
 static_assert(offsetof(OrbePoint, pos) == 4 * orbe::P_POS && offsetof(OrbePoint, normal) == 4 * orbe::P_NORMAL && offsetof(OrbePoint, min_distance) == 4 * orbe::P_MIN &&
@@ -24,48 +26,13 @@ struct orbe_blocks {
 
 static void orbe_release(orbu_store* s)
 {
-    if (s->d_refKf) (void)hipFree(s->d_refKf);
-    s->d_refKf = nullptr;
     if (!s->correct) return;
+    orbu_marks_drop(s, s->correct->dev.own);
     if (s->correct->d_block) (void)hipFree(s->correct->d_block);
     if (s->correct->d_kf) (void)hipFree(s->correct->d_kf);
     if (s->correct->d_pts) (void)hipFree(s->correct->d_pts);
     delete s->correct;
-    s->correct = nullptr; s->emarks = nullptr; s->emarkBytes = 0;
-}
-
-extern "C" int orbu_point_set_ref_kf(orbu_store_t* s, const int32_t* ids, const int32_t* kf_slots, int n)
-{
-    if (n < 0) return fail(ORBX_E_INVALID, "negative count");
-    if (n == 0) return ORBX_OK;
-    if (!ids || !kf_slots) return fail(ORBX_E_INVALID, "null argument");
-    int rc = orbu_store_check(s);
-    if (rc) return rc;
-    orbw_pool* p = s->pool;
-    std::lock_guard<std::mutex> l(p->mu);
-    if ((rc = orbw_check_ids(p, "ids", ids, n, false, false))) return rc;
-    for (int i = 0; i < n; i++)
-        if ((rc = orbu_check_slot(s, "kf_slots", i, kf_slots[i], false, true))) return rc;
-    if (!s->d_refKf) {   // every id -1
-        const size_t bytes = (size_t)p->cap * 4;
-        HIPCHK(hipMalloc((void**)&s->d_refKf, bytes));
-        p->h->nDevAlloc++;
-        hipError_t e = hipMemsetAsync(s->d_refKf, 0xff, bytes, p->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-        if (e != hipSuccess) { (void)hipFree(s->d_refKf); s->d_refKf = nullptr; return fail(ORBX_E_HIP, "clearing the reference keyframes failed: %s", hipGetErrorString(e)); }
-    }
-    const int perLaunch = (int)std::min<size_t>((size_t)n, kStoreStageBytes / 8);
-    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, (size_t)perLaunch * 8))) return rc;
-    int2* stage = (int2*)s->h_stage;
-    auto emit = [=](int i, int m) { stage[m] = make_int2(ids[i], kf_slots[i]); };   // (by value, as orbw_pool_write's)
-    auto flush = [=](int m) -> int {
-        hipLaunchKernelGGL(orbe::k_ref_scatter, dim3((unsigned)((m + orbe::kThreads - 1) / orbe::kThreads)), dim3(orbe::kThreads), 0, p->stream,
-                           s->d_refKf, p->cap, (const int2*)stage, m);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(p->stream));
-        return ORBX_OK;
-    };
-    return stage_last_wins(ids, n, perLaunch, perLaunch, p->seen, emit, flush);
+    s->correct = nullptr;
 }
 
 // (the pool's mutex is held) the fixed block, and the per-keyframe arrays for K keyframes
@@ -76,14 +43,10 @@ static int orbe_blocks_ensure(orbu_store* s, int K)
         orbe_blocks* b = new orbe_blocks();
         Packer pk;
         const size_t oOwn = pk.take((size_t)p->cap * 8), marks = pk.off, oHdr = pk.take(orbe::H_INTS * 4), bytes = pk.off;
-        auto bail = [&](int code) { if (b->d_block) (void)hipFree(b->d_block); delete b; return code; };
-        HIPCHK_OR(hipMalloc(&b->d_block, bytes), bail(0));
-        HIPCHK_OR(hipMemsetAsync(b->d_block, 0, bytes, p->stream), bail(0));
-        HIPCHK_OR(hipStreamSynchronize(p->stream), bail(0));
+        if (int rc = orbu_block_once(p, b->d_block, bytes, 0)) { delete b; return rc; }
         b->dev.own = (unsigned long long*)(b->d_block + oOwn); b->dev.hdr = (int32_t*)(b->d_block + oHdr);
         b->dev.pool = p->dev;
-        p->h->nDevAlloc++;
-        s->correct = b; s->emarks = b->dev.own; s->emarkBytes = marks;   // (the claim words: what orbu_next_generation clears at the wrap: dropped in orbe_release)
+        s->correct = b; s->marks[s->nMarks++] = {b->dev.own, marks};   // (the claim words)
     }
     orbe_blocks* b = s->correct;
     Packer pk;
@@ -92,7 +55,7 @@ static int orbe_blocks_ensure(orbu_store* s, int K)
     int rc = grow_device(b->d_kf, b->kfCap, pk.off, 1 << 12, &p->stream, &p->h->nDevAlloc);
     if (rc) return rc;
     b->dev.kf = (orbe::KfRec*)(b->d_kf + oKf); b->dev.inv = (orbe::Sim3*)(b->d_kf + oInv); b->dev.rowCnt = (int32_t*)(b->d_kf + oCnt); b->dev.rowStart = (int32_t*)(b->d_kf + oStart);
-    b->dev.refKf = s->d_refKf; b->dev.ctr = s->d_ctr;
+    b->dev.refKf = s->d_refKf; b->dev.ctr = s->ctr.d;
     return ORBX_OK;
 }
 
@@ -128,25 +91,15 @@ extern "C" int orbe_correct_sim3(orbu_store_t* s, const int32_t* slots, const fl
     if (rc) return rc;
     orbw_pool* p = s->pool;
     std::lock_guard<std::mutex> l(p->mu);
-    {   // the listed slots: set, and none twice (the store's scratch bits, all zero between calls)
-        int bad = ORBX_OK, marked = 0;
-        for (int i = 0; i < K && !bad; i++) {
-            if ((bad = orbu_check_slot(s, "slots", i, slots[i], true))) break;
-            uint64_t& w = s->kfSeen[(size_t)slots[i] >> 6];
-            const uint64_t bit = 1ull << (slots[i] & 63);
-            if (w & bit) bad = fail(ORBX_E_INVALID, "slots[%d] = %d is repeated within the call", i, slots[i]);
-            w |= bit;
-            marked = i + 1;
-        }
-        for (int i = 0; i < marked; i++) s->kfSeen[(size_t)slots[i] >> 6] = 0;
-        if (bad) return bad;
+    {   // the listed slots: set, and none twice (the store's scratch bits, all zero between calls); the fault at the lower index is reported
+        int nOk = 0;
+        while (nOk < K && !(rc = orbu_check_slot(s, "slots", nOk, slots[nOk], true))) nOk++;
+        const int dup = first_repeated_key(slots, nOk, s->kfSeen);
+        if (dup >= 0) return fail(ORBX_E_INVALID, "slots[%d] = %d is repeated within the call", dup, slots[dup]);
+        if (rc) return rc;
     }
     if ((rc = orbw_check_ids(p, "skip_ids", skip_ids, n_skip, false))) return rc;
-    for (int k = 0; k < s->hi; k++) {
-        if (!s->kfSet[k]) continue;
-        if (!s->d_ctr || !s->kfCtr[k]) return fail(ORBX_E_INVALID, "keyframe slot %d has no centre (orbu_kf_set_centres)", k);
-        if (!s->d_oct || !s->kfOct[k]) return fail(ORBX_E_INVALID, "keyframe slot %d has no octaves (orbu_kf_set_octaves)", k);
-    }
+    if ((rc = orbu_check_columns(s, false, true, true))) return rc;
     if ((rc = orbe_blocks_ensure(s, K))) return rc;
     orbe_blocks* b = s->correct;
     Packer pk;
@@ -198,24 +151,16 @@ extern "C" int orbe_correct_sim3(orbu_store_t* s, const int32_t* slots, const fl
         rcall.ids = b->dev.ids; rcall.ref = b->dev.ref; rcall.newPos = b->dev.newPos; rcall.sf = (const float*)(s->h_stage + oSf);
         rcall.n = n; rcall.what = ORBR_NORMAL_DEPTH; rcall.nlevels = nlevels;
         const unsigned ptBlocks = (unsigned)((n + orbe::kThreads - 1) / orbe::kThreads);
-        const unsigned walkBlocks = (unsigned)((s->hi + orbr::kWaves - 1) / orbr::kWaves);
         hipLaunchKernelGGL(orbe::k_rows, dim3(rowBlocks), dim3(orbe::kThreads), 0, st, s->dev, b->dev, c, 1, n);
         hipLaunchKernelGGL(orbe::k_move, dim3(ptBlocks), dim3(orbe::kThreads), 0, st, b->dev, n, K);
-        hipLaunchKernelGGL(orbr::k_mark, dim3(ptBlocks), dim3(orbr::kThreads), 0, st, rb->dev, rcall);
-        if (walkBlocks) hipLaunchKernelGGL(orbr::k_walk, dim3(walkBlocks), dim3(orbr::kThreads), 0, st, s->dev, rb->dev, n, s->hi, 0);
-        hipLaunchKernelGGL(orbr::k_segments, dim3(ptBlocks), dim3(orbr::kThreads), 0, st, rb->dev, n);
-        if (walkBlocks) hipLaunchKernelGGL(orbr::k_walk, dim3(walkBlocks), dim3(orbr::kThreads), 0, st, s->dev, rb->dev, n, s->hi, 1);
         // rule 5: every centre it reads is the store's present one, which orbr's kernels read; the commit comes behind them
-        hipLaunchKernelGGL(orbr::k_refresh_short, dim3(std::min(4096u, (unsigned)((n + orbr::kGroups - 1) / orbr::kGroups))), dim3(orbr::kThreads), 0, st, s->dev, rb->dev, rcall);
-        hipLaunchKernelGGL(orbr::k_refresh_long, dim3(std::min(1024u, (unsigned)n)), dim3(orbr::kThreads), 0, st, s->dev, rb->dev, rcall);
+        orbr_issue(s, rb, rcall, st);
         hipLaunchKernelGGL(orbe::k_records, dim3(ptBlocks), dim3(orbe::kThreads), 0, st, b->dev, (const uint32_t*)rb->dev.res, (const int32_t*)hSlots, n, K);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(hdrR, rb->dev.hdr, orbr::H_INTS * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        if (hdrR[orbr::H_ERR]) return fail(ORBX_E_UNSUPPORTED, "a moved point has more than %d observations", ORBR_MAX_OBS);
-        if (hdrR[orbr::H_NSHORT] + hdrR[orbr::H_NLONG] != n || hdrR[orbr::H_TOTAL] < 0 || hdrR[orbr::H_TOTAL] > rb->dev.keysCap)
-            return fail(ORBX_E_HIP, "the observation index holds %d + %d of %d points and %d keys", hdrR[orbr::H_NSHORT], hdrR[orbr::H_NLONG], n, hdrR[orbr::H_TOTAL]);
+        if ((rc = orbr_check_header(hdrR, n, rb, "a moved point"))) return rc;
     }
     if (commit) {
         hipLaunchKernelGGL(orbe::k_commit, dim3((unsigned)((std::max(n, K) + orbe::kThreads - 1) / orbe::kThreads)), dim3(orbe::kThreads), 0, st, s->dev, b->dev,

@@ -1,8 +1,9 @@
 // orbn_host.inc -- host side of the covisibility entries over a keyframe store (part of orbslamm_hip.hip; kernels:
 // orbn_kernels.hip, ABI: include/orbslamm_covis.h, DESIGN.md §8u).
 //   the blocks    made at the first orbn call of a store, of fixed size: the pool-sized marks, the chunk's counter matrix and
-//                 keys on the device, the chunk's rows in pinned memory; the histograms at the first culling call; the octave
-//                 bytes at the first orbu_kf_set_octaves.  The result arrays are host vectors that keep their capacity.
+//                 keys on the device, the chunk's rows in pinned memory; the histograms at the first culling call.  The result
+//                 arrays are host vectors that keep their capacity.  This file owns these and nothing of the store's: the octave
+//                 column it reads is made by orbu_kf_set_octaves (orbu_host.inc) and freed by orbu_store_destroy
 //   a call        targets kChunk at a time, each chunk under a generation tag of its own (the store's counter, shared with
 //                 orbu_update_local_map, whose scratch a larger tag leaves valid).  The tag, the slot checks and the writer's
 //                 opening: orbx_poolutil.inc
@@ -22,13 +23,13 @@ struct orbn_blocks {
 
 static void orbn_release(orbu_store* s)
 {
-    if (s->d_oct) (void)hipFree(s->d_oct);
     if (!s->covis) return;
+    orbu_marks_drop(s, s->covis->dev.mark);
     if (s->covis->d_block) (void)hipFree(s->covis->d_block);
     if (s->covis->d_hist) (void)hipFree(s->covis->d_hist);
     if (s->covis->h_rows) (void)hipHostFree(s->covis->h_rows);
     delete s->covis;
-    s->covis = nullptr; s->marks = nullptr;   // (marks is b->dev.mark: the two go together, here and in orbn_blocks_ensure)
+    s->covis = nullptr;
 }
 
 // (the pool's mutex is held)
@@ -43,67 +44,23 @@ static int orbn_blocks_ensure(orbu_store* s, bool hist)
         Packer hp;
         const size_t hHdr = hp.take((size_t)orbn::kChunk * orbn::C_INTS * 4), hCk = hp.take(R * 4), hCw = hp.take(R * 4), hOk = hp.take(R * 4),
                      hOw = hp.take(R * 4), hbytes = hp.off;
-        auto bail = [&](int code) { if (b->d_block) (void)hipFree(b->d_block); if (b->h_rows) (void)hipHostFree(b->h_rows); delete b; return code; };
-        HIPCHK_OR(hipMalloc(&b->d_block, bytes), bail(0));
-        HIPCHK_OR(hipHostMalloc((void**)&b->h_rows, hbytes, hipHostMallocCoherent), bail(0));
+        if (int rc = orbu_block_once(p, b->d_block, bytes, 0)) { delete b; return rc; }
+        HIPCHK_OR(hipHostMalloc((void**)&b->h_rows, hbytes, hipHostMallocCoherent), ((void)hipFree(b->d_block), delete b));
         memset(b->h_rows, 0, hbytes);
-        HIPCHK_OR(hipMemsetAsync(b->d_block, 0, bytes, p->stream), bail(0));
-        HIPCHK_OR(hipStreamSynchronize(p->stream), bail(0));
         b->dev.mark = (unsigned long long*)(b->d_block + oMark); b->dev.cnt = (int32_t*)(b->d_block + oCnt);
         b->dev.keys = (unsigned long long*)(b->d_block + oKeys);
         b->dev.poolFlags = p->dev.flags; b->dev.poolCap = p->cap;
         b->out.hdr = (int32_t*)(b->h_rows + hHdr); b->out.cntKf = (int32_t*)(b->h_rows + hCk); b->out.cntW = (int32_t*)(b->h_rows + hCw);
         b->out.ordKf = (int32_t*)(b->h_rows + hOk); b->out.ordW = (int32_t*)(b->h_rows + hOw);
-        p->h->nDevAlloc++; p->h->nHostAlloc++;
-        s->covis = b; s->marks = b->dev.mark;   // (what orbu_next_generation clears at the wrap: set with covis, dropped with it in orbn_release)
+        p->h->nHostAlloc++;
+        s->covis = b; s->marks[s->nMarks++] = {b->dev.mark, P * 8};
     }
     if (hist && !s->covis->d_hist) {
         HIPCHK(hipMalloc((void**)&s->covis->d_hist, (size_t)p->cap * orbn::kBins * 4));
         p->h->nDevAlloc++;
     }
     s->covis->dev.hist = s->covis->d_hist;
-    s->covis->dev.oct = s->d_oct;
-    return ORBX_OK;
-}
-
-extern "C" int orbu_kf_set_octaves(orbu_store_t* s, int slot, const uint8_t* octaves, int n)
-{
-    if (n < 0) return fail(ORBX_E_INVALID, "negative count");
-    if (slot < 0) return fail(ORBX_E_INVALID, "keyframe slot %d", slot);
-    if (n > 0 && !octaves) return fail(ORBX_E_INVALID, "null argument");
-    int rc = orbu_store_check(s);
-    if (rc) return rc;
-    orbw_pool* p = s->pool;
-    std::lock_guard<std::mutex> l(p->mu);
-    if ((rc = orbu_check_slot(s, "slot", 0, slot, true))) return rc;
-    if (n > s->stride) return fail(ORBX_E_UNSUPPORTED, "%d octaves for a stride of %d", n, s->stride);
-    {   // the distinct values the store has been given: the histograms have a bin for each
-        bool seen[256];
-        int distinct = 0;
-        for (int v = 0; v < 256; v++) { seen[v] = s->octSeen[v]; }
-        seen[0] = seen[0] || n < s->stride;
-        for (int i = 0; i < n; i++) seen[octaves[i]] = true;
-        for (int v = 0; v < 256; v++) distinct += seen[v] ? 1 : 0;
-        if (distinct > ORBN_MAX_OCTAVE_VALUES)
-            return fail(ORBX_E_UNSUPPORTED, "%d distinct octave values in the store, at most %d", distinct, ORBN_MAX_OCTAVE_VALUES);
-    }
-    if (!s->d_oct) {
-        const size_t bytes = (size_t)s->kfcap * s->pitch;
-        HIPCHK(hipMalloc((void**)&s->d_oct, bytes));
-        p->h->nDevAlloc++;
-        hipError_t e = hipMemsetAsync(s->d_oct, 0, bytes, p->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-        if (e != hipSuccess) { (void)hipFree(s->d_oct); s->d_oct = nullptr; return fail(ORBX_E_HIP, "clearing the octave block failed: %s", hipGetErrorString(e)); }
-        s->kfOct.assign((size_t)s->kfcap, 0);
-    }
-    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, (size_t)s->pitch))) return rc;
-    if (n) memcpy(s->h_stage, octaves, (size_t)n);
-    memset(s->h_stage + n, 0, (size_t)(s->pitch - n));
-    HIPCHK(hipMemcpyAsync(s->d_oct + (size_t)slot * s->pitch, s->h_stage, (size_t)s->pitch, hipMemcpyHostToDevice, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    if (n < s->stride) s->octSeen[0] = 1;
-    for (int i = 0; i < n; i++) s->octSeen[octaves[i]] = 1;
-    s->kfOct[slot] = 1;
+    s->covis->dev.oct = s->oct.d;
     return ORBX_OK;
 }
 
@@ -184,8 +141,7 @@ extern "C" int orbn_culling_counts(orbu_store_t* s, const int32_t* targets, int 
     orbw_pool* p = s->pool;
     std::lock_guard<std::mutex> l(p->mu);
     if ((rc = orbn_check_targets(s, targets, K))) return rc;
-    for (int k = 0; k < s->hi; k++)
-        if (s->kfSet[k] && (!s->d_oct || !s->kfOct[k])) return fail(ORBX_E_INVALID, "keyframe slot %d has no octaves (orbu_kf_set_octaves)", k);
+    if ((rc = orbu_check_columns(s, false, false, true))) return rc;
     if ((rc = orbn_blocks_ensure(s, true))) return rc;
     Packer pk;
     const size_t oTg = pk.take((size_t)K * 4), oBin = pk.take(256), oUpto = pk.take(257), oMps = pk.take((size_t)K * 4), oRed = pk.take((size_t)K * 4),

@@ -1,11 +1,11 @@
 // orbr_host.inc -- host side of the map-point refresh over a keyframe store (part of orbslamm_hip.hip; kernels:
 // orbr_kernels.hip, ABI: include/orbslamm_refresh.h, DESIGN.md §8w).
-//   the store     the descriptor block and the centres are made at the first call of their setters; orbu_kf_set_octaves is
-//                 orbn_host.inc's
+//   the store     the columns it reads (descriptors, centres, octaves) are the store's: set in orbu_host.inc, freed by orbu_store_destroy
 //   the blocks    the pool-sized marks and the keys (one per entry of the store) at the first refresh, of fixed size; the
-//                 per-point arrays grow with the largest n seen
-//   a call        mark, count, segments, place, the two refresh kernels, the header down, one synchronisation; the error word
-//                 checked; then the commit as a launch of its own, the records down into `out`, the second synchronisation
+//                 per-point arrays grow with the largest n seen.  This file owns these alone
+//   a call        orbr_issue (mark, count, segments, place, the two refresh kernels), the header down, one synchronisation;
+//                 orbr_check_header; then the commit as a launch of its own, the records down into `out`, the second
+//                 synchronisation.  orbe_correct_sim3 (orbe_host.inc) runs the same two functions inside its own block
 
 static_assert(sizeof(OrbrPoint) == 4 * orbr::kRecWords && ORBR_MAX_OBS == orbr::kMaxObs && ORBU_MAX_STRIDE == 1 << orbr::kQBits, "orbslamm_refresh.h layouts");
 static_assert(ORBR_ST_NOT_ASKED == orbr::ST_NOT_ASKED && ORBR_ST_DONE == orbr::ST_DONE && ORBR_ST_BAD == orbr::ST_BAD && ORBR_ST_NO_OBSERVATION == orbr::ST_NO_OBSERVATION &&
@@ -21,115 +21,12 @@ struct orbr_blocks {
 
 static void orbr_release(orbu_store* s)
 {
-    if (s->d_desc) (void)hipFree(s->d_desc);
-    if (s->d_ctr) (void)hipFree(s->d_ctr);
-    s->d_desc = nullptr; s->d_ctr = nullptr;
     if (!s->refresh) return;
+    orbu_marks_drop(s, s->refresh->dev.mark);
     if (s->refresh->d_block) (void)hipFree(s->refresh->d_block);
     if (s->refresh->d_pts) (void)hipFree(s->refresh->d_pts);
     delete s->refresh;
-    s->refresh = nullptr; s->rmarks = nullptr;
-}
-
-// (the pool's mutex is held) a zeroed device block of the store, made once
-template <class T>
-static int orbr_store_block(orbu_store* s, T*& d, size_t bytes, std::vector<uint8_t>& have)
-{
-    if (d) return ORBX_OK;
-    orbw_pool* p = s->pool;
-    HIPCHK(hipMalloc((void**)&d, bytes));
-    p->h->nDevAlloc++;
-    hipError_t e = hipMemsetAsync(d, 0, bytes, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    if (e != hipSuccess) { (void)hipFree(d); d = nullptr; return fail(ORBX_E_HIP, "clearing a block of the store failed: %s", hipGetErrorString(e)); }
-    have.assign((size_t)s->kfcap, 0);
-    return ORBX_OK;
-}
-
-extern "C" int orbu_kf_set_descriptors(orbu_store_t* s, int slot, const uint8_t* desc, int n)
-{
-    if (n < 0) return fail(ORBX_E_INVALID, "negative count");
-    if (slot < 0) return fail(ORBX_E_INVALID, "keyframe slot %d", slot);
-    if (!desc) return fail(ORBX_E_INVALID, "null argument");
-    int rc = orbu_store_check(s);
-    if (rc) return rc;
-    orbw_pool* p = s->pool;
-    std::lock_guard<std::mutex> l(p->mu);
-    if ((rc = orbu_check_slot(s, "slot", 0, slot, true))) return rc;
-    if (n > s->stride) return fail(ORBX_E_UNSUPPORTED, "%d descriptors for a stride of %d", n, s->stride);
-    const size_t rowBytes = (size_t)s->pitch * 32;
-    if ((rc = orbr_store_block(s, s->d_desc, (size_t)s->kfcap * rowBytes, s->kfDesc))) return rc;
-    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, rowBytes))) return rc;
-    if (n) memcpy(s->h_stage, desc, (size_t)n * 32);
-    memset(s->h_stage + (size_t)n * 32, 0, rowBytes - (size_t)n * 32);
-    const int n16 = (int)(rowBytes / 16);
-    hipLaunchKernelGGL(orbr::k_desc_scatter, dim3((unsigned)((n16 + orbr::kThreads - 1) / orbr::kThreads)), dim3(orbr::kThreads), 0, p->stream,
-                       s->d_desc + (size_t)slot * rowBytes, (const uint4*)s->h_stage, n16);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(p->stream));
-    s->kfDesc[slot] = 1;
-    return ORBX_OK;
-}
-
-extern "C" int orbu_kf_set_descriptors_frame(orbu_store_t* s, int slot, orbm_frameset_t* fs, int fs_slot)
-{
-    if (slot < 0) return fail(ORBX_E_INVALID, "keyframe slot %d", slot);
-    if (!fs) return fail(ORBX_E_INVALID, "null argument");
-    int rc = orbu_store_check(s);
-    if (rc) return rc;
-    if ((rc = frameset_check(fs))) return rc;
-    orbw_pool* p = s->pool;
-    if (fs->owner != p->h) return fail(ORBX_E_INVALID, "the frame set and the pool must be on one matcher handle");
-    if (fs_slot < 0 || fs_slot >= fs->slots) return fail(ORBX_E_INVALID, "slot %d outside the frame set", fs_slot);
-    std::lock_guard<std::mutex> l(p->mu);
-    if ((rc = orbu_check_slot(s, "slot", 0, slot, true))) return rc;
-    int32_t n = 0;
-    hipStream_t fst = fs_stream(fs);
-    HIPCHK(hipMemcpyAsync(&n, fs->fs.n + fs_slot, 4, hipMemcpyDeviceToHost, fst));
-    HIPCHK(hipStreamSynchronize(fst));   // (the slot's build is complete behind this)
-    if (n < 0 || n > fs->cap) return fail(ORBX_E_HIP, "a frame-set slot of %d features, capacity %d", n, fs->cap);
-    if (n > s->stride) return fail(ORBX_E_UNSUPPORTED, "%d descriptors for a stride of %d", n, s->stride);
-    const size_t rowBytes = (size_t)s->pitch * 32;
-    if ((rc = orbr_store_block(s, s->d_desc, (size_t)s->kfcap * rowBytes, s->kfDesc))) return rc;
-    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, 16))) return rc;
-    uint8_t* dst = s->d_desc + (size_t)slot * rowBytes;
-    if (n) HIPCHK(hipMemcpyAsync(dst, fs->fs.desc + (size_t)fs_slot * fs->cap * 32, (size_t)n * 32, hipMemcpyDeviceToDevice, p->stream));
-    if (rowBytes > (size_t)n * 32) HIPCHK(hipMemsetAsync(dst + (size_t)n * 32, 0, rowBytes - (size_t)n * 32, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    s->kfDesc[slot] = 1;
-    return ORBX_OK;
-}
-
-extern "C" int orbu_kf_set_centres(orbu_store_t* s, const int32_t* slots, const float* Ow, int n)
-{
-    if (n < 0) return fail(ORBX_E_INVALID, "negative count");
-    if (n == 0) return ORBX_OK;
-    if (!slots || !Ow) return fail(ORBX_E_INVALID, "null argument");
-    int rc = orbu_store_check(s);
-    if (rc) return rc;
-    orbw_pool* p = s->pool;
-    std::lock_guard<std::mutex> l(p->mu);
-    for (int i = 0; i < n; i++)
-        if ((rc = orbu_check_slot(s, "slots", i, slots[i], true))) return rc;
-    if ((rc = orbr_store_block(s, s->d_ctr, (size_t)s->kfcap * 12, s->kfCtr))) return rc;
-    const int perLaunch = (int)std::min<size_t>((size_t)n, kStoreStageBytes / 16);
-    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, (size_t)perLaunch * 16))) return rc;
-    uint4* stage = (uint4*)s->h_stage;
-    auto emit = [=](int i, int m) {   // (by value, as orbw_pool_write's)
-        uint32_t w[3];
-        memcpy(w, Ow + 3 * (size_t)i, 12);
-        stage[m] = make_uint4((uint32_t)slots[i], w[0], w[1], w[2]);
-    };
-    auto flush = [=](int m) -> int {
-        hipLaunchKernelGGL(orbr::k_centre_scatter, dim3((unsigned)((m + orbr::kThreads - 1) / orbr::kThreads)), dim3(orbr::kThreads), 0, p->stream,
-                           s->d_ctr, s->kfcap, (const uint4*)stage, m);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(p->stream));
-        return ORBX_OK;
-    };
-    if ((rc = stage_last_wins(slots, n, perLaunch, perLaunch, s->kfSeen, emit, flush))) return rc;
-    for (int i = 0; i < n; i++) s->kfCtr[slots[i]] = 1;
-    return ORBX_OK;
+    s->refresh = nullptr;
 }
 
 extern "C" int orbw_debug_pool_get(orbw_pool_t* p, const int32_t* ids, int n, OrbwPoint* out)
@@ -175,14 +72,10 @@ static int orbr_blocks_ensure(orbu_store* s, int n)
         const size_t P = (size_t)p->cap, E = (size_t)s->kfcap * s->pitch;
         Packer pk;
         const size_t oMark = pk.take(P * 8), oKeys = pk.take(E * 4), oHdr = pk.take(orbr::H_INTS * 4), bytes = pk.off;
-        auto bail = [&](int code) { if (b->d_block) (void)hipFree(b->d_block); delete b; return code; };
-        HIPCHK_OR(hipMalloc(&b->d_block, bytes), bail(0));
-        HIPCHK_OR(hipMemsetAsync(b->d_block, 0, bytes, p->stream), bail(0));
-        HIPCHK_OR(hipStreamSynchronize(p->stream), bail(0));
+        if (int rc = orbu_block_once(p, b->d_block, bytes, 0)) { delete b; return rc; }
         b->dev.mark = (unsigned long long*)(b->d_block + oMark); b->dev.keys = (uint32_t*)(b->d_block + oKeys); b->dev.hdr = (int32_t*)(b->d_block + oHdr);
         b->dev.keysCap = (int32_t)E; b->dev.pool = p->dev;
-        p->h->nDevAlloc++;
-        s->refresh = b; s->rmarks = b->dev.mark;   // (what orbu_next_generation clears at the wrap: set with refresh, dropped with it in orbr_release)
+        s->refresh = b; s->marks[s->nMarks++] = {b->dev.mark, P * 8};
     }
     orbr_blocks* b = s->refresh;
     Packer pk;
@@ -193,7 +86,31 @@ static int orbr_blocks_ensure(orbu_store* s, int n)
     if (rc) return rc;
     b->dev.cnt = (int32_t*)(b->d_pts + oCnt); b->dev.start = (int32_t*)(b->d_pts + oStart); b->dev.fill = (int32_t*)(b->d_pts + oFill);
     b->dev.listShort = (int32_t*)(b->d_pts + oShort); b->dev.listLong = (int32_t*)(b->d_pts + oLong); b->dev.res = (uint32_t*)(b->d_pts + oRes);
-    b->dev.desc = s->d_desc; b->dev.ctr = s->d_ctr; b->dev.oct = s->d_oct;
+    b->dev.desc = s->desc.d; b->dev.ctr = s->ctr.d; b->dev.oct = s->oct.d;
+    return ORBX_OK;
+}
+
+// the observation index of c's points and their refresh, on stream st: what orbr_refresh_points and orbe_correct_sim3 launch alike
+static void orbr_issue(const orbu_store* s, const orbr_blocks* b, const orbr::Call& c, hipStream_t st)
+{
+    const int n = c.n;
+    const unsigned ptBlocks = (unsigned)((n + orbr::kThreads - 1) / orbr::kThreads);
+    const unsigned walkBlocks = (unsigned)((s->hi + orbr::kWaves - 1) / orbr::kWaves);
+    hipLaunchKernelGGL(orbr::k_mark, dim3(ptBlocks), dim3(orbr::kThreads), 0, st, b->dev, c);
+    if (walkBlocks) hipLaunchKernelGGL(orbr::k_walk, dim3(walkBlocks), dim3(orbr::kThreads), 0, st, s->dev, b->dev, n, s->hi, 0);
+    hipLaunchKernelGGL(orbr::k_segments, dim3(ptBlocks), dim3(orbr::kThreads), 0, st, b->dev, n);
+    if (walkBlocks) hipLaunchKernelGGL(orbr::k_walk, dim3(walkBlocks), dim3(orbr::kThreads), 0, st, s->dev, b->dev, n, s->hi, 1);
+    // (any grid is correct: the refresh kernels stride over their lists, whose lengths only the device knows)
+    hipLaunchKernelGGL(orbr::k_refresh_short, dim3(std::min(4096u, (unsigned)((n + orbr::kGroups - 1) / orbr::kGroups))), dim3(orbr::kThreads), 0, st, s->dev, b->dev, c);
+    hipLaunchKernelGGL(orbr::k_refresh_long, dim3(std::min(1024u, (unsigned)n)), dim3(orbr::kThreads), 0, st, s->dev, b->dev, c);
+}
+
+// the header words of orbr_issue as they came down.  whose: "a listed point", "a moved point"
+static int orbr_check_header(const int32_t* hdr, int n, const orbr_blocks* b, const char* whose)
+{
+    if (hdr[orbr::H_ERR]) return fail(ORBX_E_UNSUPPORTED, "%s has more than %d observations", whose, ORBR_MAX_OBS);
+    if (hdr[orbr::H_NSHORT] + hdr[orbr::H_NLONG] != n || hdr[orbr::H_TOTAL] < 0 || hdr[orbr::H_TOTAL] > b->dev.keysCap)
+        return fail(ORBX_E_HIP, "the observation index holds %d + %d of %d points and %d keys", hdr[orbr::H_NSHORT], hdr[orbr::H_NLONG], n, hdr[orbr::H_TOTAL]);
     return ORBX_OK;
 }
 
@@ -214,25 +131,11 @@ extern "C" int orbr_refresh_points(orbu_store_t* s, const int32_t* ids, const in
     std::lock_guard<std::mutex> l(p->mu);
     if (n > p->cap) return fail(ORBX_E_UNSUPPORTED, "%d points for a pool of %d", n, p->cap);
     if ((rc = orbw_check_ids(p, "ids", ids, n, false))) return rc;
-    {   // an id repeated within the call (the pool's scratch bits, all zero between calls)
-        int dup = -1;
-        for (int i = 0; i < n && dup < 0; i++) {
-            uint64_t& w = p->seen[(size_t)ids[i] >> 6];
-            const uint64_t bit = 1ull << (ids[i] & 63);
-            if (w & bit) dup = i;
-            w |= bit;
-        }
-        for (int i = 0; i < n; i++) p->seen[(size_t)ids[i] >> 6] = 0;
-        if (dup >= 0) return fail(ORBX_E_INVALID, "ids[%d] = %d is repeated within the call", dup, ids[dup]);
-    }
+    const int dup = first_repeated_key(ids, n, p->seen);   // (the pool's scratch bits, all zero between calls)
+    if (dup >= 0) return fail(ORBX_E_INVALID, "ids[%d] = %d is repeated within the call", dup, ids[dup]);
     for (int i = 0; i < n; i++)
         if ((rc = orbu_check_slot(s, "ref_kf", i, ref_kf[i], true, true))) return rc;
-    for (int k = 0; k < s->hi; k++) {
-        if (!s->kfSet[k]) continue;
-        if ((what & ORBR_DESCRIPTOR) && (!s->d_desc || !s->kfDesc[k])) return fail(ORBX_E_INVALID, "keyframe slot %d has no descriptors (orbu_kf_set_descriptors)", k);
-        if ((what & ORBR_NORMAL_DEPTH) && (!s->d_ctr || !s->kfCtr[k])) return fail(ORBX_E_INVALID, "keyframe slot %d has no centre (orbu_kf_set_centres)", k);
-        if ((what & ORBR_NORMAL_DEPTH) && (!s->d_oct || !s->kfOct[k])) return fail(ORBX_E_INVALID, "keyframe slot %d has no octaves (orbu_kf_set_octaves)", k);
-    }
+    if ((rc = orbu_check_columns(s, what & ORBR_DESCRIPTOR, what & ORBR_NORMAL_DEPTH, what & ORBR_NORMAL_DEPTH))) return rc;
     if ((rc = orbr_blocks_ensure(s, n))) return rc;
     Packer pk;
     const size_t oIds = pk.take((size_t)n * 4), oRef = pk.take((size_t)n * 4), oPos = pk.take(new_pos ? (size_t)n * 12 : 0), oSf = pk.take(ORBX_MAX_LEVELS * 4),
@@ -251,24 +154,14 @@ extern "C" int orbr_refresh_points(orbu_store_t* s, const int32_t* ids, const in
     c.newPos = new_pos ? (const float*)(s->h_stage + oPos) : nullptr; c.sf = (const float*)(s->h_stage + oSf);
     c.n = n; c.what = what; c.nlevels = nlevels;
     int32_t* hdr = (int32_t*)(s->h_stage + oHdr);
-    const unsigned ptBlocks = (unsigned)((n + orbr::kThreads - 1) / orbr::kThreads);
-    const unsigned walkBlocks = (unsigned)((s->hi + orbr::kWaves - 1) / orbr::kWaves);
-    hipLaunchKernelGGL(orbr::k_mark, dim3(ptBlocks), dim3(orbr::kThreads), 0, st, b->dev, c);
-    if (walkBlocks) hipLaunchKernelGGL(orbr::k_walk, dim3(walkBlocks), dim3(orbr::kThreads), 0, st, s->dev, b->dev, n, s->hi, 0);
-    hipLaunchKernelGGL(orbr::k_segments, dim3(ptBlocks), dim3(orbr::kThreads), 0, st, b->dev, n);
-    if (walkBlocks) hipLaunchKernelGGL(orbr::k_walk, dim3(walkBlocks), dim3(orbr::kThreads), 0, st, s->dev, b->dev, n, s->hi, 1);
-    // (any grid is correct: the refresh kernels stride over their lists, whose lengths only the device knows)
-    hipLaunchKernelGGL(orbr::k_refresh_short, dim3(std::min(4096u, (unsigned)((n + orbr::kGroups - 1) / orbr::kGroups))), dim3(orbr::kThreads), 0, st, s->dev, b->dev, c);
-    hipLaunchKernelGGL(orbr::k_refresh_long, dim3(std::min(1024u, (unsigned)n)), dim3(orbr::kThreads), 0, st, s->dev, b->dev, c);
+    orbr_issue(s, b, c, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(hdr, b->dev.hdr, orbr::H_INTS * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    if (hdr[orbr::H_ERR]) return fail(ORBX_E_UNSUPPORTED, "a listed point has more than %d observations", ORBR_MAX_OBS);
-    if (hdr[orbr::H_NSHORT] + hdr[orbr::H_NLONG] != n || hdr[orbr::H_TOTAL] < 0 || hdr[orbr::H_TOTAL] > b->dev.keysCap)
-        return fail(ORBX_E_HIP, "the observation index holds %d + %d of %d points and %d keys", hdr[orbr::H_NSHORT], hdr[orbr::H_NLONG], n, hdr[orbr::H_TOTAL]);
+    if ((rc = orbr_check_header(hdr, n, b, "a listed point"))) return rc;
     if (commit) {
-        hipLaunchKernelGGL(orbr::k_commit, dim3(ptBlocks), dim3(orbr::kThreads), 0, st, b->dev, c);
+        hipLaunchKernelGGL(orbr::k_commit, dim3((unsigned)((n + orbr::kThreads - 1) / orbr::kThreads)), dim3(orbr::kThreads), 0, st, b->dev, c);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(out, b->dev.res, (size_t)n * sizeof(OrbrPoint), hipMemcpyDeviceToHost, st));

@@ -218,9 +218,9 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbz_host.inc"   // OptimizeSim3
 #include "orbx_poolutil.inc"   // the pool and the store as the host holds them; what orbw, orbu, orbn and orbq share on the host
 #include "orbw_host.inc"   // the map-point pool: SearchLocalPoints and TrackWithMotionModel's search from resident MapPoints
-#include "orbu_host.inc"   // the keyframe store beside the pool: UpdateLocalMap, and SearchLocalPoints from its resident list
+#include "orbu_host.inc"   // the keyframe store beside the pool and every setter of it: UpdateLocalMap, and SearchLocalPoints from its resident list
 #include "orbn_host.inc"   // the covisibility entries over the store: batched UpdateConnections and KeyFrameCulling counts
-#include "orbr_host.inc"   // the refresh entry, the store's descriptor and centre setters, orbw_debug_pool_get
-#include "orbe_host.inc"   // the loop correction's entry, and mpRefKF resident beside the pool
+#include "orbr_host.inc"   // the refresh entry and its blocks, orbw_debug_pool_get
+#include "orbe_host.inc"   // the loop correction's entry and its blocks
 #include "orbq_host.inc"   // PoseOptimization behind the pool searches: TrackWithMotionModel's and TrackLocalMap's verdicts
 #include "orby_host.inc"   // SearchBySim3 and OptimizeSim3 from the pool, the store and the frame set: ComputeSim3's verdict per candidate

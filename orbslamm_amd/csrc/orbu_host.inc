@@ -1,6 +1,9 @@
 // orbu_host.inc -- host side of Tracking::UpdateLocalMap on the device (part of orbslamm_hip.hip; kernels: orbu_kernels.hip,
 // ABI: include/orbslamm_localmap.h, DESIGN.md §8r).
-//   the store     struct orbu_store, the slot and entry checks, the generation tag, the last-wins staging: orbx_poolutil.inc
+//   the store     struct orbu_store, the slot and entry checks, the generation tag, the last-wins staging: orbx_poolutil.inc.
+//                 Create and destroy are here, and EVERY setter of the store: the records, and the columns the later families read
+//                 (octaves, descriptors, centres, mpRefKF; their scatter kernels are orbr::'s and orbe::'s).  The store owns and frees
+//                 the columns; orbn, orbr and orbe free their own blocks in their *_release
 //   the call      stamp, vote, select, mark, count, scan, write on the pool's stream, one synchronisation; the kernels leave
 //                 the result in the store's pinned block themselves
 //   the search    orbw_track (orbw_host.inc) reading the store's S where it lies
@@ -55,7 +58,7 @@ extern "C" int orbu_store_create(orbw_pool_t* pool, int kf_capacity, int stride,
     s->out.L = (int32_t*)(d + oL); s->out.S = (int32_t*)(d + oS);
     s->out.hHdr = (int32_t*)(s->h_res + hHdr); s->out.hList = (int32_t*)(s->h_res + hList); s->out.hVotes = (int32_t*)(s->h_res + hVotes);
     s->out.hL = (int32_t*)(s->h_res + hL); s->out.hSeen = s->h_res + hSeen; s->out.maxL = s->maxL;
-    s->kfSet.assign(K, 0); s->kfSeen.assign((K + 63) / 64, 0); s->idxSeen.assign(((size_t)stride + 63) / 64, 0);
+    s->kfSet.assign(K, 0); s->oct.has.assign(K, 0); s->desc.has.assign(K, 0); s->ctr.has.assign(K, 0); s->kfSeen.assign((K + 63) / 64, 0); s->idxSeen.assign(((size_t)stride + 63) / 64, 0);
     s->blocks = (unsigned)std::min<size_t>(nchunks, 1024);
     pool->h->refs++;
     pool->h->nDevAlloc++; pool->h->nHostAlloc++;
@@ -79,7 +82,7 @@ extern "C" int orbu_store_destroy(orbu_store_t* s)
     orbn_release(s);
     orbr_release(s);
     orbe_release(s);
-    (void)hipFree(s->d_block);
+    for (void* d : {(void*)s->oct.d, (void*)s->desc.d, (void*)s->ctr.d, (void*)s->d_refKf, (void*)s->d_block}) (void)hipFree(d);   // (null: no-op)
     (void)hipHostFree(s->h_res);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (h) orbm_release(h);
@@ -198,6 +201,154 @@ extern "C" int orbu_kf_set_entries(orbu_store_t* store, int slot, const int32_t*
 {
     if (slot < 0) return fail(ORBX_E_INVALID, "keyframe slot %d", slot);
     return orbu_pairs_write(store, slot, idx, vals, nullptr, n);
+}
+
+// ---- the columns: each made at the first call of its setter (orbu_block_once), read by orbn, orbr and orbe
+
+extern "C" int orbu_kf_set_octaves(orbu_store_t* s, int slot, const uint8_t* octaves, int n)
+{
+    if (n < 0) return fail(ORBX_E_INVALID, "negative count");
+    if (slot < 0) return fail(ORBX_E_INVALID, "keyframe slot %d", slot);
+    if (n > 0 && !octaves) return fail(ORBX_E_INVALID, "null argument");
+    int rc = orbu_store_check(s);
+    if (rc) return rc;
+    orbw_pool* p = s->pool;
+    std::lock_guard<std::mutex> l(p->mu);
+    if ((rc = orbu_check_slot(s, "slot", 0, slot, true))) return rc;
+    if (n > s->stride) return fail(ORBX_E_UNSUPPORTED, "%d octaves for a stride of %d", n, s->stride);
+    {   // the distinct values the store has been given: the histograms have a bin for each
+        bool seen[256];
+        int distinct = 0;
+        for (int v = 0; v < 256; v++) { seen[v] = s->octSeen[v]; }
+        seen[0] = seen[0] || n < s->stride;
+        for (int i = 0; i < n; i++) seen[octaves[i]] = true;
+        for (int v = 0; v < 256; v++) distinct += seen[v] ? 1 : 0;
+        if (distinct > ORBN_MAX_OCTAVE_VALUES)
+            return fail(ORBX_E_UNSUPPORTED, "%d distinct octave values in the store, at most %d", distinct, ORBN_MAX_OCTAVE_VALUES);
+    }
+    if ((rc = orbu_block_once(p, s->oct.d, (size_t)s->kfcap * s->pitch, 0))) return rc;
+    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, (size_t)s->pitch))) return rc;
+    if (n) memcpy(s->h_stage, octaves, (size_t)n);
+    memset(s->h_stage + n, 0, (size_t)(s->pitch - n));
+    HIPCHK(hipMemcpyAsync(s->oct.d + (size_t)slot * s->pitch, s->h_stage, (size_t)s->pitch, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (n < s->stride) s->octSeen[0] = 1;
+    for (int i = 0; i < n; i++) s->octSeen[octaves[i]] = 1;
+    s->oct.has[slot] = 1;
+    return ORBX_OK;
+}
+
+extern "C" int orbu_kf_set_descriptors(orbu_store_t* s, int slot, const uint8_t* desc, int n)
+{
+    if (n < 0) return fail(ORBX_E_INVALID, "negative count");
+    if (slot < 0) return fail(ORBX_E_INVALID, "keyframe slot %d", slot);
+    if (!desc) return fail(ORBX_E_INVALID, "null argument");
+    int rc = orbu_store_check(s);
+    if (rc) return rc;
+    orbw_pool* p = s->pool;
+    std::lock_guard<std::mutex> l(p->mu);
+    if ((rc = orbu_check_slot(s, "slot", 0, slot, true))) return rc;
+    if (n > s->stride) return fail(ORBX_E_UNSUPPORTED, "%d descriptors for a stride of %d", n, s->stride);
+    const size_t rowBytes = (size_t)s->pitch * 32;
+    if ((rc = orbu_block_once(p, s->desc.d, (size_t)s->kfcap * rowBytes, 0))) return rc;
+    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, rowBytes))) return rc;
+    if (n) memcpy(s->h_stage, desc, (size_t)n * 32);
+    memset(s->h_stage + (size_t)n * 32, 0, rowBytes - (size_t)n * 32);
+    const int n16 = (int)(rowBytes / 16);
+    hipLaunchKernelGGL(orbr::k_desc_scatter, dim3((unsigned)((n16 + orbr::kThreads - 1) / orbr::kThreads)), dim3(orbr::kThreads), 0, p->stream,
+                       s->desc.d + (size_t)slot * rowBytes, (const uint4*)s->h_stage, n16);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    s->desc.has[slot] = 1;
+    return ORBX_OK;
+}
+
+extern "C" int orbu_kf_set_descriptors_frame(orbu_store_t* s, int slot, orbm_frameset_t* fs, int fs_slot)
+{
+    if (slot < 0) return fail(ORBX_E_INVALID, "keyframe slot %d", slot);
+    if (!fs) return fail(ORBX_E_INVALID, "null argument");
+    int rc = orbu_store_check(s);
+    if (rc) return rc;
+    if ((rc = frameset_check(fs))) return rc;
+    orbw_pool* p = s->pool;
+    if (fs->owner != p->h) return fail(ORBX_E_INVALID, "the frame set and the pool must be on one matcher handle");
+    if (fs_slot < 0 || fs_slot >= fs->slots) return fail(ORBX_E_INVALID, "slot %d outside the frame set", fs_slot);
+    std::lock_guard<std::mutex> l(p->mu);
+    if ((rc = orbu_check_slot(s, "slot", 0, slot, true))) return rc;
+    int32_t n = 0;
+    hipStream_t fst = fs_stream(fs);
+    HIPCHK(hipMemcpyAsync(&n, fs->fs.n + fs_slot, 4, hipMemcpyDeviceToHost, fst));
+    HIPCHK(hipStreamSynchronize(fst));   // (the slot's build is complete behind this)
+    if (n < 0 || n > fs->cap) return fail(ORBX_E_HIP, "a frame-set slot of %d features, capacity %d", n, fs->cap);
+    if (n > s->stride) return fail(ORBX_E_UNSUPPORTED, "%d descriptors for a stride of %d", n, s->stride);
+    const size_t rowBytes = (size_t)s->pitch * 32;
+    if ((rc = orbu_block_once(p, s->desc.d, (size_t)s->kfcap * rowBytes, 0))) return rc;
+    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, 16))) return rc;
+    uint8_t* dst = s->desc.d + (size_t)slot * rowBytes;
+    if (n) HIPCHK(hipMemcpyAsync(dst, fs->fs.desc + (size_t)fs_slot * fs->cap * 32, (size_t)n * 32, hipMemcpyDeviceToDevice, p->stream));
+    if (rowBytes > (size_t)n * 32) HIPCHK(hipMemsetAsync(dst + (size_t)n * 32, 0, rowBytes - (size_t)n * 32, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    s->desc.has[slot] = 1;
+    return ORBX_OK;
+}
+
+extern "C" int orbu_kf_set_centres(orbu_store_t* s, const int32_t* slots, const float* Ow, int n)
+{
+    if (n < 0) return fail(ORBX_E_INVALID, "negative count");
+    if (n == 0) return ORBX_OK;
+    if (!slots || !Ow) return fail(ORBX_E_INVALID, "null argument");
+    int rc = orbu_store_check(s);
+    if (rc) return rc;
+    orbw_pool* p = s->pool;
+    std::lock_guard<std::mutex> l(p->mu);
+    for (int i = 0; i < n; i++)
+        if ((rc = orbu_check_slot(s, "slots", i, slots[i], true))) return rc;
+    if ((rc = orbu_block_once(p, s->ctr.d, (size_t)s->kfcap * 12, 0))) return rc;
+    const int perLaunch = (int)std::min<size_t>((size_t)n, kStoreStageBytes / 16);
+    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, (size_t)perLaunch * 16))) return rc;
+    uint4* stage = (uint4*)s->h_stage;
+    auto emit = [=](int i, int m) {   // (by value, as orbw_pool_write's)
+        uint32_t w[3];
+        memcpy(w, Ow + 3 * (size_t)i, 12);
+        stage[m] = make_uint4((uint32_t)slots[i], w[0], w[1], w[2]);
+    };
+    auto flush = [=](int m) -> int {
+        hipLaunchKernelGGL(orbr::k_centre_scatter, dim3((unsigned)((m + orbr::kThreads - 1) / orbr::kThreads)), dim3(orbr::kThreads), 0, p->stream,
+                           s->ctr.d, s->kfcap, (const uint4*)stage, m);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(p->stream));
+        return ORBX_OK;
+    };
+    if ((rc = stage_last_wins(slots, n, perLaunch, perLaunch, s->kfSeen, emit, flush))) return rc;
+    for (int i = 0; i < n; i++) s->ctr.has[slots[i]] = 1;
+    return ORBX_OK;
+}
+
+extern "C" int orbu_point_set_ref_kf(orbu_store_t* s, const int32_t* ids, const int32_t* kf_slots, int n)
+{
+    if (n < 0) return fail(ORBX_E_INVALID, "negative count");
+    if (n == 0) return ORBX_OK;
+    if (!ids || !kf_slots) return fail(ORBX_E_INVALID, "null argument");
+    int rc = orbu_store_check(s);
+    if (rc) return rc;
+    orbw_pool* p = s->pool;
+    std::lock_guard<std::mutex> l(p->mu);
+    if ((rc = orbw_check_ids(p, "ids", ids, n, false, false))) return rc;
+    for (int i = 0; i < n; i++)
+        if ((rc = orbu_check_slot(s, "kf_slots", i, kf_slots[i], false, true))) return rc;
+    if ((rc = orbu_block_once(p, s->d_refKf, (size_t)p->cap * 4, 0xff))) return rc;   // every id -1
+    const int perLaunch = (int)std::min<size_t>((size_t)n, kStoreStageBytes / 8);
+    if ((rc = orbw_begin_write(p, s->h_stage, s->stageCap, (size_t)perLaunch * 8))) return rc;
+    int2* stage = (int2*)s->h_stage;
+    auto emit = [=](int i, int m) { stage[m] = make_int2(ids[i], kf_slots[i]); };   // (by value, as orbw_pool_write's)
+    auto flush = [=](int m) -> int {
+        hipLaunchKernelGGL(orbe::k_ref_scatter, dim3((unsigned)((m + orbe::kThreads - 1) / orbe::kThreads)), dim3(orbe::kThreads), 0, p->stream,
+                           s->d_refKf, p->cap, (const int2*)stage, m);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(p->stream));
+        return ORBX_OK;
+    };
+    return stage_last_wins(ids, n, perLaunch, perLaunch, p->seen, emit, flush);
 }
 
 extern "C" int orbu_debug_set_generation(orbu_store_t* s, uint32_t generation)

@@ -1,5 +1,6 @@
-// orbx_lastwins.hpp -- the last-wins staging under orbw_pool_write, orbu_kf_write and orbu_pairs_write (orbx_poolutil.inc includes
-// it).  Plain C++ with no HIP in it, so tests/cpp/lastwins_host.cpp runs it on the host alone under the sanitizers.
+// orbx_lastwins.hpp -- the two walks over a call's keys and a bit vector: the last-wins staging under orbw_pool_write, orbu_kf_write
+// and orbu_pairs_write, and the first repeated key of a call that takes each once (orbx_poolutil.inc includes it).  Plain C++ with
+// no HIP in it, so tests/cpp/lastwins_host.cpp runs it on the host alone under the sanitizers.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -32,4 +33,20 @@ static int stage_last_wins(const int32_t* keys, int n, int window, int perLaunch
         if (m && !rc) rc = flush(m);
     }
     return rc;
+}
+
+// A key repeated within a call that takes each at most once (orbr_refresh_points' ids, orbe_correct_sim3's slots): the index of
+// the first key that an earlier one equals, or -1.  `seen` as above: all zero on entry and on exit.  (Inlined by force: the walk
+// runs once per key of the call and stands where the callers' own loops stood.)
+__attribute__((always_inline)) static inline int first_repeated_key(const int32_t* keys, int n, std::vector<uint64_t>& seen)
+{
+    int dup = -1;
+    for (int i = 0; i < n && dup < 0; i++) {
+        uint64_t& w = seen[(size_t)keys[i] >> 6];
+        const uint64_t bit = 1ull << (keys[i] & 63);
+        if (w & bit) dup = i;
+        w |= bit;
+    }
+    for (int i = 0; i < n; i++) seen[(size_t)keys[i] >> 6] = 0;
+    return dup;
 }

@@ -1,6 +1,7 @@
 // orbx_poolutil.inc -- what the host files of the map-point pool's families share (part of orbslamm_hip.hip, in front of
 // orbw_host.inc, orbu_host.inc, orbn_host.inc, orbr_host.inc, orbe_host.inc and orbq_host.inc): the pool and the keyframe store as the host holds them, the
-// steps of the concurrency rule (DESIGN.md §8q), the id and slot checks, the store's generation tag, the last-wins staging.
+// steps of the concurrency rule (DESIGN.md §8q), the id and slot checks, the store's columns, made-once blocks and mark words, its
+// generation tag, the last-wins staging and the repeated-key walk.
 
 constexpr int kPoolChunk = 1 << 16;                    // records per pool setter launch: the pinned staging is 5 MB at the most
 constexpr size_t kStoreStageBytes = (size_t)8 << 20;   // a store setter launch's staged records
@@ -24,12 +25,17 @@ struct orbw_pool {
     bool isSet(int id) const { return (setBits[(size_t)id >> 6] >> (id & 63)) & 1; }
 };
 
-struct orbn_blocks;   // orbn_host.inc: the covisibility entries' blocks, made at their first call
-struct orbr_blocks;   // orbr_host.inc: the map-point refresh's blocks, made at its first call
-struct orbe_blocks;   // orbe_host.inc: the loop correction's blocks, made at its first call
+struct orbn_blocks; struct orbr_blocks; struct orbe_blocks;   // orbn_host.inc, orbr_host.inc, orbe_host.inc: a family's blocks, made at its first call
+constexpr int kStoreFamilies = 3;   // each lists one block of mark words in the store, once
+
+// an optional per-slot array of the store, made at the first call of its setter; has[k]: slot k was given it
+template <class T>
+struct orbu_column { T* d = nullptr; std::vector<uint8_t> has; };
 
 // keyframe match lists, flags and graph records in HBM beside ONE map-point pool, whose mutex and stream it uses; a "set" byte per
-// slot on the host; all blocks of a fixed size made at create, the staging grow-only
+// slot on the host; all blocks of a fixed size made at create, the staging grow-only.  The columns and the pool-sized d_refKf are
+// the store's: orbu_host.inc's setters make and fill them, orbu_store_destroy frees them, whichever family reads them.  A family
+// owns its blocks alone (covis, refresh, correct) and lists the mark words in them in `marks` for as long as the block lives
 struct orbu_store {
     uint64_t serial = ++g_poolSerial;
     orbw_pool* pool = nullptr;
@@ -49,19 +55,16 @@ struct orbu_store {
     uint32_t updates = 0;                              // updates begun so far: each overwrites S
     unsigned blocks = 1;                               // the point walk's grid at the most: one block a chunk of the whole store, <= 1 024
     int lastNkf = 0;                                   // the local keyframes of the last update: sizes the next update's grid
-    orbn_blocks* covis = nullptr;                      // orbn_*: null until the first call
-    unsigned long long* marks = nullptr;               // ... and covis->dev.mark: set and dropped with covis (orbn_host.inc); orbn_blocks is incomplete here
-    uint8_t* d_oct = nullptr;                          // orbu_kf_set_octaves: [kfcap * pitch] bytes, null until the first call
-    std::vector<uint8_t> kfOct;                        // the slots that have octaves
+    orbu_column<uint8_t> oct;                          // orbu_kf_set_octaves: [kfcap * pitch] bytes
     uint8_t octSeen[256] = {};                         // the octave values the store has been given
-    orbr_blocks* refresh = nullptr;                    // orbr_refresh_points: null until the first call
-    unsigned long long* rmarks = nullptr;              // ... and its pool-sized marks: set and dropped with refresh (orbr_host.inc)
-    uint8_t* d_desc = nullptr;                         // orbu_kf_set_descriptors*: [kfcap * pitch * 32] bytes, null until the first call
-    float* d_ctr = nullptr;                            // orbu_kf_set_centres: [kfcap * 3], null until the first call
-    std::vector<uint8_t> kfDesc, kfCtr;                // the slots that have descriptors, a centre
+    orbu_column<uint8_t> desc;                         // orbu_kf_set_descriptors*: [kfcap * pitch * 32] bytes
+    orbu_column<float> ctr;                            // orbu_kf_set_centres: [kfcap * 3]
     int32_t* d_refKf = nullptr;                        // orbu_point_set_ref_kf: mpRefKF per pool id [pool capacity], null until the first call
+    orbn_blocks* covis = nullptr;                      // orbn_*: null until the first call
+    orbr_blocks* refresh = nullptr;                    // orbr_refresh_points: null until the first call (orbe_correct_sim3's included)
     orbe_blocks* correct = nullptr;                    // orbe_correct_sim3: null until the first call
-    unsigned long long* emarks = nullptr; size_t emarkBytes = 0;   // ... and its pool-sized claim words: set and dropped with correct (orbe_host.inc)
+    struct Marks { void* p; size_t bytes; };
+    Marks marks[kStoreFamilies]; int nMarks = 0;       // the families' mark words: what orbu_next_generation clears at the wrap
 };
 
 static int orbw_pool_check(orbw_pool* p)
@@ -146,20 +149,52 @@ __attribute__((always_inline)) static inline int orbu_check_slot(const orbu_stor
 }
 
 // ---- (the pool's mutex is held) the store's next generation tag, for kernels on stream st: what stamp, first and the
-// covisibility marks hold under an older tag reads as empty, so nothing is cleared between calls
+// families' mark words hold under an older tag reads as empty, so nothing is cleared between calls
 static int orbu_next_generation(orbu_store* s, hipStream_t st, uint32_t* tag)
 {
     if (s->gen == 0xffffffffu) {   // the tag wraps: one clear, and the tags start over
         const size_t bytes = (size_t)s->pool->cap * 8;
         HIPCHK(hipMemsetAsync(s->scr.stamp, 0, bytes, st));
         HIPCHK(hipMemsetAsync(s->scr.first, 0xff, bytes, st));
-        if (s->marks) HIPCHK(hipMemsetAsync(s->marks, 0, bytes, st));
-        if (s->rmarks) HIPCHK(hipMemsetAsync(s->rmarks, 0, bytes, st));
-        if (s->emarks) HIPCHK(hipMemsetAsync(s->emarks, 0, s->emarkBytes, st));
+        for (int i = 0; i < s->nMarks; i++) HIPCHK(hipMemsetAsync(s->marks[i].p, 0, s->marks[i].bytes, st));
         s->gen = 0;
     }
     *tag = ++s->gen;
     return ORBX_OK;
 }
 
-#include "orbx_lastwins.hpp"   // stage_last_wins: the last record of a repeated key wins, under the three setters
+// a family's block is about to be freed: its mark words leave the list (each family's *_blocks_ensure added them, once)
+static void orbu_marks_drop(orbu_store* s, const void* p)
+{
+    for (int i = 0; i < s->nMarks; i++)
+        if (s->marks[i].p == p) { s->marks[i] = s->marks[--s->nMarks]; return; }
+}
+
+// ---- (the pool's mutex is held) a device block made once: `bytes` filled with `fill` on the pool's stream and counted in
+// nDevAlloc, or ORBX_E_HIP with nothing leaked and d null.  The store's columns and d_refKf, the families' fixed blocks
+template <class T>
+static int orbu_block_once(orbw_pool* p, T*& d, size_t bytes, int fill)
+{
+    if (d) return ORBX_OK;
+    HIPCHK(hipMalloc((void**)&d, bytes));
+    p->h->nDevAlloc++;
+    hipError_t e = hipMemsetAsync(d, fill, bytes, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess) { (void)hipFree(d); d = nullptr; return fail(ORBX_E_HIP, "clearing a block of the store failed: %s", hipGetErrorString(e)); }
+    return ORBX_OK;
+}
+
+// (the pool's mutex is held) every set keyframe has the columns the call reads.  (Inlined by force, as the checkers above: a walk
+// over every slot a call, which the callers' constants cut down to the columns they ask for.)
+__attribute__((always_inline)) static inline int orbu_check_columns(const orbu_store* s, bool desc, bool ctr, bool oct)
+{
+    for (int k = 0; k < s->hi; k++) {
+        if (!s->kfSet[k]) continue;
+        if (desc && !s->desc.has[k]) return fail(ORBX_E_INVALID, "keyframe slot %d has no descriptors (orbu_kf_set_descriptors)", k);
+        if (ctr && !s->ctr.has[k]) return fail(ORBX_E_INVALID, "keyframe slot %d has no centre (orbu_kf_set_centres)", k);
+        if (oct && !s->oct.has[k]) return fail(ORBX_E_INVALID, "keyframe slot %d has no octaves (orbu_kf_set_octaves)", k);
+    }
+    return ORBX_OK;
+}
+
+#include "orbx_lastwins.hpp"   // stage_last_wins: the last record of a repeated key wins, under the setters; first_repeated_key

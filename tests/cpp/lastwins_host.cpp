@@ -1,6 +1,7 @@
 // stage_last_wins (orbslamm_amd/csrc/orbx_lastwins.hpp) on the host alone, with in-memory emit and flush: every form the three
 // setters use it in, held to "the last record of a key wins" computed directly; built with -fsanitize=address,undefined by
 // tests/test_localmap_update_cpu.py.  A flush stores its survivors into `table` as the scatter kernels do: later launches land last.
+// first_repeated_key of the same header: no repeat, a repeat at index 1 and at the last index, keys on both sides of a word, n = 0.
 #include "../../orbslamm_amd/csrc/orbx_lastwins.hpp"
 
 #include <cstdio>
@@ -28,8 +29,26 @@ static int run(int nkeys, int n, int window, int perLaunch, int failAt, unsigned
     return launches;
 }
 
+// first_repeated_key over `keys`: the index it must return, and the scratch zero behind it
+static void repeat(std::initializer_list<int32_t> keys, int want)
+{
+    std::vector<uint64_t> seen(2, 0);   // keys below 128: 63 and 64 lie in two words
+    const int got = first_repeated_key(keys.begin(), (int)keys.size(), seen);
+    if (got != want) { fprintf(stderr, "first_repeated_key over %zu keys: %d, not %d\n", keys.size(), got, want); exit(1); }
+    for (uint64_t w : seen) if (w) { fprintf(stderr, "first_repeated_key over %zu keys leaves the scratch set\n", keys.size()); exit(1); }
+}
+
 int main()
 {
+    repeat({}, -1);                          // n = 0
+    repeat({5}, -1);
+    repeat({3, 1, 4, 15, 9, 2, 6}, -1);      // no repeat
+    repeat({7, 7, 1, 2}, 1);                 // at index 1
+    repeat({3, 1, 4, 15, 9, 2, 4}, 6);       // at the last index
+    repeat({3, 1, 3, 1, 3}, 2);              // the first of several
+    repeat({63, 64}, -1);                    // bit 63 of one word, bit 0 of the next: not each other's
+    repeat({63, 64, 0, 127, 64}, 4);
+    repeat({64, 63, 63}, 2);
     int total = 0;
     // the pool's and the pair setters' form: window == perLaunch; a repeated key on both sides of a window's end; n a multiple and not
     for (int n : {1, 7, 64, 65, 128, 1000}) for (int per : {1, 8, 64}) total += run(13, n, per, per, -1, (unsigned)(n * 31 + per));
