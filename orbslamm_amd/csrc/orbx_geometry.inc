@@ -252,8 +252,28 @@ static int build_geometry(const orbx_handle* h, int w, int h0, HostGeom& out)
     // (scale factors near 2, huge frames) the per-level kernel is used instead.
     // A latency handle (max_batch <= 2) starts one refinement finer: 128 blocks instead of 32 for the one frame in flight
     out.pyrFused = false;
+    out.pyrBlocks = 1; out.pyrBufA = out.pyrBufB = out.pyrTabCap = 4;
+    // k_pyramid reads the taps of a dword group (outputs 4k .. 4k + 3, the tail repeating the level's last entry) as the 8
+    // bytes from the group's first tap on and sums a pixel's two taps with an unsigned 16-bit dot: the group's last tap,
+    // sx[3] + 1, lies at most 7 bytes behind sx[0] (5 at scale factors 1.1 - 1.3, 6 at 1.5, 7 at 1.9; level sizes are rounded,
+    // so it is checked per level, not derived), and the coefficients are in [0, 2048] (fx in [0, 1)).  Established here,
+    // once; a shape that breaks either takes the per-level kernel.
+    bool pyrWindow = true;
+    for (int l = 1; l < g.nlevels; l++) {
+        const short4* xt = &out.tabs[out.xoff[l]];
+        const int dw = g.lv[l].w;
+        for (int dx = 0; dx < dw; dx++) {
+            const int last = std::min(dx | 3, dw - 1);
+            if ((int)(uint16_t)xt[last].x + 1 - (int)(uint16_t)xt[dx & ~3].x > 7) pyrWindow = false;
+            if (xt[dx].y < 0 || xt[dx].y > 2048 || xt[dx].z < 0 || xt[dx].z > 2048) pyrWindow = false;
+        }
+        // (the vertical weights are multiplied as unsigned 16-bit halves)
+        const short4* yt = &out.tabs[out.yoff[l]];
+        for (int dy = 0; dy < g.lv[l].h; dy++)
+            if (yt[dy].z < 0 || yt[dy].z > 2048 || yt[dy].w < 0 || yt[dy].w > 2048) pyrWindow = false;
+    }
     const int refine0 = h->maxB <= h->latMaxB ? 1 : 0;
-    for (int refine = refine0; refine < 4 && !out.pyrFused; refine++) {
+    for (int refine = refine0; refine < 4 && pyrWindow && !out.pyrFused; refine++) {
         const int nl = g.nlevels;
         const int top = nl - 1;
         // 4 x 6 blocks per frame (x 2^refine each way): wide tiles -- a level-1 row of 40+ dword groups keeps a wave on one or two
@@ -264,7 +284,7 @@ static int build_geometry(const orbx_handle* h, int w, int h0, HostGeom& out)
         while (BY > 1 && g.lv[top].h / BY < 8) BY >>= 1;
         out.pyrBlocks = BX * BY;
         out.pyrRanges.assign((size_t)out.pyrBlocks * nl, PyrRange{0, 0, 0, 0, 0, 0, 0, 0});
-        int maxA = 4, maxB = 4, tabCap = 4;
+        int maxA = 4, maxB = 4, tabCap = 4, maxRowOff = 0;
         for (int bj = 0; bj < BY; bj++)
             for (int bi = 0; bi < BX; bi++) {
                 PyrRange* R = &out.pyrRanges[(size_t)(bj * BX + bi) * nl];
@@ -301,6 +321,8 @@ static int build_geometry(const orbx_handle* h, int w, int h0, HostGeom& out)
                     if (cx1 > cx0 && cy1 > cy0) {
                         const int rowBytes = (cx1 - cx0 + 3) & ~3;
                         int rows = cy1 - cy0;
+                        // the kernel stages the next level's source rows as 16-bit byte offsets from this range's first row
+                        if (l < top) maxRowOff = std::max(maxRowOff, rowBytes * (rows - 1));
                         if (l == 0 && ny1 > ny0) {
                             // the kernel stages level 0 in kPyrStrips strips: the rows the strip's level-1 rows read
                             // (same split as k_pyramid: rows [chh * s / n, chh * (s + 1) / n) of level 1's computed range)
@@ -312,6 +334,8 @@ static int build_geometry(const orbx_handle* h, int w, int h0, HostGeom& out)
                                 if (yb > ya) rows = std::max(rows, std::min<int>(yt[ny0 + yb - 1].y + 1, cy1) - (int)yt[ny0 + ya].x);
                             }
                         }
+                        // four spare words: the next level's 8-byte window (and its aligned three-dword form) starts at a tap
+                        // inside a row, below byte rowBytes, and so ends at most 11 bytes behind the last row
                         const int words = rowBytes / 4 * rows + 4;
                         if (l & 1) maxB = std::max(maxB, words); else maxA = std::max(maxA, words);
                         if (l > 0) tabCap = std::max(tabCap, std::max(rowBytes, cy1 - cy0));
@@ -321,7 +345,7 @@ static int build_geometry(const orbx_handle* h, int w, int h0, HostGeom& out)
             }
         out.pyrBufA = maxA; out.pyrBufB = maxB; out.pyrTabCap = (tabCap + 3) & ~3;
         const size_t pl = pyr_lds_bytes(maxA, maxB, out.pyrTabCap);
-        out.pyrFused = pl <= 64 * 1024 || (refine == 3 && pl <= 156 * 1024);
+        out.pyrFused = (pl <= 64 * 1024 || (refine == 3 && pl <= 156 * 1024)) && maxRowOff < 65536;
     }
     return ORBX_OK;
 }

@@ -121,6 +121,7 @@ constexpr int kPyrStrips = 2;   // level-0 tile of k_pyramid: strips per block (
 #define ORBX_PYR_THREADS 256
 #endif
 constexpr int kPyrThreads = ORBX_PYR_THREADS;   // threads of a k_pyramid workgroup (host launch and kernel)
+typedef unsigned short pyr_u16x2 __attribute__((ext_vector_type(2)));   // the operands of v_dot2_u32_u16
 struct PyrRange {
     int16_t ox0, ox1, oy0, oy1;   // owned output range at this level (exclusive ends)
     int16_t nx0, nx1, ny0, ny1;   // computed range (owned + halo needed by the next level)
@@ -230,24 +231,30 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(const Geom* __restrict_
         const uint2* __restrict__ gy_tab = (const uint2*)tabs.ytab[l];
         // stage this level's coefficient rows (entries past the level width are never used)
         for (int i = tid; i < cstride; i += T) sxt[i] = gx_tab[min(c.nx0 + i, lw - 1)];
-        for (int i = tid; i < chh; i += T) syt[i] = gy_tab[c.ny0 + i];
+        // ... the y entries with the two source rows as byte offsets into the previous level's tile (build_geometry: below
+        // 65 536), so that the row loop has no multiply; the strips read their row numbers from the table itself
+        for (int i = tid; i < chh; i += T) {
+            const uint2 yt = gy_tab[c.ny0 + i];
+            syt[i] = make_uint2(((yt.x & 0xFFFF) - pny0) * pstride | ((yt.x >> 16) - pny0) * pstride << 16, yt.y);
+        }
+        const uint2* const yrows = gy_tab + c.ny0;
         __syncthreads();  // also orders the previous level's tile writes before the reads below
         const int offP = offBuf[(l - 1) & 1], offC = offBuf[l & 1];
         const bool strips = l == 1 && have0 && chh > 0;
         const int nstrips = strips ? kPyrStrips : 1;
-        if (strips) { int r0, r1; strip_rows(0, chh, syt, r0, r1); fetch0(r0, r1); }
+        if (strips) { int r0, r1; strip_rows(0, chh, yrows, r0, r1); fetch0(r0, r1); }
         for (int strip = 0; strip < nstrips; strip++) {
         // rows [ya, yb) of this level; for level 1 they read the level-0 rows [prow0, ..) of the strip committed just now
         const int ya = strips ? (int)((int64_t)chh * strip / nstrips) : 0, yb = strips ? (int)((int64_t)chh * (strip + 1) / nstrips) : chh;
         int prow0 = pny0;
         if (strips) {
             int r0, r1;
-            strip_rows(strip, chh, syt, r0, r1);
+            strip_rows(strip, chh, yrows, r0, r1);
             prow0 = r0;
             if (strip) __syncthreads();   // the previous strip's rows are read
             commit0(r0, r1);
             __syncthreads();
-            if (strip + 1 < nstrips) { int q0, q1; strip_rows(strip + 1, chh, syt, q0, q1); fetch0(q0, q1); }
+            if (strip + 1 < nstrips) { int q0, q1; strip_rows(strip + 1, chh, yrows, q0, q1); fetch0(q0, q1); }
         }
         if (gpr > 0 && yb > ya) {
             // thread = (dword group gx, row lane): the four x-coefficient entries of the group are unpacked once
@@ -257,34 +264,55 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(const Geom* __restrict_
             const int dr = T / cols;           // row lanes
             const int yy0 = tid / cols, gx = gxb + tid - yy0 * cols;
             if (yy0 < dr) {
-                int sx[4], a0[4], a1[4];
+                // The group's eight taps of a source row lie in the 8 bytes from its first tap on (build_geometry: span <= 7, or
+                // the shape takes the per-level kernel), so a row is ONE window: three aligned dwords from (first tap) & ~3 and
+                // two v_alignbyte_b32 (an unaligned ds_read_b64 is served, but slowly: docs/experiments.md).  Pixel i takes its
+                // two taps out of the window with a byte permute -- the tap into the HIGH byte of the low half, its right
+                // neighbour into the high byte of the high half, zero elsewhere -- and sums them with one unsigned dot2 against
+                // 16 a0 | 16 a1 << 16 (a0, a1 in [0, 2048], ibid.): the dot is r << 12, its high half the r >> 4 of cv::resize.
+                const int sxf = (int)(sxt[4 * gx].x & 0xFFFF);
+                const int wo = sxf - pnx0, wsh = wo & 3;
+                uint32_t sel[4], ac[4];
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
                     const uint2 xt = sxt[4 * gx + i];
-                    sx[i] = (int)(xt.x & 0xFFFF) - pnx0;
-                    a0[i] = (int16_t)(xt.x >> 16);
-                    a1[i] = (int16_t)(xt.y & 0xFFFF);
+                    const uint32_t d = (xt.x & 0xFFFF) - (uint32_t)sxf;
+                    sel[i] = d * 0x01000100u + 0x010c000cu;
+                    ac[i] = ((xt.x >> 16) | (xt.y << 16)) << 4;
                 }
+                // a strip's rows start at prow0: one subtraction, in the base
+                const int rbase = offP - (prow0 - pny0) * pstride + (wo & ~3);
                 const int dx = c.nx0 + 4 * gx;
                 const bool ownX = dx >= c.ox0 && dx < c.ox1;
                 for (int yy = ya + yy0; yy < yb; yy += dr) {
                     const uint2 yt = syt[yy];
-                    const int sy0 = (int16_t)(yt.x & 0xFFFF), sy1 = (int16_t)(yt.x >> 16);
-                    const int b0 = (int16_t)(yt.y & 0xFFFF), b1 = (int16_t)(yt.y >> 16);
-                    const int o0 = offP + (sy0 - prow0) * pstride;
-                    const int o1 = offP + (sy1 - prow0) * pstride;
-                    uint32_t packed = 0;
+                    const uint32_t b0 = yt.y & 0xFFFF, b1 = yt.y >> 16;   // in [0, 2048] (build_geometry)
+                    const uint32_t* const q0 = (const uint32_t*)(ldsb + rbase + (int)(yt.x & 0xFFFF));
+                    const uint32_t* const q1 = (const uint32_t*)(ldsb + rbase + (int)(yt.x >> 16));
+                    const uint32_t u0 = q0[0], u1 = q0[1], u2 = q0[2], t0 = q1[0], t1 = q1[1], t2 = q1[2];
+                    const uint2 w0 = make_uint2(__builtin_amdgcn_alignbyte(u1, u0, wsh), __builtin_amdgcn_alignbyte(u2, u1, wsh));
+                    const uint2 w1 = make_uint2(__builtin_amdgcn_alignbyte(t1, t0, wsh), __builtin_amdgcn_alignbyte(t2, t1, wsh));
+                    // columns past xmax (cv::resize's `D[dx] = S[sx] * ONE` tail) carry a0 = 2048, a1 = 0 in the table, so the
+                    // two-tap form is exact there too (the second tap may read the tile's padding: times zero; the window's
+                    // bytes behind it lie in the buffer's four spare words and are selected by no permute) -- no per-pixel branch
+                    uint32_t s[4];   // s[0], s[2]: ((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16), at most 1021, of a pixel pair
 #pragma unroll
                     for (int i = 0; i < 4; i++) {
-                        // columns past xmax (cv::resize's `D[dx] = S[sx] * ONE` tail) carry a0 = 2048, a1 = 0 in the table,
-                        // so the two-tap form is exact there too (the second tap may read the tile's padding: times zero) --
-                        // no per-pixel branch, all sixteen LDS reads of the row in flight together
-                        const int s00 = ldsb[o0 + sx[i]], s10 = ldsb[o1 + sx[i]];
-                        const int r0 = s00 * a0[i] + ldsb[o0 + sx[i] + 1] * a1[i];
-                        const int r1 = s10 * a0[i] + ldsb[o1 + sx[i] + 1] * a1[i];
-                        const int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
-                        packed |= (uint32_t)(v & 0xFF) << (8 * i);
+                        const pyr_u16x2 a = __builtin_bit_cast(pyr_u16x2, ac[i]);
+                        const uint32_t r0 = __builtin_amdgcn_udot2(__builtin_bit_cast(pyr_u16x2, __builtin_amdgcn_perm(w0.y, w0.x, sel[i])), a, 0u, false);
+                        const uint32_t r1 = __builtin_amdgcn_udot2(__builtin_bit_cast(pyr_u16x2, __builtin_amdgcn_perm(w1.y, w1.x, sel[i])), a, 0u, false);
+                        const uint32_t p0 = __umul24(b0, r0 >> 16), p1 = __umul24(b1, r1 >> 16);
+                        // the odd pixel's sum into the high half of the pair's register, the low half kept; then (s + 2) >> 2 of
+                        // both halves at once: bits 2 .. 9 of s + 2 are the high byte of 64 s + 128.  (One block, so that the wait
+                        // state between a partial write and its reader is the block's own.)
+                        if (i & 1)
+                            asm("v_add_u32_sdwa %0, %1, %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_1\n\t"
+                                "s_nop 0\n\t"
+                                "v_pk_mad_u16 %0, %0, 64, %3 op_sel_hi:[1,0,0]"
+                                : "+v"(s[i - 1]) : "v"(p0), "v"(p1), "s"(128u));
+                        else s[i] = (p0 >> 16) + (p1 >> 16);
                     }
+                    const uint32_t packed = __builtin_amdgcn_perm(s[2], s[0], 0x07050301u);
                     plds[(offC >> 2) + yy * gpr + gx] = packed;
                     const int dy = c.ny0 + yy;
                     if (ownX && dy >= c.oy0 && dy < c.oy1)
