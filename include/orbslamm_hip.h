@@ -989,6 +989,9 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 /* PoseOptimization behind those searches, fed from the pool, the frame set and the search's own table (orbq_track_pose):
  * orbslamm_trackpose.h. */
 #include "orbslamm_trackpose.h"
+/* Tracking::Relocalization behind PnPsolver::iterate, per candidate: three PoseOptimizations and two keyframe projections from the
+ * pool, the store and the frame set (orbq_relocalize): orbslamm_reloc.h. */
+#include "orbslamm_reloc.h"
 /* LoopClosing::ComputeSim3 behind the Sim3Solver, per candidate: SearchBySim3 and OptimizeSim3 from the pool, the store and the
  * frame set (orby_compute_sim3): orbslamm_computesim3.h. */
 #include "orbslamm_computesim3.h"

@@ -150,6 +150,11 @@ EXPORTS_TRACKPOSE = [
     "orbq_track_pose", "orbq_track_reference",
 ]
 
+# the block that closes Relocalization behind PnPsolver::iterate (include/orbslamm_reloc.h, which include/orbslamm_hip.h includes)
+EXPORTS_RELOC = [
+    "orbq_relocalize", "orbq_debug_reloc_arena",
+]
+
 # the block that closes LoopClosing::ComputeSim3 behind the Sim3Solver (include/orbslamm_computesim3.h, which include/orbslamm_hip.h includes)
 EXPORTS_COMPUTESIM3 = [
     "orby_compute_sim3",
@@ -169,7 +174,7 @@ EXPORTS_CORRECT = [
 def build(force=False):
     """hipcc the extension in-tree for gfx950 (cross-compiles without a GPU)."""
     deps = [os.path.join(_PKG, "csrc", f) for f in os.listdir(os.path.join(_PKG, "csrc"))]
-    deps += [os.path.join(_ROOT, "include", f) for f in ("orbslamm_hip.h", "orbslamm_fuse.h", "orbslamm_loopfuse.h", "orbslamm_poseopt.h", "orbslamm_sim3opt.h", "orbslamm_mappool.h", "orbslamm_localmap.h", "orbslamm_covis.h", "orbslamm_trackpose.h", "orbslamm_computesim3.h", "orbslamm_refresh.h", "orbslamm_correct.h")]
+    deps += [os.path.join(_ROOT, "include", f) for f in ("orbslamm_hip.h", "orbslamm_fuse.h", "orbslamm_loopfuse.h", "orbslamm_poseopt.h", "orbslamm_sim3opt.h", "orbslamm_mappool.h", "orbslamm_localmap.h", "orbslamm_covis.h", "orbslamm_trackpose.h", "orbslamm_reloc.h", "orbslamm_computesim3.h", "orbslamm_refresh.h", "orbslamm_correct.h")]
     if not force and os.path.exists(SO_PATH) and all(os.path.getmtime(SO_PATH) >= os.path.getmtime(d) for d in deps):
         return SO_PATH
     cmd = ["hipcc"] + HIPCC_FLAGS + ["-o", SO_PATH, SRC]
@@ -215,7 +220,7 @@ def lib():
         L = C.CDLL(os.environ.get("ORBSLAMM_HIP_LIB") or SO_PATH)
         L.orbx_last_error.restype = C.c_char_p
         L.orbx_scale_factor.restype = C.c_float
-        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP + EXPORTS_LOCALMAP + EXPORTS_FUSE + EXPORTS_LOOPFUSE + EXPORTS_POSEOPT + EXPORTS_SIM3OPT + EXPORTS_MAPPOOL + EXPORTS_LOCALMAP_UPDATE + EXPORTS_COVIS + EXPORTS_TRACKPOSE + EXPORTS_COMPUTESIM3 + EXPORTS_REFRESH + EXPORTS_CORRECT:
+        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP + EXPORTS_LOCALMAP + EXPORTS_FUSE + EXPORTS_LOOPFUSE + EXPORTS_POSEOPT + EXPORTS_SIM3OPT + EXPORTS_MAPPOOL + EXPORTS_LOCALMAP_UPDATE + EXPORTS_COVIS + EXPORTS_TRACKPOSE + EXPORTS_RELOC + EXPORTS_COMPUTESIM3 + EXPORTS_REFRESH + EXPORTS_CORRECT:
             getattr(L, name)
         L.orbx_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
         _lib = L

@@ -1,4 +1,5 @@
-"""ctypes mirror of orbq_track_pose and orbq_track_reference (include/orbslamm_trackpose.h): Optimizer::PoseOptimization as Tracking calls
+"""ctypes mirror of orbq_track_pose, orbq_track_reference (include/orbslamm_trackpose.h) and orbq_relocalize
+(include/orbslamm_reloc.h, §8y): Optimizer::PoseOptimization as Tracking calls
 it right behind a pool search, with the loop that follows it, for any number of frames in one launch.
 
     pool.track_local_map(fs, slot, view, ids, 1.0, sf, breaks); fs.results()          # or store.track_local_map / track_frame_pose
@@ -154,3 +155,95 @@ def track_reference(matcher, pool, store, jobs, inv_level_sigma2, nnratio=0.7, c
     rc, out, ids, flags, match = track_reference_raw(matcher._h, pool._h, store._h, rec, nnratio, check_ori, min_matches, inv_level_sigma2, want_match=want_match)
     check(rc)
     return [dict(_track_fields(out["track"], ids, flags, i), status=int(out["status"][i]), n_bow=int(out["n_bow"][i]), match=match[i]) for i in range(len(jobs))]
+
+
+# ------------------------------------------------------------------ orbq_relocalize
+RELOC_JOB_DTYPE = np.dtype([("fs", "<u8"), ("slot", "<i4"), ("kf_slot", "<i4"), ("kf", "<i4"), ("n", "<i4"), ("ids", "<u8"), ("frame", FRAME_DTYPE)])
+RELOC_RESULT_DTYPE = np.dtype([("opt", RESULT_DTYPE, (3,)), ("Tcw", "<f4", (16,)), ("exit", "<i4"), ("n_good", "<i4", (3,)), ("n_additional", "<i4", (2,))])
+assert RELOC_JOB_DTYPE.itemsize == 112 and RELOC_RESULT_DTYPE.itemsize == 616
+RELOC_REJECTED, RELOC_FIRST, RELOC_WIDE_SHORT, RELOC_SECOND, RELOC_NARROW_SHORT, RELOC_THIRD = range(6)
+RELOC_KEEP = 0xff
+RELOC_ST_NOT_RUN, RELOC_ST_NO_POINT, RELOC_ST_BAD, RELOC_ST_FOUND, RELOC_ST_OUT_OF_IMAGE, RELOC_ST_DISTANCE, RELOC_ST_LEVEL_RANGE, RELOC_ST_IN_VIEW = range(8)
+
+
+def _setup_reloc(L):
+    if getattr(L, "_orbq_reloc_ready", False):
+        return
+    vp = C.c_void_p
+    L.orbq_relocalize.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.orbq_debug_reloc_arena.argtypes = [vp, C.c_int, vp]
+    L._orbq_reloc_ready = True
+
+
+def pack_reloc_jobs(jobs):
+    """(RELOC_JOB_DTYPE array, the id arrays it points into) from job dicts: fs (a FrameSet, or a raw handle value), slot, kf_slot, kf,
+    n, ids (the pool id of vvpMapPointMatches[i][t] where vbInliers[t], else -1; None: a null pointer), Tcw (PnP's pose), K"""
+    rec = np.zeros(len(jobs), dtype=RELOC_JOB_DTYPE)
+    keep = []
+    for i, j in enumerate(jobs):
+        fs = j["fs"]
+        h = getattr(fs, "_h", fs)
+        rec["fs"][i] = (h.value if isinstance(h, C.c_void_p) else h) or 0
+        rec["slot"][i], rec["kf_slot"][i], rec["kf"][i], rec["n"][i] = j["slot"], j["kf_slot"], j["kf"], j["n"]
+        ids = j.get("ids")
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+            assert ids.shape[0] >= j["n"]
+            keep.append(ids)
+            rec["ids"][i] = ids.ctypes.data
+        rec["frame"]["Tcw"][i] = np.asarray(j.get("Tcw", np.eye(4)), dtype=np.float32).reshape(16)
+        rec["frame"]["K"][i] = K4(j.get("K", [1, 1, 0, 0]))
+    return rec, keep
+
+
+def relocalize_raw(handle, pool_handle, store_handle, jobs, check_ori, inv_level_sigma2, scale_factors, level_breaks, stride, nlevels=None,
+                   n_jobs=None, fill=None, want_status=True):
+    """the C entry as it is: jobs a RELOC_JOB_DTYPE array (or None); stride: the store's (it sizes the status arrays).  Returns (rc,
+    results, [ids per job], [outlier per job], [status (2, stride) per job, or None]); no exception on a refusal.  fill: the byte the
+    output arrays hold before the call.  want_status: True, False (a null status_out) or one bool per job (nulls inside it)"""
+    L = lib()
+    _setup_reloc(L)
+    a = _raw_arrays(jobs, inv_level_sigma2, nlevels, n_jobs, fill, RELOC_RESULT_DTYPE)
+    sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, dtype=np.float32)
+    br = None if level_breaks is None else np.ascontiguousarray(level_breaks, dtype=np.float32)
+    per = [bool(want_status)] * len(a.ns) if isinstance(want_status, bool) else [bool(w) for w in want_status]
+    status = [np.full((2, max(int(stride), 1)), 0 if fill is None else fill, np.uint8) if per[i] else None for i in range(len(a.ns))]
+    ps = _table(status) if any(per) or not isinstance(want_status, bool) else None
+    rc = L.orbq_relocalize(handle, pool_handle, store_handle, ptr(jobs), a.n_jobs, int(check_ori), ptr(a.sigma), ptr(sf), ptr(br), a.nlevels,
+                           ptr(a.out), _table(a.ids), _table(a.flags), ps)
+    return rc, a.out[:len(a.ns)], _cut(a.ids, a.ns), _cut(a.flags, a.ns), [None if s is None else s[:, :int(stride)] for s in status]
+
+
+def reloc_n_good(rec):
+    """the nGood that Tracking.cc:1546 reads at the exit of a RELOC_RESULT_DTYPE record (orbq_reloc_n_good)"""
+    e = int(rec["exit"])
+    return int(rec["n_good"][2 if e == RELOC_THIRD else 1 if e in (RELOC_SECOND, RELOC_NARROW_SHORT) else 0])
+
+
+def relocalize(matcher, pool, store, jobs, inv_level_sigma2, scale_factors, level_breaks, check_ori=True, want_status=False):
+    """orbq_relocalize over job dicts (fs, slot, kf_slot, kf, n, ids, Tcw, K): the body of Tracking::Relocalization behind
+    PnPsolver::iterate, per candidate.  One result dict per job: exit (RELOC_*), n_good (3), n_additional (2), opt (the three solves'
+    records), Tcw (what mCurrentFrame.mTcw is left as), ids (mvpMapPoints as pool ids at the exit), outlier (bytes: 0, 1, or RELOC_KEEP
+    where no solve of the job had the feature as an edge), status ((2, stride) bytes or None), n_good_at_exit and ok, the verdict of
+    :1546 for a job on its own"""
+    rec, keep = pack_reloc_jobs(jobs)
+    rc, out, ids, flags, status = relocalize_raw(matcher._h, pool._h, store._h, rec, check_ori, inv_level_sigma2, scale_factors, level_breaks, store.stride,
+                                                 want_status=want_status)
+    check(rc)
+    res = []
+    for i in range(len(jobs)):
+        ng = reloc_n_good(out[i])
+        res.append(dict(exit=int(out["exit"][i]), n_good=out["n_good"][i].copy(), n_additional=out["n_additional"][i].copy(), opt=out["opt"][i].copy(),
+                        Tcw=out["Tcw"][i].reshape(4, 4).copy(), ids=ids[i], outlier=flags[i], status=status[i], n_good_at_exit=ng,
+                        ok=int(out["exit"][i]) != RELOC_REJECTED and ng >= 50))
+    return res
+
+
+def debug_reloc_arena(matcher, entries_per_job=-1):
+    """orbq_debug_reloc_arena, for the overflow tests: sets the starting size of a job's share of the candidate arena (0: the default;
+    -1: leaves it) and returns how many times the last relocalize on the matcher ran its chain"""
+    L = lib()
+    _setup_reloc(L)
+    runs = C.c_int(0)
+    check(L.orbq_debug_reloc_arena(matcher._h, int(entries_per_job), C.byref(runs)))
+    return runs.value
