@@ -3,8 +3,10 @@
 The library is the product: there is no Python/CPU compute path behind it.  If
 the shared object is missing this module raises -- loudly -- instead of falling
 back to anything."""
+import collections
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -60,121 +62,77 @@ class OrbmProjParams(C.Structure):
     _fields_ = [("mode", C.c_int32), ("nnratio", C.c_float), ("check_ori", C.c_int32), ("th_dist", C.c_int32)]
 
 
-# every symbol include/orbslamm_hip.h declares (tests check that all of them resolve)
-EXPORTS = [
-    "orbx_last_error", "orbx_device_count", "orbx_device_pci_bus_id", "orbx_device_shader_clock_mhz", "orbx_create", "orbx_create_live", "orbx_destroy", "orbx_levels", "orbx_scale_factor",
-    "orbx_scale_tables", "orbx_features_per_level", "orbx_umax", "orbx_max_keypoints", "orbx_extract",
-    "orbx_extract_batch", "orbx_submit_batch", "orbx_submit_batch_into", "orbx_collect", "orbx_host_alloc", "orbx_collect_view", "orbx_release", "orbx_collect_batch", "orbx_extract_match_batch",
-    "orbx_host_alloc_frames", "orbx_host_free", "orbx_host_register", "orbx_host_unregister", "orbx_extract_batch_device", "orbx_device_results", "orbx_download",
-    "orbx_pyramid_level", "orbx_compute_stereo_matches", "orbx_level_candidates", "orbx_sync", "orbx_device_alloc", "orbx_device_free", "orbx_upload", "orbx_match_prev_batch_device",
-    "orbx_device_matches", "orbx_download_matches", "orbx_reset_stream", "orbx_set_serial", "orbx_profile_enable",
-    "orbx_profile_read", "orbx_debug_pair_overlap", "orbx_debug_link_rate", "orbx_debug_stage_rows", "orbx_debug_blur_ops", "orbx_profile_select", "orbm_create", "orbm_destroy", "orbm_thread_handle", "orbm_alloc_stats", "orbm_distance_matrix", "orbm_match_bruteforce",
-    "orbm_search_by_bow", "orbm_search_by_projection", "orbm_search_by_projection_stereo", "orbm_projection_prepare", "orbm_features_in_area", "orbm_window_best",
-    "orbm_search_for_initialization", "orbm_search_for_triangulation", "orbm_distinctive_descriptors", "orbm_descriptors_to_text", "orbm_descriptors_from_text", "orbm_undistort_keypoints", "orbm_compute_stereo_from_rgbd", "orbm_frame_create", "orbm_frame_destroy", "orbm_frame_size", "orbm_frame_settle",
-    "orbm_frame_download_keys_un", "orbm_search_by_projection_frame", "orbm_frame_compute_bow", "orbm_search_by_bow_frames", "orbm_search_for_initialization_frames", "orbm_window_best_frame", "orbm_search_for_triangulation_frames",
-    "orbv_create", "orbv_load_text", "orbv_destroy", "orbv_transform", "orbv_score",
-    "orbm_last_search_stats", "orbm_frameset_create", "orbm_frameset_destroy", "orbm_frameset_build", "orbm_frameset_build_from_extractor",
-    "orbm_frameset_sync", "orbm_frameset_attach", "orbm_frameset_download", "orbm_track_frames", "orbm_track_local_points", "orbm_track_frame_projected", "orbm_track_results", "orbm_track_stats",
-    "orbm_frameset_compute_bow", "orbm_frameset_bow_vector", "orbm_bow_frames", "orbm_bow_results",
-]
+# what a prototype of include/orbslamm_*.h may return and take by value; everything with a `*` or a `[`, and a `_fn` typedef, is a pointer
+_RETURNS = {"int": C.c_int, "void": None, "float": C.c_float, "const char*": C.c_char_p}
+_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "int32_t": C.c_int32,
+            "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64}
+Declaration = collections.namedtuple("Declaration", "restype argtypes header")
+_declarations = None
 
-# the keyframe database's block of the header (orbk_*)
-EXPORTS_KFDB = [
-    "orbk_pool_create", "orbk_pool_destroy", "orbk_pool_size", "orbk_pool_set_bow", "orbk_pool_set_bow_from_frameset", "orbk_pool_score",
-    "orbk_pool_set_covisibility", "orbk_pool_read_state", "orbk_db_create", "orbk_db_destroy", "orbk_db_add", "orbk_db_erase", "orbk_db_clear",
-    "orbk_db_size", "orbk_db_empty", "orbk_db_last_scored", "orbk_detect_relocalization_candidates",
-    "orbk_detect_relocalization_candidates_frameset", "orbk_detect_loop_candidates", "orbk_detect_loop_batch",
-]
 
-# the Initializer's block (orbi_*)
-EXPORTS_INIT = [
-    "orbi_create", "orbi_create_frame", "orbi_initialize", "orbi_initialize_frame", "orbi_size", "orbi_normalization", "orbi_destroy",
-]
+def _parse_header(text, header):
+    """{name: Declaration} of the prototypes `ret name(args);` in a header's text.  Comments, preprocessor lines, the extern "C"
+    bracket, typedefs and whatever has a body are not prototypes; a statement that is none of these, or a type outside the two tables,
+    raises -- a signature is never guessed"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#ifdef __cplusplus\n.*?^[ \t]*#endif[^\n]*$", "", text, flags=re.S | re.M)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*$", "", text, flags=re.M)
+    n = 1
+    while n:
+        text, n = re.subn(r"\{[^{}]*\}", "\0", text)          # a body, innermost first
+    out = {}
+    for stmt in re.sub(r"\)\s*\0", ")\0;", text).split(";"):   # a function's body ends its statement
+        stmt = " ".join(stmt.split())
+        if not stmt or stmt.startswith("typedef ") or "\0" in stmt:
+            continue
+        m = re.fullmatch(r"(.+?)\b(\w+) ?\((.*)\)", stmt)
+        if not m:
+            raise RuntimeError("%s: cannot read `%s` as a prototype" % (header, stmt))
+        ret, name, params = re.sub(r" ?\* ?", "*", m.group(1).strip()), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise RuntimeError("%s: %s returns `%s`, which the mirror has no ctypes type for" % (header, name, ret))
+        argtypes = []
+        for prm in ([] if params in ("", "void") else params.split(",")):
+            words = [w for w in prm.split() if w != "const"]
+            kind = " ".join(words[:-1]) if len(words) > 1 else words[0] if words else ""
+            if "*" in prm or "[" in prm or kind.endswith("_fn"):
+                argtypes.append(C.c_void_p)
+            elif kind in _SCALARS:
+                argtypes.append(_SCALARS[kind])
+            else:
+                raise RuntimeError("%s: %s takes `%s`, which the mirror has no ctypes type for" % (header, name, prm.strip()))
+        if name in out:
+            raise RuntimeError("%s declares %s twice" % (header, name))
+        out[name] = Declaration(_RETURNS[ret], argtypes, header)
+    return out
 
-# the Sim3Solver's block (orbs_*)
-EXPORTS_SIM3 = [
-    "orbs_create", "orbs_set_ransac", "orbs_max_iterations", "orbs_size", "orbs_points", "orbs_run", "orbs_hypotheses", "orbs_iterate",
-    "orbs_last_run_ms", "orbs_destroy",
-]
 
-# the PnPsolver's block (orbp_*)
-EXPORTS_PNP = [
-    "orbp_create", "orbp_create_frame", "orbp_set_ransac", "orbp_max_iterations", "orbp_min_inliers", "orbp_size", "orbp_run", "orbp_hypotheses", "orbp_iterate",
-    "orbp_last_run_ms", "orbp_destroy",
-]
-
-# CreateNewMapPoints' block (orbl_*)
-EXPORTS_LOCALMAP = [
-    "orbl_compute_f12", "orbl_create_new_map_points", "orbl_create_new_map_points_frames",
-]
-
-# SearchInNeighbors' block (include/orbslamm_fuse.h, which include/orbslamm_hip.h includes)
-EXPORTS_FUSE = [
-    "orbl_level_breaks", "orbl_fuse_batch", "orbl_fuse_batch_frames",
-]
-
-# SearchAndFuse's block (include/orbslamm_loopfuse.h, which include/orbslamm_hip.h includes)
-EXPORTS_LOOPFUSE = [
-    "orbc_search_and_fuse", "orbc_search_and_fuse_frames",
-]
-
-# PoseOptimization's block (include/orbslamm_poseopt.h, which include/orbslamm_hip.h includes)
-EXPORTS_POSEOPT = [
-    "orbo_pose_optimize", "orbo_pose_optimize_frames",
-]
-
-# OptimizeSim3's block (include/orbslamm_sim3opt.h, which include/orbslamm_hip.h includes)
-EXPORTS_SIM3OPT = [
-    "orbz_optimize_sim3",
-]
-
-# the map-point pool's block (include/orbslamm_mappool.h, which include/orbslamm_hip.h includes)
-EXPORTS_MAPPOOL = [
-    "orbw_pool_create", "orbw_pool_destroy", "orbw_pool_set", "orbw_pool_set_flags", "orbw_view_project", "orbw_view_project_frame",
-    "orbw_track_local_map", "orbw_track_frame_pose", "orbw_track_status",
-]
-
-# UpdateLocalMap's block (include/orbslamm_localmap.h, which include/orbslamm_hip.h includes)
-EXPORTS_LOCALMAP_UPDATE = [
-    "orbu_store_create", "orbu_store_destroy", "orbu_kf_set", "orbu_kf_set_graph", "orbu_kf_set_flags", "orbu_kf_set_entries",
-    "orbu_update_local_map", "orbu_local_points", "orbu_debug_set_generation", "orbu_debug_resident_list", "orbw_track_local_map_resident",
-]
-
-# the covisibility block over the keyframe store (include/orbslamm_covis.h, which include/orbslamm_hip.h includes)
-EXPORTS_COVIS = [
-    "orbu_kf_set_octaves", "orbn_update_connections", "orbn_culling_counts",
-]
-
-# the block that closes TrackLocalMap / TrackWithMotionModel (include/orbslamm_trackpose.h, which include/orbslamm_hip.h includes)
-EXPORTS_TRACKPOSE = [
-    "orbq_track_pose", "orbq_track_reference",
-]
-
-# the block that closes Relocalization behind PnPsolver::iterate (include/orbslamm_reloc.h, which include/orbslamm_hip.h includes)
-EXPORTS_RELOC = [
-    "orbq_relocalize", "orbq_debug_reloc_arena",
-]
-
-# the block that closes LoopClosing::ComputeSim3 behind the Sim3Solver (include/orbslamm_computesim3.h, which include/orbslamm_hip.h includes)
-EXPORTS_COMPUTESIM3 = [
-    "orby_compute_sim3",
-]
-
-# the map-point refresh's block (include/orbslamm_refresh.h, which include/orbslamm_hip.h includes)
-EXPORTS_REFRESH = [
-    "orbu_kf_set_descriptors", "orbu_kf_set_descriptors_frame", "orbu_kf_set_centres", "orbw_debug_pool_get", "orbr_refresh_points",
-]
-
-# the loop correction's block (include/orbslamm_correct.h, which include/orbslamm_hip.h includes)
-EXPORTS_CORRECT = [
-    "orbu_point_set_ref_kf", "orbe_correct_sim3",
-]
+def declarations():
+    """{name: Declaration(restype, argtypes, header)} of every C entry include/orbslamm_*.h declares: the one statement of the ABI that a
+    compiler checks, read once per process.  lib() installs it on the library; the tests take their lists of names from it"""
+    global _declarations
+    if _declarations is None:
+        inc = os.path.join(_ROOT, "include")
+        headers = sorted(f for f in os.listdir(inc) if re.fullmatch(r"orbslamm_\w+\.h", f)) if os.path.isdir(inc) else []
+        if not headers:
+            raise RuntimeError("%s holds no orbslamm_*.h: the signatures of liborbslamm_hip.so are read from these headers" % inc)
+        decl = {}
+        for f in headers:
+            with open(os.path.join(inc, f)) as fh:
+                one = _parse_header(fh.read(), f)
+            twice = sorted(set(one) & set(decl))
+            if twice:
+                raise RuntimeError("%s declares %s again (%s has it)" % (f, twice[0], decl[twice[0]].header))
+            if not one:     # e.g. an extern "C" bracket in a form this reader does not set aside swallows the whole header as a body
+                raise RuntimeError("%s: no prototype read" % f)
+            decl.update(one)
+        _declarations = decl
+    return _declarations
 
 
 def build(force=False):
     """hipcc the extension in-tree for gfx950 (cross-compiles without a GPU)."""
-    deps = [os.path.join(_PKG, "csrc", f) for f in os.listdir(os.path.join(_PKG, "csrc"))]
-    deps += [os.path.join(_ROOT, "include", f) for f in ("orbslamm_hip.h", "orbslamm_fuse.h", "orbslamm_loopfuse.h", "orbslamm_poseopt.h", "orbslamm_sim3opt.h", "orbslamm_mappool.h", "orbslamm_localmap.h", "orbslamm_covis.h", "orbslamm_trackpose.h", "orbslamm_reloc.h", "orbslamm_computesim3.h", "orbslamm_refresh.h", "orbslamm_correct.h")]
+    deps = [os.path.join(d, f) for d in (os.path.join(_PKG, "csrc"), os.path.join(_ROOT, "include")) for f in os.listdir(d)]
     if not force and os.path.exists(SO_PATH) and all(os.path.getmtime(SO_PATH) >= os.path.getmtime(d) for d in deps):
         return SO_PATH
     cmd = ["hipcc"] + HIPCC_FLAGS + ["-o", SO_PATH, SRC]
@@ -218,11 +176,9 @@ def lib():
         _preload_hip_runtime()
         # ORBSLAMM_HIP_LIB: load another build of the same library (A/B timing of kernel variants, tools/ab_bench.sh)
         L = C.CDLL(os.environ.get("ORBSLAMM_HIP_LIB") or SO_PATH)
-        L.orbx_last_error.restype = C.c_char_p
-        L.orbx_scale_factor.restype = C.c_float
-        for name in EXPORTS + EXPORTS_KFDB + EXPORTS_INIT + EXPORTS_SIM3 + EXPORTS_PNP + EXPORTS_LOCALMAP + EXPORTS_FUSE + EXPORTS_LOOPFUSE + EXPORTS_POSEOPT + EXPORTS_SIM3OPT + EXPORTS_MAPPOOL + EXPORTS_LOCALMAP_UPDATE + EXPORTS_COVIS + EXPORTS_TRACKPOSE + EXPORTS_RELOC + EXPORTS_COMPUTESIM3 + EXPORTS_REFRESH + EXPORTS_CORRECT:
-            getattr(L, name)
-        L.orbx_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
+        for name, d in declarations().items():
+            fn = getattr(L, name)     # every declared entry resolves, or this raises
+            fn.restype, fn.argtypes = d.restype, d.argtypes
         _lib = L
     return _lib
 
@@ -240,6 +196,17 @@ def check(rc):
 
 def ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def table(arrays):
+    """the pointer table of per-job arrays (None: a null inside it)"""
+    return (C.c_void_p * max(len(arrays), 1))(*[None if a is None else a.ctypes.data for a in arrays])
+
+
+def handle_value(fs):
+    """a frame set's handle as the integer a job record holds: of a FrameSet, a c_void_p or a raw value (None: 0)"""
+    h = getattr(fs, "_h", fs)
+    return (h.value if isinstance(h, C.c_void_p) else h) or 0
 
 
 def K4(K):

@@ -14,11 +14,9 @@ defaults to sim3_from_rts(R12, t12, s12), th to 7.5, th2 to 10.  Each result is 
 (OptimizeSim3's), S12 (the input's when written is False: the early return of Optimizer.cc:1514), written, match (the pKF2 feature of
 vpMatches12[i] as OptimizeSim3 leaves it, or -1), ids (its pool id, or -1), removed (per correspondence), n_corr, n_bad, iterations,
 trials, lambda_, chi2.  The verdict n_in >= 20 is the caller's."""
-import ctypes as C
-
 import numpy as np
 
-from ._lib import K4, check, lib, ptr
+from ._lib import K4, check, handle_value, lib, ptr, table
 from .optimizer import SIM3_PROBLEM_DTYPE, SIM3_RESULT_DTYPE, sim3_from_rts
 
 JOB_DTYPE = np.dtype([("fs", "<u8"), ("slot1", "<i4"), ("slot2", "<i4"), ("kf1", "<i4"), ("kf2", "<i4"), ("n1", "<i4"), ("n2", "<i4"),
@@ -29,22 +27,12 @@ assert JOB_DTYPE.itemsize == 336 and RESULT_DTYPE.itemsize == 136
 (ST_NO_POINT, ST_MARKED, ST_BAD, ST_DEPTH, ST_OUTSIDE_IMAGE, ST_DISTANCE, ST_LEVEL_RANGE, ST_NO_CANDIDATE, ST_FOUND) = range(9)
 
 
-def _setup(L):
-    if getattr(L, "_orby_ready", False):
-        return
-    vp = C.c_void_p
-    L.orby_compute_sim3.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
-    L._orby_ready = True
-
-
 def pack_jobs(jobs):
     """(JOB_DTYPE array, the arrays it points into) from job dicts"""
     rec = np.zeros(len(jobs), dtype=JOB_DTYPE)
     keep = []
     for i, j in enumerate(jobs):
-        fs = j["fs"]
-        h = getattr(fs, "_h", fs)
-        rec["fs"][i] = (h.value if isinstance(h, C.c_void_p) else h) or 0
+        rec["fs"][i] = handle_value(j["fs"])
         for k in ("slot1", "slot2", "kf1", "kf2", "n1", "n2"):
             rec[k][i] = j[k]
         R12, t12, s12 = np.asarray(j["R12"], np.float32).reshape(9), np.asarray(j["t12"], np.float32).reshape(3), np.float32(j["s12"])
@@ -71,17 +59,12 @@ def pack_jobs(jobs):
     return rec, keep
 
 
-def _table(arrays):
-    return (C.c_void_p * max(len(arrays), 1))(*[None if a is None else a.ctypes.data for a in arrays])
-
-
 def compute_sim3_raw(handle, pool_handle, store_handle, jobs, sf1, sf2, breaks1, breaks2, sigma1, sigma2, nlevels=None, n_jobs=None, fill=None,
                      debug=True):
     """the C entry as it is: jobs a JOB_DTYPE array (or None).  Returns (rc, results, [match per job], [ids per job], [removed per job],
     [status per job or None], [vnMatch1 | vnMatch2 per job or None]); no exception on a refusal.  fill: the value the output arrays hold
     before the call (to see that a refusal leaves them alone); debug: ask for the status bytes and the vnMatch tables"""
     L = lib()
-    _setup(L)
     real = 0 if jobs is None else jobs.shape[0]
     f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)   # noqa: E731
     sf1, sf2, breaks1, breaks2, sigma1, sigma2 = (f(a) for a in (sf1, sf2, breaks1, breaks2, sigma1, sigma2))
@@ -93,8 +76,8 @@ def compute_sim3_raw(handle, pool_handle, store_handle, jobs, sf1, sf2, breaks1,
     match, ids, removed = mk(n1, np.int32, -2), mk(n1, np.int32, -2), mk(n1, np.uint8, 0)
     status, vn = (mk(n12, np.uint8, 0), mk(n12, np.int32, -2)) if debug else (None, None)
     rc = L.orby_compute_sim3(handle, pool_handle, store_handle, ptr(jobs), real if n_jobs is None else int(n_jobs), ptr(sf1), ptr(sf2), ptr(breaks1),
-                             ptr(breaks2), ptr(sigma1), ptr(sigma2), nl, ptr(out), _table(match), _table(ids), _table(removed),
-                             _table(status) if debug else None, _table(vn) if debug else None)
+                             ptr(breaks2), ptr(sigma1), ptr(sigma2), nl, ptr(out), table(match), table(ids), table(removed),
+                             table(status) if debug else None, table(vn) if debug else None)
     cut = lambda arrays, ns: None if arrays is None else [a[:n] for a, n in zip(arrays, ns)]   # noqa: E731
     return rc, out[:real], cut(match, n1), cut(ids, n1), cut(removed, n1), cut(status, n12), cut(vn, n12)
 

@@ -53,21 +53,6 @@ def make_sets(n, iterations, seed=0):
     return sets
 
 
-def _setup(L):
-    if getattr(L, "_orbi_ready", False):
-        return
-    vp = C.c_void_p
-    L.orbi_create.argtypes = [vp, vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, C.POINTER(vp)]
-    L.orbi_create_frame.argtypes = [vp, vp, vp, C.c_float, C.c_int, C.c_int, C.POINTER(vp)]
-    L.orbi_initialize.argtypes = [vp, vp, C.c_int, vp, vp, C.POINTER(OrbiResult), vp, vp]
-    L.orbi_initialize_frame.argtypes = [vp, vp, vp, vp, C.POINTER(OrbiResult), vp, vp]
-    L.orbi_size.argtypes = [vp, C.POINTER(C.c_int)]
-    L.orbi_normalization.argtypes = [vp, vp]
-    L.orbi_destroy.argtypes = [vp]
-    L.orbi_destroy.restype = None
-    L._orbi_ready = True
-
-
 class Initializer(Handle):
     """Initializer(ReferenceFrame, sigma, iterations) on a matcher's device and stream; the reference frame is mvKeysUn
     (KP_DTYPE records) or a device-resident frame (ORBmatcher.frame_from_device)."""
@@ -75,7 +60,6 @@ class Initializer(Handle):
 
     def __init__(self, matcher, ref, K, sigma=1.0, iterations=200, model="HF"):
         self._L = lib()
-        _setup(self._L)
         self.matcher = matcher   # (keeps the handle alive)
         self.iterations = int(iterations)
         self.model = {"HF": ORBI_MODEL_HF, "F": ORBI_MODEL_F}[model]

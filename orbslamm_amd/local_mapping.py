@@ -44,25 +44,9 @@ def keyframe(Rcw, tcw, Ow, K, median_depth=0.0):
     return kf
 
 
-def _setup(L):
-    if getattr(L, "_orbl_ready", False):
-        return
-    vp = C.c_void_p
-    L.orbl_compute_f12.argtypes = [vp, vp, vp, vp]
-    L.orbl_create_new_map_points.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_float,
-                                             C.c_int, vp, C.c_int, C.POINTER(C.c_int), vp, vp]
-    L.orbl_create_new_map_points_frames.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, C.c_int, vp, C.c_int,
-                                                    C.POINTER(C.c_int), vp, vp]
-    L.orbl_level_breaks.argtypes = [C.c_float, C.c_int, vp, vp]
-    L.orbl_fuse_batch.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, vp, vp]
-    L.orbl_fuse_batch_frames.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, vp, vp]
-    L._orbl_ready = True
-
-
 def compute_f12(kf1, kf2):
     """ComputeF12(pKF1, pKF2) and SearchForTriangulation's epipole in cv::Mat arithmetic (host; needs no GPU): F12 (3x3), (ex, ey)"""
     L = lib()
-    _setup(L)
     a, b = np.ascontiguousarray(kf1, dtype=KF_DTYPE), np.ascontiguousarray(kf2, dtype=KF_DTYPE)
     F, e = np.zeros((3, 3), np.float32), np.zeros(2, np.float32)
     check(L.orbl_compute_f12(ptr(a), ptr(b), ptr(F), ptr(e)))
@@ -90,7 +74,6 @@ def create_new_map_points(matcher, cur, neighbours, scale_factors, level_sigma2,
     (n_neighbours, 11) F12 and epipole each processed neighbour's search used (None unless want_f12).  Raises OrbError
     (ORBX_E_CAPACITY, e.needed = the count) when capacity is given and too small."""
     L = lib()
-    _setup(L)
     K = len(neighbours)
     sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
     sg = np.ascontiguousarray(level_sigma2, dtype=np.float32).reshape(-1)
@@ -162,7 +145,6 @@ def level_breaks(log_scale_factor, nlevels, predict=None):
     """orbl_level_breaks (host; needs no GPU): nlevels + 1 floats, entry L + 1 the largest ratio whose PredictScale level is
     <= L.  predict: the tree's own PredictScale as a Python callable (ratio, log_scale_factor) -> int; None: the float form"""
     L = lib()
-    _setup(L)
     out = np.zeros(int(nlevels) + 1, np.float32)
     fn = PREDICT_FN(predict) if predict is not None else None
     check(L.orbl_level_breaks(C.c_float(log_scale_factor), int(nlevels), fn, ptr(out)))
@@ -245,7 +227,6 @@ def fuse_batch(matcher, targets, points, jobs, scale_factors, inv_level_sigma2, 
     arrays or all with frames; points: a FUSE_POINT_DTYPE pool; jobs: (job_start, job_point), CSR over the targets.  Returns
     a FUSE_RESULT_DTYPE array, one record per job entry in job order.  The caller applies bestDist <= TH_LOW and edits the map."""
     L = lib()
-    _setup(L)
     T = len(targets)
     pts = np.ascontiguousarray(points, dtype=FUSE_POINT_DTYPE)
     js = np.ascontiguousarray(jobs[0], dtype=np.int32).reshape(-1)

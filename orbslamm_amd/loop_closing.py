@@ -23,16 +23,6 @@ HIT_DTYPE = np.dtype([("target", "<i4"), ("point", "<i4"), ("best_idx", "<i4"), 
 assert HIT_DTYPE.itemsize == 16
 
 
-def _setup(L):
-    if getattr(L, "_orbc_ready", False):
-        return
-    vp = C.c_void_p
-    tail = [vp, C.c_int, C.c_float, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int), vp, vp]
-    L.orbc_search_and_fuse.argtypes = [vp, vp, vp, vp, vp, C.c_int] + tail
-    L.orbc_search_and_fuse_frames.argtypes = [vp, vp, vp, C.c_int] + tail
-    L._orbc_ready = True
-
-
 def decompose_sim3(Scw):
     """ORBmatcher.cc:987-992 in OpenCV's forms: (Rcw, tcw, Ow) as float32 from a 4x4 (or 3x4) float32 Scw"""
     S = np.asarray(Scw, dtype=np.float32)
@@ -54,7 +44,6 @@ def search_and_fuse(matcher, targets, points, scale_factors, breaks, th=4.0, max
     repeated once with the needed count when the first guess was short.  A capacity given and too small raises OrbError
     (ORBX_E_CAPACITY, e.needed = the count)."""
     L = lib()
-    _setup(L)
     T = len(targets)
     pts = np.ascontiguousarray(points, dtype=FUSE_POINT_DTYPE)
     P = pts.shape[0]

@@ -25,23 +25,6 @@ VIEW_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3), (
 assert POINT_DTYPE.itemsize == 68 and VIEW_DTYPE.itemsize == 96
 
 
-def _setup(L):
-    if getattr(L, "_orbw_ready", False):
-        return
-    vp = C.c_void_p
-    L.orbw_pool_create.argtypes = [vp, C.c_int, vp]
-    L.orbw_pool_destroy.argtypes = [vp]
-    L.orbw_pool_set.argtypes = [vp, vp, vp, C.c_int]
-    L.orbw_pool_set_flags.argtypes = [vp, vp, vp, C.c_int]
-    L.orbw_view_project.argtypes = [vp, vp, vp, vp, C.c_int, C.c_float, vp, vp, C.c_int, vp, vp, vp, vp]
-    L.orbw_view_project_frame.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]
-    L.orbw_track_local_map.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp, C.c_int, vp]
-    L.orbw_track_frame_pose.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, vp, vp]
-    L.orbw_track_status.argtypes = [vp, C.c_int, vp, vp]
-    L.orbw_debug_pool_get.argtypes = [vp, vp, C.c_int, vp]
-    L._orbw_ready = True
-
-
 def map_points(pos, normal, min_distance, max_distance, desc, flags):
     """n OrbwPoint records: GetWorldPos, GetNormal, the RAW mfMinDistance / mfMaxDistance, GetDescriptor, flags (FLAG_BAD |
     FLAG_OBSERVED)"""
@@ -94,7 +77,6 @@ class MapPool(Handle):
 
     def __init__(self, matcher, capacity):
         self._L = lib()
-        _setup(self._L)
         self._m = matcher
         self.capacity = int(capacity)
         self._h = C.c_void_p()
@@ -250,33 +232,6 @@ class Culling:
         self.redundant = _copy(r.redundant, r.K, C.c_uint8, np.uint8)
 
 
-def _setup_store(L):
-    if getattr(L, "_orbu_ready", False):
-        return
-    vp = C.c_void_p
-    L.orbu_kf_set_octaves.argtypes = [vp, C.c_int, vp, C.c_int]
-    L.orbn_update_connections.argtypes = [vp, vp, C.c_int, C.c_int, vp]
-    L.orbn_culling_counts.argtypes = [vp, vp, C.c_int, C.c_int, vp]
-    L.orbu_kf_set_descriptors.argtypes = [vp, C.c_int, vp, C.c_int]
-    L.orbu_kf_set_descriptors_frame.argtypes = [vp, C.c_int, vp, C.c_int]
-    L.orbu_kf_set_centres.argtypes = [vp, vp, vp, C.c_int]
-    L.orbr_refresh_points.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]
-    L.orbu_point_set_ref_kf.argtypes = [vp, vp, vp, C.c_int]
-    L.orbe_correct_sim3.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
-    L.orbu_store_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    L.orbu_store_destroy.argtypes = [vp]
-    L.orbu_kf_set.argtypes = [vp, vp]
-    L.orbu_kf_set_graph.argtypes = [vp, vp]
-    L.orbu_kf_set_flags.argtypes = [vp, vp, vp, C.c_int]
-    L.orbu_kf_set_entries.argtypes = [vp, C.c_int, vp, vp, C.c_int]
-    L.orbu_update_local_map.argtypes = [vp, vp, C.c_int, C.c_int, vp]
-    L.orbu_local_points.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
-    L.orbu_debug_set_generation.argtypes = [vp, C.c_uint32]
-    L.orbu_debug_resident_list.argtypes = [vp, vp, C.c_int, vp]
-    L.orbw_track_local_map_resident.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_float, vp, vp, C.c_int, vp]
-    L._orbu_ready = True
-
-
 def _concat(lists):
     lists = [_ids(a) for a in lists]
     n = np.array([a.shape[0] for a in lists], np.int32)
@@ -315,7 +270,6 @@ class KeyFrameStore(Handle):
 
     def __init__(self, pool, kf_capacity, stride, max_children, max_local_points):
         self._L = lib()
-        _setup_store(self._L)
         self._pool = pool
         self.kf_capacity, self.stride, self.max_children, self.max_local_points = int(kf_capacity), int(stride), int(max_children), int(max_local_points)
         self._h = C.c_void_p()

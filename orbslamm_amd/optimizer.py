@@ -49,16 +49,6 @@ SIM3_RESULT_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8
 assert SIM3_PROBLEM_DTYPE.itemsize == 200 and SIM3_CORR_DTYPE.itemsize == 52 and SIM3_RESULT_DTYPE.itemsize == 128
 
 
-def _setup(L):
-    if getattr(L, "_orbo_ready", False):
-        return
-    vp = C.c_void_p
-    tail = [C.c_int, vp, vp, vp, C.c_int, vp, vp]
-    L.orbo_pose_optimize.argtypes = [vp, vp, vp, vp] + tail
-    L.orbo_pose_optimize_frames.argtypes = [vp, vp, vp] + tail
-    L._orbo_ready = True
-
-
 def pack_edges(feature, Xw):
     """the edges of one frame as an EDGE_DTYPE array"""
     feature = np.asarray(feature, dtype=np.int32).reshape(-1)
@@ -72,7 +62,6 @@ def pose_optimize_raw(handle, frames, keys, resident, edge_start, edges, inv_lev
     """the C entries as they are: frames a FRAME_DTYPE array, keys a list of KP_DTYPE arrays or resident a list of opaque
     frames, edge_start (n_frames + 1) and edges (EDGE_DTYPE).  Returns (rc, results, outlier); no exception on a refusal."""
     L = lib()
-    _setup(L)
     frames = None if frames is None else np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
     nf = 0 if frames is None else frames.shape[0]
     es = None if edge_start is None else np.ascontiguousarray(edge_start, dtype=np.int32)
@@ -186,10 +175,6 @@ def optimize_sim3_raw(handle, problems, corr_start, corrs, inv_level_sigma2_1, i
     """the C entry as it is: problems a SIM3_PROBLEM_DTYPE array, corr_start (n_problems + 1), corrs (SIM3_CORR_DTYPE), the two
     keyframes' level tables.  Returns (rc, results, removed); no exception on a refusal."""
     L = lib()
-    if not getattr(L, "_orbz_ready", False):
-        vp = C.c_void_p
-        L.orbz_optimize_sim3.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]
-        L._orbz_ready = True
     problems = None if problems is None else np.ascontiguousarray(problems, dtype=SIM3_PROBLEM_DTYPE)
     npb = 0 if problems is None else problems.shape[0]
     cs = None if corr_start is None else np.ascontiguousarray(corr_start, dtype=np.int32)

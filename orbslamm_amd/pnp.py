@@ -50,25 +50,6 @@ def make_pnp_sets(n, iterations, seed=0):
     return draw_sets(n, 4, iterations, seed)
 
 
-def _setup(L):
-    if getattr(L, "_orbp_ready", False):
-        return
-    vp = C.c_void_p
-    L.orbp_create.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.POINTER(vp)]
-    L.orbp_create_frame.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.POINTER(vp)]
-    L.orbp_set_ransac.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
-    L.orbp_max_iterations.argtypes = [vp, C.POINTER(C.c_int)]
-    L.orbp_min_inliers.argtypes = [vp, C.POINTER(C.c_int)]
-    L.orbp_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.orbp_run.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), vp]
-    L.orbp_hypotheses.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
-    L.orbp_iterate.argtypes = [vp, C.c_int, C.POINTER(OrbpResult), vp]
-    L.orbp_last_run_ms.argtypes = [vp, vp]
-    L.orbp_destroy.argtypes = [vp]
-    L.orbp_destroy.restype = None
-    L._orbp_ready = True
-
-
 class PnPsolver(RansacHandle):
     """PnPsolver(F, vpMapPointMatches) after its pointer chasing, on a matcher's device and stream: the n usable
     correspondences with idx their positions in vpMapPointMatches (n_all long)."""
@@ -78,7 +59,6 @@ class PnPsolver(RansacHandle):
         """frame (an opaque device-resident frame of this matcher's device) with level_sigma2: P2D and sigma2 are gathered
         from the frame's undistorted keys on the device (orbp_create_frame); n_all, P2D and sigma2 are then ignored"""
         self._L = lib()
-        _setup(self._L)
         self.matcher = matcher   # (keeps the handle alive)
         idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
         n = idx.shape[0]

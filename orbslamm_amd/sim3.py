@@ -46,24 +46,6 @@ def make_sim3_sets(n, iterations, seed=0):
     return draw_sets(n, 3, iterations, seed)
 
 
-def _setup(L):
-    if getattr(L, "_orbs_ready", False):
-        return
-    vp = C.c_void_p
-    L.orbs_create.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]
-    L.orbs_set_ransac.argtypes = [vp, C.c_double, C.c_int, C.c_int]
-    L.orbs_max_iterations.argtypes = [vp, C.POINTER(C.c_int)]
-    L.orbs_size.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.orbs_points.argtypes = [vp, vp]
-    L.orbs_run.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp)]
-    L.orbs_hypotheses.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
-    L.orbs_iterate.argtypes = [vp, C.c_int, C.POINTER(OrbsResult), vp]
-    L.orbs_last_run_ms.argtypes = [vp, vp]
-    L.orbs_destroy.argtypes = [vp]
-    L.orbs_destroy.restype = None
-    L._orbs_ready = True
-
-
 class Sim3Solver(RansacHandle):
     """Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale) after its pointer chasing, on a matcher's device and stream: the n
     usable correspondences with idx1 their positions in vpMatched12 (n1 long)."""
@@ -71,7 +53,6 @@ class Sim3Solver(RansacHandle):
 
     def __init__(self, matcher, n1, idx1, X1w, X2w, Rcw1, tcw1, Rcw2, tcw2, K1, K2, sigma2_1, sigma2_2, fix_scale=True):
         self._L = lib()
-        _setup(self._L)
         self.matcher = matcher   # (keeps the handle alive)
         idx1 = np.ascontiguousarray(idx1, dtype=np.int32).reshape(-1)
         n = idx1.shape[0]

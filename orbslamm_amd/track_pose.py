@@ -14,20 +14,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import K4, check, lib, ptr
+from ._lib import K4, check, handle_value, lib, ptr, table
 from .optimizer import FRAME_DTYPE, RESULT_DTYPE
 
 JOB_DTYPE = np.dtype([("fs", "<u8"), ("slot", "<i4"), ("back", "<i4"), ("base_ids", "<u8"), ("n", "<i4"), ("discard", "<i4"), ("frame", FRAME_DTYPE)])
 TRACK_RESULT_DTYPE = np.dtype([("opt", RESULT_DTYPE), ("n_matches", "<i4"), ("n_matches_map", "<i4")])
 assert JOB_DTYPE.itemsize == 112 and TRACK_RESULT_DTYPE.itemsize == 184
-
-
-def _setup(L):
-    if getattr(L, "_orbq_ready", False):
-        return
-    vp = C.c_void_p
-    L.orbq_track_pose.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
-    L._orbq_ready = True
 
 
 def pack_jobs(jobs):
@@ -36,9 +28,7 @@ def pack_jobs(jobs):
     rec = np.zeros(len(jobs), dtype=JOB_DTYPE)
     keep = []
     for i, j in enumerate(jobs):
-        fs = j["fs"]
-        h = getattr(fs, "_h", fs)
-        rec["fs"][i] = (h.value if isinstance(h, C.c_void_p) else h) or 0
+        rec["fs"][i] = handle_value(j["fs"])
         rec["slot"][i], rec["back"][i], rec["n"][i], rec["discard"][i] = j["slot"], j.get("back", 0), j["n"], j.get("discard", 0)
         base = j.get("base_ids")
         if base is not None:
@@ -49,11 +39,6 @@ def pack_jobs(jobs):
         rec["frame"]["Tcw"][i] = np.asarray(j["Tcw"], dtype=np.float32).reshape(16)
         rec["frame"]["K"][i] = K4(j["K"])
     return rec, keep
-
-
-def _table(arrays):
-    """the pointer table of per-job arrays (None: a null inside it)"""
-    return (C.c_void_p * max(len(arrays), 1))(*[None if a is None else a.ctypes.data for a in arrays])
 
 
 def _cut(arrays, ns):
@@ -88,9 +73,8 @@ def track_pose_raw(handle, pool_handle, jobs, inv_level_sigma2, nlevels=None, n_
     """the C entry as it is: jobs a JOB_DTYPE array (or None).  Returns (rc, results, [ids per job], [outlier per job]); no exception
     on a refusal.  fill: the byte the output arrays hold before the call (to see that a refusal leaves them alone)"""
     L = lib()
-    _setup(L)
     a = _raw_arrays(jobs, inv_level_sigma2, nlevels, n_jobs, fill, TRACK_RESULT_DTYPE)
-    rc = L.orbq_track_pose(handle, pool_handle, ptr(jobs), a.n_jobs, ptr(a.sigma), a.nlevels, ptr(a.out), _table(a.ids), _table(a.flags))
+    rc = L.orbq_track_pose(handle, pool_handle, ptr(jobs), a.n_jobs, ptr(a.sigma), a.nlevels, ptr(a.out), table(a.ids), table(a.flags))
     return rc, a.out[:len(a.ns)], _cut(a.ids, a.ns), _cut(a.flags, a.ns)
 
 
@@ -109,21 +93,11 @@ assert REF_JOB_DTYPE.itemsize == 112 and REF_RESULT_DTYPE.itemsize == 192
 REF_TRACKED, REF_TOO_FEW, REF_SEARCH_ONLY = 0, 1, 2
 
 
-def _setup_ref(L):
-    if getattr(L, "_orbq_ref_ready", False):
-        return
-    vp = C.c_void_p
-    L.orbq_track_reference.argtypes = [vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
-    L._orbq_ref_ready = True
-
-
 def pack_ref_jobs(jobs):
     """REF_JOB_DTYPE array from job dicts: fs (a FrameSet, or a raw handle value), kf_slot, slot, kf, n, solve (default 1), Tcw, K"""
     rec = np.zeros(len(jobs), dtype=REF_JOB_DTYPE)
     for i, j in enumerate(jobs):
-        fs = j["fs"]
-        h = getattr(fs, "_h", fs)
-        rec["fs"][i] = (h.value if isinstance(h, C.c_void_p) else h) or 0
+        rec["fs"][i] = handle_value(j["fs"])
         rec["kf_slot"][i], rec["slot"][i], rec["kf"][i], rec["n"][i], rec["solve"][i] = j["kf_slot"], j["slot"], j["kf"], j["n"], j.get("solve", 1)
         rec["frame"]["Tcw"][i] = np.asarray(j.get("Tcw", np.eye(4)), dtype=np.float32).reshape(16)
         rec["frame"]["K"][i] = K4(j.get("K", [1, 1, 0, 0]))
@@ -136,13 +110,12 @@ def track_reference_raw(handle, pool_handle, store_handle, jobs, nnratio, check_
     per job, or None]); no exception on a refusal.  fill: the byte the output arrays hold before the call.  want_match: True, False (a
     null match_out) or one bool per job (nulls inside it)"""
     L = lib()
-    _setup_ref(L)
     a = _raw_arrays(jobs, inv_level_sigma2, nlevels, n_jobs, fill, REF_RESULT_DTYPE)
     per = [bool(want_match)] * len(a.ns) if isinstance(want_match, bool) else [bool(w) for w in want_match]
     match = [np.full(max(n, 1), -2 if fill is None else fill, np.int32) if per[i] else None for i, n in enumerate(a.ns)]
-    pm = _table(match) if any(per) or not isinstance(want_match, bool) else None
+    pm = table(match) if any(per) or not isinstance(want_match, bool) else None
     rc = L.orbq_track_reference(handle, pool_handle, store_handle, ptr(jobs), a.n_jobs, float(nnratio), int(bool(check_ori)), int(min_matches),
-                                ptr(a.sigma), a.nlevels, ptr(a.out), _table(a.ids), _table(a.flags), pm)
+                                ptr(a.sigma), a.nlevels, ptr(a.out), table(a.ids), table(a.flags), pm)
     return rc, a.out[:len(a.ns)], _cut(a.ids, a.ns), _cut(a.flags, a.ns), _cut(match, a.ns)
 
 
@@ -166,24 +139,13 @@ RELOC_KEEP = 0xff
 RELOC_ST_NOT_RUN, RELOC_ST_NO_POINT, RELOC_ST_BAD, RELOC_ST_FOUND, RELOC_ST_OUT_OF_IMAGE, RELOC_ST_DISTANCE, RELOC_ST_LEVEL_RANGE, RELOC_ST_IN_VIEW = range(8)
 
 
-def _setup_reloc(L):
-    if getattr(L, "_orbq_reloc_ready", False):
-        return
-    vp = C.c_void_p
-    L.orbq_relocalize.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
-    L.orbq_debug_reloc_arena.argtypes = [vp, C.c_int, vp]
-    L._orbq_reloc_ready = True
-
-
 def pack_reloc_jobs(jobs):
     """(RELOC_JOB_DTYPE array, the id arrays it points into) from job dicts: fs (a FrameSet, or a raw handle value), slot, kf_slot, kf,
     n, ids (the pool id of vvpMapPointMatches[i][t] where vbInliers[t], else -1; None: a null pointer), Tcw (PnP's pose), K"""
     rec = np.zeros(len(jobs), dtype=RELOC_JOB_DTYPE)
     keep = []
     for i, j in enumerate(jobs):
-        fs = j["fs"]
-        h = getattr(fs, "_h", fs)
-        rec["fs"][i] = (h.value if isinstance(h, C.c_void_p) else h) or 0
+        rec["fs"][i] = handle_value(j["fs"])
         rec["slot"][i], rec["kf_slot"][i], rec["kf"][i], rec["n"][i] = j["slot"], j["kf_slot"], j["kf"], j["n"]
         ids = j.get("ids")
         if ids is not None:
@@ -202,15 +164,14 @@ def relocalize_raw(handle, pool_handle, store_handle, jobs, check_ori, inv_level
     results, [ids per job], [outlier per job], [status (2, stride) per job, or None]); no exception on a refusal.  fill: the byte the
     output arrays hold before the call.  want_status: True, False (a null status_out) or one bool per job (nulls inside it)"""
     L = lib()
-    _setup_reloc(L)
     a = _raw_arrays(jobs, inv_level_sigma2, nlevels, n_jobs, fill, RELOC_RESULT_DTYPE)
     sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, dtype=np.float32)
     br = None if level_breaks is None else np.ascontiguousarray(level_breaks, dtype=np.float32)
     per = [bool(want_status)] * len(a.ns) if isinstance(want_status, bool) else [bool(w) for w in want_status]
     status = [np.full((2, max(int(stride), 1)), 0 if fill is None else fill, np.uint8) if per[i] else None for i in range(len(a.ns))]
-    ps = _table(status) if any(per) or not isinstance(want_status, bool) else None
+    ps = table(status) if any(per) or not isinstance(want_status, bool) else None
     rc = L.orbq_relocalize(handle, pool_handle, store_handle, ptr(jobs), a.n_jobs, int(check_ori), ptr(a.sigma), ptr(sf), ptr(br), a.nlevels,
-                           ptr(a.out), _table(a.ids), _table(a.flags), ps)
+                           ptr(a.out), table(a.ids), table(a.flags), ps)
     return rc, a.out[:len(a.ns)], _cut(a.ids, a.ns), _cut(a.flags, a.ns), [None if s is None else s[:, :int(stride)] for s in status]
 
 
@@ -243,7 +204,6 @@ def debug_reloc_arena(matcher, entries_per_job=-1):
     """orbq_debug_reloc_arena, for the overflow tests: sets the starting size of a job's share of the candidate arena (0: the default;
     -1: leaves it) and returns how many times the last relocalize on the matcher ran its chain"""
     L = lib()
-    _setup_reloc(L)
     runs = C.c_int(0)
     check(L.orbq_debug_reloc_arena(matcher._h, int(entries_per_job), C.byref(runs)))
     return runs.value

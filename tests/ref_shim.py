@@ -35,6 +35,13 @@ def p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def declared(header, prefix=""):
+    """the C entries include/<header> declares whose names begin with `prefix`, sorted -- as the loader itself reads the headers
+    (_lib.declarations()), so a family's test and the library's signatures cannot come from two readings"""
+    from orbslamm_amd import _lib
+    return sorted(n for n, d in _lib.declarations().items() if d.header == header and n.startswith(prefix))
+
+
 def quoted_includes(path):
     """every file reached from `path` through #include "..." (resolved beside the including file, as g++ does first),
     transitively, `path` itself first: absolute paths.  A quoted include that does not exist there is an error: the

@@ -74,12 +74,12 @@ def refuse(code, rec_keep, n_jobs=None, nlevels=None, **tables):
 
 
 def test_the_library_declares_the_entry_and_its_records():
-    assert "orby_compute_sim3" in _lib.EXPORTS_COMPUTESIM3 and hasattr(_lib.lib(), "orby_compute_sim3")
+    assert _lib.declarations()["orby_compute_sim3"].header == "orbslamm_computesim3.h" and hasattr(_lib.lib(), "orby_compute_sim3")
     assert JOB_DTYPE.itemsize == 336 and RESULT_DTYPE.itemsize == 136 and cc.REF_RESULT.itemsize == 136
     assert [JOB_DTYPE.fields[f][1] for f in ("fs", "slot1", "slot2", "kf1", "kf2", "n1", "n2", "prob", "R12", "t12", "s12", "bounds1", "bounds2", "th", "m12_id", "m12_idx2")] == \
         [0, 8, 12, 16, 20, 24, 28, 32, 232, 268, 280, 284, 300, 316, 320, 328]
     assert [RESULT_DTYPE.fields[f][1] for f in ("opt", "n_found", "n_corr")] == [0, 128, 132]
-    assert "orby_compute_sim3" not in _lib.EXPORTS
+    assert _lib.declarations()["orby_compute_sim3"].header != "orbslamm_hip.h"
 
 
 def test_refusals_that_need_no_gpu():

@@ -162,7 +162,7 @@ extern "C" int layout(int i) {
 def test_the_symbols_are_exported():
     L = lib()
     for name in ("orbu_kf_set_octaves", "orbn_update_connections", "orbn_culling_counts"):
-        assert name in _lib.EXPORTS_COVIS and hasattr(L, name)
+        assert _lib.declarations()[name].header == "orbslamm_covis.h" and hasattr(L, name)
 
 
 def test_refusals_that_need_no_gpu():
@@ -170,7 +170,6 @@ def test_refusals_that_need_no_gpu():
     return ORBX_OK"""
     from orbslamm_amd import map_pool as mp
     L = lib()
-    mp._setup_store(L)
     one = np.zeros(1, np.int32)
     octs = np.zeros(4, np.uint8)
     so = L.orbu_kf_set_octaves

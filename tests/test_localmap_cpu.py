@@ -75,7 +75,6 @@ def test_refusals_that_need_no_gpu():
     zero counts return ORBX_OK"""
     from orbslamm_amd import map_pool as mp
     L = lib()
-    mp._setup(L)
     out = C.c_void_p()
     assert L.orbw_pool_create(None, 16, None) == ORBX_E_INVALID
     assert L.orbw_pool_create(None, 0, C.byref(out)) == ORBX_E_INVALID

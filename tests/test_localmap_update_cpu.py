@@ -166,8 +166,6 @@ def test_refusals_that_need_no_gpu():
     return ORBX_OK"""
     from orbslamm_amd import map_pool as mp
     L = lib()
-    mp._setup(L)
-    mp._setup_store(L)
     out = C.c_void_p()
     create = L.orbu_store_create
     assert create(None, 16, 64, 4, 100, None) == ORBX_E_INVALID

@@ -181,7 +181,7 @@ def test_the_symbols_are_exported():
     import orbslamm_amd
     L = lib()
     for name in ("orbu_kf_set_descriptors", "orbu_kf_set_descriptors_frame", "orbu_kf_set_centres", "orbw_debug_pool_get", "orbr_refresh_points"):
-        assert name in _lib.EXPORTS_REFRESH and hasattr(L, name)
+        assert _lib.declarations()[name].header == "orbslamm_refresh.h" and hasattr(L, name)
     for name in ("set_descriptors", "set_descriptors_frame", "set_centres", "refresh_points"):
         assert hasattr(orbslamm_amd.KeyFrameStore, name)
     assert hasattr(orbslamm_amd.MapPool, "debug_get") and orbslamm_amd.REFRESH_DTYPE.itemsize == 84
@@ -192,8 +192,6 @@ def test_refusals_that_need_no_gpu():
     ORBX_OK, and `out` keeps its bytes"""
     from orbslamm_amd import map_pool as mp
     L = lib()
-    mp._setup(L)
-    mp._setup_store(L)
     ids, ref, sf = np.zeros(2, np.int32), np.full(2, -1, np.int32), rc.SF.copy()
     ids[1] = 1
     pos = np.zeros((2, 3), np.float32)

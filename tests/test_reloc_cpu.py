@@ -135,5 +135,4 @@ def test_refusals_that_need_no_gpu():
     refused(E_INVALID, "null pool", rec, pool=None)
     refused(E_INVALID, "null store", rec, store=None)
     L = tp.lib()
-    tp._setup_reloc(L)
     assert L.orbq_debug_reloc_arena(H_, -2, None) == E_INVALID and L.orbq_debug_reloc_arena(H_, (1 << 24) + 1, None) == E_INVALID

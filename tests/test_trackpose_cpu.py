@@ -95,7 +95,7 @@ def refuse(code, jobs, sig=tc.sigma2(), **kw):
 
 
 def test_the_library_declares_the_entry_and_its_records():
-    assert "orbq_track_pose" in _lib.EXPORTS_TRACKPOSE and hasattr(_lib.lib(), "orbq_track_pose")
+    assert _lib.declarations()["orbq_track_pose"].header == "orbslamm_trackpose.h" and hasattr(_lib.lib(), "orbq_track_pose")
     assert JOB_DTYPE.itemsize == 112 and TRACK_RESULT_DTYPE.itemsize == 184 and tc.REF_RESULT.itemsize == 184
 
 

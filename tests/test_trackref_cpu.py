@@ -153,13 +153,13 @@ def refuse(code, jobs, sig=tc.sigma2(), min_matches=15, h=None, **kw):
 
 
 def test_the_library_declares_the_entry_and_its_records():
-    assert "orbq_track_reference" in _lib.EXPORTS_TRACKPOSE and hasattr(_lib.lib(), "orbq_track_reference")
+    assert _lib.declarations()["orbq_track_reference"].header == "orbslamm_trackpose.h" and hasattr(_lib.lib(), "orbq_track_reference")
     assert REF_JOB_DTYPE.itemsize == 112 and REF_RESULT_DTYPE.itemsize == 192 and rc.REF_RESULT.itemsize == 192
     assert [REF_JOB_DTYPE.fields[f][1] for f in ("fs", "kf_slot", "slot", "kf", "n", "solve", "frame")] == [0, 8, 12, 16, 20, 24, 28]
     assert [REF_RESULT_DTYPE.fields[f][1] for f in ("track", "n_bow", "status")] == [0, 184, 188]
     assert (REF_TRACKED, REF_TOO_FEW, REF_SEARCH_ONLY) == (rc.TRACKED, rc.TOO_FEW, rc.SEARCH_ONLY) == (0, 1, 2)
-    # the entry stays out of orbslamm_hip.h's own text and list
-    assert "orbq_track_reference" not in _lib.EXPORTS
+    # the entry stays out of orbslamm_hip.h's own text
+    assert _lib.declarations()["orbq_track_reference"].header != "orbslamm_hip.h"
 
 
 def test_refusals_that_need_no_gpu():

@@ -125,7 +125,6 @@ def main():
         import ctypes as C
         from orbslamm_amd._lib import check, lib, ptr
         L = lib()
-        lo._setup(L)
         T, P = len(frames), len(case["points"])
         recs = np.array([t["rec"] for t in frames], dtype=lm.FUSE_TARGET_DTYPE)
         fr = (C.c_void_p * T)(*[t["frame"].value for t in frames])

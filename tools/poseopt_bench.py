@@ -41,7 +41,6 @@ def main():
     from orbslamm_amd._lib import check, lib, ptr
     m = ORBmatcher(0.9, True, device=0)
     L = lib()
-    opt._setup(L)
     sig = pc.inv_level_sigma2()
     rows = []
     for B in [int(v) for v in a.frames.split(",")]:

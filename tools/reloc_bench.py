@@ -43,12 +43,10 @@ def main():
     import localmap_cases as lc
     import reloc_cases as rc
     from ref_shim import build_ref_shim
-    from orbslamm_amd._lib import lib
-    from orbslamm_amd.optimizer import EDGE_DTYPE, FRAME_DTYPE, RESULT_DTYPE, _setup as setup_orbo
-    from orbslamm_amd.track_pose import RELOC_RESULT_DTYPE, _setup_reloc, _table, pack_reloc_jobs
+    from orbslamm_amd._lib import lib, table
+    from orbslamm_amd.optimizer import EDGE_DTYPE, FRAME_DTYPE, RESULT_DTYPE
+    from orbslamm_amd.track_pose import RELOC_RESULT_DTYPE, pack_reloc_jobs
     L = lib()
-    setup_orbo(L)
-    _setup_reloc(L)
     vp, i32 = C.c_void_p, C.c_int32
     raw = lambda h: h.value if isinstance(h, vp) else int(h)
 
@@ -97,14 +95,14 @@ def main():
         ids = [np.zeros(N_FEAT, np.int32) for _ in range(nj)]
         outl = [np.zeros(N_FEAT, np.uint8) for _ in range(nj)]
         status = [np.zeros((2, N_ROW), np.uint8) for _ in range(nj)]
-        pi, po, ps = _table(ids), _table(outl), _table(status)
+        pi, po, ps = table(ids), table(outl), table(status)
         args = (rig.m._h, pool._h, store._h, rec.ctypes.data, nj, 1, sig.ctypes.data, sf.ctypes.data, brk.ctypes.data, len(sig), out.ctypes.data, pi, po, ps)
         # ---- the parent's way's arrays
         ents = [np.ascontiguousarray(cases[j]["entries"], np.int32) for j in range(nj)]
         idin = [np.ascontiguousarray(cases[j]["ids"], np.int32) for j in range(nj)]
         tcw = np.ascontiguousarray([np.asarray(cases[j]["Tcw"], np.float32).reshape(16) for j in range(nj)], np.float32)
         k = dict(fs=(vp * nj)(*[raw(sets[j // 2]._h) for j in range(nj)]), slot=np.array([2 * (j % 2) + 1 for j in range(nj)], np.int32),
-                 kfSlot=np.array([2 * (j % 2) for j in range(nj)], np.int32), resident=(vp * nj)(*[raw(f) for f in resident[:nj]]), entries=_table(ents), idsIn=_table(idin),
+                 kfSlot=np.array([2 * (j % 2) for j in range(nj)], np.int32), resident=(vp * nj)(*[raw(f) for f in resident[:nj]]), entries=table(ents), idsIn=table(idin),
                  frames=np.zeros(nj, FRAME_DTYPE), residentLive=(vp * nj)(), edges=np.zeros(nj * N_FEAT, EDGE_DTYPE), start=np.zeros(nj + 1, np.int32),
                  optOut=np.zeros(nj, RESULT_DTYPE), eflags=np.zeros(nj * N_FEAT, np.uint8), live=np.zeros(nj, np.int32), uvr=np.zeros(3 * N_ROW, np.float32),
                  lvl=np.zeros(2 * N_ROW, np.int8), qv=np.zeros(N_ROW, np.uint8), occ=np.zeros(CAP, np.uint8), mark=np.zeros(len(records), np.uint8),

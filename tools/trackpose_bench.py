@@ -56,11 +56,9 @@ def main():
     from ref_shim import p
     from orbslamm_amd import MapPool, ORBextractor, ORBmatcher, level_breaks, make_grid
     from orbslamm_amd._lib import KP_DTYPE, check, lib, ptr
-    from orbslamm_amd.optimizer import EDGE_DTYPE, FRAME_DTYPE, RESULT_DTYPE, _setup as setup_orbo
-    from orbslamm_amd.track_pose import TRACK_RESULT_DTYPE, _setup as setup_orbq, pack_jobs
+    from orbslamm_amd.optimizer import EDGE_DTYPE, FRAME_DTYPE, RESULT_DTYPE
+    from orbslamm_amd.track_pose import TRACK_RESULT_DTYPE, pack_jobs
     L = lib()
-    setup_orbo(L)
-    setup_orbq(L)
     shim = tc.ref_lib()
     vp = C.c_void_p
     shim.trackposeref_host_edges.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]

@@ -46,11 +46,9 @@ def main():
     from ref_shim import build_ref_shim
     from orbslamm_amd import KeyFrameStore, MapPool, ORBextractor, ORBmatcher, ORBVocabulary, make_grid
     from orbslamm_amd._lib import check, lib, ptr
-    from orbslamm_amd.optimizer import EDGE_DTYPE, FRAME_DTYPE, RESULT_DTYPE, _setup as setup_orbo
-    from orbslamm_amd.track_pose import REF_RESULT_DTYPE, _setup_ref, pack_ref_jobs
+    from orbslamm_amd.optimizer import EDGE_DTYPE, FRAME_DTYPE, RESULT_DTYPE
+    from orbslamm_amd.track_pose import REF_RESULT_DTYPE, pack_ref_jobs
     L = lib()
-    setup_orbo(L)
-    _setup_ref(L)
     vp = C.c_void_p
 
     class ParentWay(C.Structure):   # tests/cpp/trackref_bench_capi.cpp
