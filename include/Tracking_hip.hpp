@@ -40,6 +40,8 @@
 //
 //   iORB_SLAM::TrackReferenceKeyFrameT<Frame, KeyFrame, MapPoint>::Run(h, fs, kfSlot, slot, pool, store, kf, mCurrentFrame, mpReferenceKF,
 //                                                                      mLastFrame.mTcw);            // Tracking.cc:802-844
+//   iORB_SLAM::TrackWithMotionModelT<Frame, MapPoint>::Run(h, fs, curSlot, lastSlot, pool, mCurrentFrame, mLastFrame, mVelocity, idOfPoint,
+//                                                          mbOnlyTracking);                         // Tracking.cc:917-978
 //
 // TrackWithMotionModelT::Finish stands behind orbw_track_frame_pose issued against (fs, slot) with mLastFrame's ids and `nmatches >= 20`
 // (:944, the caller's, from orbm_track_results): it merges the table into mvpMapPoints (ORBmatcher.cc:1430), and writes back in the
@@ -330,6 +332,78 @@ struct TrackWithMotionModelT {
         res.opt = r.opt; res.nmatches = r.n_matches; res.nmatchesMap = r.n_matches_map;
         res.vo = r.n_matches_map < 10;                                          // :973
         res.ok = onlyTracking ? r.n_matches > 20 : r.n_matches_map >= 10;       // :974, :977
+        return res;
+    }
+
+    // Tracking::TrackWithMotionModel (Tracking.cc:917-978, monocular) behind UpdateLastFrame (:923, the caller's) on
+    // orbq_track_motion_model (include/orbslamm_motion.h): the pose product, the search, its retry with 2 * th, the gate,
+    // PoseOptimization and the discard loop in ONE call.  The current frame lies in curSlot and mLastFrame in lastSlot of fs, the last
+    // frame's points in the pool under idOfPoint(pMP).  Run makes the device call first and replays the host-visible effects afterwards,
+    // in the reference's order.  A refusal throws with the frame untouched.
+    struct RunOptions {
+        float th = 15.f;          // :932
+        int minMatches = 20;      // :938, :944
+        bool checkOri = true;     // ORBmatcher matcher(0.9,true), :919
+    };
+    // status, wide, nSearch: as OrbqMotionResult; nmatches is the reference's counter at :971 (the count of the search that stands less
+    // the discarded outliers), nmatchesMap that of :967; vo is mbVO as :973 would set it (meaningful under onlyTracking)
+    struct RunResult { bool ok; bool vo; int status; bool wide; int nSearch[2]; int nmatches; int nmatchesMap; OrboResult opt; };
+
+    template <class MatT, class IdOf>
+    static RunResult Run(orbm_t* h, orbm_frameset_t* fs, int curSlot, int lastSlot, orbw_pool_t* pool, Frame& F, const Frame& L, const MatT& velocity,
+                         IdOf idOfPoint, bool onlyTracking, const RunOptions& o = RunOptions())
+    {
+        const char* who = "TrackWithMotionModel(HIP): ";
+        const int N = F.N, NQ = L.N;
+        std::vector<int32_t> lastIds((size_t)NQ + 1, -1);
+        for (int i = 0; i < NQ; i++)   // ORBmatcher.cc:1355-1359
+            if (L.mvpMapPoints[i] && !L.mvbOutlier[i]) lastIds[(size_t)i] = (int32_t)idOfPoint(L.mvpMapPoints[i]);
+        OrbqMotionJob J;
+        J.fs = fs; J.cur_slot = curSlot; J.last_slot = lastSlot; J.n = N; J.nq = NQ; J.last_ids = lastIds.data();
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) { J.velocity[4 * r + c] = velocity.template at<float>(r, c); J.last_Tcw[4 * r + c] = L.mTcw.template at<float>(r, c); }
+        J.K[0] = Frame::fx; J.K[1] = Frame::fy; J.K[2] = Frame::cx; J.K[3] = Frame::cy;
+        OrbqMotionResult r;
+        std::vector<int32_t> ids((size_t)N + 1), assign((size_t)N + 1);
+        std::vector<uint8_t> outlier((size_t)N + 1);
+        int32_t* pi = ids.data(); uint8_t* po = outlier.data(); int32_t* pa = assign.data();
+        detail::check(orbq_track_motion_model(h, pool, &J, 1, o.th, o.minMatches, o.checkOri ? 1 : 0, F.mvInvLevelSigma2.data(), F.mvScaleFactors.data(),
+                                              (int)F.mvInvLevelSigma2.size(), &r, &pi, &po, &pa, nullptr), who);
+        int nDiscarded = 0;
+        for (int t = 0; t < N; t++) {
+            if (assign[t] >= NQ || (assign[t] >= 0 && lastIds[(size_t)assign[t]] < 0))
+                throw std::runtime_error(std::string(who) + "the table names a last-frame feature without a MapPoint");
+            if ((ids[t] >= 0) != (assign[t] >= 0 && !outlier[t]) || (outlier[t] && assign[t] < 0))
+                throw std::runtime_error(std::string(who) + "the ids returned are not the search's matches without the outliers");
+            nDiscarded += outlier[t] ? 1 : 0;
+        }
+        // ---- the replay, in the reference's order
+        auto pose = velocity.clone();
+        for (int rr = 0; rr < 4; rr++) for (int c = 0; c < 4; c++) pose.template at<float>(rr, c) = r.Tcw_pred[4 * rr + c];
+        F.SetPose(pose);   // :925
+        std::fill(F.mvpMapPoints.begin(), F.mvpMapPoints.end(), static_cast<MapPoint*>(NULL));   // :927 (and :940)
+        for (int t = 0; t < N; t++)
+            if (assign[t] >= 0) F.mvpMapPoints[t] = L.mvpMapPoints[(size_t)assign[t]];   // ORBmatcher.cc:1430, behind the pruning of :1464
+        RunResult res;
+        res.status = r.status; res.wide = r.wide != 0; res.nSearch[0] = r.n_search[0]; res.nSearch[1] = r.n_search[1];
+        res.nmatches = r.n_search[r.wide ? 1 : 0]; res.nmatchesMap = 0; res.opt = r.track.opt;
+        res.ok = false; res.vo = false;
+        if (r.status == ORBQ_MM_TOO_FEW) return res;   // :944-945: the frame keeps the predicted pose and the matches
+        for (int i = 0; i < N; i++)
+            if (F.mvpMapPoints[i]) F.mvbOutlier[i] = outlier[i] != 0;   // Optimizer.cc:310, :410, :416
+        detail::set_pose(F, r.track.opt);   // :470
+        for (int i = 0; i < N; i++) {   // Tracking.cc:952-969
+            if (!F.mvpMapPoints[i] || !F.mvbOutlier[i]) continue;
+            MapPoint* pMP = F.mvpMapPoints[i];
+            F.mvpMapPoints[i] = static_cast<MapPoint*>(NULL);
+            F.mvbOutlier[i] = false;
+            pMP->mbTrackInView = false;
+            pMP->mnLastFrameSeen = F.mnId;
+        }
+        res.nmatches -= nDiscarded;                                                   // :964
+        res.nmatchesMap = r.track.n_matches_map;                                      // :967
+        res.vo = res.nmatchesMap < 10;                                                // :973
+        res.ok = onlyTracking ? res.nmatches > 20 : res.nmatchesMap >= 10;            // :974, :977
         return res;
     }
 };

@@ -992,6 +992,10 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 /* Tracking::Relocalization behind PnPsolver::iterate, per candidate: three PoseOptimizations and two keyframe projections from the
  * pool, the store and the frame set (orbq_relocalize): orbslamm_reloc.h. */
 #include "orbslamm_reloc.h"
+/* Tracking::TrackWithMotionModel from the predicted pose to the counts its verdicts read: the pose product, the frame/frame
+ * search and its retry, PoseOptimization and the discard loop from the pool and the frame set (orbq_track_motion_model):
+ * orbslamm_motion.h. */
+#include "orbslamm_motion.h"
 /* LoopClosing::ComputeSim3 behind the Sim3Solver, per candidate: SearchBySim3 and OptimizeSim3 from the pool, the store and the
  * frame set (orby_compute_sim3): orbslamm_computesim3.h. */
 #include "orbslamm_computesim3.h"

@@ -15,5 +15,6 @@ from .map_pool import KeyFrameStore, MapPool  # noqa: F401
 from .map_pool import REFRESH_DESCRIPTOR, REFRESH_DTYPE, REFRESH_MAX_OBS, REFRESH_NORMAL_DEPTH  # noqa: F401
 from .map_pool import CORRECT_KF_DTYPE, CORRECT_POINT_DTYPE  # noqa: F401
 from .track_pose import pack_reloc_jobs, relocalize, relocalize_raw, track_pose, track_reference  # noqa: F401
+from .track_pose import pack_motion_jobs, track_motion_model, track_motion_model_raw  # noqa: F401
 from .compute_sim3 import compute_sim3, compute_sim3_batch  # noqa: F401
 from ._lib import KP_DTYPE, OrbError  # noqa: F401

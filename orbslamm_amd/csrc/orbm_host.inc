@@ -85,9 +85,10 @@ enum OrbmSlot {
     S_TRI_K1, S_TRI_D1, S_TRI_K2, S_TRI_D2, S_TRI_ST1, S_TRI_I1, S_TRI_ST2, S_TRI_I2, /* orbm_search_for_triangulation | tri_core */
     S_TRI_S1, S_TRI_U1, S_TRI_S2, S_TRI_U2, S_TRI_PA, S_TRI_PB, S_TRI_M12, S_TRI_BIN, S_TRI_NMATCH,
     S_UND_IN, S_UND_OUT, S_RGBD_KEYS, S_RGBD_KEYSUN, S_RGBD_DEPTH, S_RGBD_OUT, S_DIS_DESC, S_DIS_START, S_DIS_BEST,   // orbm_undistort_keypoints, _compute_stereo_from_rgbd, _distinctive_descriptors
-    S_BLOCK,                                                // THE ONE SHARED NAME: the packed block of orbl_core, orbl_fuse_core, orbc_core, orbo_core, orbw_project_sync, orby_compute_sim3 and orbq_relocalize, which never nest
+    S_BLOCK,                                                // THE ONE SHARED NAME: the packed block of orbl_core, orbl_fuse_core, orbc_core, orbo_core, orbw_project_sync, orby_compute_sim3, orbq_relocalize and orbq_track_motion_model, which never nest
     S_LF_PAIR, S_LF_TILES, S_LF_HITS, S_LF_STATUS,          // orbc_core besides S_BLOCK
     S_RELOC_ARENA,                                          // orbq_relocalize besides S_BLOCK: the searches' candidate arena, a share a job
+    S_MOTION_ARENA,                                         // orbq_track_motion_model besides S_BLOCK: the same
     T_STAGE, /* device twin of the pinned staging block: bow_core and proj_core (orbt_host.inc) | proj_core, call scratch */ T_OFF, T_CAND, T_QRES, T_TSCR,
     // PERSISTENT -- these live ACROSS calls and are the projection search's alone.  T_FS / T_PREP: the scratch frame and the upload orbm_projection_prepare
     // leaves for the next search.  T_STATS: proj_core's candidate counter, zeroed when the block is first made (slot_cap() == 0), left zero by every resolve
@@ -108,6 +109,7 @@ struct orbm_handle {
     int lastRounds = 0, lastCands = 0;   // of the last projection search (orbm_last_search_stats)
     int relocArena = 0;                  // orbq_relocalize: entries of a job's share of S_RELOC_ARENA (0: the default); grown by an overflow, set by orbq_debug_reloc_arena
     int relocRuns = 0;                   // ... and how many times its last call ran the chain (orbq_debug_reloc_arena reports it)
+    int motionArena = 0, motionRuns = 0; // orbq_track_motion_model: the same two for S_MOTION_ARENA (orbq_debug_motion_arena)
     // orbm_projection_prepare: the train side of the NEXT orbm_search_by_projection, already in HBM with its grid built
     // (identified by the caller's pointers, count and grid: the search falls back to its own upload when they differ)
     struct Prepared { bool valid = false, inFlight = false; const void* keys = nullptr; const void* desc = nullptr; int nt = 0; OrbmGrid grid{}; uint64_t seq = 0; } prep;

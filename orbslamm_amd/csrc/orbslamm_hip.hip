@@ -57,6 +57,7 @@
 #include "orbn_kernels.hip"   // covisibility: UpdateConnections' counter and ordered list, KeyFrameCulling's counts, over the store
 #include "orbq_kernels.hip"   // PoseOptimization from the pool: merge, ordered edge list, orbo's solve, Tracking's loop behind it
 #include "orbq_reloc_kernels.hip"   // Relocalization behind the PnP pose: the stage kernel on orbq's pieces, the keyframe projection, sFound
+#include "orbq_motion_kernels.hip"  // TrackWithMotionModel: the pose product, the retry decision and the solve as a stage kernel, the frame/frame projection from the device-made pose
 #include "orbr_kernels.hip"   // the map-point refresh: ComputeDistinctiveDescriptors and UpdateNormalAndDepth over the store, into the pool
 #include "orbe_kernels.hip"   // the loop correction: the Sim3 propagated, the points moved once, orbr's normals with mixed centres, the commit
 #include "orby_kernels.hip"   // ComputeSim3 behind the solver: SearchBySim3's two passes, the agreement, OptimizeSim3's walk, orbz's solve
@@ -225,4 +226,5 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbe_host.inc"   // the loop correction's entry and its blocks
 #include "orbq_host.inc"   // PoseOptimization behind the pool searches: TrackWithMotionModel's and TrackLocalMap's verdicts
 #include "orbq_reloc_host.inc"   // Relocalization behind PnPsolver::iterate: three solves and two keyframe projections per candidate
+#include "orbq_motion_host.inc"  // TrackWithMotionModel from the predicted pose to the counts: both searches, the gate, the solve and the loop in one call
 #include "orby_host.inc"   // SearchBySim3 and OptimizeSim3 from the pool, the store and the frame set: ComputeSim3's verdict per candidate

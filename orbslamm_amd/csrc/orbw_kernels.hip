@@ -60,6 +60,24 @@ struct ProjectArgs {
 
 __device__ __forceinline__ float radius_by_viewing_cos(float viewCos) { return (double)viewCos > 0.998 ? 2.5f : 4.0f; }   // ORBmatcher.cc:131-137
 
+// the frame/frame gate set (ORBmatcher.cc:1362-1389, monocular) for one LastFrame point A of the given octave under the pose
+// (Rcw, tcw): its status, and where it is in view the projection and the search radius.  k_view_project's and
+// orbq::k_motion_project's one statement of it.
+__device__ __forceinline__ uint8_t frame_gate(const float (&Rcw)[9], const float (&tcw)[3], float fx, float fy, float cx, float cy,
+                                              float minX, float maxX, float minY, float maxY, float th, const float* scale,
+                                              const float4 A, int octave, float& u, float& v, float& r)
+{
+    float pc[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) pc[i] = cvm::gemm3_elem(Rcw[3 * i], Rcw[3 * i + 1], Rcw[3 * i + 2], A.x, A.y, A.z, 1.0, tcw[i], 1.0);
+    const float invzc = (float)(1.0 / (double)pc[2]);   // :1367
+    if (invzc < 0) return ST_DEPTH;
+    u = fx * pc[0] * invzc + cx; v = fy * pc[1] * invzc + cy;
+    if (!(u >= minX && u <= maxX && v >= minY && v <= maxY)) return ST_OUT_OF_IMAGE;
+    r = th * scale[min(max(octave, 0), 15)];
+    return ST_IN_VIEW;
+}
+
 __global__ __launch_bounds__(kThreads) void k_view_project(ProjectArgs p, ViewArgs V)
 {
     const int qBlocks = (p.nq + kThreads - 1) / kThreads;
@@ -83,23 +101,9 @@ __global__ __launch_bounds__(kThreads) void k_view_project(ProjectArgs p, ViewAr
         // ORBmatcher.cc:1353-1392
         const float4 A = p.pool.a[id];
         obs = (p.pool.flags[id] >> 1) & 1;
-        {
-            const int octave = p.lastKeys[q].octave;
-            lo = octave - 1; hi = octave + 1;
-            float pc[3];
-#pragma unroll
-            for (int i = 0; i < 3; i++) pc[i] = cvm::gemm3_elem(V.Rcw[3 * i], V.Rcw[3 * i + 1], V.Rcw[3 * i + 2], A.x, A.y, A.z, 1.0, V.tcw[i], 1.0);
-            const float invzc = (float)(1.0 / (double)pc[2]);   // :1367
-            st = ST_DEPTH;
-            if (!(invzc < 0)) {
-                u = V.fx * pc[0] * invzc + V.cx; v = V.fy * pc[1] * invzc + V.cy;
-                st = ST_OUT_OF_IMAGE;
-                if (u >= V.minX && u <= V.maxX && v >= V.minY && v <= V.maxY) {
-                    st = ST_IN_VIEW;
-                    r = V.th * V.scale[min(max(octave, 0), 15)];
-                }
-            }
-        }
+        const int octave = p.lastKeys[q].octave;
+        lo = octave - 1; hi = octave + 1;
+        st = frame_gate(V.Rcw, V.tcw, V.fx, V.fy, V.cx, V.cy, V.minX, V.maxX, V.minY, V.maxY, V.th, V.scale, A, octave, u, v, r);
     } else {
         // Frame.cc:269-325, ORBmatcher.cc:57-69
         const float4 A = p.pool.a[id], B = p.pool.b[id];

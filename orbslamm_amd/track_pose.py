@@ -1,5 +1,5 @@
-"""ctypes mirror of orbq_track_pose, orbq_track_reference (include/orbslamm_trackpose.h) and orbq_relocalize
-(include/orbslamm_reloc.h, §8y): Optimizer::PoseOptimization as Tracking calls
+"""ctypes mirror of orbq_track_pose, orbq_track_reference (include/orbslamm_trackpose.h), orbq_relocalize
+(include/orbslamm_reloc.h, §8y) and orbq_track_motion_model (include/orbslamm_motion.h, §8z): Optimizer::PoseOptimization as Tracking calls
 it right behind a pool search, with the loop that follows it, for any number of frames in one launch.
 
     pool.track_local_map(fs, slot, view, ids, 1.0, sf, breaks); fs.results()          # or store.track_local_map / track_frame_pose
@@ -206,4 +206,77 @@ def debug_reloc_arena(matcher, entries_per_job=-1):
     L = lib()
     runs = C.c_int(0)
     check(L.orbq_debug_reloc_arena(matcher._h, int(entries_per_job), C.byref(runs)))
+    return runs.value
+
+
+# ------------------------------------------------------------------ orbq_track_motion_model
+MOTION_JOB_DTYPE = np.dtype([("fs", "<u8"), ("cur_slot", "<i4"), ("last_slot", "<i4"), ("n", "<i4"), ("nq", "<i4"), ("last_ids", "<u8"),
+                             ("velocity", "<f4", (16,)), ("last_Tcw", "<f4", (16,)), ("K", "<f4", (4,))])
+MOTION_RESULT_DTYPE = np.dtype([("track", TRACK_RESULT_DTYPE), ("Tcw_pred", "<f4", (16,)), ("n_search", "<i4", (2,)), ("wide", "<i4"), ("status", "<i4")])
+assert MOTION_JOB_DTYPE.itemsize == 176 and MOTION_RESULT_DTYPE.itemsize == 264
+MM_TRACKED, MM_TOO_FEW = 0, 1
+MM_ST_NOT_RUN = 0xff
+
+
+def pack_motion_jobs(jobs):
+    """(MOTION_JOB_DTYPE array, the id arrays it points into) from job dicts: fs (a FrameSet, or a raw handle value), cur_slot, last_slot,
+    n, last_ids (the pool id of mLastFrame.mvpMapPoints[i], -1 where NULL or an outlier; None: a null pointer), nq (default: len(last_ids)),
+    velocity (mVelocity), last_Tcw (mLastFrame.mTcw), K"""
+    rec = np.zeros(len(jobs), dtype=MOTION_JOB_DTYPE)
+    keep = []
+    for i, j in enumerate(jobs):
+        rec["fs"][i] = handle_value(j["fs"])
+        rec["cur_slot"][i], rec["last_slot"][i], rec["n"][i] = j["cur_slot"], j["last_slot"], j["n"]
+        ids = j.get("last_ids")
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+            keep.append(ids)
+            rec["last_ids"][i] = ids.ctypes.data
+        rec["nq"][i] = j["nq"] if "nq" in j else 0 if ids is None else ids.shape[0]
+        assert ids is None or ids.shape[0] >= rec["nq"][i]
+        rec["velocity"][i] = np.asarray(j.get("velocity", np.eye(4)), dtype=np.float32).reshape(16)
+        rec["last_Tcw"][i] = np.asarray(j.get("last_Tcw", np.eye(4)), dtype=np.float32).reshape(16)
+        rec["K"][i] = K4(j.get("K", [1, 1, 0, 0]))
+    return rec, keep
+
+
+def track_motion_model_raw(handle, pool_handle, jobs, th, min_matches, check_ori, inv_level_sigma2, scale_factors, nlevels=None, n_jobs=None,
+                           fill=None, want_tables=True):
+    """the C entry as it is: jobs a MOTION_JOB_DTYPE array (or None).  Returns (rc, results, [ids per job], [outlier per job], [assign
+    table per job, or None], [status (2, nq) per job, or None]); no exception on a refusal.  fill: the byte the output arrays hold before
+    the call.  want_tables: True, False (null assign_out and status_out) or one bool per job (nulls inside them)"""
+    L = lib()
+    a = _raw_arrays(jobs, inv_level_sigma2, nlevels, n_jobs, fill, MOTION_RESULT_DTYPE)
+    sf = None if scale_factors is None else np.ascontiguousarray(scale_factors, dtype=np.float32)
+    per = [bool(want_tables)] * len(a.ns) if isinstance(want_tables, bool) else [bool(w) for w in want_tables]
+    nqs = [max(int(jobs["nq"][i]), 0) for i in range(len(a.ns))]
+    assign = [np.full(max(n, 1), -2 if fill is None else fill, np.int32) if per[i] else None for i, n in enumerate(a.ns)]
+    status = [np.full((2, max(nq, 1)), 0 if fill is None else fill, np.uint8) if per[i] else None for i, nq in enumerate(nqs)]
+    some = any(per) or not isinstance(want_tables, bool)
+    rc = L.orbq_track_motion_model(handle, pool_handle, ptr(jobs), a.n_jobs, float(th), int(min_matches), int(check_ori), ptr(a.sigma), ptr(sf),
+                                   a.nlevels, ptr(a.out), table(a.ids), table(a.flags), table(assign) if some else None, table(status) if some else None)
+    # (the C side writes 2 * nq contiguous bytes: search 1's and then search 2's)
+    status = [None if s is None else s.reshape(-1)[:2 * nq].reshape(2, nq) for s, nq in zip(status, nqs)]
+    return rc, a.out[:len(a.ns)], _cut(a.ids, a.ns), _cut(a.flags, a.ns), _cut(assign, a.ns), status
+
+
+def track_motion_model(matcher, pool, jobs, inv_level_sigma2, scale_factors, th=15.0, min_matches=20, check_ori=True, want_tables=False):
+    """orbq_track_motion_model over job dicts (fs, cur_slot, last_slot, n, last_ids, velocity, last_Tcw, K): Tracking::TrackWithMotionModel
+    from the pose product to the loop behind PoseOptimization, the retry with 2 * th included.  One result dict per job: status (MM_TRACKED,
+    MM_TOO_FEW), Tcw_pred, n_search (2; -1 where the retry did not run), wide, assign and search_status (or None), and track_pose's fields;
+    the verdicts of Tracking.cc:971-977 are the caller's"""
+    rec, keep = pack_motion_jobs(jobs)
+    rc, out, ids, flags, assign, status = track_motion_model_raw(matcher._h, pool._h, rec, th, min_matches, check_ori, inv_level_sigma2, scale_factors,
+                                                                 want_tables=want_tables)
+    check(rc)
+    return [dict(_track_fields(out["track"], ids, flags, i), status=int(out["status"][i]), Tcw_pred=out["Tcw_pred"][i].reshape(4, 4).copy(),
+                 n_search=out["n_search"][i].copy(), wide=int(out["wide"][i]), assign=assign[i], search_status=status[i]) for i in range(len(jobs))]
+
+
+def debug_motion_arena(matcher, entries_per_job=-1):
+    """orbq_debug_motion_arena, for the overflow tests: sets the starting size of a job's share of the candidate arena (0: the default;
+    -1: leaves it) and returns how many times the last track_motion_model on the matcher ran its chain"""
+    L = lib()
+    runs = C.c_int(0)
+    check(L.orbq_debug_motion_arena(matcher._h, int(entries_per_job), C.byref(runs)))
     return runs.value
