@@ -1,7 +1,8 @@
 // Optimizer_hip.hpp -- the reference's Optimizer::PoseOptimization (include/Optimizer.h, src/Optimizer.cc:261-473 of both
 // scenarios), monocular, over the C ABI of liborbslamm_hip.so (orbo_*), and its Optimizer::OptimizeSim3
-// (src/Optimizer.cc:1348-1543; orbz_*; OptimizeSim3T, below PoseOptimizationT).  Header-only, C++11.  The rest of
-// Optimizer (the bundle adjustments, the essential graph) stays with g2o.
+// (src/Optimizer.cc:1348-1543; orbz_*; OptimizeSim3T, below PoseOptimizationT).  Header-only, C++11.  The two-keyframe bundle
+// adjustment of the initial map runs on the device as well (orbb_*; its drop-in is InitialMapT in Tracking_hip.hpp).  The rest of
+// Optimizer (the local and the global bundle adjustment, the essential graph) stays with g2o.
 //
 //   PoseOptimizationT<Frame, MapPoint>::Run(pFrame)
 //       the drop-in for Optimizer::PoseOptimization(pFrame): the reference's walk over mvpMapPoints on the host (:302-341:

@@ -51,6 +51,18 @@
 // applied from arguments.  Run composes UpdateLocalMapT::Run, SearchLocalPointsT::RunResident and Finish.  The counts come from the
 // device (the pool's observed bit): the pool's update rule keeps it equal to Observations() > 0.  A refusal throws with the frame's pose,
 // flags and points as the step before left them.
+//
+// And for Tracking::CreateInitialMapMonocular from its bundle adjustment on (:728-758), monocular, on orbb_initial_map
+// (include/orbslamm_initmap.h): GlobalBundleAdjustemnt over the two keyframes, the median depth, the verdict of :734 and
+// the rescaling in one device call.
+//
+//   iORB_SLAM::InitialMapT<KeyFrame, MapPoint>::Run(h, pKFini, pKFcur, pKFini->mnId == 0);          // Tracking.cc:728-758
+//
+// It flattens through the reference's members (GetPose, fx fy cx cy, mvKeysUn, mvInvLevelSigma2, mvScaleFactors, GetMapPointMatches,
+// GetIndexInKeyFrame, GetWorldPos), makes ONE device call, and writes back in the reference's order: SetPose of both keyframes, then per
+// point SetWorldPos and pMP->UpdateNormalAndDepth() (Optimizer.cc:214-258); with the verdict ORBB_OK the scaled SetPose of the current
+// keyframe and the scaled SetWorldPos of every point (:745-757).  It returns the verdict: any other than ORBB_OK is the caller's Reset()
+// (:737), which stays the caller's.  A refusal throws with nothing touched.
 #pragma once
 
 #include <algorithm>
@@ -58,6 +70,7 @@
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <unordered_set>
 #include <vector>
 
@@ -529,6 +542,73 @@ struct TrackReferenceKeyFrameT {
             pMP->mnLastFrameSeen = F.mnId;
         }
         res.ok = r.track.n_matches_map >= 10;   // :843
+        return res;
+    }
+};
+
+// Tracking::CreateInitialMapMonocular from its bundle adjustment on (:728-758)
+template <class KeyFrame, class MapPoint>
+struct InitialMapT {
+    struct Result { int verdict; float medianDepth, invMedianDepth; OrbbResult ba; };
+
+    static Result Run(orbm_t* h, KeyFrame* pKFini, KeyFrame* pKFcur, bool fixedFirst, int nIterations = 20, bool bRobust = true)
+    {
+        typedef typename std::decay<decltype(pKFini->GetPose())>::type Mat;
+        const Mat T1 = pKFini->GetPose(), T2 = pKFcur->GetPose();
+        OrbbProblem pr;
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) { pr.Tcw1[4 * r + c] = T1.template at<float>(r, c); pr.Tcw2[4 * r + c] = T2.template at<float>(r, c); }
+        pr.K[0] = pKFini->fx; pr.K[1] = pKFini->fy; pr.K[2] = pKFini->cx; pr.K[3] = pKFini->cy;
+        pr.fixed_first = fixedFirst ? 1 : 0; pr.fixed_second = 0; pr.iterations = nIterations; pr.robust = bRobust ? 1 : 0;
+        const std::vector<MapPoint*> vpMP = pKFini->GetMapPointMatches();   // :750: one point per matched feature of the initial frame
+        pr.n1 = (int)vpMP.size(); pr.n2 = (int)pKFcur->mvKeysUn.size();
+        std::vector<OrbxKeyPoint> keys[2];
+        KeyFrame* kfs[2] = {pKFini, pKFcur};
+        for (int s = 0; s < 2; s++) {
+            keys[s].resize(kfs[s]->mvKeysUn.size());
+            for (size_t i = 0; i < keys[s].size(); i++) {
+                OrbxKeyPoint k = {kfs[s]->mvKeysUn[i].pt.x, kfs[s]->mvKeysUn[i].pt.y, kfs[s]->mvKeysUn[i].size, kfs[s]->mvKeysUn[i].angle,
+                                  kfs[s]->mvKeysUn[i].response, kfs[s]->mvKeysUn[i].octave, kfs[s]->mvKeysUn[i].class_id};
+                keys[s][i] = k;
+            }
+        }
+        std::vector<int32_t> matches12(vpMP.size(), -1);
+        std::vector<float> P3D(3 * vpMP.size(), 0.f);
+        for (size_t i = 0; i < vpMP.size(); i++) {
+            MapPoint* pMP = vpMP[i];
+            if (!pMP || pMP->isBad()) continue;
+            matches12[i] = pMP->GetIndexInKeyFrame(pKFcur);
+            const Mat X = pMP->GetWorldPos();
+            for (int c = 0; c < 3; c++) P3D[3 * i + c] = X.template at<float>(c, 0);
+        }
+        std::vector<OrbbPoint> points(vpMP.size() ? vpMP.size() : 1);
+        const OrbxKeyPoint* k1 = keys[0].data();
+        const OrbxKeyPoint* k2 = keys[1].data();
+        const int32_t* m12 = matches12.data();
+        const float* p3d = P3D.data();
+        OrbbPoint* pts = points.data();
+        Result res;
+        detail::check(orbb_initial_map(h, &pr, 1, &k1, &k2, &m12, &p3d, pKFini->mvInvLevelSigma2.data(), pKFini->mvScaleFactors.data(),
+                               (int)pKFini->mvScaleFactors.size(), &res.ba, &pts), "InitialMap(HIP): ");
+        res.verdict = res.ba.verdict; res.medianDepth = res.ba.median_depth; res.invMedianDepth = res.ba.inv_median_depth;
+        // Optimizer.cc:214-258: the keyframes, then the points
+        const float last[4] = {0.f, 0.f, 0.f, 1.f};
+        float T[16];
+        for (int i = 0; i < 12; i++) T[i] = res.ba.Tcw1[i];
+        for (int i = 0; i < 4; i++) T[12 + i] = last[i];
+        pKFini->SetPose(detail::mat32f<Mat>(T, 4, 4));
+        for (int i = 0; i < 12; i++) T[i] = res.ba.Tcw2[i];
+        pKFcur->SetPose(detail::mat32f<Mat>(T, 4, 4));
+        for (size_t i = 0; i < vpMP.size(); i++) {
+            if (!points[i].matched) continue;
+            vpMP[i]->SetWorldPos(detail::mat32f<Mat>(points[i].pos, 3, 1));
+            vpMP[i]->UpdateNormalAndDepth();
+        }
+        if (res.verdict != ORBB_OK) return res;   // :734-739: the caller's Reset()
+        // :745-757
+        for (int i = 0; i < 12; i++) T[i] = res.ba.Tcw2_scaled[i];
+        pKFcur->SetPose(detail::mat32f<Mat>(T, 4, 4));
+        for (size_t i = 0; i < vpMP.size(); i++)
+            if (points[i].matched) vpMP[i]->SetWorldPos(detail::mat32f<Mat>(points[i].pos_scaled, 3, 1));
         return res;
     }
 };

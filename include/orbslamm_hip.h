@@ -1005,4 +1005,7 @@ int orbl_create_new_map_points_frames(orbm_t* h, orbm_frame_t* f1, const uint8_t
 /* LoopClosing::CorrectLoop's correction and MultiMapper::UpdatePosesAndAdd's over that store: the Sim3 propagated, the points
  * moved once, their normals and depths, the new poses and centres (orbe_correct_sim3, orbu_point_set_ref_kf): orbslamm_correct.h. */
 #include "orbslamm_correct.h"
+/* Tracking::CreateInitialMapMonocular from its bundle adjustment on: the two-keyframe Schur Levenberg, the median depth, the
+ * verdict and the rescaling (orbb_initial_map, orbb_initial_map_frames): orbslamm_initmap.h. */
+#include "orbslamm_initmap.h"
 #endif

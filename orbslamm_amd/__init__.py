@@ -11,6 +11,7 @@ from .local_mapping import compute_f12, create_new_map_points, fuse_batch, level
 from .loop_closing import search_and_fuse, decompose_sim3  # noqa: F401
 from .optimizer import pose_optimization, pose_optimization_batch  # noqa: F401
 from .optimizer import optimize_sim3, optimize_sim3_batch, sim3_from_rts  # noqa: F401
+from .initial_map import initial_map, initial_map_batch  # noqa: F401
 from .map_pool import KeyFrameStore, MapPool  # noqa: F401
 from .map_pool import REFRESH_DESCRIPTOR, REFRESH_DTYPE, REFRESH_MAX_OBS, REFRESH_NORMAL_DEPTH  # noqa: F401
 from .map_pool import CORRECT_KF_DTYPE, CORRECT_POINT_DTYPE  # noqa: F401

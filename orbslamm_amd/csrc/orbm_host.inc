@@ -85,7 +85,7 @@ enum OrbmSlot {
     S_TRI_K1, S_TRI_D1, S_TRI_K2, S_TRI_D2, S_TRI_ST1, S_TRI_I1, S_TRI_ST2, S_TRI_I2, /* orbm_search_for_triangulation | tri_core */
     S_TRI_S1, S_TRI_U1, S_TRI_S2, S_TRI_U2, S_TRI_PA, S_TRI_PB, S_TRI_M12, S_TRI_BIN, S_TRI_NMATCH,
     S_UND_IN, S_UND_OUT, S_RGBD_KEYS, S_RGBD_KEYSUN, S_RGBD_DEPTH, S_RGBD_OUT, S_DIS_DESC, S_DIS_START, S_DIS_BEST,   // orbm_undistort_keypoints, _compute_stereo_from_rgbd, _distinctive_descriptors
-    S_BLOCK,                                                // THE ONE SHARED NAME: the packed block of orbl_core, orbl_fuse_core, orbc_core, orbo_core, orbw_project_sync, orby_compute_sim3, orbq_relocalize and orbq_track_motion_model, which never nest
+    S_BLOCK,                                                // THE ONE SHARED NAME: the packed block of orbl_core, orbl_fuse_core, orbc_core, orbo_core, orbw_project_sync, orby_compute_sim3, orbq_relocalize, orbq_track_motion_model and orbb_core, which never nest
     S_LF_PAIR, S_LF_TILES, S_LF_HITS, S_LF_STATUS,          // orbc_core besides S_BLOCK
     S_RELOC_ARENA,                                          // orbq_relocalize besides S_BLOCK: the searches' candidate arena, a share a job
     S_MOTION_ARENA,                                         // orbq_track_motion_model besides S_BLOCK: the same

@@ -60,6 +60,8 @@
 #include "orbq_motion_kernels.hip"  // TrackWithMotionModel: the pose product, the retry decision and the solve as a stage kernel, the frame/frame projection from the device-made pose
 #include "orbr_kernels.hip"   // the map-point refresh: ComputeDistinctiveDescriptors and UpdateNormalAndDepth over the store, into the pool
 #include "orbe_kernels.hip"   // the loop correction: the Sim3 propagated, the points moved once, orbr's normals with mixed centres, the commit
+#include "orbg_schur.hip"    // the g2o pieces of a bundle adjustment with marginalised points: the two-vertex edge, the Schur share, the reduced LDLt, Levenberg over the full system
+#include "orbb_kernels.hip"   // the initial map: the two-keyframe bundle adjustment on orbg_schur's pieces, the median depth, the verdict, the rescaling
 #include "orby_kernels.hip"   // ComputeSim3 behind the solver: SearchBySim3's two passes, the agreement, OptimizeSim3's walk, orbz's solve
 
 using namespace orbx;
@@ -227,4 +229,5 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbq_host.inc"   // PoseOptimization behind the pool searches: TrackWithMotionModel's and TrackLocalMap's verdicts
 #include "orbq_reloc_host.inc"   // Relocalization behind PnPsolver::iterate: three solves and two keyframe projections per candidate
 #include "orbq_motion_host.inc"  // TrackWithMotionModel from the predicted pose to the counts: both searches, the gate, the solve and the loop in one call
+#include "orbb_host.inc"   // CreateInitialMapMonocular from its bundle adjustment on: two poses and their shared points per problem
 #include "orby_host.inc"   // SearchBySim3 and OptimizeSim3 from the pool, the store and the frame set: ComputeSim3's verdict per candidate
