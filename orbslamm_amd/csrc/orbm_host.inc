@@ -85,7 +85,7 @@ enum OrbmSlot {
     S_TRI_K1, S_TRI_D1, S_TRI_K2, S_TRI_D2, S_TRI_ST1, S_TRI_I1, S_TRI_ST2, S_TRI_I2, /* orbm_search_for_triangulation | tri_core */
     S_TRI_S1, S_TRI_U1, S_TRI_S2, S_TRI_U2, S_TRI_PA, S_TRI_PB, S_TRI_M12, S_TRI_BIN, S_TRI_NMATCH,
     S_UND_IN, S_UND_OUT, S_RGBD_KEYS, S_RGBD_KEYSUN, S_RGBD_DEPTH, S_RGBD_OUT, S_DIS_DESC, S_DIS_START, S_DIS_BEST,   // orbm_undistort_keypoints, _compute_stereo_from_rgbd, _distinctive_descriptors
-    S_BLOCK,                                                // THE ONE SHARED NAME: the packed block of orbl_core, orbl_fuse_core, orbc_core, orbo_core, orbw_project_sync, orby_compute_sim3, orbq_relocalize, orbq_track_motion_model and orbb_core, which never nest
+    S_BLOCK,                                                // THE ONE SHARED NAME: the packed block of orbl_core, orbl_fuse_core, orbc_core, orbo_core, orbw_project_sync, orby_compute_sim3, orbq_track_pose, orbq_track_reference, orbq_relocalize, orbq_track_motion_model and orbb_core, which never nest
     S_LF_PAIR, S_LF_TILES, S_LF_HITS, S_LF_STATUS,          // orbc_core besides S_BLOCK
     S_RELOC_ARENA,                                          // orbq_relocalize besides S_BLOCK: the searches' candidate arena, a share a job
     S_MOTION_ARENA,                                         // orbq_track_motion_model besides S_BLOCK: the same
@@ -107,9 +107,10 @@ struct orbm_handle {
     int32_t stageSeq = 0;
     size_t ldsAttr[8] = {0};             // hipFuncAttributeMaxDynamicSharedMemorySize already raised for kernel i
     int lastRounds = 0, lastCands = 0;   // of the last projection search (orbm_last_search_stats)
-    int relocArena = 0;                  // orbq_relocalize: entries of a job's share of S_RELOC_ARENA (0: the default); grown by an overflow, set by orbq_debug_reloc_arena
-    int relocRuns = 0;                   // ... and how many times its last call ran the chain (orbq_debug_reloc_arena reports it)
-    int motionArena = 0, motionRuns = 0; // orbq_track_motion_model: the same two for S_MOTION_ARENA (orbq_debug_motion_arena)
+    // a chain's candidate arena (orbq_scaffold.inc): entries of a job's share (0: the entry's default), grown by an overflow and set by the
+    // entry's orbq_debug_*_arena, and how many times the entry's last call ran its chain
+    struct CandArena { int entries = 0, runs = 0; };
+    CandArena relocArena, motionArena;   // orbq_relocalize's S_RELOC_ARENA, orbq_track_motion_model's S_MOTION_ARENA
     // orbm_projection_prepare: the train side of the NEXT orbm_search_by_projection, already in HBM with its grid built
     // (identified by the caller's pointers, count and grid: the search falls back to its own upload when they differ)
     struct Prepared { bool valid = false, inFlight = false; const void* keys = nullptr; const void* desc = nullptr; int nt = 0; OrbmGrid grid{}; uint64_t seq = 0; } prep;

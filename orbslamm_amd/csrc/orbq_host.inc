@@ -2,32 +2,20 @@
 // orbq_kernels.hip, ABI: include/orbslamm_trackpose.h, DESIGN.md §8s).  One call = the checks, one packed upload (job records |
 // the frames' ids before the search), ONE launch for all jobs on the handle's stream, one copy down (results | ids | outlier
 // bytes), one synchronise.  The searches' tables and ids are read where the searches left them: nothing per match goes up.
-// The pool's and the store's checks, the id and slot checkers, the reader mark: orbx_poolutil.inc.  orbq_track_reference (below)
-// repeats this entry's frame: a shared scaffold came out no shorter (docs/experiments.md).
+// The pool's and the store's checks, the id and slot checkers, the reader mark: orbx_poolutil.inc.  What this entry shares with
+// orbq_track_reference (below), orbq_relocalize and orbq_track_motion_model: orbq_scaffold.inc.
 
 static_assert(sizeof(OrbqJob) == 112 && sizeof(OrbqResult) == 184, "orbslamm_trackpose.h layouts");
 static_assert(ORBW_FLAG_OBSERVED == 2, "k_track_pose reads the observed bit");
 static_assert(sizeof(orbq::JobDev) == 136 && sizeof(orbo::FrameIn) == 104, "the per-frame upload sizes tools/trackpose_bench.py computes with");
 
-// what needs neither a handle nor a GPU.  Zero jobs are settled by the caller before this
-static int orbq_check_args(const OrbqJob* jobs, int n_jobs, const float* inv_level_sigma2, int nlevels, const OrbqResult* out,
-                           int32_t* const* ids_out, uint8_t* const* outlier_out)
+// this entry's own argument checks, behind the shared ones
+static int orbq_check_args(const OrbqJob* jobs, int n_jobs)
 {
-    if (n_jobs < 0) return fail(ORBX_E_INVALID, "negative job count");
-    if (n_jobs > ORBO_MAX_FRAMES) return fail(ORBX_E_UNSUPPORTED, "%d jobs: above %d", n_jobs, ORBO_MAX_FRAMES);
-    if (!jobs || !out || !ids_out || !outlier_out) return fail(ORBX_E_INVALID, "null argument");
-    if (!inv_level_sigma2 || nlevels < 1 || nlevels > ORBX_MAX_LEVELS) return fail(ORBX_E_INVALID, "nlevels %d outside [1, %d] or no sigma table", nlevels, ORBX_MAX_LEVELS);
-    int64_t total = 0;
     for (int j = 0; j < n_jobs; j++) {
         const OrbqJob& J = jobs[j];
-        if (!J.fs) return fail(ORBX_E_INVALID, "job %d: null frame set", j);
-        if (J.n < 0) return fail(ORBX_E_INVALID, "job %d: negative feature count", j);
-        if (J.n > ORBO_MAX_EDGES) return fail(ORBX_E_UNSUPPORTED, "job %d: %d features: above %d", j, J.n, ORBO_MAX_EDGES);
         if (J.back < -1 || J.back >= ResultRing::kSets) return fail(ORBX_E_INVALID, "job %d: back %d outside [-1, %d]", j, J.back, ResultRing::kSets - 1);
         if (J.discard != 0 && J.discard != 1) return fail(ORBX_E_INVALID, "job %d: discard is 0 or 1", j);
-        if (J.n && (!ids_out[j] || !outlier_out[j])) return fail(ORBX_E_INVALID, "job %d: null output array", j);
-        total += J.n;
-        if (total > ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "more than %d features in one call (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
     }
     return ORBX_OK;
 }
@@ -62,13 +50,15 @@ extern "C" int orbq_track_pose(orbm_t* h, orbw_pool_t* pool, const OrbqJob* jobs
                                OrbqResult* out, int32_t* const* ids_out, uint8_t* const* outlier_out)
 {
     if (n_jobs == 0) return ORBX_OK;   // nothing to do: no argument is read, no handle needed
-    int rc = orbq_check_args(jobs, n_jobs, inv_level_sigma2, nlevels, out, ids_out, outlier_out);
-    if (rc) return rc;
+    int rc = orbq_check_shared(jobs, n_jobs, out, ids_out, outlier_out, inv_level_sigma2 != nullptr, nlevels, "no sigma table", "null output array");
+    if (rc || (rc = orbq_check_args(jobs, n_jobs))) return rc;
     if ((rc = orbm_check(h)) || (rc = orbw_pool_check(pool))) return rc;
     if (pool->h->device != h->device) return fail(ORBX_E_INVALID, "the pool and the handle must share the device");
     size_t total = 0, nBase = 0;
     for (int j = 0; j < n_jobs; j++) {
         const OrbqJob& J = jobs[j];
+        // (this entry's own text, not orbq_check_frameset, and its own tail below: with the shared ones the many-job rows of
+        // tools/trackpose_bench.py left the parent's band, docs/experiments.md)
         if ((rc = frameset_check(J.fs))) return rc;
         if (J.fs->owner != h) return fail(ORBX_E_INVALID, "job %d: the frame set belongs to another handle", j);
         if (J.slot < 0 || J.slot >= J.fs->slots) return fail(ORBX_E_INVALID, "job %d: slot %d outside the frame set", j, J.slot);
@@ -107,19 +97,17 @@ extern "C" int orbq_track_pose(orbm_t* h, orbw_pool_t* pool, const OrbqJob* jobs
         if (J.base_ids) b0 += (size_t)J.n;
     }
     orbq::Args a{};
-    a.o.pw = (float4*)(d + oPw); a.o.uv = (float2*)(d + oUv); a.o.outlier = d + oFlags;
-    for (int lv = 0; lv < ORBX_MAX_LEVELS; lv++) a.o.invSigma2[lv] = lv < nlevels ? inv_level_sigma2[lv] : 0.f;
-    a.o.nlevels = nlevels;
+    orbq_fill_solver(a, pool, d, oPw, oUv, oFlags, oMerged, oIds, oOutl, inv_level_sigma2, nlevels);
     a.jobs = (const orbq::JobDev*)(d + oJobs);
-    a.pool = pool->dev;
-    a.merged = (int32_t*)(d + oMerged); a.idsOut = (int32_t*)(d + oIds); a.outlierOut = d + oOutl; a.out = (OrbqResult*)(d + oOut);
+    a.out = (OrbqResult*)(d + oOut);
     hipStream_t s = h->stream;
     HIPCHK(hipMemcpyAsync(d, hs, upBytes, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(d + oOut, 0, (size_t)n_jobs * sizeof(OrbqResult), s));   // (the records' padding word too: the same bytes every call)
     hipLaunchKernelGGL(orbq::k_track_pose, dim3((unsigned)n_jobs), dim3(orbq::kLanes), 0, s, a, n_jobs);
-    HIPCHK(hipGetLastError());
-    if ((rc = orbw_mark_reader(pool, s))) return rc;
-    HIPCHK(hipMemcpyAsync(hs, d + oOut, downBytes, hipMemcpyDeviceToHost, s));
+    // (an error from here on: the kernel in flight reads the pool, so the stream is drained before the mutex is let go)
+    HIPCHK_OR(hipGetLastError(), (void)hipStreamSynchronize(s));
+    if ((rc = orbw_mark_reader(pool, s))) { (void)hipStreamSynchronize(s); return rc; }
+    HIPCHK_OR(hipMemcpyAsync(hs, d + oOut, downBytes, hipMemcpyDeviceToHost, s), (void)hipStreamSynchronize(s));
     HIPCHK(hipStreamSynchronize(s));
     const OrbqResult* hr = (const OrbqResult*)hs;
     for (int j = 0; j < n_jobs; j++)
@@ -142,29 +130,18 @@ extern "C" int orbq_track_pose(orbm_t* h, orbw_pool_t* pool, const OrbqJob* jobs
 // (results | ids | outlier bytes | the match tables asked for), one synchronise.
 
 static_assert(sizeof(OrbqRefJob) == 112 && sizeof(OrbqRefResult) == 192, "orbslamm_trackpose.h layouts");
+static_assert(offsetof(OrbqRefResult, track) == 0 && offsetof(OrbqResult, opt) == 0, "orbq_drain reads rounds from the OrboResult at a record's head");
 static_assert(ORBW_FLAG_BAD == 1, "k_ref_valid reads the bad bit");
 static_assert(sizeof(orbq::RefJobDev) == 152, "the per-job upload size tools/trackref_bench.py computes with");
 
-// what needs neither a handle nor a GPU.  Zero jobs are settled by the caller before this
-static int orbq_ref_check_args(const void* h, const void* pool, const void* store, const OrbqRefJob* jobs, int n_jobs, int min_matches,
-                               const float* inv_level_sigma2, int nlevels, const OrbqRefResult* out, int32_t* const* ids_out, uint8_t* const* outlier_out)
+// this entry's own argument checks, behind the shared ones
+static int orbq_ref_check_args(const void* h, const void* pool, const void* store, const OrbqRefJob* jobs, int n_jobs, int min_matches)
 {
-    if (n_jobs < 0) return fail(ORBX_E_INVALID, "negative job count");
-    if (n_jobs > ORBO_MAX_FRAMES) return fail(ORBX_E_UNSUPPORTED, "%d jobs: above %d", n_jobs, ORBO_MAX_FRAMES);
-    if (!jobs || !out || !ids_out || !outlier_out) return fail(ORBX_E_INVALID, "null argument");
-    if (!inv_level_sigma2 || nlevels < 1 || nlevels > ORBX_MAX_LEVELS) return fail(ORBX_E_INVALID, "nlevels %d outside [1, %d] or no sigma table", nlevels, ORBX_MAX_LEVELS);
     if (min_matches < 0) return fail(ORBX_E_INVALID, "min_matches %d is negative", min_matches);
-    int64_t total = 0;
     for (int j = 0; j < n_jobs; j++) {
         const OrbqRefJob& J = jobs[j];
-        if (!J.fs) return fail(ORBX_E_INVALID, "job %d: null frame set", j);
-        if (J.n < 0) return fail(ORBX_E_INVALID, "job %d: negative feature count", j);
-        if (J.n > ORBO_MAX_EDGES) return fail(ORBX_E_UNSUPPORTED, "job %d: %d features: above %d", j, J.n, ORBO_MAX_EDGES);
         if (J.solve != 0 && J.solve != 1) return fail(ORBX_E_INVALID, "job %d: solve is 0 or 1", j);
         if (J.kf_slot < 0 || J.slot < 0 || J.kf < 0) return fail(ORBX_E_INVALID, "job %d: negative slot", j);
-        if (J.n && (!ids_out[j] || !outlier_out[j])) return fail(ORBX_E_INVALID, "job %d: null output array", j);
-        total += J.n;
-        if (total > ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "more than %d features in one call (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
     }
     if (!h || !pool || !store) return fail(ORBX_E_INVALID, "null handle, pool or store");
     return ORBX_OK;
@@ -175,25 +152,17 @@ extern "C" int orbq_track_reference(orbm_t* h, orbw_pool_t* pool, orbu_store_t* 
                                     OrbqRefResult* out, int32_t* const* ids_out, uint8_t* const* outlier_out, int32_t* const* match_out)
 {
     if (n_jobs == 0) return ORBX_OK;   // nothing to do: no argument is read, no handle needed
-    int rc = orbq_ref_check_args(h, pool, store, jobs, n_jobs, min_matches, inv_level_sigma2, nlevels, out, ids_out, outlier_out);
-    if (rc) return rc;
+    int rc = orbq_check_shared(jobs, n_jobs, out, ids_out, outlier_out, inv_level_sigma2 != nullptr, nlevels, "no sigma table", "null output array");
+    if (rc || (rc = orbq_ref_check_args(h, pool, store, jobs, n_jobs, min_matches))) return rc;
     if ((rc = orbm_check(h)) || (rc = orbw_pool_check(pool)) || (rc = orbu_store_check(store))) return rc;
     if (pool->h->device != h->device) return fail(ORBX_E_INVALID, "the pool and the handle must share the device");
     if (store->pool != pool) return fail(ORBX_E_INVALID, "the store stands beside another pool");
     size_t total = 0, sumCap = 0, nAsked = 0;
     for (int j = 0; j < n_jobs; j++) {
         const OrbqRefJob& J = jobs[j];
-        if ((rc = frameset_check(J.fs))) return rc;
-        if (J.fs->owner != h) return fail(ORBX_E_INVALID, "job %d: the frame set belongs to another handle", j);
-        if (J.slot >= J.fs->slots || J.kf_slot >= J.fs->slots) return fail(ORBX_E_INVALID, "job %d: slot %d or %d outside the frame set", j, J.kf_slot, J.slot);
-        if (J.n > J.fs->cap) return fail(ORBX_E_INVALID, "job %d: %d features for a frame of at most %d", j, J.n, J.fs->cap);
-        sumCap += (size_t)J.fs->cap;
-        // (the search's scratch is 11 bytes a feature of the set's CAP, whatever n is: bounded like the features)
-        if (sumCap > (size_t)ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "the jobs' frame sets hold more than %d features together (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
+        if ((rc = orbq_check_frameset(h, J.fs, j, J.kf_slot, J.slot, J.n, /* no second count */ -1, sumCap))) return rc;
         if (!J.fs->bow || !J.fs->bow->computed) return fail(ORBX_E_INVALID, "job %d: orbm_frameset_compute_bow has not run", j);
         if ((rc = orbu_check_slot(store, "kf of job", j, J.kf, false))) return rc;   // (kfcap never changes; the set byte: under the mutex, below)
-        // (a set that builds on a stream of its own: the slots' builds may still run there)
-        if (fs_stream(J.fs) != h->stream) HIPCHK(hipStreamSynchronize(fs_stream(J.fs)));
         total += (size_t)J.n;
         if (match_out && match_out[j]) nAsked += (size_t)J.n;
     }
@@ -232,11 +201,7 @@ extern "C" int orbq_track_reference(orbm_t* h, orbw_pool_t* pool, orbu_store_t* 
         maxCap = std::max(maxCap, J.fs->cap);
     }
     orbq::RefArgs a{};
-    a.q.o.pw = (float4*)(d + oPw); a.q.o.uv = (float2*)(d + oUv); a.q.o.outlier = d + oFlags;
-    for (int lv = 0; lv < ORBX_MAX_LEVELS; lv++) a.q.o.invSigma2[lv] = lv < nlevels ? inv_level_sigma2[lv] : 0.f;
-    a.q.o.nlevels = nlevels;
-    a.q.pool = pool->dev;
-    a.q.merged = (int32_t*)(d + oMerged); a.q.idsOut = (int32_t*)(d + oIds); a.q.outlierOut = d + oOutl;
+    orbq_fill_solver(a.q, pool, d, oPw, oUv, oFlags, oMerged, oIds, oOutl, inv_level_sigma2, nlevels);
     a.jobs = (const orbq::RefJobDev*)(d + oJobs);
     a.out = (OrbqRefResult*)(d + oOut);
     a.matchOut = (int32_t*)(d + oMatch);
@@ -266,24 +231,14 @@ extern "C" int orbq_track_reference(orbm_t* h, orbw_pool_t* pool, orbu_store_t* 
         j0 += nb;
     }
     hipLaunchKernelGGL(orbq::k_track_reference, dim3((unsigned)n_jobs), dim3(orbq::kLanes), 0, s, a, n_jobs);
-    HIPCHK(hipGetLastError());
-    if ((rc = orbw_mark_reader(pool, s))) return rc;
-    HIPCHK(hipMemcpyAsync(hs, d + oOut, downBytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const OrbqRefResult* hr = (const OrbqRefResult*)hs;
-    for (int j = 0; j < n_jobs; j++)
-        if (hr[j].track.opt.rounds < 0)
-            return fail(ORBX_E_INVALID, "job %d: an edge's octave lies outside [0, %d), or a feature at or above the slot's device count (or a match without a point of the pool) holds a point",
-                        j, nlevels);
-    memcpy(out, hr, (size_t)n_jobs * sizeof(OrbqRefResult));
-    f0 = 0; m0 = 0;
-    for (int j = 0; j < n_jobs; j++) {
+    if ((rc = orbq_drain("orbq_track_reference", pool, s, hs, d + oOut, downBytes, hs, sizeof(OrbqRefResult), n_jobs, nlevels, " (or a match without a point of the pool)"))) return rc;
+    orbq_hand_back(jobs, n_jobs, out, hs, sizeof(OrbqRefResult), hs + (oIds - oOut), hs + (oOutl - oOut), ids_out, outlier_out);
+    m0 = 0;
+    for (int j = 0; j < n_jobs; j++) {   // the match tables asked for
         const size_t n = (size_t)jobs[j].n;
-        const bool asked = match_out && match_out[j];
-        if (n) { memcpy(ids_out[j], hs + (oIds - oOut) + f0 * 4, n * 4); memcpy(outlier_out[j], hs + (oOutl - oOut) + f0, n); }
-        if (n && asked) memcpy(match_out[j], hs + (oMatch - oOut) + m0 * 4, n * 4);
-        f0 += n;
-        if (asked) m0 += n;
+        if (!match_out || !match_out[j]) continue;
+        if (n) memcpy(match_out[j], hs + (oMatch - oOut) + m0 * 4, n * 4);
+        m0 += n;
     }
     return ORBX_OK;
 }

@@ -7,7 +7,7 @@
 //              Optimizer.cc:302-341); Xw from the pool record, the observation from the resident mvKeysUn
 //   solve      orbo::solve_frame, the body of k_pose_optimize
 //   epilogue   per feature: mvbOutlier, the frame's ids after the discard loop, the two counts
-// The prologue (merge_and_gather) and the epilogue (loop_behind_solve) are device functions over an id SOURCE: k_track_pose's is a
+// The prologue (merge_and_gather) and the epilogue (loop_behind_solve, or leave_unsolved where a gate said no) are device functions over an id SOURCE: k_track_pose's is a
 // pool search's table, k_track_reference's (Tracking::TrackReferenceKeyFrame) SearchByBoW's table over the keyframe
 // store's entries row.
 // The prologue writes edge e from the lane of its FEATURE (t % 64); the solve reads it from lane e % 64, and the epilogue reads an
@@ -173,6 +173,24 @@ __device__ __forceinline__ void loop_behind_solve(const Args& a, int n, int f0, 
     if (lane == 0) { out->n_matches = nMatch; out->n_matches_map = nMap; }
 }
 
+// The gate said no (k_track_reference, k_motion_stage: wave-uniform): the reference returns before it touches the frame.  The pose as
+// it came, no round (-1: the merge met something the host refuses), the table's ids as they merged, no outlier
+__device__ __forceinline__ void leave_unsolved(const Args& a, int n, int f0, int lane, bool anyBad, const float* Tcw, int nMatches, OrbqResult* out)
+{
+    if (lane == 0) {
+        for (int i = 0; i < 16; i++) out->opt.Tcw[i] = Tcw[i];
+        out->opt.rounds = anyBad ? -1 : 0;
+        out->n_matches = nMatches; out->n_matches_map = 0;
+    }
+    if (anyBad) return;
+    for (int t = lane; t < n; t += kLanes) { a.idsOut[f0 + t] = a.merged[f0 + t]; a.outlierOut[f0 + t] = 0; }
+}
+
+// The overflow protocol of the chains that search through a candidate arena (k_reloc_stage, k_motion_stage): a search's count nm below
+// 0 says its share was too small and holds -(entries needed) - 1.  One lane of the job writes the need and stops the job in `overflow`;
+// the host grows the arena to the largest need and runs the whole call again
+__device__ __forceinline__ void report_overflow(int nm, int32_t* need, int32_t* state, int32_t overflow) { *need = -nm - 1; *state = overflow; }
+
 __global__ __launch_bounds__(kLanes) void k_track_pose(Args a, int nJobs)
 {
     __shared__ orbg::LmShared<6> sLm;
@@ -259,17 +277,7 @@ __global__ __launch_bounds__(kLanes) void k_track_reference(RefArgs r, int nJobs
     const bool anyBad = __any(bad);
     if (lane == 0) { out->n_bow = nBow; out->status = gate ? ORBQ_REF_TOO_FEW : J.solve ? ORBQ_REF_TRACKED : ORBQ_REF_SEARCH_ONLY; }
     __syncthreads();
-    if (!solve) {
-        // the reference returns before it touches the frame: the pose as it came, no round, the table's ids as they merged
-        if (lane == 0) {
-            for (int i = 0; i < 16; i++) out->track.opt.Tcw[i] = J.Tcw[i];
-            out->track.opt.rounds = anyBad ? -1 : 0;
-            out->track.n_matches = nBow; out->track.n_matches_map = 0;
-        }
-        if (anyBad) return;
-        for (int t = lane; t < n; t += kLanes) { a.idsOut[f0 + t] = a.merged[f0 + t]; a.outlierOut[f0 + t] = 0; }
-        return;
-    }
+    if (!solve) { leave_unsolved(a, n, f0, lane, anyBad, J.Tcw, nBow, &out->track); return; }
     orbo::solve_frame(a.o, J.Tcw, J.K, f0, nEdges, anyBad, &out->track.opt, sLm, lane);
     __syncthreads();
     if (anyBad) return;

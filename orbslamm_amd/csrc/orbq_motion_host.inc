@@ -6,42 +6,23 @@
 // the largest need and the whole call runs again, at most twice.
 
 static_assert(sizeof(OrbqMotionJob) == 176 && sizeof(OrbqMotionResult) == 264, "orbslamm_motion.h layouts");
+static_assert(offsetof(OrbqMotionResult, track) == 0, "orbq_drain reads rounds from the OrboResult at a record's head");
 static_assert(sizeof(orbq::MotionJobDev) == 288, "the per-job upload size DESIGN.md section 8z states");
 static_assert(ORBQ_MM_TRACKED == orbq::MM_TRACKED && ORBQ_MM_TOO_FEW == orbq::MM_TOO_FEW && ORBQ_MM_ST_NOT_RUN == orbq::kMotionNotRun, "orbq motion codes");
 
-extern "C" int orbq_debug_motion_arena(orbm_t* h, int entries_per_job, int* last_runs)
-{
-    if (entries_per_job < -1 || entries_per_job > kRelocArenaMax) return fail(ORBX_E_INVALID, "%d entries a job outside [-1, %d]", entries_per_job, kRelocArenaMax);
-    int rc = orbm_check(h);
-    if (rc) return rc;
-    if (entries_per_job >= 0) h->motionArena = entries_per_job;
-    if (last_runs) *last_runs = h->motionRuns;
-    return ORBX_OK;
-}
+extern "C" int orbq_debug_motion_arena(orbm_t* h, int entries_per_job, int* last_runs) { return orbq_debug_arena(h, &orbm_handle::motionArena, entries_per_job, last_runs); }
 
-// what needs neither a handle nor a GPU.  Zero jobs are settled by the caller before this
-static int orbq_motion_check_args(const void* h, const void* pool, const OrbqMotionJob* jobs, int n_jobs, float th, int min_matches, int check_ori,
-                                  const float* inv_level_sigma2, const float* scale_factors, int nlevels, const OrbqMotionResult* out,
-                                  int32_t* const* ids_out, uint8_t* const* outlier_out)
+// this entry's own argument checks, behind the shared ones
+static int orbq_motion_check_args(const void* h, const void* pool, const OrbqMotionJob* jobs, int n_jobs, float th, int min_matches, int check_ori)
 {
-    if (n_jobs < 0) return fail(ORBX_E_INVALID, "negative job count");
-    if (n_jobs > ORBO_MAX_FRAMES) return fail(ORBX_E_UNSUPPORTED, "%d jobs: above %d", n_jobs, ORBO_MAX_FRAMES);
-    if (!jobs || !out || !ids_out || !outlier_out) return fail(ORBX_E_INVALID, "null argument");
     if (check_ori != 0 && check_ori != 1) return fail(ORBX_E_INVALID, "check_ori is 0 or 1");
     if (min_matches < 0) return fail(ORBX_E_INVALID, "negative min_matches");
     if (!std::isfinite(th) || !(th > 0.f)) return fail(ORBX_E_INVALID, "th must be finite and above 0");
-    if (!inv_level_sigma2 || !scale_factors || nlevels < 1 || nlevels > ORBX_MAX_LEVELS)
-        return fail(ORBX_E_INVALID, "nlevels %d outside [1, %d] or no level table", nlevels, ORBX_MAX_LEVELS);
-    int64_t total = 0;
     for (int j = 0; j < n_jobs; j++) {
         const OrbqMotionJob& J = jobs[j];
-        if (!J.fs) return fail(ORBX_E_INVALID, "job %d: null frame set", j);
-        if (J.n < 0 || J.nq < 0) return fail(ORBX_E_INVALID, "job %d: negative feature count", j);
-        if (J.n > ORBO_MAX_EDGES) return fail(ORBX_E_UNSUPPORTED, "job %d: %d features: above %d", j, J.n, ORBO_MAX_EDGES);
+        if (J.nq < 0) return fail(ORBX_E_INVALID, "job %d: negative feature count", j);
         if (J.cur_slot < 0 || J.last_slot < 0) return fail(ORBX_E_INVALID, "job %d: negative slot", j);
-        if ((J.nq && !J.last_ids) || (J.n && (!ids_out[j] || !outlier_out[j]))) return fail(ORBX_E_INVALID, "job %d: null array", j);
-        total += J.n;
-        if (total > ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "more than %d features in one call (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
+        if (J.nq && !J.last_ids) return fail(ORBX_E_INVALID, "job %d: null array", j);
     }
     if (!h || !pool) return fail(ORBX_E_INVALID, "null handle or pool");
     return ORBX_OK;
@@ -53,8 +34,8 @@ extern "C" int orbq_track_motion_model(orbm_t* h, orbw_pool_t* pool, const OrbqM
                                        int32_t* const* assign_out, uint8_t* const* status_out)
 {
     if (n_jobs == 0) return ORBX_OK;   // nothing to do: no argument is read, no handle needed
-    int rc = orbq_motion_check_args(h, pool, jobs, n_jobs, th, min_matches, check_ori, inv_level_sigma2, scale_factors, nlevels, out, ids_out, outlier_out);
-    if (rc) return rc;
+    int rc = orbq_check_shared(jobs, n_jobs, out, ids_out, outlier_out, inv_level_sigma2 && scale_factors, nlevels, "no level table", "null array");
+    if (rc || (rc = orbq_motion_check_args(h, pool, jobs, n_jobs, th, min_matches, check_ori))) return rc;
     if ((rc = orbm_check(h)) || (rc = orbw_pool_check(pool))) return rc;
     if (pool->h->device != h->device) return fail(ORBX_E_INVALID, "the pool and the handle must share the device");
     const size_t nj = (size_t)n_jobs;
@@ -62,14 +43,7 @@ extern "C" int orbq_track_motion_model(orbm_t* h, orbw_pool_t* pool, const OrbqM
     int maxCap = 0, maxCell = 0, maxNq = 0;
     for (int j = 0; j < n_jobs; j++) {
         const OrbqMotionJob& J = jobs[j];
-        if ((rc = frameset_check(J.fs))) return rc;
-        if (J.fs->owner != h) return fail(ORBX_E_INVALID, "job %d: the frame set belongs to another handle", j);
-        if (J.cur_slot >= J.fs->slots || J.last_slot >= J.fs->slots) return fail(ORBX_E_INVALID, "job %d: slot %d or %d outside the frame set", j, J.cur_slot, J.last_slot);
-        if (J.n > J.fs->cap || J.nq > J.fs->cap) return fail(ORBX_E_INVALID, "job %d: %d and %d features for frames of at most %d", j, J.n, J.nq, J.fs->cap);
-        sumCap += (size_t)J.fs->cap;
-        if (sumCap > (size_t)ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "the jobs' frame sets hold more than %d features together (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
-        // (a set that builds on a stream of its own: the slots' builds may still run there)
-        if (fs_stream(J.fs) != h->stream) HIPCHK(hipStreamSynchronize(fs_stream(J.fs)));
+        if ((rc = orbq_check_frameset(h, J.fs, j, J.cur_slot, J.last_slot, J.n, J.nq, sumCap))) return rc;
         total += (size_t)J.n; totalQ += (size_t)J.nq;
         maxCap = std::max(maxCap, J.fs->cap); maxCell = std::max(maxCell, J.fs->ncell); maxNq = std::max(maxNq, J.nq);
     }
@@ -77,8 +51,7 @@ extern "C" int orbq_track_motion_model(orbm_t* h, orbw_pool_t* pool, const OrbqM
     if ((rc = proj_lds_plan(maxCap, maxNq, maxCell, pl))) return rc;
     orbt::ProjCommon& c = pl.c;
     c.mode = 4; c.nnratio = 0.9f; c.checkOri = check_ori; c.thDist = 100;   // ORBmatcher.cc:1420 TH_HIGH; mode 4 has no ratio test
-    c.scale = nullptr; c.nlevels = 1; c.interleave = 0;
-    if (!c.big) c.lanes = cand_lanes(n_jobs);
+    proj_plan_queries(c, n_jobs);
     Packer pk;
     const size_t oJobs = pk.take(nj * sizeof(orbq::MotionJobDev)), oIdsIn = pk.take(totalQ * 4), upBytes = pk.off;
     // cleared to 0xff in one piece: both searches' tables (-1) | the status bytes (ORBQ_MM_ST_NOT_RUN).  What goes down starts at the
@@ -99,9 +72,8 @@ extern "C" int orbq_track_motion_model(orbm_t* h, orbw_pool_t* pool, const OrbqM
         if ((rc = orbw_check_ids(pool, "last_ids", jobs[j].last_ids, jobs[j].nq, true))) return fail(rc, "job %d: %s", j, std::string(g_err).c_str());
     hipStream_t s = h->stream;
     for (int attempt = 0;; attempt++) {
-        h->motionRuns = attempt + 1;
-        const size_t arena = h->motionArena > 0 ? (size_t)h->motionArena : std::max<size_t>(16 * (size_t)maxNq, 2048);
-        if ((rc = orbm_reserve(h, S_MOTION_ARENA, nj * arena * sizeof(uint2)))) return rc;
+        size_t arena;
+        if ((rc = orbq_arena_reserve(h, h->motionArena, S_MOTION_ARENA, attempt, nj, std::max<size_t>(16 * (size_t)maxNq, 2048), arena))) return rc;
         uint8_t* hs = (uint8_t*)h->h_stage;
         uint8_t* d = slot_ptr<uint8_t>(h, S_BLOCK);
         orbq::MotionJobDev* hj = (orbq::MotionJobDev*)(hs + oJobs);
@@ -115,9 +87,7 @@ extern "C" int orbq_track_motion_model(orbm_t* h, orbw_pool_t* pool, const OrbqM
             memcpy(D.V, J.velocity, sizeof D.V); memcpy(D.T, J.last_Tcw, sizeof D.T);
             memcpy(D.K, J.K, sizeof D.K);
             memcpy(D.bounds, fs->bounds, sizeof D.bounds);
-            D.grid = fs->gd;
-            D.keys = fs->fs.keysUn + J.cur_slot * C; D.nKeys = fs->fs.n + J.cur_slot;
-            D.cellStart = fs->fs.cellStart + (int64_t)J.cur_slot * (fs->ncell + 1); D.trec = fs->fs.rec + J.cur_slot * C; D.tdesc = fs->fs.desc + J.cur_slot * C * 32;
+            D.cur = orbt::train_side(fs->fs, J.cur_slot, fs->gd);
             D.lastKeys = fs->fs.keysUn + J.last_slot * C; D.nLast = fs->fs.n + J.last_slot;
             D.lastAng = fs->fs.ang + J.last_slot * C; D.lastDesc = fs->fs.desc + J.last_slot * C * 32;
             D.ids = (const int32_t*)(d + oIdsIn) + q0;
@@ -127,11 +97,7 @@ extern "C" int orbq_track_motion_model(orbm_t* h, orbw_pool_t* pool, const OrbqM
             f0 += (size_t)J.n; q0 += (size_t)J.nq; c0 += (size_t)C;
         }
         orbq::MotionArgs a{};
-        a.q.o.pw = (float4*)(d + oPw); a.q.o.uv = (float2*)(d + oUv); a.q.o.outlier = d + oFlags;
-        for (int lv = 0; lv < ORBX_MAX_LEVELS; lv++) a.q.o.invSigma2[lv] = lv < nlevels ? inv_level_sigma2[lv] : 0.f;
-        a.q.o.nlevels = nlevels;
-        a.q.pool = pool->dev;
-        a.q.merged = (int32_t*)(d + oMerged); a.q.idsOut = (int32_t*)(d + oIds); a.q.outlierOut = d + oOutl;
+        orbq_fill_solver(a.q, pool, d, oPw, oUv, oFlags, oMerged, oIds, oOutl, inv_level_sigma2, nlevels);
         a.jobs = (const orbq::MotionJobDev*)(d + oJobs);
         a.out = (OrbqMotionResult*)(d + oOut);
         a.state = (int32_t*)(d + oState); a.need = (int32_t*)(d + oNeed); a.assignOut = (int32_t*)(d + oAsgOut);
@@ -157,35 +123,16 @@ extern "C" int orbq_track_motion_model(orbm_t* h, orbw_pool_t* pool, const OrbqM
             }
             hipLaunchKernelGGL(orbq::k_motion_stage, dim3((unsigned)n_jobs), dim3(orbq::kLanes), 0, s, a, n_jobs, (int)orbq::MM_MIDDLE + pass);
         }
-        // (an error from here on: the kernels in flight read the pool, so the stream is drained before the mutex is let go)
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(hs, d + oStatus, downBytes, hipMemcpyDeviceToHost, s);
-        const int rcMark = orbw_mark_reader(pool, s);
-        const hipError_t eSync = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = eSync;
-        if (e != hipSuccess) return fail(ORBX_E_HIP, "orbq_track_motion_model's chain failed: %s", hipGetErrorString(e));
-        if (rcMark) return rcMark;
-        const size_t hOutl = oOutl - oStatus, hIds = oIds - oStatus, hAsg = oAsgOut - oStatus, hHead = oOut - oStatus;
-        const OrbqMotionResult* hr = (const OrbqMotionResult*)(hs + hHead);
-        const int32_t* need = (const int32_t*)(hs + hHead + (oNeed - oOut));
-        int maxNeed = 0;
-        for (int j = 0; j < n_jobs; j++) {
-            if (hr[j].track.opt.rounds < 0)
-                return fail(ORBX_E_INVALID, "job %d: an edge's octave lies outside [0, %d), or a feature at or above the slot's device count holds a point", j, nlevels);
-            maxNeed = std::max(maxNeed, std::max(need[2 * j], need[2 * j + 1]));
-        }
-        if (maxNeed > 0) {
-            // nothing but the call's own scratch has been written: the arena grows to the largest need and the WHOLE call runs again
-            if (attempt == 2) return fail(ORBX_E_CAPACITY, "candidate arena overflow: %d entries a job asked for in the third run", maxNeed);
-            if (maxNeed > kRelocArenaMax) return fail(ORBX_E_CAPACITY, "candidate arena overflow: %d entries a job", maxNeed);
-            h->motionArena = maxNeed;
-            continue;
-        }
-        memcpy(out, hr, nj * sizeof(OrbqMotionResult));
+        const size_t hOutl = oOutl - oStatus, hIds = oIds - oStatus, hAsg = oAsgOut - oStatus;
+        const uint8_t* head = hs + (oOut - oStatus);   // (the zero-cleared head as it came down: results | state | need)
+        if ((rc = orbq_drain("orbq_track_motion_model", pool, s, hs, d + oStatus, downBytes, head, sizeof(OrbqMotionResult), n_jobs, nlevels, ""))) return rc;
+        bool again;
+        if ((rc = orbq_arena_grow(h->motionArena, attempt, (const int32_t*)(head + (oNeed - oOut)), n_jobs, again))) return rc;
+        if (again) continue;
+        orbq_hand_back(jobs, n_jobs, out, head, sizeof(OrbqMotionResult), hs + hIds, hs + hOutl, ids_out, outlier_out);
         f0 = 0; c0 = 0;
-        for (int j = 0; j < n_jobs; j++) {
+        for (int j = 0; j < n_jobs; j++) {   // the tables asked for
             const size_t n = (size_t)jobs[j].n, nq = (size_t)jobs[j].nq;
-            if (n) { memcpy(ids_out[j], hs + hIds + f0 * 4, n * 4); memcpy(outlier_out[j], hs + hOutl + f0, n); }
             if (n && assign_out && assign_out[j]) memcpy(assign_out[j], hs + hAsg + f0 * 4, n * 4);
             if (nq && status_out && status_out[j]) memcpy(status_out[j], hs + 2 * c0, 2 * nq);
             f0 += n; c0 += (size_t)jobs[j].fs->cap;

@@ -25,10 +25,7 @@ struct MotionJobDev {
     float V[16], T[16];         // mVelocity, mLastFrame.mTcw
     float K[4];
     float bounds[4];            // mnMinX, mnMaxX, mnMinY, mnMaxY
-    orbm::GridDev grid;
-    const orbm::KeyDev* keys;   // the current slot's mvKeysUn
-    const int32_t* nKeys;       // ... and its device count
-    const int32_t* cellStart; const uint4* trec; const uint8_t* tdesc;   // ... its grid and descriptors: the search's train side
+    orbt::TrainSide cur;        // the current slot: its mvKeysUn and device count (the merge reads them), the search's train side
     const orbm::KeyDev* lastKeys;   // the last slot's mvKeysUn: the octaves
     const int32_t* nLast;       // ... and its device count
     const float* lastAng; const uint8_t* lastDesc;   // ... its angles and descriptors: the search's query side
@@ -79,7 +76,7 @@ __global__ __launch_bounds__(kLanes) void k_motion_stage(MotionArgs r, int nJobs
     if (stage == MM_MIDDLE) {
         if (lane != 0) return;
         const int nm = r.nmatch[2 * j];
-        if (nm < 0) { r.need[2 * j] = -nm - 1; r.state[j] = MM_OVERFLOW; return; }   // the host grows the arena and runs the call again
+        if (nm < 0) { report_overflow(nm, &r.need[2 * j], &r.state[j], MM_OVERFLOW); return; }
         const int wide = nm < r.minMatches ? 1 : 0;   // :938 if(nmatches<20)
         out->n_search[0] = nm; out->n_search[1] = -1; out->wide = wide;
         return;
@@ -87,34 +84,25 @@ __global__ __launch_bounds__(kLanes) void k_motion_stage(MotionArgs r, int nJobs
     const int wide = out->wide;   // (written by the MIDDLE launch)
     const int nm = r.nmatch[2 * j + wide];
     if (nm < 0) {
-        if (lane == 0) { r.need[2 * j + 1] = -nm - 1; r.state[j] = MM_OVERFLOW; }
+        if (lane == 0) report_overflow(nm, &r.need[2 * j + 1], &r.state[j], MM_OVERFLOW);
         return;
     }
-    const int n = J.n, f0 = J.f0, nDev = *J.nKeys;
+    const int n = J.n, f0 = J.f0, nDev = *J.cur.n;
     const int32_t* assign = r.assign + (size_t)wide * r.sumCap + J.c0;   // the table that stands (-1 behind the slot's device count)
     for (int t = lane; t < n; t += kLanes) r.assignOut[f0 + t] = assign[t];
     // :944 if(nmatches<20) return false: wave-uniform
     const bool gate = nm < r.minMatches;
     bool bad = false;
     const SearchSource src = {assign, J.ids, nullptr, J.nq};
-    const int nEdges = merge_and_gather(a, src, J.keys, n, f0, nDev, lane, !gate, bad);
+    const int nEdges = merge_and_gather(a, src, J.cur.keys, n, f0, nDev, lane, !gate, bad);
     const bool anyBad = __any(bad);
     if (lane == 0) {
         if (wide) out->n_search[1] = nm;
         out->status = gate ? MM_TOO_FEW : MM_TRACKED;
     }
     __syncthreads();
-    if (gate) {
-        // the reference returns with the matches and the predicted pose in the frame: no round, the table's ids as they merged
-        if (lane == 0) {
-            for (int i = 0; i < 16; i++) out->track.opt.Tcw[i] = out->Tcw_pred[i];
-            out->track.opt.rounds = anyBad ? -1 : 0;
-            out->track.n_matches = nm; out->track.n_matches_map = 0;
-        }
-        if (anyBad) return;
-        for (int t = lane; t < n; t += kLanes) { a.idsOut[f0 + t] = a.merged[f0 + t]; a.outlierOut[f0 + t] = 0; }
-        return;
-    }
+    // (the reference returns with the matches and the predicted pose in the frame)
+    if (gate) { leave_unsolved(a, n, f0, lane, anyBad, out->Tcw_pred, nm, &out->track); return; }
     orbo::solve_frame(a.o, out->Tcw_pred, J.K, f0, nEdges, anyBad, &out->track.opt, sLm, lane);   // :948
     __syncthreads();
     if (anyBad) return;
@@ -132,14 +120,11 @@ __global__ __launch_bounds__(kMotionThreads) void k_motion_project(MotionArgs r,
     const int64_t c0 = J.c0;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         orbt::ProjPair P;
-        P.grid = J.grid;
-        P.tkeys = J.keys; P.cellStart = J.cellStart; P.trec = J.trec; P.tdesc = J.tdesc;
-        P.ntPtr = J.nKeys; P.nt = 0;
+        proj_train(P, J.cur);
+        proj_unused(P);
         P.quvr = r.quvr + 3 * c0; P.qlvl = r.qlvl + 2 * c0; P.qdesc = J.lastDesc; P.qang = J.lastAng;
         P.qvalid = r.qvalid + c0; P.qobs = r.qobs + c0;
-        P.qur = nullptr; P.turight = nullptr; P.qkeys = nullptr;
         P.nqPtr = nq > 0 ? J.nLast : nullptr; P.nq = nq;   // (a null count with nq = 0: no query at all)
-        P.th = 0.f; P.minX = 0.f; P.maxX = 0.f; P.minY = 0.f; P.maxY = 0.f;
         P.toccIn = r.tocc + c0; P.toccOut = r.toccOut + c0;
         P.assign = r.assign + (int64_t)pass * r.sumCap + c0; P.initAssign = 1;
         P.nmatch = r.nmatch + 2 * j + pass;
@@ -148,7 +133,6 @@ __global__ __launch_bounds__(kMotionThreads) void k_motion_project(MotionArgs r,
         P.cand = r.cand + (int64_t)j * r.candCap; P.candCap = r.candCap;
         P.qres = r.qres + c0; P.qscr = r.qscr + 3 * c0;
         P.tscr = r.tscr ? r.tscr + J.t0 : nullptr;
-        P.stats = nullptr; P.flag = nullptr; P.flagValue = 0;
         r.pairs[j] = P;
     }
     const int q = blockIdx.x * kMotionThreads + threadIdx.x;

@@ -5,6 +5,7 @@
 // its share of the arena: the arena grows to the largest need and the whole call runs again, at most twice.
 
 static_assert(sizeof(OrbqRelocJob) == 112 && sizeof(OrbqRelocResult) == 616, "orbslamm_reloc.h layouts");
+static_assert(offsetof(OrbqRelocResult, opt) == 0, "orbq_drain reads rounds from the OrboResult at a record's head");
 static_assert(sizeof(orbq::RelocJobDev) == 224, "the per-job upload size DESIGN.md section 8y states");
 static_assert(ORBQ_RELOC_REJECTED == orbq::RELOC_REJECTED && ORBQ_RELOC_FIRST == orbq::RELOC_FIRST && ORBQ_RELOC_WIDE_SHORT == orbq::RELOC_WIDE_SHORT &&
               ORBQ_RELOC_SECOND == orbq::RELOC_SECOND && ORBQ_RELOC_NARROW_SHORT == orbq::RELOC_NARROW_SHORT && ORBQ_RELOC_THIRD == orbq::RELOC_THIRD &&
@@ -13,55 +14,31 @@ static_assert(ORBQ_RELOC_ST_NOT_RUN == orbq::RST_NOT_RUN && ORBQ_RELOC_ST_NO_POI
               ORBQ_RELOC_ST_FOUND == orbq::RST_FOUND && ORBQ_RELOC_ST_OUT_OF_IMAGE == orbq::RST_OUT_OF_IMAGE && ORBQ_RELOC_ST_DISTANCE == orbq::RST_DISTANCE &&
               ORBQ_RELOC_ST_LEVEL_RANGE == orbq::RST_LEVEL_RANGE && ORBQ_RELOC_ST_IN_VIEW == orbq::RST_IN_VIEW, "orbq projection status codes");
 
-constexpr int kRelocArenaMax = 1 << 24;   // entries a job: what orbq_debug_reloc_arena takes at the most
+extern "C" int orbq_debug_reloc_arena(orbm_t* h, int entries_per_job, int* last_runs) { return orbq_debug_arena(h, &orbm_handle::relocArena, entries_per_job, last_runs); }
 
-extern "C" int orbq_debug_reloc_arena(orbm_t* h, int entries_per_job, int* last_runs)
-{
-    if (entries_per_job < -1 || entries_per_job > kRelocArenaMax) return fail(ORBX_E_INVALID, "%d entries a job outside [-1, %d]", entries_per_job, kRelocArenaMax);
-    int rc = orbm_check(h);
-    if (rc) return rc;
-    if (entries_per_job >= 0) h->relocArena = entries_per_job;
-    if (last_runs) *last_runs = h->relocRuns;
-    return ORBX_OK;
-}
-
-// what needs neither a handle nor a GPU.  Zero jobs are settled by the caller before this
+// this entry's own argument checks, behind the shared ones (which have seen nlevels in range and the three level tables there)
 static int orbq_reloc_check_args(const void* h, const void* pool, const void* store, const OrbqRelocJob* jobs, int n_jobs, int check_ori,
-                                 const float* inv_level_sigma2, const float* scale_factors, const float* level_breaks, int nlevels,
-                                 const OrbqRelocResult* out, int32_t* const* ids_out, uint8_t* const* outlier_out)
+                                 const float* level_breaks, int nlevels)
 {
-    if (n_jobs < 0) return fail(ORBX_E_INVALID, "negative job count");
-    if (n_jobs > ORBO_MAX_FRAMES) return fail(ORBX_E_UNSUPPORTED, "%d jobs: above %d", n_jobs, ORBO_MAX_FRAMES);
-    if (!jobs || !out || !ids_out || !outlier_out) return fail(ORBX_E_INVALID, "null argument");
     if (check_ori != 0 && check_ori != 1) return fail(ORBX_E_INVALID, "check_ori is 0 or 1");
-    if (!inv_level_sigma2 || !scale_factors || !level_breaks || nlevels < 1 || nlevels > ORBX_MAX_LEVELS)
-        return fail(ORBX_E_INVALID, "nlevels %d outside [1, %d] or no level table", nlevels, ORBX_MAX_LEVELS);
     for (int l = 0; l < nlevels; l++)
         if (!(level_breaks[l] < level_breaks[l + 1])) return fail(ORBX_E_INVALID, "the break table does not ascend strictly at %d", l);
-    int64_t total = 0;
     for (int j = 0; j < n_jobs; j++) {
         const OrbqRelocJob& J = jobs[j];
-        if (!J.fs) return fail(ORBX_E_INVALID, "job %d: null frame set", j);
-        if (J.n < 0) return fail(ORBX_E_INVALID, "job %d: negative feature count", j);
-        if (J.n > ORBO_MAX_EDGES) return fail(ORBX_E_UNSUPPORTED, "job %d: %d features: above %d", j, J.n, ORBO_MAX_EDGES);
         if (J.kf_slot < 0 || J.slot < 0 || J.kf < 0) return fail(ORBX_E_INVALID, "job %d: negative slot", j);
-        if (J.n && (!J.ids || !ids_out[j] || !outlier_out[j])) return fail(ORBX_E_INVALID, "job %d: null array", j);
-        total += J.n;
-        if (total > ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "more than %d features in one call (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
+        if (J.n && !J.ids) return fail(ORBX_E_INVALID, "job %d: null array", j);
     }
     if (!h || !pool || !store) return fail(ORBX_E_INVALID, "null handle, pool or store");
     return ORBX_OK;
 }
-
-static inline int reloc_pow2ceil(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 
 extern "C" int orbq_relocalize(orbm_t* h, orbw_pool_t* pool, orbu_store_t* store, const OrbqRelocJob* jobs, int n_jobs, int check_ori,
                                const float* inv_level_sigma2, const float* scale_factors, const float* level_breaks, int nlevels,
                                OrbqRelocResult* out, int32_t* const* ids_out, uint8_t* const* outlier_out, uint8_t* const* status_out)
 {
     if (n_jobs == 0) return ORBX_OK;   // nothing to do: no argument is read, no handle needed
-    int rc = orbq_reloc_check_args(h, pool, store, jobs, n_jobs, check_ori, inv_level_sigma2, scale_factors, level_breaks, nlevels, out, ids_out, outlier_out);
-    if (rc) return rc;
+    int rc = orbq_check_shared(jobs, n_jobs, out, ids_out, outlier_out, inv_level_sigma2 && scale_factors && level_breaks, nlevels, "no level table", "null array");
+    if (rc || (rc = orbq_reloc_check_args(h, pool, store, jobs, n_jobs, check_ori, level_breaks, nlevels))) return rc;
     if ((rc = orbm_check(h)) || (rc = orbw_pool_check(pool)) || (rc = orbu_store_check(store))) return rc;
     if (pool->h->device != h->device) return fail(ORBX_E_INVALID, "the pool and the handle must share the device");
     if (store->pool != pool) return fail(ORBX_E_INVALID, "the store stands beside another pool");
@@ -70,26 +47,18 @@ extern "C" int orbq_relocalize(orbm_t* h, orbw_pool_t* pool, orbu_store_t* store
     int maxCap = 0, maxCell = 0;
     for (int j = 0; j < n_jobs; j++) {
         const OrbqRelocJob& J = jobs[j];
-        if ((rc = frameset_check(J.fs))) return rc;
-        if (J.fs->owner != h) return fail(ORBX_E_INVALID, "job %d: the frame set belongs to another handle", j);
-        if (J.slot >= J.fs->slots || J.kf_slot >= J.fs->slots) return fail(ORBX_E_INVALID, "job %d: slot %d or %d outside the frame set", j, J.kf_slot, J.slot);
-        if (J.n > J.fs->cap) return fail(ORBX_E_INVALID, "job %d: %d features for a frame of at most %d", j, J.n, J.fs->cap);
+        if ((rc = orbq_check_frameset(h, J.fs, j, J.kf_slot, J.slot, J.n, /* no second count */ -1, sumCap))) return rc;
         if (store->stride > J.fs->cap) return fail(ORBX_E_INVALID, "job %d: the store's stride %d is above the frame set's cap %d", j, store->stride, J.fs->cap);
-        sumCap += (size_t)J.fs->cap;
-        if (sumCap > (size_t)ORBO_MAX_CALL_EDGES) return fail(ORBX_E_UNSUPPORTED, "the jobs' frame sets hold more than %d features together (reached at job %d)", ORBO_MAX_CALL_EDGES, j);
         if ((rc = orbu_check_slot(store, "kf of job", j, J.kf, false))) return rc;   // (kfcap never changes; the set byte: under the mutex, below)
-        // (a set that builds on a stream of its own: the slots' builds may still run there)
-        if (fs_stream(J.fs) != h->stream) HIPCHK(hipStreamSynchronize(fs_stream(J.fs)));
         total += (size_t)J.n;
-        sumTab += 2 * (size_t)reloc_pow2ceil(std::max(J.n, 1));
+        sumTab += 2 * (size_t)pow2ceil(std::max(J.n, 1));
         maxCap = std::max(maxCap, J.fs->cap); maxCell = std::max(maxCell, J.fs->ncell);
     }
     ProjPlan pl{};
     if ((rc = proj_lds_plan(maxCap, store->stride, maxCell, pl))) return rc;
     orbt::ProjCommon& c = pl.c;
     c.mode = 5; c.nnratio = 0.f; c.checkOri = check_ori; c.thDist = 100;
-    c.scale = nullptr; c.nlevels = 1; c.interleave = 0;
-    if (!c.big) c.lanes = cand_lanes(n_jobs);
+    proj_plan_queries(c, n_jobs);
     Packer pk;
     const size_t oJobs = pk.take(nj * sizeof(orbq::RelocJobDev)), oIdsIn = pk.take(total * 4), upBytes = pk.off;
     // cleared to -1 / 0xff in one piece: the sFound tables | the outlier bytes (ORBQ_RELOC_KEEP)
@@ -114,9 +83,8 @@ extern "C" int orbq_relocalize(orbm_t* h, orbw_pool_t* pool, orbu_store_t* store
     }
     hipStream_t s = h->stream;
     for (int attempt = 0;; attempt++) {
-        h->relocRuns = attempt + 1;
-        const size_t arena = h->relocArena > 0 ? (size_t)h->relocArena : std::max<size_t>(8 * stride, 2048);
-        if ((rc = orbm_reserve(h, S_RELOC_ARENA, nj * arena * sizeof(uint2)))) return rc;
+        size_t arena;
+        if ((rc = orbq_arena_reserve(h, h->relocArena, S_RELOC_ARENA, attempt, nj, std::max<size_t>(8 * stride, 2048), arena))) return rc;
         uint8_t* hs = (uint8_t*)h->h_stage;
         uint8_t* d = slot_ptr<uint8_t>(h, S_BLOCK);
         orbq::RelocJobDev* hj = (orbq::RelocJobDev*)(hs + oJobs);
@@ -130,25 +98,19 @@ extern "C" int orbq_relocalize(orbm_t* h, orbw_pool_t* pool, orbu_store_t* store
             memcpy(D.Tcw, J.frame.Tcw, sizeof D.Tcw);
             memcpy(D.K, J.frame.K, sizeof D.K);
             memcpy(D.bounds, fs->bounds, sizeof D.bounds);
-            D.grid = fs->gd;
-            D.keys = fs->fs.keysUn + J.slot * C; D.nKeys = fs->fs.n + J.slot;
-            D.cellStart = fs->fs.cellStart + (int64_t)J.slot * (fs->ncell + 1); D.trec = fs->fs.rec + J.slot * C; D.tdesc = fs->fs.desc + J.slot * C * 32;
+            D.cur = orbt::train_side(fs->fs, J.slot, fs->gd);
             D.kfAng = fs->fs.ang + J.kf_slot * C; D.nKf = fs->fs.n + J.kf_slot;
             D.entries = store->dev.entries + (size_t)J.kf * store->pitch;
             D.ids = (const int32_t*)(d + oIdsIn) + f0;
             D.n = J.n; D.f0 = (int32_t)f0; D.cap = fs->cap; D.c0 = (int32_t)c0;
-            const int tabWords = 2 * reloc_pow2ceil(std::max(J.n, 1));
+            const int tabWords = 2 * pow2ceil(std::max(J.n, 1));
             D.tab0 = (int32_t)tab0; D.tabMask = tabWords - 1;
             D.t0 = (int32_t)((size_t)j * c.tCap * 3);
             if (J.n) memcpy(hs + oIdsIn + f0 * 4, J.ids, (size_t)J.n * 4);
             f0 += (size_t)J.n; c0 += (size_t)C; tab0 += (size_t)tabWords;
         }
         orbq::RelocArgs a{};
-        a.q.o.pw = (float4*)(d + oPw); a.q.o.uv = (float2*)(d + oUv); a.q.o.outlier = d + oFlags;
-        for (int lv = 0; lv < ORBX_MAX_LEVELS; lv++) a.q.o.invSigma2[lv] = lv < nlevels ? inv_level_sigma2[lv] : 0.f;
-        a.q.o.nlevels = nlevels;
-        a.q.pool = pool->dev;
-        a.q.merged = (int32_t*)(d + oIds); a.q.idsOut = a.q.merged; a.q.outlierOut = d + oOutl;
+        orbq_fill_solver(a.q, pool, d, oPw, oUv, oFlags, oIds, oIds, oOutl, inv_level_sigma2, nlevels);   // (merged and idsOut: ONE array, the frame's point list)
         a.jobs = (const orbq::RelocJobDev*)(d + oJobs);
         a.out = (OrbqRelocResult*)(d + oOut);
         a.state = (int32_t*)(d + oState); a.need = (int32_t*)(d + oNeed); a.bad = (int32_t*)(d + oBad); a.table = (int32_t*)(d + oTab);
@@ -175,39 +137,17 @@ extern "C" int orbq_relocalize(orbm_t* h, orbw_pool_t* pool, orbu_store_t* store
             }
             hipLaunchKernelGGL(orbq::k_reloc_stage, dim3((unsigned)n_jobs), dim3(orbq::kLanes), 0, s, a, n_jobs, (int)orbq::RELOC_MIDDLE + search);
         }
-        // (an error from here on: the kernels in flight read the pool, so the stream is drained before the mutex is let go)
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(hs, d + oOutl, downBytes, hipMemcpyDeviceToHost, s);
-        const int rcMark = orbw_mark_reader(pool, s);
-        const hipError_t eSync = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = eSync;
-        if (e != hipSuccess) return fail(ORBX_E_HIP, "orbq_relocalize's chain failed: %s", hipGetErrorString(e));
-        if (rcMark) return rcMark;
-        const OrbqRelocResult* hr = (const OrbqRelocResult*)(hs + hHead);
-        const int32_t* need = (const int32_t*)(hs + hHead + (oNeed - oOut));
-        const int32_t* bad = (const int32_t*)(hs + hHead + (oBad - oOut));
-        int maxNeed = 0;
-        for (int j = 0; j < n_jobs; j++) {
-            if (hr[j].opt[0].rounds < 0)
-                return fail(ORBX_E_INVALID, "job %d: an edge's octave lies outside [0, %d), or a feature at or above the slot's device count holds a point", j, nlevels);
+        const uint8_t* head = hs + hHead;   // (the zero-cleared head as it came down: results | status | state | need | bad)
+        if ((rc = orbq_drain("orbq_relocalize", pool, s, hs, d + oOutl, downBytes, head, sizeof(OrbqRelocResult), n_jobs, nlevels, ""))) return rc;
+        const int32_t* bad = (const int32_t*)(head + (oBad - oOut));
+        for (int j = 0; j < n_jobs; j++)
             if (bad[j]) return fail(ORBX_E_INVALID, "job %d: a row entry at or above the keyframe slot's device count holds a point", j);
-            maxNeed = std::max(maxNeed, std::max(need[2 * j], need[2 * j + 1]));
-        }
-        if (maxNeed > 0) {
-            // nothing but the call's own scratch has been written: the arena grows to the largest need and the WHOLE call runs again
-            if (attempt == 2) return fail(ORBX_E_CAPACITY, "candidate arena overflow: %d entries a job asked for in the third run", maxNeed);
-            if (maxNeed > kRelocArenaMax) return fail(ORBX_E_CAPACITY, "candidate arena overflow: %d entries a job", maxNeed);
-            h->relocArena = maxNeed;
-            continue;
-        }
-        memcpy(out, hr, nj * sizeof(OrbqRelocResult));
-        f0 = 0;
-        for (int j = 0; j < n_jobs; j++) {
-            const size_t n = (size_t)jobs[j].n;
-            if (n) { memcpy(ids_out[j], hs + hIds + f0 * 4, n * 4); memcpy(outlier_out[j], hs + hOutl + f0, n); }
-            if (status_out && status_out[j]) memcpy(status_out[j], hs + hHead + (oStatus - oOut) + (size_t)j * 2 * stride, 2 * stride);
-            f0 += n;
-        }
+        bool again;
+        if ((rc = orbq_arena_grow(h->relocArena, attempt, (const int32_t*)(head + (oNeed - oOut)), n_jobs, again))) return rc;
+        if (again) continue;
+        orbq_hand_back(jobs, n_jobs, out, head, sizeof(OrbqRelocResult), hs + hIds, hs + hOutl, ids_out, outlier_out);
+        for (int j = 0; j < n_jobs; j++)
+            if (status_out && status_out[j]) memcpy(status_out[j], head + (oStatus - oOut) + (size_t)j * 2 * stride, 2 * stride);
         return ORBX_OK;
     }
 }

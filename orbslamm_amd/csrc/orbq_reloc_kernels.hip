@@ -30,10 +30,7 @@ struct RelocJobDev {
     float Tcw[16];
     float K[4];
     float bounds[4];            // mnMinX, mnMaxX, mnMinY, mnMaxY
-    orbm::GridDev grid;
-    const orbm::KeyDev* keys;   // the current slot's mvKeysUn
-    const int32_t* nKeys;       // ... and its device count
-    const int32_t* cellStart; const uint4* trec; const uint8_t* tdesc;   // ... its grid and descriptors: the search's train side
+    orbt::TrainSide cur;        // the current slot: its mvKeysUn and device count (the merge reads them), the search's train side
     const float* kfAng;         // the keyframe slot's angles
     const int32_t* nKf;         // ... and its device count
     const int32_t* entries;     // the keyframe's row of the store
@@ -123,7 +120,7 @@ __global__ __launch_bounds__(kLanes) void k_reloc_stage(RelocArgs r, int nJobs, 
     if (j >= nJobs) return;
     const RelocJobDev& J = r.jobs[j];
     const Args& a = r.q;
-    const int n = J.n, f0 = J.f0, nDev = *J.nKeys, nt = min(nDev, J.cap);
+    const int n = J.n, f0 = J.f0, nDev = *J.cur.n, nt = min(nDev, J.cap);
     OrbqRelocResult* out = r.out + j;
     int32_t* list = a.merged + f0;
     int32_t* tab = r.table + J.tab0;
@@ -137,8 +134,8 @@ __global__ __launch_bounds__(kLanes) void k_reloc_stage(RelocArgs r, int nJobs, 
     } else {
         const int s = stage - 1;
         const int nm = r.nmatch[j];
-        if (nm < 0) {   // the arena's share was too small: the job stops, the host grows the arena and runs the call again
-            if (lane == 0) { r.need[2 * j + s] = -nm - 1; r.state[j] = RELOC_OVERFLOW; }
+        if (nm < 0) {
+            if (lane == 0) report_overflow(nm, &r.need[2 * j + s], &r.state[j], RELOC_OVERFLOW);
             return;
         }
         // ORBmatcher.cc:1559 CurrentFrame.mvpMapPoints[bestIdx2] = pMP, behind the pruning of :1587-1597
@@ -158,7 +155,7 @@ __global__ __launch_bounds__(kLanes) void k_reloc_stage(RelocArgs r, int nJobs, 
     // :1503 / :1519 / :1534 PoseOptimization(&mCurrentFrame), from the pose the frame holds
     bool bad = false;
     const ListSource src = {list};
-    const int nEdges = merge_and_gather(a, src, J.keys, n, f0, nDev, lane, true, bad);
+    const int nEdges = merge_and_gather(a, src, J.cur.keys, n, f0, nDev, lane, true, bad);
     const bool anyBad = __any(bad);
     __syncthreads();
     OrboResult* opt = &out->opt[stage];
@@ -199,14 +196,11 @@ __global__ __launch_bounds__(kRelocThreads) void k_reloc_project(RelocArgs r, in
     const int64_t q0 = (int64_t)j * r.stride;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         orbt::ProjPair P;
-        P.grid = J.grid;
-        P.tkeys = J.keys; P.cellStart = J.cellStart; P.trec = J.trec; P.tdesc = J.tdesc;
-        P.ntPtr = J.nKeys; P.nt = 0;
+        proj_train(P, J.cur);
+        proj_unused(P);
         P.quvr = r.quvr + 3 * q0; P.qlvl = r.qlvl + 2 * q0; P.qdesc = (const uint8_t*)(r.qdesc + 2 * q0); P.qang = J.kfAng;
         P.qvalid = r.qvalid + q0; P.qobs = nullptr;
-        P.qur = nullptr; P.turight = nullptr; P.qkeys = nullptr;
         P.nqPtr = nullptr; P.nq = live ? r.stride : 0;
-        P.th = 0.f; P.minX = 0.f; P.maxX = 0.f; P.minY = 0.f; P.maxY = 0.f;
         P.toccIn = r.tocc + J.c0; P.toccOut = r.toccOut + J.c0;
         P.assign = r.assign + J.c0; P.initAssign = 1;
         P.nmatch = r.nmatch + j;
@@ -215,7 +209,6 @@ __global__ __launch_bounds__(kRelocThreads) void k_reloc_project(RelocArgs r, in
         P.cand = r.cand + (int64_t)j * r.candCap; P.candCap = r.candCap;
         P.qres = r.qres + q0; P.qscr = r.qscr + 3 * q0;
         P.tscr = r.tscr ? r.tscr + J.t0 : nullptr;
-        P.stats = nullptr; P.flag = nullptr; P.flagValue = 0;
         r.pairs[j] = P;
     }
     const int q = blockIdx.x * kRelocThreads + threadIdx.x;

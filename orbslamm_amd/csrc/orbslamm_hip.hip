@@ -226,6 +226,7 @@ static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 #include "orbn_host.inc"   // the covisibility entries over the store: batched UpdateConnections and KeyFrameCulling counts
 #include "orbr_host.inc"   // the refresh entry and its blocks, orbw_debug_pool_get
 #include "orbe_host.inc"   // the loop correction's entry and its blocks
+#include "orbq_scaffold.inc"   // what the four orbq entries below share on the host: the checks, the solver block, the arena replay, the drained tail
 #include "orbq_host.inc"   // PoseOptimization behind the pool searches: TrackWithMotionModel's and TrackLocalMap's verdicts
 #include "orbq_reloc_host.inc"   // Relocalization behind PnPsolver::iterate: three solves and two keyframe projections per candidate
 #include "orbq_motion_host.inc"  // TrackWithMotionModel from the predicted pose to the counts: both searches, the gate, the solve and the loop in one call

@@ -96,6 +96,15 @@ static int proj_lds_plan(int nt, int nq, int ncell, ProjPlan& pl, int stagePerQu
     return ORBX_OK;
 }
 
+// ... and the rest of the plan for a search over explicit query arrays (a pool's projection, host-listed queries): no scale table,
+// and the queries come in no particular order
+static void proj_plan_queries(orbt::ProjCommon& c, int npairs)
+{
+    c.scale = nullptr; c.nlevels = 1;
+    c.interleave = 0;
+    if (!c.big) c.lanes = cand_lanes(npairs);
+}
+
 static int lds_attr(const void* fn, size_t bytes, size_t& have)
 {
     if (bytes > 64 * 1024 && bytes > have) {
@@ -261,8 +270,7 @@ static int proj_core(orbm_handle* h, const OrbmProjParams* pp, const float* q_uv
     if ((rc = proj_lds_plan(nt, nq, ncell, pl))) return rc;
     orbt::ProjCommon& c = pl.c;
     c.mode = pp->mode; c.nnratio = pp->nnratio; c.checkOri = pp->check_ori; c.thDist = pp->th_dist;
-    c.scale = nullptr; c.nlevels = 1;
-    if (!c.big) c.lanes = cand_lanes(1);
+    proj_plan_queries(c, 1);
 
     Packer pk;
     const size_t oPair = pk.take(sizeof(orbt::ProjPair));
@@ -784,9 +792,7 @@ static int track_queries(orbm_frameset_t* fs, int slot, int qslot, const OrbmPro
     orbt::ProjCommon& c = pl.c;
     c.mode = pp->mode; c.nnratio = pp->nnratio; c.thDist = pp->th_dist;
     c.checkOri = qslot >= 0 ? pp->check_ori : 0;   // (host-side queries carry no angles: modes 4 / 5 run without the rotation check then)
-    c.scale = nullptr; c.nlevels = 1;
-    c.interleave = 0;   // (a local map's MapPoints come in no particular order)
-    if (!c.big) c.lanes = cand_lanes(1);
+    proj_plan_queries(c, 1);   // (a local map's MapPoints come in no particular order)
     uint8_t* hs = fs->h_q + (size_t)set * fs->qBytes;
     uint8_t* ds = fs->d_q + (size_t)set * fs->qBytes;
     memcpy(hs + oUvr, q_uvr, (size_t)nq * 12); memcpy(hs + oLvl, q_lvl, (size_t)nq * 2);
@@ -796,15 +802,11 @@ static int track_queries(orbm_frameset_t* fs, int slot, int qslot, const OrbmPro
     if (t_occ) memcpy(hs + oOcc, t_occ, C);
     const SetTables t = set_tables(fs, set);
     orbt::ProjPair P{};
-    const int64_t cs = slot;
-    P.grid = fs->gd;
-    P.tkeys = fs->fs.keysUn + cs * C; P.cellStart = fs->fs.cellStart + cs * (fs->ncell + 1); P.trec = fs->fs.rec + cs * C; P.tdesc = fs->fs.desc + cs * C * 32;
-    P.ntPtr = fs->fs.n + cs; P.nt = 0;
+    orbt::proj_train(P, orbt::train_side(fs->fs, slot, fs->gd));
     P.quvr = (const float*)(ds + oUvr); P.qlvl = (const int8_t*)(ds + oLvl);
     P.qdesc = qslot < 0 ? ds + oQd : fs->fs.desc + (int64_t)qslot * C * 32;
     P.qang = qslot < 0 ? nullptr : fs->fs.ang + (int64_t)qslot * C;
     P.qvalid = qvalid ? ds + oQv : nullptr; P.qobs = q_obs_pos ? ds + oQo : nullptr;
-    P.qur = nullptr; P.turight = nullptr; P.qkeys = nullptr;
     P.nqPtr = qslot < 0 ? nullptr : fs->fs.n + qslot; P.nq = nq;   // (never more queries than the slot holds features)
     P.toccIn = t_occ ? ds + oOcc : nullptr; P.toccOut = fs->d_occ;
     P.assign = t.assign; P.initAssign = 1; P.nmatch = t.nmatch; P.stats = t.stats; P.flag = t.flag; P.flagValue = fs->seq + 1;

@@ -258,6 +258,33 @@ struct ProjPair {
                                                  // skips the wake-up of an event wait (the one-frame-per-call path)
 };
 
+// The train side of a pair when it is slot `slot` of a frame set: stated once, for the pairs made on the device (track_pair, and
+// orbq's projection kernels from the job record that carries a TrainSide up) and on the host (orbt_host.inc, orbw_host.inc)
+struct TrainSide { GridDev grid; const KeyDev* keys; const int32_t* n; const int32_t* cellStart; const uint4* rec; const uint8_t* desc; };
+__host__ __device__ __forceinline__ TrainSide train_side(const FrameSetDev& fs, int slot, const GridDev& grid)
+{
+    const int64_t C = fs.cap;
+    TrainSide t;
+    t.grid = grid;
+    t.keys = fs.keysUn + slot * C; t.cellStart = fs.cellStart + (int64_t)slot * (fs.ncell + 1); t.rec = fs.rec + slot * C;
+    t.desc = fs.desc + slot * C * 32; t.n = fs.n + slot;
+    return t;
+}
+__host__ __device__ __forceinline__ void proj_train(ProjPair& P, const TrainSide& t)
+{
+    P.grid = t.grid;
+    P.tkeys = t.keys; P.cellStart = t.cellStart; P.trec = t.rec; P.tdesc = t.desc;
+    P.ntPtr = t.n; P.nt = 0;
+}
+// ... and what a search over explicit query arrays (a pool's projection) leaves unused: the stereo gate, the frame-derived queries
+// with their window and bounds, the counters and the flag
+__host__ __device__ __forceinline__ void proj_unused(ProjPair& P)
+{
+    P.qur = nullptr; P.turight = nullptr; P.qkeys = nullptr;
+    P.th = 0.f; P.minX = 0.f; P.maxX = 0.f; P.minY = 0.f; P.maxY = 0.f;
+    P.stats = nullptr; P.flag = nullptr; P.flagValue = 0;
+}
+
 // every thread's result writes are performed system-wide, then ONE store publishes them (the host polls the word)
 __device__ __forceinline__ void proj_publish(const ProjPair& P)
 {
@@ -859,9 +886,7 @@ __device__ __forceinline__ ProjPair track_pair(const TrackArgs& a, int b)
     const int64_t C = a.fs.cap;
     const int cs = a.cur[b], ls = a.last[b];
     ProjPair P;
-    P.grid = a.grid;
-    P.tkeys = a.fs.keysUn + cs * C; P.cellStart = a.fs.cellStart + (int64_t)cs * (a.fs.ncell + 1); P.trec = a.fs.rec + cs * C;
-    P.tdesc = a.fs.desc + cs * C * 32; P.ntPtr = a.fs.n + cs; P.nt = 0;
+    proj_train(P, train_side(a.fs, cs, a.grid));
     P.quvr = nullptr; P.qlvl = nullptr; P.qdesc = a.fs.desc + ls * C * 32; P.qang = nullptr; P.qvalid = nullptr; P.qobs = nullptr;
     P.qur = nullptr; P.turight = nullptr;
     P.qkeys = a.fs.keysUn + ls * C; P.nqPtr = a.fs.n + ls; P.nq = 0;

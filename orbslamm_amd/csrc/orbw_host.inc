@@ -233,24 +233,18 @@ static int orbw_track(orbm_frameset_t* fs, int slot, int qslot, orbw_pool* pool,
     orbt::ProjCommon& c = pl.c;
     c.mode = pp->mode; c.nnratio = pp->nnratio; c.thDist = pp->th_dist;
     c.checkOri = frame ? pp->check_ori : 0;
-    c.scale = nullptr; c.nlevels = 1;
-    c.interleave = 0;
-    if (!c.big) c.lanes = cand_lanes(1);
+    proj_plan_queries(c, 1);
     uint8_t* hs = fs->h_q + (size_t)set * fs->qBytes;
     uint8_t* ds = fs->d_q + (size_t)set * fs->qBytes;
     if (nq && !devIds) memcpy(hs + oIds, ids, (size_t)nq * 4);
     if (t_occ) memcpy(hs + oOcc, t_occ, C);
     const SetTables t = set_tables(fs, set);
     orbt::ProjPair P{};
-    const int64_t cs = slot;
-    P.grid = fs->gd;
-    P.tkeys = fs->fs.keysUn + cs * C; P.cellStart = fs->fs.cellStart + cs * (fs->ncell + 1); P.trec = fs->fs.rec + cs * C; P.tdesc = fs->fs.desc + cs * C * 32;
-    P.ntPtr = fs->fs.n + cs; P.nt = 0;
+    orbt::proj_train(P, orbt::train_side(fs->fs, slot, fs->gd));
     P.quvr = (const float*)(ds + oUvr); P.qlvl = (const int8_t*)(ds + oLvl);
     P.qdesc = frame ? fs->fs.desc + (int64_t)qslot * C * 32 : ds + oQd;
     P.qang = frame ? fs->fs.ang + (int64_t)qslot * C : nullptr;
     P.qvalid = ds + oQv; P.qobs = ds + oQo;
-    P.qur = nullptr; P.turight = nullptr; P.qkeys = nullptr;
     P.nqPtr = frame ? fs->fs.n + qslot : nullptr; P.nq = nq;
     P.toccIn = t_occ ? ds + oOcc : nullptr; P.toccOut = fs->d_occ;
     P.assign = t.assign; P.initAssign = 1; P.nmatch = t.nmatch; P.stats = t.stats; P.flag = t.flag; P.flagValue = fs->seq + 1;
