@@ -85,7 +85,9 @@ enum OrbmSlot {
     S_TRI_K1, S_TRI_D1, S_TRI_K2, S_TRI_D2, S_TRI_ST1, S_TRI_I1, S_TRI_ST2, S_TRI_I2, /* orbm_search_for_triangulation | tri_core */
     S_TRI_S1, S_TRI_U1, S_TRI_S2, S_TRI_U2, S_TRI_PA, S_TRI_PB, S_TRI_M12, S_TRI_BIN, S_TRI_NMATCH,
     S_UND_IN, S_UND_OUT, S_RGBD_KEYS, S_RGBD_KEYSUN, S_RGBD_DEPTH, S_RGBD_OUT, S_DIS_DESC, S_DIS_START, S_DIS_BEST,   // orbm_undistort_keypoints, _compute_stereo_from_rgbd, _distinctive_descriptors
-    S_BLOCK,                                                // THE ONE SHARED NAME: the packed block of orbl_core, orbl_fuse_core, orbc_core, orbo_core, orbw_project_sync, orby_compute_sim3, orbq_track_pose, orbq_track_reference, orbq_relocalize, orbq_track_motion_model and orbb_core, which never nest
+    S_BLOCK,                                                // THE ONE SHARED NAME: the packed block of orbl_core, orbl_fuse_core, orbc_core, orbo_core, orbz_optimize_sim3, orbw_project_sync, orby_compute_sim3, orbq_track_pose, orbq_track_reference, orbq_relocalize, orbq_track_motion_model and orbb_core, which never nest
+    // (each packs its whole call into it -- uploads, work arrays, results, flags -- at offsets that follow from the call's sizes, and stages through h_stage: a
+    // call lands on whatever a larger call of another family left there, so none may read a word of it before writing it.  tests/test_gpu_one_handle.py)
     S_LF_PAIR, S_LF_TILES, S_LF_HITS, S_LF_STATUS,          // orbc_core besides S_BLOCK
     S_RELOC_ARENA,                                          // orbq_relocalize besides S_BLOCK: the searches' candidate arena, a share a job
     S_MOTION_ARENA,                                         // orbq_track_motion_model besides S_BLOCK: the same
@@ -95,6 +97,10 @@ enum OrbmSlot {
     T_FS, T_PREP, T_STATS,
     ORBM_SLOT_COUNT
 };
+// What else of a handle lives ACROSS calls, besides T_FS / T_PREP / T_STATS (every other block is a call's own from its first write on): prep and
+// callSeq (a prepared train side is good for the very next entry on the handle, whatever that entry is), stageSeq and the flag word behind h_stage
+// (stage_down_wait counts on through a regrown block, whose word grow_pinned zeroes), relocArena / motionArena (a job's share of S_RELOC_ARENA /
+// S_MOTION_ARENA: set by orbq_debug_*_arena, grown by an overflow and kept), lastRounds / lastCands, ldsAttr, the frame blocks and the counters.
 struct FrameBlock { void* p; size_t bytes; };
 struct orbm_handle {
     int device = -1;

@@ -380,3 +380,36 @@ def points_from_keys(rng, view, keys, sf=SF, desc=None, jitter=1.0):
     fl = np.where(rng.random(n) < 0.9, FLAG_OBSERVED, 0) | np.where(rng.random(n) < 0.03, FLAG_BAD, 0)
     pts["flags"] = fl.astype(np.uint8)
     return pts
+
+
+# ------------------------------------------------------------------ the device side: what tests/test_gpu_localmap.py and
+# tests/one_handle_cases.py share
+NF = 500
+D0 = [0, 0, 0, 0, 0]
+
+
+class Rig:
+    """three 640 x 480 frames of about 500 features resident in a frame set of four slots, their host copies, a matcher, the level
+    tables"""
+
+    def __init__(self):
+        from orbslamm_amd import ORBextractor, ORBmatcher, level_breaks, make_grid, synth
+        self.gex = ORBextractor(NF, 1.2, 8, 20, 7, max_width=W, max_height=H, max_batch=3, device=0)
+        self.sf = np.array(self.gex.GetScaleFactors(), np.float32)
+        assert np.array_equal(self.sf, SF)
+        self.m = ORBmatcher(0.8, True, device=0)
+        self.grid = make_grid(0.0, 0.0, float(W), float(H))
+        self.fs = self.new_frame_set()
+        self.gex.extract_batch_device(*self.gex.upload_frames(synth.make_frames(W, H, 3, stream=17)))
+        self.fs.build_from_extractor(0, self.gex)
+        self.host = [self.gex.download(f) for f in range(3)]
+        self.breaks = level_breaks(LOG_SF, NLEVELS)
+        self.breaks_b = level_breaks(LOG_SF_B, NLEVELS)
+
+    def new_frame_set(self):
+        return self.m.frame_set(4, self.gex.max_keypoints, K_A, D0, self.grid, list(BOUNDS), self.sf)
+
+
+def new_pool(rig, capacity):
+    from orbslamm_amd import MapPool
+    return MapPool(rig.m, capacity)

@@ -3,8 +3,6 @@ families -- result records, match_out, ids_out, removed, the status bytes and th
 path (the matcher's resident window_best run twice, host agreement and walk, optimize_sim3 on the host-made list); one pair of 2 000
 features; 8 jobs over two frame sets against the 8 single calls, and the same call twice; a pool update between two calls; the
 refusals that need handles; and the drop-in on mocks.  A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -12,82 +10,13 @@ import computesim3_cases as cc
 import dropin
 import localmap_cases as lc
 
+from computesim3_cases import CAP, Rig, call, job, new_world
+
 pytestmark = pytest.mark.gpu
-W, H = lc.W, lc.H
-D0 = [0, 0, 0, 0, 0]
-CAP = 320
 E_INVALID, E_UNSUPPORTED = -1, -5
-
-
-class Rig:
-    """a matcher, an extractor (device memory for frames made of given keys), two frame sets of four slots of CAP features"""
-
-    def __init__(self, oracle):
-        from orbslamm_amd import ORBextractor, ORBmatcher, make_grid
-        self.oracle = oracle
-        self.gex = ORBextractor(500, 1.2, 8, 20, 7, max_width=W, max_height=H, max_batch=1, device=0)
-        self.sf = np.array(self.gex.GetScaleFactors(), np.float32)
-        assert np.array_equal(self.sf, lc.SF)
-        self.m = ORBmatcher(0.7, True, device=0)
-        self.grid = make_grid(0.0, 0.0, float(W), float(H))
-        self.sig, self.breaks = cc.sigma2(), cc.breaks()
-        self.cfs = [self.new_set(), self.new_set()]
-        self._dev = []
-
-    def new_set(self, cap=CAP):
-        return self.m.frame_set(4, cap, lc.K_A, D0, self.grid, list(lc.BOUNDS), self.sf)
-
-    def _up(self, a):
-        from orbslamm_amd._lib import check, ptr
-        L, d = self.gex._L, C.c_void_p()
-        a = np.ascontiguousarray(a)
-        check(L.orbx_device_alloc(self.gex._h, C.c_size_t(max(a.nbytes, 4)), C.byref(d)))
-        if a.nbytes:
-            check(L.orbx_upload(self.gex._h, d, ptr(a), C.c_size_t(a.nbytes)))
-        self._dev.append(d)
-        return d.value
-
-    def put(self, fs, slot, keys, desc, resident=False):
-        dk, dd, dn = self._up(keys), self._up(desc), self._up(np.array([len(keys)], np.int32))
-        fs.build(slot, 1, dk, dd, dn, len(keys))
-        fs.sync()
-        return self.m.frame_from_device(dk, dd, len(keys), lc.K_A, D0, self.grid) if resident else None
-
-    def put_pair(self, fs, slot1, slot2, case, resident=False):
-        return self.put(fs, slot1, case["keys1"], case["desc1"], resident), self.put(fs, slot2, case["keys2"], case["desc2"], resident)
-
-
 @pytest.fixture(scope="module")
 def rig(gpu, oracle):
     return Rig(oracle)
-
-
-def new_world(rig, pool_records, rows, stride, kfcap=4):
-    """(pool, store): the records at ids 0 .., keyframe k of the store holding rows[k]"""
-    from orbslamm_amd import MapPool
-    from orbslamm_amd.map_pool import KeyFrameStore
-    pool = MapPool(rig.m, len(pool_records))
-    pool.set(np.arange(len(pool_records)), pool_records)
-    store = KeyFrameStore(pool, kfcap, stride, 0, 16)
-    k = len(rows)
-    store.set(np.arange(k), np.zeros(k, np.uint8), [np.asarray(r, np.int32) for r in rows], [[] for _ in range(k)], [-1] * k, [[] for _ in range(k)])
-    return pool, store
-
-
-def job(fs, slot1, slot2, kf1, kf2, case, **kw):
-    j = dict(fs=fs, slot1=slot1, slot2=slot2, kf1=kf1, kf2=kf2, n1=case["n1"], n2=case["n2"], R12=case["R12"], t12=case["t12"], s12=case["s12"],
-             S12=(case["q"], case["t"], case["s"]), R1w=case["R1w"], t1w=case["t1w"], R2w=case["R2w"], t2w=case["t2w"], K1=case["K"], K2=case["K"],
-             bounds1=case["bounds"], bounds2=case["bounds"], th=case["th"], th2=case["th2"], fix_scale=case["fix_scale"], m12_id=case["m12_id"],
-             m12_idx2=case["m12_idx2"])
-    j.update(kw)
-    return j
-
-
-def call(rig, pool, store, jobs, sig=None, nlevels=None, fill=None, m=None, debug=True):
-    from orbslamm_amd.compute_sim3 import compute_sim3_raw, pack_jobs
-    rec, keep = pack_jobs(jobs)
-    sig = rig.sig if sig is None else sig
-    return compute_sim3_raw((m or rig.m)._h, pool._h, store._h, rec, rig.sf, rig.sf, rig.breaks, rig.breaks, sig, sig, nlevels=nlevels, fill=fill, debug=debug)
 
 
 def assert_job_equals_ref(got, j, ref, tag):

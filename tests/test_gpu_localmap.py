@@ -10,41 +10,12 @@ import pytest
 import dropin
 import localmap_cases as lc
 
+from localmap_cases import Rig, new_pool
+
 pytestmark = pytest.mark.gpu
-W, H, NF = lc.W, lc.H, 500
-D0 = [0, 0, 0, 0, 0]
-
-
-class Rig:
-    """three 640 x 480 frames of about 500 features resident in a frame set of four slots, their host copies, a matcher, the level
-    tables"""
-
-    def __init__(self):
-        from orbslamm_amd import ORBextractor, ORBmatcher, level_breaks, make_grid, synth
-        self.gex = ORBextractor(NF, 1.2, 8, 20, 7, max_width=W, max_height=H, max_batch=3, device=0)
-        self.sf = np.array(self.gex.GetScaleFactors(), np.float32)
-        assert np.array_equal(self.sf, lc.SF)
-        self.m = ORBmatcher(0.8, True, device=0)
-        self.grid = make_grid(0.0, 0.0, float(W), float(H))
-        self.fs = self.new_frame_set()
-        self.gex.extract_batch_device(*self.gex.upload_frames(synth.make_frames(W, H, 3, stream=17)))
-        self.fs.build_from_extractor(0, self.gex)
-        self.host = [self.gex.download(f) for f in range(3)]
-        self.breaks = level_breaks(lc.LOG_SF, lc.NLEVELS)
-        self.breaks_b = level_breaks(lc.LOG_SF_B, lc.NLEVELS)
-
-    def new_frame_set(self):
-        return self.m.frame_set(4, self.gex.max_keypoints, lc.K_A, D0, self.grid, list(lc.BOUNDS), self.sf)
-
-
 @pytest.fixture(scope="module")
 def rig(gpu):
     return Rig()
-
-
-def new_pool(rig, capacity):
-    from orbslamm_amd import MapPool
-    return MapPool(rig.m, capacity)
 
 
 def assert_local_bits(got, ref, tag):

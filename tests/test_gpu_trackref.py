@@ -5,8 +5,6 @@ search) and one frame of 2 000 features on the 6-node vocabulary (its memory pat
 nnratio; solve and min_matches; 1, 2 and 9 jobs over two frame sets with keyframes and frames shared between jobs; the same call
 twice; the BoW ring left alone; a pool update between two calls; the refusals that need handles; and the drop-in on mocks.
 A fault, hang or abort met on the GPU is a finding to explain from the code, not to retry."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -15,84 +13,13 @@ import localmap_cases as lc
 import trackpose_cases as tc
 import trackref_cases as rc
 
+from trackref_cases import CAP, Rig, call, job, new_world
+
 pytestmark = pytest.mark.gpu
-W, H = lc.W, lc.H
-D0 = [0, 0, 0, 0, 0]
-CAP = 320
 E_INVALID = -1
-
-
-class Rig:
-    """a matcher, the 6-node vocabulary on both sides, an extractor (device memory for frames made of given keys), two frame sets of
-    four slots of CAP features"""
-
-    def __init__(self, oracle):
-        from orbslamm_amd import ORBextractor, ORBmatcher, ORBVocabulary, make_grid
-        self.oracle = oracle
-        self.gex = ORBextractor(500, 1.2, 8, 20, 7, max_width=W, max_height=H, max_batch=1, device=0)
-        self.sf = np.array(self.gex.GetScaleFactors(), np.float32)
-        self.m = ORBmatcher(0.7, True, device=0)
-        self.grid = make_grid(0.0, 0.0, float(W), float(H))
-        v = rc.vocabulary()
-        self.G = ORBVocabulary(rc.VOC_K, rc.VOC_L, 0, 0, v["parent"], v["is_leaf"], v["desc"], v["weight"], device=0)
-        self.O = rc.oracle_voc(oracle)
-        self.sig = tc.sigma2()
-        self.cfs = [self.new_set(), self.new_set()]
-        self._dev = []
-
-    def new_set(self, cap=CAP):
-        return self.m.frame_set(4, cap, lc.K_A, D0, self.grid, list(lc.BOUNDS), self.sf)
-
-    def _up(self, a):
-        from orbslamm_amd._lib import check, ptr
-        L, d = self.gex._L, C.c_void_p()
-        a = np.ascontiguousarray(a)
-        check(L.orbx_device_alloc(self.gex._h, C.c_size_t(max(a.nbytes, 4)), C.byref(d)))
-        if a.nbytes:
-            check(L.orbx_upload(self.gex._h, d, ptr(a), C.c_size_t(a.nbytes)))
-        self._dev.append(d)
-        return d.value
-
-    def put(self, fs, slot, keys, desc, resident=False):
-        dk, dd, dn = self._up(keys), self._up(desc), self._up(np.array([len(keys)], np.int32))
-        fs.build(slot, 1, dk, dd, dn, len(keys))
-        fs.sync()
-        return self.m.frame_from_device(dk, dd, len(keys), lc.K_A, D0, self.grid) if resident else None
-
-    def put_pair(self, fs, kf_slot, slot, case, resident=False):
-        """the case's keyframe and frame into two slots, their BoW computed"""
-        self.put(fs, kf_slot, case["kkeys"], case["kdesc"])
-        frame = self.put(fs, slot, case["keys"], case["desc"], resident)
-        for s in (kf_slot, slot):
-            fs.compute_bow(self.G, s, 1, rc.LEVELSUP)
-        return frame
-
-
 @pytest.fixture(scope="module")
 def rig(gpu, oracle):
     return Rig(oracle)
-
-
-def new_world(rig, pool_records, rows, stride, kfcap=4):
-    """(pool, store): the records at ids 0 .., keyframe k of the store holding rows[k]"""
-    from orbslamm_amd import MapPool
-    from orbslamm_amd.map_pool import KeyFrameStore
-    pool = MapPool(rig.m, len(pool_records))
-    pool.set(np.arange(len(pool_records)), pool_records)
-    store = KeyFrameStore(pool, kfcap, stride, 0, 16)
-    k = len(rows)
-    store.set(np.arange(k), np.zeros(k, np.uint8), [np.asarray(r, np.int32) for r in rows], [[] for _ in range(k)], [-1] * k, [[] for _ in range(k)])
-    return pool, store
-
-
-def job(fs, kf_slot, slot, kf, case, solve=1, n=None, Tcw=None):
-    return dict(fs=fs, kf_slot=kf_slot, slot=slot, kf=kf, n=case["n"] if n is None else n, solve=solve, Tcw=case["Tcw"] if Tcw is None else Tcw, K=case["K"])
-
-
-def call(rig, pool, store, jobs, nnratio=0.7, check_ori=True, min_matches=15, sig=None, nlevels=None, fill=None, want_match=True, m=None):
-    from orbslamm_amd.track_pose import pack_ref_jobs, track_reference_raw
-    return track_reference_raw((m or rig.m)._h, pool._h, store._h, pack_ref_jobs(jobs), nnratio, check_ori, min_matches, rig.sig if sig is None else sig,
-                               nlevels=nlevels, fill=fill, want_match=want_match)
 
 
 def assert_job_equals_ref(got, j, whole, tag):

@@ -224,3 +224,70 @@ def model_run(case, discard, assign="case", n=None):
     observed = np.zeros(n, bool)
     observed[feat] = (case["pool"]["flags"][merged[feat]] & FLAG_OBSERVED) != 0
     return dict(opt=out[0], ids_out=ids_out.astype(np.int32), outlier_out=outlier, n_matches=int(alive.sum()), n_matches_map=int((alive & observed).sum()))
+
+
+# ------------------------------------------------------------------ the device side: what tests/test_gpu_trackpose.py and
+# tests/one_handle_cases.py share
+W, H, NF = lc.W, lc.H, 500
+D0 = [0, 0, 0, 0, 0]
+CAP = 320                      # the custom frame sets' cap: five chunks of 64 features
+
+
+class Rig:
+    """a matcher; an extractor (device memory for custom frames, and three real 640 x 480 frames of about 500 features in the four
+    slots of `fs`); two frame sets of four slots of CAP features for frames made of given keys"""
+
+    def __init__(self):
+        from orbslamm_amd import ORBextractor, ORBmatcher, level_breaks, make_grid, synth
+        self.gex = ORBextractor(NF, 1.2, 8, 20, 7, max_width=W, max_height=H, max_batch=3, device=0)
+        self.sf = np.array(self.gex.GetScaleFactors(), np.float32)
+        self.m = ORBmatcher(0.8, True, device=0)
+        self.grid = make_grid(0.0, 0.0, float(W), float(H))
+        self.fs = self.m.frame_set(4, self.gex.max_keypoints, lc.K_A, D0, self.grid, list(lc.BOUNDS), self.sf)
+        self.gex.extract_batch_device(*self.gex.upload_frames(synth.make_frames(W, H, 3, stream=17)))
+        self.fs.build_from_extractor(0, self.gex)
+        self.host = [self.gex.download(f) for f in range(3)]
+        self.breaks = level_breaks(lc.LOG_SF, lc.NLEVELS)
+        self.sig = sigma2()
+        self.cfs = [self.new_set(), self.new_set()]
+        self._dev = []
+
+    def new_set(self, cap=CAP):
+        return self.m.frame_set(4, cap, lc.K_A, D0, self.grid, list(lc.BOUNDS), self.sf)
+
+    def _up(self, a):
+        L, d = self.gex._L, C.c_void_p()
+        a = np.ascontiguousarray(a)
+        from orbslamm_amd._lib import check, ptr
+        check(L.orbx_device_alloc(self.gex._h, C.c_size_t(max(a.nbytes, 4)), C.byref(d)))
+        if a.nbytes:
+            check(L.orbx_upload(self.gex._h, d, ptr(a), C.c_size_t(a.nbytes)))
+        self._dev.append(d)
+        return d.value
+
+    def put(self, fs, slot, keys, desc, resident=False):
+        """a frame of the given keys into `slot` (no distortion: mvKeysUn is keys); resident: also as an opaque frame for orbo_*"""
+        dk, dd, dn = self._up(keys), self._up(desc), self._up(np.array([len(keys)], np.int32))
+        fs.build(slot, 1, dk, dd, dn, len(keys))
+        fs.sync()
+        got, _ = fs.download(slot)
+        assert len(got) == len(keys) and all(got[f].tobytes() == keys[f].tobytes() for f in ("x", "y", "octave"))
+        return self.m.frame_from_device(dk, dd, len(keys), lc.K_A, D0, self.grid) if resident else None
+
+
+def new_pool(rig, records):
+    from orbslamm_amd import MapPool
+    pool = MapPool(rig.m, len(records))
+    pool.set(np.arange(len(records)), records)
+    return pool
+
+
+def job(fs, slot, case, back, discard, n=None, base="case", Tcw=None):
+    return dict(fs=fs, slot=slot, back=back, base_ids=case["base_ids"] if isinstance(base, str) else base, n=case["n"] if n is None else n, discard=discard,
+                Tcw=case["Tcw"] if Tcw is None else Tcw, K=case["K"])
+
+
+def call(rig, pool, jobs, sig=None, nlevels=None, fill=None):
+    from orbslamm_amd.track_pose import pack_jobs, track_pose_raw
+    rec, keep = pack_jobs(jobs)
+    return track_pose_raw(rig.m._h, pool._h, rec, rig.sig if sig is None else sig, nlevels=nlevels, fill=fill)
